@@ -12,7 +12,7 @@ OUT=$ROOT/gpurun_out/$TAG
 export TMPDIR=/tmp
 mkdir -p "$OUT"
 cd /tmp
-BENCH="python3 $ROOT/bench.py --solo --steps 1 --warmup 1 --no-cpu-baseline $*"
+BENCH="python3 $ROOT/bench.py --full --solo --steps 1 --warmup 1 --no-cpu-baseline $*"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/stats" -- $BENCH > "$OUT/stats.log" 2>&1 || { echo "stats pass failed"; tail -3 "$OUT/stats.log"; }
 i=0
 for CNT in "FETCH_SIZE" "WRITE_SIZE" \

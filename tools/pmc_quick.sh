@@ -11,7 +11,7 @@ cd /tmp
 i=0
 for CNT in "$@"; do
   i=$((i+1))
-  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $CNT --output-format csv -d "$OUT/pass$i" -- python3 "$ROOT/bench.py" --steps 1 --warmup 0 --no-cpu-baseline $ARGS > "$OUT/pass$i.log" 2>&1 || { echo "pass $i ($CNT) failed"; tail -3 "$OUT/pass$i.log"; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --pmc $CNT --output-format csv -d "$OUT/pass$i" -- python3 "$ROOT/bench.py" --full --steps 1 --warmup 0 --no-cpu-baseline $ARGS > "$OUT/pass$i.log" 2>&1 || { echo "pass $i ($CNT) failed"; tail -3 "$OUT/pass$i.log"; }
 done
 python3 "$ROOT/tools/pmc_summary.py" "$OUT" > "$ROOT/gpurun_out/$TAG.txt" 2>&1
 find "$OUT" -name "*kernel_trace.csv" -delete
