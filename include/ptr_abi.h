@@ -203,7 +203,18 @@ typedef struct PtrSettings {
      * clamp_specular_pdf returns 0 for a non-finite or non-positive pdf and the pdf itself while minSpecularPdf <= 0.  With
      * them go the next-event-estimation weights of the Metal kernel (:6532-6552, 6624-6645; Appendix A row 13): a light or
      * environment sample counts when the BSDF value is positive (not: when it has a density), its balance weight is clamped to
-     * [1e-4, 0.9999], and the weight is 1 where the BSDF reports no density. */
+     * [1e-4, 0.9999], and the weight is 1 where the BSDF reports no density.
+     * Bit 7 (PTR_METAL_ENV_LOD): environment lookups read a prefiltered mip level where the Metal kernel does
+     * (environment_color_lod, :1389-1407; environment_lod_from_roughness, :1334-1344: lod = clamp(r, 0, 1)^2 * maxMip): the
+     * background of a ray that escapes after a glossy, non-delta BSDF sample at the LOD of the sampled lobe's roughness (the path
+     * state of :5755-5756, 7249-7260; every other event, and a new sample, clears it: :5807-5828), and the radiance of an
+     * environment sample at the LOD of environment_lighting_roughness (metal / metallic-roughness: roughness, plastic: coat
+     * roughness, car paint: base roughness, else 1) when it is below 0.95 (:3834-3847, 6566-6581; pdf and MIS weights stay those
+     * of the level-0 tables).  Every other lookup (camera rays that miss, portals, specular NEE / MNEE) stays at level 0.  The
+     * chain is the one material textures get (2x2 box filter, odd sizes clamp the second tap, down to 1x1), built on the first
+     * render with the bit; the filter is the sampler of the Metal kernel's environment (:20-23): bilinear inside a level with
+     * texel centres at (i + 0.5) / W, linear between levels, and repeat addressing on both axes - where the level-0 lookup clamps
+     * v (the Embree rule). */
     uint32_t metalSemantics;
     uint32_t sssMode;   /* RenderSettings::SssMode: 0 off, 1 separable, 2 random walk; read only with PTR_METAL_SSS */
     uint32_t sssMaxSteps;   /* RenderSettings::sssMaxSteps (32): closest-hit queries per random walk, at least 1 */
@@ -216,7 +227,7 @@ typedef struct PtrSettings {
 } PtrSettings;
 
 enum { PTR_METAL_MEDIA = 1u, PTR_METAL_THIN = 2u, PTR_METAL_FACE_NORMAL = 4u, PTR_METAL_SPECULAR = 8u, PTR_METAL_SSS = 16u, PTR_METAL_PBR = 32u,
-       PTR_METAL_CLAMPS = 64u };
+       PTR_METAL_CLAMPS = 64u, PTR_METAL_ENV_LOD = 128u };
 
 typedef struct PtrRenderStats {
     double totalSeconds;                /* integrate phase only (reference: out.totalSeconds) */

@@ -20,6 +20,21 @@ int ptr_debug_eval_bsdf(const PtrMaterial* material, const PtrSettings* settings
 int ptr_debug_sample_bsdf(const PtrMaterial* material, const PtrSettings* settings, const float* in,
                           const uint32_t* front_face, const uint32_t* rng_states, uint64_t n, float* out,
                           uint32_t* out_states, char* err, size_t err_cap);
+/* The lobe bookkeeping of the Metal-semantics samplers (lobeType / lobeRoughness, shaders/pathtrace.metal:4784-4866, 5136-5700) on
+ * the inputs of ptr_debug_sample_bsdf: out n*3 floats {lobe (0 diffuse, 1 specular, 2 transmission), lobe roughness, isDelta};
+ * out_sample (n*8) and out_states as ptr_debug_sample_bsdf writes them (either may be NULL); env_roughness (may be NULL): the
+ * material's environment_lighting_roughness (:3834-3847). */
+int ptr_debug_sample_lobes(const PtrMaterial* material, const PtrSettings* settings, const float* in, const uint32_t* front_face,
+                           const uint32_t* rng_states, uint64_t n, float* out, float* out_sample, uint32_t* out_states, float* env_roughness,
+                           char* err, size_t err_cap);
+/* PTR_METAL_ENV_LOD lookups of the environment map of `scene` (its mip chain is built if no render has built it yet): in n*4 floats
+ * {direction xyz, roughness}; out n*4 floats {LOD of that roughness (environment_lod_from_roughness), radiance rgb of the prefiltered
+ * lookup with the settings' environment rotation and intensity}.  Non-zero when the scene has no environment map. */
+int ptr_debug_env_lookup(PtrDeviceScene* scene, const PtrSettings* settings, const float* in, uint64_t n, float* out, char* err, size_t err_cap);
+/* Host-side (no GPU): the environment mip chain PTR_METAL_ENV_LOD builds from a w x h RGBA map, levels 0.. back to back (RGBA floats);
+ * *levels_out = its level count.  out may be NULL (levels only); non-zero when cap_floats is too small. */
+int ptr_debug_env_mips(const float* rgba, uint32_t w, uint32_t h, float* out, uint64_t cap_floats, uint32_t* levels_out);
+
 /* xys: n*3 {x, y, sample}; out: n*6 floats {origin, direction}; out_states: rng state after ray generation */
 int ptr_debug_camera_rays(const PtrSettings* settings, const uint32_t* xys, uint64_t n, float* out,
                           uint32_t* out_states, char* err, size_t err_cap);

@@ -207,6 +207,16 @@ HIT_DTYPE = np.dtype(
 assert C.sizeof(PtrSphere) == 32 and C.sizeof(PtrRect) == 80 and C.sizeof(PtrMaterial) == 576
 assert C.sizeof(PtrHit) == HIT_DTYPE.itemsize == 40
 
+# PtrSettings.metalSemantics bits (include/ptr_abi.h PTR_METAL_*)
+PTR_METAL_MEDIA = 1
+PTR_METAL_THIN = 2
+PTR_METAL_FACE_NORMAL = 4
+PTR_METAL_SPECULAR = 8
+PTR_METAL_SSS = 16
+PTR_METAL_PBR = 32
+PTR_METAL_CLAMPS = 64
+PTR_METAL_ENV_LOD = 128    # prefiltered environment lookups (environment_color_lod of the Metal kernel)
+
 # Every symbol include/ptr_abi.h declares.
 ABI_SYMBOLS = (
     "ptr_device_count", "ptr_scene_upload", "ptr_scene_release", "ptr_scene_info", "ptr_render",
@@ -218,7 +228,8 @@ ABI_SYMBOLS = (
 # include/ptr_debug.h (test-only device-function probes)
 DEBUG_SYMBOLS = ("ptr_debug_eval_bsdf", "ptr_debug_sample_bsdf", "ptr_debug_camera_rays", "ptr_debug_env_distribution",
                  "ptr_debug_scene_geometry", "ptr_debug_render_signatures", "ptr_debug_render_multi_on", "ptr_debug_texture_sample",
-                 "ptr_debug_generate_tangents", "ptr_debug_surface_hits", "ptr_debug_shade_kernel_set", "ptr_debug_exact_division", "ptr_debug_walk_counts")
+                 "ptr_debug_generate_tangents", "ptr_debug_surface_hits", "ptr_debug_shade_kernel_set", "ptr_debug_exact_division", "ptr_debug_walk_counts",
+                 "ptr_debug_sample_lobes", "ptr_debug_env_lookup", "ptr_debug_env_mips")
 
 _lib: Optional[C.CDLL] = None
 
@@ -474,6 +485,18 @@ class DeviceScene:
         _check(load_library().ptr_debug_texture_sample(self._h, texture, _fptr(uv_lod), uv_lod.shape[0], _fptr(out), err, len(err)), err)
         return out
 
+    def env_lookup(self, settings: PtrSettings, dir_roughness: np.ndarray) -> np.ndarray:
+        """ptr_debug_env_lookup: the PTR_METAL_ENV_LOD lookup of the scene's environment map with the settings' rotation and intensity:
+        dir_roughness [n, 4] {direction, roughness} -> [n, 4] {LOD, rgb}."""
+        q = np.ascontiguousarray(dir_roughness, dtype=np.float32).reshape(-1, 4)
+        out = np.zeros((q.shape[0], 4), dtype=np.float32)
+        lib = load_library()
+        lib.ptr_debug_env_lookup.argtypes = [C.c_void_p, C.POINTER(PtrSettings), C.POINTER(C.c_float), C.c_uint64, C.POINTER(C.c_float),
+                                             C.c_char_p, C.c_size_t]
+        err = _err_buf()
+        _check(lib.ptr_debug_env_lookup(self._h, C.byref(settings), _fptr(q), q.shape[0], _fptr(out), err, len(err)), err)
+        return out
+
     def trace_rays(self, rays: np.ndarray, any_hit: bool = False) -> Tuple[np.ndarray, PtrRenderStats]:
         """rays: [n, 8] float32 {ox,oy,oz,tmin,dx,dy,dz,tmax}; returns a structured array of PtrHit."""
         lib = load_library()
@@ -610,6 +633,47 @@ def debug_sample_bsdf(material: PtrMaterial, settings: PtrSettings, inputs: np.n
                                                _uptr(states), inputs.shape[0], _fptr(out), _uptr(out_states), err,
                                                len(err)), err)
     return out, out_states
+
+
+def debug_sample_lobes(material: PtrMaterial, settings: PtrSettings, inputs: np.ndarray, front: np.ndarray, states: np.ndarray):
+    """ptr_debug_sample_lobes on the inputs of debug_sample_bsdf: ([n, 3] {lobe, lobe roughness, isDelta}, [n, 8] sample as
+    debug_sample_bsdf returns it, [n] rng states after sampling, the material's environment-lighting roughness)."""
+    inputs = np.ascontiguousarray(inputs, dtype=np.float32).reshape(-1, 9)
+    front = np.ascontiguousarray(front, dtype=np.uint32)
+    states = np.ascontiguousarray(states, dtype=np.uint32)
+    n = inputs.shape[0]
+    out = np.zeros((n, 3), dtype=np.float32)
+    sample = np.zeros((n, 8), dtype=np.float32)
+    out_states = np.zeros(n, dtype=np.uint32)
+    env_rough = C.c_float()
+    lib = load_library()
+    lib.ptr_debug_sample_lobes.argtypes = [C.POINTER(PtrMaterial), C.POINTER(PtrSettings), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
+                                           C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
+                                           C.POINTER(C.c_float), C.c_char_p, C.c_size_t]
+    err = _err_buf()
+    _check(lib.ptr_debug_sample_lobes(C.byref(material), C.byref(settings), _fptr(inputs), _uptr(front), _uptr(states), n, _fptr(out),
+                                      _fptr(sample), _uptr(out_states), C.byref(env_rough), err, len(err)), err)
+    return out, sample, out_states, float(env_rough.value)
+
+
+def debug_env_mips(rgba: np.ndarray):
+    """Host-side (no GPU): the environment mip chain PTR_METAL_ENV_LOD builds - a list of [h_l, w_l, 4] float32 levels, level 0 first."""
+    rgba = np.ascontiguousarray(rgba, dtype=np.float32)
+    h, w = rgba.shape[0], rgba.shape[1]
+    lib = load_library()
+    lib.ptr_debug_env_mips.argtypes = [C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_uint64, C.POINTER(C.c_uint32)]
+    levels = C.c_uint32(0)
+    if lib.ptr_debug_env_mips(_fptr(rgba), w, h, None, 0, C.byref(levels)) != 0:
+        raise PtrError("ptr_debug_env_mips failed")
+    sizes = [(max(h >> l, 1), max(w >> l, 1)) for l in range(levels.value)]
+    out = np.zeros(sum(a * b for a, b in sizes) * 4, dtype=np.float32)
+    if lib.ptr_debug_env_mips(_fptr(rgba), w, h, _fptr(out), out.size, C.byref(levels)) != 0:
+        raise PtrError("ptr_debug_env_mips failed")
+    chain, at = [], 0
+    for a, b in sizes:
+        chain.append(out[at:at + a * b * 4].reshape(a, b, 4))
+        at += a * b * 4
+    return chain
 
 
 def debug_camera_rays(settings: PtrSettings, xys: np.ndarray):

@@ -58,6 +58,8 @@ struct CliOptions {
 
 // PTR_METAL_MEDIA | PTR_METAL_THIN | PTR_METAL_FACE_NORMAL | PTR_METAL_SPECULAR | PTR_METAL_SSS | PTR_METAL_PBR | PTR_METAL_CLAMPS
 constexpr uint32_t kMetalSemanticsAll = 127u;
+// ... and PTR_METAL_ENV_LOD, the prefiltered environment lookups (--semantics=metal-envlod)
+constexpr uint32_t kMetalSemanticsEnvLod = kMetalSemanticsAll | 128u;
 
 void printUsage(const char* exe) {
     std::cout << "Usage: " << exe << " [options]\n\n"
@@ -78,10 +80,13 @@ void printUsage(const char* exe) {
               << "Backend selection:\n"
               << "  --backend=<hip|embree|metal>   hip / embree: Embree-parity integrator (default); metal: as --semantics=metal\n"
               << "  --enableEmbree[=0|1]           Same as --backend=embree (1) / --backend=metal (0)\n"
-              << "  --semantics=<embree|metal>     Integrator semantics: embree = parity with the reference's Embree backend\n"
+              << "  --semantics=<embree|metal|metal-envlod>\n"
+              << "                                 Integrator semantics: embree = parity with the reference's Embree backend\n"
               << "                                 (default); metal = plus the Metal kernel's absorbing media, thin-walled glass, ray-facing\n"
               << "                                 glass normals, rough-metal VNDF formulas, subsurface scattering (scene: renderer sss=...),\n"
-              << "                                 three-lobe PBR with transmission, the Metal kernel's clamp variants\n"
+              << "                                 three-lobe PBR with transmission, the Metal kernel's clamp variants; metal-envlod = metal\n"
+              << "                                 plus environment lookups at a mip level chosen by roughness after glossy bounces and\n"
+              << "                                 for environment samples of glossy materials\n"
               << "  --devices=<int>                GPUs of this node to spread the frame over (default 1, 0 = all visible)\n"
               << "  --assets=<dir>                 Directory for relative mesh/env paths\n\n"
               << "Tonemapping overrides (for LDR outputs):\n"
@@ -235,10 +240,12 @@ bool parseOptions(int argc, const char** argv, CliOptions& o, std::string& error
             if (!need("--semantics")) return false;
             if (value == "metal") {
                 o.metalSemantics = kMetalSemanticsAll;
+            } else if (value == "metal-envlod") {
+                o.metalSemantics = kMetalSemanticsEnvLod;
             } else if (value == "embree") {
                 o.metalSemantics = 0u;
             } else {
-                error = "Invalid value for --semantics (expected embree or metal)";
+                error = "Invalid value for --semantics (expected embree, metal or metal-envlod)";
                 return false;
             }
             o.semanticsSet = true;

@@ -122,6 +122,9 @@ struct PtrDeviceScene {
     DeviceBuffer<float4> triUv, triTangent, texels, materialTex;
     DeviceBuffer<uint4> texInfo;
     DeviceBuffer<float> envPdf;
+    // PTR_METAL_ENV_LOD: the environment map's mip chain (EnvLodView::mips), built on the first render that sets the bit
+    DeviceBuffer<float4> envMips;
+    uint32_t envMipLevels = 0;   // 0: not built
     SceneView view{};
     uint64_t info[8] = {0};
     double uploadSeconds = 0.0;
@@ -155,6 +158,7 @@ struct PtrDeviceScene {
     int refillBelow = 40;
     uint32_t spillLevels = 0;   // stack levels beyond the LDS part that the scene's tree can need (sizes the spill area)
     DeviceBuffer<uint4> medium;
+    DeviceBuffer<float> envLod;   // PTR_METAL_ENV_LOD: EnvLodView::slotLod
     DeviceBuffer<uint32_t> scalars, pixelOfLocal, spill;
     DeviceBuffer<uint2> itemReserve;
     DeviceBuffer<uint32_t> itemHeads, zeros;
@@ -511,6 +515,35 @@ void uploadScene(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceSce
     if (knobs.verboseBuild) std::fprintf(stderr, "[upload] prepare %.2f s, copies to the device %.2f s\n", ps.seconds, copySeconds);
 }
 
+// PTR_METAL_ENV_LOD: the mip chain of the scene's environment map by the rule of the material textures (appendTextureWithMips), once per
+// device scene and only when a render asks for it: scenes and renders without the bit keep their memory and upload time.  Level 0 stays
+// where it is (envRgba); the device gets the chain's record (kernels/texture.h layout, offsets counted from the first texel after it)
+// and levels 1...  Returns the milliseconds it took (0 when the chain was there).
+double ensureEnvMips(PtrDeviceScene& ds) {
+    if (ds.envMipLevels > 0u || ds.view.envRgba == nullptr || ds.view.envWidth == 0u || ds.view.envHeight == 0u) return 0.0;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_CHECK(hipSetDevice(ds.device));
+    const uint32_t w = ds.view.envWidth, h = ds.view.envHeight;
+    const size_t level0 = static_cast<size_t>(w) * h;
+    std::vector<float> rgba(level0 * 4u);
+    HIP_CHECK(hipMemcpy(rgba.data(), ds.view.envRgba, level0 * sizeof(float4), hipMemcpyDeviceToHost));
+    const PtrTexture t{rgba.data(), w, h, 0u, 0u, 1u, 0u};   // repeat / repeat, linear
+    std::vector<float> chain;
+    std::vector<uint32_t> info;
+    appendTextureWithMips(t, chain, info);
+    const uint32_t levels = info[2];
+    for (uint32_t l = 1; l < levels; ++l) info[4 + l] -= static_cast<uint32_t>(level0);   // levels 1.. move down over level 0
+    static_assert(kTexInfoWords == 4u * 5u, "texture record layout");
+    std::vector<float> upload(kTexInfoWords + (chain.size() - level0 * 4u));
+    std::memcpy(upload.data(), info.data(), kTexInfoWords * sizeof(uint32_t));
+    std::copy(chain.begin() + static_cast<std::ptrdiff_t>(level0 * 4u), chain.end(), upload.begin() + kTexInfoWords);
+    ds.envMips.upload(reinterpret_cast<const float4*>(upload.data()), upload.size() / 4u);
+    ds.envMipLevels = levels;
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (ptr::readKnobs().verboseBuild) std::fprintf(stderr, "[upload] environment mip chain: %ux%u, %u levels, %.2f ms\n", w, h, levels, ms);
+    return ms;
+}
+
 void buildScene(const PtrSceneDesc& desc, PtrDeviceScene& ds, const char* cachePath = nullptr) {
     PreparedScene ps;
     prepareScene(desc, ps, cachePath);
@@ -585,7 +618,7 @@ void fillRenderParams(const PtrSettings& s, uint32_t spp, RenderParams& rp) {
     rp.clampEnabled = s.fireflyClampEnabled ? 1.0f : 0.0f;
     rp.emissionScale = (s.emissionScale > 0.0f && std::isfinite(s.emissionScale)) ? s.emissionScale : 1.0f;
     rp.mediaMode = s.metalSemantics & (PTR_METAL_MEDIA | PTR_METAL_THIN | PTR_METAL_FACE_NORMAL | PTR_METAL_SPECULAR | PTR_METAL_SSS | PTR_METAL_PBR |
-                                       PTR_METAL_CLAMPS);
+                                       PTR_METAL_CLAMPS | PTR_METAL_ENV_LOD);
     rp.clampMaxContribution = std::max(s.fireflyClampMaxContribution, 0.0f);   // make_firefly_params, pathtrace.metal:3545
     rp.minSpecularPdfRaw = s.minSpecularPdf;
     rp.sssMode = s.sssMode;
@@ -703,6 +736,15 @@ void renderPass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, u
     if (rp.mediaMode & PTR_METAL_MEDIA) ds.medium.ensure(slots);
     const bool texturedPaths = (rp.mediaMode & PTR_METAL_PBR) && ds.view.textureCount > 0u;   // the paths carry a ray cone
     if (texturedPaths) ds.cone.ensure(slots);
+    // PTR_METAL_ENV_LOD with an environment map: the chain (first such render of the scene) and the paths' LOD
+    EnvLodView env{};
+    if ((rp.mediaMode & PTR_METAL_ENV_LOD) && ds.view.envWidth > 0u) {
+        ensureEnvMips(ds);
+        ds.envLod.ensure(slots);
+        env.mips = ds.envMips.ptr;
+        env.slotLod = ds.envLod.ptr;
+        env.levels = ds.envMipLevels;
+    }
 
     PathPool pool;
     std::memset(&pool, 0, sizeof(pool));
@@ -739,6 +781,7 @@ void renderPass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, u
     // depend on how they interleave.
     struct Group {
         PathPool pool;
+        EnvLodView env;
         LaunchConfig cfg;
         hipStream_t stream;
         uint32_t* scalars;
@@ -804,6 +847,8 @@ void renderPass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, u
         if (gr.pool.signature) gr.pool.signature += first;
         if (gr.pool.medium) gr.pool.medium += first;
         if (gr.pool.cone) gr.pool.cone += first;
+        gr.env = env;
+        if (gr.env.slotLod) gr.env.slotLod += first;
         for (uint32_t k = 0; k < kRecSlots; ++k) {
             gr.pool.rec[k].org += first;
             gr.pool.rec[k].dir += first;
@@ -918,7 +963,7 @@ void renderPass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, u
             PathPool shadePool = gr.pool;
             if (!gr.shadeListed) shadePool.busyIn = nullptr;
             if (overlap && iterations > 0) HIP_CHECK(hipStreamWaitEvent(gr.stream, ds.sideEvents[2 * static_cast<uint32_t>(&gr - groups.data()) + 1], 0));
-            timedLaunch(1, gr.stream, [&] { launchShade(rp, ds.view, shadePool, resets, count, gr.stream); });
+            timedLaunch(1, gr.stream, [&] { launchShade(rp, ds.view, shadePool, resets, gr.env, count, gr.stream); });
             if (overlap) {
                 // k_connect of this iteration on the side stream, after this k_shade; the next k_shade waits for it (above)
                 const uint32_t gi = static_cast<uint32_t>(&gr - groups.data());
@@ -1015,7 +1060,7 @@ void renderPass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, u
     }
     if (runTail) {
         HIP_CHECK(hipMemsetAsync(ds.tailWords.ptr, 0, 4 * sizeof(uint32_t), stream));
-        timedLaunch(3, stream, [&] { launchTail(rp, ds.view, pool, groups[0].cfg, ds.tailList.ptr, ds.tailWords.ptr, ds.tailWords.ptr + 1, count, stream); });
+        timedLaunch(3, stream, [&] { launchTail(rp, ds.view, pool, env, groups[0].cfg, ds.tailList.ptr, ds.tailWords.ptr, ds.tailWords.ptr + 1, count, stream); });
     }
     launchResolve(rp, pool, parts, dOut, stream);
     HIP_CHECK(hipGetLastError());
@@ -1685,6 +1730,82 @@ int ptr_debug_sample_bsdf(const PtrMaterial* material, const PtrSettings* settin
         return 0;
     }
     PTR_CATCH_ALL(err, err_cap)
+}
+
+int ptr_debug_sample_lobes(const PtrMaterial* material, const PtrSettings* settings, const float* in, const uint32_t* front_face,
+                           const uint32_t* rng_states, uint64_t n, float* out, float* out_sample, uint32_t* out_states, float* env_roughness,
+                           char* err, size_t err_cap) {
+    try {
+        if (ptr_device_count() < 1) throw HipError{"no HIP device (the HIP path has no CPU fallback)"};
+        HIP_CHECK(hipSetDevice(0));
+        std::vector<float> m;
+        compactMaterial(*material, m);
+        RenderParams rp;
+        fillRenderParams(*settings, 1, rp);
+        DeviceBuffer<float4> dm;
+        DeviceBuffer<float> din, dout, dsample;
+        DeviceBuffer<uint32_t> dfront, drng, drngOut;
+        dm.upload(reinterpret_cast<const float4*>(m.data()), kMaterialVec4);
+        din.upload(in, n * 9);
+        dfront.upload(front_face, n);
+        drng.upload(rng_states, n);
+        dout.ensure(n * 3 + 1);
+        dsample.ensure(n * 8);
+        drngOut.ensure(n);
+        if (n > 0) {
+            launchDebugSampleLobes(dm.ptr, rp, din.ptr, dfront.ptr, drng.ptr, n, dout.ptr, dsample.ptr, drngOut.ptr, nullptr);
+            HIP_CHECK(hipGetLastError());
+        }
+        std::vector<float> o(n * 3 + 1, 0.0f);
+        HIP_CHECK(hipMemcpy(o.data(), dout.ptr, o.size() * sizeof(float), hipMemcpyDeviceToHost));
+        if (out) std::memcpy(out, o.data(), n * 3 * sizeof(float));
+        if (env_roughness) *env_roughness = o[n * 3];
+        if (out_sample) HIP_CHECK(hipMemcpy(out_sample, dsample.ptr, n * 8 * sizeof(float), hipMemcpyDeviceToHost));
+        if (out_states) HIP_CHECK(hipMemcpy(out_states, drngOut.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    PTR_CATCH_ALL(err, err_cap)
+}
+
+int ptr_debug_env_lookup(PtrDeviceScene* scene, const PtrSettings* settings, const float* in, uint64_t n, float* out, char* err, size_t err_cap) {
+    if (!scene || !settings || (!in && n) || (!out && n)) {
+        setErr(err, err_cap, "ptr_debug_env_lookup: null argument");
+        return 1;
+    }
+    try {
+        HIP_CHECK(hipSetDevice(scene->device));
+        if (scene->view.envWidth == 0u) throw HipError{"ptr_debug_env_lookup: the scene has no environment map"};
+        ensureEnvMips(*scene);
+        if (n == 0) return 0;
+        RenderParams rp;
+        fillRenderParams(*settings, 1, rp);
+        const EnvLodView env{scene->envMips.ptr, nullptr, scene->envMipLevels, 0u};
+        DeviceBuffer<float4> din, dout;
+        din.upload(reinterpret_cast<const float4*>(in), n);
+        dout.ensure(n);
+        launchDebugEnvLookup(rp, scene->view, env, din.ptr, n, dout.ptr, nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(out, dout.ptr, n * sizeof(float4), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    PTR_CATCH_ALL(err, err_cap)
+}
+
+int ptr_debug_env_mips(const float* rgba, uint32_t w, uint32_t h, float* out, uint64_t cap_floats, uint32_t* levels_out) {
+    if (!rgba || w == 0u || h == 0u) return 1;
+    try {
+        const PtrTexture t{rgba, w, h, 0u, 0u, 1u, 0u};
+        std::vector<float> chain;
+        std::vector<uint32_t> info;
+        appendTextureWithMips(t, chain, info);
+        if (levels_out) *levels_out = info[2];
+        if (!out) return 0;
+        if (cap_floats < chain.size()) return 1;
+        std::memcpy(out, chain.data(), chain.size() * sizeof(float));
+        return 0;
+    } catch (...) {
+        return 1;
+    }
 }
 
 int ptr_debug_camera_rays(const PtrSettings* settings, const uint32_t* xys, uint64_t n, float* out, uint32_t* out_states,

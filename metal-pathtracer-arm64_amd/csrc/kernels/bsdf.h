@@ -788,11 +788,29 @@ struct BsdfSampleResult {
     int mediumEvent;   // +1: refracted into a dielectric through its front face, -1: out through a back face, else 0
     bool hasExit;      // separable subsurface sample: the path leaves the surface at exitPoint (normal = the shading normal)
     f3 exitPoint;
-    // which lobe the textured metallic-roughness model sampled (0 diffuse, 1 specular, 2 transmission) and its roughness: what the
-    // ray cone of the path widens by (bsdf_cone_spread_increment, shaders/pathtrace.metal:5703-5715); read only in textured scenes
+    // lobeType / lobeRoughness of the Metal kernel's samplers: the lobe sampled (0 diffuse, 1 specular, 2 transmission) and its
+    // roughness.  Filled only in the Metal-semantics instantiation (SSS), by every sampler as the Metal kernel does (Lambert (0, 1),
+    // metal (1, r), plastic coat (1, coat r), car paint the lobe picked, glass (1, 0), subsurface (0, 0), ...: sample_bsdf, :5136-5700;
+    // sample_pbr_metallic_roughness, :4784-4866).  Read by the ray cone of textured paths (bsdf_cone_spread_increment, :5703-5715)
+    // and by the environment LOD of PTR_METAL_ENV_LOD (:7249-7260).
     int lobe = 0;
     float lobeRoughness = 0.0f;
 };
+
+// (called under `if constexpr (SSS)`: the other instantiations do not see it at all, and compile to the code they had before)
+__device__ __forceinline__ void setLobe(BsdfSampleResult& r, int lobe, float roughness) {
+    r.lobe = lobe;
+    r.lobeRoughness = roughness;
+}
+
+// environment_lighting_roughness (shaders/pathtrace.metal:3834-3847): the roughness a hit's environment sample is prefiltered for
+__device__ __forceinline__ float envLightingRoughness(const Mat& m) {
+    const uint32_t type = m.type();
+    if (type == 1u || type == 7u) return m.roughness01();
+    if (type == 4u) return clampf(smax(clampf(m.v(kMatCoatParams).x, 0.0f, 1.0f), 1.0e-3f), 0.0f, 1.0f);   // plastic_coat_roughness
+    if (type == 6u) return clampf(m.v(kMatCarpaintBase).y, 0.0f, 1.0f);                                   // carpaint_base_roughness
+    return 1.0f;
+}
 
 // ---- separable subsurface scattering of the Metal integrator (shaders/pathtrace.metal:3916-3994) ----
 struct SssCoefficients {
@@ -1068,7 +1086,7 @@ __device__ BsdfSampleResult samplePbrMetal(const Mat& m, f3 n, f3 wo, f3 inciden
     float pdfSpec = 0.0f, pdfDiffuse = 0.0f, pdfTrans = 0.0f;
     bool isDelta = false;
     r.lobe = choose < p.pSpec ? 1 : (choose < p.pSpec + p.pDiff ? 0 : 2);
-    r.lobeRoughness = p.roughness;
+    r.lobeRoughness = r.lobe == 0 ? 1.0f : p.roughness;
     if (choose < p.pSpec) {
         if (p.roughness <= 1.0e-3f) {
             wi = reflectDir(incident, n);
@@ -1172,6 +1190,7 @@ __device__ BsdfSampleResult sampleBsdf(const Mat& m, f3 position, f3 n, f3 wo, f
                 if (pdfD <= 0.0f || smax(dot(n, wi), 0.0f) <= 0.0f) return r;
                 f = p.diffuseColor / kPi;
             }
+            if constexpr (SSS) setLobe(r, pdfS > 0.0f ? 1 : 0, pdfS > 0.0f ? p.roughness : 1.0f);
             const float cosI = smax(dot(n, wi), 0.0f);
             const float pdfSc = (pdfS > 0.0f) ? clampSpecPdf(pdfS, cc) : 0.0f;
             const float pdf = p.specWeight * pdfSc + (1.0f - p.specWeight) * pdfD;
@@ -1193,9 +1212,11 @@ __device__ BsdfSampleResult sampleBsdf(const Mat& m, f3 position, f3 n, f3 wo, f
                 const f3 wh = sampleGgxHalf(rng, alpha, n);
                 if (dot(wh, n) <= 0.0f) return r;
                 wi = normalize(reflectDir(-wo, wh));
+                if constexpr (SSS) setLobe(r, 1, c.roughness);
             } else {
                 float unused;
                 wi = cosineHemisphere(rng, n, unused);
+                if constexpr (SSS) setLobe(r, 0, 1.0f);
             }
             const float cosI = smax(dot(n, wi), 0.0f), cosO = smax(dot(n, wo), 0.0f);
             if (cosI <= 0.0f || cosO <= 0.0f) return r;
@@ -1215,6 +1236,7 @@ __device__ BsdfSampleResult sampleBsdf(const Mat& m, f3 position, f3 n, f3 wo, f
             if (!(MATS & (1u << 1))) break;
             const float rough = m.roughness01();
             const Conductor c = loadMetal(m);
+            if constexpr (SSS) setLobe(r, 1, rough);
             if (rough <= 1.0e-3f) {
                 const f3 wi = normalize(reflectDir(incident, n));
                 if (dot(n, wi) <= 0.0f) return r;
@@ -1266,8 +1288,10 @@ __device__ BsdfSampleResult sampleBsdf(const Mat& m, f3 position, f3 n, f3 wo, f
                 const f3 wh = sampleGgxVndf(rng, c.coat.roughness, n, wo);
                 if (dot(wh, n) <= 0.0f) return r;
                 wi = normalize(reflectDir(-wo, wh));
+                if constexpr (SSS) setLobe(r, 1, c.coat.roughness);
             } else if (lobe == 1u) {
                 const float fr = smax(c.flakeRoughness, 1.0e-3f);
+                if constexpr (SSS) setLobe(r, 1, fr);
                 const f3 fn = carpaintFlakeNormal(c, position, n);
                 const f3 wh = sampleGgxHalf(rng, fr * fr, fn);
                 if (dot(wh, fn) <= 0.0f) return r;
@@ -1281,9 +1305,11 @@ __device__ BsdfSampleResult sampleBsdf(const Mat& m, f3 position, f3 n, f3 wo, f
                     const f3 wh = sampleGgxHalf(rng, br * br, n);
                     if (dot(wh, n) <= 0.0f) return r;
                     wi = normalize(reflectDir(-wo, wh));
+                    if constexpr (SSS) setLobe(r, 1, br);
                 } else {
                     float unused;
                     wi = cosineHemisphere(rng, n, unused);
+                    if constexpr (SSS) setLobe(r, 0, 1.0f);
                 }
             }
             if (!finite3(wi) || dot(n, wi) <= 0.0f) return r;
@@ -1306,6 +1332,7 @@ __device__ BsdfSampleResult sampleBsdf(const Mat& m, f3 position, f3 n, f3 wo, f
         case 2u: {  // smooth dielectric: Fresnel-weighted pick between mirror reflection and refraction
             if (!(MATS & (1u << 2))) break;
             r.isDelta = true;
+            if constexpr (SSS) setLobe(r, 1, 0.0f);
             const float refIdx = smax(m.ior(), 1.0f);
             // thin-walled glass (Metal semantics only, pathtrace.metal:5649-5659): both faces see air -> glass
             const bool thin = cc.thinDielectrics && m.thinFlag();
@@ -1352,6 +1379,7 @@ __device__ BsdfSampleResult sampleBsdf(const Mat& m, f3 position, f3 n, f3 wo, f
             r.dir = wi;
             r.weight = vmax0(w);
             r.pdf = pdf;
+            if constexpr (SSS) setLobe(r, 0, type == 0u ? 1.0f : 0.0f);
             return r;
         }
         default:

@@ -156,6 +156,17 @@ struct RenderParams {
     float shadowSlack;             // test knob (PtrSettings.debugShadowSlack): 0 = the reference's shadow-ray length (quirk Q9)
 };
 
+// PTR_METAL_ENV_LOD: the environment map's mip chain and the level of detail of each path's next escaped ray (shaders/pathtrace.metal:
+// 5755-5756, 7249-7260).  The Metal-semantics k_shade / k_tail_run take it as their LAST argument rather than as fields of SceneView /
+// PathPool: every other kernel argument keeps its offset, so the kernels of the Embree-parity integrator compile to the same code.
+struct EnvLodView {
+    const float4* mips;   // the chain's record in the texture layout (texture.h kTexInfoVec4 uint4: width, height, levels, flags; texel
+                          // offsets of levels 0..15), then levels 1.. back to back; level 0 is SceneView::envRgba.  Null: no chain
+    float* slotLod;       // per path slot (indexed like the PathPool fields): LOD of the slot's next escaped ray, < 0 inactive.  Null: off
+    uint32_t levels;      // levels of the chain, level 0 included
+    uint32_t pad;
+};
+
 // One pending light-connection ray of a path slot.
 //   org = (origin, tmax)   dir = (direction, bits(kind))   a = (contribution or bsdf weight, 0)   b = (throughput, 0)
 //   kind 0: any-hit; a is the finished contribution, zeroed by the connect kernel when occluded

@@ -26,14 +26,15 @@ struct ShadeResets {
     uint32_t* nextAlive;     // live-slot counter of the next k_extend
     uint32_t drained;        // nonzero once most slots are dead: waves look at the state word alone before loading the rest
 };
-void launchShade(const RenderParams& rp, const SceneView& sc, const PathPool& pool, const ShadeResets& resets, bool count,
+// env: PTR_METAL_ENV_LOD (device_types.h; all null without the bit)
+void launchShade(const RenderParams& rp, const SceneView& sc, const PathPool& pool, const ShadeResets& resets, const EnvLodView& env, bool count,
                  hipStream_t stream);
 void launchConnect(const RenderParams& rp, const SceneView& sc, const PathPool& pool, const LaunchConfig& cfg, bool count,
                    hipStream_t stream);
 // End of the frame: every busy slot of `pool` (the WHOLE pool) is run to the end of its path by one lane (k_tail_collect + k_tail_run).
 // dList: pool.slots words; dListCount / dListHead: single words, zero on entry.
-void launchTail(const RenderParams& rp, const SceneView& sc, const PathPool& pool, const LaunchConfig& cfg, uint32_t* dList, uint32_t* dListCount,
-                uint32_t* dListHead, bool count, hipStream_t stream);
+void launchTail(const RenderParams& rp, const SceneView& sc, const PathPool& pool, const EnvLodView& env, const LaunchConfig& cfg, uint32_t* dList,
+                uint32_t* dListCount, uint32_t* dListHead, bool count, hipStream_t stream);
 // Adds outstanding light connections, reduces the slots of each pixel in fixed order and writes
 // out[((localBand*PTR_BAND_ROWS + row) * width + x) * 3 + c] = sum / spp.
 void launchResolve(const RenderParams& rp, const PathPool& pool, uint32_t partCount, float* dOut, hipStream_t stream);
@@ -54,6 +55,13 @@ void launchDebugEvalBsdf(const float4* dMaterial, const RenderParams& rp, const 
                          hipStream_t stream);
 void launchDebugSampleBsdf(const float4* dMaterial, const RenderParams& rp, const float* dIn, const uint32_t* dFront,
                            const uint32_t* dRng, uint64_t n, float* dOut, uint32_t* dRngOut, hipStream_t stream);
+// sample_bsdf's lobe bookkeeping: out n x 3 {lobe, lobe roughness, isDelta} + out[3 n] = the material's environment-lighting roughness;
+// dSample n x 8 as launchDebugSampleBsdf
+void launchDebugSampleLobes(const float4* dMaterial, const RenderParams& rp, const float* dIn, const uint32_t* dFront, const uint32_t* dRng,
+                            uint64_t n, float* dOut, float* dSample, uint32_t* dRngOut, hipStream_t stream);
+// PTR_METAL_ENV_LOD lookups: in n x {direction, roughness} -> out n x {LOD, radiance}
+void launchDebugEnvLookup(const RenderParams& rp, const SceneView& sc, const EnvLodView& env, const float4* dIn, uint64_t n, float4* dOut,
+                          hipStream_t stream);
 void launchDebugTexSample(const SceneView& sc, uint32_t texture, const float* dIn, uint64_t n, float4* dOut, hipStream_t stream);
 // closest hit, surface record and next-ray origin per input ray: in n x 9 floats {origin, direction, next direction}, out n x 16 floats
 // the material / feature set of the k_shade instantiation launchShade picks (bsdf.h kAllMaterials = the full kernel)

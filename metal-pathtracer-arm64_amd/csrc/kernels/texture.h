@@ -28,14 +28,18 @@ struct TexLevel {
     uint32_t offset, width, height;
 };
 
-__device__ __forceinline__ TexLevel texLevel(const SceneView& sc, uint32_t tex, uint32_t level, uint4 head) {
-    const uint4 offs = sc.texInfo[tex * kTexInfoVec4 + 1u + (level >> 2)];
+// level `level` of the texture whose record starts at `record` (record[0] = head)
+__device__ __forceinline__ TexLevel texLevelOf(const uint4* record, uint32_t level, uint4 head) {
+    const uint4 offs = record[1u + (level >> 2)];
     const uint32_t l = level & 3u;
     TexLevel r;
     r.offset = l == 0u ? offs.x : (l == 1u ? offs.y : (l == 2u ? offs.z : offs.w));
     r.width = max(head.x >> level, 1u);
     r.height = max(head.y >> level, 1u);
     return r;
+}
+__device__ __forceinline__ TexLevel texLevel(const SceneView& sc, uint32_t tex, uint32_t level, uint4 head) {
+    return texLevelOf(sc.texInfo + tex * kTexInfoVec4, level, head);
 }
 
 __device__ __forceinline__ int texWrap(int i, int n, uint32_t mode) {
@@ -50,20 +54,21 @@ __device__ __forceinline__ int texWrap(int i, int n, uint32_t mode) {
     return j < 0 ? j + n : j;
 }
 
-__device__ __forceinline__ float4 texBilinear(const SceneView& sc, const TexLevel& L, float u, float v, uint32_t flags) {
+// `texels`: the array the level's offset counts from
+__device__ __forceinline__ float4 texBilinear(const float4* texels, const TexLevel& L, float u, float v, uint32_t flags) {
     const uint32_t wrapS = flags & 3u, wrapT = (flags >> 2) & 3u;
     const int W = static_cast<int>(L.width), H = static_cast<int>(L.height);
     if (((flags >> 4) & 1u) == 0u) {   // NEAREST
         const int x = texWrap(static_cast<int>(floorf(u * static_cast<float>(W))), W, wrapS);
         const int y = texWrap(static_cast<int>(floorf(v * static_cast<float>(H))), H, wrapT);
-        return sc.texels[L.offset + static_cast<uint32_t>(y) * L.width + static_cast<uint32_t>(x)];
+        return texels[L.offset + static_cast<uint32_t>(y) * L.width + static_cast<uint32_t>(x)];
     }
     const float fx = u * static_cast<float>(W) - 0.5f, fy = v * static_cast<float>(H) - 0.5f;
     const float x0f = floorf(fx), y0f = floorf(fy);
     const float tx = fx - x0f, ty = fy - y0f;
     const int x0 = texWrap(static_cast<int>(x0f), W, wrapS), x1 = texWrap(static_cast<int>(x0f) + 1, W, wrapS);
     const int y0 = texWrap(static_cast<int>(y0f), H, wrapT), y1 = texWrap(static_cast<int>(y0f) + 1, H, wrapT);
-    const float4* base = sc.texels + L.offset;
+    const float4* base = texels + L.offset;
     const float4 c00 = base[static_cast<uint32_t>(y0) * L.width + static_cast<uint32_t>(x0)];
     const float4 c10 = base[static_cast<uint32_t>(y0) * L.width + static_cast<uint32_t>(x1)];
     const float4 c01 = base[static_cast<uint32_t>(y1) * L.width + static_cast<uint32_t>(x0)];
@@ -73,20 +78,30 @@ __device__ __forceinline__ float4 texBilinear(const SceneView& sc, const TexLeve
                        (c00.z * ix + c10.z * tx) * iy + (c01.z * ix + c11.z * tx) * ty, (c00.w * ix + c10.w * tx) * iy + (c01.w * ix + c11.w * tx) * ty);
 }
 
+// Linear between the two nearest levels of a chain of `levels` (lod clamped to [0, levels - 1]); bilinear(l) filters level l.
+template <typename Bilinear>
+__device__ __forceinline__ float4 texTrilinear(uint32_t levels, float lod, Bilinear bilinear) {
+    const float maxMip = static_cast<float>(levels - 1u);
+    const float l = fminf(fmaxf(lod, 0.0f), maxMip);
+    const float l0f = floorf(l);
+    const uint32_t l0 = static_cast<uint32_t>(l0f), l1 = min(l0 + 1u, levels - 1u);
+    const float f = l - l0f;
+    const float4 a = bilinear(l0);
+    if (!(f > 0.0f) || l1 == l0) return a;
+    const float4 b = bilinear(l1);
+    return make_float4(a.x + (b.x - a.x) * f, a.y + (b.y - a.y) * f, a.z + (b.z - a.z) * f, a.w + (b.w - a.w) * f);
+}
+
 // sample_material_texture_level with the filtering rule above; `fallback` when the slot has no texture
 __device__ __forceinline__ float4 texSample(const SceneView& sc, uint32_t tex, float u, float v, float lod, float4 fallback) {
     if (tex == kNoTexture || tex >= sc.textureCount) return fallback;
     const uint4 head = sc.texInfo[tex * kTexInfoVec4];
     const float maxMip = static_cast<float>(head.z - 1u);
-    const float l = fminf(fmaxf(lod, 0.0f), maxMip);
-    if (((head.w >> 4) & 1u) == 0u) return texBilinear(sc, texLevel(sc, tex, static_cast<uint32_t>(floorf(l + 0.5f)), head), u, v, head.w);
-    const float l0f = floorf(l);
-    const uint32_t l0 = static_cast<uint32_t>(l0f), l1 = min(l0 + 1u, head.z - 1u);
-    const float f = l - l0f;
-    const float4 a = texBilinear(sc, texLevel(sc, tex, l0, head), u, v, head.w);
-    if (!(f > 0.0f) || l1 == l0) return a;
-    const float4 b = texBilinear(sc, texLevel(sc, tex, l1, head), u, v, head.w);
-    return make_float4(a.x + (b.x - a.x) * f, a.y + (b.y - a.y) * f, a.z + (b.z - a.z) * f, a.w + (b.w - a.w) * f);
+    if (((head.w >> 4) & 1u) == 0u) {
+        const float l = fminf(fmaxf(lod, 0.0f), maxMip);
+        return texBilinear(sc.texels, texLevel(sc, tex, static_cast<uint32_t>(floorf(l + 0.5f)), head), u, v, head.w);
+    }
+    return texTrilinear(head.z, lod, [&](uint32_t level) { return texBilinear(sc.texels, texLevel(sc, tex, level, head), u, v, head.w); });
 }
 
 // ray_cone_lod_from_footprint (:162-176)

@@ -301,6 +301,30 @@ __device__ __forceinline__ f3 envLookup(const SceneView& sc, f3 direction, float
     return (c0 * (1.0f - ty) + c1 * ty) * smax(intensity, 0.0f);
 }
 
+// ---- PTR_METAL_ENV_LOD: the prefiltered lookups of the Metal kernel ----
+// environment_lod_from_roughness (shaders/pathtrace.metal:1334-1344)
+__device__ __forceinline__ float envLodFromRoughness(float roughness, float maxMip) {
+    if (maxMip <= 0.0f) return 0.0f;
+    float alpha = clampf(roughness, 0.0f, 1.0f);
+    alpha = alpha * alpha;
+    return clampf(alpha * maxMip, 0.0f, maxMip);
+}
+
+// environment_color_lod (:1389-1407) through the sampler of the environment texture (:20-23): the (u, v) of envLookup; bilinear inside a
+// level with texel centres at (i + 0.5) / W and repeat addressing on BOTH axes (envLookup clamps v: the Embree rule), linear between
+// levels (texture.h's filter).  Level 0 is read from envRgba, levels 1.. from the chain.
+constexpr uint32_t kEnvMipFlags = 1u << 4;   // texture.h flags: wrapS = wrapT = repeat, linear
+__device__ __forceinline__ f3 envLookupLod(const SceneView& sc, const EnvLodView& env, f3 direction, float rotation, float intensity, float lod) {
+    float u, v;
+    envUv(direction, rotation, u, v);
+    const uint4* record = reinterpret_cast<const uint4*>(env.mips);
+    const uint4 head = make_uint4(sc.envWidth, sc.envHeight, env.levels, kEnvMipFlags);
+    const float4 c = texTrilinear(env.levels, lod, [&](uint32_t level) {
+        return texBilinear(level == 0u ? sc.envRgba : env.mips + kTexInfoVec4, texLevelOf(record, level, head), u, v, kEnvMipFlags);
+    });
+    return mk3(c) * smax(intensity, 0.0f);
+}
+
 // Solid-angle pdf of the texel a direction looks up (note: offset by half a turn from the texel the
 // sampler would have drawn it from — reference quirk Q2, kept).
 __device__ __forceinline__ float envPdfOf(const SceneView& sc, f3 direction, float rotation) {
@@ -1115,9 +1139,10 @@ constexpr int kShadeDense = 0, kShadeListed = 1, kShadeTail = 2;
 // separate instantiation because they cost registers whether or not a scene uses them: with the texture code in, the Metal-model
 // kernel drops to 3 waves/SIMD and untextured Metal-semantics scenes ran 19-25 % slower than in round 1.
 // MATS: the material types the scene can contain (bsdf.h kAllMaterials, or the set of a simple scene: see launchShade)
+// env: PTR_METAL_ENV_LOD (read only by the SSS instantiations)
 template <bool COUNT, bool SSS, bool TEX, int MODE, uint32_t MATS = kAllMaterials>
 __device__ __forceinline__ void shadeSlot(const RenderParams& rp, const SceneView& sc, const PathPool& pool, const uint32_t slot, const bool inRange,
-                                          const bool drained, const uint32_t listWave, ShadeCounts& counts) {
+                                          const bool drained, const uint32_t listWave, ShadeCounts& counts, const EnvLodView& env) {
     constexpr bool TAIL = MODE == kShadeTail;
     // Everything that depends only on the slot index is requested up front, and the record loads are pointed at a
     // zero word when the record is not pending, so the kernel has ~11 loads in flight per lane after ONE dependent
@@ -1179,6 +1204,10 @@ __device__ __forceinline__ void shadeSlot(const RenderParams& rp, const SceneVie
     const uint32_t envWidth = (MATS & kFeatureEnvironment) ? sc.envWidth : 0u;
     const bool envSampling = (MATS & kFeatureEnvironment) && sc.envSampling;
     const uint32_t mediaMode = (MATS & kFeatureMedia) ? rp.mediaMode : 0u;
+    // PTR_METAL_ENV_LOD (the host passes the slot array only with the bit, and only for a scene with an environment map): the LOD the
+    // next escaped ray is read at, from this visit's BSDF sample; < 0 = level 0 (every other event, and a new sample)
+    const bool envLodOn = SSS && env.slotLod != nullptr;
+    float envLodNext = -1.0f;
 
     if (touched) {
         const ClampCfg cc = clampCfg<SSS>(rp);
@@ -1288,7 +1317,9 @@ __device__ __forceinline__ void shadeSlot(const RenderParams& rp, const SceneVie
                 if (rp.backgroundMode == PTR_BG_SOLID) {
                     bg = ld3(rp.backgroundColor);
                 } else if (rp.backgroundMode == PTR_BG_ENVIRONMENT && envWidth > 0u) {
-                    bg = envLookup(sc, rayD, rp.envRotation, rp.envIntensity);
+                    // (a camera ray, depth 0, always reads level 0; every deeper ray's LOD was stored at the visit that sampled it)
+                    const float lod = (envLodOn && depth > 0u) ? env.slotLod[slot] : -1.0f;
+                    bg = lod >= 0.0f ? envLookupLod(sc, env, rayD, rp.envRotation, rp.envIntensity, lod) : envLookup(sc, rayD, rp.envRotation, rp.envIntensity);
                 } else {
                     bg = skyColor(rayD);
                 }
@@ -1417,7 +1448,12 @@ __device__ __forceinline__ void shadeSlot(const RenderParams& rp, const SceneVie
                         envSample(sc, uM, uC, uJ, rp.envRotation, edir, epdf);
                         const float nDotL = smax(dot(n, edir), 0.0f);
                         if (epdf > 0.0f && nDotL > 0.0f) {
-                            const f3 envRadiance = envLookup(sc, edir, rp.envRotation, rp.envIntensity);
+                            // (PTR_METAL_ENV_LOD: prefiltered for the material's roughness below 0.95, pathtrace.metal:6566-6581; pdf and
+                            // weights stay those of the level-0 tables)
+                            const float envRough = (envLodOn && env.levels > 1u) ? envLightingRoughness(mat) : 1.0f;
+                            const f3 envRadiance = envRough < 0.95f ? envLookupLod(sc, env, edir, rp.envRotation, rp.envIntensity,
+                                                                                   envLodFromRoughness(envRough, static_cast<float>(env.levels - 1u)))
+                                                                    : envLookup(sc, edir, rp.envRotation, rp.envIntensity);
                             const BsdfEvalResult be = evalBsdf<SSS, MATS>(mat, sf.position, n, wo, edir, cc);
                             if (neeContributes<SSS>(be, cc)) {
                                 const float w = neeWeight<SSS>(epdf, be.pdf, cc);
@@ -1536,6 +1572,10 @@ __device__ __forceinline__ void shadeSlot(const RenderParams& rp, const SceneVie
                         } else {
                             lastPdf = bs.pdf > 0.0f ? bs.pdf : lastPdf;
                             lastDelta = bs.isDelta;
+                            // PTR_METAL_ENV_LOD: a glossy, non-delta lobe sets the path's LOD (pathtrace.metal:7249-7260)
+                            if (envLodOn && bs.lobe == 1 && !bs.isDelta && env.levels > 1u) {
+                                envLodNext = envLodFromRoughness(bs.lobeRoughness, static_cast<float>(env.levels - 1u));
+                            }
                             nextO = (SSS && bs.hasExit) ? sssExitOrigin(bs.exitPoint, n, bs.dir) : offsetOrigin(of, bs.dir);
                             nextD = bs.dir;
                             if (TEX && pool.cone) {
@@ -1644,6 +1684,7 @@ __device__ __forceinline__ void shadeSlot(const RenderParams& rp, const SceneVie
         }
         if (COUNT && pool.signature) pool.signature[slot] = sig;
         if (TEX && pool.cone && stillAlive && (haveCone || newSample)) pool.cone[slot] = newSample ? primaryCone(rp) : cone;
+        if (envLodOn && stillAlive) env.slotLod[slot] = newSample ? -1.0f : envLodNext;
     }
 
     if (!TAIL && pool.connectList) {
@@ -1683,8 +1724,10 @@ __device__ __forceinline__ void shadeSlot(const RenderParams& rp, const SceneVie
 }
 
 // LISTED: the launch walks pool.busyIn instead of the slots (end of the frame, see PathPool)
+// env: last, so that the other arguments keep their offsets (device_types.h EnvLodView)
 template <bool COUNT, bool SSS, bool TEX, bool LISTED, uint32_t MATS = kAllMaterials>
-__global__ void __launch_bounds__(kShadeBlock) PTR_SHADE_WAVES_ATTR_M k_shade(RenderParams rp, SceneView sc, PathPool pool, ShadeResets resets) {
+__global__ void __launch_bounds__(kShadeBlock) PTR_SHADE_WAVES_ATTR_M k_shade(RenderParams rp, SceneView sc, PathPool pool, ShadeResets resets,
+                                                                            EnvLodView env) {
     const uint32_t index = blockIdx.x * kShadeBlock + threadIdx.x;
     if (index == 0u) {
         // k_shade runs between this iteration's k_extend and k_connect: it clears the work heads they will claim from
@@ -1710,9 +1753,9 @@ __global__ void __launch_bounds__(kShadeBlock) PTR_SHADE_WAVES_ATTR_M k_shade(Re
             const uint32_t at = lists.position(inRange ? index : 0u, pool.connectRegion);
             slot = inRange ? (pool.busyIn[at] & ~kBusyAliveBit) : 0u;
         }
-        shadeSlot<COUNT, SSS, TEX, kShadeListed, MATS>(rp, sc, pool, slot, inRange, drained, index >> 6, counts);
+        shadeSlot<COUNT, SSS, TEX, kShadeListed, MATS>(rp, sc, pool, slot, inRange, drained, index >> 6, counts, env);
     } else {
-        shadeSlot<COUNT, SSS, TEX, kShadeDense, MATS>(rp, sc, pool, index, index < pool.slots, resets.drained != 0u, index >> 6, counts);
+        shadeSlot<COUNT, SSS, TEX, kShadeDense, MATS>(rp, sc, pool, index, index < pool.slots, resets.drained != 0u, index >> 6, counts, env);
     }
     if (COUNT) {
         addCounter(pool.counters, kCntShadedHits, counts.shadedHit);
@@ -2002,7 +2045,7 @@ __global__ void __launch_bounds__(256) k_tail_collect(PathPool pool, uint32_t* l
 
 template <bool COUNT, bool SSS, bool TEX>
 __global__ void __launch_bounds__(kTraceBlock) k_tail_run(RenderParams rp, SceneView sc, PathPool pool, const uint32_t* list, const uint32_t* listCount,
-                                                          uint32_t* listHead, uint32_t* spill, uint32_t spillStride) {
+                                                          uint32_t* listHead, uint32_t* spill, uint32_t spillStride, EnvLodView env) {
     __shared__ uint32_t ldsStack[kLdsStackLevels * kTraceBlock];
     LaneStack stack;
     stack.lds = (LdsWord*)(ldsStack + threadIdx.x);
@@ -2040,7 +2083,7 @@ __global__ void __launch_bounds__(kTraceBlock) k_tail_run(RenderParams rp, Scene
                     __threadfence();
                 }
                 // k_shade's part
-                shadeSlot<COUNT, SSS, TEX, kShadeTail>(rp, sc, pool, slot, true, false, 0u, counts);
+                shadeSlot<COUNT, SSS, TEX, kShadeTail>(rp, sc, pool, slot, true, false, 0u, counts, env);
                 __threadfence();
                 // k_connect's part: the records this visit queued
                 uint32_t bits = (__float_as_uint(pool.ray1[slot].w) >> kFlagPendingShift) & kFlagPendingMask;
@@ -2274,6 +2317,36 @@ __global__ void k_debug_sample(const float4* material, RenderParams rp, const fl
     rngOut[i] = rng;
 }
 
+// sample_bsdf's lobe bookkeeping (Metal-semantics instantiation): out n x 3 {lobe, lobe roughness, isDelta}, sample n x 8 as k_debug_sample
+__global__ void k_debug_sample_lobes(const float4* material, RenderParams rp, const float* in, const uint32_t* front, const uint32_t* rngIn,
+                                     uint64_t n, float* out, float* sample, uint32_t* rngOut) {
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* p = in + i * 9u;
+    const Mat m{material};
+    uint32_t rng = rngIn[i];
+    const f3 wo = ld3(p + 6);
+    const BsdfSampleResult s = sampleBsdf<true>(m, ld3(p), ld3(p + 3), wo, -wo, front[i] != 0u, rng, clampCfg(rp));
+    float* o = out + i * 3u;
+    o[0] = static_cast<float>(s.lobe); o[1] = s.lobeRoughness; o[2] = s.isDelta ? 1.0f : 0.0f;
+    float* q = sample + i * 8u;
+    q[0] = s.dir.x; q[1] = s.dir.y; q[2] = s.dir.z;
+    q[3] = s.weight.x; q[4] = s.weight.y; q[5] = s.weight.z;
+    q[6] = s.pdf; q[7] = s.isDelta ? 1.0f : 0.0f;
+    rngOut[i] = rng;
+    if (i == 0u) out[n * 3u] = envLightingRoughness(m);
+}
+
+// PTR_METAL_ENV_LOD lookups: in n x 4 {direction, roughness}, out n x 4 {LOD of that roughness, radiance}
+__global__ void k_debug_env_lookup(RenderParams rp, SceneView sc, EnvLodView env, const float4* in, uint64_t n, float4* out) {
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 q = in[i];
+    const float lod = envLodFromRoughness(q.w, static_cast<float>(env.levels - 1u));
+    const f3 c = envLookupLod(sc, env, mk3(q), rp.envRotation, rp.envIntensity, lod);
+    out[i] = make_float4(lod, c.x, c.y, c.z);
+}
+
 __global__ void k_debug_tex_sample(SceneView sc, uint32_t texture, const float* in, uint64_t n, float4* out) {
     const uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -2362,8 +2435,11 @@ void launchExtend(const SceneView& sc, const PathPool& pool, const LaunchConfig&
 
 // The k_shade instantiation a render of this scene launches: the smallest compiled set (materials + features) that covers it, or
 // kAllMaterials.  The Metal-semantics instantiations (SSS, TEX) and the counting ones are compiled for every material.
+// The Metal-only models that run in the SSS instantiations.
+constexpr uint32_t kMetalInstantiationBits = PTR_METAL_SSS | PTR_METAL_PBR | PTR_METAL_CLAMPS | PTR_METAL_ENV_LOD;
+
 uint32_t shadeKernelSet(const RenderParams& rp, const SceneView& sc, bool count) {
-    const bool sss = (rp.mediaMode & (PTR_METAL_SSS | PTR_METAL_PBR | PTR_METAL_CLAMPS)) != 0u;
+    const bool sss = (rp.mediaMode & kMetalInstantiationBits) != 0u;
     if (sss || count || sc.materialTypes == 0u) return kAllMaterials;
     // (an environment map and the Metal media / face-normal rules are features of the set like a material type is)
     const uint32_t needs = sc.materialTypes | ((sc.envWidth > 0u || sc.envSampling) ? kFeatureEnvironment : 0u) |
@@ -2374,13 +2450,13 @@ uint32_t shadeKernelSet(const RenderParams& rp, const SceneView& sc, bool count)
     return kAllMaterials;
 }
 
-void launchShade(const RenderParams& rp, const SceneView& sc, const PathPool& pool, const ShadeResets& resets, bool count,
+void launchShade(const RenderParams& rp, const SceneView& sc, const PathPool& pool, const ShadeResets& resets, const EnvLodView& env, bool count,
                  hipStream_t stream) {
-    const bool sss = (rp.mediaMode & (PTR_METAL_SSS | PTR_METAL_PBR | PTR_METAL_CLAMPS)) != 0u;   // the instantiation that carries those Metal-only models
+    const bool sss = (rp.mediaMode & kMetalInstantiationBits) != 0u;   // the instantiation that carries those Metal-only models
     const bool listed = pool.busyIn != nullptr;   // the grid still covers every slot: waves beyond the list leave at once
     const bool tex = sss && sc.textureCount > 0u;   // the instantiation with the texture lookups and the ray cone
     const uint32_t grid = ceilDiv(pool.slots, kShadeBlock);
-    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kShadeBlock), 0, stream, rp, sc, pool, resets); };
+    auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kShadeBlock), 0, stream, rp, sc, pool, resets, env); };
     const uint32_t set = shadeKernelSet(rp, sc, count);
     auto pick = [&](auto countTag, auto listedTag) {
         constexpr bool C = decltype(countTag)::value, L = decltype(listedTag)::value;
@@ -2428,16 +2504,16 @@ void launchConnect(const RenderParams& rp, const SceneView& sc, const PathPool& 
     }
 }
 
-void launchTail(const RenderParams& rp, const SceneView& sc, const PathPool& pool, const LaunchConfig& cfgIn, uint32_t* dList, uint32_t* dListCount,
-                uint32_t* dListHead, bool count, hipStream_t stream) {
+void launchTail(const RenderParams& rp, const SceneView& sc, const PathPool& pool, const EnvLodView& env, const LaunchConfig& cfgIn, uint32_t* dList,
+                uint32_t* dListCount, uint32_t* dListHead, bool count, hipStream_t stream) {
     const LaunchConfig cfg = perBlockSize(cfgIn);
     // dListCount and dListHead are zero on entry (the caller clears them on the same stream)
     const uint32_t collectGrid = std::max(1u, std::min(cfg.traceGrid, ceilDiv(pool.slots, 256u * 16u)));
     hipLaunchKernelGGL(k_tail_collect, dim3(collectGrid), dim3(256), 0, stream, pool, dList, dListCount);
     const uint32_t stride = cfg.traceGrid * kTraceBlock;
-    const bool sss = (rp.mediaMode & (PTR_METAL_SSS | PTR_METAL_PBR | PTR_METAL_CLAMPS)) != 0u;
+    const bool sss = (rp.mediaMode & kMetalInstantiationBits) != 0u;
     auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(cfg.traceGrid), dim3(kTraceBlock), 0, stream, rp, sc, pool, dList, dListCount, dListHead, cfg.spill, stride);
+        hipLaunchKernelGGL(kernel, dim3(cfg.traceGrid), dim3(kTraceBlock), 0, stream, rp, sc, pool, dList, dListCount, dListHead, cfg.spill, stride, env);
     };
     const bool tex = sss && sc.textureCount > 0u;
     if (count) {
@@ -2486,6 +2562,17 @@ void launchDebugEvalBsdf(const float4* dMaterial, const RenderParams& rp, const 
 void launchDebugSampleBsdf(const float4* dMaterial, const RenderParams& rp, const float* dIn, const uint32_t* dFront, const uint32_t* dRng,
                            uint64_t n, float* dOut, uint32_t* dRngOut, hipStream_t stream) {
     hipLaunchKernelGGL(k_debug_sample, dim3(std::max(1u, ceilDiv(n, 128))), dim3(128), 0, stream, dMaterial, rp, dIn, dFront, dRng, n, dOut, dRngOut);
+}
+
+void launchDebugSampleLobes(const float4* dMaterial, const RenderParams& rp, const float* dIn, const uint32_t* dFront, const uint32_t* dRng,
+                            uint64_t n, float* dOut, float* dSample, uint32_t* dRngOut, hipStream_t stream) {
+    hipLaunchKernelGGL(k_debug_sample_lobes, dim3(std::max(1u, ceilDiv(n, 128))), dim3(128), 0, stream, dMaterial, rp, dIn, dFront, dRng, n, dOut, dSample,
+                       dRngOut);
+}
+
+void launchDebugEnvLookup(const RenderParams& rp, const SceneView& sc, const EnvLodView& env, const float4* dIn, uint64_t n, float4* dOut,
+                          hipStream_t stream) {
+    hipLaunchKernelGGL(k_debug_env_lookup, dim3(std::max(1u, ceilDiv(n, 128))), dim3(128), 0, stream, rp, sc, env, dIn, n, dOut);
 }
 
 void launchDebugTexSample(const SceneView& sc, uint32_t texture, const float* dIn, uint64_t n, float4* dOut, hipStream_t stream) {
