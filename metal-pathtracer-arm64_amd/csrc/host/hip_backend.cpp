@@ -642,22 +642,6 @@ void partitionPixels(uint32_t width, uint32_t height, uint32_t part, uint32_t pa
     }
 }
 
-struct EventTimer {
-    std::vector<hipEvent_t> events;
-    size_t used = 0;
-    ~EventTimer() {
-        for (hipEvent_t e : events) (void)hipEventDestroy(e);
-    }
-    hipEvent_t next() {
-        if (used == events.size()) {
-            hipEvent_t e;
-            HIP_CHECK(hipEventCreate(&e));
-            events.push_back(e);
-        }
-        return events[used++];
-    }
-};
-
 // Bytes the per-sample accumulators of one pass may take: a quarter of the device's TOTAL memory, at most 16 GiB.  Taken
 // from the device's size, never from what happens to be free: every rank of a multi-GPU render has to split a frame
 // into the same passes (k_resolve adds the per-pass sums in pass order), whatever else lives on its card.
@@ -665,15 +649,390 @@ uint64_t itemBudgetBytes(const PtrDeviceScene& ds) {
     return std::max<uint64_t>(64ull << 20, std::min<uint64_t>(16ull << 30, ds.deviceTotalBytes / 4u));
 }
 
+// Launch configuration of the one-off traversal kernels (ray batches, AOVs, debug queries): whole grid, group 0's heads and spill area
+LaunchConfig coldLaunchConfig(const PtrDeviceScene& ds) { return LaunchConfig{ds.traceGrid, ds.spill.ptr, ds.scalars.ptr + 1, ds.refillBelow}; }
+
+// Adds the per-launch figures of `b` to `a`: kernel times, k_extend launches, samples.
+void addLaunchStats(PtrRenderStats& a, const PtrRenderStats& b) {
+    a.traceKernelMs += b.traceKernelMs;
+    a.shadeKernelMs += b.shadeKernelMs;
+    a.shadowKernelMs += b.shadowKernelMs;
+    a.tailKernelMs += b.tailKernelMs;
+    a.traceLaunches += b.traceLaunches;
+    a.samples += b.samples;
+}
+
+// optional per-slot arrays: the ray cone of textured paths, the environment LOD of PTR_METAL_ENV_LOD with an environment map
+bool conePaths(const PtrDeviceScene& ds, const RenderParams& rp) { return (rp.mediaMode & PTR_METAL_PBR) && ds.view.textureCount > 0u; }
+bool envLodPaths(const PtrDeviceScene& ds, const RenderParams& rp) { return (rp.mediaMode & PTR_METAL_ENV_LOD) && ds.view.envWidth > 0u; }
+
+// Grows the buffers of a pool of `slots` path slots (and the frame's per-item ones) to this pass; slotRange lays them out.
+void sizeSlots(PtrDeviceScene& ds, const RenderParams& rp, bool count, uint32_t slots) {
+    ds.state.ensure(static_cast<size_t>(slots) * 4u);
+    ds.hit.ensure(slots);
+    ds.flushItem.ensure(slots);
+    if (count) ds.signature.ensure(slots);
+    if (ds.tailBelow > 0) {
+        ds.tailList.ensure(slots);
+        ds.tailWords.ensure(4);
+    }
+    ds.itemAccum.ensure(rp.itemCount);
+    ds.recBuf.ensure(static_cast<size_t>(slots) * kRecSlots * 4u);
+    ds.itemReserve.ensure((slots + 63u) / 64u);
+    if (rp.mediaMode & PTR_METAL_MEDIA) ds.medium.ensure(slots);
+    if (conePaths(ds, rp)) ds.cone.ensure(slots);
+    if (envLodPaths(ds, rp)) {   // the chain (first such render of the scene) and the paths' LOD
+        ensureEnvMips(ds);
+        ds.envLod.ensure(slots);
+    }
+    ds.itemHeads.ensure(kItemHeadWords);
+}
+
+// Slots [first, first + n) of the pool of `slots` slots that sizeSlots grew, and in `env` their environment LOD (all null without it).
+// The shared fields (work heads, item sums, pixel map, counters) are not offset.  The connect and busy lists stay null: a group sets
+// its own, and the whole pool ([0, slots): the tail kernels' view) probes the slots.
+PathPool slotRange(const PtrDeviceScene& ds, const RenderParams& rp, bool count, uint32_t slots, uint32_t first, uint32_t n, EnvLodView& env) {
+    PathPool p;
+    std::memset(&p, 0, sizeof(p));
+    float4* state = ds.state.ptr + first;
+    p.ray0 = state;
+    p.ray1 = state + slots;
+    p.thr = state + 2ull * slots;
+    p.accum = state + 3ull * slots;
+    p.hit = ds.hit.ptr + first;
+    p.flushItem = ds.flushItem.ptr + first;
+    p.signature = count ? ds.signature.ptr + first : nullptr;
+    p.medium = (rp.mediaMode & PTR_METAL_MEDIA) ? ds.medium.ptr + first : nullptr;
+    p.cone = conePaths(ds, rp) ? ds.cone.ptr + first : nullptr;
+    for (uint32_t k = 0; k < kRecSlots; ++k) {
+        float4* base = ds.recBuf.ptr + static_cast<size_t>(k) * 4u * slots + first;
+        p.rec[k] = ShadowRecordView{base, base + slots, base + 2ull * slots, base + 3ull * slots};
+    }
+    p.itemReserve = ds.itemReserve.ptr + first / 64u;
+    p.slots = n;
+    p.recStride = slots;
+    p.itemAccum = ds.itemAccum.ptr;
+    p.nextItem = ds.itemHeads.ptr;
+    p.pixelOfLocal = ds.pixelOfLocal.ptr;
+    p.counters = ds.counters.ptr;
+    p.zero = reinterpret_cast<const float4*>(ds.zeros.ptr);
+    env = EnvLodView{};
+    if (envLodPaths(ds, rp)) env = EnvLodView{ds.envMips.ptr, ds.envLod.ptr + first, ds.envMipLevels, 0u};
+    return p;
+}
+
+constexpr size_t kConnectCountWords = static_cast<size_t>(kConnectQueues) * kConnectCountStride;   // one set of sub-list counters
+
+// One group of the pool, driven through extend -> shade -> connect on its own stream (see makeGroups).
+struct PoolGroup {
+    PathPool pool;
+    EnvLodView env;
+    LaunchConfig cfg;
+    hipStream_t stream;
+    hipStream_t side = nullptr;   // k_connect's stream when it runs beside the next k_extend (null: on `stream`)
+    hipEvent_t shadeDone = nullptr, connectDone = nullptr;   // (with `side`) this iteration's k_shade / k_connect done
+    uint32_t* sideSpill = nullptr;   // (with `side`) spill area of k_connect
+    uint32_t* scalars;
+    bool done = false;
+    uint32_t feederChunk;   // slots per work-head atomic; grows as the group drains at the end of the frame
+    size_t listWords;       // words of one connect or busy list
+    uint32_t* connectCounts;   // two sets of sub-list counters, used in turn
+    // busy lists (end of the frame): two lists and three counter sets in rotation.  busyStage 0: the kernels walk the slots;
+    // 1: this iteration's k_shade (still walking the slots) fills the first list; 2: k_extend and k_shade walk the list of the
+    // previous iteration and k_shade fills the next one
+    uint32_t *busyLists, *busyCounts;
+    uint32_t busyStage = 0, busyTurn = 0;
+    bool shadeListed = false;
+
+    // The lists and counters of iteration `iteration`: the connect counters by its parity (k_shade clears the set of the next one);
+    // once the queue is dry, the busy lists move on by one turn per iteration.
+    void selectLists(uint64_t iteration, bool queueDry) {
+        pool.connectCount = connectCounts + kConnectCountWords * (iteration & 1u);
+        pool.connectClear = connectCounts + kConnectCountWords * ((iteration + 1u) & 1u);
+        if (busyStage != 0u) {   // the previous iteration's k_shade filled list busyTurn: walk it
+            busyStage = 2u;
+            ++busyTurn;
+        }
+        if (queueDry && busyStage == 0u) busyStage = 1u;   // the kernels decide per launch whether a list pays
+        if (busyStage == 0u) return;
+        // k_shade fills list `busyTurn` (counter set busyTurn % 3) and clears the set after it; in stage 2 this iteration's
+        // k_extend and k_shade walk the list the previous iteration filled
+        pool.busyOut = busyLists + listWords * (busyTurn & 1u);
+        pool.busyCountOut = busyCounts + kConnectCountWords * (busyTurn % 3u);
+        pool.busyCountClear = busyCounts + kConnectCountWords * ((busyTurn + 1u) % 3u);
+        if (busyStage == 2u) {
+            pool.busyIn = busyLists + listWords * ((busyTurn + 1u) & 1u);
+            pool.busyCountIn = busyCounts + kConnectCountWords * ((busyTurn + 2u) % 3u);
+        }
+    }
+
+    // A poll with the queue dry found `live` live slots in the group (baseChunk: the feeder chunk of a full pool).
+    void polledDry(uint32_t live, uint32_t baseChunk) {
+        if (live == 0u) done = true;
+        // the fewer live slots, the bigger the chunks the work list is claimed in (see WaveFeeder): a chunk
+        // should still hold about as many live slots as a full one does when the pool is full
+        // up to the point where the static first chunks of the resident waves cover the whole list and
+        // the head is not touched at all
+        const uint32_t thin = pool.slots / std::max(live, 1u);
+        const uint32_t waves = std::max(cfg.traceGrid * (kTraceGridUnit / 64u), 1u);
+        const uint32_t perWave = ((pool.slots + waves - 1u) / waves + 63u) / 64u * 64u;
+        const uint32_t cap = std::max(perWave, baseChunk);
+        feederChunk = std::min(cap, baseChunk * std::max(thin, 1u));
+        shadeListed = static_cast<uint64_t>(live) * 5u < static_cast<uint64_t>(pool.slots) * 2u;   // < 40 % live
+    }
+};
+
+// Streams and events of `groupCount` groups (group 0 runs on the caller's stream), with `overlap` a side stream and two events each.
+void ensureGroupStreams(PtrDeviceScene& ds, uint32_t groupCount, bool overlap) {
+    auto newStream = [] { hipStream_t st; HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking)); return st; };
+    auto newEvent = [] { hipEvent_t e; HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); return e; };
+    while (ds.groupStreams.size() + 1 < groupCount) ds.groupStreams.push_back(newStream());
+    while (ds.groupEvents.size() < groupCount + 1) ds.groupEvents.push_back(newEvent());
+    while (overlap && ds.sideStreams.size() < groupCount) {
+        ds.sideStreams.push_back(newStream());
+        ds.sideEvents.push_back(newEvent());
+        ds.sideEvents.push_back(newEvent());
+    }
+}
+
+// The pool is cut into independent groups, each driven through extend -> shade -> connect on its own HIP
+// stream.  Every launch of the persistent traversal kernels ends with a drain phase (the last rays of the
+// last chunks, few lanes busy); with two groups in flight the other group's kernels fill the CUs a draining
+// kernel leaves idle.  Groups share only the work-item head (one atomic per 64 items), so results do not
+// depend on how they interleave.
+std::vector<PoolGroup> makeGroups(PtrDeviceScene& ds, const RenderParams& rp, bool count, bool soloGroup, uint32_t slots, hipStream_t stream) {
+    const uint32_t wantGroups = ds.poolGroups ? ds.poolGroups : (slots > (8u << 20) ? 2u : 4u);
+    uint32_t groupCount = std::min<uint32_t>(soloGroup ? 1u : wantGroups, std::max<uint32_t>(1u, slots >> 20));   // >= 1 Mi slots per group
+    const uint32_t groupSlots = ((slots + groupCount - 1u) / groupCount + 255u) & ~255u;
+    groupCount = (slots + groupSlots - 1u) / groupSlots;
+    // k_connect beside the next k_extend: only while the streams fit the hardware queues (two groups at most), and never in a solo
+    // render, whose point is kernels that do not overlap
+    const bool overlap = ds.connectOverlap && !soloGroup && groupCount <= 2u;
+    ensureGroupStreams(ds, groupCount, overlap);
+    const size_t spillWords = spillWordsPerGroup(ds);
+    // connect lists: sub-list w % 64 takes the entries of k_shade's wave w, at most 64 each
+    const uint32_t connectRegion = ((groupSlots + 63u) / 64u + kConnectQueues - 1u) / kConnectQueues * 64u;
+    const size_t connectListWords = static_cast<size_t>(connectRegion) * kConnectQueues;
+    if (slots >= (1u << kConnectMaskShift)) throw HipError{"path-slot pool too large for the connect lists"};   // (the pool is capped at 64 Mi slots)
+    ds.connectList.ensure(connectListWords * groupCount);
+    ds.connectCounts.ensure(kConnectCountWords * 2u * kMaxPoolGroups);
+    ds.busyLists.ensure(connectListWords * 2u * groupCount);
+    ds.busyCounts.ensure(kConnectCountWords * 3u * kMaxPoolGroups);
+    std::vector<PoolGroup> groups(groupCount);
+    for (uint32_t g = 0; g < groupCount; ++g) {
+        PoolGroup& gr = groups[g];
+        const uint32_t first = g * groupSlots;
+        gr.pool = slotRange(ds, rp, count, slots, first, std::min(groupSlots, slots - first), gr.env);
+        gr.pool.connectList = ds.connectList.ptr + connectListWords * g;
+        gr.pool.connectRegion = connectRegion;
+        gr.listWords = connectListWords;
+        gr.connectCounts = ds.connectCounts.ptr + kConnectCountWords * 2u * g;
+        gr.busyLists = ds.busyLists.ptr + connectListWords * 2u * g;
+        gr.busyCounts = ds.busyCounts.ptr + kConnectCountWords * 3u * g;
+        gr.scalars = ds.scalars.ptr + static_cast<size_t>(g) * kScalarCount;
+        const bool sideBySide = groupCount > 1 && gr.pool.slots >= kHalfGridGroupSlots;
+        gr.cfg = LaunchConfig{sideBySide ? ds.traceGridHalf : ds.traceGrid, ds.spill.ptr + g * spillWords, gr.scalars + 1, ds.refillBelow};
+        gr.stream = g == 0 ? stream : ds.groupStreams[g - 1];
+        gr.feederChunk = ds.feederChunk;
+        if (overlap) {
+            gr.side = ds.sideStreams[g];
+            gr.shadeDone = ds.sideEvents[2 * g];
+            gr.connectDone = ds.sideEvents[2 * g + 1];
+            gr.sideSpill = ds.spill.ptr + (ds.maxPoolGroups() + g) * spillWords;
+        }
+    }
+    return groups;
+}
+
+// first index of work-item range k (its head's value before any claim)
+uint64_t itemRangeStart(const RenderParams& rp, uint32_t k) {
+    return std::min<uint64_t>(static_cast<uint64_t>(rp.itemHeadFirst) + static_cast<uint64_t>(k) * rp.itemsPerHead, rp.itemCount);
+}
+
+// Phase 1: while unclaimed work items remain nobody needs to count survivors; the host looks at the item head
+// only when it expects it to be nearly exhausted (items are claimed at a steady rate, so after the first look the
+// next one is scheduled at 3/4 of the predicted remaining iterations).  Phase 2 (queue dry): k_shade counts live
+// slots and every group is polled every 4 iterations until it has none left (k_extend reports how many live
+// slots it traced: one atomic per persistent wave).  A poll joins all streams, which
+// costs the overlap between groups once; polling every 4 iterations throughout was 5 % slower.  (Polling through
+// events without joining was tried: the host then runs up to a dozen empty iterations past the end - no gain.)
+constexpr uint64_t kPollEvery = 4;
+constexpr uint64_t kPollDry = 2;   // once the queue is dry: how often the live slots are counted (the hand-over to the tail kernels hangs on it)
+
+// allDone: no group has a live slot left; runTail: the last paths go to the tail kernels; queueDry: every work item is claimed;
+// nextCheck: the iteration of the next poll
+struct PollResult {
+    bool allDone, runTail, queueDry;
+    uint64_t nextCheck;
+};
+
+// A poll after `iterations` iterations: the range heads (queue not dry) or the groups' live-slot counts are copied to the host, the
+// streams joined, and the groups updated.
+PollResult poll(PtrDeviceScene& ds, std::vector<PoolGroup>& groups, const RenderParams& rp, uint32_t slots, uint64_t iterations, bool queueDry,
+                bool tracePolls) {
+    HIP_CHECK(hipGetLastError());   // a launch that failed (bad configuration, out of resources) must not pass for a slow frame
+    const uint32_t ring = static_cast<uint32_t>((iterations - 1u) % kAliveRing);   // the live-slot counters of the last iteration
+    bool headsCopied = false;
+    for (uint32_t g = 0; g < groups.size(); ++g) {
+        PoolGroup& gr = groups[g];
+        if (gr.done) continue;
+        if (queueDry) {
+            HIP_CHECK(hipMemcpyAsync(ds.pinnedAlive + g, gr.scalars + kAliveBase + ring, sizeof(uint32_t), hipMemcpyDeviceToHost, gr.stream));
+        } else if (!headsCopied) {
+            HIP_CHECK(hipMemcpy2DAsync(ds.pinnedAlive + kPinnedHeadsOffset, sizeof(uint32_t), ds.itemHeads.ptr, sizeof(uint32_t) * kItemHeadStride,
+                                       sizeof(uint32_t), kItemHeads, hipMemcpyDeviceToHost, gr.stream));
+            headsCopied = true;
+        }
+    }
+    PollResult r{true, false, queueDry, 0};
+    uint64_t live = 0;
+    for (uint32_t g = 0; g < groups.size(); ++g) {
+        PoolGroup& gr = groups[g];
+        if (gr.done) continue;
+        HIP_CHECK(hipStreamSynchronize(gr.stream));
+        if (queueDry) {
+            if (tracePolls) {
+                std::fprintf(stderr, "[poll] iteration %llu group %u live %u of %u chunk %u\n", static_cast<unsigned long long>(iterations), g,
+                             ds.pinnedAlive[g], gr.pool.slots, gr.feederChunk);
+            }
+            gr.polledDry(ds.pinnedAlive[g], ds.feederChunk);
+            if (!gr.done) live += ds.pinnedAlive[g];
+        }
+        r.allDone = r.allDone && gr.done;
+    }
+    if (queueDry && !r.allDone && ds.tailBelow > 0 && live <= ds.tailBelow) r.runTail = true;
+    if (r.allDone || r.runTail) return r;
+    r.nextCheck = iterations + (queueDry && ds.tailBelow > 0 ? kPollDry : kPollEvery);
+    if (!queueDry) {
+        uint64_t head = slots;   // items claimed so far = pre-assigned + what every range head has handed out
+        const uint32_t* heads = ds.pinnedAlive + kPinnedHeadsOffset;
+        for (uint32_t k = 0; k < kItemHeads; ++k) {
+            const uint64_t lo = itemRangeStart(rp, k);
+            const uint64_t hi = std::min<uint64_t>(lo + rp.itemsPerHead, rp.itemCount);
+            head += std::min<uint64_t>(std::max<uint64_t>(heads[k], lo), hi) - lo;
+        }
+        if (head >= rp.itemCount) {
+            r.queueDry = true;
+        } else if (head > slots) {
+            const double perIteration = static_cast<double>(head - slots) / static_cast<double>(iterations);
+            const double left = static_cast<double>(rp.itemCount - head) / std::max(perIteration, 1.0);
+            r.nextCheck = iterations + std::max<uint64_t>(kPollEvery, static_cast<uint64_t>(left * 0.75));
+        }
+    }
+    return r;
+}
+
+enum class SpanKind : int { Extend = 0, Shade = 1, Connect = 2, Tail = 3 };   // the `kind` of a [launch] line
+
+// Start and end events around the launches of a timed pass.
+struct LaunchTimer {
+    struct Span {
+        hipEvent_t a, b;   // null until created
+        SpanKind kind;
+        const void* stream;
+    };
+    bool on = false;
+    std::vector<Span> spans;
+    ~LaunchTimer() {
+        for (const Span& s : spans) {
+            for (hipEvent_t e : {s.a, s.b}) if (e) (void)hipEventDestroy(e);
+        }
+    }
+    template <typename F>
+    void launch(SpanKind kind, hipStream_t st, F&& fn) {
+        if (!on) {
+            fn();
+            return;
+        }
+        spans.push_back(Span{nullptr, nullptr, kind, st});
+        Span& s = spans.back();
+        HIP_CHECK(hipEventCreate(&s.a));
+        HIP_CHECK(hipEventCreate(&s.b));
+        HIP_CHECK(hipEventRecord(s.a, st));
+        fn();
+        HIP_CHECK(hipEventRecord(s.b, st));
+    }
+};
+
+// The figures of a finished pass: wall time, kernel times from the launch spans, the counters of a counting pass, and the
+// PTR_VERBOSE=launches / steps reports (tools/launch_timeline.py and tools/steps_probe.py parse them).
+void passStats(const PtrDeviceScene& ds, const RenderParams& rp, const std::vector<LaunchTimer::Span>& spans, bool count, const ptr::Knobs& knobs,
+               double seconds, PtrRenderStats& stats) {
+    std::memset(&stats, 0, sizeof(stats));
+    stats.totalSeconds = seconds;
+    stats.avgMsPerSample = seconds * 1000.0 / rp.spp;
+    stats.uploadSeconds = ds.uploadSeconds;
+    stats.samples = static_cast<uint64_t>(rp.localPixels) * rp.spp;
+    if (knobs.verboseLaunches && !spans.empty()) {   // debugging aid: when each launch ran (ms from the first)
+        for (const LaunchTimer::Span& s : spans) {
+            float t0 = 0.0f, t1 = 0.0f;
+            HIP_CHECK(hipEventElapsedTime(&t0, spans.front().a, s.a));
+            HIP_CHECK(hipEventElapsedTime(&t1, spans.front().a, s.b));
+            std::fprintf(stderr, "[launch] kind %d  start %.3f  end %.3f  (%.3f ms)  stream %p\n", static_cast<int>(s.kind), t0, t1, t1 - t0, s.stream);
+        }
+    }
+    for (const LaunchTimer::Span& s : spans) {
+        float ms = 0.0f;
+        HIP_CHECK(hipEventElapsedTime(&ms, s.a, s.b));
+        switch (s.kind) {
+            case SpanKind::Extend: stats.traceKernelMs += ms; ++stats.traceLaunches; break;
+            case SpanKind::Shade: stats.shadeKernelMs += ms; break;
+            case SpanKind::Connect: stats.shadowKernelMs += ms; break;
+            case SpanKind::Tail: stats.tailKernelMs += ms; break;
+        }
+    }
+    if (!count) return;
+    uint64_t c[kCounterSlots];
+    HIP_CHECK(hipMemcpy(c, ds.counters.ptr, sizeof(c), hipMemcpyDeviceToHost));
+    stats.primaryRays = c[kCntPrimaryRays];
+    stats.extendRays = c[kCntExtendRays];
+    stats.shadowRays = c[kCntShadowRays];
+    stats.extendNodesVisited = c[kCntExtendNodes];
+    stats.extendLeafPrimTests = c[kCntExtendPrims];
+    stats.nodesVisited = c[kCntExtendNodes] + c[kCntShadowNodes];
+    stats.leafPrimTests = c[kCntExtendPrims] + c[kCntShadowPrims];
+    stats.shadedHits = c[kCntShadedHits];
+    stats.triangleHits = c[kCntTriangleHits];
+    stats.shadowEarlyExits = c[kCntShadowEarlyExit];
+    if (!knobs.verboseSteps) return;
+    // lane utilisation of k_extend's step loop (counting build)
+    const double nodeLanes = static_cast<double>(c[kCntExtendNodes] - c[kCntExtendLeaves]), primLanes = static_cast<double>(c[kCntExtendPrims]);
+    const double nodeSlots = static_cast<double>(c[kCntExtendWaveNodeSteps]), primSlots = static_cast<double>(c[kCntExtendWavePrimSteps]);
+    std::fprintf(stderr, "[steps] k_extend: %.3g rays; node steps %.3g lane / %.3g slots = %.3f; prim steps %.3g lane / %.3g slots = %.3f; "
+                         "refill passes %.3g (x64 lanes)\n",
+                 static_cast<double>(c[kCntExtendRays]), nodeLanes, nodeSlots, nodeLanes / std::max(nodeSlots, 1.0), primLanes, primSlots,
+                 primLanes / std::max(primSlots, 1.0), static_cast<double>(c[kCntExtendRefillPasses]));
+    const double votes = static_cast<double>(c[kCntExtendVoteIterations]) / 64.0;
+    std::fprintf(stderr, "[steps] k_extend: %.3g vote iterations; lanes holding a ray %.1f / 64 on average, of which at a leaf %.1f\n", votes,
+                 static_cast<double>(c[kCntExtendActiveLanes]) / std::max(votes, 1.0), static_cast<double>(c[kCntExtendLeafLanes]) / std::max(votes, 1.0));
+    const double shadeLanes = std::max(static_cast<double>(c[kCntShadeWaves]), 1.0);
+    std::fprintf(stderr, "[steps] k_shade: %.3g wave visits; share of their lanes at each stage: ray traced %.3f, surface hit %.3f, of which a light "
+                         "%.3f; light sample evaluated %.3f, tested against the light's own triangles %.3f, shadow ray queued %.3f; BSDF sampled "
+                         "%.3f; new work item wanted %.3f\n",
+                 shadeLanes / 64.0, c[kCntShadeAlive] / shadeLanes, c[kCntShadeSurface] / shadeLanes, c[kCntShadeEmitter] / shadeLanes,
+                 c[kCntShadeLightEval] / shadeLanes, c[kCntShadeLightPretest] / shadeLanes, c[kCntShadeLightStored] / shadeLanes,
+                 c[kCntShadeBsdfSample] / shadeLanes, c[kCntShadeNeedItem] / shadeLanes);
+    static const char* names[kShadeParts] = {"loads + landing", "background", "surface reconstruction", "emitter", "light sample", "env sample",
+                                             "BSDF sample + next ray", "work item + camera ray", "stores + lists", "subsurface walk"};
+    double waveTotal = 0.0;
+    for (uint32_t k = 0; k < kShadeParts; ++k) waveTotal += static_cast<double>(c[kCntShadeWaveTicks + k]);
+    std::fprintf(stderr, "[steps] k_shade parts (clock ticks between the part's first and last instruction, waits included): share of the waves' time | lanes busy\n");
+    for (uint32_t k = 0; k < kShadeParts; ++k) {
+        const double wave = static_cast<double>(c[kCntShadeWaveTicks + k]), lane = static_cast<double>(c[kCntShadeLaneTicks + k]);
+        if (wave <= 0.0) continue;
+        std::fprintf(stderr, "[steps]   %-24s %5.1f %% | %.3f\n", names[k], 100.0 * wave / std::max(waveTotal, 1.0), lane / (64.0 * wave));
+    }
+    std::fprintf(stderr, "[steps] k_extend: refill passes take %.1f %% of the waves' time in the kernel\n",
+                 100.0 * static_cast<double>(c[kCntExtendRefillTicks]) / std::max(static_cast<double>(c[kCntExtendWaveTicks]), 1.0));
+}
+
 // One pass over `spp` samples per pixel starting at sample `sampleBase` of a frame of `sppTotal`; passFlags bit 0 = first pass of
 // the frame (output and counters start from zero), bit 1 = last pass (the running sum in dOut is divided by sppTotal).
+// (renderBands has checked the size and the partition, and selected the device.)
 void renderPass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, uint32_t sampleBase, uint32_t sppTotal, uint32_t passFlags,
                 uint32_t part, uint32_t parts, float* dOut, hipStream_t stream, int mode, PtrRenderStats* stats) {
     const bool count = (mode & 1) != 0;         // counting instantiation of the kernels
     const bool soloGroup = (mode & 2) != 0;     // one pool group: kernels run alone, for clean per-kernel timings
-    if (settings.width == 0 || settings.height == 0) throw HipError{"render size must be non-zero"};
-    if (parts == 0 || part >= parts) throw HipError{"bad partition"};
-    HIP_CHECK(hipSetDevice(ds.device));
 
     RenderParams rp;
     fillRenderParams(settings, spp, rp);
@@ -722,188 +1081,22 @@ void renderPass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, u
     rp.itemHeadFirst = slots;
     rp.itemsPerHead = static_cast<uint32_t>(((itemCount64 - slots + kItemHeads - 1u) / kItemHeads + 63u) & ~63ull);
 
-    ds.state.ensure(static_cast<size_t>(slots) * 4u);
-    ds.hit.ensure(slots);
-    ds.flushItem.ensure(slots);
-    if (count) ds.signature.ensure(slots);
-    if (ds.tailBelow > 0) {
-        ds.tailList.ensure(slots);
-        ds.tailWords.ensure(4);
-    }
-    ds.itemAccum.ensure(rp.itemCount);
-    ds.recBuf.ensure(static_cast<size_t>(slots) * kRecSlots * 4u);
-    ds.itemReserve.ensure((slots + 63u) / 64u);
-    if (rp.mediaMode & PTR_METAL_MEDIA) ds.medium.ensure(slots);
-    const bool texturedPaths = (rp.mediaMode & PTR_METAL_PBR) && ds.view.textureCount > 0u;   // the paths carry a ray cone
-    if (texturedPaths) ds.cone.ensure(slots);
-    // PTR_METAL_ENV_LOD with an environment map: the chain (first such render of the scene) and the paths' LOD
-    EnvLodView env{};
-    if ((rp.mediaMode & PTR_METAL_ENV_LOD) && ds.view.envWidth > 0u) {
-        ensureEnvMips(ds);
-        ds.envLod.ensure(slots);
-        env.mips = ds.envMips.ptr;
-        env.slotLod = ds.envLod.ptr;
-        env.levels = ds.envMipLevels;
-    }
-
-    PathPool pool;
-    std::memset(&pool, 0, sizeof(pool));
-    pool.ray0 = ds.state.ptr;
-    pool.ray1 = ds.state.ptr + slots;
-    pool.thr = ds.state.ptr + 2ull * slots;
-    pool.accum = ds.state.ptr + 3ull * slots;
-    pool.hit = ds.hit.ptr;
-    pool.flushItem = ds.flushItem.ptr;
-    pool.signature = count ? ds.signature.ptr : nullptr;
-    pool.medium = (rp.mediaMode & PTR_METAL_MEDIA) ? ds.medium.ptr : nullptr;
-    pool.cone = texturedPaths ? ds.cone.ptr : nullptr;
-    pool.itemAccum = ds.itemAccum.ptr;
-    ds.itemHeads.ensure(kItemHeadWords);
-    pool.nextItem = ds.itemHeads.ptr;
-    for (uint32_t k = 0; k < kRecSlots; ++k) {
-        float4* base = ds.recBuf.ptr + static_cast<size_t>(k) * 4u * slots;
-        pool.rec[k].org = base;
-        pool.rec[k].dir = base + slots;
-        pool.rec[k].a = base + 2ull * slots;
-        pool.rec[k].b = base + 3ull * slots;
-    }
-    pool.itemReserve = ds.itemReserve.ptr;
-    pool.pixelOfLocal = ds.pixelOfLocal.ptr;
-    pool.counters = ds.counters.ptr;
-    pool.zero = reinterpret_cast<const float4*>(ds.zeros.ptr);
-    pool.slots = slots;
-    pool.recStride = slots;
-
-    // The pool is cut into independent groups, each driven through extend -> shade -> connect on its own HIP
-    // stream.  Every launch of the persistent traversal kernels ends with a drain phase (the last rays of the
-    // last chunks, few lanes busy); with two groups in flight the other group's kernels fill the CUs a draining
-    // kernel leaves idle.  Groups share only the work-item head (one atomic per 64 items), so results do not
-    // depend on how they interleave.
-    struct Group {
-        PathPool pool;
-        EnvLodView env;
-        LaunchConfig cfg;
-        hipStream_t stream;
-        uint32_t* scalars;
-        bool done;
-        uint32_t feederChunk;   // slots per work-head atomic; grows as the group drains at the end of the frame
-        uint32_t* connectCounts = nullptr;   // two sets of sub-list counters, used in turn
-        // busy lists (end of the frame): two lists and three counter sets in rotation.  busyStage 0: the kernels walk the slots;
-        // 1: this iteration's k_shade (still walking the slots) fills the first list; 2: k_extend and k_shade walk the list of the
-        // previous iteration and k_shade fills the next one
-        uint32_t* busyLists = nullptr;
-        uint32_t* busyCounts = nullptr;
-        uint32_t busyStage = 0, busyTurn = 0;
-        bool shadeListed = false;
-    };
-    const uint32_t wantGroups = ds.poolGroups ? ds.poolGroups : (slots > (8u << 20) ? 2u : 4u);
-    uint32_t groupCount = std::min<uint32_t>(soloGroup ? 1u : wantGroups, std::max<uint32_t>(1u, slots >> 20));   // >= 1 Mi slots per group
-    const uint32_t groupSlots = ((slots + groupCount - 1u) / groupCount + 255u) & ~255u;
-    groupCount = (slots + groupSlots - 1u) / groupSlots;
-    while (ds.groupStreams.size() + 1 < groupCount) {
-        hipStream_t st;
-        HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        ds.groupStreams.push_back(st);
-    }
-    while (ds.groupEvents.size() < groupCount + 1) {
-        hipEvent_t e;
-        HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        ds.groupEvents.push_back(e);
-    }
-    const size_t spillWords = spillWordsPerGroup(ds);
-    // k_connect beside the next k_extend: only while the streams fit the hardware queues (two groups at most), and never in a solo
-    // render, whose point is kernels that do not overlap
-    const bool overlap = ds.connectOverlap && !soloGroup && groupCount <= 2u;
-    while (overlap && ds.sideStreams.size() < groupCount) {
-        hipStream_t st;
-        HIP_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        ds.sideStreams.push_back(st);
-        for (int k = 0; k < 2; ++k) {
-            hipEvent_t e;
-            HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            ds.sideEvents.push_back(e);
-        }
-    }
-    // connect lists: sub-list w % 64 takes the entries of k_shade's wave w, at most 64 each
-    const uint32_t connectRegion = ((groupSlots + 63u) / 64u + kConnectQueues - 1u) / kConnectQueues * 64u;
-    const size_t connectListWords = static_cast<size_t>(connectRegion) * kConnectQueues;
-    const size_t connectCountWords = static_cast<size_t>(kConnectQueues) * kConnectCountStride;   // one set
-    if (slots >= (1u << kConnectMaskShift)) throw HipError{"path-slot pool too large for the connect lists"};   // (the pool is capped at 64 Mi slots)
-    ds.connectList.ensure(connectListWords * groupCount);
-    ds.connectCounts.ensure(connectCountWords * 2u * kMaxPoolGroups);
-    ds.busyLists.ensure(connectListWords * 2u * groupCount);
-    ds.busyCounts.ensure(connectCountWords * 3u * kMaxPoolGroups);
-    std::vector<Group> groups(groupCount);
-    for (uint32_t g = 0; g < groupCount; ++g) {
-        Group& gr = groups[g];
-        const uint32_t first = g * groupSlots;
-        gr.pool = pool;
-        gr.pool.ray0 += first;
-        gr.pool.ray1 += first;
-        gr.pool.hit += first;
-        gr.pool.thr += first;
-        gr.pool.accum += first;
-        gr.pool.flushItem += first;
-        if (gr.pool.signature) gr.pool.signature += first;
-        if (gr.pool.medium) gr.pool.medium += first;
-        if (gr.pool.cone) gr.pool.cone += first;
-        gr.env = env;
-        if (gr.env.slotLod) gr.env.slotLod += first;
-        for (uint32_t k = 0; k < kRecSlots; ++k) {
-            gr.pool.rec[k].org += first;
-            gr.pool.rec[k].dir += first;
-            gr.pool.rec[k].a += first;
-            gr.pool.rec[k].b += first;
-        }
-        gr.pool.itemReserve += first / 64u;
-        gr.pool.slots = std::min(groupSlots, slots - first);
-        gr.pool.connectList = ds.connectList.ptr + connectListWords * g;
-        gr.pool.connectRegion = connectRegion;
-        gr.connectCounts = ds.connectCounts.ptr + connectCountWords * 2u * g;
-        gr.busyLists = ds.busyLists.ptr + connectListWords * 2u * g;
-        gr.busyCounts = ds.busyCounts.ptr + connectCountWords * 3u * g;
-        gr.scalars = ds.scalars.ptr + static_cast<size_t>(g) * kScalarCount;
-        const bool sideBySide = groupCount > 1 && gr.pool.slots >= kHalfGridGroupSlots;
-        gr.cfg = LaunchConfig{sideBySide ? ds.traceGridHalf : ds.traceGrid, ds.spill.ptr + g * spillWords, gr.scalars + 1, ds.refillBelow};
-        gr.stream = g == 0 ? stream : ds.groupStreams[g - 1];
-        gr.done = false;
-        gr.feederChunk = ds.feederChunk;
-    }
-
-    const bool timed = stats != nullptr;
-    EventTimer timer;
-    struct Span {
-        hipEvent_t a, b;
-        int kind;
-        const void* stream;
-    };
-    std::vector<Span> spans;
-    auto timedLaunch = [&](int kind, hipStream_t st, auto&& fn) {
-        if (timed) {
-            const hipEvent_t a = timer.next(), b = timer.next();
-            HIP_CHECK(hipEventRecord(a, st));
-            fn();
-            HIP_CHECK(hipEventRecord(b, st));
-            spans.push_back({a, b, kind, st});
-        } else {
-            fn();
-        }
-    };
+    sizeSlots(ds, rp, count, slots);
+    EnvLodView env;
+    const PathPool pool = slotRange(ds, rp, count, slots, 0u, slots, env);
+    std::vector<PoolGroup> groups = makeGroups(ds, rp, count, soloGroup, slots, stream);
+    LaunchTimer timer{stats != nullptr};
 
     if (count && (passFlags & 1u)) HIP_CHECK(hipMemsetAsync(ds.counters.ptr, 0, sizeof(uint64_t) * kCounterSlots, stream));   // counters add up over the passes
     HIP_CHECK(hipMemsetAsync(ds.scalars.ptr, 0, sizeof(uint32_t) * kScalarCount * kMaxPoolGroups, stream));
-    HIP_CHECK(hipMemsetAsync(ds.connectCounts.ptr, 0, sizeof(uint32_t) * connectCountWords * 2u * kMaxPoolGroups, stream));
-    HIP_CHECK(hipMemsetAsync(ds.busyCounts.ptr, 0, sizeof(uint32_t) * connectCountWords * 3u * kMaxPoolGroups, stream));
-    {
-        uint32_t* heads = ds.pinnedAlive + kPinnedHeadsOffset;
-        for (uint32_t k = 0; k < kItemHeads; ++k) {
-            heads[k] = static_cast<uint32_t>(std::min<uint64_t>(static_cast<uint64_t>(rp.itemHeadFirst) + static_cast<uint64_t>(k) * rp.itemsPerHead, rp.itemCount));
-        }
-        HIP_CHECK(hipMemsetAsync(pool.nextItem, 0, sizeof(uint32_t) * kItemHeadWords, stream));
-        HIP_CHECK(hipMemcpy2DAsync(pool.nextItem, sizeof(uint32_t) * kItemHeadStride, heads, sizeof(uint32_t), sizeof(uint32_t), kItemHeads,
-                                   hipMemcpyHostToDevice, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));   // the pinned staging area is reused by the polls below
-    }
+    HIP_CHECK(hipMemsetAsync(ds.connectCounts.ptr, 0, sizeof(uint32_t) * kConnectCountWords * 2u * kMaxPoolGroups, stream));
+    HIP_CHECK(hipMemsetAsync(ds.busyCounts.ptr, 0, sizeof(uint32_t) * kConnectCountWords * 3u * kMaxPoolGroups, stream));
+    uint32_t* heads = ds.pinnedAlive + kPinnedHeadsOffset;
+    for (uint32_t k = 0; k < kItemHeads; ++k) heads[k] = static_cast<uint32_t>(itemRangeStart(rp, k));
+    HIP_CHECK(hipMemsetAsync(pool.nextItem, 0, sizeof(uint32_t) * kItemHeadWords, stream));
+    HIP_CHECK(hipMemcpy2DAsync(pool.nextItem, sizeof(uint32_t) * kItemHeadStride, heads, sizeof(uint32_t), sizeof(uint32_t), kItemHeads,
+                               hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipStreamSynchronize(stream));   // the pinned staging area is reused by the polls
     HIP_CHECK(hipMemsetAsync(ds.itemReserve.ptr, 0, sizeof(uint2) * ((slots + 63u) / 64u), stream));
     if (rp.maxDepth == 0) HIP_CHECK(hipMemsetAsync(ds.itemAccum.ptr, 0, sizeof(float4) * rp.itemCount, stream));
 
@@ -911,238 +1104,66 @@ void renderPass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, u
     launchGenerate(rp, pool, stream);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(ds.groupEvents[0], stream));
-    for (uint32_t g = 1; g < groupCount; ++g) HIP_CHECK(hipStreamWaitEvent(groups[g].stream, ds.groupEvents[0], 0));
+    for (size_t g = 1; g < groups.size(); ++g) HIP_CHECK(hipStreamWaitEvent(groups[g].stream, ds.groupEvents[0], 0));
     uint64_t iterations = 0;
     // Worst case: every sample runs maxDepth bounces in sequence on its slot.
     // (a subsurface random walk adds up to sssMaxSteps iterations to a bounce)
     const uint64_t perBounce = ((rp.mediaMode & PTR_METAL_SSS) && rp.sssMode == 2u && ds.hasRandomWalkMaterial) ? 1ull + rp.sssMaxSteps : 1ull;
     const uint64_t maxIterations = static_cast<uint64_t>(rp.maxDepth) * perBounce * ((itemCount64 + slots - 1) / slots + 1) + 8;
-    // Phase 1: while unclaimed work items remain nobody needs to count survivors; the host looks at the item head
-    // only when it expects it to be nearly exhausted (items are claimed at a steady rate, so after the first look the
-    // next one is scheduled at 3/4 of the predicted remaining iterations).  Phase 2 (queue dry): k_shade counts live
-    // slots and every group is polled every 4 iterations until it has none left (k_extend reports how many live
-    // slots it traced: one atomic per persistent wave).  A poll joins all streams, which
-    // costs the overlap between groups once; polling every 4 iterations throughout was 5 % slower.  (Polling through
-    // events without joining was tried: the host then runs up to a dozen empty iterations past the end - no gain.)
-    constexpr uint64_t kPollEvery = 4;
-    constexpr uint64_t kPollDry = 2;   // once the queue is dry: how often the live slots are counted (the hand-over to the tail kernels hangs on it)
     const ptr::Knobs knobs = ptr::readKnobs();
-    const bool tracePolls = knobs.verbosePolls;   // debugging aid: live slots per poll
-    uint64_t nextCheck = kPollEvery;
-    bool queueDry = false;
-    bool runTail = false;   // the last paths are handed to the tail kernels
+    PollResult last{false, false, false, kPollEvery};   // what the last poll found (none yet)
     while (rp.maxDepth > 0) {
         const uint32_t ring = static_cast<uint32_t>(iterations % kAliveRing);
-        for (Group& gr : groups) {
+        const bool queueDry = last.queueDry;
+        for (PoolGroup& gr : groups) {
             if (gr.done) continue;
             uint32_t* aliveSlot = gr.scalars + kAliveBase + ring;
             gr.cfg.feederChunk = gr.feederChunk;
             // work heads and the next live-slot counter are cleared by k_shade (all zero at the start of the frame)
             const ShadeResets resets{gr.scalars + 1, gr.scalars + 2, gr.scalars + kAliveBase + (ring + 1u) % kAliveRing,
                                      (queueDry && gr.feederChunk > ds.feederChunk) ? 1u : 0u};
-            {   // this iteration's counters, and the set k_shade clears for the next one
-                gr.pool.connectCount = gr.connectCounts + connectCountWords * (iterations & 1u);
-                gr.pool.connectClear = gr.connectCounts + connectCountWords * ((iterations + 1u) & 1u);
-            }
-            if (queueDry && gr.busyStage == 0u) gr.busyStage = 1u;   // the kernels decide per launch whether a list pays
-            if (gr.busyStage != 0u) {
-                // k_shade fills list `busyTurn` (counter set busyTurn % 3) and clears the set after it; in stage 2 this iteration's
-                // k_extend and k_shade walk the list the previous iteration filled
-                const uint32_t turn = gr.busyTurn;
-                gr.pool.busyOut = gr.busyLists + connectListWords * (turn & 1u);
-                gr.pool.busyCountOut = gr.busyCounts + connectCountWords * (turn % 3u);
-                gr.pool.busyCountClear = gr.busyCounts + connectCountWords * ((turn + 1u) % 3u);
-                if (gr.busyStage == 2u) {
-                    gr.pool.busyIn = gr.busyLists + connectListWords * ((turn + 1u) & 1u);
-                    gr.pool.busyCountIn = gr.busyCounts + connectCountWords * ((turn + 2u) % 3u);
-                }
-            }
-            timedLaunch(0, gr.stream, [&] { launchExtend(ds.view, gr.pool, gr.cfg, queueDry ? aliveSlot : nullptr, count, gr.stream); });
+            gr.selectLists(iterations, queueDry);
+            timer.launch(SpanKind::Extend, gr.stream, [&] { launchExtend(ds.view, gr.pool, gr.cfg, queueDry ? aliveSlot : nullptr, count, gr.stream); });
             // k_shade's list instantiation claims leftover work items lane by lane and is a fifth slower than the plain kernel while
             // it still walks the slots: it is launched once the last count of live slots says its list is about to pay
             PathPool shadePool = gr.pool;
             if (!gr.shadeListed) shadePool.busyIn = nullptr;
-            if (overlap && iterations > 0) HIP_CHECK(hipStreamWaitEvent(gr.stream, ds.sideEvents[2 * static_cast<uint32_t>(&gr - groups.data()) + 1], 0));
-            timedLaunch(1, gr.stream, [&] { launchShade(rp, ds.view, shadePool, resets, gr.env, count, gr.stream); });
-            if (overlap) {
+            if (gr.side && iterations > 0) HIP_CHECK(hipStreamWaitEvent(gr.stream, gr.connectDone, 0));
+            timer.launch(SpanKind::Shade, gr.stream, [&] { launchShade(rp, ds.view, shadePool, resets, gr.env, count, gr.stream); });
+            if (gr.side) {
                 // k_connect of this iteration on the side stream, after this k_shade; the next k_shade waits for it (above)
-                const uint32_t gi = static_cast<uint32_t>(&gr - groups.data());
-                hipStream_t side = ds.sideStreams[gi];
-                HIP_CHECK(hipEventRecord(ds.sideEvents[2 * gi], gr.stream));          // shade(i) done
-                HIP_CHECK(hipStreamWaitEvent(side, ds.sideEvents[2 * gi], 0));
+                HIP_CHECK(hipEventRecord(gr.shadeDone, gr.stream));
+                HIP_CHECK(hipStreamWaitEvent(gr.side, gr.shadeDone, 0));
                 LaunchConfig ccfg = gr.cfg;
-                ccfg.spill = ds.spill.ptr + (ds.maxPoolGroups() + gi) * spillWords;
-                timedLaunch(2, side, [&] { launchConnect(rp, ds.view, gr.pool, ccfg, count, side); });
-                HIP_CHECK(hipEventRecord(ds.sideEvents[2 * gi + 1], side));           // connect(i) done
-            } else
-            timedLaunch(2, gr.stream, [&] { launchConnect(rp, ds.view, gr.pool, gr.cfg, count, gr.stream); });
-            if (gr.busyStage != 0u) {
-                gr.busyStage = 2u;
-                ++gr.busyTurn;
+                ccfg.spill = gr.sideSpill;
+                timer.launch(SpanKind::Connect, gr.side, [&] { launchConnect(rp, ds.view, gr.pool, ccfg, count, gr.side); });
+                HIP_CHECK(hipEventRecord(gr.connectDone, gr.side));
+            } else {
+                timer.launch(SpanKind::Connect, gr.stream, [&] { launchConnect(rp, ds.view, gr.pool, gr.cfg, count, gr.stream); });
             }
         }
         ++iterations;
-        if (iterations >= nextCheck || iterations >= maxIterations) {
-            HIP_CHECK(hipGetLastError());   // a launch that failed (bad configuration, out of resources) must not pass for a slow frame
-            bool headsCopied = false;
-            for (uint32_t g = 0; g < groupCount; ++g) {
-                Group& gr = groups[g];
-                if (gr.done) continue;
-                if (queueDry) {
-                    HIP_CHECK(hipMemcpyAsync(ds.pinnedAlive + g, gr.scalars + kAliveBase + ring, sizeof(uint32_t), hipMemcpyDeviceToHost, gr.stream));
-                } else if (!headsCopied) {
-                    HIP_CHECK(hipMemcpy2DAsync(ds.pinnedAlive + kPinnedHeadsOffset, sizeof(uint32_t), pool.nextItem,
-                                               sizeof(uint32_t) * kItemHeadStride, sizeof(uint32_t), kItemHeads, hipMemcpyDeviceToHost, gr.stream));
-                    headsCopied = true;
-                }
-            }
-            bool allDone = true;
-            for (uint32_t g = 0; g < groupCount; ++g) {
-                Group& gr = groups[g];
-                if (gr.done) continue;
-                HIP_CHECK(hipStreamSynchronize(gr.stream));
-                if (queueDry) {
-                    if (ds.pinnedAlive[g] == 0u) gr.done = true;
-                    if (tracePolls) {
-                        std::fprintf(stderr, "[poll] iteration %llu group %u live %u of %u chunk %u\n", static_cast<unsigned long long>(iterations), g,
-                                     ds.pinnedAlive[g], gr.pool.slots, gr.feederChunk);
-                    }
-                    // the fewer live slots, the bigger the chunks the work list is claimed in (see WaveFeeder): a chunk
-                    // should still hold about as many live slots as a full one does when the pool is full
-                    // up to the point where the static first chunks of the resident waves cover the whole list and
-                    // the head is not touched at all
-                    const uint32_t thin = gr.pool.slots / std::max(ds.pinnedAlive[g], 1u);
-                    const uint32_t waves = std::max(gr.cfg.traceGrid * (kTraceGridUnit / 64u), 1u);
-                    const uint32_t perWave = ((gr.pool.slots + waves - 1u) / waves + 63u) / 64u * 64u;
-                    const uint32_t cap = std::max(perWave, ds.feederChunk);
-                    gr.feederChunk = std::min(cap, ds.feederChunk * std::max(thin, 1u));
-                    gr.shadeListed = static_cast<uint64_t>(ds.pinnedAlive[g]) * 5u < static_cast<uint64_t>(gr.pool.slots) * 2u;   // < 40 % live
-                }
-                allDone = allDone && gr.done;
-            }
-            if (queueDry && !allDone && ds.tailBelow > 0) {
-                uint64_t live = 0;
-                for (uint32_t g = 0; g < groupCount; ++g) {
-                    if (!groups[g].done) live += ds.pinnedAlive[g];
-                }
-                if (live <= ds.tailBelow) {
-                    runTail = true;
-                    break;
-                }
-            }
-            uint64_t head = slots;   // items claimed so far = pre-assigned + what every range head has handed out
-            if (!queueDry) {
-                const uint32_t* heads = ds.pinnedAlive + kPinnedHeadsOffset;
-                for (uint32_t k = 0; k < kItemHeads; ++k) {
-                    const uint64_t lo = std::min<uint64_t>(static_cast<uint64_t>(rp.itemHeadFirst) + static_cast<uint64_t>(k) * rp.itemsPerHead, rp.itemCount);
-                    const uint64_t hi = std::min<uint64_t>(lo + rp.itemsPerHead, rp.itemCount);
-                    head += std::min<uint64_t>(std::max<uint64_t>(heads[k], lo), hi) - lo;
-                }
-            }
-            if (allDone) break;
-            nextCheck = iterations + (queueDry && ds.tailBelow > 0 ? kPollDry : kPollEvery);
-            if (!queueDry) {
-                if (head >= rp.itemCount) {
-                    queueDry = true;
-                } else if (head > slots) {
-                    const double perIteration = static_cast<double>(head - slots) / static_cast<double>(iterations);
-                    const double left = static_cast<double>(rp.itemCount - head) / std::max(perIteration, 1.0);
-                    nextCheck = iterations + std::max<uint64_t>(kPollEvery, static_cast<uint64_t>(left * 0.75));
-                }
-            }
+        if (iterations >= last.nextCheck || iterations >= maxIterations) {
+            last = poll(ds, groups, rp, slots, iterations, last.queueDry, knobs.verbosePolls);
+            if (last.allDone || last.runTail) break;
             if (iterations >= maxIterations) throw HipError{"wavefront loop did not terminate"};
         }
     }
-    for (uint32_t g = 0; overlap && g < groupCount; ++g) HIP_CHECK(hipStreamWaitEvent(groups[g].stream, ds.sideEvents[2 * g + 1], 0));
-    for (uint32_t g = 1; g < groupCount; ++g) {
+    for (const PoolGroup& gr : groups) if (gr.side) HIP_CHECK(hipStreamWaitEvent(gr.stream, gr.connectDone, 0));
+    for (size_t g = 1; g < groups.size(); ++g) {
         HIP_CHECK(hipEventRecord(ds.groupEvents[g], groups[g].stream));
         HIP_CHECK(hipStreamWaitEvent(stream, ds.groupEvents[g], 0));
     }
-    if (runTail) {
+    if (last.runTail) {
         HIP_CHECK(hipMemsetAsync(ds.tailWords.ptr, 0, 4 * sizeof(uint32_t), stream));
-        timedLaunch(3, stream, [&] { launchTail(rp, ds.view, pool, env, groups[0].cfg, ds.tailList.ptr, ds.tailWords.ptr, ds.tailWords.ptr + 1, count, stream); });
+        timer.launch(SpanKind::Tail, stream,
+                     [&] { launchTail(rp, ds.view, pool, env, groups[0].cfg, ds.tailList.ptr, ds.tailWords.ptr, ds.tailWords.ptr + 1, count, stream); });
     }
     launchResolve(rp, pool, parts, dOut, stream);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(stream));
     const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
-
-    if (stats) {
-        std::memset(stats, 0, sizeof(*stats));
-        stats->totalSeconds = seconds;
-        stats->avgMsPerSample = seconds * 1000.0 / rp.spp;
-        stats->uploadSeconds = ds.uploadSeconds;
-        stats->samples = static_cast<uint64_t>(localPixels) * rp.spp;
-        if (knobs.verboseLaunches && !spans.empty()) {   // debugging aid: when each launch ran (ms from the first)
-            for (const Span& s : spans) {
-                float t0 = 0.0f, t1 = 0.0f;
-                HIP_CHECK(hipEventElapsedTime(&t0, spans.front().a, s.a));
-                HIP_CHECK(hipEventElapsedTime(&t1, spans.front().a, s.b));
-                std::fprintf(stderr, "[launch] kind %d  start %.3f  end %.3f  (%.3f ms)  stream %p\n", s.kind, t0, t1, t1 - t0, s.stream);
-            }
-        }
-        for (const Span& s : spans) {
-            float ms = 0.0f;
-            HIP_CHECK(hipEventElapsedTime(&ms, s.a, s.b));
-            if (s.kind == 0) {
-                stats->traceKernelMs += ms;
-                ++stats->traceLaunches;
-            } else if (s.kind == 1) {
-                stats->shadeKernelMs += ms;
-            } else if (s.kind == 2) {
-                stats->shadowKernelMs += ms;
-            } else {
-                stats->tailKernelMs += ms;
-            }
-        }
-        if (count) {
-            uint64_t c[kCounterSlots];
-            HIP_CHECK(hipMemcpy(c, ds.counters.ptr, sizeof(c), hipMemcpyDeviceToHost));
-            stats->primaryRays = c[kCntPrimaryRays];
-            stats->extendRays = c[kCntExtendRays];
-            stats->shadowRays = c[kCntShadowRays];
-            stats->extendNodesVisited = c[kCntExtendNodes];
-            stats->extendLeafPrimTests = c[kCntExtendPrims];
-            stats->nodesVisited = c[kCntExtendNodes] + c[kCntShadowNodes];
-            stats->leafPrimTests = c[kCntExtendPrims] + c[kCntShadowPrims];
-            stats->shadedHits = c[kCntShadedHits];
-            stats->triangleHits = c[kCntTriangleHits];
-            stats->shadowEarlyExits = c[kCntShadowEarlyExit];
-            if (knobs.verboseSteps) {   // lane utilisation of k_extend's step loop (counting build)
-                const double nodeLanes = static_cast<double>(c[kCntExtendNodes] - c[kCntExtendLeaves]), primLanes = static_cast<double>(c[kCntExtendPrims]);
-                const double nodeSlots = static_cast<double>(c[kCntExtendWaveNodeSteps]), primSlots = static_cast<double>(c[kCntExtendWavePrimSteps]);
-                std::fprintf(stderr, "[steps] k_extend: %.3g rays; node steps %.3g lane / %.3g slots = %.3f; prim steps %.3g lane / %.3g slots = %.3f; "
-                                     "refill passes %.3g (x64 lanes)\n",
-                             static_cast<double>(c[kCntExtendRays]), nodeLanes, nodeSlots, nodeLanes / std::max(nodeSlots, 1.0), primLanes, primSlots,
-                             primLanes / std::max(primSlots, 1.0), static_cast<double>(c[kCntExtendRefillPasses]));
-                const double votes = static_cast<double>(c[kCntExtendVoteIterations]) / 64.0;
-                std::fprintf(stderr, "[steps] k_extend: %.3g vote iterations; lanes holding a ray %.1f / 64 on average, of which at a leaf %.1f\n", votes,
-                             static_cast<double>(c[kCntExtendActiveLanes]) / std::max(votes, 1.0),
-                             static_cast<double>(c[kCntExtendLeafLanes]) / std::max(votes, 1.0));
-                const double shadeLanes = std::max(static_cast<double>(c[kCntShadeWaves]), 1.0);
-                std::fprintf(stderr, "[steps] k_shade: %.3g wave visits; share of their lanes at each stage: ray traced %.3f, surface hit %.3f, of which a light "
-                                     "%.3f; light sample evaluated %.3f, tested against the light's own triangles %.3f, shadow ray queued %.3f; BSDF sampled "
-                                     "%.3f; new work item wanted %.3f\n",
-                             shadeLanes / 64.0, c[kCntShadeAlive] / shadeLanes, c[kCntShadeSurface] / shadeLanes, c[kCntShadeEmitter] / shadeLanes,
-                             c[kCntShadeLightEval] / shadeLanes, c[kCntShadeLightPretest] / shadeLanes, c[kCntShadeLightStored] / shadeLanes,
-                             c[kCntShadeBsdfSample] / shadeLanes, c[kCntShadeNeedItem] / shadeLanes);
-                {
-                    static const char* names[kShadeParts] = {"loads + landing", "background", "surface reconstruction", "emitter", "light sample", "env sample",
-                                                             "BSDF sample + next ray", "work item + camera ray", "stores + lists", "subsurface walk"};
-                    double waveTotal = 0.0;
-                    for (uint32_t k = 0; k < kShadeParts; ++k) waveTotal += static_cast<double>(c[kCntShadeWaveTicks + k]);
-                    std::fprintf(stderr, "[steps] k_shade parts (clock ticks between the part's first and last instruction, waits included): share of the waves' time | lanes busy\n");
-                    for (uint32_t k = 0; k < kShadeParts; ++k) {
-                        const double wave = static_cast<double>(c[kCntShadeWaveTicks + k]), lane = static_cast<double>(c[kCntShadeLaneTicks + k]);
-                        if (wave <= 0.0) continue;
-                        std::fprintf(stderr, "[steps]   %-24s %5.1f %% | %.3f\n", names[k], 100.0 * wave / std::max(waveTotal, 1.0), lane / (64.0 * wave));
-                    }
-                }
-                std::fprintf(stderr, "[steps] k_extend: refill passes take %.1f %% of the waves' time in the kernel\n",
-                             100.0 * static_cast<double>(c[kCntExtendRefillTicks]) / std::max(static_cast<double>(c[kCntExtendWaveTicks]), 1.0));
-            }
-        }
-    }
+    if (stats) passStats(ds, rp, timer.spans, count, knobs, seconds, *stats);
 }
 
 // A frame.  One accumulator per sample has to fit in a quarter of the free device memory (at most 16 GiB); a frame with
@@ -1178,25 +1199,10 @@ void renderBands(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, 
         const uint32_t flags = (p == 0u ? 1u : 0u) | (done + n >= spp ? 2u : 0u);
         PtrRenderStats one{};
         renderPass(ds, settings, n, done, spp, flags, part, parts, dOut, stream, mode, stats ? &one : nullptr);
-        if (stats) {
-            sum.totalSeconds += one.totalSeconds;
-            sum.traceKernelMs += one.traceKernelMs;
-            sum.shadeKernelMs += one.shadeKernelMs;
-            sum.shadowKernelMs += one.shadowKernelMs;
-            sum.tailKernelMs += one.tailKernelMs;
-            sum.traceLaunches += one.traceLaunches;
-            sum.samples += one.samples;
-            const double keepSeconds = sum.totalSeconds, keepTrace = sum.traceKernelMs, keepShade = sum.shadeKernelMs, keepShadow = sum.shadowKernelMs,
-                         keepTail = sum.tailKernelMs;
-            const uint64_t keepLaunches = sum.traceLaunches, keepSamples = sum.samples;
-            sum = one;   // counters are cumulative on the device: the last pass reports the totals
-            sum.totalSeconds = keepSeconds;
-            sum.traceKernelMs = keepTrace;
-            sum.shadeKernelMs = keepShade;
-            sum.shadowKernelMs = keepShadow;
-            sum.tailKernelMs = keepTail;
-            sum.traceLaunches = keepLaunches;
-            sum.samples = keepSamples;
+        if (stats) {   // counters are cumulative on the device: the last pass reports the totals; times, launches and samples add up
+            addLaunchStats(one, sum);
+            one.totalSeconds += sum.totalSeconds;
+            sum = one;
         }
         done += n;
     }
@@ -1481,14 +1487,7 @@ static int renderMulti(const PtrSceneDesc* scene, const PtrSettings* settings, u
             stats->totalSeconds = slowestRender;
             stats->avgMsPerSample = slowestRender * 1000.0 / std::max(1u, spp);
             stats->uploadSeconds = prepared.seconds + slowestUpload;
-            for (uint32_t p = 0; p < parts; ++p) {
-                stats->samples += partStats[p].samples;
-                stats->traceKernelMs += partStats[p].traceKernelMs;
-                stats->shadeKernelMs += partStats[p].shadeKernelMs;
-                stats->shadowKernelMs += partStats[p].shadowKernelMs;
-                stats->tailKernelMs += partStats[p].tailKernelMs;
-                stats->traceLaunches += partStats[p].traceLaunches;
-            }
+            for (uint32_t p = 0; p < parts; ++p) addLaunchStats(*stats, partStats[p]);
         }
         if (verbose) {
             std::fprintf(stderr, "[ptr] %d device(s): scene preparation %.3f s, slowest upload %.3f s, slowest render + hand-over %.3f s, whole call %.3f s\n", n,
@@ -1553,8 +1552,7 @@ int ptr_trace_rays(PtrDeviceScene* scene, const float* rays, uint64_t n, int any
         scene->rayBatch.upload(reinterpret_cast<const float4*>(rays), n * 2);
         scene->hitBatch.ensure(n);
         HIP_CHECK(hipMemset(scene->counters.ptr, 0, sizeof(uint64_t) * kCounterSlots));
-        LaunchConfig cfg{scene->traceGrid, scene->spill.ptr, scene->scalars.ptr + 1, scene->refillBelow};
-        launchTraceRays(scene->view, scene->rayBatch.ptr, n, any_hit != 0, scene->hitBatch.ptr, cfg, scene->counters.ptr, nullptr);
+        launchTraceRays(scene->view, scene->rayBatch.ptr, n, any_hit != 0, scene->hitBatch.ptr, coldLaunchConfig(*scene), scene->counters.ptr, nullptr);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipDeviceSynchronize());
         HIP_CHECK(hipMemcpy(out, scene->hitBatch.ptr, n * sizeof(PtrHit), hipMemcpyDeviceToHost));
@@ -1587,8 +1585,7 @@ int ptr_render_aovs(PtrDeviceScene* scene, const PtrSettings* settings, uint32_t
         DeviceBuffer<float4> albedo, normal;
         albedo.ensure(pixels);
         normal.ensure(pixels);
-        LaunchConfig cfg{scene->traceGrid, scene->spill.ptr, scene->scalars.ptr + 1, scene->refillBelow};
-        launchAovs(rp, scene->view, sample_index, albedo.ptr, normal.ptr, cfg, nullptr);
+        launchAovs(rp, scene->view, sample_index, albedo.ptr, normal.ptr, coldLaunchConfig(*scene), nullptr);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipDeviceSynchronize());
         if (out_albedo) HIP_CHECK(hipMemcpy(out_albedo, albedo.ptr, pixels * sizeof(float4), hipMemcpyDeviceToHost));
@@ -1659,8 +1656,7 @@ int ptr_debug_surface_hits(PtrDeviceScene* scene, const float* in, uint64_t n, f
         DeviceBuffer<float> din, dout;
         din.upload(in, n * 9);
         dout.ensure(n * 16);
-        LaunchConfig cfg{scene->traceGrid, scene->spill.ptr, scene->scalars.ptr + 1, scene->refillBelow};
-        launchDebugSurfaceHits(scene->view, din.ptr, n, dout.ptr, cfg, nullptr);
+        launchDebugSurfaceHits(scene->view, din.ptr, n, dout.ptr, coldLaunchConfig(*scene), nullptr);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpy(out, dout.ptr, n * 16 * sizeof(float), hipMemcpyDeviceToHost));
         return 0;

@@ -721,6 +721,8 @@ def test_frames_rendered_in_several_passes(cornell_small):
     assert np.array_equal(parts[0], split)                    # still independent of the partition
     assert st_split.extendRays == st_whole.extendRays and st_split.shadedHits == st_whole.shadedHits
     assert st_split.samples == st_whole.samples == 64 * 64 * 24
+    # the per-launch figures add up over the five passes
+    assert st_split.traceLaunches >= 5 and st_split.traceKernelMs > 0 and st_split.shadeKernelMs > 0
     ref, _, _ = osc.render(s, 24, threads=0)
     assert _rmse(split, ref) < 2.0 * _rmse(whole, ref) + 1e-6
 
