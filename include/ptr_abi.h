@@ -214,7 +214,17 @@ typedef struct PtrSettings {
      * chain is the one material textures get (2x2 box filter, odd sizes clamp the second tap, down to 1x1), built on the first
      * render with the bit; the filter is the sampler of the Metal kernel's environment (:20-23): bilinear inside a level with
      * texel centres at (i + 0.5) / W, linear between levels, and repeat addressing on both axes - where the level-0 lookup clamps
-     * v (the Embree rule). */
+     * v (the Embree rule).
+     * Bit 8 (PTR_METAL_RAY_DIFF, only together with PTR_METAL_PBR): at the first mesh hit of a camera ray (path depth 0) in a scene
+     * with material textures, the lookups use the Metal kernel's primary-ray differentials (:134-139, 9753-9757: dOdx = dOdy = 0,
+     * dDdx = horizontal / width, dDdy = -vertical / height on the unnormalised camera direction) turned into uv gradients per uv set
+     * (triangle_surface_partials with its area fallback, :741-820; uv_world_gradients_from_partials and
+     * first_hit_uv_gradients_igehy, :187-240) and through each slot's KHR_texture_transform (:3018-3056).  Base colour,
+     * transmission, occlusion, emissive and the normal map take the anisotropic gradient sample where the slot's gradients are
+     * non-zero (sample_material_texture_filtered, :3091-3127; the filter rule in csrc/kernels/texture.h), metallic-roughness the
+     * level sample at the gradients' LOD (:3143-3216: rho = the largest of |du| W, |dv| H; the cone's LOD where that gives none),
+     * and a normal map's variation between uv, uv + dUVdx and uv + dUVdy adds 0.35 x its variance to the roughness widening
+     * (:6348-6392).  Every other lookup keeps the ray cone. */
     uint32_t metalSemantics;
     uint32_t sssMode;   /* RenderSettings::SssMode: 0 off, 1 separable, 2 random walk; read only with PTR_METAL_SSS */
     uint32_t sssMaxSteps;   /* RenderSettings::sssMaxSteps (32): closest-hit queries per random walk, at least 1 */
@@ -227,7 +237,7 @@ typedef struct PtrSettings {
 } PtrSettings;
 
 enum { PTR_METAL_MEDIA = 1u, PTR_METAL_THIN = 2u, PTR_METAL_FACE_NORMAL = 4u, PTR_METAL_SPECULAR = 8u, PTR_METAL_SSS = 16u, PTR_METAL_PBR = 32u,
-       PTR_METAL_CLAMPS = 64u, PTR_METAL_ENV_LOD = 128u };
+       PTR_METAL_CLAMPS = 64u, PTR_METAL_ENV_LOD = 128u, PTR_METAL_RAY_DIFF = 256u };
 
 typedef struct PtrRenderStats {
     double totalSeconds;                /* integrate phase only (reference: out.totalSeconds) */

@@ -35,6 +35,17 @@ int ptr_debug_env_lookup(PtrDeviceScene* scene, const PtrSettings* settings, con
  * *levels_out = its level count.  out may be NULL (levels only); non-zero when cap_floats is too small. */
 int ptr_debug_env_mips(const float* rgba, uint32_t w, uint32_t h, float* out, uint64_t cap_floats, uint32_t* levels_out);
 
+/* PTR_METAL_RAY_DIFF: the first hit of the camera rays of n {x, y, sample} triples (xys) as k_shade textures it, by the same device code
+ * and with the settings' metalSemantics (gradients only with PTR_METAL_RAY_DIFF).  out n*36 floats: {textured (1: a mesh hit of a
+ * metallic-roughness material in a scene with textures, else 0 and the rest 0), t, uv set 0 (2), uv set 1 (2), set 0 {dudx, dvdx, dudy,
+ * dvdy}, set 1 {the same}, valid set 0, valid set 1, base-colour slot {u, v, dudx, dvdx, dudy, dvdy, valid} after its texture transform,
+ * base colour rgb, roughness, emissive rgb, shading normal xyz, metallic, alpha-test discard, 0}.  The overrides are 0 when discarded. */
+int ptr_debug_first_hit_textures(PtrDeviceScene* scene, const PtrSettings* settings, const uint32_t* xys, uint64_t n, float* out, char* err,
+                                 size_t err_cap);
+/* The anisotropic gradient sample of texture `texture` (csrc/kernels/texture.h texSampleGrad): in n*6 floats {u, v, dudx, dvdx, dudy, dvdy},
+ * out n*4 floats RGBA (-1 for a texture index that does not exist) */
+int ptr_debug_texture_sample_grad(PtrDeviceScene* scene, uint32_t texture, const float* in, uint64_t n, float* out, char* err, size_t err_cap);
+
 /* xys: n*3 {x, y, sample}; out: n*6 floats {origin, direction}; out_states: rng state after ray generation */
 int ptr_debug_camera_rays(const PtrSettings* settings, const uint32_t* xys, uint64_t n, float* out,
                           uint32_t* out_states, char* err, size_t err_cap);

@@ -216,6 +216,7 @@ PTR_METAL_SSS = 16
 PTR_METAL_PBR = 32
 PTR_METAL_CLAMPS = 64
 PTR_METAL_ENV_LOD = 128    # prefiltered environment lookups (environment_color_lod of the Metal kernel)
+PTR_METAL_RAY_DIFF = 256   # first-hit ray differentials of textured lookups (with PTR_METAL_PBR)
 
 # Every symbol include/ptr_abi.h declares.
 ABI_SYMBOLS = (
@@ -229,7 +230,8 @@ ABI_SYMBOLS = (
 DEBUG_SYMBOLS = ("ptr_debug_eval_bsdf", "ptr_debug_sample_bsdf", "ptr_debug_camera_rays", "ptr_debug_env_distribution",
                  "ptr_debug_scene_geometry", "ptr_debug_render_signatures", "ptr_debug_render_multi_on", "ptr_debug_texture_sample",
                  "ptr_debug_generate_tangents", "ptr_debug_surface_hits", "ptr_debug_shade_kernel_set", "ptr_debug_exact_division", "ptr_debug_walk_counts",
-                 "ptr_debug_sample_lobes", "ptr_debug_env_lookup", "ptr_debug_env_mips")
+                 "ptr_debug_sample_lobes", "ptr_debug_env_lookup", "ptr_debug_env_mips", "ptr_debug_first_hit_textures",
+                 "ptr_debug_texture_sample_grad")
 
 _lib: Optional[C.CDLL] = None
 
@@ -484,6 +486,39 @@ class DeviceScene:
         err = _err_buf()
         _check(load_library().ptr_debug_texture_sample(self._h, texture, _fptr(uv_lod), uv_lod.shape[0], _fptr(out), err, len(err)), err)
         return out
+
+    def texture_sample_grad(self, texture: int, uv_grad: np.ndarray) -> np.ndarray:
+        """ptr_debug_texture_sample_grad: the anisotropic gradient sample of PTR_METAL_RAY_DIFF (csrc/kernels/texture.h):
+        uv_grad [n, 6] {u, v, dudx, dvdx, dudy, dvdy} -> [n, 4] RGBA."""
+        q = np.ascontiguousarray(uv_grad, dtype=np.float32).reshape(-1, 6)
+        out = np.zeros((q.shape[0], 4), dtype=np.float32)
+        lib = load_library()
+        lib.ptr_debug_texture_sample_grad.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.c_uint64, C.POINTER(C.c_float),
+                                                      C.c_char_p, C.c_size_t]
+        err = _err_buf()
+        _check(lib.ptr_debug_texture_sample_grad(self._h, texture, _fptr(q), q.shape[0], _fptr(out), err, len(err)), err)
+        return out
+
+    # field -> column slice of the rows first_hit_textures returns (include/ptr_debug.h ptr_debug_first_hit_textures)
+    FIRST_HIT_FIELDS = {"textured": 0, "t": 1, "uv0": slice(2, 4), "uv1": slice(4, 6), "grad0": slice(6, 10), "grad1": slice(10, 14),
+                        "valid0": 14, "valid1": 15, "base_uv": slice(16, 18), "base_grad": slice(18, 22), "base_valid": 22,
+                        "base_color": slice(23, 26), "roughness": 26, "emissive": slice(27, 30), "normal": slice(30, 33), "metallic": 33,
+                        "discard": 34}
+
+    def first_hit_textures(self, settings: PtrSettings, xys: np.ndarray) -> dict:
+        """ptr_debug_first_hit_textures: the first hit of the camera rays of xys [n, 3] {x, y, sample} as k_shade textures it (with
+        PTR_METAL_RAY_DIFF in settings.metalSemantics: the first-hit gradients).  Returns FIRST_HIT_FIELDS -> arrays (grad*: {dudx, dvdx,
+        dudy, dvdy}), plus "raw" [n, 36]."""
+        xys = np.ascontiguousarray(xys, dtype=np.uint32).reshape(-1, 3)
+        out = np.zeros((xys.shape[0], 36), dtype=np.float32)
+        lib = load_library()
+        lib.ptr_debug_first_hit_textures.argtypes = [C.c_void_p, C.POINTER(PtrSettings), C.POINTER(C.c_uint32), C.c_uint64,
+                                                     C.POINTER(C.c_float), C.c_char_p, C.c_size_t]
+        err = _err_buf()
+        _check(lib.ptr_debug_first_hit_textures(self._h, C.byref(settings), _uptr(xys), xys.shape[0], _fptr(out), err, len(err)), err)
+        res = {k: out[:, v] for k, v in self.FIRST_HIT_FIELDS.items()}
+        res["raw"] = out
+        return res
 
     def env_lookup(self, settings: PtrSettings, dir_roughness: np.ndarray) -> np.ndarray:
         """ptr_debug_env_lookup: the PTR_METAL_ENV_LOD lookup of the scene's environment map with the settings' rotation and intensity:

@@ -60,6 +60,9 @@ struct CliOptions {
 constexpr uint32_t kMetalSemanticsAll = 127u;
 // ... and PTR_METAL_ENV_LOD, the prefiltered environment lookups (--semantics=metal-envlod)
 constexpr uint32_t kMetalSemanticsEnvLod = kMetalSemanticsAll | 128u;
+// ... and PTR_METAL_RAY_DIFF, the first-hit ray differentials of textured lookups (--semantics=metal-raydiff / metal-envlod-raydiff)
+constexpr uint32_t kMetalSemanticsRayDiff = kMetalSemanticsAll | 256u;
+constexpr uint32_t kMetalSemanticsEnvLodRayDiff = kMetalSemanticsEnvLod | 256u;
 
 void printUsage(const char* exe) {
     std::cout << "Usage: " << exe << " [options]\n\n"
@@ -80,13 +83,15 @@ void printUsage(const char* exe) {
               << "Backend selection:\n"
               << "  --backend=<hip|embree|metal>   hip / embree: Embree-parity integrator (default); metal: as --semantics=metal\n"
               << "  --enableEmbree[=0|1]           Same as --backend=embree (1) / --backend=metal (0)\n"
-              << "  --semantics=<embree|metal|metal-envlod>\n"
+              << "  --semantics=<embree|metal|metal-envlod|metal-raydiff|metal-envlod-raydiff>\n"
               << "                                 Integrator semantics: embree = parity with the reference's Embree backend\n"
               << "                                 (default); metal = plus the Metal kernel's absorbing media, thin-walled glass, ray-facing\n"
               << "                                 glass normals, rough-metal VNDF formulas, subsurface scattering (scene: renderer sss=...),\n"
               << "                                 three-lobe PBR with transmission, the Metal kernel's clamp variants; metal-envlod = metal\n"
               << "                                 plus environment lookups at a mip level chosen by roughness after glossy bounces and\n"
-              << "                                 for environment samples of glossy materials\n"
+              << "                                 for environment samples of glossy materials; metal-raydiff = metal plus anisotropic\n"
+              << "                                 texture lookups from camera-ray differentials at the first hit of textured meshes;\n"
+              << "                                 metal-envlod-raydiff = both\n"
               << "  --devices=<int>                GPUs of this node to spread the frame over (default 1, 0 = all visible)\n"
               << "  --assets=<dir>                 Directory for relative mesh/env paths\n\n"
               << "Tonemapping overrides (for LDR outputs):\n"
@@ -242,10 +247,14 @@ bool parseOptions(int argc, const char** argv, CliOptions& o, std::string& error
                 o.metalSemantics = kMetalSemanticsAll;
             } else if (value == "metal-envlod") {
                 o.metalSemantics = kMetalSemanticsEnvLod;
+            } else if (value == "metal-raydiff") {
+                o.metalSemantics = kMetalSemanticsRayDiff;
+            } else if (value == "metal-envlod-raydiff") {
+                o.metalSemantics = kMetalSemanticsEnvLodRayDiff;
             } else if (value == "embree") {
                 o.metalSemantics = 0u;
             } else {
-                error = "Invalid value for --semantics (expected embree, metal or metal-envlod)";
+                error = "Invalid value for --semantics (expected embree, metal, metal-envlod, metal-raydiff or metal-envlod-raydiff)";
                 return false;
             }
             o.semanticsSet = true;

@@ -618,7 +618,7 @@ void fillRenderParams(const PtrSettings& s, uint32_t spp, RenderParams& rp) {
     rp.clampEnabled = s.fireflyClampEnabled ? 1.0f : 0.0f;
     rp.emissionScale = (s.emissionScale > 0.0f && std::isfinite(s.emissionScale)) ? s.emissionScale : 1.0f;
     rp.mediaMode = s.metalSemantics & (PTR_METAL_MEDIA | PTR_METAL_THIN | PTR_METAL_FACE_NORMAL | PTR_METAL_SPECULAR | PTR_METAL_SSS | PTR_METAL_PBR |
-                                       PTR_METAL_CLAMPS | PTR_METAL_ENV_LOD);
+                                       PTR_METAL_CLAMPS | PTR_METAL_ENV_LOD | PTR_METAL_RAY_DIFF);
     rp.clampMaxContribution = std::max(s.fireflyClampMaxContribution, 0.0f);   // make_firefly_params, pathtrace.metal:3545
     rp.minSpecularPdfRaw = s.minSpecularPdf;
     rp.sssMode = s.sssMode;
@@ -1640,6 +1640,50 @@ int ptr_debug_texture_sample(PtrDeviceScene* scene, uint32_t texture, const floa
         launchDebugTexSample(scene->view, texture, din.ptr, n, dout.ptr, nullptr);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpy(out, dout.ptr, n * sizeof(float4), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    PTR_CATCH_ALL(err, err_cap)
+}
+
+int ptr_debug_texture_sample_grad(PtrDeviceScene* scene, uint32_t texture, const float* in, uint64_t n, float* out, char* err, size_t err_cap) {
+    if (!scene || (!in && n) || (!out && n)) {
+        setErr(err, err_cap, "ptr_debug_texture_sample_grad: null argument");
+        return 1;
+    }
+    try {
+        HIP_CHECK(hipSetDevice(scene->device));
+        if (n == 0) return 0;
+        DeviceBuffer<float> din;
+        DeviceBuffer<float4> dout;
+        din.upload(in, n * 6);
+        dout.ensure(n);
+        launchDebugTexSampleGrad(scene->view, texture, din.ptr, n, dout.ptr, nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(out, dout.ptr, n * sizeof(float4), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    PTR_CATCH_ALL(err, err_cap)
+}
+
+int ptr_debug_first_hit_textures(PtrDeviceScene* scene, const PtrSettings* settings, const uint32_t* xys, uint64_t n, float* out, char* err,
+                                 size_t err_cap) {
+    if (!scene || !settings || (!xys && n) || (!out && n)) {
+        setErr(err, err_cap, "ptr_debug_first_hit_textures: null argument");
+        return 1;
+    }
+    try {
+        HIP_CHECK(hipSetDevice(scene->device));
+        if (n == 0) return 0;
+        RenderParams rp;
+        fillRenderParams(*settings, 1, rp);
+        constexpr uint64_t kFloats = 36;
+        DeviceBuffer<uint32_t> dxy;
+        DeviceBuffer<float> dout;
+        dxy.upload(xys, n * 3);
+        dout.ensure(n * kFloats);
+        launchDebugFirstHit(rp, scene->view, dxy.ptr, n, dout.ptr, coldLaunchConfig(*scene), nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpy(out, dout.ptr, n * kFloats * sizeof(float), hipMemcpyDeviceToHost));
         return 0;
     }
     PTR_CATCH_ALL(err, err_cap)

@@ -66,6 +66,11 @@ void launchDebugTexSample(const SceneView& sc, uint32_t texture, const float* dI
 // closest hit, surface record and next-ray origin per input ray: in n x 9 floats {origin, direction, next direction}, out n x 16 floats
 // the material / feature set of the k_shade instantiation launchShade picks (bsdf.h kAllMaterials = the full kernel)
 uint32_t shadeKernelSet(const RenderParams& rp, const SceneView& sc, bool count);
+// PTR_METAL_RAY_DIFF: the gradient sample (in n x 6 {u, v, dudx, dvdx, dudy, dvdy}) and the first hit's textured material of the camera rays
+// of n {x, y, sample} (out n x 36 floats, ptr_debug.h ptr_debug_first_hit_textures)
+void launchDebugTexSampleGrad(const SceneView& sc, uint32_t texture, const float* dIn, uint64_t n, float4* dOut, hipStream_t stream);
+void launchDebugFirstHit(const RenderParams& rp, const SceneView& sc, const uint32_t* dXys, uint64_t n, float* dOut, const LaunchConfig& cfg,
+                         hipStream_t stream);
 void launchDebugSurfaceHits(const SceneView& sc, const float* dIn, uint64_t n, float* dOut, const LaunchConfig& cfg, hipStream_t stream);
 void launchDebugCameraRays(const RenderParams& rp, const uint32_t* dXys, uint64_t n, float* dOut, uint32_t* dRngOut,
                            hipStream_t stream);

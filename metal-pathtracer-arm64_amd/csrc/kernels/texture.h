@@ -10,7 +10,13 @@
 //   * filtering: bilinear inside a level (texel centres at (i + 0.5) / W, wrap per the glTF sampler), linear between the two
 //     nearest levels; NEAREST samplers read one texel of the rounded level.
 // What the reference derives from ray differentials at the first hit (anisotropic sampling, the normal-variance term of the
-// roughness widening) has no counterpart here.
+// roughness widening) runs under PTR_METAL_RAY_DIFF only, at the first mesh hit of a camera ray (wavefront.hip firstHitUvGrads):
+//   * level of detail from the uv gradients (material_texture_lod_from_gradients, :3143-3177), the ray cone where they give none;
+//   * `gradient2d` sampling, which the hardware defines, is fixed as the reference formula of EXT_texture_filter_anisotropic:
+//     Px = |(dudx W, dvdx H)|, Py = |(dudy W, dvdy H)|, Pmax / Pmin their max / min, Nt = min(ceil(Pmax / max(Pmin, 1e-6)), A),
+//     lambda = clamp(log2(Pmax / Nt), 0, maxMip); the mean, summed in tap order, of Nt taps of the filter above at lambda, tap i at
+//     uv + ((i + 0.5) / Nt - 0.5) g, g the uv gradient of the longer axis (x on a tie).  A = 8 (the reference's maxAnisotropy) for
+//     LINEAR textures with more than one level, else 1; a NEAREST texture reads one texel of the rounded lambda.
 #pragma once
 
 #include "device_types.h"
@@ -133,13 +139,22 @@ __device__ __forceinline__ f3 decodeNormalMap(f3 s, float normalScale, float& ou
     return n;
 }
 
-// One texture slot's sampling context (make_pbr_texture_sampling_context, :3018-3056, without the first-hit gradients):
-// transformed coordinates of the slot's uv set and its uv-per-world scale.
-struct TexSlot {
-    float u, v, uvPerWorld;
+// PTR_METAL_RAY_DIFF: the first-hit uv gradients of the two uv sets, set[k] = (dudx, dvdx, dudy, dvdy); bit k of `valid`: set k has them
+struct UvGrads {
+    float4 set[2];
+    uint32_t valid;
 };
 
-__device__ __forceinline__ TexSlot texSlot(const float4* mraw, uint32_t slot, uint32_t uvSet, float2 uv0, float2 uv1, float perWorld0, float perWorld1) {
+// One texture slot's sampling context (make_pbr_texture_sampling_context, :3018-3056): transformed coordinates of the slot's uv set,
+// its uv-per-world scale and, with PTR_METAL_RAY_DIFF at the first hit, its uv gradients through the transform's linear part.
+struct TexSlot {
+    float u, v, uvPerWorld;
+    float dudx, dvdx, dudy, dvdy;
+    bool grad;
+};
+
+__device__ __forceinline__ TexSlot texSlot(const float4* mraw, uint32_t slot, uint32_t uvSet, float2 uv0, float2 uv1, float perWorld0, float perWorld1,
+                                           const UvGrads& grads) {
     // rows of KHR_texture_transform live behind the compact material record: raw[2*slot], raw[2*slot + 1] (xyz)
     f3 row0 = mk3(mraw[2u * slot]), row1 = mk3(mraw[2u * slot + 1u]);
     const float linearSum = (fabsf(row0.x) + fabsf(row0.y)) + (fabsf(row1.x) + fabsf(row1.y));
@@ -154,7 +169,93 @@ __device__ __forceinline__ TexSlot texSlot(const float4* mraw, uint32_t slot, ui
     t.v = (row1.x * uv.x + row1.y * uv.y) + row1.z;
     const float sx = sqrtf(row0.x * row0.x + row1.x * row1.x), sy = sqrtf(row0.y * row0.y + row1.y * row1.y);
     t.uvPerWorld = perWorld * smax(smax(sx, sy), 1.0e-6f);   // pbr_transform_uv_per_world (:3002-3009)
+    // pbr_transform_uv_gradient (:2991-2996); gradients that stop being finite are dropped
+    const float4 g = uvSet == 0u ? grads.set[0] : grads.set[1];
+    t.dudx = row0.x * g.x + row0.y * g.y;
+    t.dvdx = row1.x * g.x + row1.y * g.y;
+    t.dudy = row0.x * g.z + row0.y * g.w;
+    t.dvdy = row1.x * g.z + row1.y * g.w;
+    t.grad = ((grads.valid >> uvSet) & 1u) != 0u && isfinite(t.dudx) && isfinite(t.dvdx) && isfinite(t.dudy) && isfinite(t.dvdy);
+    if (!t.grad) t.dudx = t.dvdx = t.dudy = t.dvdy = 0.0f;
     return t;
+}
+
+// max(|dudx|, |dvdx|, |dudy|, |dvdy|) of a slot with gradients (:3110-3112)
+__device__ __forceinline__ float texGradMag(const TexSlot& t) { return fmaxf(fmaxf(fabsf(t.dudx), fabsf(t.dvdx)), fmaxf(fabsf(t.dudy), fabsf(t.dvdy))); }
+
+// material_texture_lod_from_gradients (:3143-3177): false when the slot has no gradients, the texture one level, or rho is not positive
+// and finite - the caller then takes the cone's LOD (material_texture_lod_with_fallback, :3179-3216).  head: the texture's record head
+__device__ __forceinline__ bool texGradLod(uint4 head, const TexSlot& t, float& lod) {
+    if (!t.grad || head.x == 0u || head.y == 0u || head.z <= 1u) return false;
+    const float W = static_cast<float>(head.x), H = static_cast<float>(head.y);
+    const float rho = fmaxf(fmaxf(fabsf(t.dudx) * W, fabsf(t.dvdx) * H), fmaxf(fabsf(t.dudy) * W, fabsf(t.dvdy) * H));
+    if (!isfinite(rho) || !(rho > 0.0f)) return false;
+    const float l = log2f(fmaxf(rho, 1.0e-8f));
+    if (!isfinite(l)) return false;
+    lod = fminf(fmaxf(l, 0.0f), static_cast<float>(head.z - 1u));
+    return true;
+}
+
+// The taps of the gradient sample (`gradient2d`) by the rule of the header comment: level `lod`, `nt` taps along (gu, gv)
+constexpr uint32_t kTexMaxAniso = 8u;
+__device__ __forceinline__ void texAniso(uint4 head, float dudx, float dvdx, float dudy, float dvdy, float& lod, float& nt, float& gu, float& gv) {
+    const float W = static_cast<float>(head.x), H = static_cast<float>(head.y);
+    const float xw = dudx * W, xh = dvdx * H, yw = dudy * W, yh = dvdy * H;
+    const float px = sqrtf(xw * xw + xh * xh), py = sqrtf(yw * yw + yh * yh);
+    const bool xMajor = px >= py;
+    const float pMax = xMajor ? px : py, pMin = xMajor ? py : px;
+    const float maxAniso = (((head.w >> 4) & 1u) != 0u && head.z > 1u) ? static_cast<float>(kTexMaxAniso) : 1.0f;
+    nt = fmaxf(fminf(ceilf(pMax / fmaxf(pMin, 1.0e-6f)), maxAniso), 1.0f);
+    lod = fminf(fmaxf(log2f(pMax / nt), 0.0f), static_cast<float>(head.z - 1u));
+    gu = xMajor ? dudx : dudy;
+    gv = xMajor ? dvdx : dvdy;
+}
+
+// The mean, summed in tap order, of `nt` (1..kTexMaxAniso) taps of the filter at level `lod`, tap i at uv + ((i + 0.5) / nt - 0.5) g; a
+// NEAREST texture reads one texel of the rounded level at uv.  nt = 1 is texSample's level sample, to the bit.
+__device__ __forceinline__ float4 texTaps(const SceneView& sc, uint32_t tex, uint4 head, float u, float v, float lod, float nt, float gu, float gv) {
+    if (((head.w >> 4) & 1u) == 0u) {
+        const float l = fminf(fmaxf(lod, 0.0f), static_cast<float>(head.z - 1u));
+        return texBilinear(sc.texels, texLevel(sc, tex, static_cast<uint32_t>(floorf(l + 0.5f)), head), u, v, head.w);
+    }
+    const uint32_t taps = static_cast<uint32_t>(nt);
+    float4 sum = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+#pragma unroll 1
+    for (uint32_t i = 0u; i < taps; ++i) {
+        const float o = (static_cast<float>(i) + 0.5f) / nt - 0.5f;
+        const float tu = u + o * gu, tv = v + o * gv;
+        const float4 c = texTrilinear(head.z, lod, [&](uint32_t level) { return texBilinear(sc.texels, texLevel(sc, tex, level, head), tu, tv, head.w); });
+        sum.x += c.x;
+        sum.y += c.y;
+        sum.z += c.z;
+        sum.w += c.w;
+    }
+    return make_float4(sum.x / nt, sum.y / nt, sum.z / nt, sum.w / nt);
+}
+
+// The gradient sample; `fallback` when the slot has no texture
+__device__ __forceinline__ float4 texSampleGrad(const SceneView& sc, uint32_t tex, float u, float v, float dudx, float dvdx, float dudy, float dvdy,
+                                                float4 fallback) {
+    if (tex == kNoTexture || tex >= sc.textureCount) return fallback;
+    const uint4 head = sc.texInfo[tex * kTexInfoVec4];
+    float lod, nt, gu, gv;
+    texAniso(head, dudx, dvdx, dudy, dvdy, lod, nt, gu, gv);
+    return texTaps(sc, tex, head, u, v, lod, nt, gu, gv);
+}
+
+// One lookup of a slot: with `aniso` the gradient sample (sample_material_texture_filtered with non-zero gradients, :3091-3127), else the
+// level sample (sample_material_texture_level) at the gradients' LOD or, where they give none, the LOD of the cone's surface footprint.
+// Without gradients this is texSample at texLod, to the bit.
+__device__ __forceinline__ float4 texLookup(const SceneView& sc, uint32_t tex, const TexSlot& t, bool aniso, float footprint, float4 fallback) {
+    if (tex == kNoTexture || tex >= sc.textureCount) return fallback;
+    const uint4 head = sc.texInfo[tex * kTexInfoVec4];
+    float lod, nt = 1.0f, gu = 0.0f, gv = 0.0f;
+    if (aniso) {
+        texAniso(head, t.dudx, t.dvdx, t.dudy, t.dvdy, lod, nt, gu, gv);
+    } else if (!texGradLod(head, t, lod)) {
+        lod = texLod(sc, tex, t.uvPerWorld, footprint);
+    }
+    return texTaps(sc, tex, head, t.u, t.v, lod, nt, gu, gv);
 }
 
 }  // namespace ptrk

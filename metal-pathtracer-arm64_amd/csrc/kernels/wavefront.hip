@@ -776,8 +776,101 @@ struct PbrHit {
     bool twoSided;
 };
 
+// ---- PTR_METAL_RAY_DIFF: the uv gradients of a camera ray's first mesh hit (shaders/pathtrace.metal:134-139, 187-240, 741-820, 9753-9757) ----
+// triangle_surface_partials of one uv set: dP/du, dP/dv from the world edges e1 = p1 - p0, e2 = p2 - p0, else the area fallback
+__device__ __forceinline__ bool surfacePartials(f3 e1, f3 e2, float2 q0, float2 q1, float2 q2, f3& dPdu, f3& dPdv) {
+    const float du1 = q1.x - q0.x, dv1 = q1.y - q0.y, du2 = q2.x - q0.x, dv2 = q2.y - q0.y;
+    const float det = du1 * dv2 - dv1 * du2;
+    if (fabsf(det) > 1.0e-9f) {
+        const float inv = 1.0f / det;
+        dPdu = (e1 * dv2 - e2 * dv1) * inv;
+        dPdv = (e2 * du1 - e1 * du2) * inv;
+        const float lu = length(dPdu), lv = length(dPdv);
+        if (lu > 1.0e-8f && lv > 1.0e-8f) {
+            const float perWorld = smax(1.0f / lu, 1.0f / lv);
+            return isfinite(perWorld) && perWorld > 0.0f;
+        }
+    }
+    const float worldArea = length(cross(e1, e2)), uvArea = fabsf(det);
+    if (!(worldArea > 1.0e-12f && uvArea > 1.0e-12f)) return false;
+    const float perWorld = sqrtf(uvArea / worldArea);
+    const f3 t = normalize(e1);
+    const f3 b = normalize(cross(normalize(cross(e1, e2)), t));
+    if (!finite3(t) || !finite3(b)) return false;
+    dPdu = t / smax(perWorld, 1.0e-8f);
+    dPdv = b / smax(perWorld, 1.0e-8f);
+    return isfinite(perWorld) && perWorld > 0.0f;
+}
+
+// uv_world_gradients_from_partials (:187-201) and first_hit_uv_gradients_igehy (:203-240) for one uv set.  The reference differentiates
+// the unnormalised camera direction d = pixelPosition - origin (dOdx = dOdy = 0, dDdx = horizontal / width, dDdy = -vertical / height);
+// this renderer's rays carry D = d / |d| and the world distance t, so with s = t / |d| (the reference's ray parameter):
+// dPdx = s (dDdx - (N.dDdx) / (N.D) D), and the reference's threshold |N.d| < 1e-6 reads |d| |N.D| < 1e-6.
+__device__ __forceinline__ bool igehyUvGrads(f3 dPdu, f3 dPdv, f3 N, f3 D, float dLen, float t, f3 dDdx, f3 dDdy, float4& out) {
+    const float a00 = dot(dPdu, dPdu), a01 = dot(dPdu, dPdv), a11 = dot(dPdv, dPdv);
+    const float det = a00 * a11 - a01 * a01;
+    if (fabsf(det) <= 1.0e-12f) return false;
+    const f3 dudP = (dPdu * a11 - dPdv * a01) / det, dvdP = (dPdv * a00 - dPdu * a01) / det;
+    if (!finite3(dudP) || !finite3(dvdP)) return false;
+    const float nd = dot(N, D);
+    const float denom = dLen * nd;
+    if (!isfinite(denom) || fabsf(denom) < 1.0e-6f) return false;
+    const float s = t / dLen;
+    const f3 termX = dDdx * s, termY = dDdy * s;   // dOdx + t dDdx of the reference
+    if (!finite3(termX) || !finite3(termY)) return false;
+    const float kx = dot(N, dDdx) / nd, ky = dot(N, dDdy) / nd;
+    if (!isfinite(kx) || !isfinite(ky)) return false;
+    const f3 dPdx = (dDdx - D * kx) * s, dPdy = (dDdy - D * ky) * s;
+    if (!finite3(dPdx) || !finite3(dPdy)) return false;
+    out = make_float4(dot(dudP, dPdx), dot(dvdP, dPdx), dot(dudP, dPdy), dot(dvdP, dPdy));
+    return isfinite(out.x) && isfinite(out.y) && isfinite(out.z) && isfinite(out.w);
+}
+
+// Both uv sets at a mesh-triangle hit `sf` of the camera ray (D, world distance t).  |d| follows from the camera: the lens offset lies in the
+// image plane, so d . c = (lowerLeft - origin) . c for c = horizontal x vertical.  N: the normalised geometric normal.
+__device__ __forceinline__ UvGrads firstHitUvGrads(const RenderParams& rp, const SceneView& sc, const Surface& sf, f3 D, float t) {
+    UvGrads g;
+    g.set[0] = g.set[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    g.valid = 0u;
+    const CameraParams& cam = rp.cam;
+    const f3 h = ld3(cam.horizontal), vt = ld3(cam.vertical);
+    const f3 c = cross(h, vt);
+    const float dLen = dot(ld3(cam.lowerLeft) - ld3(cam.origin), c) / dot(D, c);
+    if (!isfinite(dLen) || !(dLen > 0.0f)) return g;
+    const f3 dDdx = h / smax(static_cast<float>(rp.width), 1.0f), dDdy = -vt / smax(static_cast<float>(rp.height), 1.0f);
+    const f3 N = normalize(sf.normal);
+    if (!finite3(N) || dot(N, N) <= 1.0e-12f) return g;
+    const float4* tp = sc.tris + static_cast<size_t>(sf.prim) * 3u;
+    const f3 e1 = -mk3(tp[1]), e2 = mk3(tp[2]);   // stored as v0 - v1, v2 - v0
+    const float4* tu = sc.triUv + static_cast<size_t>(sf.prim) * 4u;
+    const float4 a = tu[0], b = tu[1], cc = tu[2];
+    f3 dPdu, dPdv;
+    if (surfacePartials(e1, e2, make_float2(a.x, a.y), make_float2(b.x, b.y), make_float2(cc.x, cc.y), dPdu, dPdv) &&
+        igehyUvGrads(dPdu, dPdv, N, D, dLen, t, dDdx, dDdy, g.set[0])) {
+        g.valid |= 1u;
+    }
+    if (surfacePartials(e1, e2, make_float2(a.z, a.w), make_float2(b.z, b.w), make_float2(cc.z, cc.w), dPdu, dPdv) &&
+        igehyUvGrads(dPdu, dPdv, N, D, dLen, t, dDdx, dDdy, g.set[1])) {
+        g.valid |= 2u;
+    }
+    if (!(g.valid & 1u)) g.set[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (!(g.valid & 2u)) g.set[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    return g;
+}
+
+// No gradients: the lookups of every hit but a camera ray's first one under PTR_METAL_RAY_DIFF
+__device__ __forceinline__ UvGrads noUvGrads() {
+    UvGrads g;
+    g.set[0] = g.set[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    g.valid = 0u;
+    return g;
+}
+
+// RD: the camera ray's first hit under PTR_METAL_RAY_DIFF, with its gradients `grads` (firstHitUvGrads).  A separate instantiation: the
+// lookups of every other hit (!RD, grads ignored) compile to the ray-cone code alone and keep its registers.
+template <bool RD>
 __device__ __forceinline__ bool applyPbrTextures(const SceneView& sc, const Surface& sf, uint32_t materialIndex, const Mat& mat, f3 wo, float2 cone,
-                                                 float hitDistance, uint32_t& rng, PbrHit& out) {
+                                                 float hitDistance, const UvGrads& grads, uint32_t& rng, PbrHit& out) {
     const float4* mt = sc.materialTex + static_cast<size_t>(materialIndex) * kMaterialTexVec4;
     const float4 idx0 = mt[12], idx1 = mt[13], pbrParams = mt[14], pbrExtras = mt[15];
     const uint32_t texBase = __float_as_uint(idx0.x), texOrm = __float_as_uint(idx0.y), texNormal = __float_as_uint(idx0.z),
@@ -794,26 +887,35 @@ __device__ __forceinline__ bool applyPbrTextures(const SceneView& sc, const Surf
     // footprint of the ray cone on the surface (:158-160, 178-185, 5947-5949)
     const float coneFootprint = smax(cone.x + cone.y * smax(hitDistance, 0.0f), 1.0e-7f);
     const float surfaceFootprint = coneFootprint / smax(fabsf(dot(normalize(sf.normal), normalize(wo))), 1.0e-3f);
-    auto slot = [&](uint32_t k) { return texSlot(mt, k, (uvSets >> k) & 1u, uv0, uv1, per.x, per.y); };
-    auto lodOf = [&](uint32_t tex, const TexSlot& t) { return texLod(sc, tex, t.uvPerWorld, surfaceFootprint); };
+    auto slot = [&](uint32_t k) { return texSlot(mt, k, (uvSets >> k) & 1u, uv0, uv1, per.x, per.y, grads); };
+    // sample_material_texture_filtered (:3091-3127): the gradient sample where the slot has non-zero gradients, else the level sample at
+    // material_texture_lod_with_fallback (:3179-3216); metallic-roughness always takes the level sample
+    auto filtered = [&](uint32_t tex, const TexSlot& t, float4 fallback) {
+        if (!RD) return texSample(sc, tex, t.u, t.v, texLod(sc, tex, t.uvPerWorld, surfaceFootprint), fallback);
+        return texLookup(sc, tex, t, t.grad && texGradMag(t) > 0.0f, surfaceFootprint, fallback);
+    };
+    auto level = [&](uint32_t tex, const TexSlot& t, float4 fallback) {
+        if (!RD) return texSample(sc, tex, t.u, t.v, texLod(sc, tex, t.uvPerWorld, surfaceFootprint), fallback);
+        return texLookup(sc, tex, t, false, surfaceFootprint, fallback);
+    };
     const float4 one = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
 
     const TexSlot sBase = slot(0u);
-    const float4 baseSample = texSample(sc, texBase, sBase.u, sBase.v, lodOf(texBase, sBase), one);
+    const float4 baseSample = filtered(texBase, sBase, one);
     const float4 bcr = mat.p[kMatBaseColorRoughness];
     const f3 baseColor = mk3(bcr) * mk3(baseSample);
     float metallic = clampf(pbrParams.x, 0.0f, 1.0f), roughness = clampf(pbrParams.y, 0.0f, 1.0f);
     const bool disableOrm = (materialFlags & 1u) != 0u;   // kMaterialFlagDisableOrm
     if (!disableOrm && texOrm != kNoTexture && texOrm < sc.textureCount) {
         const TexSlot sOrm = slot(1u);
-        const float4 mr = texSample(sc, texOrm, sOrm.u, sOrm.v, lodOf(texOrm, sOrm), one);
+        const float4 mr = level(texOrm, sOrm, one);
         metallic = clampf(mr.z * metallic, 0.0f, 1.0f);
         roughness = clampf(mr.y * roughness, 0.0f, 1.0f);
     }
     float transmission = clampf(pbrExtras.z, 0.0f, 1.0f);
     if (texTrans != kNoTexture && texTrans < sc.textureCount) {
         const TexSlot sT = slot(5u);
-        transmission = clampf(transmission * texSample(sc, texTrans, sT.u, sT.v, lodOf(texTrans, sT), one).x, 0.0f, 1.0f);
+        transmission = clampf(transmission * filtered(texTrans, sT, one).x, 0.0f, 1.0f);
     }
     transmission *= (1.0f - metallic);   // (the model applies this factor once more, as the reference does: :6194, 4666)
     // alpha test (:6196-6217): MASK compares with the cutoff, BLEND keeps the hit with probability alpha
@@ -825,14 +927,14 @@ __device__ __forceinline__ bool applyPbrTextures(const SceneView& sc, const Surf
     float occlusion = 1.0f;
     if (!disableOrm && texOcc != kNoTexture && texOcc < sc.textureCount) {
         const TexSlot sO = slot(3u);
-        const float occ = texSample(sc, texOcc, sO.u, sO.v, lodOf(texOcc, sO), one).x;
+        const float occ = filtered(texOcc, sO, one).x;
         const float strength = clampf(pbrParams.z, 0.0f, 1.0f);
         occlusion = 1.0f + (occ - 1.0f) * strength;   // mix(1, occ, strength)
     }
     f3 emissive = mk3(mat.p[kMatEmission]);
     if (texEmissive != kNoTexture && texEmissive < sc.textureCount) {
         const TexSlot sE = slot(4u);
-        emissive *= mk3(texSample(sc, texEmissive, sE.u, sE.v, lodOf(texEmissive, sE), one));
+        emissive *= mk3(filtered(texEmissive, sE, one));
     }
     // normal map (:6281-6346): vertex tangent (Gram-Schmidt against the shading normal), else the triangle's UV derivatives, else an
     // arbitrary frame; the mapped normal is kept on the geometric normal's side
@@ -843,7 +945,8 @@ __device__ __forceinline__ bool applyPbrTextures(const SceneView& sc, const Surf
     const bool useNormalMap = texNormal != kNoTexture && texNormal < sc.textureCount && normalScale > 1.0e-4f;
     if (useNormalMap) {
         const TexSlot sN = slot(2u);
-        const float4 ns = texSample(sc, texNormal, sN.u, sN.v, lodOf(texNormal, sN), make_float4(0.5f, 0.5f, 1.0f, 1.0f));
+        const float4 flat = make_float4(0.5f, 0.5f, 1.0f, 1.0f);
+        const float4 ns = filtered(texNormal, sN, flat);
         float normalLength = 1.0f;
         const f3 nts = decodeNormalMap(mk3(ns), normalScale, normalLength);
         f3 t = mk3(1.0f, 0.0f, 0.0f), bt = mk3(0.0f);
@@ -899,8 +1002,25 @@ __device__ __forceinline__ bool applyPbrTextures(const SceneView& sc, const Surf
         f3 mapped = normalize((t * nts.x + bt * nts.y) + shadingNormal * nts.z);
         if (dot(mapped, sf.normal) < 0.0f) mapped = -mapped;
         shadingNormal = mapped;
-        // shortened (filtered) normals widen the lobe (:6348-6388, without the first-hit gradient term)
-        const float tok = smax((1.0f - normalLength) / smax(normalLength, 1.0e-6f), 0.0f);
+        // shortened (filtered) normals widen the lobe (:6348-6388)
+        float tok = smax((1.0f - normalLength) / smax(normalLength, 1.0e-6f), 0.0f);
+        if (RD && sN.grad) {
+            // ... and so does the normal map's variation across the pixel's footprint: the map decoded again one gradient step along x and y,
+            // at the normal's LOD (level samples)
+            const float gradMag = texGradMag(sN);
+            if (gradMag > 1.0e-6f && gradMag < 4.0f) {
+                TexSlot sX = sN, sY = sN;   // (same gradients: the same LOD)
+                sX.u += sN.dudx;
+                sX.v += sN.dvdx;
+                sY.u += sN.dudy;
+                sY.v += sN.dvdy;
+                float lenX = 1.0f, lenY = 1.0f;
+                const f3 nDx = decodeNormalMap(mk3(level(texNormal, sX, flat)), normalScale, lenX);
+                const f3 nDy = decodeNormalMap(mk3(level(texNormal, sY, flat)), normalScale, lenY);
+                const float variance = smax(smax(1.0f - dot(nts, nDx), 0.0f), smax(1.0f - dot(nts, nDy), 0.0f));
+                tok += 0.35f * variance;
+            }
+        }
         roughness = clampf(sqrtf(roughness * roughness + tok), 0.0f, 1.0f);
     }
     out.ov[0] = mk4(baseColor, roughness);
@@ -1376,7 +1496,13 @@ __device__ __forceinline__ void shadeSlot(const RenderParams& rp, const SceneVie
                     if (TEX && sf.primType == 0u && sc.textureCount > 0u && sc.triUv != nullptr) {
                         cone = pool.cone ? pool.cone[slot] : make_float2(0.0f, 0.0f);
                         haveCone = pool.cone != nullptr;
-                        passThrough = applyPbrTextures(sc, sf, materialIndex, mat, wo, cone, hitv.x, rng, pbrHit);
+                        // PTR_METAL_RAY_DIFF: the camera ray's first hit reads with its uv gradients (pathtrace.metal:5979, 5996)
+                        if ((rp.mediaMode & PTR_METAL_RAY_DIFF) && depth == 0u) {
+                            passThrough = applyPbrTextures<true>(sc, sf, materialIndex, mat, wo, cone, hitv.x, firstHitUvGrads(rp, sc, sf, rayD, hitv.x),
+                                                                 rng, pbrHit);
+                        } else {
+                            passThrough = applyPbrTextures<false>(sc, sf, materialIndex, mat, wo, cone, hitv.x, noUvGrads(), rng, pbrHit);
+                        }
                         if (!passThrough) {
                             mat.o = pbrHit.ov;
                             n = pbrHit.shadingNormal;
@@ -2353,6 +2479,73 @@ __global__ void k_debug_tex_sample(SceneView sc, uint32_t texture, const float* 
     out[i] = texSample(sc, texture, in[i * 3u], in[i * 3u + 1u], in[i * 3u + 2u], make_float4(-1.0f, -1.0f, -1.0f, -1.0f));
 }
 
+// PTR_METAL_RAY_DIFF: the gradient sample, in n x 6 {u, v, dudx, dvdx, dudy, dvdy}
+__global__ void k_debug_tex_sample_grad(SceneView sc, uint32_t texture, const float* in, uint64_t n, float4* out) {
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* q = in + i * 6u;
+    out[i] = texSampleGrad(sc, texture, q[0], q[1], q[2], q[3], q[4], q[5], make_float4(-1.0f, -1.0f, -1.0f, -1.0f));
+}
+
+// The camera ray of each {x, y, sample}, its closest hit and the textured material k_shade builds there at depth 0 (ptr_debug.h
+// ptr_debug_first_hit_textures: out n x 36 floats)
+constexpr uint32_t kFirstHitFloats = 36u;
+__global__ void __launch_bounds__(kTraceBlock) k_debug_first_hit(RenderParams rp, SceneView sc, const uint32_t* xys, uint64_t n, float* out, uint32_t* spill,
+                                                                 uint32_t spillStride) {
+    __shared__ uint32_t ldsStack[kLdsStackLevels * kTraceBlock];
+    const uint32_t gtid = blockIdx.x * kTraceBlock + threadIdx.x;
+    LaneStack stack;
+    stack.lds = (LdsWord*)(ldsStack + threadIdx.x);
+    stack.spill = spill;
+    stack.spillStride = spillStride;
+    stack.limit = sc.stackLimit;
+    TraceCounters cnt{0u, 0u};
+    for (uint64_t i = gtid; i < n; i += static_cast<uint64_t>(gridDim.x) * kTraceBlock) {
+        float* o = out + i * kFirstHitFloats;
+        for (uint32_t k = 0; k < kFirstHitFloats; ++k) o[k] = 0.0f;
+        const uint32_t x = xys[i * 3u], y = xys[i * 3u + 1u], s = xys[i * 3u + 2u];
+        uint32_t rng;
+        f3 org, dir;
+        beginSample(rp, y * rp.width + x, s, rng, org, dir);
+        const TraceHit h = traverse<false, false>(sc, org, dir, kEps, INFINITY, stack, cnt);
+        if (h.prim == kHitMiss || sc.materialCount == 0u) continue;
+        const Surface sf = reconstruct(sc, org, dir, h.t, h.prim);
+        const uint32_t materialIndex = min(sf.material, sc.materialCount - 1u);
+        const Mat mat{byteOffset(sc.materials, materialIndex * (kMaterialVec4 * 16u))};
+        if (!((rp.mediaMode & PTR_METAL_PBR) && mat.type() == 7u && sf.primType == 0u && sc.textureCount > 0u && sc.triUv != nullptr)) continue;
+        const bool rd = (rp.mediaMode & PTR_METAL_RAY_DIFF) != 0u;
+        const UvGrads grads = rd ? firstHitUvGrads(rp, sc, sf, dir, h.t) : noUvGrads();
+        PbrHit ph;
+        const bool discard = rd ? applyPbrTextures<true>(sc, sf, materialIndex, mat, -normalize(dir), primaryCone(rp), h.t, grads, rng, ph)
+                                : applyPbrTextures<false>(sc, sf, materialIndex, mat, -normalize(dir), primaryCone(rp), h.t, grads, rng, ph);
+        // the uv sets and the base-colour slot as applyPbrTextures derives them
+        f3 w = vmax0(mk3(1.0f - sf.bu - sf.bv, sf.bu, sf.bv));
+        const float wsum = (w.x + w.y) + w.z;
+        w = (wsum > 1.0e-8f) ? w / wsum : mk3(1.0f, 0.0f, 0.0f);
+        const float4* tu = sc.triUv + static_cast<size_t>(sf.prim) * 4u;
+        const float4 a = tu[0], b = tu[1], c = tu[2], per = tu[3];
+        const float2 uv0 = make_float2((a.x * w.x + b.x * w.y) + c.x * w.z, (a.y * w.x + b.y * w.y) + c.y * w.z);
+        const float2 uv1 = make_float2((a.z * w.x + b.z * w.y) + c.z * w.z, (a.w * w.x + b.w * w.y) + c.w * w.z);
+        const float4* mt = sc.materialTex + static_cast<size_t>(materialIndex) * kMaterialTexVec4;
+        const TexSlot sb = texSlot(mt, 0u, __float_as_uint(mt[13].z) & 1u, uv0, uv1, per.x, per.y, grads);
+        o[0] = 1.0f;
+        o[1] = h.t;
+        o[2] = uv0.x; o[3] = uv0.y; o[4] = uv1.x; o[5] = uv1.y;
+        o[6] = grads.set[0].x; o[7] = grads.set[0].y; o[8] = grads.set[0].z; o[9] = grads.set[0].w;
+        o[10] = grads.set[1].x; o[11] = grads.set[1].y; o[12] = grads.set[1].z; o[13] = grads.set[1].w;
+        o[14] = (grads.valid & 1u) ? 1.0f : 0.0f;
+        o[15] = (grads.valid & 2u) ? 1.0f : 0.0f;
+        o[16] = sb.u; o[17] = sb.v; o[18] = sb.dudx; o[19] = sb.dvdx; o[20] = sb.dudy; o[21] = sb.dvdy;
+        o[22] = sb.grad ? 1.0f : 0.0f;
+        o[34] = discard ? 1.0f : 0.0f;
+        if (discard) continue;
+        o[23] = ph.ov[0].x; o[24] = ph.ov[0].y; o[25] = ph.ov[0].z; o[26] = ph.ov[0].w;
+        o[27] = ph.ov[1].x; o[28] = ph.ov[1].y; o[29] = ph.ov[1].z;
+        o[30] = ph.shadingNormal.x; o[31] = ph.shadingNormal.y; o[32] = ph.shadingNormal.z;
+        o[33] = ph.ov[2].x;
+    }
+}
+
 // closest hit + surface reconstruction + next-ray origin, the pieces k_shade builds a bounce from (tests of a13 / a14)
 __global__ void __launch_bounds__(kTraceBlock) k_debug_surface(SceneView sc, const float* in, uint64_t n, float* out, uint32_t* spill, uint32_t spillStride) {
     __shared__ uint32_t ldsStack[kLdsStackLevels * kTraceBlock];
@@ -2584,6 +2777,18 @@ void launchDebugSurfaceHits(const SceneView& sc, const float* dIn, uint64_t n, f
     const uint32_t stride = cfg.traceGrid * kTraceBlock;
     const uint32_t grid = std::min(cfg.traceGrid, std::max(1u, ceilDiv(n, kTraceBlock)));
     hipLaunchKernelGGL(k_debug_surface, dim3(grid), dim3(kTraceBlock), 0, stream, sc, dIn, n, dOut, cfg.spill, stride);
+}
+
+void launchDebugTexSampleGrad(const SceneView& sc, uint32_t texture, const float* dIn, uint64_t n, float4* dOut, hipStream_t stream) {
+    hipLaunchKernelGGL(k_debug_tex_sample_grad, dim3(std::max(1u, ceilDiv(n, 128))), dim3(128), 0, stream, sc, texture, dIn, n, dOut);
+}
+
+void launchDebugFirstHit(const RenderParams& rp, const SceneView& sc, const uint32_t* dXys, uint64_t n, float* dOut, const LaunchConfig& cfgIn,
+                         hipStream_t stream) {
+    const LaunchConfig cfg = perBlockSize(cfgIn);
+    const uint32_t stride = cfg.traceGrid * kTraceBlock;
+    const uint32_t grid = std::min(cfg.traceGrid, std::max(1u, ceilDiv(n, kTraceBlock)));
+    hipLaunchKernelGGL(k_debug_first_hit, dim3(grid), dim3(kTraceBlock), 0, stream, rp, sc, dXys, n, dOut, cfg.spill, stride);
 }
 
 void launchDebugCameraRays(const RenderParams& rp, const uint32_t* dXys, uint64_t n, float* dOut, uint32_t* dRngOut, hipStream_t stream) {
