@@ -68,10 +68,28 @@ int ptr_debug_texture_sample(PtrDeviceScene* scene, uint32_t texture, const floa
  * shading normal xyz, front face (1/0), next origin xyz, 0}. */
 int ptr_debug_surface_hits(PtrDeviceScene* scene, const float* in, uint64_t n, float* out, char* err, size_t err_cap);
 
+/* Closest hits of a batch of rays through the production k_extend (the render's launcher, node format and stack: launchExtend with the
+ * scene's launch configuration), as PtrHit records the way ptr_trace_rays reports them.  rays n x 8 {origin, tmin, direction, tmax} with
+ * tmin = 1e-4f and tmax = +inf on every ray (what k_extend traces; anything else is rejected), n < 2^27.  count: the counting build.
+ * info = {node format launched: 0 float, 1 quantised binary, 2 four-wide, 3 the counting build's run-time flag; stack limit; levels of
+ * the four-wide tree (0: none); LDS stack levels}.  A slot k_extend left without a valid hit word reads t = NaN, primType = 0xFFFFFFFF. */
+int ptr_debug_extend_rays(PtrDeviceScene* scene, const float* rays, uint64_t n, int count, PtrHit* out, uint32_t info[4], char* err,
+                          size_t err_cap);
+/* Any-hit queries through the production k_connect (launchConnect, MNEE off), as light-connection records k_shade queues: rays as above
+ * with tmin = 1e-4f and tmax the any-hit bound.  ignore_light (may be NULL): 0xFFFFFFFF gives a kind-0 record, a rectangle-light index a
+ * kind-3 record that ignores that light's own triangles.  records_per_slot (1..4) records share a path slot; the slots are spread
+ * unevenly over the connect sub-lists.  occluded[i] = 1 when k_connect zeroed the record.  info as ptr_debug_extend_rays. */
+int ptr_debug_connect_rays(PtrDeviceScene* scene, const float* rays, const uint32_t* ignore_light, uint64_t n, uint32_t records_per_slot,
+                           uint32_t* occluded, uint32_t info[4], char* err, size_t err_cap);
+
 /* Host-side count of what a closest-hit walk of the scene's BVH costs with 1, 2 or 3 binary levels collapsed per step (2-, 4-, 8-wide nodes,
  * children in order of entry distance): rays n x 8 {origin, tmin, direction, tmax}; out = {node steps, box tests, primitive tests, rays that
  * hit}.  No GPU involved. */
 int ptr_debug_walk_counts(const PtrSceneDesc* scene, const float* rays, uint64_t n, uint32_t levels, uint64_t out[4], char* err, size_t err_cap);
+/* Host-side (no GPU): per ray, the most entries the traversal stack holds during the four-wide walk of ptr_debug_walk_counts (levels 5:
+ * the array the device walks, quantised boxes), counted as the device counts them: the child walked next is not on the stack, the root
+ * pushed beside the oversize leaf is one entry.  Entries past kLdsStackLevels (16) live in the HBM spill area. */
+int ptr_debug_walk_stack_depths(const PtrSceneDesc* scene, const float* rays, uint64_t n, uint32_t* out, char* err, size_t err_cap);
 
 /* The kernels' exact division by a per-render divisor (csrc/kernels/device_types.h DivU32), evaluated on the host: out[i] = n[i] / d. */
 int ptr_debug_exact_division(uint32_t d, const uint32_t* n, uint64_t count, uint32_t* out);
@@ -99,7 +117,7 @@ int ptr_debug_env_distribution(const float* rgba, uint32_t w, uint32_t h, float*
  * primitives, multiply referenced primitives, box containment violations, quantised-box violations, bad child
  * references, triangle count, sphere count, SAH cost * 1000, build milliseconds (gather+build+flatten), quantised
  * nodes usable (grid fine enough; bits 8..15: triangles kept out of the tree so that it is; bits 16..47: four-wide nodes of the
- * persistent kernels; bit 63: those nodes have a bad reference or do not reach every primitive exactly once).  leaf_max = 0 uses the default.  Returns non-zero with a message on bad input. */
+ * persistent kernels; bits 48..55: levels of their tree; bit 63: those nodes have a bad reference or do not reach every primitive exactly once).  leaf_max = 0 uses the default.  Returns non-zero with a message on bad input. */
 int ptr_debug_scene_geometry(const PtrSceneDesc* scene, uint32_t leaf_max, uint64_t out[16], char* err, size_t err_cap);
 
 /* Host-side (no GPU): the tangent generator behind glTF primitives without TANGENT (csrc/host/tangent_space.cpp, the MikkTSpace method;

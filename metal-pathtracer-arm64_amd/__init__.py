@@ -231,7 +231,7 @@ DEBUG_SYMBOLS = ("ptr_debug_eval_bsdf", "ptr_debug_sample_bsdf", "ptr_debug_came
                  "ptr_debug_scene_geometry", "ptr_debug_render_signatures", "ptr_debug_render_multi_on", "ptr_debug_texture_sample",
                  "ptr_debug_generate_tangents", "ptr_debug_surface_hits", "ptr_debug_shade_kernel_set", "ptr_debug_exact_division", "ptr_debug_walk_counts",
                  "ptr_debug_sample_lobes", "ptr_debug_env_lookup", "ptr_debug_env_mips", "ptr_debug_first_hit_textures",
-                 "ptr_debug_texture_sample_grad")
+                 "ptr_debug_texture_sample_grad", "ptr_debug_extend_rays", "ptr_debug_connect_rays", "ptr_debug_walk_stack_depths")
 
 _lib: Optional[C.CDLL] = None
 
@@ -543,6 +543,46 @@ class DeviceScene:
                                   C.byref(stats), err, len(err)), err)
         return out, stats
 
+    # node formats of the persistent traversal kernels (ptr_debug_extend_rays info[0])
+    NODE_FORMATS = {0: "float", 1: "quantised binary", 2: "four-wide", 3: "counting build"}
+
+    @staticmethod
+    def _probe_info(info) -> dict:
+        return {"format": int(info[0]), "stack_limit": int(info[1]), "wide_depth": int(info[2]), "lds_levels": int(info[3])}
+
+    def extend_rays(self, rays: np.ndarray, count: bool = False) -> Tuple[np.ndarray, dict]:
+        """ptr_debug_extend_rays: closest hits through the production k_extend (the render's launcher and node format).  rays [n, 8]
+        {origin, 1e-4, direction, inf}; returns (PtrHit records as trace_rays returns them, {format, stack_limit, wide_depth, lds_levels})."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        out = np.zeros(rays.shape[0], dtype=HIT_DTYPE)
+        info = (C.c_uint32 * 4)()
+        lib = load_library()
+        lib.ptr_debug_extend_rays.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_uint64, C.c_int, C.c_void_p, C.POINTER(C.c_uint32),
+                                              C.c_char_p, C.c_size_t]
+        err = _err_buf()
+        _check(lib.ptr_debug_extend_rays(self._h, _fptr(rays), rays.shape[0], int(count), out.ctypes.data_as(C.c_void_p), info, err,
+                                         len(err)), err)
+        return out, self._probe_info(info)
+
+    def connect_rays(self, rays: np.ndarray, ignore_light: Optional[np.ndarray] = None, records_per_slot: int = 1
+                     ) -> Tuple[np.ndarray, dict]:
+        """ptr_debug_connect_rays: any-hit queries through the production k_connect as queued light connections.  rays [n, 8] {origin,
+        1e-4, direction, tmax}; ignore_light [n] (optional): 0xFFFFFFFF or the rectangle light whose own triangles the query ignores (a
+        kind-3 record).  Returns (occluded [n] bool, info as extend_rays)."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+        occ = np.zeros(rays.shape[0], dtype=np.uint32)
+        ign = None if ignore_light is None else np.ascontiguousarray(ignore_light, dtype=np.uint32).reshape(-1)
+        if ign is not None and ign.shape[0] != rays.shape[0]:
+            raise ValueError("ignore_light needs one entry per ray")
+        info = (C.c_uint32 * 4)()
+        lib = load_library()
+        lib.ptr_debug_connect_rays.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32,
+                                               C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]
+        err = _err_buf()
+        _check(lib.ptr_debug_connect_rays(self._h, _fptr(rays), None if ign is None else _uptr(ign), rays.shape[0], records_per_slot,
+                                          _uptr(occ), info, err, len(err)), err)
+        return occ.astype(bool), self._probe_info(info)
+
     def close(self) -> None:
         if self._h:
             load_library().ptr_scene_release(self._h)
@@ -752,6 +792,20 @@ def debug_scene_geometry(desc: PtrSceneDesc, leaf_max: int = 0) -> dict:
     word = g["quantized_usable"]
     g["oversize"] = (word >> 8) & 0xFF                   # triangles kept out of the tree (tested first by every ray)
     g["wide_nodes"] = (word >> 16) & 0xFFFFFFFF          # four-wide nodes of the persistent traversal kernels
+    g["wide_depth"] = (word >> 48) & 0xFF               # levels of their (by-area) tree
     g["wide_problems"] = word >> 63                      # bad references / primitives not reached exactly once through them
     g["quantized_usable"] = word & 0xFF
     return g
+
+
+def walk_stack_depths(desc: PtrSceneDesc, rays: np.ndarray) -> np.ndarray:
+    """Host-side (no GPU), ptr_debug_walk_stack_depths: per ray [n, 8], the most entries the four-wide walk's traversal stack holds (entries
+    past the 16 LDS levels are in the HBM spill area)."""
+    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
+    out = np.zeros(rays.shape[0], dtype=np.uint32)
+    lib = load_library()
+    lib.ptr_debug_walk_stack_depths.argtypes = [C.POINTER(PtrSceneDesc), C.POINTER(C.c_float), C.c_uint64, C.POINTER(C.c_uint32), C.c_char_p,
+                                                C.c_size_t]
+    err = _err_buf()
+    _check(lib.ptr_debug_walk_stack_depths(C.byref(desc), _fptr(rays), rays.shape[0], _uptr(out), err, len(err)), err)
+    return out

@@ -264,7 +264,8 @@ int ptr_debug_scene_geometry(const PtrSceneDesc* scene, uint32_t leaf_max, uint6
                                    geo.triCount, geo.sphereCount, static_cast<uint64_t>(geo.bvh.sahCost * 1000.0),
                                    static_cast<uint64_t>((geo.gatherSeconds + geo.buildSeconds + geo.flattenSeconds) * 1000.0),
                                    ((geo.bvh.nodeCount > 0 && maxCell * 8.0f <= geo.bvh.meanPrimExtent) ? 1u : 0u) | (c.oversize << 8) |
-                                       (std::min<uint64_t>(c.wideNodes, 0xFFFFFFFFull) << 16) | (c.wideProblems ? 1ull << 63 : 0ull)};
+                                       (std::min<uint64_t>(c.wideNodes, 0xFFFFFFFFull) << 16) | (std::min<uint64_t>(c.wideDepth, 0xFFull) << 48) |
+                                       (c.wideProblems ? 1ull << 63 : 0ull)};
         std::memcpy(out, vals, sizeof(vals));
         return 0;
     });
@@ -275,10 +276,12 @@ int ptr_debug_scene_geometry(const PtrSceneDesc* scene, uint32_t leaf_max, uint6
 // array BuildWideNodes ships, quantised boxes), children visited in order of entry distance: how many node
 // steps, box tests and primitive tests a closest-hit query costs at each width.  Counts only - the product walks four-wide nodes on
 // the device; this is the measurement behind DESIGN.md section 4.3c.
-int ptr_debug_walk_counts(const PtrSceneDesc* scene, const float* rays, uint64_t n, uint32_t levels, uint64_t out[4], char* err, size_t err_cap) {
+// depths (nullable, levels 5 only): per ray, the most entries the device's stack would hold (ptr_debug_walk_stack_depths)
+static int walkBvh(const PtrSceneDesc* scene, const float* rays, uint64_t n, uint32_t levels, uint64_t out[4], uint32_t* depths, const char* who,
+                   char* err, size_t err_cap) {
     return guarded(err, err_cap, [&]() -> int {
         if (!scene || (!rays && n) || !out || levels < 1u || levels > 5u) {
-            setErr(err, err_cap, "ptr_debug_walk_counts: bad argument");
+            setErr(err, err_cap, std::string(who) + ": bad argument");
             return 1;
         }
         ptr::SceneGeometry geo;
@@ -294,7 +297,12 @@ int ptr_debug_walk_counts(const PtrSceneDesc* scene, const float* rays, uint64_t
         std::vector<uint32_t> stack;
         // levels 5: the walk goes through the four-wide array BuildWideNodes makes (what the device walks), boxes as quantised
         std::unique_ptr<uint32_t[]> wideNodes;
-        if (levels >= 5u) ptr::BuildWideNodes(bvh, ptr::WideCollapse::ByArea, wideNodes);
+        if (levels >= 5u) {
+            // (with the by-level fallback of the upload for a tree whose by-area wide tree would outgrow the traversal stack)
+            uint32_t wideDepth = 0;
+            ptr::BuildWideNodes(bvh, ptr::WideCollapse::ByArea, wideNodes, &wideDepth);
+            if (3u * wideDepth + 4u > ptrk::kTraversalStackDepth) ptr::BuildWideNodes(bvh, ptr::WideCollapse::ByLevel, wideNodes);
+        }
         for (uint64_t r = 0; r < n; ++r) {
             const float* q = rays + r * 8;
             const double o[3] = {q[0], q[1], q[2]}, d[3] = {q[4], q[5], q[6]};
@@ -336,7 +344,12 @@ int ptr_debug_walk_counts(const PtrSceneDesc* scene, const float* rays, uint64_t
                 }
             };
             stack.clear();
-            if (bvh.oversizeRef != ptrk::kRefEmpty) testLeaf(bvh.oversizeRef);
+            // the device walks the oversize leaf with the root as its one stack entry; afterwards the node it walks is not on its stack
+            size_t deepest = 0;
+            if (bvh.oversizeRef != ptrk::kRefEmpty) {
+                testLeaf(bvh.oversizeRef);
+                if (bvh.rootRef != ptrk::kRefEmpty) deepest = 1;
+            }
             if (bvh.rootRef != ptrk::kRefEmpty) stack.push_back(bvh.rootRef);
             while (!stack.empty()) {
                 const uint32_t ref = stack.back();
@@ -372,6 +385,7 @@ int ptr_debug_walk_counts(const PtrSceneDesc* scene, const float* rays, uint64_t
                     }
                     std::sort(order, order + on, [&](uint32_t a, uint32_t b) { return entry[a] > entry[b]; });
                     for (uint32_t k = 0; k < on; ++k) stack.push_back(refs[order[k]]);
+                    if (on > 0u) deepest = std::max(deepest, stack.size() - 1u);
                     continue;
                 }
                 Child kids[8];
@@ -433,6 +447,7 @@ int ptr_debug_walk_counts(const PtrSceneDesc* scene, const float* rays, uint64_t
                 for (uint32_t k = 0; k < on; ++k) stack.push_back(kids[order[k]].ref);
             }
             hits += hit ? 1u : 0u;
+            if (depths) depths[r] = static_cast<uint32_t>(deepest);
         }
         out[0] = steps;
         out[1] = boxes;
@@ -440,6 +455,19 @@ int ptr_debug_walk_counts(const PtrSceneDesc* scene, const float* rays, uint64_t
         out[3] = hits;
         return 0;
     });
+}
+
+int ptr_debug_walk_counts(const PtrSceneDesc* scene, const float* rays, uint64_t n, uint32_t levels, uint64_t out[4], char* err, size_t err_cap) {
+    return walkBvh(scene, rays, n, levels, out, nullptr, "ptr_debug_walk_counts", err, err_cap);
+}
+
+int ptr_debug_walk_stack_depths(const PtrSceneDesc* scene, const float* rays, uint64_t n, uint32_t* out, char* err, size_t err_cap) {
+    if (!out && n) {
+        setErr(err, err_cap, "ptr_debug_walk_stack_depths: bad argument");
+        return 1;
+    }
+    uint64_t counts[4];
+    return walkBvh(scene, rays, n, 5u, counts, out, "ptr_debug_walk_stack_depths", err, err_cap);
 }
 
 }  // extern "C"

@@ -157,6 +157,7 @@ struct PtrDeviceScene {
     std::vector<hipEvent_t> sideEvents;      // per group: k_shade of the iteration done / k_connect of the iteration done
     int refillBelow = 40;
     uint32_t spillLevels = 0;   // stack levels beyond the LDS part that the scene's tree can need (sizes the spill area)
+    uint32_t wideDepth = 0;     // levels of the four-wide tree (0: the scene has no four-wide nodes)
     DeviceBuffer<uint4> medium;
     DeviceBuffer<float> envLod;   // PTR_METAL_ENV_LOD: EnvLodView::slotLod
     DeviceBuffer<uint32_t> scalars, pixelOfLocal, spill;
@@ -499,6 +500,7 @@ void uploadScene(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceSce
     const uint32_t wideLevels = ps.pg.wideCount > 0u ? ps.pg.wideDepth : 0u;
     const uint32_t stackNeed = std::min<uint32_t>(kTraversalStackDepth, std::max(3u * wideLevels, static_cast<uint32_t>(bvh.maxDepth)) + 4u);
     v.stackLimit = std::max(stackNeed, kLdsStackLevels);
+    ds.wideDepth = wideLevels;
     ds.spillLevels = v.stackLimit - kLdsStackLevels;
     ds.spill.ensure(std::max<size_t>(spillWordsPerGroup(ds) * ds.maxPoolGroups() * 2u, 1u));   // a group's k_extend and k_connect may run side by side: an area each
     ds.scalars.ensure(static_cast<size_t>(kScalarCount) * kMaxPoolGroups);
@@ -1703,6 +1705,181 @@ int ptr_debug_surface_hits(PtrDeviceScene* scene, const float* in, uint64_t n, f
         launchDebugSurfaceHits(scene->view, din.ptr, n, dout.ptr, coldLaunchConfig(*scene), nullptr);
         HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipMemcpy(out, dout.ptr, n * 16 * sizeof(float), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    PTR_CATCH_ALL(err, err_cap)
+}
+
+}  // extern "C"
+
+namespace {
+
+// The production traversal kernels on a batch of rays (ptr_debug_extend_rays / ptr_debug_connect_rays): both trace from kEps, which the
+// batch must state; info = {node format launched (traversalNodeFormat), stack limit, four-wide depth, LDS stack levels}.
+bool checkProbeRays(const float* rays, uint64_t n, bool infiniteTmax, const char* who, char* err, size_t err_cap) {
+    if (n >= (1ull << kConnectMaskShift)) {
+        setErr(err, err_cap, std::string(who) + ": at most 2^27 - 1 rays");
+        return false;
+    }
+    for (uint64_t i = 0; i < n; ++i) {
+        const float tmin = rays[i * 8 + 3], tmax = rays[i * 8 + 7];
+        if (tmin != 1.0e-4f || (infiniteTmax && !(std::isinf(tmax) && tmax > 0.0f))) {
+            setErr(err, err_cap, std::string(who) + ": ray " + std::to_string(i) + " has tmin " + std::to_string(tmin) + " / tmax " +
+                                     std::to_string(tmax) + (infiniteTmax ? "; the kernel traces from 1e-4 to infinity" : "; the kernel traces from 1e-4"));
+            return false;
+        }
+    }
+    return true;
+}
+
+void probeInfo(const PtrDeviceScene& ds, bool count, uint32_t info[4]) {
+    info[0] = static_cast<uint32_t>(traversalNodeFormat(ds.view, count));
+    info[1] = ds.view.stackLimit;
+    info[2] = ds.view.useWide ? ds.wideDepth : 0u;
+    info[3] = kLdsStackLevels;
+}
+
+// the render's launch configuration of group 0 (coldLaunchConfig plus the scene's feeder chunk), with its work heads zeroed
+LaunchConfig probeLaunchConfig(const PtrDeviceScene& ds) {
+    LaunchConfig cfg = coldLaunchConfig(ds);
+    cfg.feederChunk = ds.feederChunk;
+    HIP_CHECK(hipMemset(cfg.workCounters, 0, 2 * sizeof(uint32_t)));
+    return cfg;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ptr_debug_extend_rays(PtrDeviceScene* scene, const float* rays, uint64_t n, int count, PtrHit* out, uint32_t info[4], char* err,
+                          size_t err_cap) {
+    if (!scene || (!rays && n) || (!out && n) || !info) {
+        setErr(err, err_cap, "ptr_debug_extend_rays: null argument");
+        return 1;
+    }
+    if (!checkProbeRays(rays, n, true, "ptr_debug_extend_rays", err, err_cap)) return 1;
+    try {
+        HIP_CHECK(hipSetDevice(scene->device));
+        probeInfo(*scene, count != 0, info);
+        if (n == 0) return 0;
+        // the slots as k_shade leaves them for k_extend: ray0 = (origin, d.x), ray1 = (d.y, d.z, pdf, flags), alive; hit words that k_extend
+        // must overwrite
+        std::vector<float4> state(n * 2);
+        std::vector<float2> hits(n, make_float2(-2.0f, bitsToFloat(0xFFFFFFFEu)));
+        for (uint64_t i = 0; i < n; ++i) {
+            const float* r = rays + i * 8;
+            state[i] = make_float4(r[0], r[1], r[2], r[4]);
+            state[n + i] = make_float4(r[5], r[6], 0.0f, bitsToFloat(kFlagAlive));
+        }
+        DeviceBuffer<float4> dState, dRays;
+        DeviceBuffer<float2> dHit;
+        DeviceBuffer<PtrHit> dOut;
+        dState.upload(state.data(), state.size());
+        dHit.upload(hits.data(), hits.size());
+        dRays.upload(reinterpret_cast<const float4*>(rays), n * 2);
+        dOut.ensure(n);
+        PathPool pool{};
+        pool.ray0 = dState.ptr;
+        pool.ray1 = dState.ptr + n;
+        pool.hit = dHit.ptr;
+        pool.slots = static_cast<uint32_t>(n);
+        pool.recStride = static_cast<uint32_t>(n);
+        if (count) {
+            HIP_CHECK(hipMemset(scene->counters.ptr, 0, sizeof(uint64_t) * kCounterSlots));
+            pool.counters = scene->counters.ptr;
+        }
+        launchExtend(scene->view, pool, probeLaunchConfig(*scene), nullptr, count != 0, nullptr);
+        HIP_CHECK(hipGetLastError());
+        launchDebugHitRecords(scene->view, dRays.ptr, dHit.ptr, n, static_cast<uint32_t>(scene->info[2]), static_cast<uint32_t>(scene->info[3]),
+                              dOut.ptr, nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(out, dOut.ptr, n * sizeof(PtrHit), hipMemcpyDeviceToHost));
+        return 0;
+    }
+    PTR_CATCH_ALL(err, err_cap)
+}
+
+int ptr_debug_connect_rays(PtrDeviceScene* scene, const float* rays, const uint32_t* ignore_light, uint64_t n, uint32_t records_per_slot,
+                           uint32_t* occluded, uint32_t info[4], char* err, size_t err_cap) {
+    if (!scene || (!rays && n) || (!occluded && n) || !info) {
+        setErr(err, err_cap, "ptr_debug_connect_rays: null argument");
+        return 1;
+    }
+    if (records_per_slot < 1u || records_per_slot > 4u) {
+        setErr(err, err_cap, "ptr_debug_connect_rays: records_per_slot must be 1..4");
+        return 1;
+    }
+    if (!checkProbeRays(rays, n, false, "ptr_debug_connect_rays", err, err_cap)) return 1;
+    for (uint64_t i = 0; ignore_light && i < n; ++i) {
+        if (ignore_light[i] != 0xFFFFFFFFu && ignore_light[i] >= scene->view.rectLightCount) {
+            setErr(err, err_cap, "ptr_debug_connect_rays: ray " + std::to_string(i) + " ignores light " + std::to_string(ignore_light[i]) +
+                                     " of " + std::to_string(scene->view.rectLightCount));
+            return 1;
+        }
+    }
+    try {
+        HIP_CHECK(hipSetDevice(scene->device));
+        probeInfo(*scene, false, info);
+        if (n == 0) return 0;
+        // the ignore word of a kind-3 record: the meta word of the light's own triangles (row 6 of its record, T[1].w of half 0), where
+        // k_shade takes it from (rectLightSurface)
+        std::vector<float4> lights(static_cast<size_t>(scene->view.rectLightCount) * kRectLightVec4);
+        if (!lights.empty()) HIP_CHECK(hipMemcpy(lights.data(), scene->view.rectLights, lights.size() * sizeof(float4), hipMemcpyDeviceToHost));
+        // ray i is record i % records_per_slot of slot i / records_per_slot; the record arrays are one allocation indexed as k_connect
+        // indexes them: field f of record slot k at recBase[(k*4 + f)*slots + slot]
+        const uint64_t slots = (n + records_per_slot - 1u) / records_per_slot;
+        std::vector<float4> rec(slots * kRecSlots * 4u, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+        for (uint64_t i = 0; i < n; ++i) {
+            const float* r = rays + i * 8;
+            const uint64_t slot = i / records_per_slot, k = i % records_per_slot;
+            const uint32_t light = ignore_light ? ignore_light[i] : 0xFFFFFFFFu;
+            const uint32_t kind = light == 0xFFFFFFFFu ? 0u : 3u;
+            rec[(k * 4u + 0u) * slots + slot] = make_float4(r[0], r[1], r[2], r[7]);
+            rec[(k * 4u + 1u) * slots + slot] = make_float4(r[4], r[5], r[6], bitsToFloat(kind));
+            rec[(k * 4u + 2u) * slots + slot] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
+            if (kind == 3u) rec[(k * 4u + 3u) * slots + slot] = make_float4(lights[static_cast<size_t>(light) * kRectLightVec4 + 6u].w, 0.0f, 0.0f, 0.0f);
+        }
+        // the slots spread over the connect sub-lists unevenly, as the waves of k_shade append them, with some sub-lists left empty
+        std::vector<std::vector<uint32_t>> queues(kConnectQueues);
+        for (uint64_t slot = 0; slot < slots; ++slot) {
+            uint32_t q = static_cast<uint32_t>(((slot * 2654435761ull) >> 7) % 97u) % kConnectQueues;
+            if (q % 5u == 2u) q = (q * 3u + 1u) % kConnectQueues;
+            if (q % 5u == 2u) q = (q + 1u) % kConnectQueues;
+            const uint32_t records = static_cast<uint32_t>(std::min<uint64_t>(records_per_slot, n - slot * records_per_slot));
+            queues[q].push_back(static_cast<uint32_t>(slot) | (((1u << records) - 1u) << kConnectMaskShift));
+        }
+        size_t region = 1;
+        for (const auto& q : queues) region = std::max(region, q.size());
+        std::vector<uint32_t> list(region * kConnectQueues, 0u), counts(kConnectQueues * kConnectCountStride, 0u);
+        for (uint32_t q = 0; q < kConnectQueues; ++q) {
+            std::copy(queues[q].begin(), queues[q].end(), list.begin() + static_cast<size_t>(q) * region);
+            counts[q * kConnectCountStride] = static_cast<uint32_t>(queues[q].size());
+        }
+        DeviceBuffer<float4> dRec;
+        DeviceBuffer<uint32_t> dList, dCounts;
+        dRec.upload(rec.data(), rec.size());
+        dList.upload(list.data(), list.size());
+        dCounts.upload(counts.data(), counts.size());
+        PathPool pool{};
+        for (uint32_t k = 0; k < kRecSlots; ++k) {
+            pool.rec[k] = ShadowRecordView{dRec.ptr + (k * 4u + 0u) * slots, dRec.ptr + (k * 4u + 1u) * slots, dRec.ptr + (k * 4u + 2u) * slots,
+                                           dRec.ptr + (k * 4u + 3u) * slots};
+        }
+        pool.slots = static_cast<uint32_t>(slots);
+        pool.recStride = static_cast<uint32_t>(slots);
+        pool.connectList = dList.ptr;
+        pool.connectCount = dCounts.ptr;
+        pool.connectRegion = static_cast<uint32_t>(region);
+        RenderParams rp{};   // MNEE off: launchConnect launches k_connect alone
+        launchConnect(rp, scene->view, pool, probeLaunchConfig(*scene), false, nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        HIP_CHECK(hipMemcpy(rec.data(), dRec.ptr, rec.size() * sizeof(float4), hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < n; ++i) {
+            const float4 a = rec[((i % records_per_slot) * 4u + 2u) * slots + i / records_per_slot];
+            occluded[i] = (a.x == 0.0f && a.y == 0.0f && a.z == 0.0f) ? 1u : 0u;
+        }
         return 0;
     }
     PTR_CATCH_ALL(err, err_cap)

@@ -17,6 +17,9 @@ struct LaunchConfig {
 };
 
 void launchGenerate(const RenderParams& rp, const PathPool& pool, hipStream_t stream);
+// The node format launchExtend / launchConnect instantiate the persistent kernels for: 0 float, 1 quantised binary, 2 four-wide, 3 the
+// counting build (which reads the scene's flag at run time)
+int traversalNodeFormat(const SceneView& sc, bool count);
 // aliveOut (nullable): += number of live slots the launch traced (host termination check)
 void launchExtend(const SceneView& sc, const PathPool& pool, const LaunchConfig& cfg, uint32_t* aliveOut, bool count, hipStream_t stream);
 // words k_shade sets to zero for the launches that follow it (each may be null)
@@ -71,6 +74,9 @@ uint32_t shadeKernelSet(const RenderParams& rp, const SceneView& sc, bool count)
 void launchDebugTexSampleGrad(const SceneView& sc, uint32_t texture, const float* dIn, uint64_t n, float4* dOut, hipStream_t stream);
 void launchDebugFirstHit(const RenderParams& rp, const SceneView& sc, const uint32_t* dXys, uint64_t n, float* dOut, const LaunchConfig& cfg,
                          hipStream_t stream);
+// ptr_debug_extend_rays: k_extend's hit words (dHits, n) of the rays dRays (n x 2 float4) as PtrHit records
+void launchDebugHitRecords(const SceneView& sc, const float4* dRays, const float2* dHits, uint64_t n, uint32_t triCount, uint32_t sphereCount,
+                           PtrHit* dOut, hipStream_t stream);
 void launchDebugSurfaceHits(const SceneView& sc, const float* dIn, uint64_t n, float* dOut, const LaunchConfig& cfg, hipStream_t stream);
 void launchDebugCameraRays(const RenderParams& rp, const uint32_t* dXys, uint64_t n, float* dOut, uint32_t* dRngOut,
                            hipStream_t stream);

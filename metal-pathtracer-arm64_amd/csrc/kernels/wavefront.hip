@@ -2353,6 +2353,50 @@ __global__ void __launch_bounds__(kTraceBlock) k_aovs(RenderParams rp, SceneView
 // =====================================================================================================
 // k_trace_rays: ray-batch queries for ptr_trace_rays (parity tests against the oracle ray caster)
 // =====================================================================================================
+// The PtrHit of a traced ray: t (-1: miss, 0: an any-hit query found something), and for a closest hit the primitive, the barycentrics
+// (triangleUv) and the geometric normal.  Shared by k_trace_rays and the conversion of k_extend's hit words (k_debug_hit_records).
+__device__ __forceinline__ PtrHit ptrHitOf(const SceneView& sc, f3 org, f3 dir, const TraceHit& h, bool anyHit) {
+    float hu = 0.0f, hv = 0.0f;
+    PtrHit r;
+    r.t = -1.0f;
+    r.u = 0.0f;
+    r.v = 0.0f;
+    r.primType = 0u;
+    r.geomIndex = 0u;
+    r.primIndex = 0u;
+    r.ng[0] = r.ng[1] = r.ng[2] = 0.0f;
+    r.pad = 0u;
+    if (h.prim != kHitMiss) {
+        r.t = anyHit ? 0.0f : h.t;
+        if (!anyHit) {
+            if (h.prim & kHitSphereBit) {
+                r.primType = 1u;
+                r.primIndex = sc.sphereInfo[h.prim & kHitIndexMask].x;
+            } else {
+                const float4* tp = sc.tris + static_cast<size_t>(h.prim & kHitIndexMask) * 3u;
+                const float4 t0 = tp[0], t1 = tp[1], t2 = tp[2];
+                const uint32_t meta = __float_as_uint(t1.w);
+                triangleUv(mk3(t0), mk3(t1), mk3(t2), org, dir, hu, hv);
+                r.u = hu;
+                r.v = hv;
+                const f3 ng = cross(mk3(t2), mk3(t1));
+                r.ng[0] = ng.x;
+                r.ng[1] = ng.y;
+                r.ng[2] = ng.z;
+                if ((meta >> 30) == 0u) {
+                    r.primType = 0u;
+                    r.geomIndex = meta & kTriGeomMask;
+                    r.primIndex = __float_as_uint(t2.w);
+                } else {
+                    r.primType = 2u;
+                    r.primIndex = meta & kTriGeomMask;
+                }
+            }
+        }
+    }
+    return r;
+}
+
 template <bool ANY>
 __global__ void __launch_bounds__(kTraceBlock) k_trace_rays(SceneView sc, const float4* rays, uint64_t n, PtrHit* out, uint32_t* spill,
                                                              uint32_t spillStride, uint64_t* counters) {
@@ -2368,49 +2412,33 @@ __global__ void __launch_bounds__(kTraceBlock) k_trace_rays(SceneView sc, const 
         const float4 a = rays[i * 2u], b = rays[i * 2u + 1u];
         const f3 org = mk3(a), dir = mk3(b);
         const TraceHit h = traverse<ANY, true>(sc, org, dir, a.w, b.w, stack, cnt);
-        float hu = 0.0f, hv = 0.0f;
-        PtrHit r;
-        r.t = -1.0f;
-        r.u = 0.0f;
-        r.v = 0.0f;
-        r.primType = 0u;
-        r.geomIndex = 0u;
-        r.primIndex = 0u;
-        r.ng[0] = r.ng[1] = r.ng[2] = 0.0f;
-        r.pad = 0u;
-        if (h.prim != kHitMiss) {
-            r.t = ANY ? 0.0f : h.t;
-            if (!ANY) {
-                if (h.prim & kHitSphereBit) {
-                    r.primType = 1u;
-                    r.primIndex = sc.sphereInfo[h.prim & kHitIndexMask].x;
-                } else {
-                    const float4* tp = sc.tris + static_cast<size_t>(h.prim & kHitIndexMask) * 3u;
-                    const float4 t0 = tp[0], t1 = tp[1], t2 = tp[2];
-                    const uint32_t meta = __float_as_uint(t1.w);
-                    triangleUv(mk3(t0), mk3(t1), mk3(t2), org, dir, hu, hv);
-                    r.u = hu;
-                    r.v = hv;
-                    const f3 ng = cross(mk3(t2), mk3(t1));
-                    r.ng[0] = ng.x;
-                    r.ng[1] = ng.y;
-                    r.ng[2] = ng.z;
-                    if ((meta >> 30) == 0u) {
-                        r.primType = 0u;
-                        r.geomIndex = meta & kTriGeomMask;
-                        r.primIndex = __float_as_uint(t2.w);
-                    } else {
-                        r.primType = 2u;
-                        r.primIndex = meta & kTriGeomMask;
-                    }
-                }
-            }
-        }
-        out[i] = r;
+        out[i] = ptrHitOf(sc, org, dir, h, ANY);
     }
     if (counters) {
         addCounter(counters, ANY ? kCntShadowNodes : kCntExtendNodes, cnt.nodes);
         addCounter(counters, ANY ? kCntShadowPrims : kCntExtendPrims, cnt.prims);
+    }
+}
+
+// ptr_debug_extend_rays: the hit words k_extend left in pool.hit as PtrHit records (rays: the batch, n x {o, tmin, d, tmax}).  A word
+// that names no primitive of the scene (k_extend never wrote the slot, or wrote garbage) becomes t = NaN, primType = 0xFFFFFFFF.
+__global__ void k_debug_hit_records(SceneView sc, const float4* rays, const float2* hits, uint64_t n, uint32_t triCount, uint32_t sphereCount,
+                                    PtrHit* out) {
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float4 a = rays[i * 2u], b = rays[i * 2u + 1u];
+    const TraceHit h{hits[i].x, __float_as_uint(hits[i].y)};
+    const uint32_t index = h.prim & kHitIndexMask;
+    const bool known = h.prim == kHitMiss || ((h.prim & kHitSphereBit) ? ((h.prim & ~kHitSphereBit) == index && index < sphereCount)
+                                                                      : ((h.prim & ~kHitIndexMask) == 0u && index < triCount));
+    if (known) {
+        out[i] = ptrHitOf(sc, mk3(a), mk3(b), h, false);
+    } else {
+        PtrHit r{};
+        r.t = __uint_as_float(0x7FC00000u);
+        r.primType = 0xFFFFFFFFu;
+        r.primIndex = h.prim;
+        out[i] = r;
     }
 }
 
@@ -2603,6 +2631,12 @@ void launchGenerate(const RenderParams& rp, const PathPool& pool, hipStream_t st
     hipLaunchKernelGGL(k_generate, dim3(ceilDiv(pool.slots, 256)), dim3(256), 0, stream, rp, pool);
 }
 
+int traversalNodeFormat(const SceneView& sc, bool count) {
+    if (count) return 3;
+    if (sc.useQuantized && sc.useWide) return 2;
+    return sc.useQuantized ? 1 : 0;
+}
+
 void launchExtend(const SceneView& sc, const PathPool& pool, const LaunchConfig& cfgIn, uint32_t* aliveOut, bool count, hipStream_t stream) {
     const LaunchConfig cfg = perBlockSize(cfgIn);
     const uint32_t stride = cfg.traceGrid * kTraceBlock;
@@ -2614,11 +2648,12 @@ void launchExtend(const SceneView& sc, const PathPool& pool, const LaunchConfig&
     };
     // the node format is a compile-time choice of the persistent kernels (no dead float / quantised path in the step loop); the
     // counting build keeps the run-time flag
-    if (count) {
+    const int format = traversalNodeFormat(sc, count);
+    if (format == 3) {
         if (aliveOut) launch(k_extend<true, true, -1>); else launch(k_extend<true, false, -1>);
-    } else if (sc.useQuantized && sc.useWide) {
+    } else if (format == 2) {
         if (aliveOut) launch(k_extend<false, true, 2>); else launch(k_extend<false, false, 2>);
-    } else if (sc.useQuantized) {
+    } else if (format == 1) {
         if (aliveOut) launch(k_extend<false, true, 1>); else launch(k_extend<false, false, 1>);
     } else {
         if (aliveOut) launch(k_extend<false, true, 0>); else launch(k_extend<false, false, 0>);
@@ -2678,11 +2713,12 @@ void launchConnect(const RenderParams& rp, const SceneView& sc, const PathPool& 
             hipLaunchKernelGGL(kernel, dim3(cfg.traceGrid), dim3(kTraceBlock), 0, stream, rp, sc, pool, cfg.spill, stride, cfg.workCounters + 1,
                                cfg.refillBelow, cfg.feederChunk);
         };
-        if (count) {
+        const int format = traversalNodeFormat(sc, count);
+        if (format == 3) {
             launch(k_connect<true, -1>);
-        } else if (sc.useQuantized && sc.useWide) {
+        } else if (format == 2) {
             launch(k_connect<false, 2>);
-        } else if (sc.useQuantized) {
+        } else if (format == 1) {
             launch(k_connect<false, 1>);
         } else {
             launch(k_connect<false, 0>);
@@ -2770,6 +2806,12 @@ void launchDebugEnvLookup(const RenderParams& rp, const SceneView& sc, const Env
 
 void launchDebugTexSample(const SceneView& sc, uint32_t texture, const float* dIn, uint64_t n, float4* dOut, hipStream_t stream) {
     hipLaunchKernelGGL(k_debug_tex_sample, dim3(std::max(1u, ceilDiv(n, 128))), dim3(128), 0, stream, sc, texture, dIn, n, dOut);
+}
+
+void launchDebugHitRecords(const SceneView& sc, const float4* dRays, const float2* dHits, uint64_t n, uint32_t triCount, uint32_t sphereCount,
+                           PtrHit* dOut, hipStream_t stream) {
+    hipLaunchKernelGGL(k_debug_hit_records, dim3(std::max(1u, ceilDiv(n, 256))), dim3(256), 0, stream, sc, dRays, dHits, n, triCount,
+                       sphereCount, dOut);
 }
 
 void launchDebugSurfaceHits(const SceneView& sc, const float* dIn, uint64_t n, float* dOut, const LaunchConfig& cfgIn, hipStream_t stream) {

@@ -51,6 +51,21 @@ def test_device_path_fails_loudly_without_gpu():
     s = host.settings_for(64, 64)
     rc = pt.load_library().ptr_render(C.byref(host.desc), C.byref(s), 1, 0, out.ctypes.data_as(C.POINTER(C.c_float)), None, err, 256)
     assert rc != 0 and b"no CPU fallback" in err.value and not out.any()
+    # the probes of the production traversal kernels need a device scene, which cannot exist here: they fail with a message
+    lib = pt.load_library()
+    rays = np.zeros((1, 8), np.float32)
+    info = (C.c_uint32 * 4)()
+    hits = np.zeros(1, pt.HIT_DTYPE)
+    lib.ptr_debug_extend_rays.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_uint64, C.c_int, C.c_void_p, C.POINTER(C.c_uint32), C.c_char_p,
+                                          C.c_size_t]
+    rc = lib.ptr_debug_extend_rays(None, rays.ctypes.data_as(C.POINTER(C.c_float)), 1, 0, hits.ctypes.data_as(C.c_void_p), info, err, 256)
+    assert rc != 0 and b"ptr_debug_extend_rays" in err.value
+    occ = np.zeros(1, np.uint32)
+    lib.ptr_debug_connect_rays.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32),
+                                           C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]
+    rc = lib.ptr_debug_connect_rays(None, rays.ctypes.data_as(C.POINTER(C.c_float)), None, 1, 1, occ.ctypes.data_as(C.POINTER(C.c_uint32)), info,
+                                    err, 256)
+    assert rc != 0 and b"ptr_debug_connect_rays" in err.value
 
 
 def test_division_by_a_render_constant_is_exact():
