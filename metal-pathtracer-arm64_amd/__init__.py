@@ -218,20 +218,61 @@ PTR_METAL_CLAMPS = 64
 PTR_METAL_ENV_LOD = 128    # prefiltered environment lookups (environment_color_lod of the Metal kernel)
 PTR_METAL_RAY_DIFF = 256   # first-hit ray differentials of textured lookups (with PTR_METAL_PBR)
 
-# Every symbol include/ptr_abi.h declares.
-ABI_SYMBOLS = (
-    "ptr_device_count", "ptr_scene_upload", "ptr_scene_release", "ptr_scene_info", "ptr_render",
-    "ptr_render_bands_device", "ptr_part_band_count", "ptr_render_bands", "ptr_trace_rays", "ptr_render_aovs",
-    "ptr_host_scene_load", "ptr_host_scene_free", "ptr_host_scene_desc", "ptr_host_write_image", "ptr_host_write_exr_multilayer",
-    "ptr_host_read_pfm", "ptr_version", "ptr_render_multi", "ptr_host_write_exr_aovs", "ptr_host_decode_image",
-    "ptr_scene_timings", "ptr_scene_prepare_geometry", "ptr_scene_upload_prepared",
-)
-# include/ptr_debug.h (test-only device-function probes)
-DEBUG_SYMBOLS = ("ptr_debug_eval_bsdf", "ptr_debug_sample_bsdf", "ptr_debug_camera_rays", "ptr_debug_env_distribution",
-                 "ptr_debug_scene_geometry", "ptr_debug_render_signatures", "ptr_debug_render_multi_on", "ptr_debug_texture_sample",
-                 "ptr_debug_generate_tangents", "ptr_debug_surface_hits", "ptr_debug_shade_kernel_set", "ptr_debug_exact_division", "ptr_debug_walk_counts",
-                 "ptr_debug_sample_lobes", "ptr_debug_env_lookup", "ptr_debug_env_mips", "ptr_debug_first_hit_textures",
-                 "ptr_debug_texture_sample_grad", "ptr_debug_extend_rays", "ptr_debug_connect_rays", "ptr_debug_walk_stack_depths")
+# The C signature of every function of include/ptr_abi.h and include/ptr_debug.h, in header order: name -> (restype, argtypes).  The one
+# place they are declared: load_library() applies it, tests/test_host.py holds its argument counts against the headers.
+_int, _u32, _u64, _vp, _cp = C.c_int, C.c_uint32, C.c_uint64, C.c_void_p, C.c_char_p
+_fp, _up, _u64p = C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)
+_desc, _settings, _material, _stats = C.POINTER(PtrSceneDesc), C.POINTER(PtrSettings), C.POINTER(PtrMaterial), C.POINTER(PtrRenderStats)
+_err = [_cp, C.c_size_t]   # the trailing (char* err, size_t err_cap)
+_SIGNATURES = {
+    "ptr_device_count": (_int, []),
+    "ptr_scene_upload": (_int, [_desc, _int, C.POINTER(_vp)] + _err),
+    "ptr_scene_release": (None, [_vp]),
+    "ptr_scene_info": (_int, [_vp, _u64p]),
+    "ptr_scene_timings": (_int, [_vp, C.POINTER(C.c_double)]),
+    "ptr_scene_prepare_geometry": (_int, [_desc, _cp, C.POINTER(C.c_double)] + _err),
+    "ptr_scene_upload_prepared": (_int, [_desc, _cp, _int, C.POINTER(_vp)] + _err),
+    "ptr_render": (_int, [_desc, _settings, _u32, _int, _fp, _stats] + _err),
+    "ptr_render_multi": (_int, [_desc, _settings, _u32, _int, _int, _fp, _stats] + _err),
+    "ptr_render_bands_device": (_int, [_vp, _settings, _u32, _u32, _u32, _vp, _vp, _int, _stats] + _err),
+    "ptr_part_band_count": (_u32, [_u32, _u32, _u32]),
+    "ptr_render_bands": (_int, [_vp, _settings, _u32, _u32, _u32, _fp, _int, _stats] + _err),
+    "ptr_render_aovs": (_int, [_vp, _settings, _u32, _fp, _fp] + _err),
+    "ptr_trace_rays": (_int, [_vp, _fp, _u64, _int, _vp, _stats] + _err),
+    "ptr_host_scene_load": (_int, [_cp, _cp, C.POINTER(_vp)] + _err),
+    "ptr_host_scene_free": (None, [_vp]),
+    "ptr_host_scene_desc": (_int, [_vp, _desc, _settings]),
+    "ptr_host_write_image": (_int, [_cp, _cp, _fp, _u32, _u32, _int, _u32, _u32, C.c_float, C.c_float] + _err),
+    "ptr_host_write_exr_multilayer": (_int, [_cp, _fp, _u32, _u32, _fp, _cp] + _err),
+    "ptr_host_write_exr_aovs": (_int, [_cp, _fp, _fp, _fp, _u32, _u32] + _err),
+    "ptr_host_decode_image": (_int, [_cp, _u64, C.POINTER(C.c_uint8), _u64, _up, _up] + _err),
+    "ptr_host_read_pfm": (_int, [_cp, _fp, _u32, _up, _up]),
+    "ptr_version": (_cp, []),
+    # include/ptr_debug.h (test-only device-function probes)
+    "ptr_debug_eval_bsdf": (_int, [_material, _settings, _fp, _u64, _fp] + _err),
+    "ptr_debug_sample_bsdf": (_int, [_material, _settings, _fp, _up, _up, _u64, _fp, _up] + _err),
+    "ptr_debug_sample_lobes": (_int, [_material, _settings, _fp, _up, _up, _u64, _fp, _fp, _up, _fp] + _err),
+    "ptr_debug_env_lookup": (_int, [_vp, _settings, _fp, _u64, _fp] + _err),
+    "ptr_debug_env_mips": (_int, [_fp, _u32, _u32, _fp, _u64, _up]),
+    "ptr_debug_first_hit_textures": (_int, [_vp, _settings, _up, _u64, _fp] + _err),
+    "ptr_debug_texture_sample_grad": (_int, [_vp, _u32, _fp, _u64, _fp] + _err),
+    "ptr_debug_camera_rays": (_int, [_settings, _up, _u64, _fp, _up] + _err),
+    "ptr_debug_render_signatures": (_int, [_vp, _settings, _fp, _up] + _err),
+    "ptr_debug_texture_sample": (_int, [_vp, _u32, _fp, _u64, _fp] + _err),
+    "ptr_debug_surface_hits": (_int, [_vp, _fp, _u64, _fp] + _err),
+    "ptr_debug_extend_rays": (_int, [_vp, _fp, _u64, _int, _vp, _up] + _err),
+    "ptr_debug_connect_rays": (_int, [_vp, _fp, _up, _u64, _u32, _up, _up] + _err),
+    "ptr_debug_walk_counts": (_int, [_desc, _fp, _u64, _u32, _u64p] + _err),
+    "ptr_debug_walk_stack_depths": (_int, [_desc, _fp, _u64, _up] + _err),
+    "ptr_debug_exact_division": (_int, [_u32, _up, _u64, _up]),
+    "ptr_debug_shade_kernel_set": (_int, [_vp, _settings, _int, _up]),
+    "ptr_debug_render_multi_on": (_int, [_desc, _settings, _u32, C.POINTER(_int), _int, _fp, _stats] + _err),
+    "ptr_debug_env_distribution": (_int, [_fp, _u32, _u32, _fp, _up, _fp, _up, _fp, _fp]),
+    "ptr_debug_scene_geometry": (_int, [_desc, _u32, _u64p] + _err),
+    "ptr_debug_generate_tangents": (_int, [_fp, _fp, _fp, _u64, _fp]),
+}
+DEBUG_SYMBOLS = tuple(name for name in _SIGNATURES if name.startswith("ptr_debug_"))
+ABI_SYMBOLS = tuple(name for name in _SIGNATURES if name not in DEBUG_SYMBOLS)
 
 _lib: Optional[C.CDLL] = None
 
@@ -249,47 +290,9 @@ def load_library() -> C.CDLL:
     if not os.path.exists(path):
         raise PtrError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` first")
     lib = C.CDLL(path)
-    vp, cp, u32, u64, sz = C.c_void_p, C.c_char_p, C.c_uint32, C.c_uint64, C.c_size_t
-    lib.ptr_device_count.restype = C.c_int
-    lib.ptr_scene_upload.argtypes = [C.POINTER(PtrSceneDesc), C.c_int, C.POINTER(vp), cp, sz]
-    lib.ptr_scene_release.argtypes = [vp]
-    lib.ptr_scene_timings.argtypes = [vp, C.POINTER(C.c_double)]
-    lib.ptr_scene_prepare_geometry.argtypes = [C.POINTER(PtrSceneDesc), cp, C.POINTER(C.c_double), cp, sz]
-    lib.ptr_scene_upload_prepared.argtypes = [C.POINTER(PtrSceneDesc), cp, C.c_int, C.POINTER(vp), cp, sz]
-    lib.ptr_scene_release.restype = None
-    lib.ptr_scene_info.argtypes = [vp, C.POINTER(u64)]
-    lib.ptr_render.argtypes = [C.POINTER(PtrSceneDesc), C.POINTER(PtrSettings), u32, C.c_int, C.POINTER(C.c_float),
-                               C.POINTER(PtrRenderStats), cp, sz]
-    lib.ptr_render_bands_device.argtypes = [vp, C.POINTER(PtrSettings), u32, u32, u32, vp, vp, C.c_int,
-                                            C.POINTER(PtrRenderStats), cp, sz]
-    lib.ptr_part_band_count.argtypes = [u32, u32, u32]
-    lib.ptr_part_band_count.restype = u32
-    lib.ptr_render_bands.argtypes = [vp, C.POINTER(PtrSettings), u32, u32, u32, C.POINTER(C.c_float), C.c_int,
-                                     C.POINTER(PtrRenderStats), cp, sz]
-    lib.ptr_render_aovs.argtypes = [vp, C.POINTER(PtrSettings), u32, C.POINTER(C.c_float), C.POINTER(C.c_float), cp, sz]
-    lib.ptr_trace_rays.argtypes = [vp, C.POINTER(C.c_float), u64, C.c_int, vp, C.POINTER(PtrRenderStats), cp, sz]
-    lib.ptr_host_scene_load.argtypes = [cp, cp, C.POINTER(vp), cp, sz]
-    lib.ptr_host_scene_free.argtypes = [vp]
-    lib.ptr_host_scene_free.restype = None
-    lib.ptr_host_scene_desc.argtypes = [vp, C.POINTER(PtrSceneDesc), C.POINTER(PtrSettings)]
-    lib.ptr_host_write_image.argtypes = [cp, cp, C.POINTER(C.c_float), u32, u32, C.c_int, u32, u32, C.c_float,
-                                         C.c_float, cp, sz]
-    lib.ptr_host_write_exr_multilayer.argtypes = [cp, C.POINTER(C.c_float), u32, u32, C.POINTER(C.c_float), cp, cp, sz]
-    lib.ptr_host_read_pfm.argtypes = [cp, C.POINTER(C.c_float), u32, C.POINTER(u32), C.POINTER(u32)]
-    lib.ptr_version.restype = cp
-    fp, up = C.POINTER(C.c_float), C.POINTER(C.c_uint32)
-    lib.ptr_debug_eval_bsdf.argtypes = [C.POINTER(PtrMaterial), C.POINTER(PtrSettings), fp, u64, fp, cp, sz]
-    lib.ptr_debug_sample_bsdf.argtypes = [C.POINTER(PtrMaterial), C.POINTER(PtrSettings), fp, up, up, u64, fp, up, cp, sz]
-    lib.ptr_debug_camera_rays.argtypes = [C.POINTER(PtrSettings), up, u64, fp, up, cp, sz]
-    lib.ptr_debug_env_distribution.argtypes = [fp, u32, u32, fp, up, fp, up, fp, fp]
-    lib.ptr_debug_scene_geometry.argtypes = [C.POINTER(PtrSceneDesc), u32, C.POINTER(u64), cp, sz]
-    lib.ptr_debug_render_signatures.argtypes = [vp, C.POINTER(PtrSettings), fp, up, cp, sz]
-    lib.ptr_debug_texture_sample.argtypes = [vp, u32, fp, u64, fp, cp, sz]
-    lib.ptr_render_multi.argtypes = [C.POINTER(PtrSceneDesc), C.POINTER(PtrSettings), u32, C.c_int, C.c_int, fp, C.POINTER(PtrRenderStats), cp, sz]
-    lib.ptr_debug_render_multi_on.argtypes = [C.POINTER(PtrSceneDesc), C.POINTER(PtrSettings), u32, C.POINTER(C.c_int), C.c_int, fp,
-                                              C.POINTER(PtrRenderStats), cp, sz]
-    lib.ptr_host_write_exr_aovs.argtypes = [cp, fp, fp, fp, u32, u32, cp, sz]
-    lib.ptr_host_decode_image.argtypes = [cp, u64, C.POINTER(C.c_uint8), u64, up, up, cp, sz]
+    for name, (restype, argtypes) in _SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
@@ -305,6 +308,21 @@ def _check(rc: int, err) -> None:
 
 def _fptr(a: np.ndarray):
     return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def _uptr(a: np.ndarray):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+def _batch(fn, lead, inp, dtype, cols, outs, more=(), tail=()):
+    """The batch pattern of the probes, fn(*lead, in, *more, n, *out, *tail, err, err_cap): `inp` as a contiguous [n, cols] array of
+    `dtype` (float32 or uint32) and one zeroed [n, *shape] array per (shape, dtype) of `outs`.  Returns the output array or arrays."""
+    ptr = lambda a: _uptr(a) if a.dtype == np.uint32 else _fptr(a)
+    inp = np.ascontiguousarray(inp, dtype=dtype).reshape(-1, cols)
+    res = [np.zeros((inp.shape[0],) + shape, dtype=dt) for shape, dt in outs]
+    err = _err_buf()
+    _check(fn(*lead, ptr(inp), *more, inp.shape[0], *map(ptr, res), *tail, err, len(err)), err)
+    return res[0] if len(res) == 1 else tuple(res)
 
 
 def device_count() -> int:
@@ -416,22 +434,14 @@ class DeviceScene:
 
     def shade_kernel_set(self, settings: PtrSettings, count: bool = False) -> int:
         """ptr_debug_shade_kernel_set: the material / feature mask of the k_shade instantiation a render launches (0x3FF = full)."""
-        lib = load_library()
-        lib.ptr_debug_shade_kernel_set.argtypes = [C.c_void_p, C.POINTER(PtrSettings), C.c_int, C.POINTER(C.c_uint32)]
         out = C.c_uint32(0)
-        if lib.ptr_debug_shade_kernel_set(self._h, C.byref(settings), int(count), C.byref(out)) != 0:
+        if load_library().ptr_debug_shade_kernel_set(self._h, C.byref(settings), int(count), C.byref(out)) != 0:
             raise PtrError("ptr_debug_shade_kernel_set failed")
         return int(out.value)
 
     def surface_hits(self, rays) -> np.ndarray:
         """ptr_debug_surface_hits: rays [n, 9] {origin, direction, next direction} -> [n, 16]."""
-        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 9)
-        out = np.zeros((rays.shape[0], 16), dtype=np.float32)
-        lib = load_library()
-        lib.ptr_debug_surface_hits.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_uint64, C.POINTER(C.c_float), C.c_char_p, C.c_size_t]
-        err = _err_buf()
-        _check(lib.ptr_debug_surface_hits(self._h, _fptr(rays), rays.shape[0], _fptr(out), err, len(err)), err)
-        return out
+        return _batch(load_library().ptr_debug_surface_hits, (self._h,), rays, np.float32, 9, [((16,), np.float32)])
 
     def render(self, settings: PtrSettings, spp: int, part: int = 0, parts: int = 1, count: bool = False
                ) -> Tuple[np.ndarray, PtrRenderStats]:
@@ -481,23 +491,12 @@ class DeviceScene:
 
     def texture_sample(self, texture: int, uv_lod: np.ndarray) -> np.ndarray:
         """Filtered texture lookups on the device (include/ptr_debug.h): uv_lod [n, 3] -> [n, 4] RGBA."""
-        uv_lod = np.ascontiguousarray(uv_lod, dtype=np.float32).reshape(-1, 3)
-        out = np.zeros((uv_lod.shape[0], 4), dtype=np.float32)
-        err = _err_buf()
-        _check(load_library().ptr_debug_texture_sample(self._h, texture, _fptr(uv_lod), uv_lod.shape[0], _fptr(out), err, len(err)), err)
-        return out
+        return _batch(load_library().ptr_debug_texture_sample, (self._h, texture), uv_lod, np.float32, 3, [((4,), np.float32)])
 
     def texture_sample_grad(self, texture: int, uv_grad: np.ndarray) -> np.ndarray:
         """ptr_debug_texture_sample_grad: the anisotropic gradient sample of PTR_METAL_RAY_DIFF (csrc/kernels/texture.h):
         uv_grad [n, 6] {u, v, dudx, dvdx, dudy, dvdy} -> [n, 4] RGBA."""
-        q = np.ascontiguousarray(uv_grad, dtype=np.float32).reshape(-1, 6)
-        out = np.zeros((q.shape[0], 4), dtype=np.float32)
-        lib = load_library()
-        lib.ptr_debug_texture_sample_grad.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_float), C.c_uint64, C.POINTER(C.c_float),
-                                                      C.c_char_p, C.c_size_t]
-        err = _err_buf()
-        _check(lib.ptr_debug_texture_sample_grad(self._h, texture, _fptr(q), q.shape[0], _fptr(out), err, len(err)), err)
-        return out
+        return _batch(load_library().ptr_debug_texture_sample_grad, (self._h, texture), uv_grad, np.float32, 6, [((4,), np.float32)])
 
     # field -> column slice of the rows first_hit_textures returns (include/ptr_debug.h ptr_debug_first_hit_textures)
     FIRST_HIT_FIELDS = {"textured": 0, "t": 1, "uv0": slice(2, 4), "uv1": slice(4, 6), "grad0": slice(6, 10), "grad1": slice(10, 14),
@@ -509,13 +508,7 @@ class DeviceScene:
         """ptr_debug_first_hit_textures: the first hit of the camera rays of xys [n, 3] {x, y, sample} as k_shade textures it (with
         PTR_METAL_RAY_DIFF in settings.metalSemantics: the first-hit gradients).  Returns FIRST_HIT_FIELDS -> arrays (grad*: {dudx, dvdx,
         dudy, dvdy}), plus "raw" [n, 36]."""
-        xys = np.ascontiguousarray(xys, dtype=np.uint32).reshape(-1, 3)
-        out = np.zeros((xys.shape[0], 36), dtype=np.float32)
-        lib = load_library()
-        lib.ptr_debug_first_hit_textures.argtypes = [C.c_void_p, C.POINTER(PtrSettings), C.POINTER(C.c_uint32), C.c_uint64,
-                                                     C.POINTER(C.c_float), C.c_char_p, C.c_size_t]
-        err = _err_buf()
-        _check(lib.ptr_debug_first_hit_textures(self._h, C.byref(settings), _uptr(xys), xys.shape[0], _fptr(out), err, len(err)), err)
+        out = _batch(load_library().ptr_debug_first_hit_textures, (self._h, C.byref(settings)), xys, np.uint32, 3, [((36,), np.float32)])
         res = {k: out[:, v] for k, v in self.FIRST_HIT_FIELDS.items()}
         res["raw"] = out
         return res
@@ -523,14 +516,7 @@ class DeviceScene:
     def env_lookup(self, settings: PtrSettings, dir_roughness: np.ndarray) -> np.ndarray:
         """ptr_debug_env_lookup: the PTR_METAL_ENV_LOD lookup of the scene's environment map with the settings' rotation and intensity:
         dir_roughness [n, 4] {direction, roughness} -> [n, 4] {LOD, rgb}."""
-        q = np.ascontiguousarray(dir_roughness, dtype=np.float32).reshape(-1, 4)
-        out = np.zeros((q.shape[0], 4), dtype=np.float32)
-        lib = load_library()
-        lib.ptr_debug_env_lookup.argtypes = [C.c_void_p, C.POINTER(PtrSettings), C.POINTER(C.c_float), C.c_uint64, C.POINTER(C.c_float),
-                                             C.c_char_p, C.c_size_t]
-        err = _err_buf()
-        _check(lib.ptr_debug_env_lookup(self._h, C.byref(settings), _fptr(q), q.shape[0], _fptr(out), err, len(err)), err)
-        return out
+        return _batch(load_library().ptr_debug_env_lookup, (self._h, C.byref(settings)), dir_roughness, np.float32, 4, [((4,), np.float32)])
 
     def trace_rays(self, rays: np.ndarray, any_hit: bool = False) -> Tuple[np.ndarray, PtrRenderStats]:
         """rays: [n, 8] float32 {ox,oy,oz,tmin,dx,dy,dz,tmax}; returns a structured array of PtrHit."""
@@ -556,12 +542,9 @@ class DeviceScene:
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
         out = np.zeros(rays.shape[0], dtype=HIT_DTYPE)
         info = (C.c_uint32 * 4)()
-        lib = load_library()
-        lib.ptr_debug_extend_rays.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_uint64, C.c_int, C.c_void_p, C.POINTER(C.c_uint32),
-                                              C.c_char_p, C.c_size_t]
         err = _err_buf()
-        _check(lib.ptr_debug_extend_rays(self._h, _fptr(rays), rays.shape[0], int(count), out.ctypes.data_as(C.c_void_p), info, err,
-                                         len(err)), err)
+        _check(load_library().ptr_debug_extend_rays(self._h, _fptr(rays), rays.shape[0], int(count), out.ctypes.data_as(C.c_void_p), info,
+                                                    err, len(err)), err)
         return out, self._probe_info(info)
 
     def connect_rays(self, rays: np.ndarray, ignore_light: Optional[np.ndarray] = None, records_per_slot: int = 1
@@ -575,12 +558,9 @@ class DeviceScene:
         if ign is not None and ign.shape[0] != rays.shape[0]:
             raise ValueError("ignore_light needs one entry per ray")
         info = (C.c_uint32 * 4)()
-        lib = load_library()
-        lib.ptr_debug_connect_rays.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32,
-                                               C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]
         err = _err_buf()
-        _check(lib.ptr_debug_connect_rays(self._h, _fptr(rays), None if ign is None else _uptr(ign), rays.shape[0], records_per_slot,
-                                          _uptr(occ), info, err, len(err)), err)
+        _check(load_library().ptr_debug_connect_rays(self._h, _fptr(rays), None if ign is None else _uptr(ign), rays.shape[0],
+                                                     records_per_slot, _uptr(occ), info, err, len(err)), err)
         return occ.astype(bool), self._probe_info(info)
 
     def close(self) -> None:
@@ -683,51 +663,27 @@ def read_pfm(path: str) -> np.ndarray:
 # ----------------------------------------------------------------------------- device-function probes (tests)
 
 
-def _uptr(a: np.ndarray):
-    return a.ctypes.data_as(C.POINTER(C.c_uint32))
-
-
 def debug_eval_bsdf(material: PtrMaterial, settings: PtrSettings, inputs: np.ndarray) -> np.ndarray:
-    inputs = np.ascontiguousarray(inputs, dtype=np.float32).reshape(-1, 12)
-    out = np.zeros((inputs.shape[0], 5), dtype=np.float32)
-    err = _err_buf()
-    _check(load_library().ptr_debug_eval_bsdf(C.byref(material), C.byref(settings), _fptr(inputs), inputs.shape[0],
-                                             _fptr(out), err, len(err)), err)
-    return out
+    return _batch(load_library().ptr_debug_eval_bsdf, (C.byref(material), C.byref(settings)), inputs, np.float32, 12, [((5,), np.float32)])
 
 
 def debug_sample_bsdf(material: PtrMaterial, settings: PtrSettings, inputs: np.ndarray, front: np.ndarray,
                       states: np.ndarray):
-    inputs = np.ascontiguousarray(inputs, dtype=np.float32).reshape(-1, 9)
     front = np.ascontiguousarray(front, dtype=np.uint32)
     states = np.ascontiguousarray(states, dtype=np.uint32)
-    out = np.zeros((inputs.shape[0], 8), dtype=np.float32)
-    out_states = np.zeros(inputs.shape[0], dtype=np.uint32)
-    err = _err_buf()
-    _check(load_library().ptr_debug_sample_bsdf(C.byref(material), C.byref(settings), _fptr(inputs), _uptr(front),
-                                               _uptr(states), inputs.shape[0], _fptr(out), _uptr(out_states), err,
-                                               len(err)), err)
-    return out, out_states
+    return _batch(load_library().ptr_debug_sample_bsdf, (C.byref(material), C.byref(settings)), inputs, np.float32, 9,
+                  [((8,), np.float32), ((), np.uint32)], more=(_uptr(front), _uptr(states)))
 
 
 def debug_sample_lobes(material: PtrMaterial, settings: PtrSettings, inputs: np.ndarray, front: np.ndarray, states: np.ndarray):
     """ptr_debug_sample_lobes on the inputs of debug_sample_bsdf: ([n, 3] {lobe, lobe roughness, isDelta}, [n, 8] sample as
     debug_sample_bsdf returns it, [n] rng states after sampling, the material's environment-lighting roughness)."""
-    inputs = np.ascontiguousarray(inputs, dtype=np.float32).reshape(-1, 9)
     front = np.ascontiguousarray(front, dtype=np.uint32)
     states = np.ascontiguousarray(states, dtype=np.uint32)
-    n = inputs.shape[0]
-    out = np.zeros((n, 3), dtype=np.float32)
-    sample = np.zeros((n, 8), dtype=np.float32)
-    out_states = np.zeros(n, dtype=np.uint32)
     env_rough = C.c_float()
-    lib = load_library()
-    lib.ptr_debug_sample_lobes.argtypes = [C.POINTER(PtrMaterial), C.POINTER(PtrSettings), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
-                                           C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint32),
-                                           C.POINTER(C.c_float), C.c_char_p, C.c_size_t]
-    err = _err_buf()
-    _check(lib.ptr_debug_sample_lobes(C.byref(material), C.byref(settings), _fptr(inputs), _uptr(front), _uptr(states), n, _fptr(out),
-                                      _fptr(sample), _uptr(out_states), C.byref(env_rough), err, len(err)), err)
+    out, sample, out_states = _batch(load_library().ptr_debug_sample_lobes, (C.byref(material), C.byref(settings)), inputs, np.float32, 9,
+                                     [((3,), np.float32), ((8,), np.float32), ((), np.uint32)], more=(_uptr(front), _uptr(states)),
+                                     tail=(C.byref(env_rough),))
     return out, sample, out_states, float(env_rough.value)
 
 
@@ -736,7 +692,6 @@ def debug_env_mips(rgba: np.ndarray):
     rgba = np.ascontiguousarray(rgba, dtype=np.float32)
     h, w = rgba.shape[0], rgba.shape[1]
     lib = load_library()
-    lib.ptr_debug_env_mips.argtypes = [C.POINTER(C.c_float), C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.c_uint64, C.POINTER(C.c_uint32)]
     levels = C.c_uint32(0)
     if lib.ptr_debug_env_mips(_fptr(rgba), w, h, None, 0, C.byref(levels)) != 0:
         raise PtrError("ptr_debug_env_mips failed")
@@ -752,13 +707,7 @@ def debug_env_mips(rgba: np.ndarray):
 
 
 def debug_camera_rays(settings: PtrSettings, xys: np.ndarray):
-    xys = np.ascontiguousarray(xys, dtype=np.uint32).reshape(-1, 3)
-    out = np.zeros((xys.shape[0], 6), dtype=np.float32)
-    states = np.zeros(xys.shape[0], dtype=np.uint32)
-    err = _err_buf()
-    _check(load_library().ptr_debug_camera_rays(C.byref(settings), _uptr(xys), xys.shape[0], _fptr(out), _uptr(states),
-                                               err, len(err)), err)
-    return out, states
+    return _batch(load_library().ptr_debug_camera_rays, (C.byref(settings),), xys, np.uint32, 3, [((6,), np.float32), ((), np.uint32)])
 
 
 def debug_env_distribution(rgba: np.ndarray) -> dict:
@@ -801,11 +750,4 @@ def debug_scene_geometry(desc: PtrSceneDesc, leaf_max: int = 0) -> dict:
 def walk_stack_depths(desc: PtrSceneDesc, rays: np.ndarray) -> np.ndarray:
     """Host-side (no GPU), ptr_debug_walk_stack_depths: per ray [n, 8], the most entries the four-wide walk's traversal stack holds (entries
     past the 16 LDS levels are in the HBM spill area)."""
-    rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 8)
-    out = np.zeros(rays.shape[0], dtype=np.uint32)
-    lib = load_library()
-    lib.ptr_debug_walk_stack_depths.argtypes = [C.POINTER(PtrSceneDesc), C.POINTER(C.c_float), C.c_uint64, C.POINTER(C.c_uint32), C.c_char_p,
-                                                C.c_size_t]
-    err = _err_buf()
-    _check(lib.ptr_debug_walk_stack_depths(C.byref(desc), _fptr(rays), rays.shape[0], _uptr(out), err, len(err)), err)
-    return out
+    return _batch(load_library().ptr_debug_walk_stack_depths, (C.byref(desc),), rays, np.float32, 8, [((), np.uint32)])

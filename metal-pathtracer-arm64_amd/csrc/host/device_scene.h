@@ -1,0 +1,192 @@
+// What the two hipcc-compiled host files share (hip_backend.cpp: scene upload and the render loop; debug_probes.cpp: the test-only entry
+// points of include/ptr_debug.h): HIP error handling, device buffers, the device scene, and the few backend functions the probes call.
+// Internal: not part of the C-ABI.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdio>
+#include <cstring>
+#include <exception>
+#include <string>
+#include <vector>
+
+#include "../kernels/device_types.h"
+#include "../kernels/launch.h"
+#include "ptr_abi.h"
+
+namespace ptrhost {
+
+struct HipError {
+    std::string message;
+};
+
+#define HIP_CHECK(expr)                                                                                     \
+    do {                                                                                                    \
+        hipError_t _e = (expr);                                                                             \
+        if (_e != hipSuccess) {                                                                             \
+            throw ptrhost::HipError{std::string(#expr) + ": " + hipGetErrorString(_e)};                     \
+        }                                                                                                   \
+    } while (0)
+
+inline void setErr(char* err, size_t cap, const std::string& msg) {
+    if (err && cap > 0) std::snprintf(err, cap, "%s", msg.c_str());
+}
+
+// Nothing may unwind across the C boundary: the BVH build allocates multi-GB vectors and starts threads
+// (std::bad_alloc, std::system_error), and the callers are ctypes / a C++ program built with another runtime.
+#define PTR_CATCH_ALL(err, cap)                                                                             \
+    catch (const ptrhost::HipError& e) {                                                                    \
+        ptrhost::setErr(err, cap, e.message);                                                               \
+        return 1;                                                                                           \
+    }                                                                                                       \
+    catch (const std::exception& e) {                                                                       \
+        ptrhost::setErr(err, cap, std::string("exception: ") + e.what());                                   \
+        return 1;                                                                                           \
+    }                                                                                                       \
+    catch (...) {                                                                                           \
+        ptrhost::setErr(err, cap, "unknown exception");                                                     \
+        return 1;                                                                                           \
+    }
+
+template <typename T>
+struct DeviceBuffer {
+    T* ptr = nullptr;
+    size_t count = 0;
+    DeviceBuffer() = default;
+    DeviceBuffer(const DeviceBuffer&) = delete;
+    DeviceBuffer& operator=(const DeviceBuffer&) = delete;
+    ~DeviceBuffer() { release(); }
+    void release() {
+        if (ptr) (void)hipFree(ptr);
+        ptr = nullptr;
+        count = 0;
+    }
+    void ensure(size_t n) {
+        if (n <= count && ptr) return;
+        release();
+        if (n == 0) n = 1;
+        HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ptr), n * sizeof(T)));
+        count = n;
+    }
+    void upload(const T* src, size_t n) {
+        ensure(n);
+        if (n) HIP_CHECK(hipMemcpy(ptr, src, n * sizeof(T), hipMemcpyHostToDevice));
+    }
+    void download(T* dst, size_t n) const {   // blocking, like upload
+        if (n) HIP_CHECK(hipMemcpy(dst, ptr, n * sizeof(T), hipMemcpyDeviceToHost));
+    }
+};
+
+inline float bitsToFloat(uint32_t u) {
+    float f;
+    std::memcpy(&f, &u, 4);
+    return f;
+}
+
+}  // namespace ptrhost
+
+using ptrhost::DeviceBuffer;
+
+struct PtrDeviceScene {
+    int device = 0;
+    DeviceBuffer<uint4> qnodes;
+    DeviceBuffer<uint4> wnodes;   // PTR_WIDE_NODES=1: four-wide nodes (SceneView::wnodes)
+    DeviceBuffer<float4> nodes, tris, triNormals, spheres, materials, rects, rectLights, envRgba;
+    DeviceBuffer<uint2> sphereInfo;
+    DeviceBuffer<int32_t> lightIndexByRect;
+    DeviceBuffer<float2> envCond, envMarg, cone;
+    DeviceBuffer<float4> triUv, triTangent, texels, materialTex;
+    DeviceBuffer<uint4> texInfo;
+    DeviceBuffer<float> envPdf;
+    // PTR_METAL_ENV_LOD: the environment map's mip chain (EnvLodView::mips), built on the first render that sets the bit
+    DeviceBuffer<float4> envMips;
+    uint32_t envMipLevels = 0;   // 0: not built
+    ptrk::SceneView view{};
+    uint64_t info[8] = {0};
+    double uploadSeconds = 0.0;
+    double timings[4] = {0.0, 0.0, 0.0, 0.0};   // geometry preparation (or cache read), shading tables, copies to the device, 1 = geometry came from a cache
+    uint64_t deviceTotalBytes = 0;        // hipDeviceProp_t::totalGlobalMem
+    bool hasRandomWalkMaterial = false;   // a type-5 material with sssParams.y >= 0.5 (Metal random-walk subsurface)
+
+    // render-time resources, grown on demand and kept across calls
+    DeviceBuffer<float4> state, recBuf, itemAccum;   // state: the four 16 B words of every slot (PathPool::ray0 / ray1 / thr / accum)
+    DeviceBuffer<float2> hit;
+    DeviceBuffer<uint32_t> flushItem, signature, tailList, tailWords;
+    DeviceBuffer<uint32_t> connectList, connectCounts;   // PathPool::connectList: per group a list and two sets of sub-list counters
+    DeviceBuffer<uint32_t> busyLists, busyCounts;        // PathPool::busyIn / busyOut: per group two lists and three sets of counters
+    // end of the frame: once the item queue is dry and at most this many slots are still alive, the remaining paths are finished by
+    // k_tail_run (one lane per path, no launches between bounces) instead of further extend / shade / connect rounds; 0 = never
+    uint64_t tailBelow = 512ull << 10;
+    uint64_t poolSlots = 32ull << 20;        // resident path slots at most (PTR_POOL_SLOTS)
+    // The pool is split into this many independent groups.  Two by default, each on a main stream (k_extend, k_shade) and a side stream
+    // on which the k_connect of an iteration runs beside the k_extend of the next (they share nothing: one reads the rays k_shade wrote,
+    // the other its connection records): four streams in flight, which is what the runtime's four hardware queues carry without
+    // serialising.  (Rounds 1-3 ran four groups of one stream each; profiles/r3_ab_connect_overlap.txt.)
+    // Frames of a few milliseconds (a pool of at most 8 Mi slots: config 1) keep four groups of one stream each: -6 % with two.
+    uint32_t poolGroups = 0;      // PTR_POOL_GROUPS (0: two groups, four for small pools)
+    bool connectOverlap = true;   // PTR_CONNECT_OVERLAP=0: k_connect on the group's own stream
+    uint32_t maxPoolGroups() const { return poolGroups ? poolGroups : 4u; }
+    uint32_t feederChunk = 256;   // slots per work-head claim while the pool is full (it grows as the pool drains)
+    std::vector<hipStream_t> groupStreams;   // streams of groups 1.. (group 0 runs on the caller's stream)
+    std::vector<hipEvent_t> groupEvents;
+    std::vector<hipStream_t> sideStreams;    // per group: the stream of its k_connect launches (see poolGroups)
+    std::vector<hipEvent_t> sideEvents;      // per group: k_shade of the iteration done / k_connect of the iteration done
+    int refillBelow = 40;
+    uint32_t spillLevels = 0;   // stack levels beyond the LDS part that the scene's tree can need (sizes the spill area)
+    uint32_t wideDepth = 0;     // levels of the four-wide tree (0: the scene has no four-wide nodes)
+    DeviceBuffer<uint4> medium;
+    DeviceBuffer<float> envLod;   // PTR_METAL_ENV_LOD: EnvLodView::slotLod
+    DeviceBuffer<uint32_t> scalars, pixelOfLocal, spill;
+    DeviceBuffer<uint2> itemReserve;
+    DeviceBuffer<uint32_t> itemHeads, zeros;
+    DeviceBuffer<uint64_t> counters;
+    DeviceBuffer<float> outBands;
+    DeviceBuffer<float4> rayBatch;
+    DeviceBuffer<PtrHit> hitBatch;
+    uint32_t* pinnedAlive = nullptr;
+    uint32_t traceGrid = 0;       // persistent blocks of the traversal kernels: fills every wave slot (also sizes the spill area)
+    uint32_t traceGridHalf = 0;   // ... of k_extend / k_connect when several pool groups run large launches side by side
+    // cached partition
+    uint32_t cachedW = 0, cachedH = 0, cachedPart = 0, cachedParts = 0, cachedLocalPixels = 0;
+
+    ~PtrDeviceScene() {
+        if (pinnedAlive) (void)hipHostFree(pinnedAlive);
+        for (hipStream_t st : groupStreams) (void)hipStreamDestroy(st);
+        for (hipEvent_t e : groupEvents) (void)hipEventDestroy(e);
+        for (hipStream_t st : sideStreams) (void)hipStreamDestroy(st);
+        for (hipEvent_t e : sideEvents) (void)hipEventDestroy(e);
+    }
+};
+
+namespace ptrhost {
+
+// Defined in hip_backend.cpp.
+void compactMaterial(const PtrMaterial& m, std::vector<float>& out);
+void appendTextureWithMips(const PtrTexture& t, std::vector<float>& texels, std::vector<uint32_t>& info);
+double ensureEnvMips(PtrDeviceScene& ds);
+void fillRenderParams(const PtrSettings& s, uint32_t spp, ptrk::RenderParams& rp);
+ptrk::LaunchConfig coldLaunchConfig(const PtrDeviceScene& ds);
+void renderBands(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, uint32_t part, uint32_t parts, float* dOut, hipStream_t stream,
+                 int mode, PtrRenderStats* stats);
+
+// The frame of a C-ABI entry point that works on a device: "<who>: null argument" unless argsOk (a call that needs `scene` says so
+// there), the device selected (the scene's; device 0 for a call without a scene, which fails when there is none), the body, the error
+// a launch in it may have left, and nothing unwinding to the caller.
+template <typename Body>
+int deviceCall(const char* who, const PtrDeviceScene* scene, bool argsOk, char* err, size_t cap, Body&& body) {
+    if (!argsOk) {
+        setErr(err, cap, std::string(who) + ": null argument");
+        return 1;
+    }
+    try {
+        if (!scene && ptr_device_count() < 1) throw HipError{"no HIP device (the HIP path has no CPU fallback)"};
+        HIP_CHECK(hipSetDevice(scene ? scene->device : 0));
+        body();
+        HIP_CHECK(hipGetLastError());
+        return 0;
+    }
+    PTR_CATCH_ALL(err, cap)
+}
+
+}  // namespace ptrhost

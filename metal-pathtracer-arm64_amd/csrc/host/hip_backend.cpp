@@ -20,79 +20,20 @@
 #include <thread>
 #include <vector>
 
-#include "../kernels/device_types.h"
-#include "../kernels/launch.h"
 #include "bvh_builder.h"
+#include "device_scene.h"
 #include "env_importance_sampler.h"
 #include "geometry_cache.h"
 #include "knobs.h"
 #include "parallel.h"
-#include "ptr_abi.h"
 #include "ptr_debug.h"
 #include "scene_geometry.h"
 #include "vecmath.h"
 
 using namespace ptrk;
+using namespace ptrhost;
 
 namespace {
-
-struct HipError {
-    std::string message;
-};
-
-#define HIP_CHECK(expr)                                                                                     \
-    do {                                                                                                    \
-        hipError_t _e = (expr);                                                                             \
-        if (_e != hipSuccess) {                                                                             \
-            throw HipError{std::string(#expr) + ": " + hipGetErrorString(_e)};                              \
-        }                                                                                                   \
-    } while (0)
-
-void setErr(char* err, size_t cap, const std::string& msg) {
-    if (err && cap > 0) std::snprintf(err, cap, "%s", msg.c_str());
-}
-
-// Nothing may unwind across the C boundary: the BVH build allocates multi-GB vectors and starts threads
-// (std::bad_alloc, std::system_error), and the callers are ctypes / a C++ program built with another runtime.
-#define PTR_CATCH_ALL(err, cap)                                                                             \
-    catch (const HipError& e) {                                                                             \
-        setErr(err, cap, e.message);                                                                        \
-        return 1;                                                                                           \
-    }                                                                                                       \
-    catch (const std::exception& e) {                                                                       \
-        setErr(err, cap, std::string("exception: ") + e.what());                                            \
-        return 1;                                                                                           \
-    }                                                                                                       \
-    catch (...) {                                                                                           \
-        setErr(err, cap, "unknown exception");                                                              \
-        return 1;                                                                                           \
-    }
-
-template <typename T>
-struct DeviceBuffer {
-    T* ptr = nullptr;
-    size_t count = 0;
-    DeviceBuffer() = default;
-    DeviceBuffer(const DeviceBuffer&) = delete;
-    DeviceBuffer& operator=(const DeviceBuffer&) = delete;
-    ~DeviceBuffer() { release(); }
-    void release() {
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        count = 0;
-    }
-    void ensure(size_t n) {
-        if (n <= count && ptr) return;
-        release();
-        if (n == 0) n = 1;
-        HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&ptr), n * sizeof(T)));
-        count = n;
-    }
-    void upload(const T* src, size_t n) {
-        ensure(n);
-        if (n) HIP_CHECK(hipMemcpy(ptr, src, n * sizeof(T), hipMemcpyHostToDevice));
-    }
-};
 
 using ptr::float3;
 
@@ -102,87 +43,6 @@ void put4(std::vector<float>& dst, const float3& v, float w) {
     dst.push_back(v.z);
     dst.push_back(w);
 }
-
-float bitsToFloat(uint32_t u) {
-    float f;
-    std::memcpy(&f, &u, 4);
-    return f;
-}
-
-}  // namespace
-
-struct PtrDeviceScene {
-    int device = 0;
-    DeviceBuffer<uint4> qnodes;
-    DeviceBuffer<uint4> wnodes;   // PTR_WIDE_NODES=1: four-wide nodes (SceneView::wnodes)
-    DeviceBuffer<float4> nodes, tris, triNormals, spheres, materials, rects, rectLights, envRgba;
-    DeviceBuffer<uint2> sphereInfo;
-    DeviceBuffer<int32_t> lightIndexByRect;
-    DeviceBuffer<float2> envCond, envMarg, cone;
-    DeviceBuffer<float4> triUv, triTangent, texels, materialTex;
-    DeviceBuffer<uint4> texInfo;
-    DeviceBuffer<float> envPdf;
-    // PTR_METAL_ENV_LOD: the environment map's mip chain (EnvLodView::mips), built on the first render that sets the bit
-    DeviceBuffer<float4> envMips;
-    uint32_t envMipLevels = 0;   // 0: not built
-    SceneView view{};
-    uint64_t info[8] = {0};
-    double uploadSeconds = 0.0;
-    double timings[4] = {0.0, 0.0, 0.0, 0.0};   // geometry preparation (or cache read), shading tables, copies to the device, 1 = geometry came from a cache
-    uint64_t deviceTotalBytes = 0;        // hipDeviceProp_t::totalGlobalMem
-    bool hasRandomWalkMaterial = false;   // a type-5 material with sssParams.y >= 0.5 (Metal random-walk subsurface)
-
-    // render-time resources, grown on demand and kept across calls
-    DeviceBuffer<float4> state, recBuf, itemAccum;   // state: the four 16 B words of every slot (PathPool::ray0 / ray1 / thr / accum)
-    DeviceBuffer<float2> hit;
-    DeviceBuffer<uint32_t> flushItem, signature, tailList, tailWords;
-    DeviceBuffer<uint32_t> connectList, connectCounts;   // PathPool::connectList: per group a list and two sets of sub-list counters
-    DeviceBuffer<uint32_t> busyLists, busyCounts;        // PathPool::busyIn / busyOut: per group two lists and three sets of counters
-    // end of the frame: once the item queue is dry and at most this many slots are still alive, the remaining paths are finished by
-    // k_tail_run (one lane per path, no launches between bounces) instead of further extend / shade / connect rounds; 0 = never
-    uint64_t tailBelow = 512ull << 10;
-    uint64_t poolSlots = 32ull << 20;        // resident path slots at most (PTR_POOL_SLOTS)
-    // The pool is split into this many independent groups.  Two by default, each on a main stream (k_extend, k_shade) and a side stream
-    // on which the k_connect of an iteration runs beside the k_extend of the next (they share nothing: one reads the rays k_shade wrote,
-    // the other its connection records): four streams in flight, which is what the runtime's four hardware queues carry without
-    // serialising.  (Rounds 1-3 ran four groups of one stream each; profiles/r3_ab_connect_overlap.txt.)
-    // Frames of a few milliseconds (a pool of at most 8 Mi slots: config 1) keep four groups of one stream each: -6 % with two.
-    uint32_t poolGroups = 0;      // PTR_POOL_GROUPS (0: two groups, four for small pools)
-    bool connectOverlap = true;   // PTR_CONNECT_OVERLAP=0: k_connect on the group's own stream
-    uint32_t maxPoolGroups() const { return poolGroups ? poolGroups : 4u; }
-    uint32_t feederChunk = 256;   // slots per work-head claim while the pool is full (it grows as the pool drains)
-    std::vector<hipStream_t> groupStreams;   // streams of groups 1.. (group 0 runs on the caller's stream)
-    std::vector<hipEvent_t> groupEvents;
-    std::vector<hipStream_t> sideStreams;    // per group: the stream of its k_connect launches (see poolGroups)
-    std::vector<hipEvent_t> sideEvents;      // per group: k_shade of the iteration done / k_connect of the iteration done
-    int refillBelow = 40;
-    uint32_t spillLevels = 0;   // stack levels beyond the LDS part that the scene's tree can need (sizes the spill area)
-    uint32_t wideDepth = 0;     // levels of the four-wide tree (0: the scene has no four-wide nodes)
-    DeviceBuffer<uint4> medium;
-    DeviceBuffer<float> envLod;   // PTR_METAL_ENV_LOD: EnvLodView::slotLod
-    DeviceBuffer<uint32_t> scalars, pixelOfLocal, spill;
-    DeviceBuffer<uint2> itemReserve;
-    DeviceBuffer<uint32_t> itemHeads, zeros;
-    DeviceBuffer<uint64_t> counters;
-    DeviceBuffer<float> outBands;
-    DeviceBuffer<float4> rayBatch;
-    DeviceBuffer<PtrHit> hitBatch;
-    uint32_t* pinnedAlive = nullptr;
-    uint32_t traceGrid = 0;       // persistent blocks of the traversal kernels: fills every wave slot (also sizes the spill area)
-    uint32_t traceGridHalf = 0;   // ... of k_extend / k_connect when several pool groups run large launches side by side
-    // cached partition
-    uint32_t cachedW = 0, cachedH = 0, cachedPart = 0, cachedParts = 0, cachedLocalPixels = 0;
-
-    ~PtrDeviceScene() {
-        if (pinnedAlive) (void)hipHostFree(pinnedAlive);
-        for (hipStream_t st : groupStreams) (void)hipStreamDestroy(st);
-        for (hipEvent_t e : groupEvents) (void)hipEventDestroy(e);
-        for (hipStream_t st : sideStreams) (void)hipStreamDestroy(st);
-        for (hipEvent_t e : sideEvents) (void)hipEventDestroy(e);
-    }
-};
-
-namespace {
 
 // per-group scalars: [0] unused, [1] k_extend work head, [2] k_connect work head, [3] pad,
 //                    [4..19] ring of live-slot counters (one per iteration, written by k_extend at the end of a frame)
@@ -199,6 +59,10 @@ constexpr uint32_t kTexInfoWords = 20;   // kernels/texture.h kTexInfoVec4 uint4
 // depth d needs 3 ceil(d / 2) + 2 entries, not the worst case kTraversalStackDepth (1 GB of HBM per scene for 8 groups).
 size_t spillWordsPerGroup(const PtrDeviceScene& ds) { return static_cast<size_t>(ds.spillLevels) * ds.traceGrid * kTraceGridUnit; }
 
+}  // namespace
+
+namespace ptrhost {
+
 // 576 B MaterialData -> the 13 float4 the integrator reads (kernels/device_types.h MaterialSlot).
 void compactMaterial(const PtrMaterial& m, std::vector<float>& out) {
     const float* rows[kMaterialVec4] = {m.baseColorRoughness, m.typeEta,        m.emission,           m.conductorEta,
@@ -212,28 +76,6 @@ void compactMaterial(const PtrMaterial& m, std::vector<float>& out) {
         out.insert(out.end(), v, v + 4);
     }
 }
-
-// Device-independent half of a scene upload: geometry bake + BVH, compact materials, light list, environment tables.  Built once
-// and uploaded to every device a frame is rendered on (ptr_render_multi).
-struct PreparedScene {
-    ptr::PreparedGeometry pg;   // BVH, leaf-order arrays, four-wide nodes, node format: what a geometry cache file holds
-    std::vector<float> mats, lights;
-    std::vector<int32_t> lightIndexByRect;
-    uint32_t lightCount = 0;
-    bool lightsHaveTriangles = true;   // every rectangle light found its two triangles in the geometry (always, unless degenerate)
-    bool hasRandomWalkMaterial = false;
-    ptr::EnvImportanceDistribution envDist;
-    bool hasEnvDist = false;
-    // material textures (kernels/texture.h): every level of every texture in one array, the per-texture records, and the
-    // per-material texture records; empty when the scene has no textures
-    std::vector<float> texels;
-    std::vector<uint32_t> texInfo;
-    std::vector<float> materialTex;
-    double geometrySeconds = 0.0;   // bake + BVH + leaf order + wide nodes, or reading them from a geometry cache
-    double shadingSeconds = 0.0;    // materials, lights, environment tables, texture mips
-    bool geometryFromCache = false;
-    double seconds = 0.0;           // both
-};
 
 // Mip chain of one texture appended to `texels`: level l + 1 halves both sizes (at least 1) and averages the 2x2 block of level
 // l under each of its texels, the second tap clamped at the edge of odd-sized levels; sums in the order ((a + b) + (c + d)) * 0.25.
@@ -272,6 +114,32 @@ void appendTextureWithMips(const PtrTexture& t, std::vector<float>& texels, std:
         h = nh;
     }
 }
+
+}  // namespace ptrhost
+
+namespace {
+
+// Device-independent half of a scene upload: geometry bake + BVH, compact materials, light list, environment tables.  Built once
+// and uploaded to every device a frame is rendered on (ptr_render_multi).
+struct PreparedScene {
+    ptr::PreparedGeometry pg;   // BVH, leaf-order arrays, four-wide nodes, node format: what a geometry cache file holds
+    std::vector<float> mats, lights;
+    std::vector<int32_t> lightIndexByRect;
+    uint32_t lightCount = 0;
+    bool lightsHaveTriangles = true;   // every rectangle light found its two triangles in the geometry (always, unless degenerate)
+    bool hasRandomWalkMaterial = false;
+    ptr::EnvImportanceDistribution envDist;
+    bool hasEnvDist = false;
+    // material textures (kernels/texture.h): every level of every texture in one array, the per-texture records, and the
+    // per-material texture records; empty when the scene has no textures
+    std::vector<float> texels;
+    std::vector<uint32_t> texInfo;
+    std::vector<float> materialTex;
+    double geometrySeconds = 0.0;   // bake + BVH + leaf order + wide nodes, or reading them from a geometry cache
+    double shadingSeconds = 0.0;    // materials, lights, environment tables, texture mips
+    bool geometryFromCache = false;
+    double seconds = 0.0;           // both
+};
 
 // The geometry half of the preparation: everything a geometry cache file holds (host/geometry_cache.h).
 void prepareGeometry(const PtrSceneDesc& desc, ptr::PreparedGeometry& pg) {
@@ -517,35 +385,6 @@ void uploadScene(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceSce
     if (knobs.verboseBuild) std::fprintf(stderr, "[upload] prepare %.2f s, copies to the device %.2f s\n", ps.seconds, copySeconds);
 }
 
-// PTR_METAL_ENV_LOD: the mip chain of the scene's environment map by the rule of the material textures (appendTextureWithMips), once per
-// device scene and only when a render asks for it: scenes and renders without the bit keep their memory and upload time.  Level 0 stays
-// where it is (envRgba); the device gets the chain's record (kernels/texture.h layout, offsets counted from the first texel after it)
-// and levels 1...  Returns the milliseconds it took (0 when the chain was there).
-double ensureEnvMips(PtrDeviceScene& ds) {
-    if (ds.envMipLevels > 0u || ds.view.envRgba == nullptr || ds.view.envWidth == 0u || ds.view.envHeight == 0u) return 0.0;
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_CHECK(hipSetDevice(ds.device));
-    const uint32_t w = ds.view.envWidth, h = ds.view.envHeight;
-    const size_t level0 = static_cast<size_t>(w) * h;
-    std::vector<float> rgba(level0 * 4u);
-    HIP_CHECK(hipMemcpy(rgba.data(), ds.view.envRgba, level0 * sizeof(float4), hipMemcpyDeviceToHost));
-    const PtrTexture t{rgba.data(), w, h, 0u, 0u, 1u, 0u};   // repeat / repeat, linear
-    std::vector<float> chain;
-    std::vector<uint32_t> info;
-    appendTextureWithMips(t, chain, info);
-    const uint32_t levels = info[2];
-    for (uint32_t l = 1; l < levels; ++l) info[4 + l] -= static_cast<uint32_t>(level0);   // levels 1.. move down over level 0
-    static_assert(kTexInfoWords == 4u * 5u, "texture record layout");
-    std::vector<float> upload(kTexInfoWords + (chain.size() - level0 * 4u));
-    std::memcpy(upload.data(), info.data(), kTexInfoWords * sizeof(uint32_t));
-    std::copy(chain.begin() + static_cast<std::ptrdiff_t>(level0 * 4u), chain.end(), upload.begin() + kTexInfoWords);
-    ds.envMips.upload(reinterpret_cast<const float4*>(upload.data()), upload.size() / 4u);
-    ds.envMipLevels = levels;
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    if (ptr::readKnobs().verboseBuild) std::fprintf(stderr, "[upload] environment mip chain: %ux%u, %u levels, %.2f ms\n", w, h, levels, ms);
-    return ms;
-}
-
 void buildScene(const PtrSceneDesc& desc, PtrDeviceScene& ds, const char* cachePath = nullptr) {
     PreparedScene ps;
     prepareScene(desc, ps, cachePath);
@@ -590,6 +429,39 @@ void buildCamera(const PtrSettings& s, CameraParams& c) {
     c.lensRadius = focus * std::tan((defocus * 0.5f) * (kPiF / 180.0f));
 }
 
+}  // namespace
+
+namespace ptrhost {
+
+// PTR_METAL_ENV_LOD: the mip chain of the scene's environment map by the rule of the material textures (appendTextureWithMips), once per
+// device scene and only when a render asks for it: scenes and renders without the bit keep their memory and upload time.  Level 0 stays
+// where it is (envRgba); the device gets the chain's record (kernels/texture.h layout, offsets counted from the first texel after it)
+// and levels 1...  Returns the milliseconds it took (0 when the chain was there).
+double ensureEnvMips(PtrDeviceScene& ds) {
+    if (ds.envMipLevels > 0u || ds.view.envRgba == nullptr || ds.view.envWidth == 0u || ds.view.envHeight == 0u) return 0.0;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_CHECK(hipSetDevice(ds.device));
+    const uint32_t w = ds.view.envWidth, h = ds.view.envHeight;
+    const size_t level0 = static_cast<size_t>(w) * h;
+    std::vector<float> rgba(level0 * 4u);
+    HIP_CHECK(hipMemcpy(rgba.data(), ds.view.envRgba, level0 * sizeof(float4), hipMemcpyDeviceToHost));
+    const PtrTexture t{rgba.data(), w, h, 0u, 0u, 1u, 0u};   // repeat / repeat, linear
+    std::vector<float> chain;
+    std::vector<uint32_t> info;
+    appendTextureWithMips(t, chain, info);
+    const uint32_t levels = info[2];
+    for (uint32_t l = 1; l < levels; ++l) info[4 + l] -= static_cast<uint32_t>(level0);   // levels 1.. move down over level 0
+    static_assert(kTexInfoWords == 4u * 5u, "texture record layout");
+    std::vector<float> upload(kTexInfoWords + (chain.size() - level0 * 4u));
+    std::memcpy(upload.data(), info.data(), kTexInfoWords * sizeof(uint32_t));
+    std::copy(chain.begin() + static_cast<std::ptrdiff_t>(level0 * 4u), chain.end(), upload.begin() + kTexInfoWords);
+    ds.envMips.upload(reinterpret_cast<const float4*>(upload.data()), upload.size() / 4u);
+    ds.envMipLevels = levels;
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    if (ptr::readKnobs().verboseBuild) std::fprintf(stderr, "[upload] environment mip chain: %ux%u, %u levels, %.2f ms\n", w, h, levels, ms);
+    return ms;
+}
+
 void fillRenderParams(const PtrSettings& s, uint32_t spp, RenderParams& rp) {
     std::memset(&rp, 0, sizeof(rp));
     buildCamera(s, rp.cam);
@@ -627,6 +499,13 @@ void fillRenderParams(const PtrSettings& s, uint32_t spp, RenderParams& rp) {
     rp.sssMaxSteps = std::max(s.sssMaxSteps, 1u);
 }
 
+// Launch configuration of the one-off traversal kernels (ray batches, AOVs, debug queries): whole grid, group 0's heads and spill area
+LaunchConfig coldLaunchConfig(const PtrDeviceScene& ds) { return LaunchConfig{ds.traceGrid, ds.spill.ptr, ds.scalars.ptr + 1, ds.refillBelow}; }
+
+}  // namespace ptrhost
+
+namespace {
+
 // Local pixel order of a partition: its PTR_BAND_ROWS-row bands top to bottom, each walked in 8x8 blocks so the
 // 64 lanes of a wave start with a compact, coherent bundle of primary rays.
 void partitionPixels(uint32_t width, uint32_t height, uint32_t part, uint32_t parts, std::vector<uint32_t>& out) {
@@ -650,9 +529,6 @@ void partitionPixels(uint32_t width, uint32_t height, uint32_t part, uint32_t pa
 uint64_t itemBudgetBytes(const PtrDeviceScene& ds) {
     return std::max<uint64_t>(64ull << 20, std::min<uint64_t>(16ull << 30, ds.deviceTotalBytes / 4u));
 }
-
-// Launch configuration of the one-off traversal kernels (ray batches, AOVs, debug queries): whole grid, group 0's heads and spill area
-LaunchConfig coldLaunchConfig(const PtrDeviceScene& ds) { return LaunchConfig{ds.traceGrid, ds.spill.ptr, ds.scalars.ptr + 1, ds.refillBelow}; }
 
 // Adds the per-launch figures of `b` to `a`: kernel times, k_extend launches, samples.
 void addLaunchStats(PtrRenderStats& a, const PtrRenderStats& b) {
@@ -1168,6 +1044,10 @@ void renderPass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, u
     if (stats) passStats(ds, rp, timer.spans, count, knobs, seconds, *stats);
 }
 
+}  // namespace
+
+namespace ptrhost {
+
 // A frame.  One accumulator per sample has to fit in a quarter of the free device memory (at most 16 GiB); a frame with
 // more samples than that is rendered in several passes of equal sample counts whose per-pixel sums add up in the output
 // buffer.  (Folding C samples into one work item instead keeps one pass but lengthens the end-of-frame drain: 4096 spp of
@@ -1214,7 +1094,7 @@ void renderBands(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, 
     }
 }
 
-}  // namespace
+}  // namespace ptrhost
 
 extern "C" {
 
@@ -1544,43 +1424,30 @@ int ptr_debug_render_multi_on(const PtrSceneDesc* scene, const PtrSettings* sett
 
 int ptr_trace_rays(PtrDeviceScene* scene, const float* rays, uint64_t n, int any_hit, PtrHit* out, PtrRenderStats* stats,
                    char* err, size_t err_cap) {
-    if (!scene || (!rays && n) || (!out && n)) {
-        setErr(err, err_cap, "ptr_trace_rays: null argument");
-        return 1;
-    }
-    try {
-        HIP_CHECK(hipSetDevice(scene->device));
-        if (n == 0) return 0;
+    return deviceCall("ptr_trace_rays", scene, scene && (rays || !n) && (out || !n), err, err_cap, [&] {
+        if (n == 0) return;
         scene->rayBatch.upload(reinterpret_cast<const float4*>(rays), n * 2);
         scene->hitBatch.ensure(n);
         HIP_CHECK(hipMemset(scene->counters.ptr, 0, sizeof(uint64_t) * kCounterSlots));
         launchTraceRays(scene->view, scene->rayBatch.ptr, n, any_hit != 0, scene->hitBatch.ptr, coldLaunchConfig(*scene), scene->counters.ptr, nullptr);
-        HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipMemcpy(out, scene->hitBatch.ptr, n * sizeof(PtrHit), hipMemcpyDeviceToHost));
+        scene->hitBatch.download(out, n);
         if (stats) {
             std::memset(stats, 0, sizeof(*stats));
             uint64_t c[kCounterSlots];
-            HIP_CHECK(hipMemcpy(c, scene->counters.ptr, sizeof(c), hipMemcpyDeviceToHost));
+            scene->counters.download(c, kCounterSlots);
             stats->nodesVisited = c[kCntExtendNodes] + c[kCntShadowNodes];
             stats->leafPrimTests = c[kCntExtendPrims] + c[kCntShadowPrims];
             stats->extendRays = any_hit ? 0 : n;
             stats->shadowRays = any_hit ? n : 0;
         }
-        return 0;
-    }
-    PTR_CATCH_ALL(err, err_cap)
+    });
 }
 
 int ptr_render_aovs(PtrDeviceScene* scene, const PtrSettings* settings, uint32_t sample_index, float* out_albedo, float* out_normal,
                     char* err, size_t err_cap) {
-    if (!scene || !settings) {
-        setErr(err, err_cap, "ptr_render_aovs: null argument");
-        return 1;
-    }
-    try {
+    return deviceCall("ptr_render_aovs", scene, scene && settings, err, err_cap, [&] {
         if (settings->width == 0 || settings->height == 0) throw HipError{"render size must be non-zero"};
-        HIP_CHECK(hipSetDevice(scene->device));
         RenderParams rp;
         fillRenderParams(*settings, 1u, rp);
         const size_t pixels = static_cast<size_t>(settings->width) * settings->height;
@@ -1588,462 +1455,10 @@ int ptr_render_aovs(PtrDeviceScene* scene, const PtrSettings* settings, uint32_t
         albedo.ensure(pixels);
         normal.ensure(pixels);
         launchAovs(rp, scene->view, sample_index, albedo.ptr, normal.ptr, coldLaunchConfig(*scene), nullptr);
-        HIP_CHECK(hipGetLastError());
         HIP_CHECK(hipDeviceSynchronize());
-        if (out_albedo) HIP_CHECK(hipMemcpy(out_albedo, albedo.ptr, pixels * sizeof(float4), hipMemcpyDeviceToHost));
-        if (out_normal) HIP_CHECK(hipMemcpy(out_normal, normal.ptr, pixels * sizeof(float4), hipMemcpyDeviceToHost));
-        return 0;
-    }
-    PTR_CATCH_ALL(err, err_cap)
-}
-
-// ---- test-only entry points (include/ptr_debug.h) ----
-
-int ptr_debug_render_signatures(PtrDeviceScene* scene, const PtrSettings* settings, float* out_rgb, uint32_t* out_signature, char* err,
-                                size_t err_cap) {
-    if (!scene || !settings || !out_signature) {
-        setErr(err, err_cap, "ptr_debug_render_signatures: null argument");
-        return 1;
-    }
-    try {
-        const size_t pixels = static_cast<size_t>(settings->width) * settings->height;
-        const size_t floats = static_cast<size_t>(ptr_part_band_count(settings->height, 0, 1)) * PTR_BAND_ROWS * settings->width * 3u;
-        HIP_CHECK(hipSetDevice(scene->device));
-        scene->outBands.ensure(floats);
-        PtrRenderStats stats{};
-        renderBands(*scene, *settings, 1u, 0u, 1u, scene->outBands.ptr, nullptr, 1, &stats);   // counting build, 1 spp: item = local pixel
-        if (out_rgb) HIP_CHECK(hipMemcpy(out_rgb, scene->outBands.ptr, pixels * 3u * sizeof(float), hipMemcpyDeviceToHost));
-        std::vector<float4> items(pixels);
-        std::vector<uint32_t> pixelOfLocal(pixels);
-        HIP_CHECK(hipMemcpy(items.data(), scene->itemAccum.ptr, pixels * sizeof(float4), hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(pixelOfLocal.data(), scene->pixelOfLocal.ptr, pixels * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        for (size_t lp = 0; lp < pixels; ++lp) {
-            uint32_t bits;
-            std::memcpy(&bits, &items[lp].w, sizeof(bits));
-            out_signature[pixelOfLocal[lp]] = bits;
-        }
-        return 0;
-    }
-    PTR_CATCH_ALL(err, err_cap)
-}
-
-int ptr_debug_texture_sample(PtrDeviceScene* scene, uint32_t texture, const float* in, uint64_t n, float* out, char* err, size_t err_cap) {
-    if (!scene || (!in && n) || (!out && n)) {
-        setErr(err, err_cap, "ptr_debug_texture_sample: null argument");
-        return 1;
-    }
-    try {
-        HIP_CHECK(hipSetDevice(scene->device));
-        if (n == 0) return 0;
-        DeviceBuffer<float> din;
-        DeviceBuffer<float4> dout;
-        din.upload(in, n * 3);
-        dout.ensure(n);
-        launchDebugTexSample(scene->view, texture, din.ptr, n, dout.ptr, nullptr);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(out, dout.ptr, n * sizeof(float4), hipMemcpyDeviceToHost));
-        return 0;
-    }
-    PTR_CATCH_ALL(err, err_cap)
-}
-
-int ptr_debug_texture_sample_grad(PtrDeviceScene* scene, uint32_t texture, const float* in, uint64_t n, float* out, char* err, size_t err_cap) {
-    if (!scene || (!in && n) || (!out && n)) {
-        setErr(err, err_cap, "ptr_debug_texture_sample_grad: null argument");
-        return 1;
-    }
-    try {
-        HIP_CHECK(hipSetDevice(scene->device));
-        if (n == 0) return 0;
-        DeviceBuffer<float> din;
-        DeviceBuffer<float4> dout;
-        din.upload(in, n * 6);
-        dout.ensure(n);
-        launchDebugTexSampleGrad(scene->view, texture, din.ptr, n, dout.ptr, nullptr);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(out, dout.ptr, n * sizeof(float4), hipMemcpyDeviceToHost));
-        return 0;
-    }
-    PTR_CATCH_ALL(err, err_cap)
-}
-
-int ptr_debug_first_hit_textures(PtrDeviceScene* scene, const PtrSettings* settings, const uint32_t* xys, uint64_t n, float* out, char* err,
-                                 size_t err_cap) {
-    if (!scene || !settings || (!xys && n) || (!out && n)) {
-        setErr(err, err_cap, "ptr_debug_first_hit_textures: null argument");
-        return 1;
-    }
-    try {
-        HIP_CHECK(hipSetDevice(scene->device));
-        if (n == 0) return 0;
-        RenderParams rp;
-        fillRenderParams(*settings, 1, rp);
-        constexpr uint64_t kFloats = 36;
-        DeviceBuffer<uint32_t> dxy;
-        DeviceBuffer<float> dout;
-        dxy.upload(xys, n * 3);
-        dout.ensure(n * kFloats);
-        launchDebugFirstHit(rp, scene->view, dxy.ptr, n, dout.ptr, coldLaunchConfig(*scene), nullptr);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(out, dout.ptr, n * kFloats * sizeof(float), hipMemcpyDeviceToHost));
-        return 0;
-    }
-    PTR_CATCH_ALL(err, err_cap)
-}
-
-int ptr_debug_surface_hits(PtrDeviceScene* scene, const float* in, uint64_t n, float* out, char* err, size_t err_cap) {
-    if (!scene || (!in && n) || (!out && n)) {
-        setErr(err, err_cap, "ptr_debug_surface_hits: null argument");
-        return 1;
-    }
-    try {
-        HIP_CHECK(hipSetDevice(scene->device));
-        if (n == 0) return 0;
-        DeviceBuffer<float> din, dout;
-        din.upload(in, n * 9);
-        dout.ensure(n * 16);
-        launchDebugSurfaceHits(scene->view, din.ptr, n, dout.ptr, coldLaunchConfig(*scene), nullptr);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(out, dout.ptr, n * 16 * sizeof(float), hipMemcpyDeviceToHost));
-        return 0;
-    }
-    PTR_CATCH_ALL(err, err_cap)
-}
-
-}  // extern "C"
-
-namespace {
-
-// The production traversal kernels on a batch of rays (ptr_debug_extend_rays / ptr_debug_connect_rays): both trace from kEps, which the
-// batch must state; info = {node format launched (traversalNodeFormat), stack limit, four-wide depth, LDS stack levels}.
-bool checkProbeRays(const float* rays, uint64_t n, bool infiniteTmax, const char* who, char* err, size_t err_cap) {
-    if (n >= (1ull << kConnectMaskShift)) {
-        setErr(err, err_cap, std::string(who) + ": at most 2^27 - 1 rays");
-        return false;
-    }
-    for (uint64_t i = 0; i < n; ++i) {
-        const float tmin = rays[i * 8 + 3], tmax = rays[i * 8 + 7];
-        if (tmin != 1.0e-4f || (infiniteTmax && !(std::isinf(tmax) && tmax > 0.0f))) {
-            setErr(err, err_cap, std::string(who) + ": ray " + std::to_string(i) + " has tmin " + std::to_string(tmin) + " / tmax " +
-                                     std::to_string(tmax) + (infiniteTmax ? "; the kernel traces from 1e-4 to infinity" : "; the kernel traces from 1e-4"));
-            return false;
-        }
-    }
-    return true;
-}
-
-void probeInfo(const PtrDeviceScene& ds, bool count, uint32_t info[4]) {
-    info[0] = static_cast<uint32_t>(traversalNodeFormat(ds.view, count));
-    info[1] = ds.view.stackLimit;
-    info[2] = ds.view.useWide ? ds.wideDepth : 0u;
-    info[3] = kLdsStackLevels;
-}
-
-// the render's launch configuration of group 0 (coldLaunchConfig plus the scene's feeder chunk), with its work heads zeroed
-LaunchConfig probeLaunchConfig(const PtrDeviceScene& ds) {
-    LaunchConfig cfg = coldLaunchConfig(ds);
-    cfg.feederChunk = ds.feederChunk;
-    HIP_CHECK(hipMemset(cfg.workCounters, 0, 2 * sizeof(uint32_t)));
-    return cfg;
-}
-
-}  // namespace
-
-extern "C" {
-
-int ptr_debug_extend_rays(PtrDeviceScene* scene, const float* rays, uint64_t n, int count, PtrHit* out, uint32_t info[4], char* err,
-                          size_t err_cap) {
-    if (!scene || (!rays && n) || (!out && n) || !info) {
-        setErr(err, err_cap, "ptr_debug_extend_rays: null argument");
-        return 1;
-    }
-    if (!checkProbeRays(rays, n, true, "ptr_debug_extend_rays", err, err_cap)) return 1;
-    try {
-        HIP_CHECK(hipSetDevice(scene->device));
-        probeInfo(*scene, count != 0, info);
-        if (n == 0) return 0;
-        // the slots as k_shade leaves them for k_extend: ray0 = (origin, d.x), ray1 = (d.y, d.z, pdf, flags), alive; hit words that k_extend
-        // must overwrite
-        std::vector<float4> state(n * 2);
-        std::vector<float2> hits(n, make_float2(-2.0f, bitsToFloat(0xFFFFFFFEu)));
-        for (uint64_t i = 0; i < n; ++i) {
-            const float* r = rays + i * 8;
-            state[i] = make_float4(r[0], r[1], r[2], r[4]);
-            state[n + i] = make_float4(r[5], r[6], 0.0f, bitsToFloat(kFlagAlive));
-        }
-        DeviceBuffer<float4> dState, dRays;
-        DeviceBuffer<float2> dHit;
-        DeviceBuffer<PtrHit> dOut;
-        dState.upload(state.data(), state.size());
-        dHit.upload(hits.data(), hits.size());
-        dRays.upload(reinterpret_cast<const float4*>(rays), n * 2);
-        dOut.ensure(n);
-        PathPool pool{};
-        pool.ray0 = dState.ptr;
-        pool.ray1 = dState.ptr + n;
-        pool.hit = dHit.ptr;
-        pool.slots = static_cast<uint32_t>(n);
-        pool.recStride = static_cast<uint32_t>(n);
-        if (count) {
-            HIP_CHECK(hipMemset(scene->counters.ptr, 0, sizeof(uint64_t) * kCounterSlots));
-            pool.counters = scene->counters.ptr;
-        }
-        launchExtend(scene->view, pool, probeLaunchConfig(*scene), nullptr, count != 0, nullptr);
-        HIP_CHECK(hipGetLastError());
-        launchDebugHitRecords(scene->view, dRays.ptr, dHit.ptr, n, static_cast<uint32_t>(scene->info[2]), static_cast<uint32_t>(scene->info[3]),
-                              dOut.ptr, nullptr);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipMemcpy(out, dOut.ptr, n * sizeof(PtrHit), hipMemcpyDeviceToHost));
-        return 0;
-    }
-    PTR_CATCH_ALL(err, err_cap)
-}
-
-int ptr_debug_connect_rays(PtrDeviceScene* scene, const float* rays, const uint32_t* ignore_light, uint64_t n, uint32_t records_per_slot,
-                           uint32_t* occluded, uint32_t info[4], char* err, size_t err_cap) {
-    if (!scene || (!rays && n) || (!occluded && n) || !info) {
-        setErr(err, err_cap, "ptr_debug_connect_rays: null argument");
-        return 1;
-    }
-    if (records_per_slot < 1u || records_per_slot > 4u) {
-        setErr(err, err_cap, "ptr_debug_connect_rays: records_per_slot must be 1..4");
-        return 1;
-    }
-    if (!checkProbeRays(rays, n, false, "ptr_debug_connect_rays", err, err_cap)) return 1;
-    for (uint64_t i = 0; ignore_light && i < n; ++i) {
-        if (ignore_light[i] != 0xFFFFFFFFu && ignore_light[i] >= scene->view.rectLightCount) {
-            setErr(err, err_cap, "ptr_debug_connect_rays: ray " + std::to_string(i) + " ignores light " + std::to_string(ignore_light[i]) +
-                                     " of " + std::to_string(scene->view.rectLightCount));
-            return 1;
-        }
-    }
-    try {
-        HIP_CHECK(hipSetDevice(scene->device));
-        probeInfo(*scene, false, info);
-        if (n == 0) return 0;
-        // the ignore word of a kind-3 record: the meta word of the light's own triangles (row 6 of its record, T[1].w of half 0), where
-        // k_shade takes it from (rectLightSurface)
-        std::vector<float4> lights(static_cast<size_t>(scene->view.rectLightCount) * kRectLightVec4);
-        if (!lights.empty()) HIP_CHECK(hipMemcpy(lights.data(), scene->view.rectLights, lights.size() * sizeof(float4), hipMemcpyDeviceToHost));
-        // ray i is record i % records_per_slot of slot i / records_per_slot; the record arrays are one allocation indexed as k_connect
-        // indexes them: field f of record slot k at recBase[(k*4 + f)*slots + slot]
-        const uint64_t slots = (n + records_per_slot - 1u) / records_per_slot;
-        std::vector<float4> rec(slots * kRecSlots * 4u, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-        for (uint64_t i = 0; i < n; ++i) {
-            const float* r = rays + i * 8;
-            const uint64_t slot = i / records_per_slot, k = i % records_per_slot;
-            const uint32_t light = ignore_light ? ignore_light[i] : 0xFFFFFFFFu;
-            const uint32_t kind = light == 0xFFFFFFFFu ? 0u : 3u;
-            rec[(k * 4u + 0u) * slots + slot] = make_float4(r[0], r[1], r[2], r[7]);
-            rec[(k * 4u + 1u) * slots + slot] = make_float4(r[4], r[5], r[6], bitsToFloat(kind));
-            rec[(k * 4u + 2u) * slots + slot] = make_float4(1.0f, 1.0f, 1.0f, 0.0f);
-            if (kind == 3u) rec[(k * 4u + 3u) * slots + slot] = make_float4(lights[static_cast<size_t>(light) * kRectLightVec4 + 6u].w, 0.0f, 0.0f, 0.0f);
-        }
-        // the slots spread over the connect sub-lists unevenly, as the waves of k_shade append them, with some sub-lists left empty
-        std::vector<std::vector<uint32_t>> queues(kConnectQueues);
-        for (uint64_t slot = 0; slot < slots; ++slot) {
-            uint32_t q = static_cast<uint32_t>(((slot * 2654435761ull) >> 7) % 97u) % kConnectQueues;
-            if (q % 5u == 2u) q = (q * 3u + 1u) % kConnectQueues;
-            if (q % 5u == 2u) q = (q + 1u) % kConnectQueues;
-            const uint32_t records = static_cast<uint32_t>(std::min<uint64_t>(records_per_slot, n - slot * records_per_slot));
-            queues[q].push_back(static_cast<uint32_t>(slot) | (((1u << records) - 1u) << kConnectMaskShift));
-        }
-        size_t region = 1;
-        for (const auto& q : queues) region = std::max(region, q.size());
-        std::vector<uint32_t> list(region * kConnectQueues, 0u), counts(kConnectQueues * kConnectCountStride, 0u);
-        for (uint32_t q = 0; q < kConnectQueues; ++q) {
-            std::copy(queues[q].begin(), queues[q].end(), list.begin() + static_cast<size_t>(q) * region);
-            counts[q * kConnectCountStride] = static_cast<uint32_t>(queues[q].size());
-        }
-        DeviceBuffer<float4> dRec;
-        DeviceBuffer<uint32_t> dList, dCounts;
-        dRec.upload(rec.data(), rec.size());
-        dList.upload(list.data(), list.size());
-        dCounts.upload(counts.data(), counts.size());
-        PathPool pool{};
-        for (uint32_t k = 0; k < kRecSlots; ++k) {
-            pool.rec[k] = ShadowRecordView{dRec.ptr + (k * 4u + 0u) * slots, dRec.ptr + (k * 4u + 1u) * slots, dRec.ptr + (k * 4u + 2u) * slots,
-                                           dRec.ptr + (k * 4u + 3u) * slots};
-        }
-        pool.slots = static_cast<uint32_t>(slots);
-        pool.recStride = static_cast<uint32_t>(slots);
-        pool.connectList = dList.ptr;
-        pool.connectCount = dCounts.ptr;
-        pool.connectRegion = static_cast<uint32_t>(region);
-        RenderParams rp{};   // MNEE off: launchConnect launches k_connect alone
-        launchConnect(rp, scene->view, pool, probeLaunchConfig(*scene), false, nullptr);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipDeviceSynchronize());
-        HIP_CHECK(hipMemcpy(rec.data(), dRec.ptr, rec.size() * sizeof(float4), hipMemcpyDeviceToHost));
-        for (uint64_t i = 0; i < n; ++i) {
-            const float4 a = rec[((i % records_per_slot) * 4u + 2u) * slots + i / records_per_slot];
-            occluded[i] = (a.x == 0.0f && a.y == 0.0f && a.z == 0.0f) ? 1u : 0u;
-        }
-        return 0;
-    }
-    PTR_CATCH_ALL(err, err_cap)
-}
-
-int ptr_debug_exact_division(uint32_t d, const uint32_t* n, uint64_t count, uint32_t* out) {
-    if (d == 0u || (!n && count) || (!out && count)) return 1;
-    const DivU32 by = makeDivU32(d);
-    for (uint64_t i = 0; i < count; ++i) out[i] = by.quotient(n[i]);
-    return 0;
-}
-
-int ptr_debug_shade_kernel_set(const PtrDeviceScene* scene, const PtrSettings* settings, int count, uint32_t* out) {
-    if (!scene || !settings || !out) return 1;
-    RenderParams rp;
-    fillRenderParams(*settings, 1, rp);
-    *out = shadeKernelSet(rp, scene->view, count != 0);
-    return 0;
-}
-
-int ptr_debug_eval_bsdf(const PtrMaterial* material, const PtrSettings* settings, const float* in, uint64_t n, float* out,
-                        char* err, size_t err_cap) {
-    try {
-        if (ptr_device_count() < 1) throw HipError{"no HIP device (the HIP path has no CPU fallback)"};
-        HIP_CHECK(hipSetDevice(0));
-        std::vector<float> m;
-        compactMaterial(*material, m);
-        RenderParams rp;
-        fillRenderParams(*settings, 1, rp);
-        DeviceBuffer<float4> dm;
-        DeviceBuffer<float> din, dout;
-        dm.upload(reinterpret_cast<const float4*>(m.data()), kMaterialVec4);
-        din.upload(in, n * 12);
-        dout.ensure(n * 5);
-        launchDebugEvalBsdf(dm.ptr, rp, din.ptr, n, dout.ptr, nullptr);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(out, dout.ptr, n * 5 * sizeof(float), hipMemcpyDeviceToHost));
-        return 0;
-    }
-    PTR_CATCH_ALL(err, err_cap)
-}
-
-int ptr_debug_sample_bsdf(const PtrMaterial* material, const PtrSettings* settings, const float* in, const uint32_t* front_face,
-                          const uint32_t* rng_states, uint64_t n, float* out, uint32_t* out_states, char* err, size_t err_cap) {
-    try {
-        if (ptr_device_count() < 1) throw HipError{"no HIP device (the HIP path has no CPU fallback)"};
-        HIP_CHECK(hipSetDevice(0));
-        std::vector<float> m;
-        compactMaterial(*material, m);
-        RenderParams rp;
-        fillRenderParams(*settings, 1, rp);
-        DeviceBuffer<float4> dm;
-        DeviceBuffer<float> din, dout;
-        DeviceBuffer<uint32_t> dfront, drng, drngOut;
-        dm.upload(reinterpret_cast<const float4*>(m.data()), kMaterialVec4);
-        din.upload(in, n * 9);
-        dfront.upload(front_face, n);
-        drng.upload(rng_states, n);
-        dout.ensure(n * 8);
-        drngOut.ensure(n);
-        launchDebugSampleBsdf(dm.ptr, rp, din.ptr, dfront.ptr, drng.ptr, n, dout.ptr, drngOut.ptr, nullptr);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(out, dout.ptr, n * 8 * sizeof(float), hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(out_states, drngOut.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        return 0;
-    }
-    PTR_CATCH_ALL(err, err_cap)
-}
-
-int ptr_debug_sample_lobes(const PtrMaterial* material, const PtrSettings* settings, const float* in, const uint32_t* front_face,
-                           const uint32_t* rng_states, uint64_t n, float* out, float* out_sample, uint32_t* out_states, float* env_roughness,
-                           char* err, size_t err_cap) {
-    try {
-        if (ptr_device_count() < 1) throw HipError{"no HIP device (the HIP path has no CPU fallback)"};
-        HIP_CHECK(hipSetDevice(0));
-        std::vector<float> m;
-        compactMaterial(*material, m);
-        RenderParams rp;
-        fillRenderParams(*settings, 1, rp);
-        DeviceBuffer<float4> dm;
-        DeviceBuffer<float> din, dout, dsample;
-        DeviceBuffer<uint32_t> dfront, drng, drngOut;
-        dm.upload(reinterpret_cast<const float4*>(m.data()), kMaterialVec4);
-        din.upload(in, n * 9);
-        dfront.upload(front_face, n);
-        drng.upload(rng_states, n);
-        dout.ensure(n * 3 + 1);
-        dsample.ensure(n * 8);
-        drngOut.ensure(n);
-        if (n > 0) {
-            launchDebugSampleLobes(dm.ptr, rp, din.ptr, dfront.ptr, drng.ptr, n, dout.ptr, dsample.ptr, drngOut.ptr, nullptr);
-            HIP_CHECK(hipGetLastError());
-        }
-        std::vector<float> o(n * 3 + 1, 0.0f);
-        HIP_CHECK(hipMemcpy(o.data(), dout.ptr, o.size() * sizeof(float), hipMemcpyDeviceToHost));
-        if (out) std::memcpy(out, o.data(), n * 3 * sizeof(float));
-        if (env_roughness) *env_roughness = o[n * 3];
-        if (out_sample) HIP_CHECK(hipMemcpy(out_sample, dsample.ptr, n * 8 * sizeof(float), hipMemcpyDeviceToHost));
-        if (out_states) HIP_CHECK(hipMemcpy(out_states, drngOut.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        return 0;
-    }
-    PTR_CATCH_ALL(err, err_cap)
-}
-
-int ptr_debug_env_lookup(PtrDeviceScene* scene, const PtrSettings* settings, const float* in, uint64_t n, float* out, char* err, size_t err_cap) {
-    if (!scene || !settings || (!in && n) || (!out && n)) {
-        setErr(err, err_cap, "ptr_debug_env_lookup: null argument");
-        return 1;
-    }
-    try {
-        HIP_CHECK(hipSetDevice(scene->device));
-        if (scene->view.envWidth == 0u) throw HipError{"ptr_debug_env_lookup: the scene has no environment map"};
-        ensureEnvMips(*scene);
-        if (n == 0) return 0;
-        RenderParams rp;
-        fillRenderParams(*settings, 1, rp);
-        const EnvLodView env{scene->envMips.ptr, nullptr, scene->envMipLevels, 0u};
-        DeviceBuffer<float4> din, dout;
-        din.upload(reinterpret_cast<const float4*>(in), n);
-        dout.ensure(n);
-        launchDebugEnvLookup(rp, scene->view, env, din.ptr, n, dout.ptr, nullptr);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(out, dout.ptr, n * sizeof(float4), hipMemcpyDeviceToHost));
-        return 0;
-    }
-    PTR_CATCH_ALL(err, err_cap)
-}
-
-int ptr_debug_env_mips(const float* rgba, uint32_t w, uint32_t h, float* out, uint64_t cap_floats, uint32_t* levels_out) {
-    if (!rgba || w == 0u || h == 0u) return 1;
-    try {
-        const PtrTexture t{rgba, w, h, 0u, 0u, 1u, 0u};
-        std::vector<float> chain;
-        std::vector<uint32_t> info;
-        appendTextureWithMips(t, chain, info);
-        if (levels_out) *levels_out = info[2];
-        if (!out) return 0;
-        if (cap_floats < chain.size()) return 1;
-        std::memcpy(out, chain.data(), chain.size() * sizeof(float));
-        return 0;
-    } catch (...) {
-        return 1;
-    }
-}
-
-int ptr_debug_camera_rays(const PtrSettings* settings, const uint32_t* xys, uint64_t n, float* out, uint32_t* out_states,
-                          char* err, size_t err_cap) {
-    try {
-        if (ptr_device_count() < 1) throw HipError{"no HIP device (the HIP path has no CPU fallback)"};
-        HIP_CHECK(hipSetDevice(0));
-        RenderParams rp;
-        fillRenderParams(*settings, 1, rp);
-        DeviceBuffer<uint32_t> dxy, drng;
-        DeviceBuffer<float> dout;
-        dxy.upload(xys, n * 3);
-        dout.ensure(n * 6);
-        drng.ensure(n);
-        launchDebugCameraRays(rp, dxy.ptr, n, dout.ptr, drng.ptr, nullptr);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(out, dout.ptr, n * 6 * sizeof(float), hipMemcpyDeviceToHost));
-        HIP_CHECK(hipMemcpy(out_states, drng.ptr, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
-        return 0;
-    }
-    PTR_CATCH_ALL(err, err_cap)
+        if (out_albedo) albedo.download(reinterpret_cast<float4*>(out_albedo), pixels);
+        if (out_normal) normal.download(reinterpret_cast<float4*>(out_normal), pixels);
+    });
 }
 
 }  // extern "C"

@@ -32,6 +32,20 @@ def test_library_exports_every_declared_symbol():
     for name in declared:
         assert hasattr(lib, name), name
     assert lib.ptr_version().startswith(b"ptr-hip")
+    # ... and the package declares each of them with as many arguments as its header does, and with its return type
+    counts = {}
+    for header in ("ptr_abi.h", "ptr_debug.h"):
+        text = open(os.path.join(ROOT, "include", header)).read()
+        text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+        for name, params in re.findall(r"\b(ptr_[a-z_]+)\s*\(([^()]*)\)\s*;", text):
+            counts[name] = 0 if params.strip() in ("", "void") else params.count(",") + 1
+    assert set(counts) == declared and len(counts) == 44
+    assert min(counts.values()) == 0 and max(counts.values()) == 12
+    restypes = {"ptr_version": C.c_char_p, "ptr_part_band_count": C.c_uint32, "ptr_scene_release": None, "ptr_host_scene_free": None}
+    for name, count in counts.items():
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == count, name
+        assert fn.restype is restypes.get(name, C.c_int), name
 
 
 def test_struct_layouts_match_reference_contract():
@@ -56,13 +70,9 @@ def test_device_path_fails_loudly_without_gpu():
     rays = np.zeros((1, 8), np.float32)
     info = (C.c_uint32 * 4)()
     hits = np.zeros(1, pt.HIT_DTYPE)
-    lib.ptr_debug_extend_rays.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.c_uint64, C.c_int, C.c_void_p, C.POINTER(C.c_uint32), C.c_char_p,
-                                          C.c_size_t]
     rc = lib.ptr_debug_extend_rays(None, rays.ctypes.data_as(C.POINTER(C.c_float)), 1, 0, hits.ctypes.data_as(C.c_void_p), info, err, 256)
     assert rc != 0 and b"ptr_debug_extend_rays" in err.value
     occ = np.zeros(1, np.uint32)
-    lib.ptr_debug_connect_rays.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_uint64, C.c_uint32, C.POINTER(C.c_uint32),
-                                           C.POINTER(C.c_uint32), C.c_char_p, C.c_size_t]
     rc = lib.ptr_debug_connect_rays(None, rays.ctypes.data_as(C.POINTER(C.c_float)), None, 1, 1, occ.ctypes.data_as(C.POINTER(C.c_uint32)), info,
                                     err, 256)
     assert rc != 0 and b"ptr_debug_connect_rays" in err.value
@@ -73,7 +83,6 @@ def test_division_by_a_render_constant_is_exact():
     # every divisor class (1, powers of two, 2^k +- 1, image widths, 2^32 - 1) at the ends of the range and at multiples +- 1
     import ctypes as C
     lib = pt.load_library()
-    lib.ptr_debug_exact_division.argtypes = [C.c_uint32, C.POINTER(C.c_uint32), C.c_uint64, C.POINTER(C.c_uint32)]
     rng = np.random.default_rng(3)
     divisors = [1, 2, 3, 5, 7, 64, 641, 1920, 1080, 3840, 2073600, 8294400, 65535, 65536, 65537, 2**31 - 1, 2**31, 2**31 + 1, 2**32 - 1]
     divisors += [int(v) for v in rng.integers(1, 2**32, 40)] + [int(v) for v in rng.integers(1, 5000, 40)]
@@ -96,7 +105,6 @@ def test_walk_counts_of_collapsed_levels(tmp_path):
     scenes = os.path.join(ROOT, "scenes")
     host = pt.HostScene.load(os.path.join(scenes, "cornell_mesh.scene"), scenes)
     lib = pt.load_library()
-    lib.ptr_debug_walk_counts.argtypes = [C.POINTER(pt.PtrSceneDesc), C.POINTER(C.c_float), C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
     rng = np.random.default_rng(2)
     n = 4000
     d = rng.normal(size=(n, 3))

@@ -20,7 +20,6 @@ pytestmark = pytest.mark.skipif(not ref.available(), reason="oracle/_ref librari
 
 def own_tangents(p, n, t):
     lib = pt.load_library()
-    lib.ptr_debug_generate_tangents.argtypes = [C.POINTER(C.c_float)] * 3 + [C.c_uint64, C.POINTER(C.c_float)]
     p, n, t = (np.ascontiguousarray(a, np.float32) for a in (p, n, t))
     out = np.zeros((p.shape[0], 4), np.float32)
     fp = C.POINTER(C.c_float)

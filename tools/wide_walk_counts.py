@@ -50,7 +50,6 @@ def main():
     from scenes.gen_assets import ensure_assets, ensure_large_asset
     ensure_assets()
     lib = pt.load_library()
-    lib.ptr_debug_walk_counts.argtypes = [C.POINTER(pt.PtrSceneDesc), C.POINTER(C.c_float), C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
     print("# tools/wide_walk_counts.py: closest-hit walks of %d random rays (origins uniform in the scene's box, directions uniform) on the host,"
           % args.rays)
     print("# children in order of entry distance; per ray: node steps | box tests | primitive tests")
