@@ -35,6 +35,30 @@ int ptr_debug_env_lookup(PtrDeviceScene* scene, const PtrSettings* settings, con
  * *levels_out = its level count.  out may be NULL (levels only); non-zero when cap_floats is too small. */
 int ptr_debug_env_mips(const float* rgba, uint32_t w, uint32_t h, float* out, uint64_t cap_floats, uint32_t* levels_out);
 
+/* The light side of a path vertex, function by function (csrc/kernels/wavefront.hip; reference: EmbreeHeadlessRenderer.mm 241-291, 887-1168,
+ * EnvImportanceSampler.mm 173-236).
+ * Environment NEE in parts: u n*3 {marginal, conditional, jitter} -> out n*8 {envSample's direction xyz and pdf (the sampled texel's) with
+ * the settings' rotation, then envLookup's level-0 radiance rgb and envPdfOf's pdf along that direction (the texel half a turn away: quirk
+ * Q2)}.  Non-zero when the scene has no environment map or the map has no sampling distribution. */
+int ptr_debug_env_sample(PtrDeviceScene* scene, const PtrSettings* settings, const float* u, uint64_t n, float* out, char* err, size_t err_cap);
+/* envLookup (level 0: wrap in x, clamp in y) and envPdfOf of arbitrary directions, which need not be normalised: dir n*3 -> out n*4
+ * {radiance rgb, pdf}.  Non-zero when the scene has no environment map. */
+int ptr_debug_env_eval(PtrDeviceScene* scene, const PtrSettings* settings, const float* dir, uint64_t n, float* out, char* err, size_t err_cap);
+/* rectLightNee at the vertex each ray hits: rays n*6 {origin, direction} are traced to their closest hit, the surface, offset frame, normal
+ * and wo are derived as k_shade derives them (no texture lookups), and the production function runs with the hit's material, or with
+ * `material` when it is not NULL, throughput thr n*3 and random state rng_states[n], in the instantiation k_shade would run (one light /
+ * several; Metal-only models by the settings' metalSemantics).  out n*16 {hit, queued, shadow origin xyz, direction xyz, tmax,
+ * contribution rgb, 0, 0, 0, 0}; out_states: the random state afterwards.  An emitter or a delta surface takes no sample, as in k_shade.
+ * Non-zero when the scene has no rectangle light. */
+int ptr_debug_rect_light_nee(PtrDeviceScene* scene, const PtrSettings* settings, const PtrMaterial* material, const float* rays, const float* thr,
+                             const uint32_t* rng_states, uint64_t n, float* out, uint32_t* out_states, char* err, size_t err_cap);
+/* A specular connection settled in k_shade: in n*14 {origin, direction, bsdf weight rgb, bsdf pdf, throughput rgb, 0} -> out n*12 {found
+ * (nearestRectLight), t, light, half, ignore word (uint bits), contribution rgb (rectLightSurface + rectContributionAt), rectLightPdfForHit
+ * at the found point from origin, front face, 0, 0}; zeros where no light lies along the ray.  info = {the scene settles connections
+ * (SceneView::settleRectLights), rectangle lights}. */
+int ptr_debug_light_connection(PtrDeviceScene* scene, const PtrSettings* settings, const float* in, uint64_t n, float* out, uint32_t info[2],
+                               char* err, size_t err_cap);
+
 /* PTR_METAL_RAY_DIFF: the first hit of the camera rays of n {x, y, sample} triples (xys) as k_shade textures it, by the same device code
  * and with the settings' metalSemantics (gradients only with PTR_METAL_RAY_DIFF).  out n*36 floats: {textured (1: a mesh hit of a
  * metallic-roughness material in a scene with textures, else 0 and the rest 0), t, uv set 0 (2), uv set 1 (2), set 0 {dudx, dvdx, dudy,

@@ -254,6 +254,10 @@ _SIGNATURES = {
     "ptr_debug_sample_lobes": (_int, [_material, _settings, _fp, _up, _up, _u64, _fp, _fp, _up, _fp] + _err),
     "ptr_debug_env_lookup": (_int, [_vp, _settings, _fp, _u64, _fp] + _err),
     "ptr_debug_env_mips": (_int, [_fp, _u32, _u32, _fp, _u64, _up]),
+    "ptr_debug_env_sample": (_int, [_vp, _settings, _fp, _u64, _fp] + _err),
+    "ptr_debug_env_eval": (_int, [_vp, _settings, _fp, _u64, _fp] + _err),
+    "ptr_debug_rect_light_nee": (_int, [_vp, _settings, _material, _fp, _fp, _up, _u64, _fp, _up] + _err),
+    "ptr_debug_light_connection": (_int, [_vp, _settings, _fp, _u64, _fp, _up] + _err),
     "ptr_debug_first_hit_textures": (_int, [_vp, _settings, _up, _u64, _fp] + _err),
     "ptr_debug_texture_sample_grad": (_int, [_vp, _u32, _fp, _u64, _fp] + _err),
     "ptr_debug_camera_rays": (_int, [_settings, _up, _u64, _fp, _up] + _err),
@@ -517,6 +521,36 @@ class DeviceScene:
         """ptr_debug_env_lookup: the PTR_METAL_ENV_LOD lookup of the scene's environment map with the settings' rotation and intensity:
         dir_roughness [n, 4] {direction, roughness} -> [n, 4] {LOD, rgb}."""
         return _batch(load_library().ptr_debug_env_lookup, (self._h, C.byref(settings)), dir_roughness, np.float32, 4, [((4,), np.float32)])
+
+    def env_sample(self, settings: PtrSettings, u: np.ndarray) -> np.ndarray:
+        """ptr_debug_env_sample: u [n, 3] {marginal, conditional, jitter} -> [n, 8] {envSample's direction and pdf, then envLookup's rgb and
+        envPdfOf's pdf along that direction}."""
+        return _batch(load_library().ptr_debug_env_sample, (self._h, C.byref(settings)), u, np.float32, 3, [((8,), np.float32)])
+
+    def env_eval(self, settings: PtrSettings, directions: np.ndarray) -> np.ndarray:
+        """ptr_debug_env_eval: directions [n, 3] (any length) -> [n, 4] {envLookup's level-0 rgb, envPdfOf's pdf}."""
+        return _batch(load_library().ptr_debug_env_eval, (self._h, C.byref(settings)), directions, np.float32, 3, [((4,), np.float32)])
+
+    def rect_light_nee(self, settings: PtrSettings, rays: np.ndarray, thr: np.ndarray, states: np.ndarray,
+                       material: Optional[PtrMaterial] = None) -> Tuple[np.ndarray, np.ndarray]:
+        """ptr_debug_rect_light_nee: rectLightNee at the hits of rays [n, 6] {origin, direction} with throughput thr [n, 3] and random
+        states [n]; material: an override for the hit's own.  Returns ([n, 16] {hit, queued, shadow origin, direction, tmax, contribution,
+        0...}, the random states afterwards)."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        thr = np.ascontiguousarray(thr, dtype=np.float32).reshape(-1, 3)
+        states = np.ascontiguousarray(states, dtype=np.uint32).reshape(-1)
+        if thr.shape[0] != rays.shape[0] or states.shape[0] != rays.shape[0]:
+            raise ValueError("thr and states need one entry per ray")
+        return _batch(load_library().ptr_debug_rect_light_nee, (self._h, C.byref(settings), None if material is None else C.byref(material)),
+                      rays, np.float32, 6, [((16,), np.float32), ((), np.uint32)], more=(_fptr(thr), _uptr(states)))
+
+    def light_connection(self, settings: PtrSettings, inputs: np.ndarray) -> Tuple[np.ndarray, dict]:
+        """ptr_debug_light_connection: inputs [n, 14] {origin, direction, bsdf weight, bsdf pdf, throughput, 0} -> ([n, 12] {found, t, light,
+        half, ignore word bits, contribution, pdf, front face, 0, 0}, {settles, lights})."""
+        info = (C.c_uint32 * 2)()
+        out = _batch(load_library().ptr_debug_light_connection, (self._h, C.byref(settings)), inputs, np.float32, 14, [((12,), np.float32)],
+                     tail=(info,))
+        return out, {"settles": bool(info[0]), "lights": int(info[1])}
 
     def trace_rays(self, rays: np.ndarray, any_hit: bool = False) -> Tuple[np.ndarray, PtrRenderStats]:
         """rays: [n, 8] float32 {ox,oy,oz,tmin,dx,dy,dz,tmax}; returns a structured array of PtrHit."""

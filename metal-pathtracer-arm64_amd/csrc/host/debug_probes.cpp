@@ -344,6 +344,99 @@ int ptr_debug_env_lookup(PtrDeviceScene* scene, const PtrSettings* settings, con
     });
 }
 
+int ptr_debug_env_sample(PtrDeviceScene* scene, const PtrSettings* settings, const float* u, uint64_t n, float* out, char* err, size_t err_cap) {
+    return deviceCall("ptr_debug_env_sample", scene, scene && settings && (u || !n) && (out || !n), err, err_cap, [&] {
+        if (scene->view.envWidth == 0u || !scene->view.envSampling) {
+            throw HipError{"ptr_debug_env_sample: the scene has no environment map with a sampling distribution"};
+        }
+        if (n == 0) return;
+        RenderParams rp;
+        fillRenderParams(*settings, 1, rp);
+        DeviceBuffer<float> din;
+        DeviceBuffer<float4> dout;
+        din.upload(u, n * 3);
+        dout.ensure(n * 2);
+        launchDebugEnvSample(rp, scene->view, din.ptr, n, dout.ptr, nullptr);
+        dout.download(reinterpret_cast<float4*>(out), n * 2);
+    });
+}
+
+int ptr_debug_env_eval(PtrDeviceScene* scene, const PtrSettings* settings, const float* dir, uint64_t n, float* out, char* err, size_t err_cap) {
+    return deviceCall("ptr_debug_env_eval", scene, scene && settings && (dir || !n) && (out || !n), err, err_cap, [&] {
+        if (scene->view.envWidth == 0u) throw HipError{"ptr_debug_env_eval: the scene has no environment map"};
+        if (n == 0) return;
+        RenderParams rp;
+        fillRenderParams(*settings, 1, rp);
+        DeviceBuffer<float> din;
+        DeviceBuffer<float4> dout;
+        din.upload(dir, n * 3);
+        dout.ensure(n);
+        launchDebugEnvEval(rp, scene->view, din.ptr, n, dout.ptr, nullptr);
+        dout.download(reinterpret_cast<float4*>(out), n);
+    });
+}
+
+int ptr_debug_rect_light_nee(PtrDeviceScene* scene, const PtrSettings* settings, const PtrMaterial* material, const float* rays, const float* thr,
+                             const uint32_t* rng_states, uint64_t n, float* out, uint32_t* out_states, char* err, size_t err_cap) {
+    const bool argsOk = scene && settings && ((rays && thr && rng_states && out && out_states) || !n);
+    return deviceCall("ptr_debug_rect_light_nee", scene, argsOk, err, err_cap, [&] {
+        if (scene->view.rectLightCount == 0u) throw HipError{"ptr_debug_rect_light_nee: the scene has no rectangle light"};
+        if (n >= (1ull << kConnectMaskShift)) throw HipError{"ptr_debug_rect_light_nee: at most 2^27 - 1 rays"};
+        if (n == 0) return;
+        RenderParams rp;
+        fillRenderParams(*settings, 1, rp);
+        DeviceBuffer<float4> dMaterial, dRec, dHead;
+        if (material) {
+            std::vector<float> rows;
+            compactMaterial(*material, rows);
+            dMaterial.upload(reinterpret_cast<const float4*>(rows.data()), kMaterialVec4);
+        }
+        DeviceBuffer<float> dRays, dThr;
+        DeviceBuffer<uint32_t> dRng, dRngOut;
+        dRays.upload(rays, n * 6);
+        dThr.upload(thr, n * 3);
+        dRng.upload(rng_states, n);
+        dRngOut.ensure(n);
+        dHead.ensure(n);
+        // record 0 of a pool of n slots: rectLightNee's storeRecord writes slot i of {org | tmax, dir | kind, contribution | depth}; zero
+        // where it queued nothing
+        dRec.ensure(n * 4);
+        HIP_CHECK(hipMemset(dRec.ptr, 0, n * 4 * sizeof(float4)));
+        PathPool pool{};
+        pool.rec[0] = ShadowRecordView{dRec.ptr, dRec.ptr + n, dRec.ptr + 2 * n, dRec.ptr + 3 * n};
+        pool.slots = static_cast<uint32_t>(n);
+        pool.recStride = static_cast<uint32_t>(n);
+        launchDebugRectLightNee(rp, scene->view, pool, material ? dMaterial.ptr : nullptr, dRays.ptr, dThr.ptr, dRng.ptr, n, dHead.ptr, dRngOut.ptr,
+                                coldLaunchConfig(*scene), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        std::vector<float4> rec(n * 4), head(n);
+        dRec.download(rec.data(), rec.size());
+        dHead.download(head.data(), n);
+        dRngOut.download(out_states, n);
+        for (uint64_t i = 0; i < n; ++i) {
+            const float4 org = rec[i], dir = rec[n + i], a = rec[2 * n + i];
+            const float row[16] = {head[i].x, head[i].y, org.x, org.y, org.z, dir.x, dir.y, dir.z, org.w, a.x, a.y, a.z, 0.0f, 0.0f, 0.0f, 0.0f};
+            std::memcpy(out + i * 16, row, sizeof(row));
+        }
+    });
+}
+
+int ptr_debug_light_connection(PtrDeviceScene* scene, const PtrSettings* settings, const float* in, uint64_t n, float* out, uint32_t info[2],
+                               char* err, size_t err_cap) {
+    return deviceCall("ptr_debug_light_connection", scene, scene && settings && (in || !n) && (out || !n) && info, err, err_cap, [&] {
+        info[0] = scene->view.settleRectLights;
+        info[1] = scene->view.rectLightCount;
+        if (n == 0) return;
+        RenderParams rp;
+        fillRenderParams(*settings, 1, rp);
+        DeviceBuffer<float> din, dout;
+        din.upload(in, n * 14);
+        dout.ensure(n * 12);
+        launchDebugLightConnection(rp, scene->view, din.ptr, n, dout.ptr, nullptr);
+        dout.download(out, n * 12);
+    });
+}
+
 int ptr_debug_env_mips(const float* rgba, uint32_t w, uint32_t h, float* out, uint64_t cap_floats, uint32_t* levels_out) {
     if (!rgba || w == 0u || h == 0u) return 1;
     try {

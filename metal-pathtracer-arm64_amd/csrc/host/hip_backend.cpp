@@ -304,7 +304,7 @@ void uploadScene(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceSce
     v.rectCount = desc.rectCount;
     v.rectLightCount = lightCount;
     for (uint32_t i = 0; i < desc.materialCount; ++i) v.materialTypes |= 1u << std::min(static_cast<uint32_t>(desc.materials[i].typeEta[0]), 7u);
-    v.settleRectLights = (lightCount > 0u && lightCount <= 8u && ps.lightsHaveTriangles) ? 1u : 0u;   // kSettleLightsMax of wavefront.hip
+    v.settleRectLights = (lightCount > 0u && lightCount <= kSettleLightsMax && ps.lightsHaveTriangles) ? 1u : 0u;
 
     if (desc.envRgba && desc.envWidth > 0 && desc.envHeight > 0) {
         const size_t texels = static_cast<size_t>(desc.envWidth) * desc.envHeight;

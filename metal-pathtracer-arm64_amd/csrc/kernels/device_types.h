@@ -76,6 +76,7 @@ struct SceneView {
 constexpr uint32_t kMaterialTexVec4 = 16u;
 
 constexpr uint32_t kRectLightVec4 = 11u;
+constexpr uint32_t kSettleLightsMax = 8u;   // most rectangle lights a scene may have for SceneView::settleRectLights (nearestRectLight tests them all)
 
 // Compact material record: the MaterialData fields the Embree-semantics integrator reads.
 constexpr uint32_t kMaterialVec4 = 16u;

@@ -81,4 +81,13 @@ void launchDebugSurfaceHits(const SceneView& sc, const float* dIn, uint64_t n, f
 void launchDebugCameraRays(const RenderParams& rp, const uint32_t* dXys, uint64_t n, float* dOut, uint32_t* dRngOut,
                            hipStream_t stream);
 
+// The light side of a path vertex (ptr_debug.h): environment sampling and level-0 lookups (out: 2 n / n float4), rectLightNee at the hits of
+// a batch of rays (record 0 of `pool` and dHead receive the result; dMaterial null = the hit's own material), settled connections
+void launchDebugEnvSample(const RenderParams& rp, const SceneView& sc, const float* dU, uint64_t n, float4* dOut, hipStream_t stream);
+void launchDebugEnvEval(const RenderParams& rp, const SceneView& sc, const float* dDir, uint64_t n, float4* dOut, hipStream_t stream);
+void launchDebugRectLightNee(const RenderParams& rp, const SceneView& sc, const PathPool& pool, const float4* dMaterial, const float* dRays,
+                             const float* dThr, const uint32_t* dRng, uint64_t n, float4* dHead, uint32_t* dRngOut, const LaunchConfig& cfg,
+                             hipStream_t stream);
+void launchDebugLightConnection(const RenderParams& rp, const SceneView& sc, const float* dIn, uint64_t n, float* dOut, hipStream_t stream);
+
 }  // namespace ptrk

@@ -532,8 +532,8 @@ __device__ __forceinline__ bool rectLightHit(const SceneView& sc, const Surface&
 // so the same test on the same operands gives the traversal's distance bit for bit.  A direction that meets no light's rectangle
 // needs no ray at all (nearly every delta bounce of a glass object: config 4 queued one closest-hit ray per bounce and k_connect was
 // its largest kernel); one that does becomes an any-hit query up to that distance which ignores the light's own two triangles
-// (record kind 3), with the contribution already computed.
-constexpr uint32_t kSettleLightsMax = 8u;   // scenes with more rectangle lights (or lights without triangles) keep the closest-hit record
+// (record kind 3), with the contribution already computed.  Scenes with more than kSettleLightsMax rectangle lights (device_types.h),
+// or with lights without triangles, keep the closest-hit record: the host clears settleRectLights for them.
 
 __device__ __forceinline__ bool nearestRectLight(const SceneView& sc, f3 org, f3 dir, float& tHit, uint32_t& light, uint32_t& half) {
     float best = INFINITY;
@@ -2615,6 +2615,103 @@ __global__ void k_debug_camera(RenderParams rp, const uint32_t* xys, uint64_t n,
     rngOut[i] = rng;
 }
 
+// ---- the light side of a path vertex (ptr_debug.h: ptr_debug_env_sample / env_eval / rect_light_nee / light_connection) ----
+// environment NEE in parts: u n x 3 {marginal, conditional, jitter} -> out n x 2 float4 {direction, pdf of the sampled texel},
+// {level-0 radiance and pdf (envPdfOf: quirk Q2) looked up along that direction}
+__global__ void k_debug_env_sample(RenderParams rp, SceneView sc, const float* u, uint64_t n, float4* out) {
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    f3 dir;
+    float pdf;
+    envSample(sc, u[i * 3u], u[i * 3u + 1u], u[i * 3u + 2u], rp.envRotation, dir, pdf);
+    out[i * 2u] = mk4(dir, pdf);
+    out[i * 2u + 1u] = mk4(envLookup(sc, dir, rp.envRotation, rp.envIntensity), envPdfOf(sc, dir, rp.envRotation));
+}
+
+// level-0 lookup and pdf of arbitrary directions: dir n x 3 -> out n float4 {radiance, pdf}
+__global__ void k_debug_env_eval(RenderParams rp, SceneView sc, const float* dir, uint64_t n, float4* out) {
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f3 d = ld3(dir + i * 3u);
+    out[i] = mk4(envLookup(sc, d, rp.envRotation, rp.envIntensity), envPdfOf(sc, d, rp.envRotation));
+}
+
+// rectLightNee at the vertex each ray hits: the closest hit, the surface and offset frame, n and wo by the lines of shadeSlot (without
+// the per-hit texture lookups), then the production function with slot = ray index on a pool whose record 0 is the probe's own output.
+// material: null = the hit's own.  head n float4 {hit, queued, 0, 0}; the record arrays are zero where nothing was queued.  As in
+// shadeSlot, an emitter or a delta surface takes no light sample (and draws no random number).
+template <bool SSS, bool ONE>
+__global__ void __launch_bounds__(kTraceBlock) k_debug_rect_light_nee(RenderParams rp, SceneView sc, PathPool pool, const float4* material,
+                                                                      const float* rays, const float* thrIn, const uint32_t* rngIn, uint64_t n,
+                                                                      float4* head, uint32_t* rngOut, uint32_t* spill, uint32_t spillStride) {
+    __shared__ uint32_t ldsStack[kLdsStackLevels * kTraceBlock];
+    const uint32_t gtid = blockIdx.x * kTraceBlock + threadIdx.x;
+    LaneStack stack;
+    stack.lds = (LdsWord*)(ldsStack + threadIdx.x);
+    stack.spill = spill;
+    stack.spillStride = spillStride;
+    stack.limit = sc.stackLimit;
+    TraceCounters cnt{0u, 0u};
+    const ClampCfg cc = clampCfg<SSS>(rp);
+    ShadeCounts counts;
+    for (uint64_t i = gtid; i < n; i += static_cast<uint64_t>(gridDim.x) * kTraceBlock) {
+        uint32_t rng = rngIn[i];
+        const f3 rayO = ld3(rays + i * 6u), rayD = ld3(rays + i * 6u + 3u);
+        const TraceHit h = traverse<false, false>(sc, rayO, rayD, kEps, INFINITY, stack, cnt);
+        bool queued = false;
+        if (h.prim != kHitMiss && sc.materialCount != 0u) {
+            const Surface sf = reconstruct(sc, rayO, rayD, h.t, h.prim);
+            const OffsetFrame of = offsetFrame(sf);
+            const uint32_t materialIndex = min(sf.material, sc.materialCount - 1u);
+            const Mat mat{material ? material : byteOffset(sc.materials, materialIndex * (kMaterialVec4 * 16u))};
+            const uint32_t type = mat.type();
+            const f3 wo = -normalize(rayD);
+            f3 nn = sf.hitShadingNormal;
+            if (dot(nn, nn) <= 0.0f) nn = sf.normal;
+            if (type == 2u) {
+                nn = sf.normal;
+                if ((rp.mediaMode & PTR_METAL_FACE_NORMAL) && !sf.frontFace) nn = -nn;
+            }
+            nn = normalize(nn);
+            bool surfaceDelta = materialIsDelta(mat);
+            if (SSS && cc.metalPbr && type == 7u) surfaceDelta = mat.roughness01() <= 1.0e-3f;
+            if (type != 3u && !surfaceDelta) {
+                queued = rectLightNee<false, SSS, kAllMaterials, ONE>(rp, sc, pool, static_cast<uint32_t>(i), mat, sf, of, nn, wo, ld3(thrIn + i * 3u), cc,
+                                                                      0u, rng, counts);
+            }
+        }
+        head[i] = make_float4(h.prim != kHitMiss ? 1.0f : 0.0f, queued ? 1.0f : 0.0f, 0.0f, 0.0f);
+        rngOut[i] = rng;
+    }
+}
+
+// a settled specular connection: in n x 14 {origin, direction, bsdf weight rgb, bsdf pdf, throughput rgb, 0} -> out n x 12 {found, t, light,
+// half, bits of the ignore word, contribution rgb, rectLightPdfForHit at the found point, front face, 0, 0} (zeros where no light is found)
+__global__ void k_debug_light_connection(RenderParams rp, SceneView sc, bool sss, const float* in, uint64_t n, float* out) {
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* p = in + i * 14u;
+    float* o = out + i * 12u;
+    for (int k = 0; k < 12; ++k) o[k] = 0.0f;
+    const ClampCfg cc = sss ?   // sss: the instantiation launchShade picks
+        clampCfg<true>(rp) : clampCfg<false>(rp);
+    const f3 org = ld3(p), dir = ld3(p + 3);
+    float tl;
+    uint32_t li, half;
+    if (!nearestRectLight(sc, org, dir, tl, li, half)) return;
+    uint32_t ignore;
+    const Surface ls = rectLightSurface(sc, org, dir, tl, li, half, ignore);
+    const f3 c = rectContributionAt(rp, sc, cc, ls, org, ld3(p + 6), p[9], ld3(p + 10));
+    o[0] = 1.0f;
+    o[1] = tl;
+    o[2] = static_cast<float>(li);
+    o[3] = static_cast<float>(half);
+    o[4] = __uint_as_float(ignore);
+    o[5] = c.x; o[6] = c.y; o[7] = c.z;
+    o[8] = rectLightPdfForHit(sc, ls.primType, ls.primIndex, ls.position, org);
+    o[9] = ls.frontFace ? 1.0f : 0.0f;
+}
+
 // =====================================================================================================
 // launchers
 // =====================================================================================================
@@ -2831,6 +2928,39 @@ void launchDebugFirstHit(const RenderParams& rp, const SceneView& sc, const uint
     const uint32_t stride = cfg.traceGrid * kTraceBlock;
     const uint32_t grid = std::min(cfg.traceGrid, std::max(1u, ceilDiv(n, kTraceBlock)));
     hipLaunchKernelGGL(k_debug_first_hit, dim3(grid), dim3(kTraceBlock), 0, stream, rp, sc, dXys, n, dOut, cfg.spill, stride);
+}
+
+void launchDebugEnvSample(const RenderParams& rp, const SceneView& sc, const float* dU, uint64_t n, float4* dOut, hipStream_t stream) {
+    hipLaunchKernelGGL(k_debug_env_sample, dim3(std::max(1u, ceilDiv(n, 128))), dim3(128), 0, stream, rp, sc, dU, n, dOut);
+}
+
+void launchDebugEnvEval(const RenderParams& rp, const SceneView& sc, const float* dDir, uint64_t n, float4* dOut, hipStream_t stream) {
+    hipLaunchKernelGGL(k_debug_env_eval, dim3(std::max(1u, ceilDiv(n, 128))), dim3(128), 0, stream, rp, sc, dDir, n, dOut);
+}
+
+// the instantiation of rectLightNee that launchShade's k_shade runs for this scene and these settings: SSS by the Metal-only models, ONE
+// exactly when the scene has a single rectangle light (shadeSlot)
+void launchDebugRectLightNee(const RenderParams& rp, const SceneView& sc, const PathPool& pool, const float4* dMaterial, const float* dRays,
+                             const float* dThr, const uint32_t* dRng, uint64_t n, float4* dHead, uint32_t* dRngOut, const LaunchConfig& cfgIn,
+                             hipStream_t stream) {
+    const LaunchConfig cfg = perBlockSize(cfgIn);
+    const uint32_t stride = cfg.traceGrid * kTraceBlock;
+    const uint32_t grid = std::min(cfg.traceGrid, std::max(1u, ceilDiv(n, kTraceBlock)));
+    auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kTraceBlock), 0, stream, rp, sc, pool, dMaterial, dRays, dThr, dRng, n, dHead, dRngOut, cfg.spill,
+                           stride);
+    };
+    const bool sss = (rp.mediaMode & kMetalInstantiationBits) != 0u;
+    if (sc.rectLightCount == 1u) {
+        if (sss) launch(k_debug_rect_light_nee<true, true>); else launch(k_debug_rect_light_nee<false, true>);
+    } else {
+        if (sss) launch(k_debug_rect_light_nee<true, false>); else launch(k_debug_rect_light_nee<false, false>);
+    }
+}
+
+void launchDebugLightConnection(const RenderParams& rp, const SceneView& sc, const float* dIn, uint64_t n, float* dOut, hipStream_t stream) {
+    const bool sss = (rp.mediaMode & kMetalInstantiationBits) != 0u;
+    hipLaunchKernelGGL(k_debug_light_connection, dim3(std::max(1u, ceilDiv(n, 128))), dim3(128), 0, stream, rp, sc, sss, dIn, n, dOut);
 }
 
 void launchDebugCameraRays(const RenderParams& rp, const uint32_t* dXys, uint64_t n, float* dOut, uint32_t* dRngOut, hipStream_t stream) {

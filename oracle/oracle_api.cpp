@@ -232,4 +232,33 @@ int oracle_env_sample(const float* rgba, uint32_t w, uint32_t h, float rotation,
     return 0;
 }
 
+// SampleEnvironment and EnvironmentPdf along arbitrary directions (need not be normalised): dirs n*3; out n*4 {rgb, pdf}.
+// Returns non-zero when the map has no positive radiance (no distribution: the pdfs would all be 0).
+int oracle_env_eval(const float* rgba, uint32_t w, uint32_t h, float rotation, float intensity, const float* dirs, uint64_t n, float* out) {
+    EnvMap env;
+    env.rgba = rgba;
+    env.width = w;
+    env.height = h;
+    env.hasDistribution = buildEnvDistribution(rgba, w, h, env.dist);
+    for (uint64_t i = 0; i < n; ++i) {
+        const V3 d(dirs + i * 3);
+        const V3 c = sampleEnvironment(env, d, rotation, intensity);
+        float* o = out + i * 4;
+        o[0] = c.x; o[1] = c.y; o[2] = c.z;
+        o[3] = env.hasDistribution ? environmentPdf(env, rotation, d) : 0.0f;
+    }
+    return env.hasDistribution ? 0 : 1;
+}
+
+// Rectangle-light NEE at the vertex each ray hits (oracle_integrator.h rectLightNeeBatch); material may be NULL (the hit's own)
+void oracle_rect_light_nee(const OracleScene* s, const PtrSettings* settings, const PtrMaterial* material, const float* rays, const float* thr,
+                           const uint32_t* rng_states, uint64_t n, float* out, uint32_t* out_states) {
+    rectLightNeeBatch(s->scene, s->desc, *settings, material, rays, thr, rng_states, n, out, out_states);
+}
+
+// The specular connection to the rectangle lights along each ray (oracle_integrator.h lightConnectionBatch)
+void oracle_light_connection(const OracleScene* s, const PtrSettings* settings, const float* in, uint64_t n, float* out) {
+    lightConnectionBatch(s->scene, s->desc, *settings, in, n, out);
+}
+
 }  // extern "C"

@@ -2173,28 +2173,46 @@ static uint32_t sigHashStep(uint32_t h, uint32_t primType, uint32_t geomIndex, u
     return x & 0xFFFFu;
 }
 
-void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& settings, uint32_t spp, uint32_t threads,
-            uint32_t yBegin, uint32_t yEnd, float* outRgb, RenderCounters* outCounters, uint32_t* outSignature, uint8_t* outMarginal) {
-    const uint32_t width = settings.width, height = settings.height;
+// ---------------------------------------------------------------------------------------------
+// The light side of a path vertex as functions: what render() runs at every vertex, callable one vertex at a time by the
+// function-level tests (oracle_api.cpp oracle_rect_light_nee / oracle_light_connection).
+// ---------------------------------------------------------------------------------------------
+namespace {
+
+// what the function-level entry points report besides the contribution
+struct RectNeeRecord {
+    bool sampled = false;   // a light sample with a positive pdf on the lit side of the shading normal: the shadow query was made
+    V3 direction, emission, shadowOrigin;
+    float distance = 0.0f, pdf = 0.0f, shadowMax = 0.0f;
+};
+struct RectAlongRecord {
+    bool hit = false, isLight = false;
+    HitInfo lightHit;
+    float pdfForHit = 0.0f;   // rectLightPdfForHit of the closest hit, whatever it is (the emitter branch's MIS term, E:2660-2706)
+};
+
+bool sceneEnvMap(const PtrSceneDesc& desc, EnvMap& envMap) {
+    if (!(desc.envRgba && desc.envWidth > 0 && desc.envHeight > 0)) return false;
+    envMap.rgba = desc.envRgba;
+    envMap.width = desc.envWidth;
+    envMap.height = desc.envHeight;
+    envMap.hasDistribution = buildEnvDistribution(desc.envRgba, desc.envWidth, desc.envHeight, envMap.dist);
+    return true;
+}
+
+float sceneEmissionScale(const PtrSettings& settings) {
+    return (settings.emissionScale > 0.0f && std::isfinite(settings.emissionScale)) ? settings.emissionScale : 1.0f;
+}
+float sceneShadowSlack(const PtrSettings& settings) {   // test knob (PtrSettings.debugShadowSlack): 0 = the reference's shadow-ray length, quirk Q9
+    return (settings.debugShadowSlack > 0.0f && settings.debugShadowSlack < 1.0f) ? settings.debugShadowSlack : 0.0f;
+}
+
+void buildRectLights(const PtrSceneDesc& desc, float emissionScale, std::vector<RectLight>& rectLights, std::vector<int32_t>& lightIndexByRect) {
     const PtrMaterial* materials = desc.materials;
     const uint32_t materialCount = desc.materialCount;
     const PtrRect* rectangles = desc.rects;
     const uint32_t rectangleCount = desc.rectCount;
-    const float emissionScale = (settings.emissionScale > 0.0f && std::isfinite(settings.emissionScale)) ? settings.emissionScale : 1.0f;
-
-    EnvMap envMap;
-    EnvMap* env = nullptr;
-    if (desc.envRgba && desc.envWidth > 0 && desc.envHeight > 0) {
-        envMap.rgba = desc.envRgba;
-        envMap.width = desc.envWidth;
-        envMap.height = desc.envHeight;
-        envMap.hasDistribution = buildEnvDistribution(desc.envRgba, desc.envWidth, desc.envHeight, envMap.dist);
-        env = &envMap;
-    }
-
     // rectangle lights: DiffuseLight rectangles with non-zero emission (E:2484-2522)
-    std::vector<RectLight> rectLights;
-    std::vector<int32_t> lightIndexByRect;
     if (rectangles && rectangleCount > 0 && materials && materialCount > 0) {
         lightIndexByRect.assign(rectangleCount, -1);
         for (uint32_t i = 0; i < rectangleCount; ++i) {
@@ -2217,6 +2235,110 @@ void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& set
             rectLights.push_back(li);
         }
     }
+}
+
+// the normal a vertex is shaded with (E:2636-2645)
+V3 vertexShadingNormal(const HitInfo& hit, uint32_t type, const PtrSettings& settings) {
+    V3 shadingNormal = hit.shadingNormal;
+    if (dot(shadingNormal, shadingNormal) <= 0.0f) shadingNormal = hit.normal;
+    if (type == PTR_MAT_DIELECTRIC) {
+        shadingNormal = hit.normal;  // dielectrics shade with the geometric normal, as stored (E:2641-2644)
+        // Metal-only: the normal faces the incoming ray (set_face_normal, shaders/pathtrace.metal:1187-1191)
+        if ((settings.metalSemantics & PTR_METAL_FACE_NORMAL) && !hit.frontFace) shadingNormal = -shadingNormal;
+    }
+    return normalize(shadingNormal);
+}
+
+bool surfaceIsDeltaAt(const PtrMaterial& material, const ClampParams& cp) {
+    bool surfaceIsDelta = materialIsDelta(material);
+    if (cp.metalPbr && matType(material) == PTR_MAT_PBR) {   // M:4578-4581
+        surfaceIsDelta = clampf(material.baseColorRoughness[3], 0.0f, 1.0f) <= 1.0e-3f;
+    }
+    return surfaceIsDelta;
+}
+
+// Rectangle-light NEE at a vertex (E:2710-2772).  `occluded(origin, direction, tMax)` answers the shadow query; true with `clamped` set
+// when a contribution is to be added.  marginal (optional): set when the shadow test flips within +-2e-6 (relative) of the ray length.
+template <typename Occluded>
+bool rectLightNeeAt(const Scene& scene, const std::vector<RectLight>& rectLights, const EnvMap* env, const PtrSettings& settings, const ClampParams& cp,
+                    float shadowSlack, const HitInfo& hit, const PtrMaterial& material, V3 shadingNormal, V3 wo, V3 throughput, Rng& rng,
+                    Occluded&& occluded, bool* marginal, V3& clamped, RectNeeRecord* record = nullptr) {
+    RectLightSample ls;
+    if (!sampleRectLight(rectLights, env, settings, hit, rng, ls)) return false;
+    const float nDotL = std::max(dot(shadingNormal, ls.direction), 0.0f);
+    if (!(ls.pdf > 0.0f && nDotL > 0.0f)) return false;
+    const float shadowMax = std::max(ls.distance * (1.0f - shadowSlack) - kEpsilon, kEpsilon);
+    if (marginal) {
+        const V3 so = offsetRayOrigin(hit, ls.direction);
+        if (scene.occluded(so, ls.direction, kEpsilon, shadowMax * (1.0f - 2.0e-6f), false, nullptr) !=
+            scene.occluded(so, ls.direction, kEpsilon, shadowMax * (1.0f + 2.0e-6f), false, nullptr)) {
+            *marginal = true;
+        }
+    }
+    if (record) {
+        record->sampled = true;
+        record->direction = ls.direction;
+        record->emission = ls.emission;
+        record->distance = ls.distance;
+        record->pdf = ls.pdf;
+        record->shadowOrigin = offsetRayOrigin(hit, ls.direction);
+        record->shadowMax = shadowMax;
+    }
+    if (occluded(offsetRayOrigin(hit, ls.direction), ls.direction, shadowMax)) return false;
+    const BsdfEval be = evaluateBsdf(material, hit.position, shadingNormal, wo, ls.direction, cp);
+    if (!neeContributes(be, cp)) return false;
+    const float weight = neeWeight(ls.pdf, be.pdf, cp);
+    V3 contribution = (ls.emission * be.value) * nDotL;
+    contribution *= weight / ls.pdf;
+    if (!finite3(contribution)) return false;
+    clamped = clampFireflyContribution(throughput, contribution, cp);
+    return true;
+}
+
+// "NEE along the specular direction" to the rectangle lights (E:2856-2917): `trace(ray, hit)` finds the closest hit over the whole scene.
+template <typename Trace>
+bool rectLightAlong(const std::vector<int32_t>& lightIndexByRect, const std::vector<RectLight>& rectLights, const PtrRect* rectangles,
+                    uint32_t rectangleCount, const EnvMap* env, const PtrSettings& settings, const ClampParams& cp, V3 origin, V3 dir, V3 weight,
+                    float bsdfPdfFloorInput, V3 throughput, Trace&& trace, V3& clamped, RectAlongRecord* record = nullptr) {
+    HitInfo lightHit;
+    if (!trace(Ray{origin, dir}, lightHit)) return false;
+    if (record) {
+        record->hit = true;
+        record->lightHit = lightHit;
+        record->pdfForHit = rectLightPdfForHit(lightIndexByRect, rectangles, rectangleCount, static_cast<uint32_t>(rectLights.size()), lightHit, origin);
+    }
+    RectLightHit rh;
+    if (!rectLightHitInfo(lightIndexByRect, rectLights, rectangles, rectangleCount, env, settings, lightHit, origin, rh)) return false;
+    if (record) record->isLight = true;
+    const float lightPdf = std::max(rh.pdf, kSpecularNeePdfFloor);
+    const float invLightPdf = std::min(1.0f / lightPdf, kSpecularNeeInvPdfClamp);
+    const float bsdfPdf = std::max(bsdfPdfFloorInput, kSpecularNeePdfFloor);
+    const float denom = lightPdf + bsdfPdf;
+    float misWeight = denom > 0.0f ? (lightPdf / denom) : 0.0f;
+    misWeight = clampf(misWeight, kMisWeightClampMin, kMisWeightClampMax);
+    const V3 c = (weight * rh.emission) * (misWeight * invLightPdf);
+    if (!finite3(c)) return false;
+    clamped = clampFireflyContribution(throughput, c, cp);
+    return true;
+}
+
+}  // namespace
+
+void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& settings, uint32_t spp, uint32_t threads,
+            uint32_t yBegin, uint32_t yEnd, float* outRgb, RenderCounters* outCounters, uint32_t* outSignature, uint8_t* outMarginal) {
+    const uint32_t width = settings.width, height = settings.height;
+    const PtrMaterial* materials = desc.materials;
+    const uint32_t materialCount = desc.materialCount;
+    const PtrRect* rectangles = desc.rects;
+    const uint32_t rectangleCount = desc.rectCount;
+    const float emissionScale = sceneEmissionScale(settings);
+
+    EnvMap envMap;
+    EnvMap* env = sceneEnvMap(desc, envMap) ? &envMap : nullptr;
+
+    std::vector<RectLight> rectLights;
+    std::vector<int32_t> lightIndexByRect;
+    buildRectLights(desc, emissionScale, rectLights, lightIndexByRect);
     const uint32_t rectLightCount = static_cast<uint32_t>(rectLights.size());
     const bool envMapAvailable = env && env->width > 0 && env->height > 0 && env->rgba;
     const bool envSampling = env && env->hasDistribution && envMapAvailable;
@@ -2228,8 +2350,7 @@ void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& set
     std::atomic<uint64_t> cExtend{0}, cShadow{0}, cNodes{0}, cPrims{0}, cShaded{0}, cTri{0};
     const bool counting = outCounters != nullptr;
 
-    // test knob (PtrSettings.debugShadowSlack): 0 = the reference's shadow-ray length, quirk Q9
-    const float shadowSlack = (settings.debugShadowSlack > 0.0f && settings.debugShadowSlack < 1.0f) ? settings.debugShadowSlack : 0.0f;
+    const float shadowSlack = sceneShadowSlack(settings);
     const bool wantSignature = outSignature != nullptr || outMarginal != nullptr;
     // material textures: sampled by the Metal metallic-roughness model only (the Embree backend never reads them)
     const std::vector<OracleTexture> textures = cp.metalPbr ? buildTextures(desc) : std::vector<OracleTexture>();
@@ -2319,14 +2440,7 @@ void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& set
                 const uint32_t type = matType(*materialPtr);
                 const V3 incidentDir = normalize(ray.direction);
                 const V3 wo = -incidentDir;
-                V3 shadingNormal = hit.shadingNormal;
-                if (dot(shadingNormal, shadingNormal) <= 0.0f) shadingNormal = hit.normal;
-                if (type == PTR_MAT_DIELECTRIC) {
-                    shadingNormal = hit.normal;  // dielectrics shade with the geometric normal, as stored (E:2641-2644)
-                    // Metal-only: the normal faces the incoming ray (set_face_normal, shaders/pathtrace.metal:1187-1191)
-                    if ((settings.metalSemantics & PTR_METAL_FACE_NORMAL) && !hit.frontFace) shadingNormal = -shadingNormal;
-                }
-                shadingNormal = normalize(shadingNormal);
+                V3 shadingNormal = vertexShadingNormal(hit, type, settings);
                 if (cp.metalPbr && type == PTR_MAT_PBR) {
                     bool passThrough = false;
                     if (texturedScene && hit.primitiveType == GeomType::Mesh && !scene.geoms[hit.geom].positions.empty()) {
@@ -2374,38 +2488,14 @@ void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& set
                     break;
                 }
 
-                bool surfaceIsDelta = materialIsDelta(material);
-                if (cp.metalPbr && matType(material) == PTR_MAT_PBR) {   // M:4578-4581
-                    surfaceIsDelta = clampf(material.baseColorRoughness[3], 0.0f, 1.0f) <= 1.0e-3f;
-                }
+                const bool surfaceIsDelta = surfaceIsDeltaAt(material, cp);
 
                 if (!surfaceIsDelta && rectLightCount > 0) {  // rect-light NEE, E:2710-2772
-                    RectLightSample ls;
-                    if (sampleRectLight(rectLights, env, settings, hit, rng, ls)) {
-                        const float nDotL = std::max(dot(shadingNormal, ls.direction), 0.0f);
-                        if (ls.pdf > 0.0f && nDotL > 0.0f) {
-                            const float shadowMax = std::max(ls.distance * (1.0f - shadowSlack) - kEpsilon, kEpsilon);
-                            if (outMarginal) {
-                                const V3 so = offsetRayOrigin(hit, ls.direction);
-                                if (scene.occluded(so, ls.direction, kEpsilon, shadowMax * (1.0f - 2.0e-6f), false, nullptr) !=
-                                    scene.occluded(so, ls.direction, kEpsilon, shadowMax * (1.0f + 2.0e-6f), false, nullptr)) {
-                                    marginal = true;
-                                }
-                            }
-                            if (!occluded(offsetRayOrigin(hit, ls.direction), ls.direction, shadowMax)) {
-                                const BsdfEval be = evaluateBsdf(material, hit.position, shadingNormal, wo, ls.direction, cp);
-                                if (neeContributes(be, cp)) {
-                                    const float weight = neeWeight(ls.pdf, be.pdf, cp);
-                                    V3 contribution = (ls.emission * be.value) * nDotL;
-                                    contribution *= weight / ls.pdf;
-                                    if (finite3(contribution)) {
-                                        const V3 clamped = clampFireflyContribution(throughput, contribution, cp);
-                                        radiance += clamped;
-                                        if (wantSignature && depth < 16u && (clamped.x > 0.0f || clamped.y > 0.0f || clamped.z > 0.0f)) sig |= 1u << depth;
-                                    }
-                                }
-                            }
-                        }
+                    V3 clamped;
+                    if (rectLightNeeAt(scene, rectLights, env, settings, cp, shadowSlack, hit, material, shadingNormal, wo, throughput, rng, occluded,
+                                       outMarginal ? &marginal : nullptr, clamped)) {
+                        radiance += clamped;
+                        if (wantSignature && depth < 16u && (clamped.x > 0.0f || clamped.y > 0.0f || clamped.z > 0.0f)) sig |= 1u << depth;
                     }
                 }
 
@@ -2483,18 +2573,11 @@ void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& set
                     if (finite3(c)) radiance += clampFireflyContribution(throughput, c, cp);
                 };
                 auto rectAlong = [&](V3 origin, V3 dir, V3 weight, float bsdfPdfFloorInput) {
-                    HitInfo lightHit;
-                    if (!trace(Ray{origin, dir}, lightHit)) return;
-                    RectLightHit rh;
-                    if (!rectLightHitInfo(lightIndexByRect, rectLights, rectangles, rectangleCount, env, settings, lightHit, origin, rh)) return;
-                    const float lightPdf = std::max(rh.pdf, kSpecularNeePdfFloor);
-                    const float invLightPdf = std::min(1.0f / lightPdf, kSpecularNeeInvPdfClamp);
-                    const float bsdfPdf = std::max(bsdfPdfFloorInput, kSpecularNeePdfFloor);
-                    const float denom = lightPdf + bsdfPdf;
-                    float misWeight = denom > 0.0f ? (lightPdf / denom) : 0.0f;
-                    misWeight = clampf(misWeight, kMisWeightClampMin, kMisWeightClampMax);
-                    const V3 c = (weight * rh.emission) * (misWeight * invLightPdf);
-                    if (finite3(c)) radiance += clampFireflyContribution(throughput, c, cp);
+                    V3 clamped;
+                    if (rectLightAlong(lightIndexByRect, rectLights, rectangles, rectangleCount, env, settings, cp, origin, dir, weight, bsdfPdfFloorInput,
+                                       throughput, trace, clamped)) {
+                        radiance += clamped;
+                    }
                 };
 
                 if (specNeeEligible || mneeEligible) {
@@ -2628,6 +2711,92 @@ void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& set
         outCounters->prims = cPrims;
         outCounters->shadedHits = cShaded;
         outCounters->triangleHits = cTri;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// function-level entry points of the vertex light code (oracle_api.cpp)
+// ---------------------------------------------------------------------------------------------
+void rectLightNeeBatch(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& settings, const PtrMaterial* materialOverride, const float* rays,
+                       const float* thr, const uint32_t* states, uint64_t n, float* out, uint32_t* outStates) {
+    std::vector<RectLight> rectLights;
+    std::vector<int32_t> lightIndexByRect;
+    buildRectLights(desc, sceneEmissionScale(settings), rectLights, lightIndexByRect);
+    EnvMap envMap;
+    const EnvMap* env = sceneEnvMap(desc, envMap) ? &envMap : nullptr;
+    const ClampParams cp = makeClampParams(settings);
+    const float shadowSlack = sceneShadowSlack(settings);
+    for (uint64_t i = 0; i < n; ++i) {
+        float* o = out + i * kRectNeeFloats;
+        std::memset(o, 0, kRectNeeFloats * sizeof(float));
+        Rng rng;
+        rng.state = states[i];
+        HitInfo hit;
+        const Ray ray{V3(rays + i * 6), V3(rays + i * 6 + 3)};
+        if (intersectScene(scene, ray, hit) && desc.materials && desc.materialCount > 0) {
+            o[0] = 1.0f;
+            const PtrMaterial& material = materialOverride ? *materialOverride : desc.materials[std::min(hit.materialIndex, desc.materialCount - 1)];
+            const uint32_t type = matType(material);
+            const V3 wo = -normalize(ray.direction);
+            const V3 shadingNormal = vertexShadingNormal(hit, type, settings);
+            if (type != PTR_MAT_DIFFUSE_LIGHT && !surfaceIsDeltaAt(material, cp) && !rectLights.empty()) {
+                o[1] = 1.0f;
+                // the shadow query is answered and put on record, and the sample is carried on as if it were unoccluded: the contribution
+                // is reported for every sample that reaches the query
+                bool blocked = false;
+                auto occluded = [&](V3 org, V3 dir, float tMax) {
+                    blocked = scene.occluded(org, dir, kEpsilon, tMax, false, nullptr);
+                    return false;
+                };
+                RectNeeRecord rec;
+                V3 clamped;
+                const bool adds = rectLightNeeAt(scene, rectLights, env, settings, cp, shadowSlack, hit, material, shadingNormal, wo, V3(thr + i * 3), rng,
+                                                 occluded, nullptr, clamped, &rec);
+                const bool positive = adds && (clamped.x > 0.0f || clamped.y > 0.0f || clamped.z > 0.0f);
+                o[2] = rec.sampled ? 1.0f : 0.0f;
+                o[3] = blocked ? 1.0f : 0.0f;
+                o[4] = rec.direction.x, o[5] = rec.direction.y, o[6] = rec.direction.z;
+                o[7] = rec.distance;
+                o[8] = rec.pdf;
+                o[9] = rec.emission.x, o[10] = rec.emission.y, o[11] = rec.emission.z;
+                o[12] = rec.shadowOrigin.x, o[13] = rec.shadowOrigin.y, o[14] = rec.shadowOrigin.z;
+                o[15] = rec.shadowMax;
+                if (adds) o[16] = clamped.x, o[17] = clamped.y, o[18] = clamped.z;
+                o[19] = (positive && !blocked) ? 1.0f : 0.0f;
+            }
+        }
+        outStates[i] = rng.state;
+    }
+}
+
+void lightConnectionBatch(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& settings, const float* in, uint64_t n, float* out) {
+    std::vector<RectLight> rectLights;
+    std::vector<int32_t> lightIndexByRect;
+    buildRectLights(desc, sceneEmissionScale(settings), rectLights, lightIndexByRect);
+    EnvMap envMap;
+    const EnvMap* env = sceneEnvMap(desc, envMap) ? &envMap : nullptr;
+    const ClampParams cp = makeClampParams(settings);
+    auto trace = [&](const Ray& r, HitInfo& h) { return intersectScene(scene, r, h); };
+    for (uint64_t i = 0; i < n; ++i) {
+        const float* p = in + i * 14;
+        float* o = out + i * kLightConnectionFloats;
+        std::memset(o, 0, kLightConnectionFloats * sizeof(float));
+        RectAlongRecord rec;
+        V3 clamped;
+        const bool adds = rectLightAlong(lightIndexByRect, rectLights, desc.rects, desc.rectCount, env, settings, cp, V3(p), V3(p + 3), V3(p + 6), p[9],
+                                         V3(p + 10), trace, clamped, &rec);
+        if (!rec.hit) continue;
+        const HitInfo& h = rec.lightHit;
+        o[0] = 1.0f;
+        o[1] = h.t;
+        o[2] = h.primitiveType == GeomType::Mesh ? 0.0f : (h.primitiveType == GeomType::Spheres ? 1.0f : 2.0f);
+        o[3] = static_cast<float>(h.primitiveIndex);
+        o[4] = rec.isLight ? 1.0f : 0.0f;
+        const bool rect = h.primitiveType == GeomType::Rectangles && h.primitiveIndex < lightIndexByRect.size();
+        o[5] = static_cast<float>(rect ? lightIndexByRect[h.primitiveIndex] : -1);
+        if (adds) o[6] = clamped.x, o[7] = clamped.y, o[8] = clamped.z;
+        o[9] = rec.pdfForHit;
+        o[10] = h.frontFace ? 1.0f : 0.0f;
     }
 }
 

@@ -134,6 +134,20 @@ V3 nextRayOrigin(const HitInfo& hit, V3 direction);   // OffsetRayOrigin, E:917-
 // Samples texture `texture` of the scene with the filtering rule of the textured metallic-roughness model: in n * {u, v, lod}, out n * RGBA.
 void sampleTextures(const PtrSceneDesc& desc, uint32_t texture, const float* in, uint64_t n, float* out);
 
+// The light side of a path vertex, one vertex at a time (the code render() runs, E:2710-2772 and the rectAlong of E:2856-2917).
+// rectLightNeeBatch: the vertex each ray of rays (n * 6 {origin, direction}) hits, shaded with its own material or with materialOverride,
+// throughput thr (n * 3), random state states[n].  out n * kRectNeeFloats {hit, light sampling ran (no emitter, no delta surface),
+// sampled (the shadow query was made), occluded (its answer), direction xyz, distance, pdf, emission rgb, shadow origin xyz, shadowMax,
+// contribution rgb (evaluated whatever the query answered), contributes (positive and not occluded: what render() adds), 0...}.
+constexpr uint32_t kRectNeeFloats = 24;
+void rectLightNeeBatch(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& settings, const PtrMaterial* materialOverride, const float* rays,
+                       const float* thr, const uint32_t* states, uint64_t n, float* out, uint32_t* outStates);
+// lightConnectionBatch: in n * 14 {origin, direction, bsdf weight rgb, bsdf pdf, throughput rgb, 0}; out n * kLightConnectionFloats {hit, t,
+// primitive type (0 mesh, 1 sphere, 2 rectangle), primitive index, the hit is a light that emits towards the ray (rectLightHitInfo), its
+// light index (-1: none), contribution rgb, rectLightPdfForHit of the hit from the origin, front face, 0}.
+constexpr uint32_t kLightConnectionFloats = 12;
+void lightConnectionBatch(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& settings, const float* in, uint64_t n, float* out);
+
 // Renders pixels with y in [y0, y1) (full width); out_rgb is the full W*H*3 image, other rows untouched.
 // out_signature / out_marginal (optional, W*H each): path signature of every pixel's last sample and whether one of its
 // rectangle-light shadow tests is decided within rounding noise of the ray length (deterministic-stream diagnostics).

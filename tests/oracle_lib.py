@@ -44,6 +44,10 @@ def lib():
         l.oracle_env_build.restype = C.c_int
         l.oracle_env_sample.argtypes = [fp, u32, u32, C.c_float, C.c_float, fp, u64, fp, fp]
         l.oracle_env_sample.restype = C.c_int
+        l.oracle_env_eval.argtypes = [fp, u32, u32, C.c_float, C.c_float, fp, u64, fp]
+        l.oracle_env_eval.restype = C.c_int
+        l.oracle_rect_light_nee.argtypes = [vp, C.POINTER(pt.PtrSettings), C.POINTER(pt.PtrMaterial), fp, fp, up, u64, fp, up]
+        l.oracle_light_connection.argtypes = [vp, C.POINTER(pt.PtrSettings), fp, u64, fp]
         _lib = l
     return _lib
 
@@ -98,6 +102,39 @@ class OracleScene:
         out = np.zeros((rays.shape[0], 16), dtype=np.float32)
         lib().oracle_surface_hits(self._h, _f(rays), rays.shape[0], _f(out))
         return out
+
+    # columns of rect_light_nee's rows (oracle/oracle_integrator.h rectLightNeeBatch)
+    NEE_FIELDS = {"hit": 0, "ran": 1, "sampled": 2, "occluded": 3, "direction": slice(4, 7), "distance": 7, "pdf": 8, "emission": slice(9, 12),
+                  "shadow_origin": slice(12, 15), "shadow_max": 15, "contribution": slice(16, 19), "contributes": 19}
+    # columns of light_connection's rows (lightConnectionBatch)
+    CONNECTION_FIELDS = {"hit": 0, "t": 1, "prim_type": 2, "prim_index": 3, "is_light": 4, "light": 5, "contribution": slice(6, 9), "pdf": 9,
+                         "front_face": 10}
+
+    def rect_light_nee(self, settings, rays, thr, states, material=None):
+        """The integrator's rectangle-light NEE (E:2710-2772) at the vertex each ray [n, 6] {origin, direction} hits, with throughput thr
+        [n, 3] and random states [n]; material: an override for the hit's own.  Returns (NEE_FIELDS -> arrays plus "raw" [n, 24], the random
+        states afterwards)."""
+        rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)
+        thr = np.ascontiguousarray(thr, dtype=np.float32).reshape(-1, 3)
+        states = np.ascontiguousarray(states, dtype=np.uint32).reshape(-1)
+        assert thr.shape[0] == rays.shape[0] == states.shape[0]
+        out = np.zeros((rays.shape[0], 24), dtype=np.float32)
+        out_states = np.zeros(rays.shape[0], dtype=np.uint32)
+        lib().oracle_rect_light_nee(self._h, C.byref(settings), None if material is None else C.byref(material), _f(rays), _f(thr), _u(states),
+                                    rays.shape[0], _f(out), _u(out_states))
+        res = {k: out[:, v] for k, v in self.NEE_FIELDS.items()}
+        res["raw"] = out
+        return res, out_states
+
+    def light_connection(self, settings, inputs):
+        """The specular connection to the rectangle lights (rectAlong, E:2856-2917) along inputs [n, 14] {origin, direction, bsdf weight,
+        bsdf pdf, throughput, 0}: CONNECTION_FIELDS -> arrays plus "raw" [n, 12]."""
+        inputs = np.ascontiguousarray(inputs, dtype=np.float32).reshape(-1, 14)
+        out = np.zeros((inputs.shape[0], 12), dtype=np.float32)
+        lib().oracle_light_connection(self._h, C.byref(settings), _f(inputs), inputs.shape[0], _f(out))
+        res = {k: out[:, v] for k, v in self.CONNECTION_FIELDS.items()}
+        res["raw"] = out
+        return res
 
     def close(self):
         if self._h:
@@ -181,3 +218,12 @@ def env_sample(rgba, rotation, intensity, u):
     look = np.zeros((u.shape[0], 4), dtype=np.float32)
     rc = lib().oracle_env_sample(_f(rgba), rgba.shape[1], rgba.shape[0], rotation, intensity, _f(u), u.shape[0], _f(out), _f(look))
     return rc, out, look
+
+
+def env_eval(rgba, rotation, intensity, directions):
+    """SampleEnvironment and EnvironmentPdf along directions [n, 3] (any length): (rc, [n, 4] {rgb, pdf}); rc != 0: no distribution."""
+    rgba = np.ascontiguousarray(rgba, dtype=np.float32)
+    directions = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+    out = np.zeros((directions.shape[0], 4), dtype=np.float32)
+    rc = lib().oracle_env_eval(_f(rgba), rgba.shape[1], rgba.shape[0], rotation, intensity, _f(directions), directions.shape[0], _f(out))
+    return rc, out

@@ -39,7 +39,7 @@ def test_library_exports_every_declared_symbol():
         text = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
         for name, params in re.findall(r"\b(ptr_[a-z_]+)\s*\(([^()]*)\)\s*;", text):
             counts[name] = 0 if params.strip() in ("", "void") else params.count(",") + 1
-    assert set(counts) == declared and len(counts) == 44
+    assert set(counts) == declared and len(counts) == 48
     assert min(counts.values()) == 0 and max(counts.values()) == 12
     restypes = {"ptr_version": C.c_char_p, "ptr_part_band_count": C.c_uint32, "ptr_scene_release": None, "ptr_host_scene_free": None}
     for name, count in counts.items():

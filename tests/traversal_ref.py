@@ -52,6 +52,11 @@ class Reference:
         self.v0, self.e1, self.e2 = v0, v1 - v0, v2 - v0
         self.n = np.cross(self.e1, self.e2)
 
+    def extent(self):
+        """The length L per triangle that turns a position error into a barycentric one (see the margin's resolution in _chunk): the
+        square root of the parallelogram's area, the edge length of a triangle that is about as wide as it is long."""
+        return np.sqrt(np.maximum(np.linalg.norm(self.n, axis=1), 1e-300))
+
     def trace(self, rays, chunk=0):
         """rays [n, 8] float32 {o, tmin, d, tmax}.  Returns a dict of [n] arrays: t (inf on a miss), kind (-1 miss, 0 triangle, 1 sphere),
         index (triangle or sphere number), cos (|cos| between ray and normal at the hit), margin (the smallest |signed barycentric| of any
@@ -113,7 +118,7 @@ class Reference:
             # known to about 8 * 2^-24 * X / (L |cos|) - the margin is counted in units of that resolution instead)
             nlen = np.maximum(np.linalg.norm(self.n, axis=1), 1e-300)[None]
             cosr = np.maximum(np.abs(den) / (nlen * np.linalg.norm(d, axis=2)), 1e-300)
-            resol = np.maximum(1.0, 8.0 * 2.0 ** -24 * (np.abs(o).max(axis=2) + np.abs(self.v0).max(axis=1)[None]) / (np.sqrt(nlen) * cosr) / 1e-6)
+            resol = np.maximum(1.0, 8.0 * 2.0 ** -24 * (np.abs(o).max(axis=2) + np.abs(self.v0).max(axis=1)[None]) / (self.extent()[None] * cosr) / 1e-6)
             m = np.abs(np.minimum(np.minimum(u, v), w)) / resol
             margin = np.minimum(margin, np.where(plane, m, np.inf).min(axis=1))
             near |= (inside & np.isfinite(t) & ends(t)).any(axis=1)
