@@ -32,6 +32,8 @@ struct ShadeResets {
 // env: PTR_METAL_ENV_LOD (device_types.h; all null without the bit)
 void launchShade(const RenderParams& rp, const SceneView& sc, const PathPool& pool, const ShadeResets& resets, const EnvLodView& env, bool count,
                  hipStream_t stream);
+// the material / feature set of the k_shade instantiation launchShade picks (bsdf.h kAllMaterials = the full kernel)
+uint32_t shadeKernelSet(const RenderParams& rp, const SceneView& sc, bool count);
 void launchConnect(const RenderParams& rp, const SceneView& sc, const PathPool& pool, const LaunchConfig& cfg, bool count,
                    hipStream_t stream);
 // End of the frame: every busy slot of `pool` (the WHOLE pool) is run to the end of its path by one lane (k_tail_collect + k_tail_run).
@@ -53,7 +55,8 @@ void launchTraceRays(const SceneView& sc, const float4* dRays, uint64_t n, bool 
 void launchAovs(const RenderParams& rp, const SceneView& sc, uint32_t sample, float4* dAlbedo, float4* dNormal, const LaunchConfig& cfg,
                 hipStream_t stream);
 
-// Debug / known-answer kernels (tests only): evaluate and sample a material for a batch of inputs.
+// ---- tests only: debug / known-answer kernels (ptr_debug.h) ----
+// evaluate and sample a material for a batch of inputs
 void launchDebugEvalBsdf(const float4* dMaterial, const RenderParams& rp, const float* dIn, uint64_t n, float* dOut,
                          hipStream_t stream);
 void launchDebugSampleBsdf(const float4* dMaterial, const RenderParams& rp, const float* dIn, const uint32_t* dFront,
@@ -66,9 +69,6 @@ void launchDebugSampleLobes(const float4* dMaterial, const RenderParams& rp, con
 void launchDebugEnvLookup(const RenderParams& rp, const SceneView& sc, const EnvLodView& env, const float4* dIn, uint64_t n, float4* dOut,
                           hipStream_t stream);
 void launchDebugTexSample(const SceneView& sc, uint32_t texture, const float* dIn, uint64_t n, float4* dOut, hipStream_t stream);
-// closest hit, surface record and next-ray origin per input ray: in n x 9 floats {origin, direction, next direction}, out n x 16 floats
-// the material / feature set of the k_shade instantiation launchShade picks (bsdf.h kAllMaterials = the full kernel)
-uint32_t shadeKernelSet(const RenderParams& rp, const SceneView& sc, bool count);
 // PTR_METAL_RAY_DIFF: the gradient sample (in n x 6 {u, v, dudx, dvdx, dudy, dvdy}) and the first hit's textured material of the camera rays
 // of n {x, y, sample} (out n x 36 floats, ptr_debug.h ptr_debug_first_hit_textures)
 void launchDebugTexSampleGrad(const SceneView& sc, uint32_t texture, const float* dIn, uint64_t n, float4* dOut, hipStream_t stream);
@@ -77,10 +77,10 @@ void launchDebugFirstHit(const RenderParams& rp, const SceneView& sc, const uint
 // ptr_debug_extend_rays: k_extend's hit words (dHits, n) of the rays dRays (n x 2 float4) as PtrHit records
 void launchDebugHitRecords(const SceneView& sc, const float4* dRays, const float2* dHits, uint64_t n, uint32_t triCount, uint32_t sphereCount,
                            PtrHit* dOut, hipStream_t stream);
+// closest hit, surface record and next-ray origin per input ray: in n x 9 floats {origin, direction, next direction}, out n x 16 floats
 void launchDebugSurfaceHits(const SceneView& sc, const float* dIn, uint64_t n, float* dOut, const LaunchConfig& cfg, hipStream_t stream);
 void launchDebugCameraRays(const RenderParams& rp, const uint32_t* dXys, uint64_t n, float* dOut, uint32_t* dRngOut,
                            hipStream_t stream);
-
 // The light side of a path vertex (ptr_debug.h): environment sampling and level-0 lookups (out: 2 n / n float4), rectLightNee at the hits of
 // a batch of rays (record 0 of `pool` and dHead receive the result; dMaterial null = the hit's own material), settled connections
 void launchDebugEnvSample(const RenderParams& rp, const SceneView& sc, const float* dU, uint64_t n, float4* dOut, hipStream_t stream);

@@ -204,9 +204,6 @@ struct SubLists {
 #ifndef PTR_BUSY_SHADE_DIV
 #define PTR_BUSY_SHADE_DIV 4
 #endif
-#ifndef PTR_LIGHT_PRETEST   // A/B switch of the light self-occlusion test in k_shade
-#define PTR_LIGHT_PRETEST 1
-#endif
 constexpr uint32_t kItemReserve = 64u;   // work items a wave reserves per atomic on the global head
 
 // ---------------------------------------------------------------- camera
@@ -579,19 +576,38 @@ __device__ __forceinline__ Surface rectLightSurface(const SceneView& sc, f3 org,
     return s;
 }
 
+// What a light found straight along a delta direction is weighted with: the inverse of its (floored) pdf, clamped, and the MIS term
+// against the BSDF's pdf, clamped to [kMisMin, kMisMax].  The call sites multiply (BSDF weight * radiance) by (mis * invPdf): the two
+// scalars are handed back apart so that the product stays where k_shade's schedule has it.
+struct SpecularLightWeight {
+    float mis, invPdf;
+};
+__device__ __forceinline__ SpecularLightWeight specularLightWeight(float lightPdfIn, float bsdfPdfIn) {
+    const float lightPdf = smax(lightPdfIn, kSpecNeePdfFloor);
+    const float invLightPdf = smin(1.0f / lightPdf, kSpecNeeInvPdfClamp);
+    const float bsdfPdf = smax(bsdfPdfIn, kSpecNeePdfFloor);
+    const float denom = lightPdf + bsdfPdf;
+    float mis = denom > 0.0f ? (lightPdf / denom) : 0.0f;
+    mis = clampf(mis, kMisMin, kMisMax);
+    return {mis, invLightPdf};
+}
+
+// MIS weight of a BSDF-sampled ray (density lastPdf) that reaches a light whose sampling would have chosen the direction with lightPdf
+__device__ __forceinline__ float bsdfSideMis(float lastPdf, float lightPdf) {
+    float mis = 1.0f;
+    const float denom = lastPdf + lightPdf;
+    if (denom > 0.0f) mis = lastPdf / denom;
+    return clampf(mis, kMisMin, kMisMax);
+}
+
 // Contribution of a specular-NEE ray whose closest hit is the light surface `ls` (kind 1 records once traced; kind 3 records up front).
 __device__ __forceinline__ f3 rectContributionAt(const RenderParams& rp, const SceneView& sc, const ClampCfg& cc, const Surface& ls, f3 org, f3 weight,
                                                  float bsdfPdfIn, f3 thr) {
     f3 emission;
     float pdf;
     if (!rectLightHit(sc, ls, org, rp.emissionScale, emission, pdf)) return mk3(0.0f);
-    const float lightPdf = smax(pdf, kSpecNeePdfFloor);
-    const float invLightPdf = smin(1.0f / lightPdf, kSpecNeeInvPdfClamp);
-    const float bsdfPdf = smax(bsdfPdfIn, kSpecNeePdfFloor);
-    const float denom = lightPdf + bsdfPdf;
-    float mis = denom > 0.0f ? (lightPdf / denom) : 0.0f;
-    mis = clampf(mis, kMisMin, kMisMax);
-    const f3 contrib = (weight * emission) * (mis * invLightPdf);
+    const SpecularLightWeight w = specularLightWeight(pdf, bsdfPdfIn);
+    const f3 contrib = (weight * emission) * (w.mis * w.invPdf);
     return finite3(contrib) ? clampFirefly(thr, contrib, cc) : mk3(0.0f);
 }
 
@@ -602,11 +618,6 @@ __device__ __forceinline__ bool anyHitFound(uint32_t hitWord) {
     return (hitWord >> 30) == 0u || ((hitWord >> 30) == 2u && ((hitWord >> kHitKeyShift) & kHitKeyMask) == 0u);
 }
 
-struct PendingRay {
-    f3 org, dir;
-    float tmax;
-};
-
 __device__ __forceinline__ void storeRecord(const PathPool& pool, uint32_t slot, uint32_t which, uint32_t kind, f3 org, float tmaxOrBits,
                                             f3 dir, f3 a, float aw, f3 b) {
     const ShadowRecordView& r = pool.rec[which];
@@ -614,6 +625,42 @@ __device__ __forceinline__ void storeRecord(const PathPool& pool, uint32_t slot,
     r.dir[slot] = mk4(dir, __uint_as_float(kind));
     r.a[slot] = mk4(a, aw);
     if (kind != 0u) r.b[slot] = mk4(b, 0.0f);
+}
+
+// The traversal stack of one lane of a kernel that traces rays: its column of the block's LDS words (kLdsStackLevels * kTraceBlock of them),
+// then of the launch's spill area; empty.
+__device__ __forceinline__ LaneStack laneStack(uint32_t* ldsStack, uint32_t* spill, uint32_t spillStride, const SceneView& sc) {
+    LaneStack stack;
+    stack.lds = (LdsWord*)(ldsStack + threadIdx.x);
+    stack.spill = spill;
+    stack.spillStride = spillStride;
+    stack.limit = sc.stackLimit;
+    stack.sp = 0u;
+    return stack;
+}
+
+// Feeder chunk of a persistent kernel that walks a connect / busy list of `entries` with `waves` resident waves: a list with fewer than
+// 256 entries per wave is dealt out in smaller chunks, down to one wave-load each.  On a scene that queues few connections (config 5:
+// 0.2 M records per launch over a 29 M-triangle tree) chunks of 256 put four latency-bound batches one after the other on a quarter of
+// the waves while the others had nothing ("short connect / busy lists in chunks": +1.8 %).
+// (waves is passed in: a helper that read blockDim itself made k_connect reload the block size from the dispatch packet)
+__device__ __forceinline__ uint32_t shortListChunk(uint32_t entries, uint32_t waves) {
+    return min(256u, max(64u, ((entries + waves - 1u) / waves + 63u) & ~63u));
+}
+
+// counting build: rays, nodes and primitive tests of a kernel's any-hit queries (booked as shadow rays) and of its closest-hit ones
+// (booked with the extend counters, as the reference counts them)
+template <bool COUNT>
+__device__ __forceinline__ void addTraceCounters(uint64_t* counters, uint32_t raysAny, const TraceCounters& any, uint32_t raysClosest,
+                                                 const TraceCounters& closest) {
+    if constexpr (COUNT) {
+        addCounter(counters, kCntShadowRays, raysAny);
+        addCounter(counters, kCntShadowNodes, any.nodes);
+        addCounter(counters, kCntShadowPrims, any.prims);
+        addCounter(counters, kCntExtendRays, raysClosest);
+        addCounter(counters, kCntExtendNodes, closest.nodes);
+        addCounter(counters, kCntExtendPrims, closest.prims);
+    }
 }
 
 }  // namespace
@@ -652,12 +699,7 @@ template <bool COUNT, bool ALIVE, int NODES>
 __global__ void __launch_bounds__(kTraceBlock) PTR_EXTEND_ATTR k_extend(SceneView sc, PathPool pool, uint32_t* spill, uint32_t spillStride, uint32_t* workCounter,
                                                          int kRefillBelow, uint32_t feederChunk, uint32_t* aliveOut) {
     __shared__ uint32_t ldsStack[kLdsStackLevels * kTraceBlock];
-    LaneStack stack;
-    stack.lds = (LdsWord*)(ldsStack + threadIdx.x);
-    stack.spill = spill;
-    stack.spillStride = spillStride;
-    stack.limit = sc.stackLimit;
-    stack.sp = 0u;
+    LaneStack stack = laneStack(ldsStack, spill, spillStride, sc);
     TraceCounters cnt{0u, 0u};
     uint32_t rays = 0u;
     uint32_t aliveSeen = 0u;   // live slots this wave picked up (host termination check, end of the frame only)
@@ -678,13 +720,7 @@ __global__ void __launch_bounds__(kTraceBlock) PTR_EXTEND_ATTR k_extend(SceneVie
         }
     }
     WaveFeeder feeder;
-    // (a short list is dealt out in chunks of less than 256, down to one wave-load per resident wave: see k_connect)
-#ifdef PTR_CONNECT_CHUNK_FIXED   // (A/B switch)
-    const uint32_t listChunk = 256u;
-#else
-    const uint32_t listWaves = (gridDim.x * blockDim.x) >> 6;
-    const uint32_t listChunk = min(256u, max(64u, ((lists.total + listWaves - 1u) / listWaves + 63u) & ~63u));
-#endif
+    const uint32_t listChunk = shortListChunk(lists.total, (gridDim.x * blockDim.x) >> 6);
     feeder.init(workCounter, lists.total, listed ? listChunk : feederChunk);
     Trav t;
     t.cur = 0u;
@@ -1238,7 +1274,7 @@ __device__ __forceinline__ bool rectLightNee(const RenderParams& rp, const Scene
     float tt, tu, tv;
     bool occludedByLight = false;
     if (COUNT) counts.stage[5] += 1u;
-    if (PTR_LIGHT_PRETEST != 0 && l3.w != 0.0f) {
+    if (l3.w != 0.0f) {
         occludedByLight = triangleTest(mk3(row(5)), mk3(row(6)), mk3(row(7)), shadowOrg, ldir, kEps, shadowMax, tt, tu, tv) ||
                           triangleTest(mk3(row(8)), mk3(row(9)), mk3(row(10)), shadowOrg, ldir, kEps, shadowMax, tt, tu, tv);
     }
@@ -1247,6 +1283,14 @@ __device__ __forceinline__ bool rectLightNee(const RenderParams& rp, const Scene
     if (COUNT) counts.stage[6] += 1u;
     storeRecord(pool, slot, 0u, 0u, shadowOrg, shadowMax, ldir, clamped, static_cast<float>(depth), mk3(0.0f));
     return true;
+}
+
+// Whether a surface scatters into delta directions only: it then takes no light sample (and draws no random number for one).
+template <bool SSS>
+__device__ __forceinline__ bool surfaceIsDelta(const Mat& mat, uint32_t type, const ClampCfg& cc) {
+    bool surfaceDelta = materialIsDelta(mat);
+    if (SSS && cc.metalPbr && type == 7u) surfaceDelta = mat.roughness01() <= 1.0e-3f;   // pathtrace.metal:4578-4581
+    return surfaceDelta;
 }
 
 // One visit of a path slot: what k_shade does for its thread's slot.  MODE kShadeDense: lane l of wave w holds slot 64 w + l.
@@ -1445,12 +1489,7 @@ __device__ __forceinline__ void shadeSlot(const RenderParams& rp, const SceneVie
                 }
                 float mis = 1.0f;
                 const bool useMis = (!lastDelta) || rp.enableSpecularNee || rp.enableMnee;
-                if (useMis && envSampling) {
-                    const float lightPdf = envPdfOf(sc, rayD, rp.envRotation);
-                    const float denom = lastPdf + lightPdf;
-                    if (denom > 0.0f) mis = lastPdf / denom;
-                    mis = clampf(mis, kMisMin, kMisMax);
-                }
+                if (useMis && envSampling) mis = bsdfSideMis(lastPdf, envPdfOf(sc, rayD, rp.envRotation));
                 acc += clampFirefly(thr, bg * mis, cc);
                 if (COUNT) sig = (sig & 0xFFFFu) | (sigHashStep(sig >> 16, 7u, 0u, 0u) << 16);
                 endPath = true;
@@ -1539,18 +1578,14 @@ __device__ __forceinline__ void shadeSlot(const RenderParams& rp, const SceneVie
                         float mis = 1.0f;
                         const bool useMis = (!lastDelta) || rp.enableSpecularNee || rp.enableMnee;
                         if (useMis && sc.rectLightCount > 0u) {
-                            const float lightPdf = rectLightPdfForHit(sc, sf.primType, sf.primIndex, sf.position, rayO);
-                            const float denom = lastPdf + lightPdf;
-                            if (denom > 0.0f) mis = lastPdf / denom;
-                            mis = clampf(mis, kMisMin, kMisMax);
+                            mis = bsdfSideMis(lastPdf, rectLightPdfForHit(sc, sf.primType, sf.primIndex, sf.position, rayO));
                         }
                         acc += clampFirefly(thr, emission * mis, cc);
                     }
                     endPath = true;
                     partEnd<COUNT>(counts, kShadePartEmitter, tEmitter);
                 } else {
-                    bool surfaceDelta = materialIsDelta(mat);
-                    if (SSS && cc.metalPbr && type == 7u) surfaceDelta = mat.roughness01() <= 1.0e-3f;   // pathtrace.metal:4578-4581
+                    const bool surfaceDelta = surfaceIsDelta<SSS>(mat, type, cc);
 
                     // ---- rectangle-light NEE (3 random numbers, drawn even if the sample is rejected) ----
                     if (!surfaceDelta && sc.rectLightCount > 0u) {
@@ -1650,14 +1685,9 @@ __device__ __forceinline__ void shadeSlot(const RenderParams& rp, const SceneVie
                             const f3 sdir = normalize(bs.dir);
                             const f3 sorg = offsetOrigin(of, sdir);
                             if (envSampling) {
-                                const float envPdf = smax(envPdfOf(sc, sdir, rp.envRotation), kSpecNeePdfFloor);
-                                const float invEnvPdf = smin(1.0f / envPdf, kSpecNeeInvPdfClamp);
-                                const float bsdfPdf = smax(bs.pdf, kSpecNeePdfFloor);
-                                const float denom = envPdf + bsdfPdf;
-                                float mis = denom > 0.0f ? (envPdf / denom) : 0.0f;
-                                mis = clampf(mis, kMisMin, kMisMax);
+                                const SpecularLightWeight w = specularLightWeight(envPdfOf(sc, sdir, rp.envRotation), bs.pdf);
                                 const f3 envColor = envLookup(sc, sdir, rp.envRotation, rp.envIntensity);
-                                const f3 contrib = (bs.weight * envColor) * (mis * invEnvPdf);
+                                const f3 contrib = (bs.weight * envColor) * (w.mis * w.invPdf);
                                 if (finite3(contrib)) {
                                     const f3 clamped = clampFirefly(thr, contrib, cc);
                                     if (clamped.x > 0.0f || clamped.y > 0.0f || clamped.z > 0.0f) {
@@ -1903,23 +1933,19 @@ __global__ void __launch_bounds__(kShadeBlock) PTR_SHADE_WAVES_ATTR_M k_shade(Re
 // =====================================================================================================
 namespace {
 
+// Contribution of a specular-NEE ray whose closest hit `h` has been found (kind 1 records).
+__device__ __forceinline__ f3 rectContribution(const RenderParams& rp, const SceneView& sc, const ClampCfg& cc, f3 org, f3 dir,
+                                               const TraceHit& h, f3 weight, float bsdfPdfIn, f3 thr) {
+    if (h.prim == kHitMiss) return mk3(0.0f);
+    const Surface ls = reconstruct(sc, org, dir, h.t, h.prim);
+    return rectContributionAt(rp, sc, cc, ls, org, weight, bsdfPdfIn, thr);
+}
+
 template <bool COUNT>
 __device__ __forceinline__ f3 alongRect(const RenderParams& rp, const SceneView& sc, const ClampCfg& cc, f3 org, f3 dir, f3 weight,
                                         float bsdfPdfIn, f3 thr, LaneStack& stack, TraceCounters& cnt) {
     const TraceHit h = traverse<false, COUNT>(sc, org, dir, kEps, INFINITY, stack, cnt);
-    if (h.prim == kHitMiss) return mk3(0.0f);
-    const Surface ls = reconstruct(sc, org, dir, h.t, h.prim);
-    f3 emission;
-    float pdf;
-    if (!rectLightHit(sc, ls, org, rp.emissionScale, emission, pdf)) return mk3(0.0f);
-    const float lightPdf = smax(pdf, kSpecNeePdfFloor);
-    const float invLightPdf = smin(1.0f / lightPdf, kSpecNeeInvPdfClamp);
-    const float bsdfPdf = smax(bsdfPdfIn, kSpecNeePdfFloor);
-    const float denom = lightPdf + bsdfPdf;
-    float mis = denom > 0.0f ? (lightPdf / denom) : 0.0f;
-    mis = clampf(mis, kMisMin, kMisMax);
-    const f3 contrib = (weight * emission) * (mis * invLightPdf);
-    return finite3(contrib) ? clampFirefly(thr, contrib, cc) : mk3(0.0f);
+    return rectContribution(rp, sc, cc, org, dir, h, weight, bsdfPdfIn, thr);
 }
 
 template <bool COUNT>
@@ -1927,25 +1953,10 @@ __device__ __forceinline__ f3 alongEnv(const RenderParams& rp, const SceneView& 
                                        float bsdfPdfIn, f3 thr, LaneStack& stack, TraceCounters& cnt) {
     const TraceHit h = traverse<true, COUNT>(sc, org, dir, kEps, INFINITY, stack, cnt);
     if (h.prim != kHitMiss) return mk3(0.0f);
-    const float envPdf = smax(envPdfOf(sc, dir, rp.envRotation), kSpecNeePdfFloor);
-    const float invEnvPdf = smin(1.0f / envPdf, kSpecNeeInvPdfClamp);
-    const float bsdfPdf = smax(bsdfPdfIn, kSpecNeePdfFloor);
-    const float denom = envPdf + bsdfPdf;
-    float mis = denom > 0.0f ? (envPdf / denom) : 0.0f;
-    mis = clampf(mis, kMisMin, kMisMax);
+    const SpecularLightWeight w = specularLightWeight(envPdfOf(sc, dir, rp.envRotation), bsdfPdfIn);
     const f3 envColor = envLookup(sc, dir, rp.envRotation, rp.envIntensity);
-    const f3 contrib = (weight * envColor) * (mis * invEnvPdf);
+    const f3 contrib = (weight * envColor) * (w.mis * w.invPdf);
     return finite3(contrib) ? clampFirefly(thr, contrib, cc) : mk3(0.0f);
-}
-
-
-
-// Contribution of a specular-NEE ray whose closest hit `h` has been found (kind 1 records).
-__device__ __forceinline__ f3 rectContribution(const RenderParams& rp, const SceneView& sc, const ClampCfg& cc, f3 org, f3 dir,
-                                               const TraceHit& h, f3 weight, float bsdfPdfIn, f3 thr) {
-    if (h.prim == kHitMiss) return mk3(0.0f);
-    const Surface ls = reconstruct(sc, org, dir, h.t, h.prim);
-    return rectContributionAt(rp, sc, cc, ls, org, weight, bsdfPdfIn, thr);
 }
 
 // MNEE second bounce (kind 2 records): follow the specular ray to the next delta surface, scatter with a copy
@@ -1991,12 +2002,7 @@ template <bool COUNT, int NODES>
 __global__ void __launch_bounds__(kTraceBlock) PTR_EXTEND_ATTR k_connect(RenderParams rp, SceneView sc, PathPool pool, uint32_t* spill, uint32_t spillStride,
                                                           uint32_t* workCounter, int kRefillBelow, uint32_t feederChunk) {
     __shared__ uint32_t ldsStack[kLdsStackLevels * kTraceBlock];
-    LaneStack stack;
-    stack.lds = (LdsWord*)(ldsStack + threadIdx.x);
-    stack.spill = spill;
-    stack.spillStride = spillStride;
-    stack.limit = sc.stackLimit;
-    stack.sp = 0u;
+    LaneStack stack = laneStack(ldsStack, spill, spillStride, sc);
     TraceCounters cnt{0u, 0u}, cntClosest{0u, 0u};
     uint32_t rays = 0u, raysClosest = 0u, early = 0u;
     const ClampCfg cc = clampCfg(rp);
@@ -2008,16 +2014,7 @@ __global__ void __launch_bounds__(kTraceBlock) PTR_EXTEND_ATTR k_connect(RenderP
     SubLists lists;
     lists.init(pool.connectCount, pool.connectRegion);
     WaveFeeder feeder;
-    // a list with fewer than 256 entries per resident wave is dealt out in smaller chunks, down to one wave-load each: on a scene that
-    // queues few connections (config 5: 0.2 M records per launch over a 29 M-triangle tree) chunks of 256 put four latency-bound
-    // batches one after the other on a quarter of the waves while the others had nothing
-#ifdef PTR_CONNECT_CHUNK_FIXED   // (A/B switch)
-    const uint32_t connectChunk = 256u;
-#else
-    const uint32_t connectWaves = (gridDim.x * blockDim.x) >> 6;
-    const uint32_t connectChunk = min(256u, max(64u, ((lists.total + connectWaves - 1u) / connectWaves + 63u) & ~63u));
-#endif
-    feeder.init(workCounter, lists.total, connectChunk);
+    feeder.init(workCounter, lists.total, shortListChunk(lists.total, (gridDim.x * blockDim.x) >> 6));
     Trav t;
     t.cur = 0u;
     bool active = false;
@@ -2081,15 +2078,8 @@ __global__ void __launch_bounds__(kTraceBlock) PTR_EXTEND_ATTR k_connect(RenderP
             }
         }
     }
-    if (COUNT) {
-        addCounter(pool.counters, kCntShadowRays, rays);
-        addCounter(pool.counters, kCntShadowNodes, cnt.nodes);
-        addCounter(pool.counters, kCntShadowPrims, cnt.prims);
-        addCounter(pool.counters, kCntShadowEarlyExit, early);
-        addCounter(pool.counters, kCntExtendRays, raysClosest);
-        addCounter(pool.counters, kCntExtendNodes, cntClosest.nodes);
-        addCounter(pool.counters, kCntExtendPrims, cntClosest.prims);
-    }
+    addTraceCounters<COUNT>(pool.counters, rays, cnt, raysClosest, cntClosest);
+    if (COUNT) addCounter(pool.counters, kCntShadowEarlyExit, early);
 }
 
 // MNEE two-bounce chains (record slot 4, kind 2; only launched when enableMnee && enableMneeSecondary).
@@ -2097,12 +2087,7 @@ template <bool COUNT>
 __global__ void __launch_bounds__(kTraceBlock) k_connect_chain(RenderParams rp, SceneView sc, PathPool pool, uint32_t* spill, uint32_t spillStride) {
     __shared__ uint32_t ldsStack[kLdsStackLevels * kTraceBlock];
     const uint32_t gtid = blockIdx.x * kTraceBlock + threadIdx.x;
-    LaneStack stack;
-    stack.lds = (LdsWord*)(ldsStack + threadIdx.x);
-    stack.spill = spill;
-    stack.spillStride = spillStride;
-    stack.limit = sc.stackLimit;
-    stack.sp = 0u;
+    LaneStack stack = laneStack(ldsStack, spill, spillStride, sc);
     TraceCounters cnt{0u, 0u}, cntClosest{0u, 0u};
     uint32_t rays = 0u, raysClosest = 0u;
     const ClampCfg cc = clampCfg(rp);
@@ -2116,14 +2101,7 @@ __global__ void __launch_bounds__(kTraceBlock) k_connect_chain(RenderParams rp, 
                                       cntClosest, rays, raysClosest);
         r.a[slot] = mk4(c, 0.0f);
     }
-    if (COUNT) {
-        addCounter(pool.counters, kCntShadowRays, rays);
-        addCounter(pool.counters, kCntShadowNodes, cnt.nodes);
-        addCounter(pool.counters, kCntShadowPrims, cnt.prims);
-        addCounter(pool.counters, kCntExtendRays, raysClosest);
-        addCounter(pool.counters, kCntExtendNodes, cntClosest.nodes);
-        addCounter(pool.counters, kCntExtendPrims, cntClosest.prims);
-    }
+    addTraceCounters<COUNT>(pool.counters, rays, cnt, raysClosest, cntClosest);
 }
 
 // =====================================================================================================
@@ -2173,12 +2151,7 @@ template <bool COUNT, bool SSS, bool TEX>
 __global__ void __launch_bounds__(kTraceBlock) k_tail_run(RenderParams rp, SceneView sc, PathPool pool, const uint32_t* list, const uint32_t* listCount,
                                                           uint32_t* listHead, uint32_t* spill, uint32_t spillStride, EnvLodView env) {
     __shared__ uint32_t ldsStack[kLdsStackLevels * kTraceBlock];
-    LaneStack stack;
-    stack.lds = (LdsWord*)(ldsStack + threadIdx.x);
-    stack.spill = spill;
-    stack.spillStride = spillStride;
-    stack.limit = sc.stackLimit;
-    stack.sp = 0u;
+    LaneStack stack = laneStack(ldsStack, spill, spillStride, sc);
     const ClampCfg cc = clampCfg<SSS>(rp);
     TraceCounters cntExtend{0u, 0u}, cntAny{0u, 0u}, cntClosest{0u, 0u};
     uint32_t raysExtend = 0u, raysAny = 0u, raysClosest = 0u, early = 0u;
@@ -2243,13 +2216,9 @@ __global__ void __launch_bounds__(kTraceBlock) k_tail_run(RenderParams rp, Scene
             }
         }
     }
+    addTraceCounters<COUNT>(pool.counters, raysAny, cntAny, raysExtend + raysClosest,
+                            TraceCounters{cntExtend.nodes + cntClosest.nodes, cntExtend.prims + cntClosest.prims});
     if (COUNT) {
-        addCounter(pool.counters, kCntExtendRays, raysExtend + raysClosest);
-        addCounter(pool.counters, kCntExtendNodes, cntExtend.nodes + cntClosest.nodes);
-        addCounter(pool.counters, kCntExtendPrims, cntExtend.prims + cntClosest.prims);
-        addCounter(pool.counters, kCntShadowRays, raysAny);
-        addCounter(pool.counters, kCntShadowNodes, cntAny.nodes);
-        addCounter(pool.counters, kCntShadowPrims, cntAny.prims);
         addCounter(pool.counters, kCntShadowEarlyExit, early);
         addCounter(pool.counters, kCntShadedHits, counts.shadedHit);
         addCounter(pool.counters, kCntTriangleHits, counts.triHit);
@@ -2322,11 +2291,7 @@ __global__ void __launch_bounds__(kTraceBlock) k_aovs(RenderParams rp, SceneView
                                                        uint32_t spillStride) {
     __shared__ uint32_t ldsStack[kLdsStackLevels * kTraceBlock];
     const uint32_t gtid = blockIdx.x * kTraceBlock + threadIdx.x;
-    LaneStack stack;
-    stack.lds = (LdsWord*)(ldsStack + threadIdx.x);
-    stack.spill = spill;
-    stack.spillStride = spillStride;
-    stack.limit = sc.stackLimit;
+    LaneStack stack = laneStack(ldsStack, spill, spillStride, sc);
     TraceCounters cnt{0u, 0u};
     const uint32_t pixels = rp.width * rp.height;
     for (uint32_t pixel = gtid; pixel < pixels; pixel += gridDim.x * kTraceBlock) {
@@ -2402,11 +2367,7 @@ __global__ void __launch_bounds__(kTraceBlock) k_trace_rays(SceneView sc, const 
                                                              uint32_t spillStride, uint64_t* counters) {
     __shared__ uint32_t ldsStack[kLdsStackLevels * kTraceBlock];
     const uint32_t gtid = blockIdx.x * kTraceBlock + threadIdx.x;
-    LaneStack stack;
-    stack.lds = (LdsWord*)(ldsStack + threadIdx.x);
-    stack.spill = spill;
-    stack.spillStride = spillStride;
-    stack.limit = sc.stackLimit;
+    LaneStack stack = laneStack(ldsStack, spill, spillStride, sc);
     TraceCounters cnt{0u, 0u};
     for (uint64_t i = gtid; i < n; i += static_cast<uint64_t>(gridDim.x) * kTraceBlock) {
         const float4 a = rays[i * 2u], b = rays[i * 2u + 1u];
@@ -2522,11 +2483,7 @@ __global__ void __launch_bounds__(kTraceBlock) k_debug_first_hit(RenderParams rp
                                                                  uint32_t spillStride) {
     __shared__ uint32_t ldsStack[kLdsStackLevels * kTraceBlock];
     const uint32_t gtid = blockIdx.x * kTraceBlock + threadIdx.x;
-    LaneStack stack;
-    stack.lds = (LdsWord*)(ldsStack + threadIdx.x);
-    stack.spill = spill;
-    stack.spillStride = spillStride;
-    stack.limit = sc.stackLimit;
+    LaneStack stack = laneStack(ldsStack, spill, spillStride, sc);
     TraceCounters cnt{0u, 0u};
     for (uint64_t i = gtid; i < n; i += static_cast<uint64_t>(gridDim.x) * kTraceBlock) {
         float* o = out + i * kFirstHitFloats;
@@ -2578,11 +2535,7 @@ __global__ void __launch_bounds__(kTraceBlock) k_debug_first_hit(RenderParams rp
 __global__ void __launch_bounds__(kTraceBlock) k_debug_surface(SceneView sc, const float* in, uint64_t n, float* out, uint32_t* spill, uint32_t spillStride) {
     __shared__ uint32_t ldsStack[kLdsStackLevels * kTraceBlock];
     const uint32_t gtid = blockIdx.x * kTraceBlock + threadIdx.x;
-    LaneStack stack;
-    stack.lds = (LdsWord*)(ldsStack + threadIdx.x);
-    stack.spill = spill;
-    stack.spillStride = spillStride;
-    stack.limit = sc.stackLimit;
+    LaneStack stack = laneStack(ldsStack, spill, spillStride, sc);
     TraceCounters cnt{0u, 0u};
     for (uint64_t i = gtid; i < n; i += static_cast<uint64_t>(gridDim.x) * kTraceBlock) {
         const float* r = in + i * 9u;
@@ -2646,11 +2599,7 @@ __global__ void __launch_bounds__(kTraceBlock) k_debug_rect_light_nee(RenderPara
                                                                       float4* head, uint32_t* rngOut, uint32_t* spill, uint32_t spillStride) {
     __shared__ uint32_t ldsStack[kLdsStackLevels * kTraceBlock];
     const uint32_t gtid = blockIdx.x * kTraceBlock + threadIdx.x;
-    LaneStack stack;
-    stack.lds = (LdsWord*)(ldsStack + threadIdx.x);
-    stack.spill = spill;
-    stack.spillStride = spillStride;
-    stack.limit = sc.stackLimit;
+    LaneStack stack = laneStack(ldsStack, spill, spillStride, sc);
     TraceCounters cnt{0u, 0u};
     const ClampCfg cc = clampCfg<SSS>(rp);
     ShadeCounts counts;
@@ -2673,9 +2622,7 @@ __global__ void __launch_bounds__(kTraceBlock) k_debug_rect_light_nee(RenderPara
                 if ((rp.mediaMode & PTR_METAL_FACE_NORMAL) && !sf.frontFace) nn = -nn;
             }
             nn = normalize(nn);
-            bool surfaceDelta = materialIsDelta(mat);
-            if (SSS && cc.metalPbr && type == 7u) surfaceDelta = mat.roughness01() <= 1.0e-3f;
-            if (type != 3u && !surfaceDelta) {
+            if (type != 3u && !surfaceIsDelta<SSS>(mat, type, cc)) {
                 queued = rectLightNee<false, SSS, kAllMaterials, ONE>(rp, sc, pool, static_cast<uint32_t>(i), mat, sf, of, nn, wo, ld3(thrIn + i * 3u), cc,
                                                                       0u, rng, counts);
             }
@@ -2717,11 +2664,43 @@ __global__ void k_debug_light_connection(RenderParams rp, SceneView sc, bool sss
 // =====================================================================================================
 static inline uint32_t ceilDiv(uint64_t a, uint32_t b) { return static_cast<uint32_t>((a + b - 1) / b); }
 
-// The host sizes the traversal grids in units of kTraceGridUnit threads; the kernels may be built with smaller blocks (PTR_TRACE_BLOCK in
-// bvh_layout.h): same number of resident threads, so the spill area and its stride are unchanged.
-static inline LaunchConfig perBlockSize(LaunchConfig cfg) {
+// Geometry of a traversal launch.  The host sizes the traversal grids in units of kTraceGridUnit threads; the kernels may be built with
+// smaller blocks (PTR_TRACE_BLOCK in bvh_layout.h): same number of resident threads, so the spill area and its stride are unchanged.
+struct TraceLaunch {
+    LaunchConfig cfg;   // traceGrid in blocks of kTraceBlock threads
+    uint32_t stride;    // of the spill area: the resident threads
+    uint32_t grid;      // blocks to launch
+};
+// the whole resident grid (the persistent kernels that walk a list)
+static inline TraceLaunch traceLaunch(LaunchConfig cfg) {
     cfg.traceGrid *= kTraceGridUnit / kTraceBlock;
-    return cfg;
+    return {cfg, cfg.traceGrid * kTraceBlock, cfg.traceGrid};
+}
+// ... or no more of it than n items need (grid-stride kernels)
+static inline TraceLaunch traceLaunch(const LaunchConfig& cfg, uint64_t n) {
+    TraceLaunch t = traceLaunch(cfg);
+    t.grid = std::min(t.grid, std::max(1u, ceilDiv(n, kTraceBlock)));
+    return t;
+}
+
+// One thread per item of a batch (the probes)
+template <typename Kernel, typename... Args>
+static void launchFlat(Kernel kernel, uint32_t block, uint64_t n, hipStream_t stream, const Args&... args) {
+    hipLaunchKernelGGL(kernel, dim3(std::max(1u, ceilDiv(n, block))), dim3(block), 0, stream, args...);
+}
+
+// Run-time bools as template arguments: withBools(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{})
+template <typename F>
+static void withBools(F&& f) {
+    f();
+}
+template <typename F, typename... Rest>
+static void withBools(F&& f, bool first, Rest... rest) {
+    if (first) {
+        withBools([&](auto... tags) { f(std::true_type{}, tags...); }, rest...);
+    } else {
+        withBools([&](auto... tags) { f(std::false_type{}, tags...); }, rest...);
+    }
 }
 
 void launchGenerate(const RenderParams& rp, const PathPool& pool, hipStream_t stream) {
@@ -2734,119 +2713,103 @@ int traversalNodeFormat(const SceneView& sc, bool count) {
     return sc.useQuantized ? 1 : 0;
 }
 
-void launchExtend(const SceneView& sc, const PathPool& pool, const LaunchConfig& cfgIn, uint32_t* aliveOut, bool count, hipStream_t stream) {
-    const LaunchConfig cfg = perBlockSize(cfgIn);
-    const uint32_t stride = cfg.traceGrid * kTraceBlock;
-    const uint32_t grid = std::min(cfg.traceGrid, ceilDiv(pool.slots, kTraceBlock));
-    // the live-slot count is a separate instantiation so the common launch carries no extra register
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kTraceBlock), 0, stream, sc, pool, cfg.spill, stride, cfg.workCounters, cfg.refillBelow,
-                           cfg.feederChunk, aliveOut);
-    };
-    // the node format is a compile-time choice of the persistent kernels (no dead float / quantised path in the step loop); the
-    // counting build keeps the run-time flag
+// The node format is a compile-time choice of the persistent kernels (no dead float / quantised path in the step loop); the counting
+// build keeps the run-time flag.  f(countTag, nodesTag)
+template <typename F>
+static void withNodeFormat(const SceneView& sc, bool count, F&& f) {
     const int format = traversalNodeFormat(sc, count);
-    if (format == 3) {
-        if (aliveOut) launch(k_extend<true, true, -1>); else launch(k_extend<true, false, -1>);
-    } else if (format == 2) {
-        if (aliveOut) launch(k_extend<false, true, 2>); else launch(k_extend<false, false, 2>);
-    } else if (format == 1) {
-        if (aliveOut) launch(k_extend<false, true, 1>); else launch(k_extend<false, false, 1>);
-    } else {
-        if (aliveOut) launch(k_extend<false, true, 0>); else launch(k_extend<false, false, 0>);
-    }
+    if (format == 3) f(std::true_type{}, std::integral_constant<int, -1>{});
+    else if (format == 2) f(std::false_type{}, std::integral_constant<int, 2>{});
+    else if (format == 1) f(std::false_type{}, std::integral_constant<int, 1>{});
+    else f(std::false_type{}, std::integral_constant<int, 0>{});
 }
 
+void launchExtend(const SceneView& sc, const PathPool& pool, const LaunchConfig& cfgIn, uint32_t* aliveOut, bool count, hipStream_t stream) {
+    const TraceLaunch t = traceLaunch(cfgIn, pool.slots);
+    withNodeFormat(sc, count, [&](auto countTag, auto nodesTag) {
+        // the live-slot count is a separate instantiation so the common launch carries no extra register
+        withBools([&](auto aliveTag) {
+            hipLaunchKernelGGL((k_extend<decltype(countTag)::value, decltype(aliveTag)::value, decltype(nodesTag)::value>), dim3(t.grid), dim3(kTraceBlock),
+                               0, stream, sc, pool, t.cfg.spill, t.stride, t.cfg.workCounters, t.cfg.refillBelow, t.cfg.feederChunk, aliveOut);
+        }, aliveOut != nullptr);
+    });
+}
 
-// The k_shade instantiation a render of this scene launches: the smallest compiled set (materials + features) that covers it, or
-// kAllMaterials.  The Metal-semantics instantiations (SSS, TEX) and the counting ones are compiled for every material.
+// The instantiation of the k_shade family (k_shade, k_tail_run, the light probes) a render of this scene and these settings runs.  The
+// only place that reads kMetalInstantiationBits: a probe then cannot test another instantiation than the render launches.
 // The Metal-only models that run in the SSS instantiations.
 constexpr uint32_t kMetalInstantiationBits = PTR_METAL_SSS | PTR_METAL_PBR | PTR_METAL_CLAMPS | PTR_METAL_ENV_LOD;
-
-uint32_t shadeKernelSet(const RenderParams& rp, const SceneView& sc, bool count) {
-    const bool sss = (rp.mediaMode & kMetalInstantiationBits) != 0u;
-    if (sss || count || sc.materialTypes == 0u) return kAllMaterials;
+struct ShadeVariant {
+    bool sss;       // the instantiation that carries those Metal-only models
+    bool tex;       // the instantiation with the texture lookups and the ray cone
+    uint32_t set;   // the smallest compiled set (materials + features) that covers the scene, or kAllMaterials.  The Metal-semantics
+                    // instantiations (SSS, TEX) and the counting ones are compiled for every material.
+};
+static ShadeVariant shadeVariant(const RenderParams& rp, const SceneView& sc, bool count) {
+    ShadeVariant v;
+    v.sss = (rp.mediaMode & kMetalInstantiationBits) != 0u;
+    v.tex = v.sss && sc.textureCount > 0u;
+    v.set = kAllMaterials;
+    if (v.sss || count || sc.materialTypes == 0u) return v;
     // (an environment map and the Metal media / face-normal rules are features of the set like a material type is)
     const uint32_t needs = sc.materialTypes | ((sc.envWidth > 0u || sc.envSampling) ? kFeatureEnvironment : 0u) |
                            ((rp.mediaMode & (PTR_METAL_MEDIA | PTR_METAL_FACE_NORMAL)) ? kFeatureMedia : 0u);
     for (uint32_t set : {kDiffuseMaterials, kBasicMaterials, kMetalMaterials, kCarPaintMaterials, kPbrMaterials}) {
-        if ((needs & ~set) == 0u) return set;
+        if ((needs & ~set) == 0u) {
+            v.set = set;
+            break;
+        }
     }
-    return kAllMaterials;
+    return v;
 }
+
+uint32_t shadeKernelSet(const RenderParams& rp, const SceneView& sc, bool count) { return shadeVariant(rp, sc, count).set; }
 
 void launchShade(const RenderParams& rp, const SceneView& sc, const PathPool& pool, const ShadeResets& resets, const EnvLodView& env, bool count,
                  hipStream_t stream) {
-    const bool sss = (rp.mediaMode & kMetalInstantiationBits) != 0u;   // the instantiation that carries those Metal-only models
+    const ShadeVariant v = shadeVariant(rp, sc, count);
     const bool listed = pool.busyIn != nullptr;   // the grid still covers every slot: waves beyond the list leave at once
-    const bool tex = sss && sc.textureCount > 0u;   // the instantiation with the texture lookups and the ray cone
     const uint32_t grid = ceilDiv(pool.slots, kShadeBlock);
     auto launch = [&](auto kernel) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(kShadeBlock), 0, stream, rp, sc, pool, resets, env); };
-    const uint32_t set = shadeKernelSet(rp, sc, count);
-    auto pick = [&](auto countTag, auto listedTag) {
+    withBools([&](auto countTag, auto listedTag) {
         constexpr bool C = decltype(countTag)::value, L = decltype(listedTag)::value;
-        if (tex) launch(k_shade<C, true, true, L>);
-        else if (sss) launch(k_shade<C, true, false, L>);
+        if (v.tex) launch(k_shade<C, true, true, L>);
+        else if (v.sss) launch(k_shade<C, true, false, L>);
         else if (C) launch(k_shade<C, false, false, L>);
-        else if (set == kDiffuseMaterials) launch(k_shade<false, false, false, L, kDiffuseMaterials>);
-        else if (set == kBasicMaterials) launch(k_shade<false, false, false, L, kBasicMaterials>);
-        else if (set == kMetalMaterials) launch(k_shade<false, false, false, L, kMetalMaterials>);
-        else if (set == kCarPaintMaterials) launch(k_shade<false, false, false, L, kCarPaintMaterials>);
-        else if (set == kPbrMaterials) launch(k_shade<false, false, false, L, kPbrMaterials>);
+        else if (v.set == kDiffuseMaterials) launch(k_shade<false, false, false, L, kDiffuseMaterials>);
+        else if (v.set == kBasicMaterials) launch(k_shade<false, false, false, L, kBasicMaterials>);
+        else if (v.set == kMetalMaterials) launch(k_shade<false, false, false, L, kMetalMaterials>);
+        else if (v.set == kCarPaintMaterials) launch(k_shade<false, false, false, L, kCarPaintMaterials>);
+        else if (v.set == kPbrMaterials) launch(k_shade<false, false, false, L, kPbrMaterials>);
         else launch(k_shade<C, false, false, L>);
-    };
-    if (count) {
-        if (listed) pick(std::true_type{}, std::true_type{}); else pick(std::true_type{}, std::false_type{});
-    } else {
-        if (listed) pick(std::false_type{}, std::true_type{}); else pick(std::false_type{}, std::false_type{});
-    }
+    }, count, listed);
 }
 
 void launchConnect(const RenderParams& rp, const SceneView& sc, const PathPool& pool, const LaunchConfig& cfgIn, bool count, hipStream_t stream) {
-    const LaunchConfig cfg = perBlockSize(cfgIn);
-    const uint32_t stride = cfg.traceGrid * kTraceBlock;
-    {
-        auto launch = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3(cfg.traceGrid), dim3(kTraceBlock), 0, stream, rp, sc, pool, cfg.spill, stride, cfg.workCounters + 1,
-                               cfg.refillBelow, cfg.feederChunk);
-        };
-        const int format = traversalNodeFormat(sc, count);
-        if (format == 3) {
-            launch(k_connect<true, -1>);
-        } else if (format == 2) {
-            launch(k_connect<false, 2>);
-        } else if (format == 1) {
-            launch(k_connect<false, 1>);
-        } else {
-            launch(k_connect<false, 0>);
-        }
-    }
+    const TraceLaunch t = traceLaunch(cfgIn);
+    withNodeFormat(sc, count, [&](auto countTag, auto nodesTag) {
+        hipLaunchKernelGGL((k_connect<decltype(countTag)::value, decltype(nodesTag)::value>), dim3(t.grid), dim3(kTraceBlock), 0, stream, rp, sc, pool,
+                           t.cfg.spill, t.stride, t.cfg.workCounters + 1, t.cfg.refillBelow, t.cfg.feederChunk);
+    });
     if (rp.enableMnee && rp.enableMneeSecondary) {
-        if (count) {
-            hipLaunchKernelGGL(k_connect_chain<true>, dim3(cfg.traceGrid), dim3(kTraceBlock), 0, stream, rp, sc, pool, cfg.spill, stride);
-        } else {
-            hipLaunchKernelGGL(k_connect_chain<false>, dim3(cfg.traceGrid), dim3(kTraceBlock), 0, stream, rp, sc, pool, cfg.spill, stride);
-        }
+        withBools([&](auto countTag) {
+            hipLaunchKernelGGL(k_connect_chain<decltype(countTag)::value>, dim3(t.grid), dim3(kTraceBlock), 0, stream, rp, sc, pool, t.cfg.spill, t.stride);
+        }, count);
     }
 }
 
 void launchTail(const RenderParams& rp, const SceneView& sc, const PathPool& pool, const EnvLodView& env, const LaunchConfig& cfgIn, uint32_t* dList,
                 uint32_t* dListCount, uint32_t* dListHead, bool count, hipStream_t stream) {
-    const LaunchConfig cfg = perBlockSize(cfgIn);
+    const TraceLaunch t = traceLaunch(cfgIn);
     // dListCount and dListHead are zero on entry (the caller clears them on the same stream)
-    const uint32_t collectGrid = std::max(1u, std::min(cfg.traceGrid, ceilDiv(pool.slots, 256u * 16u)));
+    const uint32_t collectGrid = std::max(1u, std::min(t.grid, ceilDiv(pool.slots, 256u * 16u)));
     hipLaunchKernelGGL(k_tail_collect, dim3(collectGrid), dim3(256), 0, stream, pool, dList, dListCount);
-    const uint32_t stride = cfg.traceGrid * kTraceBlock;
-    const bool sss = (rp.mediaMode & kMetalInstantiationBits) != 0u;
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(cfg.traceGrid), dim3(kTraceBlock), 0, stream, rp, sc, pool, dList, dListCount, dListHead, cfg.spill, stride, env);
-    };
-    const bool tex = sss && sc.textureCount > 0u;
-    if (count) {
-        if (tex) launch(k_tail_run<true, true, true>); else if (sss) launch(k_tail_run<true, true, false>); else launch(k_tail_run<true, false, false>);
-    } else {
-        if (tex) launch(k_tail_run<false, true, true>); else if (sss) launch(k_tail_run<false, true, false>); else launch(k_tail_run<false, false, false>);
-    }
+    const ShadeVariant v = shadeVariant(rp, sc, count);
+    withBools([&](auto countTag, auto sssTag, auto texTag) {
+        constexpr bool C = decltype(countTag)::value, S = decltype(sssTag)::value, T = decltype(texTag)::value;
+        hipLaunchKernelGGL((k_tail_run<C, S, S && T>), dim3(t.grid), dim3(kTraceBlock), 0, stream, rp, sc, pool, dList, dListCount, dListHead,
+                           t.cfg.spill, t.stride, env);   // (tex only with sss)
+    }, count, v.sss, v.tex);
 }
 
 void launchResolve(const RenderParams& rp, const PathPool& pool, uint32_t partCount, float* dOut, hipStream_t stream) {
@@ -2862,80 +2825,73 @@ void launchInterleaveBands(const float* dGathered, const uint64_t* dPartOffset, 
 
 void launchTraceRays(const SceneView& sc, const float4* dRays, uint64_t n, bool anyHit, PtrHit* dOut, const LaunchConfig& cfgIn,
                      uint64_t* dCounters, hipStream_t stream) {
-    const LaunchConfig cfg = perBlockSize(cfgIn);
-    const uint32_t stride = cfg.traceGrid * kTraceBlock;
-    const uint32_t grid = std::min(cfg.traceGrid, std::max(1u, ceilDiv(n, kTraceBlock)));
-    if (anyHit) {
-        hipLaunchKernelGGL(k_trace_rays<true>, dim3(grid), dim3(kTraceBlock), 0, stream, sc, dRays, n, dOut, cfg.spill, stride, dCounters);
-    } else {
-        hipLaunchKernelGGL(k_trace_rays<false>, dim3(grid), dim3(kTraceBlock), 0, stream, sc, dRays, n, dOut, cfg.spill, stride, dCounters);
-    }
+    const TraceLaunch t = traceLaunch(cfgIn, n);
+    withBools([&](auto anyTag) {
+        hipLaunchKernelGGL(k_trace_rays<decltype(anyTag)::value>, dim3(t.grid), dim3(kTraceBlock), 0, stream, sc, dRays, n, dOut, t.cfg.spill, t.stride,
+                           dCounters);
+    }, anyHit);
 }
 
 void launchAovs(const RenderParams& rp, const SceneView& sc, uint32_t sample, float4* dAlbedo, float4* dNormal, const LaunchConfig& cfgIn,
                 hipStream_t stream) {
-    const LaunchConfig cfg = perBlockSize(cfgIn);
-    const uint32_t pixels = rp.width * rp.height;
-    const uint32_t stride = cfg.traceGrid * kTraceBlock;
-    const uint32_t grid = std::min(cfg.traceGrid, std::max(1u, ceilDiv(pixels, kTraceBlock)));
-    hipLaunchKernelGGL(k_aovs, dim3(grid), dim3(kTraceBlock), 0, stream, rp, sc, sample, dAlbedo, dNormal, cfg.spill, stride);
+    const TraceLaunch t = traceLaunch(cfgIn, rp.width * rp.height);
+    hipLaunchKernelGGL(k_aovs, dim3(t.grid), dim3(kTraceBlock), 0, stream, rp, sc, sample, dAlbedo, dNormal, t.cfg.spill, t.stride);
 }
 
+// ---- tests only: the probes ----
 void launchDebugEvalBsdf(const float4* dMaterial, const RenderParams& rp, const float* dIn, uint64_t n, float* dOut, hipStream_t stream) {
-    hipLaunchKernelGGL(k_debug_eval, dim3(std::max(1u, ceilDiv(n, 128))), dim3(128), 0, stream, dMaterial, rp, dIn, n, dOut);
+    launchFlat(k_debug_eval, 128, n, stream, dMaterial, rp, dIn, n, dOut);
 }
 
 void launchDebugSampleBsdf(const float4* dMaterial, const RenderParams& rp, const float* dIn, const uint32_t* dFront, const uint32_t* dRng,
                            uint64_t n, float* dOut, uint32_t* dRngOut, hipStream_t stream) {
-    hipLaunchKernelGGL(k_debug_sample, dim3(std::max(1u, ceilDiv(n, 128))), dim3(128), 0, stream, dMaterial, rp, dIn, dFront, dRng, n, dOut, dRngOut);
+    launchFlat(k_debug_sample, 128, n, stream, dMaterial, rp, dIn, dFront, dRng, n, dOut, dRngOut);
 }
 
 void launchDebugSampleLobes(const float4* dMaterial, const RenderParams& rp, const float* dIn, const uint32_t* dFront, const uint32_t* dRng,
                             uint64_t n, float* dOut, float* dSample, uint32_t* dRngOut, hipStream_t stream) {
-    hipLaunchKernelGGL(k_debug_sample_lobes, dim3(std::max(1u, ceilDiv(n, 128))), dim3(128), 0, stream, dMaterial, rp, dIn, dFront, dRng, n, dOut, dSample,
-                       dRngOut);
+    launchFlat(k_debug_sample_lobes, 128, n, stream, dMaterial, rp, dIn, dFront, dRng, n, dOut, dSample, dRngOut);
 }
 
 void launchDebugEnvLookup(const RenderParams& rp, const SceneView& sc, const EnvLodView& env, const float4* dIn, uint64_t n, float4* dOut,
                           hipStream_t stream) {
-    hipLaunchKernelGGL(k_debug_env_lookup, dim3(std::max(1u, ceilDiv(n, 128))), dim3(128), 0, stream, rp, sc, env, dIn, n, dOut);
+    launchFlat(k_debug_env_lookup, 128, n, stream, rp, sc, env, dIn, n, dOut);
 }
 
 void launchDebugTexSample(const SceneView& sc, uint32_t texture, const float* dIn, uint64_t n, float4* dOut, hipStream_t stream) {
-    hipLaunchKernelGGL(k_debug_tex_sample, dim3(std::max(1u, ceilDiv(n, 128))), dim3(128), 0, stream, sc, texture, dIn, n, dOut);
-}
-
-void launchDebugHitRecords(const SceneView& sc, const float4* dRays, const float2* dHits, uint64_t n, uint32_t triCount, uint32_t sphereCount,
-                           PtrHit* dOut, hipStream_t stream) {
-    hipLaunchKernelGGL(k_debug_hit_records, dim3(std::max(1u, ceilDiv(n, 256))), dim3(256), 0, stream, sc, dRays, dHits, n, triCount,
-                       sphereCount, dOut);
-}
-
-void launchDebugSurfaceHits(const SceneView& sc, const float* dIn, uint64_t n, float* dOut, const LaunchConfig& cfgIn, hipStream_t stream) {
-    const LaunchConfig cfg = perBlockSize(cfgIn);
-    const uint32_t stride = cfg.traceGrid * kTraceBlock;
-    const uint32_t grid = std::min(cfg.traceGrid, std::max(1u, ceilDiv(n, kTraceBlock)));
-    hipLaunchKernelGGL(k_debug_surface, dim3(grid), dim3(kTraceBlock), 0, stream, sc, dIn, n, dOut, cfg.spill, stride);
+    launchFlat(k_debug_tex_sample, 128, n, stream, sc, texture, dIn, n, dOut);
 }
 
 void launchDebugTexSampleGrad(const SceneView& sc, uint32_t texture, const float* dIn, uint64_t n, float4* dOut, hipStream_t stream) {
-    hipLaunchKernelGGL(k_debug_tex_sample_grad, dim3(std::max(1u, ceilDiv(n, 128))), dim3(128), 0, stream, sc, texture, dIn, n, dOut);
+    launchFlat(k_debug_tex_sample_grad, 128, n, stream, sc, texture, dIn, n, dOut);
 }
 
 void launchDebugFirstHit(const RenderParams& rp, const SceneView& sc, const uint32_t* dXys, uint64_t n, float* dOut, const LaunchConfig& cfgIn,
                          hipStream_t stream) {
-    const LaunchConfig cfg = perBlockSize(cfgIn);
-    const uint32_t stride = cfg.traceGrid * kTraceBlock;
-    const uint32_t grid = std::min(cfg.traceGrid, std::max(1u, ceilDiv(n, kTraceBlock)));
-    hipLaunchKernelGGL(k_debug_first_hit, dim3(grid), dim3(kTraceBlock), 0, stream, rp, sc, dXys, n, dOut, cfg.spill, stride);
+    const TraceLaunch t = traceLaunch(cfgIn, n);
+    hipLaunchKernelGGL(k_debug_first_hit, dim3(t.grid), dim3(kTraceBlock), 0, stream, rp, sc, dXys, n, dOut, t.cfg.spill, t.stride);
+}
+
+void launchDebugHitRecords(const SceneView& sc, const float4* dRays, const float2* dHits, uint64_t n, uint32_t triCount, uint32_t sphereCount,
+                           PtrHit* dOut, hipStream_t stream) {
+    launchFlat(k_debug_hit_records, 256, n, stream, sc, dRays, dHits, n, triCount, sphereCount, dOut);
+}
+
+void launchDebugSurfaceHits(const SceneView& sc, const float* dIn, uint64_t n, float* dOut, const LaunchConfig& cfgIn, hipStream_t stream) {
+    const TraceLaunch t = traceLaunch(cfgIn, n);
+    hipLaunchKernelGGL(k_debug_surface, dim3(t.grid), dim3(kTraceBlock), 0, stream, sc, dIn, n, dOut, t.cfg.spill, t.stride);
+}
+
+void launchDebugCameraRays(const RenderParams& rp, const uint32_t* dXys, uint64_t n, float* dOut, uint32_t* dRngOut, hipStream_t stream) {
+    launchFlat(k_debug_camera, 128, n, stream, rp, dXys, n, dOut, dRngOut);
 }
 
 void launchDebugEnvSample(const RenderParams& rp, const SceneView& sc, const float* dU, uint64_t n, float4* dOut, hipStream_t stream) {
-    hipLaunchKernelGGL(k_debug_env_sample, dim3(std::max(1u, ceilDiv(n, 128))), dim3(128), 0, stream, rp, sc, dU, n, dOut);
+    launchFlat(k_debug_env_sample, 128, n, stream, rp, sc, dU, n, dOut);
 }
 
 void launchDebugEnvEval(const RenderParams& rp, const SceneView& sc, const float* dDir, uint64_t n, float4* dOut, hipStream_t stream) {
-    hipLaunchKernelGGL(k_debug_env_eval, dim3(std::max(1u, ceilDiv(n, 128))), dim3(128), 0, stream, rp, sc, dDir, n, dOut);
+    launchFlat(k_debug_env_eval, 128, n, stream, rp, sc, dDir, n, dOut);
 }
 
 // the instantiation of rectLightNee that launchShade's k_shade runs for this scene and these settings: SSS by the Metal-only models, ONE
@@ -2943,28 +2899,15 @@ void launchDebugEnvEval(const RenderParams& rp, const SceneView& sc, const float
 void launchDebugRectLightNee(const RenderParams& rp, const SceneView& sc, const PathPool& pool, const float4* dMaterial, const float* dRays,
                              const float* dThr, const uint32_t* dRng, uint64_t n, float4* dHead, uint32_t* dRngOut, const LaunchConfig& cfgIn,
                              hipStream_t stream) {
-    const LaunchConfig cfg = perBlockSize(cfgIn);
-    const uint32_t stride = cfg.traceGrid * kTraceBlock;
-    const uint32_t grid = std::min(cfg.traceGrid, std::max(1u, ceilDiv(n, kTraceBlock)));
-    auto launch = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(kTraceBlock), 0, stream, rp, sc, pool, dMaterial, dRays, dThr, dRng, n, dHead, dRngOut, cfg.spill,
-                           stride);
-    };
-    const bool sss = (rp.mediaMode & kMetalInstantiationBits) != 0u;
-    if (sc.rectLightCount == 1u) {
-        if (sss) launch(k_debug_rect_light_nee<true, true>); else launch(k_debug_rect_light_nee<false, true>);
-    } else {
-        if (sss) launch(k_debug_rect_light_nee<true, false>); else launch(k_debug_rect_light_nee<false, false>);
-    }
+    const TraceLaunch t = traceLaunch(cfgIn, n);
+    withBools([&](auto oneTag, auto sssTag) {
+        hipLaunchKernelGGL((k_debug_rect_light_nee<decltype(sssTag)::value, decltype(oneTag)::value>), dim3(t.grid), dim3(kTraceBlock), 0, stream, rp, sc,
+                           pool, dMaterial, dRays, dThr, dRng, n, dHead, dRngOut, t.cfg.spill, t.stride);
+    }, sc.rectLightCount == 1u, shadeVariant(rp, sc, false).sss);
 }
 
 void launchDebugLightConnection(const RenderParams& rp, const SceneView& sc, const float* dIn, uint64_t n, float* dOut, hipStream_t stream) {
-    const bool sss = (rp.mediaMode & kMetalInstantiationBits) != 0u;
-    hipLaunchKernelGGL(k_debug_light_connection, dim3(std::max(1u, ceilDiv(n, 128))), dim3(128), 0, stream, rp, sc, sss, dIn, n, dOut);
-}
-
-void launchDebugCameraRays(const RenderParams& rp, const uint32_t* dXys, uint64_t n, float* dOut, uint32_t* dRngOut, hipStream_t stream) {
-    hipLaunchKernelGGL(k_debug_camera, dim3(std::max(1u, ceilDiv(n, 128))), dim3(128), 0, stream, rp, dXys, n, dOut, dRngOut);
+    launchFlat(k_debug_light_connection, 128, n, stream, rp, sc, shadeVariant(rp, sc, false).sss, dIn, n, dOut);
 }
 
 }  // namespace ptrk
