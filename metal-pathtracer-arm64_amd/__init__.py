@@ -1,4 +1,4 @@
-"""MI355X wavefront path tracer — Python host bindings over the C-ABI (include/ptr_abi.h).
+"""MI355X wavefront path tracer — Python host bindings over the C-ABI (include/ptr_abi.h, include/ptr_post.h).
 
 The package is only plumbing: it loads ``libptr_hip.so`` (hand-written HIP kernels + C++ host layer) with
 ctypes and mirrors the POD structs of the ABI.  There is no CPU fallback: every render entry point needs the
@@ -204,6 +204,27 @@ HIT_DTYPE = np.dtype(
      ("ng", "<f4", (3,)), ("pad", "<u4")]
 )
 
+class PtrDenoiseParams(C.Structure):
+    """include/ptr_post.h PtrDenoiseParams; PtrDenoiseParams.defaults() asks the library for its defaults."""
+    _fields_ = [
+        ("iterations", C.c_uint32),
+        ("sigmaLuminance", C.c_float),
+        ("sigmaNormal", C.c_float),
+        ("sigmaDepth", C.c_float),
+        ("flags", C.c_uint32),
+    ]
+
+    @classmethod
+    def defaults(cls, **overrides) -> "PtrDenoiseParams":
+        p = cls()
+        load_library().ptr_denoise_default_params(C.byref(p))
+        for k, v in overrides.items():
+            setattr(p, k, v)
+        return p
+
+
+PTR_DENOISE_DEMODULATE = 1   # PtrDenoiseParams.flags bit 0
+
 assert C.sizeof(PtrSphere) == 32 and C.sizeof(PtrRect) == 80 and C.sizeof(PtrMaterial) == 576
 assert C.sizeof(PtrHit) == HIT_DTYPE.itemsize == 40
 
@@ -278,6 +299,16 @@ _SIGNATURES = {
 DEBUG_SYMBOLS = tuple(name for name in _SIGNATURES if name.startswith("ptr_debug_"))
 ABI_SYMBOLS = tuple(name for name in _SIGNATURES if name not in DEBUG_SYMBOLS)
 
+# ... and of include/ptr_post.h (the denoiser), a table of its own: tests/test_post_host.py holds it against that header
+_denoise = C.POINTER(PtrDenoiseParams)
+_POST_SIGNATURES = {
+    "ptr_denoise_default_params": (None, [_denoise]),
+    "ptr_denoise": (_int, [_fp, _fp, _fp, _u32, _u32, _denoise, _int, _fp, C.POINTER(C.c_double)] + _err),
+    "ptr_denoise_device": (_int, [_vp, _vp, _vp, _u32, _u32, _denoise, _vp, _vp] + _err),
+    "ptr_denoise_timed": (_int, [_vp, _vp, _vp, _u32, _u32, _denoise, _vp, _u32, _u32, C.POINTER(C.c_double), _up] + _err),
+}
+POST_SYMBOLS = tuple(_POST_SIGNATURES)
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -294,7 +325,7 @@ def load_library() -> C.CDLL:
     if not os.path.exists(path):
         raise PtrError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` first")
     lib = C.CDLL(path)
-    for name, (restype, argtypes) in _SIGNATURES.items():
+    for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_POST_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -644,6 +675,52 @@ def write_exr_aovs(path: str, rgb: np.ndarray, albedo: np.ndarray, normal: np.nd
     h, w = rgb.shape[0], rgb.shape[1]
     err = _err_buf()
     _check(load_library().ptr_host_write_exr_aovs(os.fsencode(path), _fptr(rgb), _fptr(albedo), _fptr(normal), w, h, err, len(err)), err)
+
+
+# ----------------------------------------------------------------------------- post-processing (include/ptr_post.h)
+
+
+def denoise(rgb: np.ndarray, albedo: np.ndarray, normal: np.ndarray, params: Optional[PtrDenoiseParams] = None, device: int = 0,
+            return_ms: bool = False):
+    """The edge-avoiding a-trous wavelet filter of include/ptr_post.h on host arrays: rgb [H, W, 3] and the first-hit feature buffers of
+    DeviceScene.render_aovs ([H, W, 4] each) -> [H, W, 3] float32 (with return_ms: and the milliseconds its kernels took)."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    albedo = np.ascontiguousarray(albedo, dtype=np.float32)
+    normal = np.ascontiguousarray(normal, dtype=np.float32)
+    if rgb.ndim != 3 or rgb.shape[2] != 3 or albedo.shape != rgb.shape[:2] + (4,) or normal.shape != albedo.shape:
+        raise ValueError("denoise: rgb must be [H, W, 3], albedo and normal [H, W, 4]")
+    lib = load_library()
+    params = params if params is not None else PtrDenoiseParams.defaults()
+    out = np.empty_like(rgb)
+    ms = C.c_double(0.0)
+    err = _err_buf()
+    _check(lib.ptr_denoise(_fptr(rgb), _fptr(albedo), _fptr(normal), rgb.shape[1], rgb.shape[0], C.byref(params), device, _fptr(out),
+                           C.byref(ms), err, len(err)), err)
+    return (out, float(ms.value)) if return_ms else out
+
+
+def denoise_device(d_rgb: int, d_albedo: int, d_normal: int, width: int, height: int, params: Optional[PtrDenoiseParams] = None,
+                   d_out: Optional[int] = None, stream: int = 0) -> None:
+    """The same filter on device buffers given as raw pointers (a torch tensor's data_ptr()), asynchronous on `stream`; d_out defaults
+    to d_rgb (in place)."""
+    lib = load_library()
+    params = params if params is not None else PtrDenoiseParams.defaults()
+    err = _err_buf()
+    _check(lib.ptr_denoise_device(C.c_void_p(d_rgb), C.c_void_p(d_albedo), C.c_void_p(d_normal), width, height, C.byref(params),
+                                  C.c_void_p(d_rgb if d_out is None else d_out), C.c_void_p(stream), err, len(err)), err)
+
+
+def denoise_timed(d_rgb: int, d_albedo: int, d_normal: int, width: int, height: int, d_out: int, params: Optional[PtrDenoiseParams] = None,
+                  runs: int = 20, warmup: int = 5) -> Tuple[list, list]:
+    """ptr_denoise_timed: (mean ms of prepare, every a-trous pass and finish over `runs` runs, 1 where the LDS-tiled kernel ran)."""
+    lib = load_library()
+    params = params if params is not None else PtrDenoiseParams.defaults()
+    n = params.iterations + 2
+    ms, tiled = (C.c_double * n)(), (C.c_uint32 * n)()
+    err = _err_buf()
+    _check(lib.ptr_denoise_timed(C.c_void_p(d_rgb), C.c_void_p(d_albedo), C.c_void_p(d_normal), width, height, C.byref(params),
+                                 C.c_void_p(d_out), runs, warmup, ms, tiled, err, len(err)), err)
+    return [float(v) for v in ms], [int(v) for v in tiled]
 
 
 def assemble_bands(parts_out, width: int, height: int) -> np.ndarray:

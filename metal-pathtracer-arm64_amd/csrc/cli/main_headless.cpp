@@ -48,6 +48,8 @@ struct CliOptions {
     uint32_t metalSemantics = 0;
     uint32_t devices = 1;            // --devices: GPUs of this node the frame is spread over (0 = all visible)
     std::string aovExrPath;          // --aovExr: also write the first-hit feature layers
+    bool denoise = false;            // --denoise: filter the frame, guided by the first-hit feature buffers (include/ptr_post.h)
+    uint32_t denoiseIterations = 0;  // --denoiseIterations: a-trous passes (0 = the filter's default)
     uint32_t backendSemantics = 0;   // what --backend / --enableEmbree imply; an explicit --semantics overrides it
     bool semanticsSet = false;
     std::string formatString = "exr";
@@ -102,6 +104,9 @@ void printUsage(const char* exe) {
               << "  --format=<exr|pfm|ppm>        Output format (default exr)\n"
               << "  --rgbaExr[=0|1]               Write RGBA EXR with colorspace attribute (Embree-backend layout)\n"
               << "  --aovExr=<path>               Also write beauty + first-hit albedo / normal / depth layers (denoiser inputs) as one EXR\n"
+              << "  --denoise[=0|1]               Denoise the image (and the beauty layer of --aovExr) with the edge-avoiding a-trous\n"
+              << "                                wavelet filter guided by the first-hit albedo / normal / depth (default 0)\n"
+              << "  --denoiseIterations=<1..8>    A-trous passes of --denoise (default 5)\n"
               << "  --verbose                     Print progress\n"
               << "  --help                        Show this message\n";
 }
@@ -241,6 +246,14 @@ bool parseOptions(int argc, const char** argv, CliOptions& o, std::string& error
         } else if (arg == "--aovExr") {
             if (!need("--aovExr")) return false;
             o.aovExrPath = value;
+        } else if (arg == "--denoise") {
+            if (!boolArg("--denoise", o.denoise, nullptr)) return false;
+        } else if (arg == "--denoiseIterations") {
+            if (!intArg("--denoiseIterations", 1, o.denoiseIterations, nullptr)) return false;
+            if (o.denoiseIterations > PTR_DENOISE_MAX_ITERATIONS) {
+                error = "--denoiseIterations must be in [1,8]";
+                return false;
+            }
         } else if (arg == "--semantics") {
             if (!need("--semantics")) return false;
             if (value == "metal") {
@@ -372,6 +385,12 @@ int main(int argc, const char** argv) {
     auto hipRenderer = std::make_unique<ptr::HipHeadlessRenderer>();
     hipRenderer->setDeviceCount(static_cast<int>(options.devices));
     hipRenderer->setCaptureAovs(!options.aovExrPath.empty());
+    if (options.denoise) {
+        PtrDenoiseParams denoiseParams;
+        ptr_denoise_default_params(&denoiseParams);
+        if (options.denoiseIterations) denoiseParams.iterations = options.denoiseIterations;
+        hipRenderer->setDenoise(&denoiseParams);
+    }
     const ptr::HipHeadlessRenderer* const hip = hipRenderer.get();
     std::unique_ptr<ptr::IHeadlessRenderer> renderer = std::move(hipRenderer);
     ptr::HeadlessRenderOutput output;

@@ -1,6 +1,7 @@
 #include "headless.h"
 
 #include <algorithm>
+#include <cstdio>
 
 namespace ptr {
 
@@ -61,19 +62,21 @@ bool HipHeadlessRenderer::render(const HeadlessScene& scene, const HeadlessCamer
     m_stats = PtrRenderStats{};
     m_aovAlbedo.clear();
     m_aovNormal.clear();
+    m_denoiseMs = 0.0;
+    const bool captureAovs = m_captureAovs || m_denoise;   // the denoiser's guides are the feature buffers
     if (m_devices != 1) {
         // the frame in interleaved bands over several devices of the node, gathered on the first one
         if (ptr_render_multi(&desc, &ps, spp, m_devices, verbose ? 1 : 0, out.linearRGB.data(), &m_stats, err, sizeof(err)) != 0) {
             error = err[0] ? err : "HIP render failed";
             return false;
         }
-    } else if (!m_captureAovs) {
+    } else if (!captureAovs) {
         if (ptr_render(&desc, &ps, spp, verbose ? 1 : 0, out.linearRGB.data(), &m_stats, err, sizeof(err)) != 0) {
             error = err[0] ? err : "HIP render failed";
             return false;
         }
     }
-    if (m_captureAovs) {
+    if (captureAovs) {
         // one upload serves the frame (single device) and the first-hit feature buffers
         PtrDeviceScene* ds = nullptr;
         if (ptr_scene_upload(&desc, 0, &ds, err, sizeof(err)) != 0) {
@@ -97,6 +100,14 @@ bool HipHeadlessRenderer::render(const HeadlessScene& scene, const HeadlessCamer
             error = err[0] ? err : "HIP render failed";
             return false;
         }
+    }
+    if (m_denoise) {
+        if (ptr_denoise(out.linearRGB.data(), m_aovAlbedo.data(), m_aovNormal.data(), ps.width, ps.height, &m_denoiseParams, 0, out.linearRGB.data(),
+                        &m_denoiseMs, err, sizeof(err)) != 0) {
+            error = err[0] ? err : "HIP denoise failed";
+            return false;
+        }
+        if (verbose) std::fprintf(stderr, "denoise: %u a-trous passes, %.3f ms on device 0\n", m_denoiseParams.iterations, m_denoiseMs);
     }
     out.width = ps.width;
     out.height = ps.height;

@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "ptr_post.h"
 #include "render_settings.h"
 #include "scene_resources.h"
 
@@ -58,12 +59,22 @@ public:
     void setCaptureAovs(bool on) { m_captureAovs = on; }
     const std::vector<float>& aovAlbedo() const { return m_aovAlbedo; }
     const std::vector<float>& aovNormal() const { return m_aovNormal; }
+    // denoise the frame with the filter of include/ptr_post.h, guided by those feature buffers, on device 0 (after the gather of a
+    // multi-device frame); null = off.  Its time goes to the verbose output, not into totalSeconds: --denoise of the CLI
+    void setDenoise(const PtrDenoiseParams* params) {
+        m_denoise = params != nullptr;
+        if (params) m_denoiseParams = *params;
+    }
+    double lastDenoiseMs() const { return m_denoiseMs; }
 
 private:
     PtrRenderStats m_stats{};
     int m_devices = 1;
     bool m_captureAovs = false;
     std::vector<float> m_aovAlbedo, m_aovNormal;
+    bool m_denoise = false;
+    PtrDenoiseParams m_denoiseParams{};
+    double m_denoiseMs = 0.0;
 };
 
 // RenderSettings -> POD settings of the C-ABI.

@@ -18,6 +18,7 @@ struct Knobs {
     int refillBelow = 0;           // PTR_REFILL_BELOW      traversing lanes below which a persistent wave refills, 1..64 (0: default 40)
     uint32_t buildThreads = 0;     // PTR_BUILD_THREADS     BVH builder threads (0: all cores)
     bool noOversize = false;       // PTR_NO_OVERSIZE       keep every triangle in the tree
+    int denoiseTiled = -1;         // PTR_DENOISE_TILED     0: every denoiser kernel reads its taps through the caches; 1: the LDS-tiled kernel wherever there is one (-1: default, csrc/host/denoise.cpp)
     // PTR_VERBOSE: comma-separated topics printed to stderr - build (BVH / upload timings), polls (live slots per host poll),
     // launches (when each kernel ran), steps (lane-utilisation counters of a counting render)
     bool verboseBuild = false, verbosePolls = false, verboseLaunches = false, verboseSteps = false;
