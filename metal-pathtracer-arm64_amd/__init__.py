@@ -1,4 +1,4 @@
-"""MI355X wavefront path tracer — Python host bindings over the C-ABI (include/ptr_abi.h, include/ptr_post.h).
+"""MI355X wavefront path tracer — Python host bindings over the C-ABI (include/ptr_abi.h, include/ptr_post.h, include/ptr_stats.h).
 
 The package is only plumbing: it loads ``libptr_hip.so`` (hand-written HIP kernels + C++ host layer) with
 ctypes and mirrors the POD structs of the ABI.  There is no CPU fallback: every render entry point needs the
@@ -309,6 +309,16 @@ _POST_SIGNATURES = {
 }
 POST_SYMBOLS = tuple(_POST_SIGNATURES)
 
+# ... and of include/ptr_stats.h (per-pixel sample covariance), again a table of its own: tests/test_stats_host.py holds it against that header
+_STATS_SIGNATURES = {
+    "ptr_render_bands_cov_device": (_int, [_vp, _settings, _u32, _u32, _u32, _vp, _vp, _vp, _int, _stats] + _err),
+    "ptr_render_bands_cov": (_int, [_vp, _settings, _u32, _u32, _u32, _fp, _fp, _int, _stats] + _err),
+    "ptr_denoise_cov": (_int, [_fp, _fp, _fp, _fp, _u32, _u32, _denoise, _int, _fp, C.POINTER(C.c_double)] + _err),
+    "ptr_denoise_cov_device": (_int, [_vp, _vp, _vp, _vp, _u32, _u32, _denoise, _vp, _vp] + _err),
+    "ptr_stats_debug_samples": (_int, [_vp, _settings, _u32, _fp] + _err),
+}
+STATS_SYMBOLS = tuple(_STATS_SIGNATURES)
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -325,7 +335,7 @@ def load_library() -> C.CDLL:
     if not os.path.exists(path):
         raise PtrError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` first")
     lib = C.CDLL(path)
-    for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_POST_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_POST_SIGNATURES.items()) + list(_STATS_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -507,6 +517,42 @@ class DeviceScene:
                                            err, len(err)), err)
         return stats if want_stats else None
 
+    def render_cov(self, settings: PtrSettings, spp: int, part: int = 0, parts: int = 1, count: bool = False
+                   ) -> Tuple[np.ndarray, np.ndarray, PtrRenderStats]:
+        """render() plus the covariance of every pixel's mean (include/ptr_stats.h; spp >= 2).  Returns ([bands*BAND_ROWS, W, 3],
+        [bands*BAND_ROWS, W, 6] {rr, gg, bb, rg, rb, gb}, stats)."""
+        lib = load_library()
+        bands = band_count(settings.height, part, parts)
+        out = np.zeros((bands * BAND_ROWS, settings.width, 3), dtype=np.float32)
+        cov = np.zeros((bands * BAND_ROWS, settings.width, 6), dtype=np.float32)
+        stats = PtrRenderStats()
+        err = _err_buf()
+        _check(lib.ptr_render_bands_cov(self._h, C.byref(settings), spp, part, parts, _fptr(out), _fptr(cov), int(count),
+                                        C.byref(stats), err, len(err)), err)
+        return out, cov, stats
+
+    def render_image_cov(self, settings: PtrSettings, spp: int) -> Tuple[np.ndarray, np.ndarray, PtrRenderStats]:
+        """([H, W, 3] image - the bits of render_image - , [H, W, 6] covariance of the pixel means, stats)."""
+        out, cov, stats = self.render_cov(settings, spp)
+        return out[: settings.height], cov[: settings.height], stats
+
+    def render_cov_device(self, settings: PtrSettings, spp: int, d_out_ptr: int, d_cov_ptr: int, stream: int = 0, part: int = 0,
+                          parts: int = 1, count: bool = False, want_stats: bool = True) -> Optional[PtrRenderStats]:
+        """render_device() with a second caller-owned DEVICE buffer for the covariance (bands * BAND_ROWS * W * 6 floats)."""
+        stats = PtrRenderStats()
+        err = _err_buf()
+        _check(load_library().ptr_render_bands_cov_device(self._h, C.byref(settings), spp, part, parts, C.c_void_p(d_out_ptr),
+                                                          C.c_void_p(d_cov_ptr), C.c_void_p(stream), int(count),
+                                                          C.byref(stats) if want_stats else None, err, len(err)), err)
+        return stats if want_stats else None
+
+    def debug_samples(self, settings: PtrSettings, spp: int) -> np.ndarray:
+        """ptr_stats_debug_samples (tests): the frame's per-sample accumulators, [spp, H, W, 3] in sample order."""
+        out = np.zeros((spp, settings.height, settings.width, 3), dtype=np.float32)
+        err = _err_buf()
+        _check(load_library().ptr_stats_debug_samples(self._h, C.byref(settings), spp, _fptr(out), err, len(err)), err)
+        return out
+
     def render_aovs(self, settings: PtrSettings, sample_index: int = 0) -> Tuple[np.ndarray, np.ndarray]:
         """First-hit feature buffers: ([H, W, 4] albedo rgb | hit flag, [H, W, 4] encoded normal | distance)."""
         albedo = np.zeros((settings.height, settings.width, 4), dtype=np.float32)
@@ -681,9 +727,10 @@ def write_exr_aovs(path: str, rgb: np.ndarray, albedo: np.ndarray, normal: np.nd
 
 
 def denoise(rgb: np.ndarray, albedo: np.ndarray, normal: np.ndarray, params: Optional[PtrDenoiseParams] = None, device: int = 0,
-            return_ms: bool = False):
+            return_ms: bool = False, cov: Optional[np.ndarray] = None):
     """The edge-avoiding a-trous wavelet filter of include/ptr_post.h on host arrays: rgb [H, W, 3] and the first-hit feature buffers of
-    DeviceScene.render_aovs ([H, W, 4] each) -> [H, W, 3] float32 (with return_ms: and the milliseconds its kernels took)."""
+    DeviceScene.render_aovs ([H, W, 4] each) -> [H, W, 3] float32 (with return_ms: and the milliseconds its kernels took).
+    cov ([H, W, 6], DeviceScene.render_image_cov): the filter takes its variance from it (include/ptr_stats.h ptr_denoise_cov)."""
     rgb = np.ascontiguousarray(rgb, dtype=np.float32)
     albedo = np.ascontiguousarray(albedo, dtype=np.float32)
     normal = np.ascontiguousarray(normal, dtype=np.float32)
@@ -694,20 +741,32 @@ def denoise(rgb: np.ndarray, albedo: np.ndarray, normal: np.ndarray, params: Opt
     out = np.empty_like(rgb)
     ms = C.c_double(0.0)
     err = _err_buf()
-    _check(lib.ptr_denoise(_fptr(rgb), _fptr(albedo), _fptr(normal), rgb.shape[1], rgb.shape[0], C.byref(params), device, _fptr(out),
-                           C.byref(ms), err, len(err)), err)
+    if cov is not None:
+        cov = np.ascontiguousarray(cov, dtype=np.float32)
+        if cov.shape != rgb.shape[:2] + (6,):
+            raise ValueError("denoise: cov must be [H, W, 6]")
+        _check(lib.ptr_denoise_cov(_fptr(rgb), _fptr(albedo), _fptr(normal), _fptr(cov), rgb.shape[1], rgb.shape[0], C.byref(params), device,
+                                   _fptr(out), C.byref(ms), err, len(err)), err)
+    else:
+        _check(lib.ptr_denoise(_fptr(rgb), _fptr(albedo), _fptr(normal), rgb.shape[1], rgb.shape[0], C.byref(params), device, _fptr(out),
+                               C.byref(ms), err, len(err)), err)
     return (out, float(ms.value)) if return_ms else out
 
 
 def denoise_device(d_rgb: int, d_albedo: int, d_normal: int, width: int, height: int, params: Optional[PtrDenoiseParams] = None,
-                   d_out: Optional[int] = None, stream: int = 0) -> None:
+                   d_out: Optional[int] = None, stream: int = 0, d_cov: int = 0) -> None:
     """The same filter on device buffers given as raw pointers (a torch tensor's data_ptr()), asynchronous on `stream`; d_out defaults
-    to d_rgb (in place)."""
+    to d_rgb (in place).  d_cov (width * height * 6 floats): the variance comes from it (ptr_denoise_cov_device)."""
     lib = load_library()
     params = params if params is not None else PtrDenoiseParams.defaults()
     err = _err_buf()
-    _check(lib.ptr_denoise_device(C.c_void_p(d_rgb), C.c_void_p(d_albedo), C.c_void_p(d_normal), width, height, C.byref(params),
-                                  C.c_void_p(d_rgb if d_out is None else d_out), C.c_void_p(stream), err, len(err)), err)
+    out = C.c_void_p(d_rgb if d_out is None else d_out)
+    if d_cov:
+        _check(lib.ptr_denoise_cov_device(C.c_void_p(d_rgb), C.c_void_p(d_albedo), C.c_void_p(d_normal), C.c_void_p(d_cov), width, height,
+                                          C.byref(params), out, C.c_void_p(stream), err, len(err)), err)
+    else:
+        _check(lib.ptr_denoise_device(C.c_void_p(d_rgb), C.c_void_p(d_albedo), C.c_void_p(d_normal), width, height, C.byref(params), out,
+                                      C.c_void_p(stream), err, len(err)), err)
 
 
 def denoise_timed(d_rgb: int, d_albedo: int, d_normal: int, width: int, height: int, d_out: int, params: Optional[PtrDenoiseParams] = None,
@@ -724,10 +783,11 @@ def denoise_timed(d_rgb: int, d_albedo: int, d_normal: int, width: int, height: 
 
 
 def assemble_bands(parts_out, width: int, height: int) -> np.ndarray:
-    """Interleave per-partition band buffers ([bands*BAND_ROWS, W, 3] each, band b of part p = image band p + b*P)."""
+    """Interleave per-partition band buffers ([bands*BAND_ROWS, W, C] each - C = 3 for images, 6 for covariances - , band b of part p =
+    image band p + b*P)."""
     parts = len(parts_out)
     R = BAND_ROWS
-    img = np.zeros((((height + R - 1) // R) * R, width, 3), dtype=np.float32)
+    img = np.zeros((((height + R - 1) // R) * R, width, parts_out[0].shape[2] if parts else 3), dtype=np.float32)
     for p, buf in enumerate(parts_out):
         nb = buf.shape[0] // R
         for b in range(nb):

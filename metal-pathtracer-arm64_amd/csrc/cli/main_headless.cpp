@@ -50,6 +50,7 @@ struct CliOptions {
     std::string aovExrPath;          // --aovExr: also write the first-hit feature layers
     bool denoise = false;            // --denoise: filter the frame, guided by the first-hit feature buffers (include/ptr_post.h)
     uint32_t denoiseIterations = 0;  // --denoiseIterations: a-trous passes (0 = the filter's default)
+    bool denoiseSampleVariance = false;   // --denoiseVariance=sample: the filter's variance from the per-pixel sample covariance (include/ptr_stats.h)
     uint32_t backendSemantics = 0;   // what --backend / --enableEmbree imply; an explicit --semantics overrides it
     bool semanticsSet = false;
     std::string formatString = "exr";
@@ -107,6 +108,9 @@ void printUsage(const char* exe) {
               << "  --denoise[=0|1]               Denoise the image (and the beauty layer of --aovExr) with the edge-avoiding a-trous\n"
               << "                                wavelet filter guided by the first-hit albedo / normal / depth (default 0)\n"
               << "  --denoiseIterations=<1..8>    A-trous passes of --denoise (default 5)\n"
+              << "  --denoiseVariance=<spatial|sample>  Variance of --denoise's luminance edge-stop: spatial = estimated from a 7x7 window of\n"
+              << "                                the image (default); sample = measured per pixel from the frame's own samples (needs\n"
+              << "                                --denoise, --sppTotal >= 2 and --devices=1)\n"
               << "  --verbose                     Print progress\n"
               << "  --help                        Show this message\n";
 }
@@ -254,6 +258,13 @@ bool parseOptions(int argc, const char** argv, CliOptions& o, std::string& error
                 error = "--denoiseIterations must be in [1,8]";
                 return false;
             }
+        } else if (arg == "--denoiseVariance") {
+            if (!need("--denoiseVariance")) return false;
+            if (value != "spatial" && value != "sample") {
+                error = "Invalid value for --denoiseVariance (expected spatial or sample)";
+                return false;
+            }
+            o.denoiseSampleVariance = value == "sample";
         } else if (arg == "--semantics") {
             if (!need("--semantics")) return false;
             if (value == "metal") {
@@ -301,6 +312,14 @@ bool parseOptions(int argc, const char** argv, CliOptions& o, std::string& error
         error = "--scene is required";
         return false;
     }
+    if (o.denoiseSampleVariance && !o.denoise) {
+        error = "--denoiseVariance=sample requires --denoise";
+        return false;
+    }
+    if (o.denoiseSampleVariance && o.sppTotal < 2u) {
+        error = "--denoiseVariance=sample requires --sppTotal >= 2";
+        return false;
+    }
     if (!ptr::ParseImageFileFormat(o.formatString, o.format)) {
         error = "Unknown format: " + o.formatString;
         return false;
@@ -326,6 +345,11 @@ int main(int argc, const char** argv) {
     if (!parseOptions(argc, argv, options, error)) {
         if (!error.empty()) std::cerr << "Error: " << error << "\n\n";
         printUsage(argv[0]);
+        return 1;
+    }
+
+    if (options.denoiseSampleVariance && options.devices != 1u) {
+        std::cerr << "Error: --denoiseVariance=sample renders on one device; it cannot be combined with --devices=" << options.devices << std::endl;
         return 1;
     }
 
@@ -390,6 +414,7 @@ int main(int argc, const char** argv) {
         ptr_denoise_default_params(&denoiseParams);
         if (options.denoiseIterations) denoiseParams.iterations = options.denoiseIterations;
         hipRenderer->setDenoise(&denoiseParams);
+        hipRenderer->setDenoiseVariance(options.denoiseSampleVariance);
     }
     const ptr::HipHeadlessRenderer* const hip = hipRenderer.get();
     std::unique_ptr<ptr::IHeadlessRenderer> renderer = std::move(hipRenderer);

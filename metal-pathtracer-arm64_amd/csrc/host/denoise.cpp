@@ -11,6 +11,7 @@
 #include "device_scene.h"
 #include "knobs.h"
 #include "ptr_post.h"
+#include "ptr_stats.h"
 
 using namespace ptrhost;
 
@@ -63,8 +64,9 @@ struct KernelTimes {   // ptr_denoise_timed: one event before every kernel and o
 };
 
 // The whole filter on `stream` of the current device.  Caller holds g_scratchMutex.
+// dCov (nullable; include/ptr_stats.h): prepare takes the variance from it instead of the 7x7 spatial estimate.
 void enqueueDenoise(Scratch& s, const void* dRgb, const void* dAlbedo, const void* dNormal, uint32_t width, uint32_t height,
-                    const PtrDenoiseParams& p, void* dOut, hipStream_t stream, KernelTimes* times) {
+                    const PtrDenoiseParams& p, void* dOut, hipStream_t stream, KernelTimes* times, const void* dCov = nullptr) {
     const size_t pixels = static_cast<size_t>(width) * height;
     if (pixels > s.guide.count) {   // growing frees the old buffers, which waits for the device: nothing can still be using them
         for (auto& c : s.colour) c.ensure(pixels);
@@ -84,8 +86,13 @@ void enqueueDenoise(Scratch& s, const void* dRgb, const void* dAlbedo, const voi
     };
     const auto* rgb = static_cast<const float*>(dRgb);
     const auto* albedo = static_cast<const float4*>(dAlbedo);
-    mark(prepareTiled(knob));
-    ptrk::launchDenoisePrepare(rgb, albedo, static_cast<const float4*>(dNormal), width, height, p, buf, prepareTiled(knob), stream);
+    if (dCov) {
+        mark(false);
+        ptrk::launchDenoisePrepareCov(rgb, albedo, static_cast<const float4*>(dNormal), static_cast<const float*>(dCov), width, height, p, buf, stream);
+    } else {
+        mark(prepareTiled(knob));
+        ptrk::launchDenoisePrepare(rgb, albedo, static_cast<const float4*>(dNormal), width, height, p, buf, prepareTiled(knob), stream);
+    }
     uint32_t src = 0;
     for (uint32_t i = 0; i < p.iterations; ++i, src ^= 1u) {
         mark(passTiled(1u << i, knob));
@@ -149,6 +156,19 @@ int ptr_denoise_device(const void* d_rgb, const void* d_albedo, const void* d_no
     });
 }
 
+int ptr_denoise_cov_device(const void* d_rgb, const void* d_albedo, const void* d_normal, const void* d_cov, uint32_t width, uint32_t height,
+                           const PtrDenoiseParams* params, void* d_out_rgb, void* stream, char* err, size_t err_cap) {
+    std::string bad = badArgument("ptr_denoise_cov_device", d_rgb, d_albedo, d_normal, width, height, params, d_out_rgb);
+    if (bad.empty() && !d_cov) bad = "ptr_denoise_cov_device: null argument";
+    if (!bad.empty()) {
+        setErr(err, err_cap, bad);
+        return 1;
+    }
+    return onDeviceOf(d_rgb, err, err_cap, [&](Scratch& s) {
+        enqueueDenoise(s, d_rgb, d_albedo, d_normal, width, height, *params, d_out_rgb, static_cast<hipStream_t>(stream), nullptr, d_cov);
+    });
+}
+
 int ptr_denoise_timed(const void* d_rgb, const void* d_albedo, const void* d_normal, uint32_t width, uint32_t height,
                       const PtrDenoiseParams* params, void* d_out_rgb, uint32_t runs, uint32_t warmup, double* out_ms, uint32_t* out_tiled,
                       char* err, size_t err_cap) {
@@ -190,17 +210,17 @@ int ptr_denoise_timed(const void* d_rgb, const void* d_albedo, const void* d_nor
     });
 }
 
-int ptr_denoise(const float* rgb, const float* albedo_rgba, const float* normal_rgba, uint32_t width, uint32_t height,
-                const PtrDenoiseParams* params, int device, float* out_rgb, double* kernel_ms, char* err, size_t err_cap) {
-    const std::string bad = badArgument("ptr_denoise", rgb, albedo_rgba, normal_rgba, width, height, params, out_rgb);
-    if (!bad.empty()) {
-        setErr(err, err_cap, bad);
-        return 1;
-    }
+}  // extern "C"
+
+namespace {
+
+// ptr_denoise / ptr_denoise_cov (cov null / given): host buffers through the device and back.
+int denoiseHost(const char* who, const float* rgb, const float* albedo_rgba, const float* normal_rgba, const float* cov, uint32_t width,
+                uint32_t height, const PtrDenoiseParams* params, int device, float* out_rgb, double* kernel_ms, char* err, size_t err_cap) {
     try {
         const int available = ptr_device_count();
         if (device < 0 || device >= available) {
-            setErr(err, err_cap, "ptr_denoise: no such HIP device (the HIP path has no CPU fallback)");
+            setErr(err, err_cap, std::string(who) + ": no such HIP device (the HIP path has no CPU fallback)");
             return 2;
         }
         HIP_CHECK(hipSetDevice(device));
@@ -210,6 +230,8 @@ int ptr_denoise(const float* rgb, const float* albedo_rgba, const float* normal_
         dRgb.upload(rgb, pixels * 3u);
         dAlbedo.upload(reinterpret_cast<const float4*>(albedo_rgba), pixels);
         dNormal.upload(reinterpret_cast<const float4*>(normal_rgba), pixels);
+        DeviceBuffer<float> dCov;
+        if (cov) dCov.upload(cov, pixels * 6u);
         hipEvent_t begin = nullptr, end = nullptr;
         struct Release {
             hipEvent_t &a, &b;
@@ -223,7 +245,8 @@ int ptr_denoise(const float* rgb, const float* albedo_rgba, const float* normal_
         {
             std::lock_guard<std::mutex> lock(g_scratchMutex);
             HIP_CHECK(hipEventRecord(begin, nullptr));
-            enqueueDenoise(scratchByDevice()[device], dRgb.ptr, dAlbedo.ptr, dNormal.ptr, width, height, *params, dRgb.ptr, nullptr, nullptr);
+            enqueueDenoise(scratchByDevice()[device], dRgb.ptr, dAlbedo.ptr, dNormal.ptr, width, height, *params, dRgb.ptr, nullptr, nullptr,
+                           cov ? dCov.ptr : nullptr);
             HIP_CHECK(hipEventRecord(end, nullptr));
         }
         HIP_CHECK(hipStreamSynchronize(nullptr));
@@ -236,6 +259,31 @@ int ptr_denoise(const float* rgb, const float* albedo_rgba, const float* normal_
         return 0;
     }
     PTR_CATCH_ALL(err, err_cap)
+}
+
+}  // namespace
+
+extern "C" {
+
+int ptr_denoise(const float* rgb, const float* albedo_rgba, const float* normal_rgba, uint32_t width, uint32_t height,
+                const PtrDenoiseParams* params, int device, float* out_rgb, double* kernel_ms, char* err, size_t err_cap) {
+    const std::string bad = badArgument("ptr_denoise", rgb, albedo_rgba, normal_rgba, width, height, params, out_rgb);
+    if (!bad.empty()) {
+        setErr(err, err_cap, bad);
+        return 1;
+    }
+    return denoiseHost("ptr_denoise", rgb, albedo_rgba, normal_rgba, nullptr, width, height, params, device, out_rgb, kernel_ms, err, err_cap);
+}
+
+int ptr_denoise_cov(const float* rgb, const float* albedo_rgba, const float* normal_rgba, const float* cov, uint32_t width, uint32_t height,
+                    const PtrDenoiseParams* params, int device, float* out_rgb, double* kernel_ms, char* err, size_t err_cap) {
+    std::string bad = badArgument("ptr_denoise_cov", rgb, albedo_rgba, normal_rgba, width, height, params, out_rgb);
+    if (bad.empty() && !cov) bad = "ptr_denoise_cov: null argument";
+    if (!bad.empty()) {
+        setErr(err, err_cap, bad);
+        return 1;
+    }
+    return denoiseHost("ptr_denoise_cov", rgb, albedo_rgba, normal_rgba, cov, width, height, params, device, out_rgb, kernel_ms, err, err_cap);
 }
 
 }  // extern "C"

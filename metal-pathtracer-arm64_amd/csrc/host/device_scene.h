@@ -142,6 +142,8 @@ struct PtrDeviceScene {
     DeviceBuffer<uint32_t> itemHeads, zeros;
     DeviceBuffer<uint64_t> counters;
     DeviceBuffer<float> outBands;
+    DeviceBuffer<float> covBands;    // ptr_render_bands_cov: the covariance beside outBands (include/ptr_stats.h)
+    DeviceBuffer<float4> covMean;    // k_resolve_cov: per local pixel, the running mean between the passes of a frame
     DeviceBuffer<float4> rayBatch;
     DeviceBuffer<PtrHit> hitBatch;
     uint32_t* pinnedAlive = nullptr;
@@ -167,8 +169,11 @@ void appendTextureWithMips(const PtrTexture& t, std::vector<float>& texels, std:
 double ensureEnvMips(PtrDeviceScene& ds);
 void fillRenderParams(const PtrSettings& s, uint32_t spp, ptrk::RenderParams& rp);
 ptrk::LaunchConfig coldLaunchConfig(const PtrDeviceScene& ds);
+// dCov (nullable): the covariance of the pixel mean beside the image (include/ptr_stats.h), six floats per pixel in dOut's band layout
 void renderBands(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, uint32_t part, uint32_t parts, float* dOut, hipStream_t stream,
-                 int mode, PtrRenderStats* stats);
+                 int mode, PtrRenderStats* stats, float* dCov = nullptr);
+// passes renderBands splits a frame of `spp` samples per pixel into (the per-sample accumulators of a pass have to fit in memory)
+uint32_t framePasses(const PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp);
 
 // The frame of a C-ABI entry point that works on a device: "<who>: null argument" unless argsOk (a call that needs `scene` says so
 // there), the device selected (the scene's; device 0 for a call without a scene, which fails when there is none), the body, the error

@@ -64,6 +64,13 @@ bool HipHeadlessRenderer::render(const HeadlessScene& scene, const HeadlessCamer
     m_aovNormal.clear();
     m_denoiseMs = 0.0;
     const bool captureAovs = m_captureAovs || m_denoise;   // the denoiser's guides are the feature buffers
+    const bool sampleVariance = m_denoise && m_denoiseFromSamples;
+    if (sampleVariance && (m_devices != 1 || spp < 2u)) {
+        error = m_devices != 1 ? "the denoiser's sample variance needs a frame rendered on one device (--devices=1)"
+                               : "the denoiser's sample variance needs at least 2 samples per pixel";
+        return false;
+    }
+    std::vector<float> cov;
     if (m_devices != 1) {
         // the frame in interleaved bands over several devices of the node, gathered on the first one
         if (ptr_render_multi(&desc, &ps, spp, m_devices, verbose ? 1 : 0, out.linearRGB.data(), &m_stats, err, sizeof(err)) != 0) {
@@ -87,7 +94,12 @@ bool HipHeadlessRenderer::render(const HeadlessScene& scene, const HeadlessCamer
         if (m_devices == 1) {
             const uint32_t bands = ptr_part_band_count(ps.height, 0, 1);
             std::vector<float> banded(static_cast<size_t>(bands) * PTR_BAND_ROWS * ps.width * 3u);
-            ok = ptr_render_bands(ds, &ps, spp, 0, 1, banded.data(), 0, &m_stats, err, sizeof(err)) == 0;
+            if (sampleVariance) {
+                cov.resize(banded.size() * 2u);   // one partition: its bands are the image's rows in order, then padding
+                ok = ptr_render_bands_cov(ds, &ps, spp, 0, 1, banded.data(), cov.data(), 0, &m_stats, err, sizeof(err)) == 0;
+            } else {
+                ok = ptr_render_bands(ds, &ps, spp, 0, 1, banded.data(), 0, &m_stats, err, sizeof(err)) == 0;
+            }
             if (ok) std::copy(banded.begin(), banded.begin() + static_cast<std::ptrdiff_t>(out.linearRGB.size()), out.linearRGB.begin());
         }
         if (ok) {
@@ -102,12 +114,18 @@ bool HipHeadlessRenderer::render(const HeadlessScene& scene, const HeadlessCamer
         }
     }
     if (m_denoise) {
-        if (ptr_denoise(out.linearRGB.data(), m_aovAlbedo.data(), m_aovNormal.data(), ps.width, ps.height, &m_denoiseParams, 0, out.linearRGB.data(),
-                        &m_denoiseMs, err, sizeof(err)) != 0) {
+        const int rc = sampleVariance ? ptr_denoise_cov(out.linearRGB.data(), m_aovAlbedo.data(), m_aovNormal.data(), cov.data(), ps.width, ps.height,
+                                                        &m_denoiseParams, 0, out.linearRGB.data(), &m_denoiseMs, err, sizeof(err))
+                                      : ptr_denoise(out.linearRGB.data(), m_aovAlbedo.data(), m_aovNormal.data(), ps.width, ps.height, &m_denoiseParams,
+                                                    0, out.linearRGB.data(), &m_denoiseMs, err, sizeof(err));
+        if (rc != 0) {
             error = err[0] ? err : "HIP denoise failed";
             return false;
         }
-        if (verbose) std::fprintf(stderr, "denoise: %u a-trous passes, %.3f ms on device 0\n", m_denoiseParams.iterations, m_denoiseMs);
+        if (verbose) {
+            std::fprintf(stderr, "denoise: %u a-trous passes, %.3f ms on device 0\n", m_denoiseParams.iterations, m_denoiseMs);
+            std::fprintf(stderr, "denoise: variance from %s\n", sampleVariance ? "the per-pixel sample covariance" : "the 7x7 spatial estimate");
+        }
     }
     out.width = ps.width;
     out.height = ps.height;

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "ptr_post.h"
+#include "ptr_stats.h"
 #include "render_settings.h"
 #include "scene_resources.h"
 
@@ -66,6 +67,9 @@ public:
         if (params) m_denoiseParams = *params;
     }
     double lastDenoiseMs() const { return m_denoiseMs; }
+    // where the denoiser's variance comes from: false = the filter's own 7x7 spatial estimate (include/ptr_post.h), true = the frame's
+    // per-pixel sample covariance (include/ptr_stats.h; needs sppTotal >= 2 and one device): --denoiseVariance of the CLI
+    void setDenoiseVariance(bool fromSamples) { m_denoiseFromSamples = fromSamples; }
 
 private:
     PtrRenderStats m_stats{};
@@ -75,6 +79,7 @@ private:
     bool m_denoise = false;
     PtrDenoiseParams m_denoiseParams{};
     double m_denoiseMs = 0.0;
+    bool m_denoiseFromSamples = false;
 };
 
 // RenderSettings -> POD settings of the C-ABI.

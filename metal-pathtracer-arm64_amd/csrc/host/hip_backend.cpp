@@ -800,7 +800,7 @@ PollResult poll(PtrDeviceScene& ds, std::vector<PoolGroup>& groups, const Render
     return r;
 }
 
-enum class SpanKind : int { Extend = 0, Shade = 1, Connect = 2, Tail = 3 };   // the `kind` of a [launch] line
+enum class SpanKind : int { Extend = 0, Shade = 1, Connect = 2, Tail = 3, ResolveCov = 4 };   // the `kind` of a [launch] line
 
 // Start and end events around the launches of a timed pass.
 struct LaunchTimer {
@@ -857,6 +857,7 @@ void passStats(const PtrDeviceScene& ds, const RenderParams& rp, const std::vect
             case SpanKind::Shade: stats.shadeKernelMs += ms; break;
             case SpanKind::Connect: stats.shadowKernelMs += ms; break;
             case SpanKind::Tail: stats.tailKernelMs += ms; break;
+            case SpanKind::ResolveCov: break;   // (PTR_VERBOSE=launches shows it: tools/cov_cost.py)
         }
     }
     if (!count) return;
@@ -907,8 +908,9 @@ void passStats(const PtrDeviceScene& ds, const RenderParams& rp, const std::vect
 // One pass over `spp` samples per pixel starting at sample `sampleBase` of a frame of `sppTotal`; passFlags bit 0 = first pass of
 // the frame (output and counters start from zero), bit 1 = last pass (the running sum in dOut is divided by sppTotal).
 // (renderBands has checked the size and the partition, and selected the device.)
+// dCov (nullable; include/ptr_stats.h): six floats per pixel in the band layout of dOut, the covariance of the pixel mean.
 void renderPass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, uint32_t sampleBase, uint32_t sppTotal, uint32_t passFlags,
-                uint32_t part, uint32_t parts, float* dOut, hipStream_t stream, int mode, PtrRenderStats* stats) {
+                uint32_t part, uint32_t parts, float* dOut, float* dCov, hipStream_t stream, int mode, PtrRenderStats* stats) {
     const bool count = (mode & 1) != 0;         // counting instantiation of the kernels
     const bool soloGroup = (mode & 2) != 0;     // one pool group: kernels run alone, for clean per-kernel timings
 
@@ -932,6 +934,7 @@ void renderPass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, u
     const uint32_t bandCount = ptr_part_band_count(settings.height, part, parts);
     const size_t outFloats = static_cast<size_t>(bandCount) * PTR_BAND_ROWS * settings.width * 3u;
     if (passFlags & 1u) HIP_CHECK(hipMemsetAsync(dOut, 0, outFloats * sizeof(float), stream));
+    if (dCov && (passFlags & 1u)) HIP_CHECK(hipMemsetAsync(dCov, 0, outFloats * 2u * sizeof(float), stream));
     if (localPixels == 0) {
         HIP_CHECK(hipStreamSynchronize(stream));
         return;
@@ -1038,6 +1041,10 @@ void renderPass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, u
                      [&] { launchTail(rp, ds.view, pool, env, groups[0].cfg, ds.tailList.ptr, ds.tailWords.ptr, ds.tailWords.ptr + 1, count, stream); });
     }
     launchResolve(rp, pool, parts, dOut, stream);
+    if (dCov) {
+        ds.covMean.ensure(localPixels);
+        timer.launch(SpanKind::ResolveCov, stream, [&] { launchResolveCov(rp, pool, parts, ds.covMean.ptr, dCov, stream); });
+    }
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(stream));
     const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
@@ -1052,25 +1059,26 @@ namespace ptrhost {
 // more samples than that is rendered in several passes of equal sample counts whose per-pixel sums add up in the output
 // buffer.  (Folding C samples into one work item instead keeps one pass but lengthens the end-of-frame drain: 4096 spp of
 // config 2 as items of 9 samples ran at 1116 Msamples/s.)  The sample streams do not depend on the split.
+uint32_t framePasses(const PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp) {
+    const uint64_t budget = itemBudgetBytes(ds);
+    uint64_t maxItems = std::min<uint64_t>(budget / sizeof(float4), 0xFFFFFFF0ull);
+    if (const uint64_t forced = ptr::readKnobs().maxItems) maxItems = forced;   // test knob
+    // counted on the whole frame, not on this partition: every partition then splits the samples the same way and the image
+    // stays bit-identical whatever the number of partitions
+    const uint64_t pixels = static_cast<uint64_t>(settings.width) * settings.height;
+    const uint64_t perPixel = std::max<uint64_t>(1u, maxItems / std::max<uint64_t>(pixels, 1u));   // samples per pixel that fit in one pass
+    return static_cast<uint32_t>((std::max(1u, spp) + perPixel - 1u) / perPixel);
+}
+
 void renderBands(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, uint32_t part, uint32_t parts, float* dOut,
-                 hipStream_t stream, int mode, PtrRenderStats* stats) {
+                 hipStream_t stream, int mode, PtrRenderStats* stats, float* dCov) {
     if (settings.width == 0 || settings.height == 0) throw HipError{"render size must be non-zero"};
     if (parts == 0 || part >= parts) throw HipError{"bad partition"};
     HIP_CHECK(hipSetDevice(ds.device));
     spp = std::max(1u, spp);
-    uint32_t passes = 1u;
-    {
-        const uint64_t budget = itemBudgetBytes(ds);
-        uint64_t maxItems = std::min<uint64_t>(budget / sizeof(float4), 0xFFFFFFF0ull);
-        if (const uint64_t forced = ptr::readKnobs().maxItems) maxItems = forced;   // test knob
-        // counted on the whole frame, not on this partition: every partition then splits the samples the same way and the image
-        // stays bit-identical whatever the number of partitions
-        const uint64_t pixels = static_cast<uint64_t>(settings.width) * settings.height;
-        const uint64_t perPixel = std::max<uint64_t>(1u, maxItems / std::max<uint64_t>(pixels, 1u));   // samples per pixel that fit in one pass
-        passes = static_cast<uint32_t>((spp + perPixel - 1u) / perPixel);
-    }
+    const uint32_t passes = framePasses(ds, settings, spp);
     if (passes <= 1u) {
-        renderPass(ds, settings, spp, 0u, spp, 3u, part, parts, dOut, stream, mode, stats);
+        renderPass(ds, settings, spp, 0u, spp, 3u, part, parts, dOut, dCov, stream, mode, stats);
         return;
     }
     const uint32_t perPass = (spp + passes - 1u) / passes;
@@ -1080,7 +1088,7 @@ void renderBands(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, 
         const uint32_t n = std::min(perPass, spp - done);
         const uint32_t flags = (p == 0u ? 1u : 0u) | (done + n >= spp ? 2u : 0u);
         PtrRenderStats one{};
-        renderPass(ds, settings, n, done, spp, flags, part, parts, dOut, stream, mode, stats ? &one : nullptr);
+        renderPass(ds, settings, n, done, spp, flags, part, parts, dOut, dCov, stream, mode, stats ? &one : nullptr);
         if (stats) {   // counters are cumulative on the device: the last pass reports the totals; times, launches and samples add up
             addLaunchStats(one, sum);
             one.totalSeconds += sum.totalSeconds;

@@ -23,6 +23,10 @@ constexpr uint32_t kDenoiseMaxTiledStep = 4u;
 // same order: the two variants give the same bits.
 void launchDenoisePrepare(const float* dRgb, const float4* dAlbedo, const float4* dNormal, uint32_t width, uint32_t height,
                           const PtrDenoiseParams& p, const DenoiseBuffers& buf, bool tiled, hipStream_t stream);
+// prepare with the variance taken from dCov (width*height*6 floats; include/ptr_stats.h) instead of the 7x7 spatial estimate.  Simple
+// variant only (nine taps).
+void launchDenoisePrepareCov(const float* dRgb, const float4* dAlbedo, const float4* dNormal, const float* dCov, uint32_t width, uint32_t height,
+                             const PtrDenoiseParams& p, const DenoiseBuffers& buf, hipStream_t stream);
 // pass at step `step` (a power of two) from buf.colour[src] to buf.colour[src ^ 1]; tiled needs step <= kDenoiseMaxTiledStep
 void launchDenoiseAtrous(uint32_t width, uint32_t height, uint32_t step, const PtrDenoiseParams& p, const DenoiseBuffers& buf, uint32_t src,
                          bool tiled, hipStream_t stream);

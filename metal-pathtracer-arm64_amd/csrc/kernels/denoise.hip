@@ -133,6 +133,47 @@ __device__ inline void preparePixel(int x, int y, int width, int height, const D
     buf.slope[i] = slope;
 }
 
+// ---- prepare on a measured variance (include/ptr_stats.h): v_p from the covariance of the pixel mean instead of the 7x7 window
+
+// v_q of a hit pixel q: the variance of its demodulated luminance, sum over c, d of (g_c g_d) C_cd with g = k / albedo divisor
+__device__ inline float luminanceVariance(const float* cov, size_t q, const float3& a) {
+    const float g[3] = {0.2126f / a.x, 0.7152f / a.y, 0.0722f / a.z};
+    const float* c = cov + q * 6u;   // rr, gg, bb, rg, rb, gb
+    const float C[3][3] = {{c[0], c[3], c[4]}, {c[3], c[1], c[5]}, {c[4], c[5], c[2]}};
+    float v = 0.0f;
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) v += (g[i] * g[j]) * C[i][j];
+    }
+    return (__builtin_isfinite(v) && v > 0.0f) ? v : 0.0f;
+}
+
+// Prepare for the pixel (x, y) with v_p = the 3x3 prefilter of v_q.  Guide and depth slope as preparePixel writes them.
+template <typename Fetch>
+__device__ inline void preparePixelCov(int x, int y, int width, int height, const DenoiseConsts& k, const DenoiseBuffers& buf, const float4* albedo,
+                                       const float* cov, Fetch fetch) {
+    const Pixel p = fetch(x, y);
+    const size_t i = static_cast<size_t>(y) * width + x;
+    buf.guide[i] = p.guide;
+    if (!(p.guide.w > 0.0f)) return;   // a miss pixel: its colour and slope are never read
+    auto depthAt = [&](int qx, int qy) { return (qx < 0 || qy < 0 || qx >= width || qy >= height) ? -1.0f : fetch(qx, qy).guide.w; };
+    const float z = p.guide.w;
+    const float slope = fmaxf(axisSlope(z, depthAt(x - 1, y), depthAt(x + 1, y)), axisSlope(z, depthAt(x, y - 1), depthAt(x, y + 1)));
+    float sumW = 0.0f, sumWv = 0.0f;
+    for (int dy = -1; dy <= 1; ++dy) {
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int qx = x + dx, qy = y + dy;
+            if (qx < 0 || qy < 0 || qx >= width || qy >= height) continue;
+            if (!(fetch(qx, qy).guide.w > 0.0f)) continue;
+            const size_t q = static_cast<size_t>(qy) * width + qx;
+            const float w = (dx == 0 ? 0.5f : 0.25f) * (dy == 0 ? 0.5f : 0.25f);   // 1/4, 1/8, 1/16
+            sumW += w;
+            sumWv += w * luminanceVariance(cov, q, albedoDivisor(albedo[q], k.demodulate));
+        }
+    }
+    buf.colour[0][i] = make_float4(p.colour.x, p.colour.y, p.colour.z, sumWv / sumW);
+    buf.slope[i] = slope;
+}
+
 __device__ inline float b3(int d) { return d == 0 ? 0.375f : ((d == 1 || d == -1) ? 0.25f : 0.0625f); }
 
 // One a-trous pass at step s for the pixel (x, y).  fetch(qx, qy, colour, guide) reads an in-image pixel's colour | variance and guide.
@@ -182,6 +223,14 @@ __global__ void __launch_bounds__(kTile* kTile) k_denoise_prepare(const float* r
     if (x >= width || y >= height) return;
     preparePixel(x, y, width, height, k, buf,
                  [&](int qx, int qy) { return decodePixel(rgb, albedo, normal, static_cast<size_t>(qy) * width + qx, k.demodulate); });
+}
+
+__global__ void __launch_bounds__(kTile* kTile) k_denoise_prepare_cov(const float* rgb, const float4* albedo, const float4* normal, const float* cov,
+                                                                       int width, int height, DenoiseConsts k, DenoiseBuffers buf) {
+    const int x = blockIdx.x * kTile + threadIdx.x, y = blockIdx.y * kTile + threadIdx.y;
+    if (x >= width || y >= height) return;
+    preparePixelCov(x, y, width, height, k, buf, albedo, cov,
+                    [&](int qx, int qy) { return decodePixel(rgb, albedo, normal, static_cast<size_t>(qy) * width + qx, k.demodulate); });
 }
 
 __global__ void __launch_bounds__(kTile* kTile) k_denoise_atrous(int width, int height, int step, DenoiseConsts k, const float4* src,
@@ -280,6 +329,12 @@ void launchDenoisePrepare(const float* dRgb, const float4* dAlbedo, const float4
     } else {
         hipLaunchKernelGGL(k_denoise_prepare, grid, block, 0, stream, dRgb, dAlbedo, dNormal, w, h, constsOf(p), buf);
     }
+}
+
+void launchDenoisePrepareCov(const float* dRgb, const float4* dAlbedo, const float4* dNormal, const float* dCov, uint32_t width, uint32_t height,
+                             const PtrDenoiseParams& p, const DenoiseBuffers& buf, hipStream_t stream) {
+    hipLaunchKernelGGL(k_denoise_prepare_cov, gridOf(width, height), dim3(kTile, kTile), 0, stream, dRgb, dAlbedo, dNormal, dCov,
+                       static_cast<int>(width), static_cast<int>(height), constsOf(p), buf);
 }
 
 void launchDenoiseAtrous(uint32_t width, uint32_t height, uint32_t step, const PtrDenoiseParams& p, const DenoiseBuffers& buf, uint32_t src,

@@ -43,6 +43,10 @@ void launchTail(const RenderParams& rp, const SceneView& sc, const PathPool& poo
 // Adds outstanding light connections, reduces the slots of each pixel in fixed order and writes
 // out[((localBand*PTR_BAND_ROWS + row) * width + x) * 3 + c] = sum / spp.
 void launchResolve(const RenderParams& rp, const PathPool& pool, uint32_t partCount, float* dOut, hipStream_t stream);
+// After launchResolve of the same pass (defined in stats.hip; include/ptr_stats.h): the covariance of every pixel's mean, six floats per
+// pixel in the band layout of dOut.  dMean: localPixels float4, the running mean between the passes of a frame; dCov holds the
+// unnormalised sums until the last pass.
+void launchResolveCov(const RenderParams& rp, const PathPool& pool, uint32_t partCount, float4* dMean, float* dCov, hipStream_t stream);
 
 // Multi-device gather: writes image[y][x][c] from the partitions' band buffers laid end to end (dPartOffset: float offsets).
 void launchInterleaveBands(const float* dGathered, const uint64_t* dPartOffset, uint32_t parts, uint32_t width, uint32_t height, float* dImage,
