@@ -225,6 +225,42 @@ class PtrDenoiseParams(C.Structure):
 
 PTR_DENOISE_DEMODULATE = 1   # PtrDenoiseParams.flags bit 0
 
+
+class PtrAdaptiveParams(C.Structure):
+    """include/ptr_adaptive.h PtrAdaptiveParams; PtrAdaptiveParams.defaults(max_spp) asks the library for its defaults."""
+    _fields_ = [
+        ("minSpp", C.c_uint32),
+        ("maxSpp", C.c_uint32),
+        ("stepSpp", C.c_uint32),
+        ("threshold", C.c_float),
+    ]
+
+    @classmethod
+    def defaults(cls, max_spp: int, **overrides) -> "PtrAdaptiveParams":
+        p = cls()
+        load_library().ptr_adaptive_default_params(C.byref(p), max_spp)
+        for k, v in overrides.items():
+            setattr(p, k, v)
+        return p
+
+
+ADAPTIVE_INFO_ROUNDS = 32   # PTR_ADAPTIVE_INFO_ROUNDS
+
+
+class PtrAdaptiveInfo(C.Structure):
+    """include/ptr_adaptive.h PtrAdaptiveInfo."""
+    _fields_ = [
+        ("rounds", C.c_uint32),
+        ("pixelsAtMax", C.c_uint32),
+        ("totalSamples", C.c_uint64),
+        ("activeAfter", C.c_uint32 * ADAPTIVE_INFO_ROUNDS),
+    ]
+
+    def active_counts(self) -> list:
+        """the length of the active list after each round (the first 32)"""
+        return [int(v) for v in self.activeAfter[: min(self.rounds, ADAPTIVE_INFO_ROUNDS)]]
+
+
 assert C.sizeof(PtrSphere) == 32 and C.sizeof(PtrRect) == 80 and C.sizeof(PtrMaterial) == 576
 assert C.sizeof(PtrHit) == HIT_DTYPE.itemsize == 40
 
@@ -319,6 +355,16 @@ _STATS_SIGNATURES = {
 }
 STATS_SYMBOLS = tuple(_STATS_SIGNATURES)
 
+# ... and of include/ptr_adaptive.h (adaptive sampling): tests/test_adaptive_host.py holds it against that header
+_adaptive, _adaptive_info = C.POINTER(PtrAdaptiveParams), C.POINTER(PtrAdaptiveInfo)
+_ADAPTIVE_SIGNATURES = {
+    "ptr_adaptive_default_params": (None, [_adaptive, _u32]),
+    "ptr_render_adaptive_device": (_int, [_vp, _settings, _adaptive, _vp, _vp, _vp, _vp, _stats, _adaptive_info] + _err),
+    "ptr_render_adaptive": (_int, [_vp, _settings, _adaptive, _fp, _fp, _up, _stats, _adaptive_info] + _err),
+    "ptr_adaptive_debug_round": (_int, [_u32, _u32, _adaptive, _u32, _u32, _int, _up, _u32, _fp, _fp, _fp, _fp, _up, _fp, _up, _up] + _err),
+}
+ADAPTIVE_SYMBOLS = tuple(_ADAPTIVE_SIGNATURES)
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -335,7 +381,8 @@ def load_library() -> C.CDLL:
     if not os.path.exists(path):
         raise PtrError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` first")
     lib = C.CDLL(path)
-    for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_POST_SIGNATURES.items()) + list(_STATS_SIGNATURES.items()):
+    for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_POST_SIGNATURES.items()) + list(_STATS_SIGNATURES.items()) + \
+            list(_ADAPTIVE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -552,6 +599,31 @@ class DeviceScene:
         err = _err_buf()
         _check(load_library().ptr_stats_debug_samples(self._h, C.byref(settings), spp, _fptr(out), err, len(err)), err)
         return out
+
+    def render_adaptive(self, settings: PtrSettings, params: PtrAdaptiveParams, want_cov: bool = True, want_count: bool = True
+                        ) -> Tuple[np.ndarray, Optional[np.ndarray], Optional[np.ndarray], PtrRenderStats, PtrAdaptiveInfo]:
+        """An adaptive frame (include/ptr_adaptive.h): ([H, W, 3] image, [H, W, 6] covariance of the pixel means, [H, W] uint32 samples per
+        pixel, stats, info), all in image order."""
+        h, w = settings.height, settings.width
+        rgb = np.zeros((h, w, 3), dtype=np.float32)
+        cov = np.zeros((h, w, 6), dtype=np.float32) if want_cov else None
+        count = np.zeros((h, w), dtype=np.uint32) if want_count else None
+        stats, info = PtrRenderStats(), PtrAdaptiveInfo()
+        err = _err_buf()
+        _check(load_library().ptr_render_adaptive(self._h, C.byref(settings), C.byref(params), _fptr(rgb), _fptr(cov) if want_cov else None,
+                                                  _uptr(count) if want_count else None, C.byref(stats), C.byref(info), err, len(err)), err)
+        return rgb, cov, count, stats, info
+
+    def render_adaptive_device(self, settings: PtrSettings, params: PtrAdaptiveParams, d_rgb_ptr: int, d_cov_ptr: int = 0, d_count_ptr: int = 0,
+                               stream: int = 0, want_stats: bool = True) -> Tuple[Optional[PtrRenderStats], PtrAdaptiveInfo]:
+        """render_adaptive() into caller-owned DEVICE buffers (e.g. torch tensors' data_ptr(); W*H*3 floats, W*H*6 floats or 0, W*H
+        uint32 or 0) on `stream`.  Returns (stats, info)."""
+        stats, info = PtrRenderStats(), PtrAdaptiveInfo()
+        err = _err_buf()
+        _check(load_library().ptr_render_adaptive_device(self._h, C.byref(settings), C.byref(params), C.c_void_p(d_rgb_ptr),
+                                                         C.c_void_p(d_cov_ptr or None), C.c_void_p(d_count_ptr or None), C.c_void_p(stream or None),
+                                                         C.byref(stats) if want_stats else None, C.byref(info), err, len(err)), err)
+        return (stats if want_stats else None), info
 
     def render_aovs(self, settings: PtrSettings, sample_index: int = 0) -> Tuple[np.ndarray, np.ndarray]:
         """First-hit feature buffers: ([H, W, 4] albedo rgb | hit flag, [H, W, 4] encoded normal | distance)."""
@@ -780,6 +852,23 @@ def denoise_timed(d_rgb: int, d_albedo: int, d_normal: int, width: int, height: 
     _check(lib.ptr_denoise_timed(C.c_void_p(d_rgb), C.c_void_p(d_albedo), C.c_void_p(d_normal), width, height, C.byref(params),
                                  C.c_void_p(d_out), runs, warmup, ms, tiled, err, len(err)), err)
     return [float(v) for v in ms], [int(v) for v in tiled]
+
+
+def adaptive_debug_round(width: int, height: int, params: PtrAdaptiveParams, n_before: int, samples: np.ndarray, active: np.ndarray,
+                         state: dict, last_sub_pass: bool = True):
+    """ptr_adaptive_debug_round (tests): one round - or one sub-pass of it - of update -> select -> compact on synthetic data.  samples
+    [round_spp, len(active), 4]; state = {"sum": [H*W, 3], "mean": [H*W, 3], "m": [H*W, 6], "n": [H*W] uint32, "e": [H*W]}.  Returns (new
+    state, next list as handed back - its first `next_count` words are the kept entries, the rest are 0xFFFFFFFF - , next_count)."""
+    samples = np.ascontiguousarray(samples, dtype=np.float32)
+    active = np.ascontiguousarray(active, dtype=np.uint32).reshape(-1)
+    out = {k: np.ascontiguousarray(state[k], dtype=np.uint32 if k == "n" else np.float32).copy() for k in ("sum", "mean", "m", "n", "e")}
+    nxt = np.full(active.size, 0xFFFFFFFF, dtype=np.uint32)
+    nxt_count = C.c_uint32(0)
+    err = _err_buf()
+    _check(load_library().ptr_adaptive_debug_round(width, height, C.byref(params), n_before, samples.shape[0], int(last_sub_pass), _uptr(active),
+                                                   active.size, _fptr(samples), _fptr(out["sum"]), _fptr(out["mean"]), _fptr(out["m"]),
+                                                   _uptr(out["n"]), _fptr(out["e"]), _uptr(nxt), C.byref(nxt_count), err, len(err)), err)
+    return out, nxt, int(nxt_count.value)
 
 
 def assemble_bands(parts_out, width: int, height: int) -> np.ndarray:

@@ -51,6 +51,10 @@ struct CliOptions {
     bool denoise = false;            // --denoise: filter the frame, guided by the first-hit feature buffers (include/ptr_post.h)
     uint32_t denoiseIterations = 0;  // --denoiseIterations: a-trous passes (0 = the filter's default)
     bool denoiseSampleVariance = false;   // --denoiseVariance=sample: the filter's variance from the per-pixel sample covariance (include/ptr_stats.h)
+    bool adaptive = false;           // --adaptive: the frame in rounds over the pixels whose error is above a threshold (include/ptr_adaptive.h)
+    float adaptiveThreshold = 0.0f;  // --adaptive=<threshold>
+    bool adaptiveThresholdSet = false;
+    uint32_t adaptiveMinSpp = 0, adaptiveStep = 0;   // --adaptiveMinSpp / --adaptiveStep (0 = the default)
     uint32_t backendSemantics = 0;   // what --backend / --enableEmbree imply; an explicit --semantics overrides it
     bool semanticsSet = false;
     std::string formatString = "exr";
@@ -111,6 +115,11 @@ void printUsage(const char* exe) {
               << "  --denoiseVariance=<spatial|sample>  Variance of --denoise's luminance edge-stop: spatial = estimated from a 7x7 window of\n"
               << "                                the image (default); sample = measured per pixel from the frame's own samples (needs\n"
               << "                                --denoise, --sppTotal >= 2 and --devices=1)\n"
+              << "  --adaptive[=<threshold>]      Render in rounds: every pixel gets --adaptiveMinSpp samples, then only the pixels whose\n"
+              << "                                relative standard error (or a neighbour's) is above the threshold go on, up to\n"
+              << "                                --sppTotal samples (default threshold 0.05; needs --devices=1)\n"
+              << "  --adaptiveMinSpp=<n>          Samples of the first round of --adaptive (>= 2, default 8)\n"
+              << "  --adaptiveStep=<n>            Samples of every later round of --adaptive (>= 1, default 8)\n"
               << "  --verbose                     Print progress\n"
               << "  --help                        Show this message\n";
 }
@@ -265,6 +274,25 @@ bool parseOptions(int argc, const char** argv, CliOptions& o, std::string& error
                 return false;
             }
             o.denoiseSampleVariance = value == "sample";
+        } else if (arg == "--adaptive") {
+            o.adaptive = true;
+            if (inlineValue) {
+                size_t used = 0;
+                try {
+                    o.adaptiveThreshold = std::stof(value, &used);
+                } catch (...) {
+                    used = 0;
+                }
+                if (used == 0 || used != value.size() || !std::isfinite(o.adaptiveThreshold) || o.adaptiveThreshold < 0.0f) {
+                    error = "Invalid value for --adaptive (expected a finite threshold >= 0)";
+                    return false;
+                }
+                o.adaptiveThresholdSet = true;
+            }
+        } else if (arg == "--adaptiveMinSpp") {
+            if (!intArg("--adaptiveMinSpp", 2, o.adaptiveMinSpp, nullptr)) return false;
+        } else if (arg == "--adaptiveStep") {
+            if (!intArg("--adaptiveStep", 1, o.adaptiveStep, nullptr)) return false;
         } else if (arg == "--semantics") {
             if (!need("--semantics")) return false;
             if (value == "metal") {
@@ -320,6 +348,14 @@ bool parseOptions(int argc, const char** argv, CliOptions& o, std::string& error
         error = "--denoiseVariance=sample requires --sppTotal >= 2";
         return false;
     }
+    if ((o.adaptiveMinSpp || o.adaptiveStep) && !o.adaptive) {
+        error = "--adaptiveMinSpp and --adaptiveStep require --adaptive";
+        return false;
+    }
+    if (o.adaptive && o.sppTotal < (o.adaptiveMinSpp ? o.adaptiveMinSpp : 8u)) {
+        error = "--adaptive requires --sppTotal (the most samples a pixel gets) >= --adaptiveMinSpp";
+        return false;
+    }
     if (!ptr::ParseImageFileFormat(o.formatString, o.format)) {
         error = "Unknown format: " + o.formatString;
         return false;
@@ -350,6 +386,11 @@ int main(int argc, const char** argv) {
 
     if (options.denoiseSampleVariance && options.devices != 1u) {
         std::cerr << "Error: --denoiseVariance=sample renders on one device; it cannot be combined with --devices=" << options.devices << std::endl;
+        return 1;
+    }
+
+    if (options.adaptive && options.devices != 1u) {
+        std::cerr << "Error: --adaptive renders on one device; it cannot be combined with --devices=" << options.devices << std::endl;
         return 1;
     }
 
@@ -416,6 +457,14 @@ int main(int argc, const char** argv) {
         hipRenderer->setDenoise(&denoiseParams);
         hipRenderer->setDenoiseVariance(options.denoiseSampleVariance);
     }
+    if (options.adaptive) {
+        PtrAdaptiveParams adaptiveParams;
+        ptr_adaptive_default_params(&adaptiveParams, options.sppTotal);
+        if (options.adaptiveThresholdSet) adaptiveParams.threshold = options.adaptiveThreshold;
+        if (options.adaptiveMinSpp) adaptiveParams.minSpp = options.adaptiveMinSpp;
+        if (options.adaptiveStep) adaptiveParams.stepSpp = options.adaptiveStep;
+        hipRenderer->setAdaptive(&adaptiveParams);
+    }
     const ptr::HipHeadlessRenderer* const hip = hipRenderer.get();
     std::unique_ptr<ptr::IHeadlessRenderer> renderer = std::move(hipRenderer);
     ptr::HeadlessRenderOutput output;
@@ -474,9 +523,16 @@ int main(int argc, const char** argv) {
         std::cout << "Feature layers written to: " << aovFs << std::endl;
     }
 
-    std::cout << "Rendered " << output.samples << " spp at " << output.width << "x" << output.height << " in "
-              << std::fixed << std::setprecision(2) << output.totalSeconds << " s"
-              << " (~" << std::setprecision(3) << output.avgMsPerSample << " ms/sample)." << std::endl;
+    if (options.adaptive) {
+        const double meanSpp = static_cast<double>(hip->lastAdaptiveInfo().totalSamples) / (static_cast<double>(output.width) * output.height);
+        std::cout << "Rendered up to " << output.samples << " spp (" << std::fixed << std::setprecision(2) << meanSpp << " spp on average, "
+                  << hip->lastAdaptiveInfo().rounds << " rounds) at " << output.width << "x" << output.height << " in " << output.totalSeconds << " s"
+                  << " (~" << std::setprecision(3) << output.avgMsPerSample << " ms/sample)." << std::endl;
+    } else {
+        std::cout << "Rendered " << output.samples << " spp at " << output.width << "x" << output.height << " in "
+                  << std::fixed << std::setprecision(2) << output.totalSeconds << " s"
+                  << " (~" << std::setprecision(3) << output.avgMsPerSample << " ms/sample)." << std::endl;
+    }
     std::cout << "Output written to: " << outFs << std::endl;
     return 0;
 }

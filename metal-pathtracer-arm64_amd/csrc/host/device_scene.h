@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstring>
 #include <exception>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -144,6 +145,11 @@ struct PtrDeviceScene {
     DeviceBuffer<float> outBands;
     DeviceBuffer<float> covBands;    // ptr_render_bands_cov: the covariance beside outBands (include/ptr_stats.h)
     DeviceBuffer<float4> covMean;    // k_resolve_cov: per local pixel, the running mean between the passes of a frame
+    // adaptive frames (include/ptr_adaptive.h): the per-pixel state in image order, the two active lists, the compaction's scratch
+    DeviceBuffer<float> adaptiveSum, adaptiveMean, adaptiveM, adaptiveE;
+    DeviceBuffer<uint32_t> adaptiveN, adaptiveLists, adaptiveBlockWords;
+    DeviceBuffer<uint8_t> adaptiveKeep;
+    DeviceBuffer<float> adaptiveOut;   // ptr_render_adaptive: rgb, cov and count of the frame before they go to the host
     DeviceBuffer<float4> rayBatch;
     DeviceBuffer<PtrHit> hitBatch;
     uint32_t* pinnedAlive = nullptr;
@@ -174,6 +180,19 @@ void renderBands(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, 
                  int mode, PtrRenderStats* stats, float* dCov = nullptr);
 // passes renderBands splits a frame of `spp` samples per pixel into (the per-sample accumulators of a pass have to fit in memory)
 uint32_t framePasses(const PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp);
+
+// most per-sample accumulators one pass may hold (the memory budget, or PTR_MAX_ITEMS)
+uint64_t maxPassItems(const PtrDeviceScene& ds);
+// The tracing part of a pass, for a caller that brings its own local-pixel table (include/ptr_adaptive.h): samples sampleBase ..
+// sampleBase + spp - 1 of the `localPixels` (> 0) pixels dPixelOfLocal names, non-counting kernels.  `consume` is handed the pass's
+// accumulators - sample c of local pixel lp at [c * localPixels + lp] - and launches what reads them on `stream`; the stream is joined
+// before the call returns.  Uses ds.outBands as scratch; leaves the scene's cached partition table alone.
+void traceItems(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, uint32_t sampleBase, const uint32_t* dPixelOfLocal,
+                uint32_t localPixels, hipStream_t stream, PtrRenderStats* stats, const std::function<void(const float4*)>& consume);
+// the local-pixel order of a one-partition frame (8-row bands, 8x8 blocks)
+void imagePixelOrder(uint32_t width, uint32_t height, std::vector<uint32_t>& out);
+// adds the times, launches and samples of pass `one` to `sum`
+void addPassStats(const PtrRenderStats& one, PtrRenderStats& sum);
 
 // The frame of a C-ABI entry point that works on a device: "<who>: null argument" unless argsOk (a call that needs `scene` says so
 // there), the device selected (the scene's; device 0 for a call without a scene, which fails when there is none), the body, the error

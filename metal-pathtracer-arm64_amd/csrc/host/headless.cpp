@@ -71,7 +71,41 @@ bool HipHeadlessRenderer::render(const HeadlessScene& scene, const HeadlessCamer
         return false;
     }
     std::vector<float> cov;
-    if (m_devices != 1) {
+    m_sampleCounts.clear();
+    m_adaptiveInfo = PtrAdaptiveInfo{};
+    if (m_adaptive) {
+        if (m_devices != 1) {
+            error = "an adaptive frame is rendered on one device (--devices=1)";
+            return false;
+        }
+        // one upload serves the frame and, where asked for, the first-hit feature buffers
+        PtrAdaptiveParams ap = m_adaptiveParams;
+        ap.maxSpp = spp;
+        PtrDeviceScene* ds = nullptr;
+        if (ptr_scene_upload(&desc, 0, &ds, err, sizeof(err)) != 0) {
+            error = err[0] ? err : "HIP scene upload failed";
+            return false;
+        }
+        const size_t pixels = static_cast<size_t>(ps.width) * ps.height;
+        m_sampleCounts.assign(pixels, 0u);
+        if (sampleVariance) cov.resize(pixels * 6u);   // already the covariance of each pixel's mean: unequal counts need no special case
+        bool ok = ptr_render_adaptive(ds, &ps, &ap, out.linearRGB.data(), sampleVariance ? cov.data() : nullptr, m_sampleCounts.data(), &m_stats,
+                                      &m_adaptiveInfo, err, sizeof(err)) == 0;
+        if (ok && captureAovs) {
+            m_aovAlbedo.assign(pixels * 4u, 0.0f);
+            m_aovNormal.assign(pixels * 4u, 0.0f);
+            ok = ptr_render_aovs(ds, &ps, 0u, m_aovAlbedo.data(), m_aovNormal.data(), err, sizeof(err)) == 0;
+        }
+        ptr_scene_release(ds);
+        if (!ok) {
+            error = err[0] ? err : "HIP render failed";
+            return false;
+        }
+        if (verbose) {
+            std::fprintf(stderr, "adaptive: %u rounds, %.2f samples per pixel on average, %u pixels at %u spp\n", m_adaptiveInfo.rounds,
+                         static_cast<double>(m_adaptiveInfo.totalSamples) / static_cast<double>(pixels), m_adaptiveInfo.pixelsAtMax, spp);
+        }
+    } else if (m_devices != 1) {
         // the frame in interleaved bands over several devices of the node, gathered on the first one
         if (ptr_render_multi(&desc, &ps, spp, m_devices, verbose ? 1 : 0, out.linearRGB.data(), &m_stats, err, sizeof(err)) != 0) {
             error = err[0] ? err : "HIP render failed";
@@ -83,7 +117,7 @@ bool HipHeadlessRenderer::render(const HeadlessScene& scene, const HeadlessCamer
             return false;
         }
     }
-    if (captureAovs) {
+    if (captureAovs && !m_adaptive) {
         // one upload serves the frame (single device) and the first-hit feature buffers
         PtrDeviceScene* ds = nullptr;
         if (ptr_scene_upload(&desc, 0, &ds, err, sizeof(err)) != 0) {

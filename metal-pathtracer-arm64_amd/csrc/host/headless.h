@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "ptr_adaptive.h"
 #include "ptr_post.h"
 #include "ptr_stats.h"
 #include "render_settings.h"
@@ -70,6 +71,15 @@ public:
     // where the denoiser's variance comes from: false = the filter's own 7x7 spatial estimate (include/ptr_post.h), true = the frame's
     // per-pixel sample covariance (include/ptr_stats.h; needs sppTotal >= 2 and one device): --denoiseVariance of the CLI
     void setDenoiseVariance(bool fromSamples) { m_denoiseFromSamples = fromSamples; }
+    // render the frame adaptively (include/ptr_adaptive.h; one device): null = off.  maxSpp is taken from render()'s sppTotal:
+    // --adaptive of the CLI
+    void setAdaptive(const PtrAdaptiveParams* params) {
+        m_adaptive = params != nullptr;
+        if (params) m_adaptiveParams = *params;
+    }
+    // of the last adaptive frame: samples per pixel in image order, and the rounds it took
+    const std::vector<uint32_t>& sampleCounts() const { return m_sampleCounts; }
+    const PtrAdaptiveInfo& lastAdaptiveInfo() const { return m_adaptiveInfo; }
 
 private:
     PtrRenderStats m_stats{};
@@ -80,6 +90,10 @@ private:
     PtrDenoiseParams m_denoiseParams{};
     double m_denoiseMs = 0.0;
     bool m_denoiseFromSamples = false;
+    bool m_adaptive = false;
+    PtrAdaptiveParams m_adaptiveParams{};
+    PtrAdaptiveInfo m_adaptiveInfo{};
+    std::vector<uint32_t> m_sampleCounts;
 };
 
 // RenderSettings -> POD settings of the C-ABI.

@@ -18,6 +18,7 @@
 #include <memory>
 #include <string>
 #include <thread>
+#include <functional>
 #include <vector>
 
 #include "bvh_builder.h"
@@ -905,21 +906,16 @@ void passStats(const PtrDeviceScene& ds, const RenderParams& rp, const std::vect
                  100.0 * static_cast<double>(c[kCntExtendRefillTicks]) / std::max(static_cast<double>(c[kCntExtendWaveTicks]), 1.0));
 }
 
+template <typename Resolve>
+void tracePass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, uint32_t sampleBase, uint32_t sppTotal, uint32_t passFlags,
+               const uint32_t* dPixelOfLocal, uint32_t localPixels, hipStream_t stream, int mode, PtrRenderStats* stats, Resolve&& resolve);
+
 // One pass over `spp` samples per pixel starting at sample `sampleBase` of a frame of `sppTotal`; passFlags bit 0 = first pass of
 // the frame (output and counters start from zero), bit 1 = last pass (the running sum in dOut is divided by sppTotal).
 // (renderBands has checked the size and the partition, and selected the device.)
 // dCov (nullable; include/ptr_stats.h): six floats per pixel in the band layout of dOut, the covariance of the pixel mean.
 void renderPass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, uint32_t sampleBase, uint32_t sppTotal, uint32_t passFlags,
                 uint32_t part, uint32_t parts, float* dOut, float* dCov, hipStream_t stream, int mode, PtrRenderStats* stats) {
-    const bool count = (mode & 1) != 0;         // counting instantiation of the kernels
-    const bool soloGroup = (mode & 2) != 0;     // one pool group: kernels run alone, for clean per-kernel timings
-
-    RenderParams rp;
-    fillRenderParams(settings, spp, rp);
-    rp.sampleBase = sampleBase;
-    rp.sppTotal = std::max(1u, sppTotal);
-    rp.passFlags = passFlags;
-
     if (ds.cachedW != settings.width || ds.cachedH != settings.height || ds.cachedPart != part || ds.cachedParts != parts) {
         std::vector<uint32_t> pixels;
         partitionPixels(settings.width, settings.height, part, parts, pixels);
@@ -939,6 +935,30 @@ void renderPass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, u
         HIP_CHECK(hipStreamSynchronize(stream));
         return;
     }
+    tracePass(ds, settings, spp, sampleBase, sppTotal, passFlags, ds.pixelOfLocal.ptr, localPixels, stream, mode, stats,
+              [&](const RenderParams& rp, const PathPool& pool, LaunchTimer& timer) {
+                  launchResolve(rp, pool, parts, dOut, stream);
+                  if (dCov) {
+                      ds.covMean.ensure(localPixels);
+                      timer.launch(SpanKind::ResolveCov, stream, [&] { launchResolveCov(rp, pool, parts, ds.covMean.ptr, dCov, stream); });
+                  }
+              });
+}
+
+// The part of a pass that traces its work items: from the parameter set-up through the end-of-frame kernels, then `resolve` (what
+// reads the per-sample accumulators: see renderPass), the stream joined and the figures of the pass.  dPixelOfLocal: the image pixel
+// of each of the pass's `localPixels` (> 0) local pixels, on the device.
+template <typename Resolve>
+void tracePass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, uint32_t sampleBase, uint32_t sppTotal, uint32_t passFlags,
+               const uint32_t* dPixelOfLocal, uint32_t localPixels, hipStream_t stream, int mode, PtrRenderStats* stats, Resolve&& resolve) {
+    const bool count = (mode & 1) != 0;         // counting instantiation of the kernels
+    const bool soloGroup = (mode & 2) != 0;     // one pool group: kernels run alone, for clean per-kernel timings
+
+    RenderParams rp;
+    fillRenderParams(settings, spp, rp);
+    rp.sampleBase = sampleBase;
+    rp.sppTotal = std::max(1u, sppTotal);
+    rp.passFlags = passFlags;
 
     // Work items = single pixel samples: item w = sample * localPixels + localPixel.  Slots claim items from 64 range heads,
     // so the pool stays full until the last items regardless of how path length varies over the image.  (Items of C > 1
@@ -964,8 +984,10 @@ void renderPass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, u
 
     sizeSlots(ds, rp, count, slots);
     EnvLodView env;
-    const PathPool pool = slotRange(ds, rp, count, slots, 0u, slots, env);
+    PathPool pool = slotRange(ds, rp, count, slots, 0u, slots, env);
+    pool.pixelOfLocal = dPixelOfLocal;
     std::vector<PoolGroup> groups = makeGroups(ds, rp, count, soloGroup, slots, stream);
+    for (PoolGroup& gr : groups) gr.pool.pixelOfLocal = dPixelOfLocal;
     LaunchTimer timer{stats != nullptr};
 
     if (count && (passFlags & 1u)) HIP_CHECK(hipMemsetAsync(ds.counters.ptr, 0, sizeof(uint64_t) * kCounterSlots, stream));   // counters add up over the passes
@@ -1040,11 +1062,7 @@ void renderPass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, u
         timer.launch(SpanKind::Tail, stream,
                      [&] { launchTail(rp, ds.view, pool, env, groups[0].cfg, ds.tailList.ptr, ds.tailWords.ptr, ds.tailWords.ptr + 1, count, stream); });
     }
-    launchResolve(rp, pool, parts, dOut, stream);
-    if (dCov) {
-        ds.covMean.ensure(localPixels);
-        timer.launch(SpanKind::ResolveCov, stream, [&] { launchResolveCov(rp, pool, parts, ds.covMean.ptr, dCov, stream); });
-    }
+    resolve(rp, pool, timer);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(stream));
     const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
@@ -1059,10 +1077,15 @@ namespace ptrhost {
 // more samples than that is rendered in several passes of equal sample counts whose per-pixel sums add up in the output
 // buffer.  (Folding C samples into one work item instead keeps one pass but lengthens the end-of-frame drain: 4096 spp of
 // config 2 as items of 9 samples ran at 1116 Msamples/s.)  The sample streams do not depend on the split.
-uint32_t framePasses(const PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp) {
+uint64_t maxPassItems(const PtrDeviceScene& ds) {
     const uint64_t budget = itemBudgetBytes(ds);
     uint64_t maxItems = std::min<uint64_t>(budget / sizeof(float4), 0xFFFFFFF0ull);
     if (const uint64_t forced = ptr::readKnobs().maxItems) maxItems = forced;   // test knob
+    return maxItems;
+}
+
+uint32_t framePasses(const PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp) {
+    const uint64_t maxItems = maxPassItems(ds);
     // counted on the whole frame, not on this partition: every partition then splits the samples the same way and the image
     // stays bit-identical whatever the number of partitions
     const uint64_t pixels = static_cast<uint64_t>(settings.width) * settings.height;
@@ -1100,6 +1123,26 @@ void renderBands(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, 
         sum.avgMsPerSample = sum.totalSeconds * 1000.0 / spp;
         *stats = sum;
     }
+}
+
+void traceItems(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, uint32_t sampleBase, const uint32_t* dPixelOfLocal,
+                uint32_t localPixels, hipStream_t stream, PtrRenderStats* stats, const std::function<void(const float4*)>& consume) {
+    // (pass flags 1: k_resolve, which launchResolve runs behind the flush of the outstanding connections, overwrites dScratch)
+    const size_t scratchFloats = static_cast<size_t>(ptr_part_band_count(settings.height, 0u, 1u)) * PTR_BAND_ROWS * settings.width * 3u;
+    ds.outBands.ensure(scratchFloats);
+    tracePass(ds, settings, spp, sampleBase, spp, 1u, dPixelOfLocal, localPixels, stream, 0, stats,
+              [&](const RenderParams& rp, const PathPool& pool, LaunchTimer&) {
+                  launchResolve(rp, pool, 1u, ds.outBands.ptr, stream);
+                  consume(pool.itemAccum);
+              });
+}
+
+void imagePixelOrder(uint32_t width, uint32_t height, std::vector<uint32_t>& out) { partitionPixels(width, height, 0u, 1u, out); }
+
+void addPassStats(const PtrRenderStats& one, PtrRenderStats& sum) {
+    addLaunchStats(sum, one);
+    sum.totalSeconds += one.totalSeconds;
+    sum.uploadSeconds = one.uploadSeconds;
 }
 
 }  // namespace ptrhost
