@@ -8,8 +8,8 @@
  * Kernels: csrc/kernels/adaptive.hip (k_adaptive_update, k_adaptive_select, k_adaptive_scan, k_adaptive_scatter, k_adaptive_finish).
  * Host: csrc/host/adaptive.cpp.  Restatement in numpy (the tests' reference): tests/adaptive_ref.py.
  *
- * Scope: one device, the whole image, the non-counting build of the kernels.  Partitions, ptr_render_multi and count_traversal are not
- * supported.
+ * Scope: one device, the whole image, the non-counting build of the kernels.  The same frame on several devices, bit for bit, is
+ * ptr_render_multi_adaptive of ptr_multi.h; count_traversal is not supported.
  *
  * ---- The specification (kernels and restatement are written from this text) ---------------------------------------------------------
  *
@@ -52,7 +52,8 @@
  *   ptr_stats.h prefilters).
  *
  * Compact.  The next active list is the kept entries of the current list in the current list's order.  The first list is the local
- * pixel order of a one-partition frame: 8-row bands top to bottom, each walked in 8x8 blocks left to right, each block row-major.
+ * pixel order of a one-partition frame: 8-row bands top to bottom, each walked in 8x8 blocks left to right, each block row-major
+ * (on several devices every partition starts from its own bands in that order: ptr_multi.h).
  *
  * Outputs, in image order (row 0 = top), NOT the band layout:
  *       rgb   (width*height*3):            sum / float(n_p)

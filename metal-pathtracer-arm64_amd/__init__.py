@@ -261,6 +261,24 @@ class PtrAdaptiveInfo(C.Structure):
         return [int(v) for v in self.activeAfter[: min(self.rounds, ADAPTIVE_INFO_ROUNDS)]]
 
 
+MULTI_MAX_PARTS = 64   # PTR_MULTI_MAX_PARTS
+
+
+class PtrMultiInfo(C.Structure):
+    """include/ptr_multi.h PtrMultiInfo."""
+    _fields_ = [
+        ("parts", C.c_uint32),
+        ("stagedParts", C.c_uint32),
+        ("partSamples", C.c_uint64 * MULTI_MAX_PARTS),
+        ("partRenderSeconds", C.c_double * MULTI_MAX_PARTS),
+        ("partWaitSeconds", C.c_double * MULTI_MAX_PARTS),
+    ]
+
+    def per_part(self) -> list:
+        """[(samples, render seconds, wait seconds)] of the partitions the frame ran on"""
+        return [(int(self.partSamples[p]), float(self.partRenderSeconds[p]), float(self.partWaitSeconds[p])) for p in range(self.parts)]
+
+
 assert C.sizeof(PtrSphere) == 32 and C.sizeof(PtrRect) == 80 and C.sizeof(PtrMaterial) == 576
 assert C.sizeof(PtrHit) == HIT_DTYPE.itemsize == 40
 
@@ -365,6 +383,17 @@ _ADAPTIVE_SIGNATURES = {
 }
 ADAPTIVE_SYMBOLS = tuple(_ADAPTIVE_SIGNATURES)
 
+# ... and of include/ptr_multi.h (covariance and adaptive sampling on several devices): tests/test_multi_host.py holds it against that header
+_multi_info, _ids = C.POINTER(PtrMultiInfo), C.POINTER(_int)
+_MULTI_SIGNATURES = {
+    "ptr_render_multi_cov": (_int, [_desc, _settings, _u32, _int, _int, _fp, _fp, _fp, _fp, _stats, _multi_info] + _err),
+    "ptr_render_multi_adaptive": (_int, [_desc, _settings, _adaptive, _int, _int, _fp, _fp, _up, _fp, _fp, _stats, _adaptive_info, _multi_info] + _err),
+    "ptr_multi_debug_cov_on": (_int, [_desc, _settings, _u32, _ids, _int, _fp, _fp, _fp, _fp, _stats, _multi_info] + _err),
+    "ptr_multi_debug_adaptive_on": (_int, [_desc, _settings, _adaptive, _ids, _int, _fp, _fp, _up, _fp, _fp, _stats, _adaptive_info, _multi_info] + _err),
+    "ptr_multi_debug_adaptive_frame": (_int, [_u32, _u32, _adaptive, _fp, _ids, _int, _fp, _fp, _up, _adaptive_info] + _err),
+}
+MULTI_SYMBOLS = tuple(_MULTI_SIGNATURES)
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -382,7 +411,7 @@ def load_library() -> C.CDLL:
         raise PtrError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` first")
     lib = C.CDLL(path)
     for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_POST_SIGNATURES.items()) + list(_STATS_SIGNATURES.items()) + \
-            list(_ADAPTIVE_SIGNATURES.items()):
+            list(_ADAPTIVE_SIGNATURES.items()) + list(_MULTI_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -772,6 +801,80 @@ def render_multi(desc: PtrSceneDesc, settings: PtrSettings, spp: int, n_devices:
     else:
         _check(lib.ptr_render_multi(C.byref(desc), C.byref(settings), spp, n_devices, int(verbose), _fptr(img), C.byref(stats), err, len(err)), err)
     return img, stats
+
+
+def _aov_pair(settings: PtrSettings, want: bool):
+    if not want:
+        return None, None
+    return (np.zeros((settings.height, settings.width, 4), dtype=np.float32), np.zeros((settings.height, settings.width, 4), dtype=np.float32))
+
+
+def _opt(a, ptr):
+    return None if a is None else ptr(a)
+
+
+def render_multi_cov(desc: PtrSceneDesc, settings: PtrSettings, spp: int, n_devices: int = 0, device_ids=None, want_aovs: bool = False,
+                     verbose: bool = False) -> dict:
+    """A uniform frame over several devices with the covariance of the pixel means (include/ptr_multi.h ptr_render_multi_cov): a dict
+    with rgb [H, W, 3], cov [H, W, 6], albedo / normal ([H, W, 4] each, None unless want_aovs), stats and multi (PtrMultiInfo).
+    `device_ids` (tests) names the devices explicitly as render_multi's does; -(id + 1) forces the staged hand-over."""
+    lib = load_library()
+    rgb = np.zeros((settings.height, settings.width, 3), dtype=np.float32)
+    cov = np.zeros((settings.height, settings.width, 6), dtype=np.float32)
+    albedo, normal = _aov_pair(settings, want_aovs)
+    stats, multi = PtrRenderStats(), PtrMultiInfo()
+    err = _err_buf()
+    tail = (_fptr(rgb), _fptr(cov), _opt(albedo, _fptr), _opt(normal, _fptr), C.byref(stats), C.byref(multi), err, len(err))
+    if device_ids is not None:
+        ids = (C.c_int * len(device_ids))(*device_ids)
+        _check(lib.ptr_multi_debug_cov_on(C.byref(desc), C.byref(settings), spp, ids, len(device_ids), *tail), err)
+    else:
+        _check(lib.ptr_render_multi_cov(C.byref(desc), C.byref(settings), spp, n_devices, int(verbose), *tail), err)
+    return {"rgb": rgb, "cov": cov, "albedo": albedo, "normal": normal, "stats": stats, "multi": multi}
+
+
+def render_multi_adaptive(desc: PtrSceneDesc, settings: PtrSettings, params: PtrAdaptiveParams, n_devices: int = 0, device_ids=None,
+                          want_cov: bool = True, want_count: bool = True, want_aovs: bool = False, verbose: bool = False) -> dict:
+    """An adaptive frame over several devices (include/ptr_multi.h ptr_render_multi_adaptive), bit for bit DeviceScene.render_adaptive's:
+    a dict with rgb [H, W, 3], cov [H, W, 6] or None, count [H, W] uint32 or None, albedo / normal (None unless want_aovs), stats, info
+    (PtrAdaptiveInfo) and multi (PtrMultiInfo).  `device_ids` as render_multi_cov's."""
+    lib = load_library()
+    h, w = settings.height, settings.width
+    rgb = np.zeros((h, w, 3), dtype=np.float32)
+    cov = np.zeros((h, w, 6), dtype=np.float32) if want_cov else None
+    count = np.zeros((h, w), dtype=np.uint32) if want_count else None
+    albedo, normal = _aov_pair(settings, want_aovs)
+    stats, info, multi = PtrRenderStats(), PtrAdaptiveInfo(), PtrMultiInfo()
+    err = _err_buf()
+    tail = (_fptr(rgb), _opt(cov, _fptr), _opt(count, _uptr), _opt(albedo, _fptr), _opt(normal, _fptr), C.byref(stats), C.byref(info), C.byref(multi),
+            err, len(err))
+    if device_ids is not None:
+        ids = (C.c_int * len(device_ids))(*device_ids)
+        _check(lib.ptr_multi_debug_adaptive_on(C.byref(desc), C.byref(settings), C.byref(params), ids, len(device_ids), *tail), err)
+    else:
+        _check(lib.ptr_render_multi_adaptive(C.byref(desc), C.byref(settings), C.byref(params), n_devices, int(verbose), *tail), err)
+    return {"rgb": rgb, "cov": cov, "count": count, "albedo": albedo, "normal": normal, "stats": stats, "info": info, "multi": multi}
+
+
+def multi_adaptive_debug_frame(samples: np.ndarray, params: PtrAdaptiveParams, device_ids):
+    """ptr_multi_debug_adaptive_frame (tests): the partition loop of render_multi_adaptive on samples [maxSpp, H, W, 3 or 4] instead of a
+    scene.  Returns (rgb [H, W, 3], cov [H, W, 6], count [H, W] uint32, info)."""
+    samples = np.asarray(samples, dtype=np.float32)
+    if samples.ndim != 4 or samples.shape[3] not in (3, 4) or samples.shape[0] < params.maxSpp:
+        raise ValueError("multi_adaptive_debug_frame: samples must be [>= maxSpp, H, W, 3 or 4]")
+    if samples.shape[3] == 3:
+        samples = np.concatenate([samples, np.zeros(samples.shape[:3] + (1,), np.float32)], axis=3)
+    samples = np.ascontiguousarray(samples)
+    h, w = samples.shape[1], samples.shape[2]
+    rgb = np.zeros((h, w, 3), dtype=np.float32)
+    cov = np.zeros((h, w, 6), dtype=np.float32)
+    count = np.zeros((h, w), dtype=np.uint32)
+    info = PtrAdaptiveInfo()
+    ids = (C.c_int * len(device_ids))(*device_ids)
+    err = _err_buf()
+    _check(load_library().ptr_multi_debug_adaptive_frame(w, h, C.byref(params), _fptr(samples), ids, len(device_ids), _fptr(rgb), _fptr(cov),
+                                                         _uptr(count), C.byref(info), err, len(err)), err)
+    return rgb, cov, count, info
 
 
 def decode_image(data: bytes) -> np.ndarray:

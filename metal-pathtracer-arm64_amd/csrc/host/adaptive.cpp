@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../kernels/adaptive.h"
+#include "adaptive_host.h"
 #include "device_scene.h"
 #include "knobs.h"
 #include "ptr_adaptive.h"
@@ -15,10 +16,9 @@
 using namespace ptrhost;
 using namespace ptrk;
 
-namespace {
+namespace ptrhost {
 
-// "<who>: ..." for bad parameters, empty when all are good.  No device call.
-std::string badParams(const char* who, const PtrAdaptiveParams& p) {
+std::string badAdaptiveParams(const char* who, const PtrAdaptiveParams& p) {
     const std::string w(who);
     if (p.minSpp < 2u) return w + ": minSpp must be >= 2 (a sample covariance needs two samples)";
     if (p.maxSpp < p.minSpp) return w + ": maxSpp must be >= minSpp";
@@ -27,30 +27,14 @@ std::string badParams(const char* who, const PtrAdaptiveParams& p) {
     return std::string();
 }
 
-std::string badRender(const char* who, bool pointersOk, const PtrSettings* settings, const PtrAdaptiveParams* params) {
-    const std::string w(who);
-    if (!pointersOk) return w + ": null argument";
-    if (settings->width == 0u || settings->height == 0u) return w + ": render size must be non-zero";
-    return badParams(who, *params);
-}
-
-constexpr uint32_t kBlock = 256u;   // threads per block of the compaction kernels (adaptive.hip)
-
-// The state of a `pixels`-pixel image, the two lists and the compaction's scratch, grown on demand.
-struct AdaptiveBuffers {
-    AdaptiveState state;
-    uint32_t* lists[2];
-    AdaptiveScratch scratch;
-};
-
-AdaptiveBuffers ensureBuffers(PtrDeviceScene& ds, size_t pixels) {
+AdaptiveBuffers ensureAdaptiveBuffers(PtrDeviceScene& ds, size_t pixels) {
     ds.adaptiveSum.ensure(pixels * 3u);
     ds.adaptiveMean.ensure(pixels * 3u);
     ds.adaptiveM.ensure(pixels * 6u);
     ds.adaptiveN.ensure(pixels);
     ds.adaptiveE.ensure(pixels);
     ds.adaptiveLists.ensure(pixels * 2u);
-    const size_t blocks = (pixels + kBlock - 1u) / kBlock;
+    const size_t blocks = (pixels + kAdaptiveBlock - 1u) / kAdaptiveBlock;
     ds.adaptiveBlockWords.ensure(blocks * 2u + 1u);
     ds.adaptiveKeep.ensure(pixels);
     AdaptiveBuffers b;
@@ -61,20 +45,35 @@ AdaptiveBuffers ensureBuffers(PtrDeviceScene& ds, size_t pixels) {
     return b;
 }
 
-void renderAdaptive(PtrDeviceScene& ds, const PtrSettings& settings, const PtrAdaptiveParams& params, float* dRgb, float* dCov, uint32_t* dCount,
-                    hipStream_t stream, PtrRenderStats* stats, PtrAdaptiveInfo* info) {
-    HIP_CHECK(hipSetDevice(ds.device));
-    const size_t pixels = static_cast<size_t>(settings.width) * settings.height;
-    if (pixels > 0xFFFF0000ull) throw HipError{"image too large for an adaptive frame"};
-    const AdaptiveBuffers b = ensureBuffers(ds, pixels);
-    std::vector<uint32_t> order;
-    imagePixelOrder(settings.width, settings.height, order);
-    HIP_CHECK(hipMemcpyAsync(b.lists[0], order.data(), pixels * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+void zeroAdaptiveState(const AdaptiveBuffers& b, size_t pixels, hipStream_t stream) {
     HIP_CHECK(hipMemsetAsync(b.state.sum, 0, pixels * 3u * sizeof(float), stream));
     HIP_CHECK(hipMemsetAsync(b.state.mean, 0, pixels * 3u * sizeof(float), stream));
     HIP_CHECK(hipMemsetAsync(b.state.m, 0, pixels * 6u * sizeof(float), stream));
     HIP_CHECK(hipMemsetAsync(b.state.n, 0, pixels * sizeof(uint32_t), stream));
     HIP_CHECK(hipMemsetAsync(b.state.e, 0, pixels * sizeof(float), stream));
+}
+
+}  // namespace ptrhost
+
+namespace {
+
+std::string badRender(const char* who, bool pointersOk, const PtrSettings* settings, const PtrAdaptiveParams* params) {
+    const std::string w(who);
+    if (!pointersOk) return w + ": null argument";
+    if (settings->width == 0u || settings->height == 0u) return w + ": render size must be non-zero";
+    return badAdaptiveParams(who, *params);
+}
+
+void renderAdaptive(PtrDeviceScene& ds, const PtrSettings& settings, const PtrAdaptiveParams& params, float* dRgb, float* dCov, uint32_t* dCount,
+                    hipStream_t stream, PtrRenderStats* stats, PtrAdaptiveInfo* info) {
+    HIP_CHECK(hipSetDevice(ds.device));
+    const size_t pixels = static_cast<size_t>(settings.width) * settings.height;
+    if (pixels > 0xFFFF0000ull) throw HipError{"image too large for an adaptive frame"};
+    const AdaptiveBuffers b = ensureAdaptiveBuffers(ds, pixels);
+    std::vector<uint32_t> order;
+    imagePixelOrder(settings.width, settings.height, order);
+    HIP_CHECK(hipMemcpyAsync(b.lists[0], order.data(), pixels * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    zeroAdaptiveState(b, pixels, stream);
     HIP_CHECK(hipStreamSynchronize(stream));   // `order` is pageable host memory
 
     PtrAdaptiveInfo local{};
@@ -94,13 +93,9 @@ void renderAdaptive(PtrDeviceScene& ds, const PtrSettings& settings, const PtrAd
         for (hipEvent_t& ev : marks.e) HIP_CHECK(hipEventCreate(&ev));
     }
     while (active > 0u && n < params.maxSpp) {
-        const uint32_t roundSpp = n == 0u ? params.minSpp : std::min(params.stepSpp, params.maxSpp - n);
-        // a round whose accumulators do not fit one pass arrives in sub-passes; the update is sample-ordered, so the split changes nothing
-        const uint32_t perPass = static_cast<uint32_t>(std::max<uint64_t>(1u, std::min<uint64_t>(maxItems / active, roundSpp)));
+        const uint32_t roundSpp = adaptiveRoundSpp(params, n);
         const uint32_t* list = b.lists[turn];
-        for (uint32_t done = 0u; done < roundSpp;) {
-            const uint32_t spp = std::min(perPass, roundSpp - done);
-            const bool last = done + spp == roundSpp;
+        forEachSubPass(maxItems, active, roundSpp, [&](uint32_t done, uint32_t spp, bool last) {
             PtrRenderStats one{};
             traceItems(ds, settings, spp, n + done, list, active, stream, stats ? &one : nullptr, [&](const float4* items) {
                 if (timed) HIP_CHECK(hipEventRecord(marks[0], stream));
@@ -120,8 +115,7 @@ void renderAdaptive(PtrDeviceScene& ds, const PtrSettings& settings, const PtrAd
                 std::fprintf(stderr, "[adaptive] round %u first sample %u: %u active x %u spp; update %.4f ms, select + compact %.4f ms\n", local.rounds,
                              n + done, active, spp, updateMs, last ? selectMs : 0.0f);
             }
-            done += spp;
-        }
+        });
         n += roundSpp;
         local.totalSamples += static_cast<uint64_t>(active) * roundSpp;
         if (n >= params.maxSpp) local.pixelsAtMax = active;
@@ -210,7 +204,7 @@ int ptr_adaptive_debug_round(uint32_t width, uint32_t height, const PtrAdaptiveP
         bad = std::string(who) + ": null argument";
     } else if (width == 0u || height == 0u || static_cast<uint64_t>(width) * height > 0xFFFF0000ull) {
         bad = std::string(who) + ": image size must be non-zero";
-    } else if ((bad = badParams(who, *params)).empty()) {
+    } else if ((bad = badAdaptiveParams(who, *params)).empty()) {
         const uint64_t pixels = static_cast<uint64_t>(width) * height;
         if (active_count == 0u || active_count > pixels || round_spp == 0u) bad = std::string(who) + ": the list and the round must not be empty";
         else if (static_cast<uint64_t>(n_before) + round_spp > params->maxSpp) bad = std::string(who) + ": the round goes past maxSpp";
@@ -230,7 +224,7 @@ int ptr_adaptive_debug_round(uint32_t width, uint32_t height, const PtrAdaptiveP
     try {
         HIP_CHECK(hipSetDevice(0));
         const size_t pixels = static_cast<size_t>(width) * height;
-        const size_t blocks = (static_cast<size_t>(active_count) + kBlock - 1u) / kBlock;
+        const size_t blocks = (static_cast<size_t>(active_count) + kAdaptiveBlock - 1u) / kAdaptiveBlock;
         DeviceBuffer<float> dSum, dMean, dM, dE;
         DeviceBuffer<uint32_t> dN, dList, dNext, dWords;
         DeviceBuffer<uint8_t> dKeep;

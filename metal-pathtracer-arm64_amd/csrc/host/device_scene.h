@@ -14,6 +14,8 @@
 
 #include "../kernels/device_types.h"
 #include "../kernels/launch.h"
+#include "env_importance_sampler.h"
+#include "geometry_cache.h"
 #include "ptr_abi.h"
 
 namespace ptrhost {
@@ -193,6 +195,41 @@ void traceItems(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, u
 void imagePixelOrder(uint32_t width, uint32_t height, std::vector<uint32_t>& out);
 // adds the times, launches and samples of pass `one` to `sum`
 void addPassStats(const PtrRenderStats& one, PtrRenderStats& sum);
+// adds the per-launch figures of `b` to `a` (kernel times, k_extend launches, samples), as a frame on several devices sums its partitions
+void addLaunchStats(PtrRenderStats& a, const PtrRenderStats& b);
+
+// What the frames on several devices share (ptr_render_multi here, include/ptr_multi.h in multi.cpp).
+// the local-pixel order of partition `part` of `parts`: its bands top to bottom, each in 8x8 blocks
+void partitionPixels(uint32_t width, uint32_t height, uint32_t part, uint32_t parts, std::vector<uint32_t>& out);
+// Device-independent half of a scene upload: geometry bake + BVH, compact materials, light list, environment tables.  Built once
+// and uploaded to every device a frame is rendered on (ptr_render_multi).
+struct PreparedScene {
+    ptr::PreparedGeometry pg;   // BVH, leaf-order arrays, four-wide nodes, node format: what a geometry cache file holds
+    std::vector<float> mats, lights;
+    std::vector<int32_t> lightIndexByRect;
+    uint32_t lightCount = 0;
+    bool lightsHaveTriangles = true;   // every rectangle light found its two triangles in the geometry (always, unless degenerate)
+    bool hasRandomWalkMaterial = false;
+    ptr::EnvImportanceDistribution envDist;
+    bool hasEnvDist = false;
+    // material textures (kernels/texture.h): every level of every texture in one array, the per-texture records, and the
+    // per-material texture records; empty when the scene has no textures
+    std::vector<float> texels;
+    std::vector<uint32_t> texInfo;
+    std::vector<float> materialTex;
+    double geometrySeconds = 0.0;   // bake + BVH + leaf order + wide nodes, or reading them from a geometry cache
+    double shadingSeconds = 0.0;    // materials, lights, environment tables, texture mips
+    bool geometryFromCache = false;
+    double seconds = 0.0;           // both
+};
+// cachePath (may be null): read the geometry from that file instead of building it
+void prepareScene(const PtrSceneDesc& desc, PreparedScene& ps, const char* cachePath = nullptr);
+// ds.device names the device
+void uploadScene(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceScene& ds);
+// A partition's band buffer travels to the first device of the frame: a plain copy when it is local, device-to-device over the fabric
+// when the two devices can address each other, through pinned host memory otherwise (or with forceStaged, the tests' hook).  Called on
+// the partition's thread with `device` current; asynchronous on `stream` except for the staged path.  True when the bytes were staged.
+bool sendBandsToRoot(void* dRootDst, int rootDevice, const void* dSrc, int device, size_t bytes, bool forceStaged, hipStream_t stream);
 
 // The frame of a C-ABI entry point that works on a device: "<who>: null argument" unless argsOk (a call that needs `scene` says so
 // there), the device selected (the scene's; device 0 for a call without a scene, which fails when there is none), the body, the error

@@ -120,28 +120,6 @@ void appendTextureWithMips(const PtrTexture& t, std::vector<float>& texels, std:
 
 namespace {
 
-// Device-independent half of a scene upload: geometry bake + BVH, compact materials, light list, environment tables.  Built once
-// and uploaded to every device a frame is rendered on (ptr_render_multi).
-struct PreparedScene {
-    ptr::PreparedGeometry pg;   // BVH, leaf-order arrays, four-wide nodes, node format: what a geometry cache file holds
-    std::vector<float> mats, lights;
-    std::vector<int32_t> lightIndexByRect;
-    uint32_t lightCount = 0;
-    bool lightsHaveTriangles = true;   // every rectangle light found its two triangles in the geometry (always, unless degenerate)
-    bool hasRandomWalkMaterial = false;
-    ptr::EnvImportanceDistribution envDist;
-    bool hasEnvDist = false;
-    // material textures (kernels/texture.h): every level of every texture in one array, the per-texture records, and the
-    // per-material texture records; empty when the scene has no textures
-    std::vector<float> texels;
-    std::vector<uint32_t> texInfo;
-    std::vector<float> materialTex;
-    double geometrySeconds = 0.0;   // bake + BVH + leaf order + wide nodes, or reading them from a geometry cache
-    double shadingSeconds = 0.0;    // materials, lights, environment tables, texture mips
-    bool geometryFromCache = false;
-    double seconds = 0.0;           // both
-};
-
 // The geometry half of the preparation: everything a geometry cache file holds (host/geometry_cache.h).
 void prepareGeometry(const PtrSceneDesc& desc, ptr::PreparedGeometry& pg) {
     const ptr::Knobs knobs = ptr::readKnobs();
@@ -163,8 +141,12 @@ void prepareGeometry(const PtrSceneDesc& desc, ptr::PreparedGeometry& pg) {
     }
 }
 
-// cachePath (may be null): read the geometry from that file instead of building it
-void prepareScene(const PtrSceneDesc& desc, PreparedScene& ps, const char* cachePath = nullptr) {
+}  // namespace
+
+namespace ptrhost {
+
+void prepareScene(const PtrSceneDesc& desc, PreparedScene& ps, const char* cachePath) {
+    using ptr::float3;
     const auto t0 = std::chrono::steady_clock::now();
     if (cachePath && *cachePath) {
         std::string error;
@@ -386,6 +368,10 @@ void uploadScene(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceSce
     if (knobs.verboseBuild) std::fprintf(stderr, "[upload] prepare %.2f s, copies to the device %.2f s\n", ps.seconds, copySeconds);
 }
 
+}  // namespace ptrhost
+
+namespace {
+
 void buildScene(const PtrSceneDesc& desc, PtrDeviceScene& ds, const char* cachePath = nullptr) {
     PreparedScene ps;
     prepareScene(desc, ps, cachePath);
@@ -503,10 +489,6 @@ void fillRenderParams(const PtrSettings& s, uint32_t spp, RenderParams& rp) {
 // Launch configuration of the one-off traversal kernels (ray batches, AOVs, debug queries): whole grid, group 0's heads and spill area
 LaunchConfig coldLaunchConfig(const PtrDeviceScene& ds) { return LaunchConfig{ds.traceGrid, ds.spill.ptr, ds.scalars.ptr + 1, ds.refillBelow}; }
 
-}  // namespace ptrhost
-
-namespace {
-
 // Local pixel order of a partition: its PTR_BAND_ROWS-row bands top to bottom, each walked in 8x8 blocks so the
 // 64 lanes of a wave start with a compact, coherent bundle of primary rays.
 void partitionPixels(uint32_t width, uint32_t height, uint32_t part, uint32_t parts, std::vector<uint32_t>& out) {
@@ -524,13 +506,6 @@ void partitionPixels(uint32_t width, uint32_t height, uint32_t part, uint32_t pa
     }
 }
 
-// Bytes the per-sample accumulators of one pass may take: a quarter of the device's TOTAL memory, at most 16 GiB.  Taken
-// from the device's size, never from what happens to be free: every rank of a multi-GPU render has to split a frame
-// into the same passes (k_resolve adds the per-pass sums in pass order), whatever else lives on its card.
-uint64_t itemBudgetBytes(const PtrDeviceScene& ds) {
-    return std::max<uint64_t>(64ull << 20, std::min<uint64_t>(16ull << 30, ds.deviceTotalBytes / 4u));
-}
-
 // Adds the per-launch figures of `b` to `a`: kernel times, k_extend launches, samples.
 void addLaunchStats(PtrRenderStats& a, const PtrRenderStats& b) {
     a.traceKernelMs += b.traceKernelMs;
@@ -539,6 +514,17 @@ void addLaunchStats(PtrRenderStats& a, const PtrRenderStats& b) {
     a.tailKernelMs += b.tailKernelMs;
     a.traceLaunches += b.traceLaunches;
     a.samples += b.samples;
+}
+
+}  // namespace ptrhost
+
+namespace {
+
+// Bytes the per-sample accumulators of one pass may take: a quarter of the device's TOTAL memory, at most 16 GiB.  Taken
+// from the device's size, never from what happens to be free: every rank of a multi-GPU render has to split a frame
+// into the same passes (k_resolve adds the per-pass sums in pass order), whatever else lives on its card.
+uint64_t itemBudgetBytes(const PtrDeviceScene& ds) {
+    return std::max<uint64_t>(64ull << 20, std::min<uint64_t>(16ull << 30, ds.deviceTotalBytes / 4u));
 }
 
 // optional per-slot arrays: the ray cone of textured paths, the environment LOD of PTR_METAL_ENV_LOD with an environment map
@@ -1145,6 +1131,36 @@ void addPassStats(const PtrRenderStats& one, PtrRenderStats& sum) {
     sum.uploadSeconds = one.uploadSeconds;
 }
 
+bool sendBandsToRoot(void* dRootDst, int rootDevice, const void* dSrc, int device, size_t bytes, bool forceStaged, hipStream_t stream) {
+    if (device == rootDevice && !forceStaged) {
+        HIP_CHECK(hipMemcpyAsync(dRootDst, dSrc, bytes, hipMemcpyDeviceToDevice, stream));
+        return false;
+    }
+    int direct = 0;
+    if (device != rootDevice) HIP_CHECK(hipDeviceCanAccessPeer(&direct, device, rootDevice));
+    if (forceStaged) direct = 0;
+    if (direct) {
+        const hipError_t enabled = hipDeviceEnablePeerAccess(rootDevice, 0);   // (this thread's current device is `device`)
+        if (enabled != hipSuccess && enabled != hipErrorPeerAccessAlreadyEnabled) direct = 0;
+        (void)hipGetLastError();
+    }
+    if (direct) {
+        HIP_CHECK(hipMemcpyPeerAsync(dRootDst, rootDevice, dSrc, device, bytes, stream));
+        return false;
+    }
+    std::fprintf(stderr, "[ptr] device %d does not address device %d directly: its bands go through pinned host memory\n", device, rootDevice);
+    void* staging = nullptr;
+    HIP_CHECK(hipHostMalloc(&staging, bytes, hipHostMallocDefault));
+    hipError_t copied = hipMemcpyAsync(staging, dSrc, bytes, hipMemcpyDeviceToHost, stream);
+    if (copied == hipSuccess) copied = hipStreamSynchronize(stream);
+    if (copied == hipSuccess) copied = hipSetDevice(rootDevice);
+    if (copied == hipSuccess) copied = hipMemcpy(dRootDst, staging, bytes, hipMemcpyHostToDevice);
+    (void)hipSetDevice(device);
+    (void)hipHostFree(staging);
+    HIP_CHECK(copied);
+    return true;
+}
+
 }  // namespace ptrhost
 
 extern "C" {
@@ -1359,34 +1375,9 @@ static int renderMulti(const PtrSceneDesc* scene, const PtrSettings* settings, u
                 HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
                 const auto r0 = std::chrono::steady_clock::now();
                 renderBands(*ds, *settings, spp, p, parts, ds->outBands.ptr, stream, 0, &partStats[p]);
-                // the partition's bands travel to the first device: a plain copy when it is local, device-to-device over the fabric
-                // (xGMI between the GPUs of a node) when the two devices can address each other, through pinned host memory otherwise
-                if (floats && ds->device == rootDevice && !forceStaged[p]) {
-                    HIP_CHECK(hipMemcpyAsync(gathered.ptr + partOffset[p], ds->outBands.ptr, floats * sizeof(float), hipMemcpyDeviceToDevice, stream));
-                } else if (floats) {
-                    int direct = 0;
-                    if (ds->device != rootDevice) HIP_CHECK(hipDeviceCanAccessPeer(&direct, ds->device, rootDevice));
-                    if (forceStaged[p]) direct = 0;
-                    if (direct) {
-                        const hipError_t enabled = hipDeviceEnablePeerAccess(rootDevice, 0);   // (this thread's current device is ds->device)
-                        if (enabled != hipSuccess && enabled != hipErrorPeerAccessAlreadyEnabled) direct = 0;
-                        (void)hipGetLastError();
-                    }
-                    if (direct) {
-                        HIP_CHECK(hipMemcpyPeerAsync(gathered.ptr + partOffset[p], rootDevice, ds->outBands.ptr, ds->device, floats * sizeof(float), stream));
-                    } else {
-                        std::fprintf(stderr, "[ptr] device %d does not address device %d directly: its bands go through pinned host memory\n", ds->device, rootDevice);
-                        float* staging = nullptr;
-                        HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&staging), floats * sizeof(float), hipHostMallocDefault));
-                        hipError_t copied = hipMemcpyAsync(staging, ds->outBands.ptr, floats * sizeof(float), hipMemcpyDeviceToHost, stream);
-                        if (copied == hipSuccess) copied = hipStreamSynchronize(stream);
-                        if (copied == hipSuccess) copied = hipSetDevice(rootDevice);
-                        if (copied == hipSuccess) copied = hipMemcpy(gathered.ptr + partOffset[p], staging, floats * sizeof(float), hipMemcpyHostToDevice);
-                        (void)hipSetDevice(ds->device);
-                        (void)hipHostFree(staging);
-                        HIP_CHECK(copied);
-                        stagedParts.fetch_add(1);
-                    }
+                if (floats && sendBandsToRoot(gathered.ptr + partOffset[p], rootDevice, ds->outBands.ptr, ds->device, floats * sizeof(float),
+                                              forceStaged[p] != 0, stream)) {
+                    stagedParts.fetch_add(1);
                 }
                 HIP_CHECK(hipStreamSynchronize(stream));
                 renderSeconds[p] = std::chrono::duration<double>(std::chrono::steady_clock::now() - r0).count();

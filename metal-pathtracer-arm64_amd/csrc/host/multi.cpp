@@ -1,0 +1,520 @@
+// Host side of include/ptr_multi.h: the argument checks, one host thread per partition (each with its own device scene and stream, as
+// ptr_render_multi), the lock-step rounds of an adaptive frame with the exchange of the band-edge rows of e between them, and the finish
+// and gather in band layout.  The sample source of a pass is a parameter of the partition loop: traceItems for the renderer,
+// k_multi_gather_items for the test-only probe, which therefore runs everything else the renderer runs.
+#include <algorithm>
+#include <atomic>
+#include <chrono>
+#include <cstdio>
+#include <cstring>
+#include <functional>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../kernels/multi.h"
+#include "adaptive_host.h"
+#include "device_scene.h"
+#include "knobs.h"
+#include "parallel.h"
+#include "ptr_multi.h"
+#include "round_barrier.h"
+
+using namespace ptrhost;
+using namespace ptrk;
+
+namespace {
+
+using Clock = std::chrono::steady_clock;
+double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
+
+// What one call asks for.  scene == nullptr: the probe (samples != nullptr); params == nullptr: the uniform frame with covariance.
+struct Request {
+    const char* who = "";
+    const PtrSceneDesc* scene = nullptr;
+    PtrSettings settings{};   // the probe fills in width and height only
+    uint32_t spp = 0u;
+    const PtrAdaptiveParams* params = nullptr;
+    const float* samples = nullptr;
+    std::vector<int> devices;
+    std::vector<char> forceStaged;
+    int verbose = 0;
+    float* outRgb = nullptr;
+    float* outCov = nullptr;
+    uint32_t* outCount = nullptr;
+    float* outAlbedo = nullptr;
+    float* outNormal = nullptr;
+    PtrRenderStats* stats = nullptr;
+    PtrAdaptiveInfo* info = nullptr;
+    PtrMultiInfo* multi = nullptr;
+};
+
+// The pinned host memory the partitions exchange their edge rows through (portable: every device's copies may use it).  Partition p
+// publishes into its outbox - its edge rows as k_multi_halo_pack lays them out - and collects its neighbours' rows in its inbox.
+struct Exchange {
+    float* host = nullptr;
+    std::vector<size_t> offset;   // of partition p's edge rows in either half, in floats; [parts] = the size of a half
+    ~Exchange() {
+        if (host) (void)hipHostFree(host);
+    }
+    float* outbox(uint32_t p) const { return host + offset[p]; }
+    float* inbox(uint32_t p) const { return host + offset.back() + offset[p]; }
+};
+
+// samples sampleBase .. sampleBase + spp - 1 of the `active` list entries: hands `consume` the accumulators and joins the stream
+using PassSource = std::function<void(uint32_t spp, uint32_t sampleBase, const uint32_t* dList, uint32_t active, PtrRenderStats* one,
+                                      const std::function<void(const float4*)>& consume)>;
+
+void runFrame(const Request& rq) {
+    const bool adaptive = rq.params != nullptr;
+    const bool probe = rq.scene == nullptr;
+    const uint32_t parts = static_cast<uint32_t>(rq.devices.size());
+    const uint32_t width = rq.settings.width, height = rq.settings.height;
+    const size_t pixels = static_cast<size_t>(width) * height;
+    if (pixels + static_cast<size_t>(PTR_BAND_ROWS) * width > 0xFFFF0000ull) throw HipError{"image too large"};
+    const auto t0 = Clock::now();
+    PreparedScene prepared;
+    if (!probe) prepareScene(*rq.scene, prepared);
+
+    // where partition p's band-layout buffer starts among all of them, in pixels
+    std::vector<uint64_t> partPixel(parts + 1u, 0u);
+    std::vector<uint32_t> partBands(parts, 0u);
+    for (uint32_t p = 0; p < parts; ++p) {
+        partBands[p] = ptr_part_band_count(height, p, parts);
+        partPixel[p + 1u] = partPixel[p] + static_cast<uint64_t>(partBands[p]) * PTR_BAND_ROWS * width;
+    }
+    const size_t bandPixels = partPixel[parts];
+    const int rootDevice = rq.devices[0];
+    const bool wantCov = rq.outCov != nullptr, wantCount = adaptive && rq.outCount != nullptr;
+    // A partition's outputs are one buffer in band layout - rgb, then cov, then count, the last two where they are asked for - so that it
+    // travels to the first device in one transfer.  On the first device: the partitions' buffers one after the other, the word each
+    // output of each partition starts at (k_multi_interleave's table: [output][partition]), and the image-order outputs.
+    const uint32_t covAt = 3u, countAt = wantCov ? 9u : 3u, pixelWords = countAt + (wantCount ? 1u : 0u);
+    std::vector<uint64_t> wordOffset(static_cast<size_t>(parts) * 3u, 0u);
+    for (uint32_t p = 0; p < parts; ++p) {
+        const uint64_t start = partPixel[p] * pixelWords, mine = partPixel[p + 1u] - partPixel[p];
+        wordOffset[p] = start;
+        wordOffset[parts + p] = start + mine * covAt;
+        wordOffset[2u * parts + p] = start + mine * countAt;
+    }
+    DeviceBuffer<float> gathered, image;
+    DeviceBuffer<uint64_t> dWordOffset;
+    HIP_CHECK(hipSetDevice(rootDevice));
+    gathered.ensure(bandPixels * pixelWords);
+    image.ensure(pixels * pixelWords);
+    dWordOffset.upload(wordOffset.data(), wordOffset.size());
+
+    Exchange ex;
+    if (adaptive && parts > 1u) {
+        ex.offset.assign(parts + 1u, 0u);
+        for (uint32_t p = 0; p < parts; ++p) ex.offset[p + 1u] = ex.offset[p] + static_cast<size_t>(partBands[p]) * 2u * width;
+        const size_t bytes = ex.offset.back() * 2u * sizeof(float);
+        HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&ex.host), bytes, hipHostMallocPortable));
+        std::memset(ex.host, 0, bytes);
+    }
+
+    std::vector<std::unique_ptr<PtrDeviceScene>> scenes(parts);
+    std::vector<PtrRenderStats> partStats(parts);
+    std::vector<std::string> errors(parts);
+    std::vector<double> uploadSeconds(parts, 0.0), stateSeconds(parts, 0.0), renderSeconds(parts, 0.0), waitSeconds(parts, 0.0);
+    std::vector<uint64_t> partSamples(parts, 0u);
+    std::vector<uint32_t> partAtMax(parts, 0u), published(parts, 0u);
+    std::atomic<uint32_t> stagedParts{0};
+    ptr::RoundBarrier barrier(parts);
+    PtrAdaptiveInfo info{};   // written by partition 0's thread (every thread computes the same figures)
+    uint32_t sharedCount = 0u;
+    const double setupSeconds = since(t0) - prepared.seconds;   // the first device's buffers and the exchange memory
+
+    auto body = [&](uint32_t p, hipStream_t& stream) {
+        const auto w0 = Clock::now();
+        auto ds = std::make_unique<PtrDeviceScene>();
+        ds->device = rq.devices[p];
+        if (!probe) uploadScene(*rq.scene, prepared, *ds);
+        uploadSeconds[p] = since(w0);
+        HIP_CHECK(hipSetDevice(ds->device));
+        HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+        const MultiPart mp{p, parts, partBands[p], width, height};
+        const size_t myBandPixels = static_cast<size_t>(partPixel[p + 1u] - partPixel[p]);
+        ds->adaptiveOut.ensure(myBandPixels * pixelWords);   // the partition's rgb, cov and count in band layout
+        float* const dRgb = ds->adaptiveOut.ptr;
+        float* const dCov = wantCov ? dRgb + myBandPixels * covAt : nullptr;
+        uint32_t* const dCount = wantCount ? reinterpret_cast<uint32_t*>(dRgb + myBandPixels * countAt) : nullptr;
+
+        auto handOver = [&] {   // the band buffer travels to the first device (the three transports of ptr_render_multi), in one piece
+            if (myBandPixels && sendBandsToRoot(gathered.ptr + wordOffset[p], rootDevice, dRgb, ds->device, myBandPixels * pixelWords * sizeof(float),
+                                                rq.forceStaged[p] != 0, stream)) {
+                stagedParts.fetch_add(1);
+            }
+            HIP_CHECK(hipStreamSynchronize(stream));
+        };
+
+        if (!adaptive) {
+            const auto r0 = Clock::now();
+            if (myBandPixels) renderBands(*ds, rq.settings, rq.spp, p, parts, dRgb, stream, 0, &partStats[p], dCov);
+            std::vector<uint32_t> order;
+            partitionPixels(width, height, p, parts, order);
+            partSamples[p] = static_cast<uint64_t>(order.size()) * rq.spp;
+            handOver();
+            renderSeconds[p] = since(r0);
+            scenes[p] = std::move(ds);
+            return;
+        }
+
+        const PtrAdaptiveParams& params = *rq.params;
+        std::vector<uint32_t> order;
+        partitionPixels(width, height, p, parts, order);
+        const uint32_t local = static_cast<uint32_t>(order.size());
+        const AdaptiveBuffers b = ensureAdaptiveBuffers(*ds, pixels);   // image order: the lists name image pixels, select reads e around them
+        DeviceBuffer<float> edge;
+        edge.ensure(static_cast<size_t>(mp.bands) * 2u * width);
+        const uint64_t maxItems = maxPassItems(*ds);
+        DeviceBuffer<float4> probeSamples, probeItems;
+        PassSource source;
+        if (probe) {
+            probeSamples.upload(reinterpret_cast<const float4*>(rq.samples), static_cast<size_t>(params.maxSpp) * pixels);
+            const uint64_t mostSpp = std::max(params.minSpp, std::min(params.stepSpp, params.maxSpp));
+            probeItems.ensure(static_cast<size_t>(std::max<uint64_t>(local, std::min<uint64_t>(maxItems, static_cast<uint64_t>(local) * mostSpp))));
+            source = [&](uint32_t spp, uint32_t sampleBase, const uint32_t* dList, uint32_t active, PtrRenderStats*, const std::function<void(const float4*)>& consume) {
+                launchMultiGatherItems(probeSamples.ptr, pixels, dList, active, spp, sampleBase, probeItems.ptr, stream);
+                consume(probeItems.ptr);
+                HIP_CHECK(hipGetLastError());
+                HIP_CHECK(hipStreamSynchronize(stream));
+            };
+        } else {
+            source = [&](uint32_t spp, uint32_t sampleBase, const uint32_t* dList, uint32_t active, PtrRenderStats* one, const std::function<void(const float4*)>& consume) {
+                traceItems(*ds, rq.settings, spp, sampleBase, dList, active, stream, one, consume);
+            };
+        }
+        if (local) HIP_CHECK(hipMemcpyAsync(b.lists[0], order.data(), local * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        zeroAdaptiveState(b, pixels, stream);
+        HIP_CHECK(hipStreamSynchronize(stream));   // `order` is pageable host memory
+        stateSeconds[p] = since(w0) - uploadSeconds[p];
+
+        const auto r0 = Clock::now();
+        auto meet = [&]() -> bool {
+            const auto m0 = Clock::now();
+            const bool all = barrier.arriveAndWait();
+            waitSeconds[p] += since(m0);
+            return all;
+        };
+        PtrRenderStats sum{};
+        uint32_t active = local, n = 0u, turn = 0u, rounds = 0u;
+        // PTR_VERBOSE=launches: device events around the two halves of the exchange (tools/multi_adaptive_cost.py parses the line)
+        struct Marks {
+            hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+            ~Marks() {
+                for (hipEvent_t ev : e) if (ev) (void)hipEventDestroy(ev);
+            }
+        } marks;
+        const bool timed = parts > 1u && ptr::readKnobs().verboseLaunches;
+        if (timed) {
+            for (hipEvent_t& ev : marks.e) HIP_CHECK(hipEventCreate(&ev));
+        }
+        const size_t haloBytes = static_cast<size_t>(mp.bands) * 2u * width * sizeof(float);
+        for (bool more = true; more;) {
+            const uint32_t roundSpp = adaptiveRoundSpp(params, n);
+            const uint32_t* list = b.lists[turn];
+            // 1. trace and update; behind the last update the edge rows of e go to the outbox
+            if (active > 0u) {
+                forEachSubPass(maxItems, active, roundSpp, [&](uint32_t done, uint32_t spp, bool last) {
+                    PtrRenderStats one{};
+                    source(spp, n + done, list, active, rq.stats ? &one : nullptr, [&](const float4* items) {
+                        launchAdaptiveUpdate(items, list, active, spp, n + done, last, b.state, stream);
+                        if (last && parts > 1u) {
+                            if (timed) HIP_CHECK(hipEventRecord(marks.e[0], stream));
+                            launchMultiHaloPack(mp, b.state.e, edge.ptr, stream);
+                            HIP_CHECK(hipMemcpyAsync(ex.outbox(p), edge.ptr, haloBytes, hipMemcpyDeviceToHost, stream));
+                            if (timed) HIP_CHECK(hipEventRecord(marks.e[1], stream));
+                        }
+                    });
+                    if (rq.stats) addPassStats(one, sum);
+                });
+                HIP_CHECK(hipStreamSynchronize(stream));   // (the source joined the stream already: the outbox is written)
+                partSamples[p] += static_cast<uint64_t>(active) * roundSpp;
+            }
+            n += roundSpp;
+            if (n >= params.maxSpp) partAtMax[p] = active;
+            // 2. every partition has published
+            if (!meet()) return;
+            // 3. the neighbours' rows, select and compact on the own list, the own total
+            if (active > 0u) {
+                if (parts > 1u) {
+                    multiCollectNeighbourRows(mp, ex.host, ex.offset.data(), ex.inbox(p));
+                    if (timed) HIP_CHECK(hipEventRecord(marks.e[2], stream));
+                    HIP_CHECK(hipMemcpyAsync(edge.ptr, ex.inbox(p), haloBytes, hipMemcpyHostToDevice, stream));
+                    launchMultiHaloUnpack(mp, edge.ptr, b.state.e, stream);
+                    if (timed) HIP_CHECK(hipEventRecord(marks.e[3], stream));
+                }
+                launchAdaptiveSelect(list, active, width, height, b.state, params.maxSpp, params.threshold, b.scratch, b.lists[turn ^ 1u], stream);
+                HIP_CHECK(hipGetLastError());
+                HIP_CHECK(hipMemcpyAsync(&active, b.scratch.total, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+                HIP_CHECK(hipStreamSynchronize(stream));
+                if (timed) {
+                    float outMs = 0.0f, inMs = 0.0f;
+                    HIP_CHECK(hipEventElapsedTime(&outMs, marks.e[0], marks.e[1]));
+                    HIP_CHECK(hipEventElapsedTime(&inMs, marks.e[2], marks.e[3]));
+                    std::fprintf(stderr, "[multi] partition %u round %u: halo %zu bytes each way; pack + copy %.4f ms, copy + unpack %.4f ms\n", p, rounds,
+                                 haloBytes, outMs, inMs);
+                }
+            }
+            published[p] = active;
+            // 4. every total is published; the outboxes may be overwritten again
+            if (!meet()) return;
+            // 5. the same total and the same n on every thread: all leave or all go on
+            uint64_t total = 0u;
+            for (uint32_t q = 0; q < parts; ++q) total += published[q];
+            if (p == 0u) {
+                if (rounds < PTR_ADAPTIVE_INFO_ROUNDS) info.activeAfter[rounds] = static_cast<uint32_t>(total);
+                info.rounds = rounds + 1u;
+                sharedCount = n;
+            }
+            ++rounds;
+            turn ^= 1u;
+            more = total > 0u && n < params.maxSpp;
+        }
+        launchMultiFinishBands(mp, b.state, dRgb, dCov, dCount, stream);
+        HIP_CHECK(hipGetLastError());
+        handOver();
+        renderSeconds[p] = since(r0);
+        partStats[p] = sum;
+        scenes[p] = std::move(ds);
+    };
+
+    // Every way out of a worker but the regular one releases the partitions that wait for it; a worker released that way joins its own
+    // stream and launches nothing more.
+    auto worker = [&](uint32_t p) {
+        hipStream_t stream = nullptr;
+        try {
+            body(p, stream);
+        } catch (const HipError& e) {
+            barrier.fail();
+            errors[p] = e.message;
+        } catch (const std::exception& e) {
+            barrier.fail();
+            errors[p] = std::string("exception: ") + e.what();
+        } catch (...) {
+            barrier.fail();
+            errors[p] = "unknown exception";
+        }
+        if (stream) {
+            (void)hipStreamSynchronize(stream);
+            (void)hipStreamDestroy(stream);
+        }
+    };
+    ptr::runOnThreads(parts, worker, [&] { barrier.fail(); });   // (a thread that could not be started never arrives)
+    for (uint32_t p = 0; p < parts; ++p) {
+        if (!errors[p].empty()) throw HipError{"device " + std::to_string(rq.devices[p]) + ": " + errors[p]};
+    }
+    if (barrier.failed()) throw HipError{"a partition left the frame early"};
+
+    const double partsDone = since(t0);
+    HIP_CHECK(hipSetDevice(rootDevice));
+    float* const iRgb = image.ptr;
+    float* const iCov = image.ptr + pixels * covAt;
+    float* const iCount = image.ptr + pixels * countAt;
+    launchMultiInterleave(gathered.ptr, dWordOffset.ptr, parts, width, height, 3u, iRgb, nullptr);
+    if (wantCov) launchMultiInterleave(gathered.ptr, dWordOffset.ptr + parts, parts, width, height, 6u, iCov, nullptr);
+    if (wantCount) launchMultiInterleave(gathered.ptr, dWordOffset.ptr + 2u * parts, parts, width, height, 1u, iCount, nullptr);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipMemcpy(rq.outRgb, iRgb, pixels * 3u * sizeof(float), hipMemcpyDeviceToHost));
+    if (wantCov) HIP_CHECK(hipMemcpy(rq.outCov, iCov, pixels * 6u * sizeof(float), hipMemcpyDeviceToHost));
+    if (wantCount) HIP_CHECK(hipMemcpy(rq.outCount, iCount, pixels * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (!probe && (rq.outAlbedo || rq.outNormal)) {   // the first partition's scene is on the first device
+        RenderParams rp;
+        fillRenderParams(rq.settings, 1u, rp);
+        DeviceBuffer<float4> albedo, normal;
+        albedo.ensure(pixels);
+        normal.ensure(pixels);
+        launchAovs(rp, scenes[0]->view, 0u, albedo.ptr, normal.ptr, coldLaunchConfig(*scenes[0]), nullptr);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipDeviceSynchronize());
+        if (rq.outAlbedo) albedo.download(reinterpret_cast<float4*>(rq.outAlbedo), pixels);
+        if (rq.outNormal) normal.download(reinterpret_cast<float4*>(rq.outNormal), pixels);
+    }
+    const double gatherSeconds = since(t0) - partsDone;   // interleave, download, feature buffers
+    for (uint32_t p = 0; p < parts; ++p) {
+        if (scenes[p]) {
+            (void)hipSetDevice(scenes[p]->device);
+            scenes[p].reset();
+        }
+    }
+    (void)hipSetDevice(rootDevice);
+    const double wall = since(t0);
+
+    double slowestRender = 0.0, slowestUpload = 0.0;
+    uint64_t samples = 0u;
+    for (uint32_t p = 0; p < parts; ++p) {
+        slowestRender = std::max(slowestRender, renderSeconds[p]);
+        slowestUpload = std::max(slowestUpload, uploadSeconds[p]);
+        samples += partSamples[p];
+        info.pixelsAtMax += partAtMax[p];
+    }
+    info.totalSamples = samples;
+    if (rq.stats) {
+        std::memset(rq.stats, 0, sizeof(*rq.stats));
+        rq.stats->totalSeconds = slowestRender;
+        rq.stats->avgMsPerSample = slowestRender * 1000.0 / std::max(1u, adaptive ? sharedCount : rq.spp);
+        rq.stats->uploadSeconds = prepared.seconds + slowestUpload;
+        for (uint32_t p = 0; p < parts; ++p) addLaunchStats(*rq.stats, partStats[p]);
+        rq.stats->samples = samples;
+    }
+    if (rq.info && adaptive) *rq.info = info;
+    if (rq.multi) {
+        std::memset(rq.multi, 0, sizeof(*rq.multi));
+        rq.multi->parts = parts;
+        rq.multi->stagedParts = stagedParts.load();
+        for (uint32_t p = 0; p < parts; ++p) {
+            rq.multi->partSamples[p] = partSamples[p];
+            rq.multi->partRenderSeconds[p] = renderSeconds[p];
+            rq.multi->partWaitSeconds[p] = waitSeconds[p];
+        }
+    }
+    if (rq.verbose) {
+        std::fprintf(stderr, "[ptr] %u device(s): scene preparation %.3f s, slowest upload %.3f s, slowest render + hand-over %.3f s, whole call %.3f s\n", parts,
+                     prepared.seconds, slowestUpload, slowestRender, wall);
+        // (tools/multi_adaptive_cost.py parses this line; the partitions' threads are what the whole call has beside the other four)
+        std::fprintf(stderr, "[ptr]   outside the partitions' threads: first-device buffers %.4f s, interleave + download %.4f s, release of the scenes %.4f s\n",
+                     setupSeconds, gatherSeconds, wall - partsDone - gatherSeconds);
+        for (uint32_t p = 0; p < parts; ++p) {
+            std::fprintf(stderr, "[ptr]   device %d: %u bands, %llu samples, upload %.4f s, state %.4f s, render %.4f s, of which waiting %.4f s\n", rq.devices[p],
+                         partBands[p], static_cast<unsigned long long>(partSamples[p]), uploadSeconds[p], stateSeconds[p], renderSeconds[p], waitSeconds[p]);
+        }
+    }
+}
+
+// The checks every entry point makes before any device call, then the device list: `ids` (n of them, the debug variants' list) or the
+// first n_devices devices.  Returns the C-ABI's code; 0 with rq.devices filled in.
+int admit(Request& rq, bool pointersOk, const int* ids, int n, bool explicitIds, int nDevices, char* err, size_t cap) {
+    const std::string w(rq.who);
+    std::string bad;
+    if (!pointersOk) bad = w + ": null argument";
+    else if (rq.settings.width == 0u || rq.settings.height == 0u) bad = w + ": render size must be non-zero";
+    else if (rq.params) bad = badAdaptiveParams(rq.who, *rq.params);
+    else if (rq.spp < 2u) bad = w + ": a sample covariance needs spp >= 2";
+    if (bad.empty() && explicitIds && (n < 1 || n > PTR_MULTI_MAX_PARTS)) bad = w + ": the id list must name 1 .. " + std::to_string(PTR_MULTI_MAX_PARTS) + " devices";
+    if (bad.empty() && !explicitIds && nDevices > PTR_MULTI_MAX_PARTS) bad = w + ": at most " + std::to_string(PTR_MULTI_MAX_PARTS) + " devices";
+    if (!bad.empty()) {
+        setErr(err, cap, bad);
+        return 1;
+    }
+    const int available = ptr_device_count();
+    if (available < 1) {
+        setErr(err, cap, w + ": no HIP device (the HIP path has no CPU fallback)");
+        return 2;
+    }
+    if (explicitIds) {
+        for (int i = 0; i < n; ++i) {
+            const int id = ids[i] < 0 ? -(ids[i] + 1) : ids[i];
+            if (id < 0 || id >= available) {
+                setErr(err, cap, w + ": no such HIP device");
+                return 1;
+            }
+            rq.devices.push_back(id);
+            rq.forceStaged.push_back(ids[i] < 0 ? 1 : 0);
+        }
+        return 0;
+    }
+    int count = nDevices <= 0 ? available : nDevices;
+    if (count > available) {
+        setErr(err, cap, w + ": " + std::to_string(count) + " devices requested, " + std::to_string(available) + " visible");
+        return 2;
+    }
+    count = std::min(count, PTR_MULTI_MAX_PARTS);
+    // never more partitions than bands
+    count = static_cast<int>(std::min<uint32_t>(static_cast<uint32_t>(count), std::max(1u, (rq.settings.height + PTR_BAND_ROWS - 1u) / PTR_BAND_ROWS)));
+    for (int i = 0; i < count; ++i) rq.devices.push_back(i);
+    rq.forceStaged.assign(static_cast<size_t>(count), 0);
+    return 0;
+}
+
+int run(const Request& rq, char* err, size_t cap) {
+    try {
+        runFrame(rq);
+        return 0;
+    }
+    PTR_CATCH_ALL(err, cap)
+}
+
+int covFrame(const char* who, const PtrSceneDesc* scene, const PtrSettings* settings, uint32_t spp, const int* ids, int n, bool explicitIds, int nDevices,
+             int verbose, float* outRgb, float* outCov, float* outAlbedo, float* outNormal, PtrRenderStats* stats, PtrMultiInfo* multi, char* err,
+             size_t cap) {
+    Request rq;
+    rq.who = who;
+    const bool ok = scene && settings && outRgb && (!explicitIds || ids);
+    if (ok) rq.settings = *settings;
+    rq.scene = scene;
+    rq.spp = spp;
+    rq.verbose = verbose;
+    rq.outRgb = outRgb, rq.outCov = outCov, rq.outAlbedo = outAlbedo, rq.outNormal = outNormal;
+    rq.stats = stats, rq.multi = multi;
+    if (const int rc = admit(rq, ok, ids, n, explicitIds, nDevices, err, cap)) return rc;
+    return run(rq, err, cap);
+}
+
+int adaptiveFrame(const char* who, const PtrSceneDesc* scene, const PtrSettings* settings, const PtrAdaptiveParams* params, const int* ids, int n,
+                  bool explicitIds, int nDevices, int verbose, float* outRgb, float* outCov, uint32_t* outCount, float* outAlbedo, float* outNormal,
+                  PtrRenderStats* stats, PtrAdaptiveInfo* info, PtrMultiInfo* multi, char* err, size_t cap) {
+    Request rq;
+    rq.who = who;
+    const bool ok = scene && settings && params && outRgb && (!explicitIds || ids);
+    if (ok) rq.settings = *settings;
+    rq.scene = scene;
+    rq.params = ok ? params : nullptr;
+    rq.verbose = verbose;
+    rq.outRgb = outRgb, rq.outCov = outCov, rq.outCount = outCount, rq.outAlbedo = outAlbedo, rq.outNormal = outNormal;
+    rq.stats = stats, rq.info = info, rq.multi = multi;
+    if (const int rc = admit(rq, ok, ids, n, explicitIds, nDevices, err, cap)) return rc;
+    return run(rq, err, cap);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ptr_render_multi_cov(const PtrSceneDesc* scene, const PtrSettings* settings, uint32_t spp, int n_devices, int verbose, float* out_rgb,
+                         float* out_cov, float* out_albedo, float* out_normal, PtrRenderStats* stats, PtrMultiInfo* multi_info, char* err,
+                         size_t err_cap) {
+    return covFrame("ptr_render_multi_cov", scene, settings, spp, nullptr, 0, false, n_devices, verbose, out_rgb, out_cov, out_albedo, out_normal, stats,
+                    multi_info, err, err_cap);
+}
+
+int ptr_render_multi_adaptive(const PtrSceneDesc* scene, const PtrSettings* settings, const PtrAdaptiveParams* params, int n_devices,
+                              int verbose, float* out_rgb, float* out_cov, uint32_t* out_count, float* out_albedo, float* out_normal,
+                              PtrRenderStats* stats, PtrAdaptiveInfo* adaptive_info, PtrMultiInfo* multi_info, char* err, size_t err_cap) {
+    return adaptiveFrame("ptr_render_multi_adaptive", scene, settings, params, nullptr, 0, false, n_devices, verbose, out_rgb, out_cov, out_count, out_albedo,
+                         out_normal, stats, adaptive_info, multi_info, err, err_cap);
+}
+
+int ptr_multi_debug_cov_on(const PtrSceneDesc* scene, const PtrSettings* settings, uint32_t spp, const int* device_ids, int n,
+                           float* out_rgb, float* out_cov, float* out_albedo, float* out_normal, PtrRenderStats* stats,
+                           PtrMultiInfo* multi_info, char* err, size_t err_cap) {
+    return covFrame("ptr_multi_debug_cov_on", scene, settings, spp, device_ids, n, true, 0, 0, out_rgb, out_cov, out_albedo, out_normal, stats, multi_info, err,
+                    err_cap);
+}
+
+int ptr_multi_debug_adaptive_on(const PtrSceneDesc* scene, const PtrSettings* settings, const PtrAdaptiveParams* params,
+                                const int* device_ids, int n, float* out_rgb, float* out_cov, uint32_t* out_count, float* out_albedo,
+                                float* out_normal, PtrRenderStats* stats, PtrAdaptiveInfo* adaptive_info, PtrMultiInfo* multi_info,
+                                char* err, size_t err_cap) {
+    return adaptiveFrame("ptr_multi_debug_adaptive_on", scene, settings, params, device_ids, n, true, 0, 0, out_rgb, out_cov, out_count, out_albedo, out_normal,
+                         stats, adaptive_info, multi_info, err, err_cap);
+}
+
+int ptr_multi_debug_adaptive_frame(uint32_t width, uint32_t height, const PtrAdaptiveParams* params, const float* samples,
+                                   const int* device_ids, int n, float* out_rgb, float* out_cov, uint32_t* out_count,
+                                   PtrAdaptiveInfo* adaptive_info, char* err, size_t err_cap) {
+    Request rq;
+    rq.who = "ptr_multi_debug_adaptive_frame";
+    const bool ok = params && samples && device_ids && out_rgb;
+    rq.settings.width = width;
+    rq.settings.height = height;
+    if (!ok) rq.settings.width = rq.settings.height = 1u;   // (the null argument is reported first)
+    rq.params = ok ? params : nullptr;
+    rq.samples = samples;
+    rq.outRgb = out_rgb, rq.outCov = out_cov, rq.outCount = out_count;
+    rq.info = adaptive_info;
+    if (const int rc = admit(rq, ok, device_ids, n, true, 0, err, err_cap)) return rc;
+    return run(rq, err, err_cap);
+}
+
+}  // extern "C"

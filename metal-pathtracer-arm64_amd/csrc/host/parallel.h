@@ -14,9 +14,10 @@
 
 namespace ptr {
 
-// fn(k) for k in [0, n): k = 0 on the calling thread, the others on threads of their own.
-template <typename Fn>
-void runOnThreads(uint32_t n, Fn&& fn) {
+// fn(k) for k in [0, n): k = 0 on the calling thread, the others on threads of their own.  onShort() runs before fn(0) when not every
+// thread could be started: workers that wait for each other (multi.cpp's round barrier) are told there that some will never come.
+template <typename Fn, typename OnShort>
+void runOnThreads(uint32_t n, Fn&& fn, OnShort&& onShort) {
     if (n <= 1u) {
         if (n == 1u) fn(0u);
         return;
@@ -40,11 +41,17 @@ void runOnThreads(uint32_t n, Fn&& fn) {
         if (!first) first = std::current_exception();
     }
     const uint32_t started = static_cast<uint32_t>(pool.size()) + 1u;
+    if (started < n) onShort();
     body(0u);
     for (std::thread& th : pool) th.join();
     if (first) std::rethrow_exception(first);
     // (shares k >= started were never run: only reachable together with the exception rethrown above)
     (void)started;
+}
+
+template <typename Fn>
+void runOnThreads(uint32_t n, Fn&& fn) {
+    runOnThreads(n, fn, [] {});
 }
 
 // The same contract on threads that are kept: a BVH build over tens of millions of primitives runs a few hundred passes of a few
