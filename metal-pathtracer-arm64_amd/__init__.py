@@ -394,6 +394,38 @@ _MULTI_SIGNATURES = {
 }
 MULTI_SYMBOLS = tuple(_MULTI_SIGNATURES)
 
+
+
+class PtrFrameInfo(C.Structure):
+    """include/ptr_frame.h PtrFrameInfo."""
+    _fields_ = [
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("minCount", C.c_uint32),
+        ("maxCount", C.c_uint32),
+        ("totalSamples", C.c_uint64),
+        ("uniform", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+# ... and of include/ptr_frame.h (resumable frames): tests/test_frame_host.py holds it against that header
+_frame_info = C.POINTER(PtrFrameInfo)
+_FRAME_SIGNATURES = {
+    "ptr_frame_create": (_int, [_vp, _settings, C.POINTER(_vp)] + _err),
+    "ptr_frame_release": (None, [_vp]),
+    "ptr_frame_reset": (_int, [_vp, _settings] + _err),
+    "ptr_frame_accumulate": (_int, [_vp, _u32, _vp, _stats] + _err),
+    "ptr_frame_refine": (_int, [_vp, _adaptive, _vp, _stats, _adaptive_info] + _err),
+    "ptr_frame_resolve_device": (_int, [_vp, _vp, _vp, _vp, _vp] + _err),
+    "ptr_frame_resolve": (_int, [_vp, _fp, _fp, _up] + _err),
+    "ptr_frame_info": (_int, [_vp, _frame_info]),
+    "ptr_frame_export": (_int, [_vp, _fp, _fp, _fp, _up, _fp] + _err),
+    "ptr_frame_import": (_int, [_vp, _fp, _fp, _fp, _up, _fp] + _err),
+    "ptr_frame_debug_create": (_int, [_u32, _u32, _fp, _u32, _int, C.POINTER(_vp)] + _err),
+}
+FRAME_SYMBOLS = tuple(_FRAME_SIGNATURES)
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -411,7 +443,7 @@ def load_library() -> C.CDLL:
         raise PtrError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` first")
     lib = C.CDLL(path)
     for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_POST_SIGNATURES.items()) + list(_STATS_SIGNATURES.items()) + \
-            list(_ADAPTIVE_SIGNATURES.items()) + list(_MULTI_SIGNATURES.items()):
+            list(_ADAPTIVE_SIGNATURES.items()) + list(_MULTI_SIGNATURES.items()) + list(_FRAME_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -654,6 +686,13 @@ class DeviceScene:
                                                          C.byref(stats) if want_stats else None, C.byref(info), err, len(err)), err)
         return (stats if want_stats else None), info
 
+    def frame(self, settings: PtrSettings) -> "Frame":
+        """A resumable frame on this scene (include/ptr_frame.h): its per-pixel sample state stays on the device between calls."""
+        h = C.c_void_p()
+        err = _err_buf()
+        _check(load_library().ptr_frame_create(self._h, C.byref(settings), C.byref(h), err, len(err)), err)
+        return Frame(h, keepalive=self)
+
     def render_aovs(self, settings: PtrSettings, sample_index: int = 0) -> Tuple[np.ndarray, np.ndarray]:
         """First-hit feature buffers: ([H, W, 4] albedo rgb | hit flag, [H, W, 4] encoded normal | distance)."""
         albedo = np.zeros((settings.height, settings.width, 4), dtype=np.float32)
@@ -785,6 +824,109 @@ class DeviceScene:
             self.close()
         except Exception:
             pass
+
+
+FRAME_STATE = (("sum", 3, np.float32), ("mean", 3, np.float32), ("m", 6, np.float32), ("n", 0, np.uint32), ("e", 0, np.float32))
+
+
+class Frame:
+    """include/ptr_frame.h: the sample state of a frame, continued call by call; made by DeviceScene.frame() or debug_frame().  It keeps
+    its scene alive (a scene closed by hand must be closed after its frames)."""
+
+    def __init__(self, handle: C.c_void_p, keepalive=None):
+        self._h = handle
+        self._keepalive = keepalive
+
+    def _handle(self):
+        if not self._h:
+            raise PtrError("the frame is closed")
+        return self._h
+
+    def accumulate(self, spp: int, stream: int = 0) -> PtrRenderStats:
+        """Every pixel gets `spp` more samples (the frame must be uniform)."""
+        stats = PtrRenderStats()
+        err = _err_buf()
+        _check(load_library().ptr_frame_accumulate(self._handle(), spp, C.c_void_p(stream or None), C.byref(stats), err, len(err)), err)
+        return stats
+
+    def refine(self, params: PtrAdaptiveParams, stream: int = 0) -> Tuple[PtrRenderStats, PtrAdaptiveInfo]:
+        """The resumable adaptive loop: pixels whose dilated error is above params.threshold go on, each from its own count, up to
+        params.maxSpp.  Returns (stats, info) of this call."""
+        stats, info = PtrRenderStats(), PtrAdaptiveInfo()
+        err = _err_buf()
+        _check(load_library().ptr_frame_refine(self._handle(), C.byref(params), C.c_void_p(stream or None), C.byref(stats), C.byref(info), err,
+                                               len(err)), err)
+        return stats, info
+
+    def info(self) -> PtrFrameInfo:
+        out = PtrFrameInfo()
+        if load_library().ptr_frame_info(self._handle(), C.byref(out)) != 0:
+            raise PtrError("ptr_frame_info failed")
+        return out
+
+    def resolve(self, want_cov: bool = True, want_count: bool = True) -> Tuple[np.ndarray, Optional[np.ndarray], Optional[np.ndarray]]:
+        """([H, W, 3] image, [H, W, 6] covariance of the pixel means, [H, W] uint32 samples per pixel), image order; the state stays."""
+        i = self.info()
+        rgb = np.zeros((i.height, i.width, 3), dtype=np.float32)
+        cov = np.zeros((i.height, i.width, 6), dtype=np.float32) if want_cov else None
+        count = np.zeros((i.height, i.width), dtype=np.uint32) if want_count else None
+        err = _err_buf()
+        _check(load_library().ptr_frame_resolve(self._handle(), _fptr(rgb), _fptr(cov) if want_cov else None, _uptr(count) if want_count else None,
+                                                err, len(err)), err)
+        return rgb, cov, count
+
+    def resolve_device(self, d_rgb: int, d_cov: int = 0, d_count: int = 0, stream: int = 0) -> None:
+        """resolve() into caller-owned DEVICE buffers (W*H*3 floats, W*H*6 floats or 0, W*H uint32 or 0) on `stream`."""
+        err = _err_buf()
+        _check(load_library().ptr_frame_resolve_device(self._handle(), C.c_void_p(d_rgb), C.c_void_p(d_cov or None), C.c_void_p(d_count or None),
+                                                       C.c_void_p(stream or None), err, len(err)), err)
+
+    def export_state(self) -> dict:
+        """The checkpoint: {"sum" [P, 3], "mean" [P, 3], "m" [P, 6], "n" [P] uint32, "e" [P]}, image order."""
+        i = self.info()
+        pixels = i.width * i.height
+        st = {k: np.zeros((pixels, cols) if cols else pixels, dtype=dt) for k, cols, dt in FRAME_STATE}
+        err = _err_buf()
+        _check(load_library().ptr_frame_export(self._handle(), _fptr(st["sum"]), _fptr(st["mean"]), _fptr(st["m"]), _uptr(st["n"]), _fptr(st["e"]),
+                                               err, len(err)), err)
+        return st
+
+    def import_state(self, state: dict) -> None:
+        i = self.info()
+        pixels = i.width * i.height
+        st = {k: np.ascontiguousarray(state[k], dtype=dt).reshape((pixels, cols) if cols else pixels) for k, cols, dt in FRAME_STATE}
+        err = _err_buf()
+        _check(load_library().ptr_frame_import(self._handle(), _fptr(st["sum"]), _fptr(st["mean"]), _fptr(st["m"]), _uptr(st["n"]), _fptr(st["e"]),
+                                               err, len(err)), err)
+
+    def reset(self, settings: Optional[PtrSettings] = None) -> None:
+        """The state back to zero; `settings` of the same size replace the stored ones."""
+        err = _err_buf()
+        _check(load_library().ptr_frame_reset(self._handle(), C.byref(settings) if settings is not None else None, err, len(err)), err)
+
+    def close(self) -> None:
+        if self._h:
+            load_library().ptr_frame_release(self._h)
+            self._h = None
+        self._keepalive = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def debug_frame(samples: np.ndarray, device: int = 0) -> Frame:
+    """ptr_frame_debug_create (tests): a frame without a scene whose samples are `samples` [S, H, W, 3 or 4]."""
+    samples = np.asarray(samples, dtype=np.float32)
+    count, h, w = samples.shape[:3]
+    x4 = np.zeros((count, h, w, 4), dtype=np.float32)
+    x4[..., :3] = samples[..., :3]
+    handle = C.c_void_p()
+    err = _err_buf()
+    _check(load_library().ptr_frame_debug_create(w, h, _fptr(x4), count, device, C.byref(handle), err, len(err)), err)
+    return Frame(handle)
 
 
 def render_multi(desc: PtrSceneDesc, settings: PtrSettings, spp: int, n_devices: int = 0, device_ids=None, verbose: bool = False

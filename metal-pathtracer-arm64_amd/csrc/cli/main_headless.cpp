@@ -55,6 +55,7 @@ struct CliOptions {
     float adaptiveThreshold = 0.0f;  // --adaptive=<threshold>
     bool adaptiveThresholdSet = false;
     uint32_t adaptiveMinSpp = 0, adaptiveStep = 0;   // --adaptiveMinSpp / --adaptiveStep (0 = the default)
+    std::vector<uint32_t> snapshots; // --snapshots: also write the image at these samples per pixel on the way to --sppTotal (include/ptr_frame.h)
     uint32_t backendSemantics = 0;   // what --backend / --enableEmbree imply; an explicit --semantics overrides it
     bool semanticsSet = false;
     std::string formatString = "exr";
@@ -120,6 +121,10 @@ void printUsage(const char* exe) {
               << "                                --sppTotal samples (default threshold 0.05; needs --devices=1)\n"
               << "  --adaptiveMinSpp=<n>          Samples of the first round of --adaptive (>= 2, default 8)\n"
               << "  --adaptiveStep=<n>            Samples of every later round of --adaptive (>= 1, default 8)\n"
+              << "  --snapshots=<n1,n2,...>       Also write the image at n1, n2, ... samples per pixel on the way to --sppTotal, next to\n"
+              << "                                --output as <stem>.<n><ext> (strictly ascending, each >= 2 and below --sppTotal; the frame\n"
+              << "                                is continued, not rendered again; snapshots are not denoised; needs --devices=1, not\n"
+              << "                                with --adaptive)\n"
               << "  --verbose                     Print progress\n"
               << "  --help                        Show this message\n";
 }
@@ -293,6 +298,26 @@ bool parseOptions(int argc, const char** argv, CliOptions& o, std::string& error
             if (!intArg("--adaptiveMinSpp", 2, o.adaptiveMinSpp, nullptr)) return false;
         } else if (arg == "--adaptiveStep") {
             if (!intArg("--adaptiveStep", 1, o.adaptiveStep, nullptr)) return false;
+        } else if (arg == "--snapshots") {
+            if (!need("--snapshots")) return false;
+            o.snapshots.clear();
+            for (size_t at = 0; at <= value.size();) {
+                const size_t comma = std::min(value.find(',', at), value.size());
+                const std::string item = value.substr(at, comma - at);
+                size_t used = 0;
+                unsigned long n = 0;
+                try {
+                    n = std::stoul(item, &used);
+                } catch (...) {
+                    used = 0;
+                }
+                if (item.empty() || used != item.size() || item[0] == '-' || n > 0xFFFFFFFFul) {
+                    error = "Invalid value for --snapshots (expected a comma-separated list of sample counts)";
+                    return false;
+                }
+                o.snapshots.push_back(static_cast<uint32_t>(n));
+                at = comma + 1;
+            }
         } else if (arg == "--semantics") {
             if (!need("--semantics")) return false;
             if (value == "metal") {
@@ -356,6 +381,12 @@ bool parseOptions(int argc, const char** argv, CliOptions& o, std::string& error
         error = "--adaptive requires --sppTotal (the most samples a pixel gets) >= --adaptiveMinSpp";
         return false;
     }
+    for (size_t i = 0; i < o.snapshots.size(); ++i) {
+        if (o.snapshots[i] < 2u || o.snapshots[i] >= o.sppTotal || (i > 0 && o.snapshots[i] <= o.snapshots[i - 1])) {
+            error = "--snapshots must be strictly ascending, each >= 2 and below --sppTotal";
+            return false;
+        }
+    }
     if (!ptr::ParseImageFileFormat(o.formatString, o.format)) {
         error = "Unknown format: " + o.formatString;
         return false;
@@ -391,6 +422,15 @@ int main(int argc, const char** argv) {
 
     if (options.adaptive && options.devices != 1u) {
         std::cerr << "Error: --adaptive renders on one device; it cannot be combined with --devices=" << options.devices << std::endl;
+        return 1;
+    }
+
+    if (!options.snapshots.empty() && options.adaptive) {
+        std::cerr << "Error: --snapshots continues a uniform frame; it cannot be combined with --adaptive" << std::endl;
+        return 1;
+    }
+    if (!options.snapshots.empty() && options.devices != 1u) {
+        std::cerr << "Error: --snapshots renders on one device; it cannot be combined with --devices=" << options.devices << std::endl;
         return 1;
     }
 
@@ -465,6 +505,47 @@ int main(int argc, const char** argv) {
         if (options.adaptiveStep) adaptiveParams.stepSpp = options.adaptiveStep;
         hipRenderer->setAdaptive(&adaptiveParams);
     }
+    // where the image goes (the default name carries the size), and how a linear image is written there
+    auto outputPathFor = [&](uint32_t width, uint32_t height) {
+        if (!options.outputPath.empty()) return options.outputPath;
+        std::ostringstream name;
+        name << sanitizeSceneName(options.scene) << "_" << width << "x" << height << "." << ptr::FormatExtension(options.format);
+        return (fs::path("renders") / name.str()).string();
+    };
+    auto writeImageFile = [&](const fs::path& path, const float* linearRGB, uint32_t width, uint32_t height, std::string& writeError) {
+        if (!path.parent_path().empty()) {
+            std::error_code ec;
+            fs::create_directories(path.parent_path(), ec);
+        }
+        if (options.format == ptr::ImageFileFormat::EXR && options.rgbaExr) {
+            std::vector<float> rgba(static_cast<size_t>(width) * height * 4u, 1.0f);
+            for (size_t i = 0; i < static_cast<size_t>(width) * height; ++i) {
+                rgba[i * 4 + 0] = linearRGB[i * 3 + 0];
+                rgba[i * 4 + 1] = linearRGB[i * 3 + 1];
+                rgba[i * 4 + 2] = linearRGB[i * 3 + 2];
+            }
+            return ptr::WriteExrRgba(path.string(), rgba.data(), width, height, "Linear sRGB", &writeError);
+        }
+        ptr::TonemapSettings tm;
+        tm.tonemapMode = settings.tonemapMode;
+        tm.acesVariant = settings.acesVariant;
+        tm.exposure = settings.exposure;
+        tm.reinhardWhitePoint = settings.reinhardWhitePoint;
+        return ptr::WriteImage(path.string(), options.format, linearRGB, width, height, tm, &writeError);
+    };
+    if (!options.snapshots.empty()) {
+        // <stem>.<n><ext> next to the output, in its format and with its tonemap options
+        hipRenderer->setSnapshots(options.snapshots, [&](uint32_t spp, uint32_t width, uint32_t height, const float* linearRGB, std::string& sinkError) {
+            const fs::path out(outputPathFor(width, height));
+            const fs::path path = out.parent_path() / (out.stem().string() + "." + std::to_string(spp) + out.extension().string());
+            if (!writeImageFile(path, linearRGB, width, height, sinkError)) {
+                sinkError = "failed to write snapshot " + path.string() + ": " + sinkError;
+                return false;
+            }
+            std::cout << "Snapshot at " << spp << " spp written to: " << path << std::endl;
+            return true;
+        });
+    }
     const ptr::HipHeadlessRenderer* const hip = hipRenderer.get();
     std::unique_ptr<ptr::IHeadlessRenderer> renderer = std::move(hipRenderer);
     ptr::HeadlessRenderOutput output;
@@ -474,37 +555,10 @@ int main(int argc, const char** argv) {
         return 1;
     }
 
-    std::string outputPath = options.outputPath;
-    if (outputPath.empty()) {
-        std::ostringstream name;
-        name << sanitizeSceneName(options.scene) << "_" << output.width << "x" << output.height << "."
-             << ptr::FormatExtension(options.format);
-        outputPath = (fs::path("renders") / name.str()).string();
-    }
+    const std::string outputPath = outputPathFor(output.width, output.height);
     const fs::path outFs(outputPath);
-    if (!outFs.parent_path().empty()) {
-        std::error_code ec;
-        fs::create_directories(outFs.parent_path(), ec);
-    }
-
     std::string writeError;
-    bool ok;
-    if (options.format == ptr::ImageFileFormat::EXR && options.rgbaExr) {
-        std::vector<float> rgba(static_cast<size_t>(output.width) * output.height * 4u, 1.0f);
-        for (size_t i = 0; i < static_cast<size_t>(output.width) * output.height; ++i) {
-            rgba[i * 4 + 0] = output.linearRGB[i * 3 + 0];
-            rgba[i * 4 + 1] = output.linearRGB[i * 3 + 1];
-            rgba[i * 4 + 2] = output.linearRGB[i * 3 + 2];
-        }
-        ok = ptr::WriteExrRgba(outputPath, rgba.data(), output.width, output.height, "Linear sRGB", &writeError);
-    } else {
-        ptr::TonemapSettings tm;
-        tm.tonemapMode = settings.tonemapMode;
-        tm.acesVariant = settings.acesVariant;
-        tm.exposure = settings.exposure;
-        tm.reinhardWhitePoint = settings.reinhardWhitePoint;
-        ok = ptr::WriteImage(outputPath, options.format, output.linearRGB.data(), output.width, output.height, tm, &writeError);
-    }
+    const bool ok = writeImageFile(outFs, output.linearRGB.data(), output.width, output.height, writeError);
     if (!ok) {
         std::cerr << "Failed to write output image: " << writeError << std::endl;
         return 1;

@@ -105,6 +105,59 @@ bool HipHeadlessRenderer::render(const HeadlessScene& scene, const HeadlessCamer
             std::fprintf(stderr, "adaptive: %u rounds, %.2f samples per pixel on average, %u pixels at %u spp\n", m_adaptiveInfo.rounds,
                          static_cast<double>(m_adaptiveInfo.totalSamples) / static_cast<double>(pixels), m_adaptiveInfo.pixelsAtMax, spp);
         }
+    } else if (!m_snapshots.empty()) {
+        if (m_devices != 1) {
+            error = "snapshots are taken of a frame rendered on one device (--devices=1)";
+            return false;
+        }
+        // one upload serves the frame, its snapshots and, where asked for, the first-hit feature buffers
+        PtrDeviceScene* ds = nullptr;
+        if (ptr_scene_upload(&desc, 0, &ds, err, sizeof(err)) != 0) {
+            error = err[0] ? err : "HIP scene upload failed";
+            return false;
+        }
+        const size_t pixels = static_cast<size_t>(ps.width) * ps.height;
+        PtrFrame* frame = nullptr;
+        bool ok = ptr_frame_create(ds, &ps, &frame, err, sizeof(err)) == 0;
+        std::vector<uint32_t> stops = m_snapshots;
+        stops.push_back(spp);
+        uint32_t done = 0u;
+        for (size_t i = 0; ok && i < stops.size(); ++i) {
+            if (stops[i] <= done) {
+                std::snprintf(err, sizeof(err), "snapshot counts must ascend and stay below the frame's samples per pixel");
+                ok = false;
+                break;
+            }
+            PtrRenderStats one{};
+            ok = ptr_frame_accumulate(frame, stops[i] - done, nullptr, &one, err, sizeof(err)) == 0;
+            if (!ok) break;
+            done = stops[i];
+            m_stats.totalSeconds += one.totalSeconds;
+            m_stats.samples += one.samples;
+            const bool last = i + 1u == stops.size();
+            if (last && sampleVariance) cov.resize(pixels * 6u);
+            ok = ptr_frame_resolve(frame, out.linearRGB.data(), last && sampleVariance ? cov.data() : nullptr, nullptr, err, sizeof(err)) == 0;
+            if (ok && !last) {
+                std::string sinkError;
+                if (m_snapshotSink && !m_snapshotSink(done, ps.width, ps.height, out.linearRGB.data(), sinkError)) {
+                    std::snprintf(err, sizeof(err), "%s", sinkError.c_str());
+                    ok = false;
+                }
+                if (ok && verbose) std::fprintf(stderr, "snapshot: %u spp after %.3f s\n", done, m_stats.totalSeconds);
+            }
+        }
+        m_stats.avgMsPerSample = m_stats.totalSeconds * 1000.0 / spp;
+        ptr_frame_release(frame);
+        if (ok && captureAovs) {
+            m_aovAlbedo.assign(pixels * 4u, 0.0f);
+            m_aovNormal.assign(pixels * 4u, 0.0f);
+            ok = ptr_render_aovs(ds, &ps, 0u, m_aovAlbedo.data(), m_aovNormal.data(), err, sizeof(err)) == 0;
+        }
+        ptr_scene_release(ds);
+        if (!ok) {
+            error = err[0] ? err : "HIP render failed";
+            return false;
+        }
     } else if (m_devices != 1) {
         // the frame in interleaved bands over several devices of the node, gathered on the first one
         if (ptr_render_multi(&desc, &ps, spp, m_devices, verbose ? 1 : 0, out.linearRGB.data(), &m_stats, err, sizeof(err)) != 0) {
@@ -117,7 +170,7 @@ bool HipHeadlessRenderer::render(const HeadlessScene& scene, const HeadlessCamer
             return false;
         }
     }
-    if (captureAovs && !m_adaptive) {
+    if (captureAovs && !m_adaptive && m_snapshots.empty()) {
         // one upload serves the frame (single device) and the first-hit feature buffers
         PtrDeviceScene* ds = nullptr;
         if (ptr_scene_upload(&desc, 0, &ds, err, sizeof(err)) != 0) {

@@ -4,10 +4,12 @@
 #pragma once
 
 #include <cstdint>
+#include <functional>
 #include <string>
 #include <vector>
 
 #include "ptr_adaptive.h"
+#include "ptr_frame.h"
 #include "ptr_post.h"
 #include "ptr_stats.h"
 #include "render_settings.h"
@@ -81,7 +83,18 @@ public:
     const std::vector<uint32_t>& sampleCounts() const { return m_sampleCounts; }
     const PtrAdaptiveInfo& lastAdaptiveInfo() const { return m_adaptiveInfo; }
 
+    // render the frame through a PtrFrame (include/ptr_frame.h; one device, not adaptive) and hand `sink` the raw resolved image - linear
+    // RGB, width*height*3 floats - at each of `counts` samples per pixel on the way to sppTotal (strictly ascending, each below sppTotal);
+    // a false return of the sink ends the render with its message.  Empty = off: --snapshots of the CLI
+    using SnapshotSink = std::function<bool(uint32_t spp, uint32_t width, uint32_t height, const float* linearRGB, std::string& error)>;
+    void setSnapshots(const std::vector<uint32_t>& counts, SnapshotSink sink) {
+        m_snapshots = counts;
+        m_snapshotSink = std::move(sink);
+    }
+
 private:
+    std::vector<uint32_t> m_snapshots;
+    SnapshotSink m_snapshotSink;
     PtrRenderStats m_stats{};
     int m_devices = 1;
     bool m_captureAovs = false;

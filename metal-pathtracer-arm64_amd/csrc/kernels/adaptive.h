@@ -112,8 +112,35 @@ struct AdaptiveScratch {
 };
 void launchAdaptiveSelect(const uint32_t* dList, uint32_t activeCount, uint32_t width, uint32_t height, const AdaptiveState& state, uint32_t maxSpp,
                           float threshold, const AdaptiveScratch& scratch, uint32_t* dNext, hipStream_t stream);
+// The stable compaction alone (k_adaptive_scan, k_adaptive_scatter), for a caller that wrote the keep flags dKeep[activeCount] and the
+// per-block counts scratch.blockCounts itself (frame.hip): dNext receives the kept entries of dList in order, *scratch.total their number.
+void launchAdaptiveCompact(const uint32_t* dList, uint32_t activeCount, const uint8_t* dKeep, const AdaptiveScratch& scratch, uint32_t* dNext,
+                           hipStream_t stream);
 // rgb = sum / n, cov = M / (n (n - 1)), count = n for every pixel of the image (dCov and dCount may be null)
 void launchAdaptiveFinish(const AdaptiveState& state, uint32_t pixels, float* dRgb, float* dCov, uint32_t* dCount, hipStream_t stream);
+#endif
+
+#if defined(__HIP__)
+// Device code of the compaction kernels (adaptive.hip, frame.hip), 256 threads per block.
+constexpr uint32_t kCompactBlock = 256u;
+constexpr uint32_t kCompactWaves = kCompactBlock / 64u;
+
+// The rank of this thread's kept entry among the block's kept entries, and in blockTotal their number (every thread of the block calls).
+__device__ inline uint32_t blockRank(bool keep, uint32_t* waveCounts, uint32_t& blockTotal) {
+    const uint64_t votes = __ballot(keep);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (lane == 0u) waveCounts[wave] = static_cast<uint32_t>(__popcll(votes));
+    __syncthreads();
+    uint32_t before = 0u, total = 0u;
+#pragma unroll
+    for (uint32_t w = 0; w < kCompactWaves; ++w) {
+        const uint32_t cnt = waveCounts[w];
+        if (w < wave) before += cnt;
+        total += cnt;
+    }
+    blockTotal = total;
+    return before + static_cast<uint32_t>(__popcll(votes & ((1ull << lane) - 1ull)));
+}
 #endif
 
 }  // namespace ptrk

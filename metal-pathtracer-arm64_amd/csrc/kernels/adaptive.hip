@@ -17,8 +17,8 @@ namespace ptrk {
 namespace {
 
 constexpr uint32_t kUpdateUnroll = 4u;
-constexpr uint32_t kBlock = 256u;
-constexpr uint32_t kWaves = kBlock / 64u;
+constexpr uint32_t kBlock = kCompactBlock;
+constexpr uint32_t kWaves = kCompactWaves;
 
 __global__ void __launch_bounds__(kBlock) k_adaptive_update(const float4* __restrict__ items, const uint32_t* __restrict__ list, uint32_t activeCount,
                                                             uint32_t spp, uint32_t nBefore, uint32_t last, AdaptiveState st) {
@@ -45,23 +45,6 @@ __global__ void __launch_bounds__(kBlock) k_adaptive_update(const float4* __rest
     const uint32_t n = nBefore + spp;
     st.n[pixel] = n;
     if (last) st.e[pixel] = p.error(n);
-}
-
-// The rank of this thread's kept entry among the block's kept entries, and in blockTotal their number (every thread of the block calls).
-__device__ inline uint32_t blockRank(bool keep, uint32_t* waveCounts, uint32_t& blockTotal) {
-    const uint64_t votes = __ballot(keep);
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (lane == 0u) waveCounts[wave] = static_cast<uint32_t>(__popcll(votes));
-    __syncthreads();
-    uint32_t before = 0u, total = 0u;
-#pragma unroll
-    for (uint32_t w = 0; w < kWaves; ++w) {
-        const uint32_t cnt = waveCounts[w];
-        if (w < wave) before += cnt;
-        total += cnt;
-    }
-    blockTotal = total;
-    return before + static_cast<uint32_t>(__popcll(votes & ((1ull << lane) - 1ull)));
 }
 
 __global__ void __launch_bounds__(kBlock) k_adaptive_select(const uint32_t* __restrict__ list, uint32_t activeCount, uint32_t width, uint32_t height,
@@ -151,9 +134,15 @@ void launchAdaptiveSelect(const uint32_t* dList, uint32_t activeCount, uint32_t 
         hipLaunchKernelGGL(k_adaptive_select, dim3(blocks), dim3(kBlock), 0, stream, dList, activeCount, width, height, state.e, state.n, maxSpp, threshold,
                            scratch.keep, scratch.blockCounts);
     }
+    launchAdaptiveCompact(dList, activeCount, scratch.keep, scratch, dNext, stream);
+}
+
+void launchAdaptiveCompact(const uint32_t* dList, uint32_t activeCount, const uint8_t* dKeep, const AdaptiveScratch& scratch, uint32_t* dNext,
+                           hipStream_t stream) {
+    const uint32_t blocks = blocksFor(activeCount);
     hipLaunchKernelGGL(k_adaptive_scan, dim3(1), dim3(kBlock), 0, stream, scratch.blockCounts, blocks, scratch.blockOffsets, scratch.total);
     if (blocks > 0u) {
-        hipLaunchKernelGGL(k_adaptive_scatter, dim3(blocks), dim3(kBlock), 0, stream, dList, activeCount, scratch.keep, scratch.blockOffsets, dNext);
+        hipLaunchKernelGGL(k_adaptive_scatter, dim3(blocks), dim3(kBlock), 0, stream, dList, activeCount, dKeep, scratch.blockOffsets, dNext);
     }
 }
 
