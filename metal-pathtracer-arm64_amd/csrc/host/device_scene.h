@@ -89,6 +89,8 @@ inline float bitsToFloat(uint32_t u) {
 
 }  // namespace ptrhost
 
+#include "adaptive_state.h"   // AdaptiveStore, which needs DeviceBuffer and which PtrDeviceScene holds
+
 using ptrhost::DeviceBuffer;
 
 struct PtrDeviceScene {
@@ -147,10 +149,7 @@ struct PtrDeviceScene {
     DeviceBuffer<float> outBands;
     DeviceBuffer<float> covBands;    // ptr_render_bands_cov: the covariance beside outBands (include/ptr_stats.h)
     DeviceBuffer<float4> covMean;    // k_resolve_cov: per local pixel, the running mean between the passes of a frame
-    // adaptive frames (include/ptr_adaptive.h): the per-pixel state in image order, the two active lists, the compaction's scratch
-    DeviceBuffer<float> adaptiveSum, adaptiveMean, adaptiveM, adaptiveE;
-    DeviceBuffer<uint32_t> adaptiveN, adaptiveLists, adaptiveBlockWords;
-    DeviceBuffer<uint8_t> adaptiveKeep;
+    ptrhost::AdaptiveStore adaptive;   // adaptive frames (include/ptr_adaptive.h): the per-pixel state, the two active lists, the scratch
     DeviceBuffer<float> adaptiveOut;   // ptr_render_adaptive: rgb, cov and count of the frame before they go to the host
     DeviceBuffer<float4> rayBatch;
     DeviceBuffer<PtrHit> hitBatch;
@@ -183,8 +182,8 @@ void renderBands(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, 
 // passes renderBands splits a frame of `spp` samples per pixel into (the per-sample accumulators of a pass have to fit in memory)
 uint32_t framePasses(const PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp);
 
-// most per-sample accumulators one pass may hold (the memory budget, or PTR_MAX_ITEMS)
-uint64_t maxPassItems(const PtrDeviceScene& ds);
+// most per-sample accumulators one pass may hold (the scene's memory budget, or the 32-bit cap without a scene; PTR_MAX_ITEMS)
+uint64_t maxPassItems(const PtrDeviceScene* ds);
 // The tracing part of a pass, for a caller that brings its own local-pixel table (include/ptr_adaptive.h): samples sampleBase ..
 // sampleBase + spp - 1 of the `localPixels` (> 0) pixels dPixelOfLocal names, non-counting kernels.  `consume` is handed the pass's
 // accumulators - sample c of local pixel lp at [c * localPixels + lp] - and launches what reads them on `stream`; the stream is joined
@@ -231,15 +230,26 @@ void uploadScene(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceSce
 // the partition's thread with `device` current; asynchronous on `stream` except for the staged path.  True when the bytes were staged.
 bool sendBandsToRoot(void* dRootDst, int rootDevice, const void* dSrc, int device, size_t bytes, bool forceStaged, hipStream_t stream);
 
+// What an entry point refuses before any device call: returns the C-ABI's code with the message in `err`.
+inline int refuse(char* err, size_t cap, const std::string& message) {
+    setErr(err, cap, message);
+    return 1;
+}
+inline int nullArgument(const char* who, char* err, size_t cap) { return refuse(err, cap, std::string(who) + ": null argument"); }
+inline int noDevice(const char* who, char* err, size_t cap) {
+    setErr(err, cap, std::string(who) + ": no HIP device (the HIP path has no CPU fallback)");
+    return 2;
+}
+// Pixels, list entries and per-sample accumulators are 32-bit indices with room for a block of threads past the last one.
+constexpr uint64_t kIndexLimit = 0xFFFF0000ull;
+inline bool pastIndexLimit(uint64_t count) { return count > kIndexLimit; }
+
 // The frame of a C-ABI entry point that works on a device: "<who>: null argument" unless argsOk (a call that needs `scene` says so
 // there), the device selected (the scene's; device 0 for a call without a scene, which fails when there is none), the body, the error
 // a launch in it may have left, and nothing unwinding to the caller.
 template <typename Body>
 int deviceCall(const char* who, const PtrDeviceScene* scene, bool argsOk, char* err, size_t cap, Body&& body) {
-    if (!argsOk) {
-        setErr(err, cap, std::string(who) + ": null argument");
-        return 1;
-    }
+    if (!argsOk) return nullArgument(who, err, cap);
     try {
         if (!scene && ptr_device_count() < 1) throw HipError{"no HIP device (the HIP path has no CPU fallback)"};
         HIP_CHECK(hipSetDevice(scene ? scene->device : 0));

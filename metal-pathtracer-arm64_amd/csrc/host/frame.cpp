@@ -1,18 +1,17 @@
 // Host side of include/ptr_frame.h: the frame object (the per-pixel state of an adaptive frame, owned by the frame and kept on the device
 // between calls), the argument checks, accumulate, the loop of refine (class minimum -> split -> an ordinary pass of the wavefront kernels
 // over S -> update -> select on S and merge), resolve, the checkpoint, and the test-only frame whose accumulators are gathered from
-// given samples instead of being traced.
+// given samples instead of being traced.  The state's buffers, the sample sources and the sample step are the ones adaptive.cpp and
+// multi.cpp use (adaptive_host.h); the frame's own are the first list, S, and the count classes it keeps on the host.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "../kernels/frame.h"
-#include "../kernels/multi.h"
 #include "adaptive_host.h"
 #include "device_scene.h"
 #include "knobs.h"
@@ -26,11 +25,9 @@ struct PtrFrame {
     int device = 0;
     PtrSettings settings{};
     size_t pixels = 0;
-    // the state, image order; the first list; L's two buffers; S; the flag "in S" per entry of L; the compaction's scratch and the word
-    // the class minimum arrives in
-    DeviceBuffer<float> sum, mean, m, e;
-    DeviceBuffer<uint32_t> n, order, lists, listS, blockWords;
-    DeviceBuffer<uint8_t> inS, keep;
+    AdaptiveStore store;   // the state, image order; L's two buffers; the compaction's scratch and the word the class minimum arrives in
+    DeviceBuffer<uint32_t> order, listS;   // the first list; S
+    DeviceBuffer<uint8_t> inS;             // the flag "in S" per entry of L
     DeviceBuffer<float> out;   // ptr_frame_resolve: rgb, cov and count before they go to the host
     // the test-only frame: the samples it was given, and the accumulators of a pass gathered from them
     DeviceBuffer<float4> probeSamples, probeItems;
@@ -39,12 +36,6 @@ struct PtrFrame {
     // no device call
     std::map<uint32_t, uint64_t> classes;
 
-    AdaptiveState state() const { return AdaptiveState{sum.ptr, mean.ptr, m.ptr, n.ptr, e.ptr}; }
-    AdaptiveScratch scratch() const {
-        const size_t blocks = (pixels + kAdaptiveBlock - 1u) / kAdaptiveBlock;
-        return AdaptiveScratch{keep.ptr, blockWords.ptr, blockWords.ptr + blocks, blockWords.ptr + 2u * blocks};
-    }
-    uint32_t* minWord() const { return scratch().total + 1; }
     bool uniform() const { return classes.size() == 1u; }
     uint32_t minCount() const { return classes.begin()->first; }
     uint32_t maxCount() const { return classes.rbegin()->first; }
@@ -52,40 +43,14 @@ struct PtrFrame {
 
 namespace {
 
-// samples sampleBase .. sampleBase + spp - 1 of the `active` list entries: hands `consume` the accumulators and joins the stream
-using PassSource = std::function<void(uint32_t spp, uint32_t sampleBase, const uint32_t* dList, uint32_t active, PtrRenderStats* one,
-                                      const std::function<void(const float4*)>& consume)>;
-
-PassSource passSource(PtrFrame& f, hipStream_t stream) {
-    if (f.scene) {
-        return [&f, stream](uint32_t spp, uint32_t sampleBase, const uint32_t* dList, uint32_t active, PtrRenderStats* one,
-                            const std::function<void(const float4*)>& consume) {
-            traceItems(*f.scene, f.settings, spp, sampleBase, dList, active, stream, one, consume);
-        };
-    }
-    return [&f, stream](uint32_t spp, uint32_t sampleBase, const uint32_t* dList, uint32_t active, PtrRenderStats*,
-                        const std::function<void(const float4*)>& consume) {
-        if (static_cast<uint64_t>(sampleBase) + spp > f.sampleCount) throw HipError{"a sample past the ones the frame was given"};
-        f.probeItems.ensure(static_cast<size_t>(active) * spp);
-        launchMultiGatherItems(f.probeSamples.ptr, f.pixels, dList, active, spp, sampleBase, f.probeItems.ptr, stream);
-        consume(f.probeItems.ptr);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipStreamSynchronize(stream));
-    };
-}
-
-uint64_t passItems(const PtrFrame& f) {
-    if (f.scene) return maxPassItems(*f.scene);
-    const uint64_t forced = ptr::readKnobs().maxItems;   // test knob, as in maxPassItems
-    return forced ? forced : 0xFFFFFFF0ull;
+// what the sample steps of one call on the frame share; `sum` (nullable) collects the stats
+SampleStep sampleStep(PtrFrame& f, hipStream_t stream, PtrRenderStats* sum) {
+    return SampleStep{f.scene ? tracedSource(*f.scene, f.settings, stream) : gatheredSource(f.probeSamples.ptr, f.pixels, f.sampleCount, f.probeItems, stream),
+                      maxPassItems(f.scene), f.store.state(), stream, sum};
 }
 
 void zeroState(PtrFrame& f, hipStream_t stream) {
-    HIP_CHECK(hipMemsetAsync(f.sum.ptr, 0, f.pixels * 3u * sizeof(float), stream));
-    HIP_CHECK(hipMemsetAsync(f.mean.ptr, 0, f.pixels * 3u * sizeof(float), stream));
-    HIP_CHECK(hipMemsetAsync(f.m.ptr, 0, f.pixels * 6u * sizeof(float), stream));
-    HIP_CHECK(hipMemsetAsync(f.n.ptr, 0, f.pixels * sizeof(uint32_t), stream));
-    HIP_CHECK(hipMemsetAsync(f.e.ptr, 0, f.pixels * sizeof(float), stream));
+    f.store.zero(stream);
     HIP_CHECK(hipStreamSynchronize(stream));
     f.classes.clear();
     f.classes[0u] = f.pixels;
@@ -93,35 +58,18 @@ void zeroState(PtrFrame& f, hipStream_t stream) {
 
 // the buffers of a new frame and its empty state; `device` is current
 void allocate(PtrFrame& f) {
-    const size_t pixels = f.pixels;
-    f.sum.ensure(pixels * 3u);
-    f.mean.ensure(pixels * 3u);
-    f.m.ensure(pixels * 6u);
-    f.e.ensure(pixels);
-    f.n.ensure(pixels);
-    f.lists.ensure(pixels * 2u);
-    f.listS.ensure(pixels);
-    f.inS.ensure(pixels);
-    f.keep.ensure(pixels);
-    const size_t blocks = (pixels + kAdaptiveBlock - 1u) / kAdaptiveBlock;
-    f.blockWords.ensure(blocks * 2u + 2u);   // counts, offsets, the total and the class minimum
+    f.store.ensure(f.pixels);
+    f.listS.ensure(f.pixels);
+    f.inS.ensure(f.pixels);
     std::vector<uint32_t> order;
     imagePixelOrder(f.settings.width, f.settings.height, order);
-    f.order.upload(order.data(), pixels);
+    f.order.upload(order.data(), f.pixels);
     zeroState(f, nullptr);
 }
 
-// The samples of one class: `list` (count entries, all at nBefore samples) gets spp more, in sub-passes; e on the last one.
-void addSamples(PtrFrame& f, const PassSource& source, const uint32_t* list, uint32_t count, uint32_t nBefore, uint32_t spp, hipStream_t stream,
-                PtrRenderStats* sum) {
-    const AdaptiveState st = f.state();
-    forEachSubPass(passItems(f), count, spp, [&](uint32_t done, uint32_t part, bool last) {
-        PtrRenderStats one{};
-        source(part, nBefore + done, list, count, sum ? &one : nullptr,
-               [&](const float4* items) { launchAdaptiveUpdate(items, list, count, part, nBefore + done, last, st, stream); });
-        if (sum) addPassStats(one, *sum);
-    });
-    // pixels of the class move to the new count
+// The samples of one class: `list` (count entries, all at nBefore samples) gets spp more, and its pixels move to the new count.
+void addClassSamples(PtrFrame& f, const SampleStep& step, const uint32_t* list, uint32_t count, uint32_t nBefore, uint32_t spp) {
+    addSamples(step, list, count, nBefore, spp);
     auto it = f.classes.find(nBefore);
     if (it != f.classes.end()) {   // (always, unless an import brought counts that disagree with themselves)
         it->second -= std::min<uint64_t>(it->second, count);
@@ -133,8 +81,7 @@ void addSamples(PtrFrame& f, const PassSource& source, const uint32_t* list, uin
 void accumulate(PtrFrame& f, uint32_t spp, hipStream_t stream, PtrRenderStats* stats) {
     HIP_CHECK(hipSetDevice(f.device));
     PtrRenderStats sum{};
-    const PassSource source = passSource(f, stream);
-    addSamples(f, source, f.order.ptr, static_cast<uint32_t>(f.pixels), f.minCount(), spp, stream, stats ? &sum : nullptr);
+    addClassSamples(f, sampleStep(f, stream, stats ? &sum : nullptr), f.order.ptr, static_cast<uint32_t>(f.pixels), f.minCount(), spp);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(stream));
     if (stats) {
@@ -147,12 +94,11 @@ void accumulate(PtrFrame& f, uint32_t spp, hipStream_t stream, PtrRenderStats* s
 void refine(PtrFrame& f, const PtrAdaptiveParams& params, hipStream_t stream, PtrRenderStats* stats, PtrAdaptiveInfo* info) {
     HIP_CHECK(hipSetDevice(f.device));
     const uint32_t width = f.settings.width, height = f.settings.height, pixels = static_cast<uint32_t>(f.pixels);
-    const AdaptiveState st = f.state();
-    const AdaptiveScratch scratch = f.scratch();
-    const PassSource source = passSource(f, stream);
+    const AdaptiveScratch scratch = f.store.scratch();
     PtrAdaptiveInfo local{};
     PtrRenderStats sum{};
-    PtrRenderStats* const sumPtr = stats ? &sum : nullptr;
+    const SampleStep step = sampleStep(f, stream, stats ? &sum : nullptr);
+    const AdaptiveState& st = step.state;
     auto note = [&](uint32_t active) {
         if (local.rounds < PTR_ADAPTIVE_INFO_ROUNDS) local.activeAfter[local.rounds] = active;
         ++local.rounds;
@@ -169,60 +115,52 @@ void refine(PtrFrame& f, const PtrAdaptiveParams& params, hipStream_t stream, Pt
     const bool empty = f.uniform() && f.minCount() == 0u;
     uint32_t deepest = 0u;   // the most samples this call gave one pixel
     if (empty) {
-        addSamples(f, source, f.order.ptr, pixels, 0u, params.minSpp, stream, sumPtr);
+        addClassSamples(f, step, f.order.ptr, pixels, 0u, params.minSpp);
         local.totalSamples += static_cast<uint64_t>(pixels) * params.minSpp;
         deepest = params.minSpp;
     }
     // the start list, and with it the class minimum of the first round
     uint32_t turn = 0u, active = 0u, nMin = kFrameNoCount;
-    uint32_t* lists[2] = {f.lists.ptr, f.lists.ptr + f.pixels};
-    launchAdaptiveSelect(f.order.ptr, pixels, width, height, st, params.maxSpp, params.threshold, scratch, lists[0], stream);
+    launchAdaptiveSelect(f.order.ptr, pixels, width, height, st, params.maxSpp, params.threshold, scratch, f.store.list(0u), stream);
     HIP_CHECK(hipGetLastError());
     readWords(&active, nullptr);
     if (empty) note(active);
 
     // PTR_VERBOSE=launches: device events around the kernels between the rounds (tools/frame_cost.py parses the line)
-    struct Marks {
-        hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-        ~Marks() {
-            for (hipEvent_t ev : e) if (ev) (void)hipEventDestroy(ev);
-        }
-    } marks;
+    EventSet marks;
     const bool timed = ptr::readKnobs().verboseLaunches;
-    if (timed) {
-        for (hipEvent_t& ev : marks.e) HIP_CHECK(hipEventCreate(&ev));
-    }
+    if (timed) marks.create(4u);
     while (active > 0u) {
-        const uint32_t* list = lists[turn];
+        const uint32_t* list = f.store.list(turn);
         // n_min, then S
-        if (timed) HIP_CHECK(hipEventRecord(marks.e[0], stream));
-        HIP_CHECK(hipMemsetAsync(f.minWord(), 0xFF, sizeof(uint32_t), stream));   // kFrameNoCount
-        launchFrameClassMin(list, active, st.n, f.minWord(), stream);
+        if (timed) HIP_CHECK(hipEventRecord(marks[0], stream));
+        HIP_CHECK(hipMemsetAsync(f.store.minWord(), 0xFF, sizeof(uint32_t), stream));   // kFrameNoCount
+        launchFrameClassMin(list, active, st.n, f.store.minWord(), stream);
         HIP_CHECK(hipGetLastError());
         uint32_t ignored = 0u, inClass = 0u;
         readWords(&ignored, &nMin);
         if (nMin >= params.maxSpp) throw HipError{"ptr_frame_refine: the active list holds a pixel at maxSpp"};   // (select never keeps one)
         launchFrameSplit(list, active, st.n, nMin, f.inS.ptr, scratch, f.listS.ptr, stream);
-        if (timed) HIP_CHECK(hipEventRecord(marks.e[1], stream));
+        if (timed) HIP_CHECK(hipEventRecord(marks[1], stream));
         HIP_CHECK(hipGetLastError());
         readWords(&inClass, nullptr);
         if (inClass == 0u || inClass > active) throw HipError{"ptr_frame_refine: the class of the round is empty"};
         // its samples
         const uint32_t k = std::min(params.stepSpp, params.maxSpp - nMin);
-        addSamples(f, source, f.listS.ptr, inClass, nMin, k, stream, sumPtr);
+        addClassSamples(f, step, f.listS.ptr, inClass, nMin, k);
         local.totalSamples += static_cast<uint64_t>(inClass) * k;
         deepest = std::max(deepest, k);
         // select on S, merged into the next L
-        if (timed) HIP_CHECK(hipEventRecord(marks.e[2], stream));
-        launchFrameMerge(list, active, f.inS.ptr, width, height, st, params.maxSpp, params.threshold, scratch, lists[turn ^ 1u], stream);
-        if (timed) HIP_CHECK(hipEventRecord(marks.e[3], stream));
+        if (timed) HIP_CHECK(hipEventRecord(marks[2], stream));
+        launchFrameMerge(list, active, f.inS.ptr, width, height, st, params.maxSpp, params.threshold, scratch, f.store.list(turn ^ 1u), stream);
+        if (timed) HIP_CHECK(hipEventRecord(marks[3], stream));
         HIP_CHECK(hipGetLastError());
         const uint32_t before = active;
         readWords(&active, nullptr);
         if (timed) {   // debugging aid, like the [adaptive] lines of ptr_render_adaptive
             float splitMs = 0.0f, mergeMs = 0.0f;
-            HIP_CHECK(hipEventElapsedTime(&splitMs, marks.e[0], marks.e[1]));
-            HIP_CHECK(hipEventElapsedTime(&mergeMs, marks.e[2], marks.e[3]));
+            HIP_CHECK(hipEventElapsedTime(&splitMs, marks[0], marks[1]));
+            HIP_CHECK(hipEventElapsedTime(&mergeMs, marks[2], marks[3]));
             std::fprintf(stderr, "[frame] round %u: class %u, %u of %u active x %u spp; minimum + split %.4f ms, select + merge %.4f ms\n", local.rounds,
                          nMin, inClass, before, k, splitMs, mergeMs);
         }
@@ -241,25 +179,15 @@ void refine(PtrFrame& f, const PtrAdaptiveParams& params, hipStream_t stream, Pt
 
 void resolveDevice(PtrFrame& f, float* dRgb, float* dCov, uint32_t* dCount, hipStream_t stream) {
     HIP_CHECK(hipSetDevice(f.device));
-    launchAdaptiveFinish(f.state(), static_cast<uint32_t>(f.pixels), dRgb, dCov, dCount, stream);
+    launchAdaptiveFinish(f.store.state(), static_cast<uint32_t>(f.pixels), dRgb, dCov, dCount, stream);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(stream));
 }
 
 std::string badSize(const std::string& w, uint32_t width, uint32_t height) {
     if (width == 0u || height == 0u) return w + ": render size must be non-zero";
-    if (static_cast<uint64_t>(width) * height > 0xFFFF0000ull) return w + ": image too large for a frame";
+    if (pastIndexLimit(static_cast<uint64_t>(width) * height)) return w + ": image too large for a frame";
     return std::string();
-}
-
-int refuse(char* err, size_t cap, const std::string& message) {
-    setErr(err, cap, message);
-    return 1;
-}
-
-int noDevice(const char* who, char* err, size_t cap) {
-    setErr(err, cap, std::string(who) + ": no HIP device (the HIP path has no CPU fallback)");
-    return 2;
 }
 
 }  // namespace
@@ -268,7 +196,7 @@ extern "C" {
 
 int ptr_frame_create(PtrDeviceScene* scene, const PtrSettings* settings, PtrFrame** out_frame, char* err, size_t err_cap) {
     static const char* const who = "ptr_frame_create";
-    if (!scene || !settings || !out_frame) return refuse(err, err_cap, std::string(who) + ": null argument");
+    if (!scene || !settings || !out_frame) return nullArgument(who, err, err_cap);
     const std::string bad = badSize(who, settings->width, settings->height);
     if (!bad.empty()) return refuse(err, err_cap, bad);
     if (ptr_device_count() < 1) return noDevice(who, err, err_cap);
@@ -295,7 +223,7 @@ void ptr_frame_release(PtrFrame* frame) {
 int ptr_frame_debug_create(uint32_t width, uint32_t height, const float* samples, uint32_t sample_count, int device, PtrFrame** out_frame,
                            char* err, size_t err_cap) {
     static const char* const who = "ptr_frame_debug_create";
-    if (!samples || !out_frame) return refuse(err, err_cap, std::string(who) + ": null argument");
+    if (!samples || !out_frame) return nullArgument(who, err, err_cap);
     const std::string bad = badSize(who, width, height);
     if (!bad.empty()) return refuse(err, err_cap, bad);
     if (sample_count == 0u) return refuse(err, err_cap, std::string(who) + ": sample_count must be >= 1");
@@ -320,7 +248,7 @@ int ptr_frame_debug_create(uint32_t width, uint32_t height, const float* samples
 
 int ptr_frame_reset(PtrFrame* frame, const PtrSettings* settings, char* err, size_t err_cap) {
     static const char* const who = "ptr_frame_reset";
-    if (!frame) return refuse(err, err_cap, std::string(who) + ": null argument");
+    if (!frame) return nullArgument(who, err, err_cap);
     if (settings && (settings->width != frame->settings.width || settings->height != frame->settings.height)) {
         return refuse(err, err_cap, std::string(who) + ": a frame keeps its width and height for its life");
     }
@@ -335,7 +263,7 @@ int ptr_frame_reset(PtrFrame* frame, const PtrSettings* settings, char* err, siz
 
 int ptr_frame_accumulate(PtrFrame* frame, uint32_t spp, void* stream, PtrRenderStats* stats, char* err, size_t err_cap) {
     static const char* const who = "ptr_frame_accumulate";
-    if (!frame) return refuse(err, err_cap, std::string(who) + ": null argument");
+    if (!frame) return nullArgument(who, err, err_cap);
     if (spp == 0u) return refuse(err, err_cap, std::string(who) + ": spp must be >= 1");
     if (!frame->uniform()) {
         return refuse(err, err_cap, std::string(who) + ": the frame is not uniform (its pixels hold different sample counts); a refine with threshold 0 "
@@ -355,7 +283,7 @@ int ptr_frame_accumulate(PtrFrame* frame, uint32_t spp, void* stream, PtrRenderS
 int ptr_frame_refine(PtrFrame* frame, const PtrAdaptiveParams* params, void* stream, PtrRenderStats* stats, PtrAdaptiveInfo* info, char* err,
                      size_t err_cap) {
     static const char* const who = "ptr_frame_refine";
-    if (!frame || !params) return refuse(err, err_cap, std::string(who) + ": null argument");
+    if (!frame || !params) return nullArgument(who, err, err_cap);
     const std::string bad = badAdaptiveParams(who, *params);
     if (!bad.empty()) return refuse(err, err_cap, bad);
     const bool empty = frame->uniform() && frame->minCount() == 0u;
@@ -372,7 +300,7 @@ int ptr_frame_refine(PtrFrame* frame, const PtrAdaptiveParams* params, void* str
 
 int ptr_frame_resolve_device(PtrFrame* frame, void* d_out_rgb, void* d_out_cov, void* d_out_count, void* stream, char* err, size_t err_cap) {
     static const char* const who = "ptr_frame_resolve_device";
-    if (!frame || !d_out_rgb) return refuse(err, err_cap, std::string(who) + ": null argument");
+    if (!frame || !d_out_rgb) return nullArgument(who, err, err_cap);
     try {
         resolveDevice(*frame, static_cast<float*>(d_out_rgb), static_cast<float*>(d_out_cov), static_cast<uint32_t*>(d_out_count),
                       static_cast<hipStream_t>(stream));
@@ -383,18 +311,11 @@ int ptr_frame_resolve_device(PtrFrame* frame, void* d_out_rgb, void* d_out_cov, 
 
 int ptr_frame_resolve(PtrFrame* frame, float* out_rgb, float* out_cov, uint32_t* out_count, char* err, size_t err_cap) {
     static const char* const who = "ptr_frame_resolve";
-    if (!frame || !out_rgb) return refuse(err, err_cap, std::string(who) + ": null argument");
+    if (!frame || !out_rgb) return nullArgument(who, err, err_cap);
     try {
-        const size_t pixels = frame->pixels;
         HIP_CHECK(hipSetDevice(frame->device));
-        frame->out.ensure(pixels * 10u);   // rgb 3, cov 6, count 1 (as words)
-        float* dRgb = frame->out.ptr;
-        float* dCov = out_cov ? dRgb + pixels * 3u : nullptr;
-        uint32_t* dCount = out_count ? reinterpret_cast<uint32_t*>(dRgb + pixels * 9u) : nullptr;
-        resolveDevice(*frame, dRgb, dCov, dCount, nullptr);
-        HIP_CHECK(hipMemcpy(out_rgb, dRgb, pixels * 3u * sizeof(float), hipMemcpyDeviceToHost));
-        if (out_cov) HIP_CHECK(hipMemcpy(out_cov, dCov, pixels * 6u * sizeof(float), hipMemcpyDeviceToHost));
-        if (out_count) HIP_CHECK(hipMemcpy(out_count, dCount, pixels * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        finishAndDownload(frame->out, frame->pixels, out_rgb, out_cov, out_count,
+                          [&](float* dRgb, float* dCov, uint32_t* dCount) { resolveDevice(*frame, dRgb, dCov, dCount, nullptr); });
         return 0;
     }
     PTR_CATCH_ALL(err, err_cap)
@@ -414,15 +335,10 @@ int ptr_frame_info(const PtrFrame* frame, PtrFrameInfo* out) {
 
 int ptr_frame_export(PtrFrame* frame, float* sum, float* mean, float* m, uint32_t* n, float* e, char* err, size_t err_cap) {
     static const char* const who = "ptr_frame_export";
-    if (!frame || !sum || !mean || !m || !n || !e) return refuse(err, err_cap, std::string(who) + ": null argument");
+    if (!frame || !sum || !mean || !m || !n || !e) return nullArgument(who, err, err_cap);
     try {
         HIP_CHECK(hipSetDevice(frame->device));
-        const size_t pixels = frame->pixels;
-        frame->sum.download(sum, pixels * 3u);
-        frame->mean.download(mean, pixels * 3u);
-        frame->m.download(m, pixels * 6u);
-        frame->n.download(n, pixels);
-        frame->e.download(e, pixels);
+        frame->store.download(sum, mean, m, n, e);
         return 0;
     }
     PTR_CATCH_ALL(err, err_cap)
@@ -431,17 +347,12 @@ int ptr_frame_export(PtrFrame* frame, float* sum, float* mean, float* m, uint32_
 int ptr_frame_import(PtrFrame* frame, const float* sum, const float* mean, const float* m, const uint32_t* n, const float* e, char* err,
                      size_t err_cap) {
     static const char* const who = "ptr_frame_import";
-    if (!frame || !sum || !mean || !m || !n || !e) return refuse(err, err_cap, std::string(who) + ": null argument");
+    if (!frame || !sum || !mean || !m || !n || !e) return nullArgument(who, err, err_cap);
     try {
         HIP_CHECK(hipSetDevice(frame->device));
-        const size_t pixels = frame->pixels;
-        frame->sum.upload(sum, pixels * 3u);
-        frame->mean.upload(mean, pixels * 3u);
-        frame->m.upload(m, pixels * 6u);
-        frame->n.upload(n, pixels);
-        frame->e.upload(e, pixels);
+        frame->store.upload(sum, mean, m, n, e);
         frame->classes.clear();
-        for (size_t p = 0; p < pixels; ++p) ++frame->classes[n[p]];
+        for (size_t p = 0; p < frame->pixels; ++p) ++frame->classes[n[p]];
         return 0;
     }
     PTR_CATCH_ALL(err, err_cap)

@@ -1063,15 +1063,15 @@ namespace ptrhost {
 // more samples than that is rendered in several passes of equal sample counts whose per-pixel sums add up in the output
 // buffer.  (Folding C samples into one work item instead keeps one pass but lengthens the end-of-frame drain: 4096 spp of
 // config 2 as items of 9 samples ran at 1116 Msamples/s.)  The sample streams do not depend on the split.
-uint64_t maxPassItems(const PtrDeviceScene& ds) {
-    const uint64_t budget = itemBudgetBytes(ds);
-    uint64_t maxItems = std::min<uint64_t>(budget / sizeof(float4), 0xFFFFFFF0ull);
+uint64_t maxPassItems(const PtrDeviceScene* ds) {
+    uint64_t maxItems = 0xFFFFFFF0ull;
+    if (ds) maxItems = std::min<uint64_t>(itemBudgetBytes(*ds) / sizeof(float4), maxItems);
     if (const uint64_t forced = ptr::readKnobs().maxItems) maxItems = forced;   // test knob
     return maxItems;
 }
 
 uint32_t framePasses(const PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp) {
-    const uint64_t maxItems = maxPassItems(ds);
+    const uint64_t maxItems = maxPassItems(&ds);
     // counted on the whole frame, not on this partition: every partition then splits the samples the same way and the image
     // stays bit-identical whatever the number of partitions
     const uint64_t pixels = static_cast<uint64_t>(settings.width) * settings.height;

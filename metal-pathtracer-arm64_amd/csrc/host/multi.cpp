@@ -1,13 +1,13 @@
 // Host side of include/ptr_multi.h: the argument checks, one host thread per partition (each with its own device scene and stream, as
 // ptr_render_multi), the lock-step rounds of an adaptive frame with the exchange of the band-edge rows of e between them, and the finish
-// and gather in band layout.  The sample source of a pass is a parameter of the partition loop: traceItems for the renderer,
-// k_multi_gather_items for the test-only probe, which therefore runs everything else the renderer runs.
+// and gather in band layout.  The sample source of a pass is a parameter of the partition loop: the traced one for the renderer, the
+// gathered one for the test-only probe, which therefore runs everything else the renderer runs.  The state's buffers, the sources and
+// the sample step are the ones adaptive.cpp and frame.cpp use (adaptive_host.h); the halo goes out from the step's hook.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <memory>
 #include <string>
 #include <vector>
@@ -61,17 +61,13 @@ struct Exchange {
     float* inbox(uint32_t p) const { return host + offset.back() + offset[p]; }
 };
 
-// samples sampleBase .. sampleBase + spp - 1 of the `active` list entries: hands `consume` the accumulators and joins the stream
-using PassSource = std::function<void(uint32_t spp, uint32_t sampleBase, const uint32_t* dList, uint32_t active, PtrRenderStats* one,
-                                      const std::function<void(const float4*)>& consume)>;
-
 void runFrame(const Request& rq) {
     const bool adaptive = rq.params != nullptr;
     const bool probe = rq.scene == nullptr;
     const uint32_t parts = static_cast<uint32_t>(rq.devices.size());
     const uint32_t width = rq.settings.width, height = rq.settings.height;
     const size_t pixels = static_cast<size_t>(width) * height;
-    if (pixels + static_cast<size_t>(PTR_BAND_ROWS) * width > 0xFFFF0000ull) throw HipError{"image too large"};
+    if (pastIndexLimit(pixels + static_cast<size_t>(PTR_BAND_ROWS) * width)) throw HipError{"image too large"};
     const auto t0 = Clock::now();
     PreparedScene prepared;
     if (!probe) prepareScene(*rq.scene, prepared);
@@ -164,29 +160,24 @@ void runFrame(const Request& rq) {
         std::vector<uint32_t> order;
         partitionPixels(width, height, p, parts, order);
         const uint32_t local = static_cast<uint32_t>(order.size());
-        const AdaptiveBuffers b = ensureAdaptiveBuffers(*ds, pixels);   // image order: the lists name image pixels, select reads e around them
+        AdaptiveStore& b = ds->adaptive;
+        b.ensure(pixels);   // image order: the lists name image pixels, select reads e around them
         DeviceBuffer<float> edge;
         edge.ensure(static_cast<size_t>(mp.bands) * 2u * width);
-        const uint64_t maxItems = maxPassItems(*ds);
+        PtrRenderStats sum{};
+        SampleStep step{nullptr, maxPassItems(ds.get()), b.state(), stream, rq.stats ? &sum : nullptr};
         DeviceBuffer<float4> probeSamples, probeItems;
-        PassSource source;
         if (probe) {
             probeSamples.upload(reinterpret_cast<const float4*>(rq.samples), static_cast<size_t>(params.maxSpp) * pixels);
+            // the largest sub-pass of the frame: the source then frees nothing in the middle of it
             const uint64_t mostSpp = std::max(params.minSpp, std::min(params.stepSpp, params.maxSpp));
-            probeItems.ensure(static_cast<size_t>(std::max<uint64_t>(local, std::min<uint64_t>(maxItems, static_cast<uint64_t>(local) * mostSpp))));
-            source = [&](uint32_t spp, uint32_t sampleBase, const uint32_t* dList, uint32_t active, PtrRenderStats*, const std::function<void(const float4*)>& consume) {
-                launchMultiGatherItems(probeSamples.ptr, pixels, dList, active, spp, sampleBase, probeItems.ptr, stream);
-                consume(probeItems.ptr);
-                HIP_CHECK(hipGetLastError());
-                HIP_CHECK(hipStreamSynchronize(stream));
-            };
+            probeItems.ensure(static_cast<size_t>(std::max<uint64_t>(local, std::min<uint64_t>(step.maxItems, static_cast<uint64_t>(local) * mostSpp))));
+            step.source = gatheredSource(probeSamples.ptr, pixels, params.maxSpp, probeItems, stream);
         } else {
-            source = [&](uint32_t spp, uint32_t sampleBase, const uint32_t* dList, uint32_t active, PtrRenderStats* one, const std::function<void(const float4*)>& consume) {
-                traceItems(*ds, rq.settings, spp, sampleBase, dList, active, stream, one, consume);
-            };
+            step.source = tracedSource(*ds, rq.settings, stream);
         }
-        if (local) HIP_CHECK(hipMemcpyAsync(b.lists[0], order.data(), local * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
-        zeroAdaptiveState(b, pixels, stream);
+        if (local) HIP_CHECK(hipMemcpyAsync(b.list(0u), order.data(), local * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        b.zero(stream);
         HIP_CHECK(hipStreamSynchronize(stream));   // `order` is pageable host memory
         stateSeconds[p] = since(w0) - uploadSeconds[p];
 
@@ -197,37 +188,23 @@ void runFrame(const Request& rq) {
             waitSeconds[p] += since(m0);
             return all;
         };
-        PtrRenderStats sum{};
         uint32_t active = local, n = 0u, turn = 0u, rounds = 0u;
         // PTR_VERBOSE=launches: device events around the two halves of the exchange (tools/multi_adaptive_cost.py parses the line)
-        struct Marks {
-            hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
-            ~Marks() {
-                for (hipEvent_t ev : e) if (ev) (void)hipEventDestroy(ev);
-            }
-        } marks;
+        EventSet marks;
         const bool timed = parts > 1u && ptr::readKnobs().verboseLaunches;
-        if (timed) {
-            for (hipEvent_t& ev : marks.e) HIP_CHECK(hipEventCreate(&ev));
-        }
+        if (timed) marks.create(4u);
         const size_t haloBytes = static_cast<size_t>(mp.bands) * 2u * width * sizeof(float);
         for (bool more = true; more;) {
             const uint32_t roundSpp = adaptiveRoundSpp(params, n);
-            const uint32_t* list = b.lists[turn];
+            const uint32_t* list = b.list(turn);
             // 1. trace and update; behind the last update the edge rows of e go to the outbox
             if (active > 0u) {
-                forEachSubPass(maxItems, active, roundSpp, [&](uint32_t done, uint32_t spp, bool last) {
-                    PtrRenderStats one{};
-                    source(spp, n + done, list, active, rq.stats ? &one : nullptr, [&](const float4* items) {
-                        launchAdaptiveUpdate(items, list, active, spp, n + done, last, b.state, stream);
-                        if (last && parts > 1u) {
-                            if (timed) HIP_CHECK(hipEventRecord(marks.e[0], stream));
-                            launchMultiHaloPack(mp, b.state.e, edge.ptr, stream);
-                            HIP_CHECK(hipMemcpyAsync(ex.outbox(p), edge.ptr, haloBytes, hipMemcpyDeviceToHost, stream));
-                            if (timed) HIP_CHECK(hipEventRecord(marks.e[1], stream));
-                        }
-                    });
-                    if (rq.stats) addPassStats(one, sum);
+                addSamples(step, list, active, n, roundSpp, [&](uint32_t, uint32_t, bool last) {
+                    if (!last || parts == 1u) return;
+                    if (timed) HIP_CHECK(hipEventRecord(marks[0], stream));
+                    launchMultiHaloPack(mp, step.state.e, edge.ptr, stream);
+                    HIP_CHECK(hipMemcpyAsync(ex.outbox(p), edge.ptr, haloBytes, hipMemcpyDeviceToHost, stream));
+                    if (timed) HIP_CHECK(hipEventRecord(marks[1], stream));
                 });
                 HIP_CHECK(hipStreamSynchronize(stream));   // (the source joined the stream already: the outbox is written)
                 partSamples[p] += static_cast<uint64_t>(active) * roundSpp;
@@ -240,19 +217,19 @@ void runFrame(const Request& rq) {
             if (active > 0u) {
                 if (parts > 1u) {
                     multiCollectNeighbourRows(mp, ex.host, ex.offset.data(), ex.inbox(p));
-                    if (timed) HIP_CHECK(hipEventRecord(marks.e[2], stream));
+                    if (timed) HIP_CHECK(hipEventRecord(marks[2], stream));
                     HIP_CHECK(hipMemcpyAsync(edge.ptr, ex.inbox(p), haloBytes, hipMemcpyHostToDevice, stream));
-                    launchMultiHaloUnpack(mp, edge.ptr, b.state.e, stream);
-                    if (timed) HIP_CHECK(hipEventRecord(marks.e[3], stream));
+                    launchMultiHaloUnpack(mp, edge.ptr, step.state.e, stream);
+                    if (timed) HIP_CHECK(hipEventRecord(marks[3], stream));
                 }
-                launchAdaptiveSelect(list, active, width, height, b.state, params.maxSpp, params.threshold, b.scratch, b.lists[turn ^ 1u], stream);
+                launchAdaptiveSelect(list, active, width, height, step.state, params.maxSpp, params.threshold, b.scratch(), b.list(turn ^ 1u), stream);
                 HIP_CHECK(hipGetLastError());
-                HIP_CHECK(hipMemcpyAsync(&active, b.scratch.total, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+                HIP_CHECK(hipMemcpyAsync(&active, b.scratch().total, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
                 HIP_CHECK(hipStreamSynchronize(stream));
                 if (timed) {
                     float outMs = 0.0f, inMs = 0.0f;
-                    HIP_CHECK(hipEventElapsedTime(&outMs, marks.e[0], marks.e[1]));
-                    HIP_CHECK(hipEventElapsedTime(&inMs, marks.e[2], marks.e[3]));
+                    HIP_CHECK(hipEventElapsedTime(&outMs, marks[0], marks[1]));
+                    HIP_CHECK(hipEventElapsedTime(&inMs, marks[2], marks[3]));
                     std::fprintf(stderr, "[multi] partition %u round %u: halo %zu bytes each way; pack + copy %.4f ms, copy + unpack %.4f ms\n", p, rounds,
                                  haloBytes, outMs, inMs);
                 }
@@ -272,7 +249,7 @@ void runFrame(const Request& rq) {
             turn ^= 1u;
             more = total > 0u && n < params.maxSpp;
         }
-        launchMultiFinishBands(mp, b.state, dRgb, dCov, dCount, stream);
+        launchMultiFinishBands(mp, step.state, dRgb, dCov, dCount, stream);
         HIP_CHECK(hipGetLastError());
         handOver();
         renderSeconds[p] = since(r0);
@@ -393,22 +370,13 @@ int admit(Request& rq, bool pointersOk, const int* ids, int n, bool explicitIds,
     else if (rq.spp < 2u) bad = w + ": a sample covariance needs spp >= 2";
     if (bad.empty() && explicitIds && (n < 1 || n > PTR_MULTI_MAX_PARTS)) bad = w + ": the id list must name 1 .. " + std::to_string(PTR_MULTI_MAX_PARTS) + " devices";
     if (bad.empty() && !explicitIds && nDevices > PTR_MULTI_MAX_PARTS) bad = w + ": at most " + std::to_string(PTR_MULTI_MAX_PARTS) + " devices";
-    if (!bad.empty()) {
-        setErr(err, cap, bad);
-        return 1;
-    }
+    if (!bad.empty()) return refuse(err, cap, bad);
     const int available = ptr_device_count();
-    if (available < 1) {
-        setErr(err, cap, w + ": no HIP device (the HIP path has no CPU fallback)");
-        return 2;
-    }
+    if (available < 1) return noDevice(rq.who, err, cap);
     if (explicitIds) {
         for (int i = 0; i < n; ++i) {
             const int id = ids[i] < 0 ? -(ids[i] + 1) : ids[i];
-            if (id < 0 || id >= available) {
-                setErr(err, cap, w + ": no such HIP device");
-                return 1;
-            }
+            if (id < 0 || id >= available) return refuse(err, cap, w + ": no such HIP device");
             rq.devices.push_back(id);
             rq.forceStaged.push_back(ids[i] < 0 ? 1 : 0);
         }

@@ -1,11 +1,15 @@
 """GPU tests of resumable frames (include/ptr_frame.h, csrc/kernels/frame.hip, csrc/host/frame.cpp): the frame without a scene against the
 numpy restatement (tests/frame_ref.py) call by call, the frame continued against the frame rendered at once, resuming, the checkpoint,
-independence from whatever else the scene renders, reset, and the CLI's --snapshots.
+independence from whatever else the scene renders, reset, the CLI's --snapshots, and the lines the three round loops print under
+PTR_VERBOSE=launches.
 
 Unless stated the scene is tests/golden/cornell_small_mesh.scene at 37x21, depth 4, seed 1337.  Everything is compared bit for bit."""
 import importlib
+import json
 import os
+import re
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -343,3 +347,97 @@ def test_cli_snapshots(tmp_path):
         assert r.returncode == 0, r.stderr
         assert np.array_equal(pt.read_pfm(str(path)), pt.read_pfm(str(alone))), n
     assert sorted(p.name for p in tmp_path.iterdir() if p.name.startswith("series")) == ["series.4.pfm", "series.8.pfm", "series.pfm"]
+
+
+# --------------------------------------------------------------------------- 8. the timed path of the three round loops
+# The child of test_verbose_lines_of_the_three_loops: argv = root, the two thresholds.  The knobs are read once per process, so the timed
+# path needs a process of its own.
+VERBOSE_CHILD = """
+import importlib, json, os, sys
+root, thr, thr2 = sys.argv[1], float(sys.argv[2]), float(sys.argv[3])
+sys.path.insert(0, root)
+pt = importlib.import_module("metal-pathtracer-arm64_amd")
+host = pt.HostScene.load(os.path.join(root, "tests", "golden", "cornell_small_mesh.scene"), os.path.join(root, "scenes"))
+dev = pt.DeviceScene(host.desc, 0, keepalive=host)
+s = host.settings_for(width=%d, height=%d, max_depth=4, seed=1337)
+p1, p2 = pt.PtrAdaptiveParams(%d, %d, %d, thr), pt.PtrAdaptiveParams(%d, %d, %d, thr2)
+out = {}
+def note(name, info):
+    out[name] = dict(rounds=int(info.rounds), active=info.active_counts())
+note("adaptive", dev.render_adaptive(s, p1)[4])
+frame = dev.frame(s)
+note("refine1", frame.refine(p1)[1])
+note("refine2", frame.refine(p2)[1])
+frame.close()
+multi = pt.render_multi_adaptive(host.desc, s, p1, device_ids=[0, 0])
+note("multi", multi["info"])
+out["multi_count"] = multi["count"].tolist()
+print(json.dumps(out))
+""" % (W, H, MIN, MAX, STEP, MIN, MORE, STEP)
+# the expressions tools/adaptive_cost.py, tools/frame_cost.py and tools/multi_adaptive_cost.py parse the lines with
+ADAPTIVE_LINE = r"\[adaptive\] .*: (\d+) active x (\d+) spp; update ([0-9.]+) ms, select \+ compact ([0-9.]+) ms"
+FRAME_LINE = r"\[frame\] round (\d+): class (\d+), (\d+) of (\d+) active x (\d+) spp; minimum \+ split ([0-9.]+) ms, select \+ merge ([0-9.]+) ms"
+MULTI_LINE = r"\[multi\] partition (\d+) round (\d+): halo (\d+) bytes each way; pack \+ copy ([0-9.]+) ms, copy \+ unpack ([0-9.]+) ms"
+
+
+def test_verbose_lines_of_the_three_loops(resumed):
+    """PTR_VERBOSE=launches in a fresh process: ptr_render_adaptive, two refines of a frame and a two-partition frame on one device print
+    one line per round each, with the counts the calls report.  777 x 4 accumulators fit one pass, so no round is split."""
+    env = dict(os.environ, PTR_VERBOSE="launches")
+    r = subprocess.run([sys.executable, "-c", VERBOSE_CHILD, ROOT, repr(float(resumed["p1"].threshold)), repr(float(resumed["p2"].threshold))],
+                       capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    got = json.loads(r.stdout.strip().splitlines()[-1])
+    lines = r.stderr.splitlines()
+
+    def parsed(pattern, ints):
+        rows = [m.groups() for m in (re.search(pattern, l) for l in lines) if m]
+        for row in rows:
+            assert all(float(ms) >= 0.0 for ms in row[ints:]), row
+        return [tuple(int(v) for v in row[:ints]) for row in rows]
+
+    def round_spp(n):
+        return MIN if n == 0 else min(STEP, MAX - n)
+
+    # [adaptive]: one line per round, with the list the round starts with and its samples
+    a = got["adaptive"]
+    assert a["rounds"] == resumed["info1"].rounds and a["active"] == resumed["info1"].active_counts()
+    rows = parsed(ADAPTIVE_LINE, 2)
+    print("[adaptive]", rows)
+    n, want = 0, []
+    for i in range(a["rounds"]):
+        want.append((W * H if i == 0 else a["active"][i - 1], round_spp(n)))
+        n += round_spp(n)
+    assert rows == want
+    # [frame]: one line per round beyond the one that ends with the first list (the empty frame's first samples)
+    r1, r2 = got["refine1"], got["refine2"]
+    assert (r1["rounds"], r1["active"]) == (a["rounds"], a["active"])
+    assert (r2["rounds"], r2["active"]) == (resumed["info2"].rounds, resumed["info2"].active_counts())
+    rows = parsed(FRAME_LINE, 5)
+    print("[frame]", rows)
+    assert len(rows) == r1["rounds"] - 1 + r2["rounds"]
+    first, second = rows[:r1["rounds"] - 1], rows[r1["rounds"] - 1:]
+    assert [row[0] for row in first] == list(range(1, r1["rounds"])) and [row[0] for row in second] == list(range(r2["rounds"]))
+    for rnd, cls, in_class, active, spp in rows:
+        assert 1 <= spp <= STEP and 1 <= in_class <= active <= W * H and cls % STEP == 0 and MIN <= cls < MORE
+    for rnd, cls, in_class, active, spp in first:      # an empty frame: S = L, the class is the round's common count
+        assert (cls, in_class, active, spp) == (MIN + (rnd - 1) * STEP, r1["active"][rnd - 1], r1["active"][rnd - 1], round_spp(cls))
+    for rnd, cls, in_class, active, spp in second[1:]:
+        assert active == r2["active"][rnd - 1]
+    assert [row[1] for row in second] == sorted(row[1] for row in second)      # the lowest class first
+    # [multi]: one line per partition and round in which the partition's list is not empty, i.e. one of its pixels ends above the
+    # count the round starts at (partition q owns the 8-row bands b with b % 2 == q)
+    m = got["multi"]
+    assert (m["rounds"], m["active"]) == (a["rounds"], a["active"])
+    rows = parsed(MULTI_LINE, 3)
+    print("[multi]", rows)
+    count = np.array(got["multi_count"])
+    band = np.arange(H) // 8
+    want, n = set(), 0
+    for rnd in range(m["rounds"]):
+        want |= {(q, rnd) for q in (0, 1) if (count[band % 2 == q] > n).any()}
+        n += round_spp(n)
+    assert len(rows) == len(want) and {row[:2] for row in rows} == want
+    assert len(want) == 2 * m["rounds"]      # on this scene both partitions stay active to the end
+    bands = [int((band % 2 == q)[::8].sum()) for q in (0, 1)]
+    assert all(halo == bands[q] * 2 * W * 4 for q, _, halo in rows)
