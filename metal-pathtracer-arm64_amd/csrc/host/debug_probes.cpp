@@ -1,6 +1,6 @@
 // The test-only entry points of include/ptr_debug.h that need the device code or the device scene: each runs one device function (or one
 // production kernel) on a batch so that a test can compare it with the oracle.  Compiled with hipcc (host code only), like hip_backend.cpp;
-// the host-only probes live in cabi_host.cpp, and ptr_debug_render_multi_on beside renderMulti in hip_backend.cpp.
+// the host-only probes live in cabi_host.cpp, and ptr_debug_render_multi_on beside ptr_render_multi in multi.cpp.
 //
 // A probe is deviceCall (device_scene.h) around its buffers, its launch on the null stream and its downloads.
 #include <algorithm>

@@ -197,11 +197,11 @@ void addPassStats(const PtrRenderStats& one, PtrRenderStats& sum);
 // adds the per-launch figures of `b` to `a` (kernel times, k_extend launches, samples), as a frame on several devices sums its partitions
 void addLaunchStats(PtrRenderStats& a, const PtrRenderStats& b);
 
-// What the frames on several devices share (ptr_render_multi here, include/ptr_multi.h in multi.cpp).
+// What the frames on several devices (multi.cpp) share with the single-device ones here.
 // the local-pixel order of partition `part` of `parts`: its bands top to bottom, each in 8x8 blocks
 void partitionPixels(uint32_t width, uint32_t height, uint32_t part, uint32_t parts, std::vector<uint32_t>& out);
 // Device-independent half of a scene upload: geometry bake + BVH, compact materials, light list, environment tables.  Built once
-// and uploaded to every device a frame is rendered on (ptr_render_multi).
+// and uploaded to every device a frame is rendered on.
 struct PreparedScene {
     ptr::PreparedGeometry pg;   // BVH, leaf-order arrays, four-wide nodes, node format: what a geometry cache file holds
     std::vector<float> mats, lights;
@@ -225,10 +225,6 @@ struct PreparedScene {
 void prepareScene(const PtrSceneDesc& desc, PreparedScene& ps, const char* cachePath = nullptr);
 // ds.device names the device
 void uploadScene(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceScene& ds);
-// A partition's band buffer travels to the first device of the frame: a plain copy when it is local, device-to-device over the fabric
-// when the two devices can address each other, through pinned host memory otherwise (or with forceStaged, the tests' hook).  Called on
-// the partition's thread with `device` current; asynchronous on `stream` except for the staged path.  True when the bytes were staged.
-bool sendBandsToRoot(void* dRootDst, int rootDevice, const void* dSrc, int device, size_t bytes, bool forceStaged, hipStream_t stream);
 
 // What an entry point refuses before any device call: returns the C-ABI's code with the message in `err`.
 inline int refuse(char* err, size_t cap, const std::string& message) {

@@ -8,7 +8,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -17,7 +16,6 @@
 #include <exception>
 #include <memory>
 #include <string>
-#include <thread>
 #include <functional>
 #include <vector>
 
@@ -26,8 +24,6 @@
 #include "env_importance_sampler.h"
 #include "geometry_cache.h"
 #include "knobs.h"
-#include "parallel.h"
-#include "ptr_debug.h"
 #include "scene_geometry.h"
 #include "vecmath.h"
 
@@ -372,10 +368,23 @@ void uploadScene(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceSce
 
 namespace {
 
-void buildScene(const PtrSceneDesc& desc, PtrDeviceScene& ds, const char* cachePath = nullptr) {
-    PreparedScene ps;
-    prepareScene(desc, ps, cachePath);
-    uploadScene(desc, ps, ds);
+// ptr_scene_upload and, with the path of a geometry cache file, ptr_scene_upload_prepared
+int uploadTo(const char* who, const PtrSceneDesc* scene, const char* cachePath, int device, PtrDeviceScene** outScene, char* err, size_t cap) {
+    if (!scene || !outScene) return nullArgument(who, err, cap);
+    if (ptr_device_count() <= device || device < 0) {
+        setErr(err, cap, std::string(who) + ": no such HIP device (the HIP path has no CPU fallback)");
+        return 2;
+    }
+    try {
+        auto ds = std::make_unique<PtrDeviceScene>();
+        ds->device = device;
+        PreparedScene ps;
+        prepareScene(*scene, ps, cachePath);
+        uploadScene(*scene, ps, *ds);
+        *outScene = ds.release();
+        return 0;
+    }
+    PTR_CATCH_ALL(err, cap)
 }
 
 // Camera basis on the host (BuildCamera, EmbreeHeadlessRenderer.mm:150-198).
@@ -1131,36 +1140,6 @@ void addPassStats(const PtrRenderStats& one, PtrRenderStats& sum) {
     sum.uploadSeconds = one.uploadSeconds;
 }
 
-bool sendBandsToRoot(void* dRootDst, int rootDevice, const void* dSrc, int device, size_t bytes, bool forceStaged, hipStream_t stream) {
-    if (device == rootDevice && !forceStaged) {
-        HIP_CHECK(hipMemcpyAsync(dRootDst, dSrc, bytes, hipMemcpyDeviceToDevice, stream));
-        return false;
-    }
-    int direct = 0;
-    if (device != rootDevice) HIP_CHECK(hipDeviceCanAccessPeer(&direct, device, rootDevice));
-    if (forceStaged) direct = 0;
-    if (direct) {
-        const hipError_t enabled = hipDeviceEnablePeerAccess(rootDevice, 0);   // (this thread's current device is `device`)
-        if (enabled != hipSuccess && enabled != hipErrorPeerAccessAlreadyEnabled) direct = 0;
-        (void)hipGetLastError();
-    }
-    if (direct) {
-        HIP_CHECK(hipMemcpyPeerAsync(dRootDst, rootDevice, dSrc, device, bytes, stream));
-        return false;
-    }
-    std::fprintf(stderr, "[ptr] device %d does not address device %d directly: its bands go through pinned host memory\n", device, rootDevice);
-    void* staging = nullptr;
-    HIP_CHECK(hipHostMalloc(&staging, bytes, hipHostMallocDefault));
-    hipError_t copied = hipMemcpyAsync(staging, dSrc, bytes, hipMemcpyDeviceToHost, stream);
-    if (copied == hipSuccess) copied = hipStreamSynchronize(stream);
-    if (copied == hipSuccess) copied = hipSetDevice(rootDevice);
-    if (copied == hipSuccess) copied = hipMemcpy(dRootDst, staging, bytes, hipMemcpyHostToDevice);
-    (void)hipSetDevice(device);
-    (void)hipHostFree(staging);
-    HIP_CHECK(copied);
-    return true;
-}
-
 }  // namespace ptrhost
 
 extern "C" {
@@ -1178,22 +1157,7 @@ uint32_t ptr_part_band_count(uint32_t height, uint32_t part_index, uint32_t part
 }
 
 int ptr_scene_upload(const PtrSceneDesc* scene, int device, PtrDeviceScene** out_scene, char* err, size_t err_cap) {
-    if (!scene || !out_scene) {
-        setErr(err, err_cap, "ptr_scene_upload: null argument");
-        return 1;
-    }
-    if (ptr_device_count() <= device || device < 0) {
-        setErr(err, err_cap, "ptr_scene_upload: no such HIP device (the HIP path has no CPU fallback)");
-        return 2;
-    }
-    try {
-        auto ds = std::make_unique<PtrDeviceScene>();
-        ds->device = device;
-        buildScene(*scene, *ds);
-        *out_scene = ds.release();
-        return 0;
-    }
-    PTR_CATCH_ALL(err, err_cap)
+    return uploadTo("ptr_scene_upload", scene, nullptr, device, out_scene, err, err_cap);
 }
 
 void ptr_scene_release(PtrDeviceScene* scene) {
@@ -1232,22 +1196,8 @@ int ptr_scene_prepare_geometry(const PtrSceneDesc* scene, const char* cache_path
 }
 
 int ptr_scene_upload_prepared(const PtrSceneDesc* scene, const char* cache_path, int device, PtrDeviceScene** out_scene, char* err, size_t err_cap) {
-    if (!scene || !out_scene || !cache_path || !*cache_path) {
-        setErr(err, err_cap, "ptr_scene_upload_prepared: null argument");
-        return 1;
-    }
-    if (ptr_device_count() <= device || device < 0) {
-        setErr(err, err_cap, "ptr_scene_upload_prepared: no such HIP device (the HIP path has no CPU fallback)");
-        return 2;
-    }
-    try {
-        auto ds = std::make_unique<PtrDeviceScene>();
-        ds->device = device;
-        buildScene(*scene, *ds, cache_path);
-        *out_scene = ds.release();
-        return 0;
-    }
-    PTR_CATCH_ALL(err, err_cap)
+    if (!cache_path || !*cache_path) return nullArgument("ptr_scene_upload_prepared", err, err_cap);
+    return uploadTo("ptr_scene_upload_prepared", scene, cache_path, device, out_scene, err, err_cap);
 }
 
 int ptr_render_bands_device(PtrDeviceScene* scene, const PtrSettings* settings, uint32_t spp, uint32_t part_index,
@@ -1316,152 +1266,6 @@ int ptr_render(const PtrSceneDesc* scene, const PtrSettings* settings, uint32_t 
     }
     ptr_scene_release(ds);
     return rc;
-}
-
-// A frame on several devices: the scene is prepared once on the host, every device gets its own copy (uploads run in
-// parallel, one host thread per device), renders the bands b = rank (mod n) and hands them to the first device over the
-// fabric (hipMemcpyPeerAsync: xGMI between the GPUs of a node), which interleaves them into the image.
-// device_ids may name the same device more than once (how the single-GPU tests exercise the whole path).
-static int renderMulti(const PtrSceneDesc* scene, const PtrSettings* settings, uint32_t spp, const int* device_ids, int n, int verbose,
-                       float* out_rgb, PtrRenderStats* stats, char* err, size_t err_cap) {
-    try {
-        if (settings->width == 0 || settings->height == 0) throw HipError{"render size must be non-zero"};
-        const int available = ptr_device_count();
-        if (available < 1) throw HipError{"no HIP device (the HIP path has no CPU fallback)"};
-        // (test hook of ptr_debug_render_multi_on: an id given as -(id + 1) sends that partition's bands through the host-staging path)
-        std::vector<int> devices(static_cast<size_t>(n));
-        std::vector<char> forceStaged(static_cast<size_t>(n), 0);
-        for (int i = 0; i < n; ++i) {
-            forceStaged[static_cast<size_t>(i)] = device_ids[i] < 0 ? 1 : 0;
-            devices[static_cast<size_t>(i)] = device_ids[i] < 0 ? -device_ids[i] - 1 : device_ids[i];
-            if (devices[static_cast<size_t>(i)] >= available) throw HipError{"ptr_render_multi: no such HIP device"};
-        }
-        device_ids = devices.data();
-        const auto t0 = std::chrono::steady_clock::now();
-        PreparedScene prepared;
-        prepareScene(*scene, prepared);
-
-        const uint32_t parts = static_cast<uint32_t>(n);
-        const uint32_t width = settings->width, height = settings->height;
-        const size_t rowFloats = static_cast<size_t>(width) * 3u;
-        std::vector<uint64_t> partOffset(parts + 1u, 0u);
-        for (uint32_t p = 0; p < parts; ++p) {
-            partOffset[p + 1u] = partOffset[p] + static_cast<uint64_t>(ptr_part_band_count(height, p, parts)) * PTR_BAND_ROWS * rowFloats;
-        }
-        const int rootDevice = device_ids[0];
-        DeviceBuffer<float> gathered, image;
-        DeviceBuffer<uint64_t> dOffsets;
-        HIP_CHECK(hipSetDevice(rootDevice));
-        gathered.ensure(partOffset[parts]);
-        image.ensure(rowFloats * height);
-        dOffsets.upload(partOffset.data(), parts);
-
-        std::vector<std::unique_ptr<PtrDeviceScene>> scenes(parts);
-        std::vector<PtrRenderStats> partStats(parts);
-        std::vector<std::string> errors(parts);
-        std::vector<double> uploadSeconds(parts, 0.0), renderSeconds(parts, 0.0);
-        std::atomic<uint32_t> stagedParts{0};   // partitions whose bands went through host memory (no peer access)
-        auto worker = [&](uint32_t p) {
-            try {
-                const auto w0 = std::chrono::steady_clock::now();
-                auto ds = std::make_unique<PtrDeviceScene>();
-                ds->device = device_ids[p];
-                uploadScene(*scene, prepared, *ds);
-                uploadSeconds[p] = std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count();
-                const size_t floats = static_cast<size_t>(partOffset[p + 1u] - partOffset[p]);
-                HIP_CHECK(hipSetDevice(ds->device));
-                ds->outBands.ensure(floats);
-                hipStream_t stream = nullptr;
-                HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-                const auto r0 = std::chrono::steady_clock::now();
-                renderBands(*ds, *settings, spp, p, parts, ds->outBands.ptr, stream, 0, &partStats[p]);
-                if (floats && sendBandsToRoot(gathered.ptr + partOffset[p], rootDevice, ds->outBands.ptr, ds->device, floats * sizeof(float),
-                                              forceStaged[p] != 0, stream)) {
-                    stagedParts.fetch_add(1);
-                }
-                HIP_CHECK(hipStreamSynchronize(stream));
-                renderSeconds[p] = std::chrono::duration<double>(std::chrono::steady_clock::now() - r0).count();
-                HIP_CHECK(hipStreamDestroy(stream));
-                scenes[p] = std::move(ds);
-            } catch (const HipError& e) {
-                errors[p] = e.message;
-            } catch (const std::exception& e) {
-                errors[p] = std::string("exception: ") + e.what();
-            } catch (...) {
-                errors[p] = "unknown exception";
-            }
-        };
-        ptr::runOnThreads(parts, worker);
-        for (uint32_t p = 0; p < parts; ++p) {
-            if (!errors[p].empty()) throw HipError{"device " + std::to_string(device_ids[p]) + ": " + errors[p]};
-        }
-        HIP_CHECK(hipSetDevice(rootDevice));
-        launchInterleaveBands(gathered.ptr, dOffsets.ptr, parts, width, height, image.ptr, nullptr);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipMemcpy(out_rgb, image.ptr, rowFloats * height * sizeof(float), hipMemcpyDeviceToHost));
-        const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        double slowestRender = 0.0, slowestUpload = 0.0;
-        for (uint32_t p = 0; p < parts; ++p) {
-            slowestRender = std::max(slowestRender, renderSeconds[p]);
-            slowestUpload = std::max(slowestUpload, uploadSeconds[p]);
-        }
-        if (stats) {
-            std::memset(stats, 0, sizeof(*stats));
-            // the integrate phase of the whole job: the slowest device's render + hand-over (devices run concurrently)
-            stats->totalSeconds = slowestRender;
-            stats->avgMsPerSample = slowestRender * 1000.0 / std::max(1u, spp);
-            stats->uploadSeconds = prepared.seconds + slowestUpload;
-            for (uint32_t p = 0; p < parts; ++p) addLaunchStats(*stats, partStats[p]);
-        }
-        if (verbose) {
-            std::fprintf(stderr, "[ptr] %d device(s): scene preparation %.3f s, slowest upload %.3f s, slowest render + hand-over %.3f s, whole call %.3f s\n", n,
-                         prepared.seconds, slowestUpload, slowestRender, wall);
-            for (uint32_t p = 0; p < parts; ++p) {
-                std::fprintf(stderr, "[ptr]   device %d: %u bands, render %.3f s\n", device_ids[p], ptr_part_band_count(height, p, parts), renderSeconds[p]);
-            }
-        }
-        for (uint32_t p = 0; p < parts; ++p) {
-            if (scenes[p]) {
-                (void)hipSetDevice(scenes[p]->device);
-                scenes[p].reset();
-            }
-        }
-        (void)hipSetDevice(rootDevice);
-        return 0;
-    }
-    PTR_CATCH_ALL(err, err_cap)
-}
-
-int ptr_render_multi(const PtrSceneDesc* scene, const PtrSettings* settings, uint32_t spp, int n_devices, int verbose, float* out_rgb,
-                     PtrRenderStats* stats, char* err, size_t err_cap) {
-    if (!scene || !settings || !out_rgb) {
-        setErr(err, err_cap, "ptr_render_multi: null argument");
-        return 1;
-    }
-    const int available = ptr_device_count();
-    if (available < 1) {
-        setErr(err, err_cap, "ptr_render_multi: no HIP device (the HIP path has no CPU fallback)");
-        return 2;
-    }
-    int n = n_devices <= 0 ? available : n_devices;
-    if (n > available) {
-        setErr(err, err_cap, "ptr_render_multi: " + std::to_string(n) + " devices requested, " + std::to_string(available) + " visible");
-        return 2;
-    }
-    // never more partitions than bands
-    n = static_cast<int>(std::min<uint32_t>(static_cast<uint32_t>(n), std::max(1u, (settings->height + PTR_BAND_ROWS - 1u) / PTR_BAND_ROWS)));
-    std::vector<int> ids(static_cast<size_t>(n));
-    for (int i = 0; i < n; ++i) ids[static_cast<size_t>(i)] = i;
-    return renderMulti(scene, settings, spp, ids.data(), n, verbose, out_rgb, stats, err, err_cap);
-}
-
-int ptr_debug_render_multi_on(const PtrSceneDesc* scene, const PtrSettings* settings, uint32_t spp, const int* device_ids, int n, float* out_rgb,
-                              PtrRenderStats* stats, char* err, size_t err_cap) {
-    if (!scene || !settings || !out_rgb || !device_ids || n < 1) {
-        setErr(err, err_cap, "ptr_debug_render_multi_on: bad argument");
-        return 1;
-    }
-    return renderMulti(scene, settings, spp, device_ids, n, 0, out_rgb, stats, err, err_cap);
 }
 
 int ptr_trace_rays(PtrDeviceScene* scene, const float* rays, uint64_t n, int any_hit, PtrHit* out, PtrRenderStats* stats,

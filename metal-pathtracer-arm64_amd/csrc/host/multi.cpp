@@ -1,8 +1,10 @@
-// Host side of include/ptr_multi.h: the argument checks, one host thread per partition (each with its own device scene and stream, as
-// ptr_render_multi), the lock-step rounds of an adaptive frame with the exchange of the band-edge rows of e between them, and the finish
-// and gather in band layout.  The sample source of a pass is a parameter of the partition loop: the traced one for the renderer, the
-// gathered one for the test-only probe, which therefore runs everything else the renderer runs.  The state's buffers, the sources and
-// the sample step are the ones adaptive.cpp and frame.cpp use (adaptive_host.h); the halo goes out from the step's hook.
+// Every frame on several devices: ptr_render_multi (include/ptr_abi.h) with its test-only variant of include/ptr_debug.h, and the frames of
+// include/ptr_multi.h that carry a covariance or are sampled adaptively.  The argument checks, the scene prepared once, one host thread
+// per partition (each with its own device scene and stream), the lock-step rounds of an adaptive frame with the exchange of the band-edge
+// rows of e between them, the hand-over of the band-layout buffers to the first device, which interleaves them into the image.  The
+// sample source of a pass is a parameter of the partition loop: the traced one for the renderer, the gathered one for the test-only probe,
+// which therefore runs everything else the renderer runs.  The state's buffers, the sources and the sample step are the ones adaptive.cpp
+// and frame.cpp use (adaptive_host.h); the halo goes out from the step's hook.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -17,6 +19,7 @@
 #include "device_scene.h"
 #include "knobs.h"
 #include "parallel.h"
+#include "ptr_debug.h"
 #include "ptr_multi.h"
 #include "round_barrier.h"
 
@@ -28,16 +31,20 @@ namespace {
 using Clock = std::chrono::steady_clock;
 double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
 
-// What one call asks for.  scene == nullptr: the probe (samples != nullptr); params == nullptr: the uniform frame with covariance.
+// What one call asks for.  The kind says which pointers it needs and what it reports; everything else runFrame reads off the outputs asked for.
+enum class Kind { Plain, Covariance, Adaptive, Probe };   // ptr_render_multi; ..._cov; ..._adaptive; the test-only probe, which has no scene
 struct Request {
     const char* who = "";
+    Kind kind = Kind::Plain;
     const PtrSceneDesc* scene = nullptr;
-    PtrSettings settings{};   // the probe fills in width and height only
+    const PtrSettings* settings = nullptr;   // the probe fills in width and height only
     uint32_t spp = 0u;
     const PtrAdaptiveParams* params = nullptr;
     const float* samples = nullptr;
-    std::vector<int> devices;
-    std::vector<char> forceStaged;
+    // the devices asked for: the n that `ids` lists (the debug variants), or the first n (n <= 0: all there are)
+    const int* ids = nullptr;
+    int n = 0;
+    bool listed = false;
     int verbose = 0;
     float* outRgb = nullptr;
     float* outCov = nullptr;
@@ -47,6 +54,8 @@ struct Request {
     PtrRenderStats* stats = nullptr;
     PtrAdaptiveInfo* info = nullptr;
     PtrMultiInfo* multi = nullptr;
+    std::vector<int> devices;   // admit fills these two in
+    std::vector<char> forceStaged;
 };
 
 // The pinned host memory the partitions exchange their edge rows through (portable: every device's copies may use it).  Partition p
@@ -61,11 +70,44 @@ struct Exchange {
     float* inbox(uint32_t p) const { return host + offset.back() + offset[p]; }
 };
 
+// A partition's band buffer travels to the first device of the frame: a plain copy when it is local, device-to-device over the fabric
+// when the two devices can address each other, through pinned host memory otherwise (or with forceStaged, the tests' hook).  Called on
+// the partition's thread with `device` current; asynchronous on `stream` except for the staged path.  True when the bytes were staged.
+bool sendBandsToRoot(void* dRootDst, int rootDevice, const void* dSrc, int device, size_t bytes, bool forceStaged, hipStream_t stream) {
+    if (device == rootDevice && !forceStaged) {
+        HIP_CHECK(hipMemcpyAsync(dRootDst, dSrc, bytes, hipMemcpyDeviceToDevice, stream));
+        return false;
+    }
+    int direct = 0;
+    if (device != rootDevice) HIP_CHECK(hipDeviceCanAccessPeer(&direct, device, rootDevice));
+    if (forceStaged) direct = 0;
+    if (direct) {
+        const hipError_t enabled = hipDeviceEnablePeerAccess(rootDevice, 0);   // (this thread's current device is `device`)
+        if (enabled != hipSuccess && enabled != hipErrorPeerAccessAlreadyEnabled) direct = 0;
+        (void)hipGetLastError();
+    }
+    if (direct) {
+        HIP_CHECK(hipMemcpyPeerAsync(dRootDst, rootDevice, dSrc, device, bytes, stream));
+        return false;
+    }
+    std::fprintf(stderr, "[ptr] device %d does not address device %d directly: its bands go through pinned host memory\n", device, rootDevice);
+    void* staging = nullptr;
+    HIP_CHECK(hipHostMalloc(&staging, bytes, hipHostMallocDefault));
+    hipError_t copied = hipMemcpyAsync(staging, dSrc, bytes, hipMemcpyDeviceToHost, stream);
+    if (copied == hipSuccess) copied = hipStreamSynchronize(stream);
+    if (copied == hipSuccess) copied = hipSetDevice(rootDevice);
+    if (copied == hipSuccess) copied = hipMemcpy(dRootDst, staging, bytes, hipMemcpyHostToDevice);
+    (void)hipSetDevice(device);
+    (void)hipHostFree(staging);
+    HIP_CHECK(copied);
+    return true;
+}
+
 void runFrame(const Request& rq) {
-    const bool adaptive = rq.params != nullptr;
-    const bool probe = rq.scene == nullptr;
+    const bool probe = rq.kind == Kind::Probe, adaptive = probe || rq.kind == Kind::Adaptive;
+    const PtrSettings& settings = *rq.settings;
     const uint32_t parts = static_cast<uint32_t>(rq.devices.size());
-    const uint32_t width = rq.settings.width, height = rq.settings.height;
+    const uint32_t width = settings.width, height = settings.height;
     const size_t pixels = static_cast<size_t>(width) * height;
     if (pastIndexLimit(pixels + static_cast<size_t>(PTR_BAND_ROWS) * width)) throw HipError{"image too large"};
     const auto t0 = Clock::now();
@@ -136,7 +178,7 @@ void runFrame(const Request& rq) {
         float* const dCov = wantCov ? dRgb + myBandPixels * covAt : nullptr;
         uint32_t* const dCount = wantCount ? reinterpret_cast<uint32_t*>(dRgb + myBandPixels * countAt) : nullptr;
 
-        auto handOver = [&] {   // the band buffer travels to the first device (the three transports of ptr_render_multi), in one piece
+        auto handOver = [&] {   // the band buffer travels to the first device in one piece
             if (myBandPixels && sendBandsToRoot(gathered.ptr + wordOffset[p], rootDevice, dRgb, ds->device, myBandPixels * pixelWords * sizeof(float),
                                                 rq.forceStaged[p] != 0, stream)) {
                 stagedParts.fetch_add(1);
@@ -146,10 +188,8 @@ void runFrame(const Request& rq) {
 
         if (!adaptive) {
             const auto r0 = Clock::now();
-            if (myBandPixels) renderBands(*ds, rq.settings, rq.spp, p, parts, dRgb, stream, 0, &partStats[p], dCov);
-            std::vector<uint32_t> order;
-            partitionPixels(width, height, p, parts, order);
-            partSamples[p] = static_cast<uint64_t>(order.size()) * rq.spp;
+            if (myBandPixels) renderBands(*ds, settings, rq.spp, p, parts, dRgb, stream, 0, &partStats[p], dCov);
+            partSamples[p] = partStats[p].samples;   // the partition's pixels, as renderPass counted them, times spp
             handOver();
             renderSeconds[p] = since(r0);
             scenes[p] = std::move(ds);
@@ -174,7 +214,7 @@ void runFrame(const Request& rq) {
             probeItems.ensure(static_cast<size_t>(std::max<uint64_t>(local, std::min<uint64_t>(step.maxItems, static_cast<uint64_t>(local) * mostSpp))));
             step.source = gatheredSource(probeSamples.ptr, pixels, params.maxSpp, probeItems, stream);
         } else {
-            step.source = tracedSource(*ds, rq.settings, stream);
+            step.source = tracedSource(*ds, settings, stream);
         }
         if (local) HIP_CHECK(hipMemcpyAsync(b.list(0u), order.data(), local * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
         b.zero(stream);
@@ -298,7 +338,7 @@ void runFrame(const Request& rq) {
     if (wantCount) HIP_CHECK(hipMemcpy(rq.outCount, iCount, pixels * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (!probe && (rq.outAlbedo || rq.outNormal)) {   // the first partition's scene is on the first device
         RenderParams rp;
-        fillRenderParams(rq.settings, 1u, rp);
+        fillRenderParams(settings, 1u, rp);
         DeviceBuffer<float4> albedo, normal;
         albedo.ensure(pixels);
         normal.ensure(pixels);
@@ -349,53 +389,63 @@ void runFrame(const Request& rq) {
     if (rq.verbose) {
         std::fprintf(stderr, "[ptr] %u device(s): scene preparation %.3f s, slowest upload %.3f s, slowest render + hand-over %.3f s, whole call %.3f s\n", parts,
                      prepared.seconds, slowestUpload, slowestRender, wall);
+        const bool plain = rq.kind == Kind::Plain;   // the plain frame reports the render time of each partition and nothing more
         // (tools/multi_adaptive_cost.py parses this line; the partitions' threads are what the whole call has beside the other four)
-        std::fprintf(stderr, "[ptr]   outside the partitions' threads: first-device buffers %.4f s, interleave + download %.4f s, release of the scenes %.4f s\n",
-                     setupSeconds, gatherSeconds, wall - partsDone - gatherSeconds);
+        if (!plain) {
+            std::fprintf(stderr, "[ptr]   outside the partitions' threads: first-device buffers %.4f s, interleave + download %.4f s, release of the scenes %.4f s\n",
+                         setupSeconds, gatherSeconds, wall - partsDone - gatherSeconds);
+        }
         for (uint32_t p = 0; p < parts; ++p) {
+            if (plain) {
+                std::fprintf(stderr, "[ptr]   device %d: %u bands, render %.3f s\n", rq.devices[p], partBands[p], renderSeconds[p]);
+                continue;
+            }
             std::fprintf(stderr, "[ptr]   device %d: %u bands, %llu samples, upload %.4f s, state %.4f s, render %.4f s, of which waiting %.4f s\n", rq.devices[p],
                          partBands[p], static_cast<unsigned long long>(partSamples[p]), uploadSeconds[p], stateSeconds[p], renderSeconds[p], waitSeconds[p]);
         }
     }
 }
 
-// The checks every entry point makes before any device call, then the device list: `ids` (n of them, the debug variants' list) or the
-// first n_devices devices.  Returns the C-ABI's code; 0 with rq.devices filled in.
-int admit(Request& rq, bool pointersOk, const int* ids, int n, bool explicitIds, int nDevices, char* err, size_t cap) {
+// The checks every entry point makes before any device call, then the device list.  Returns the C-ABI's code; 0 with rq.devices filled in.
+int admit(Request& rq, char* err, size_t cap) {
     const std::string w(rq.who);
+    const bool probe = rq.kind == Kind::Probe, adaptive = probe || rq.kind == Kind::Adaptive;
+    if (!(probe ? rq.samples != nullptr : rq.scene != nullptr) || !rq.settings || !rq.outRgb || (adaptive && !rq.params) || (rq.listed && !rq.ids)) {
+        return nullArgument(rq.who, err, cap);
+    }
     std::string bad;
-    if (!pointersOk) bad = w + ": null argument";
-    else if (rq.settings.width == 0u || rq.settings.height == 0u) bad = w + ": render size must be non-zero";
-    else if (rq.params) bad = badAdaptiveParams(rq.who, *rq.params);
-    else if (rq.spp < 2u) bad = w + ": a sample covariance needs spp >= 2";
-    if (bad.empty() && explicitIds && (n < 1 || n > PTR_MULTI_MAX_PARTS)) bad = w + ": the id list must name 1 .. " + std::to_string(PTR_MULTI_MAX_PARTS) + " devices";
-    if (bad.empty() && !explicitIds && nDevices > PTR_MULTI_MAX_PARTS) bad = w + ": at most " + std::to_string(PTR_MULTI_MAX_PARTS) + " devices";
+    if (rq.settings->width == 0u || rq.settings->height == 0u) bad = w + ": render size must be non-zero";
+    else if (adaptive) bad = badAdaptiveParams(rq.who, *rq.params);
+    else if (rq.kind == Kind::Covariance && rq.spp < 2u) bad = w + ": a sample covariance needs spp >= 2";
+    if (bad.empty() && rq.listed && (rq.n < 1 || rq.n > PTR_MULTI_MAX_PARTS)) bad = w + ": the id list must name 1 .. " + std::to_string(PTR_MULTI_MAX_PARTS) + " devices";
+    if (bad.empty() && !rq.listed && rq.n > PTR_MULTI_MAX_PARTS) bad = w + ": at most " + std::to_string(PTR_MULTI_MAX_PARTS) + " devices";
     if (!bad.empty()) return refuse(err, cap, bad);
     const int available = ptr_device_count();
     if (available < 1) return noDevice(rq.who, err, cap);
-    if (explicitIds) {
-        for (int i = 0; i < n; ++i) {
-            const int id = ids[i] < 0 ? -(ids[i] + 1) : ids[i];
+    if (rq.listed) {   // (an id given as -(id + 1) sends that partition's bands through pinned host memory: the tests' hook)
+        for (int i = 0; i < rq.n; ++i) {
+            const int id = rq.ids[i] < 0 ? -(rq.ids[i] + 1) : rq.ids[i];
             if (id < 0 || id >= available) return refuse(err, cap, w + ": no such HIP device");
             rq.devices.push_back(id);
-            rq.forceStaged.push_back(ids[i] < 0 ? 1 : 0);
+            rq.forceStaged.push_back(rq.ids[i] < 0 ? 1 : 0);
         }
         return 0;
     }
-    int count = nDevices <= 0 ? available : nDevices;
+    int count = rq.n <= 0 ? available : rq.n;
     if (count > available) {
         setErr(err, cap, w + ": " + std::to_string(count) + " devices requested, " + std::to_string(available) + " visible");
         return 2;
     }
     count = std::min(count, PTR_MULTI_MAX_PARTS);
     // never more partitions than bands
-    count = static_cast<int>(std::min<uint32_t>(static_cast<uint32_t>(count), std::max(1u, (rq.settings.height + PTR_BAND_ROWS - 1u) / PTR_BAND_ROWS)));
+    count = static_cast<int>(std::min<uint32_t>(static_cast<uint32_t>(count), std::max(1u, (rq.settings->height + PTR_BAND_ROWS - 1u) / PTR_BAND_ROWS)));
     for (int i = 0; i < count; ++i) rq.devices.push_back(i);
     rq.forceStaged.assign(static_cast<size_t>(count), 0);
     return 0;
 }
 
-int run(const Request& rq, char* err, size_t cap) {
+int frame(Request& rq, char* err, size_t cap) {
+    if (const int rc = admit(rq, err, cap)) return rc;
     try {
         runFrame(rq);
         return 0;
@@ -403,86 +453,91 @@ int run(const Request& rq, char* err, size_t cap) {
     PTR_CATCH_ALL(err, cap)
 }
 
-int covFrame(const char* who, const PtrSceneDesc* scene, const PtrSettings* settings, uint32_t spp, const int* ids, int n, bool explicitIds, int nDevices,
-             int verbose, float* outRgb, float* outCov, float* outAlbedo, float* outNormal, PtrRenderStats* stats, PtrMultiInfo* multi, char* err,
-             size_t cap) {
-    Request rq;
-    rq.who = who;
-    const bool ok = scene && settings && outRgb && (!explicitIds || ids);
-    if (ok) rq.settings = *settings;
-    rq.scene = scene;
-    rq.spp = spp;
-    rq.verbose = verbose;
-    rq.outRgb = outRgb, rq.outCov = outCov, rq.outAlbedo = outAlbedo, rq.outNormal = outNormal;
-    rq.stats = stats, rq.multi = multi;
-    if (const int rc = admit(rq, ok, ids, n, explicitIds, nDevices, err, cap)) return rc;
-    return run(rq, err, cap);
-}
-
-int adaptiveFrame(const char* who, const PtrSceneDesc* scene, const PtrSettings* settings, const PtrAdaptiveParams* params, const int* ids, int n,
-                  bool explicitIds, int nDevices, int verbose, float* outRgb, float* outCov, uint32_t* outCount, float* outAlbedo, float* outNormal,
-                  PtrRenderStats* stats, PtrAdaptiveInfo* info, PtrMultiInfo* multi, char* err, size_t cap) {
-    Request rq;
-    rq.who = who;
-    const bool ok = scene && settings && params && outRgb && (!explicitIds || ids);
-    if (ok) rq.settings = *settings;
-    rq.scene = scene;
-    rq.params = ok ? params : nullptr;
-    rq.verbose = verbose;
-    rq.outRgb = outRgb, rq.outCov = outCov, rq.outCount = outCount, rq.outAlbedo = outAlbedo, rq.outNormal = outNormal;
-    rq.stats = stats, rq.info = info, rq.multi = multi;
-    if (const int rc = admit(rq, ok, ids, n, explicitIds, nDevices, err, cap)) return rc;
-    return run(rq, err, cap);
-}
-
 }  // namespace
 
 extern "C" {
 
+int ptr_render_multi(const PtrSceneDesc* scene, const PtrSettings* settings, uint32_t spp, int n_devices, int verbose, float* out_rgb,
+                     PtrRenderStats* stats, char* err, size_t err_cap) {
+    Request rq;
+    rq.who = "ptr_render_multi", rq.kind = Kind::Plain;
+    rq.scene = scene, rq.settings = settings, rq.spp = std::max(1u, spp);   // (spp 0 renders one sample, as renderBands has it)
+    rq.n = n_devices, rq.verbose = verbose;
+    rq.outRgb = out_rgb, rq.stats = stats;
+    return frame(rq, err, err_cap);
+}
+
+int ptr_debug_render_multi_on(const PtrSceneDesc* scene, const PtrSettings* settings, uint32_t spp, const int* device_ids, int n, float* out_rgb,
+                              PtrRenderStats* stats, char* err, size_t err_cap) {
+    Request rq;
+    rq.who = "ptr_debug_render_multi_on", rq.kind = Kind::Plain;
+    rq.scene = scene, rq.settings = settings, rq.spp = std::max(1u, spp);
+    rq.ids = device_ids, rq.n = n, rq.listed = true;
+    rq.outRgb = out_rgb, rq.stats = stats;
+    return frame(rq, err, err_cap);
+}
+
 int ptr_render_multi_cov(const PtrSceneDesc* scene, const PtrSettings* settings, uint32_t spp, int n_devices, int verbose, float* out_rgb,
                          float* out_cov, float* out_albedo, float* out_normal, PtrRenderStats* stats, PtrMultiInfo* multi_info, char* err,
                          size_t err_cap) {
-    return covFrame("ptr_render_multi_cov", scene, settings, spp, nullptr, 0, false, n_devices, verbose, out_rgb, out_cov, out_albedo, out_normal, stats,
-                    multi_info, err, err_cap);
+    Request rq;
+    rq.who = "ptr_render_multi_cov", rq.kind = Kind::Covariance;
+    rq.scene = scene, rq.settings = settings, rq.spp = spp;
+    rq.n = n_devices, rq.verbose = verbose;
+    rq.outRgb = out_rgb, rq.outCov = out_cov, rq.outAlbedo = out_albedo, rq.outNormal = out_normal;
+    rq.stats = stats, rq.multi = multi_info;
+    return frame(rq, err, err_cap);
 }
 
 int ptr_render_multi_adaptive(const PtrSceneDesc* scene, const PtrSettings* settings, const PtrAdaptiveParams* params, int n_devices,
                               int verbose, float* out_rgb, float* out_cov, uint32_t* out_count, float* out_albedo, float* out_normal,
                               PtrRenderStats* stats, PtrAdaptiveInfo* adaptive_info, PtrMultiInfo* multi_info, char* err, size_t err_cap) {
-    return adaptiveFrame("ptr_render_multi_adaptive", scene, settings, params, nullptr, 0, false, n_devices, verbose, out_rgb, out_cov, out_count, out_albedo,
-                         out_normal, stats, adaptive_info, multi_info, err, err_cap);
+    Request rq;
+    rq.who = "ptr_render_multi_adaptive", rq.kind = Kind::Adaptive;
+    rq.scene = scene, rq.settings = settings, rq.params = params;
+    rq.n = n_devices, rq.verbose = verbose;
+    rq.outRgb = out_rgb, rq.outCov = out_cov, rq.outCount = out_count, rq.outAlbedo = out_albedo, rq.outNormal = out_normal;
+    rq.stats = stats, rq.info = adaptive_info, rq.multi = multi_info;
+    return frame(rq, err, err_cap);
 }
 
 int ptr_multi_debug_cov_on(const PtrSceneDesc* scene, const PtrSettings* settings, uint32_t spp, const int* device_ids, int n,
                            float* out_rgb, float* out_cov, float* out_albedo, float* out_normal, PtrRenderStats* stats,
                            PtrMultiInfo* multi_info, char* err, size_t err_cap) {
-    return covFrame("ptr_multi_debug_cov_on", scene, settings, spp, device_ids, n, true, 0, 0, out_rgb, out_cov, out_albedo, out_normal, stats, multi_info, err,
-                    err_cap);
+    Request rq;
+    rq.who = "ptr_multi_debug_cov_on", rq.kind = Kind::Covariance;
+    rq.scene = scene, rq.settings = settings, rq.spp = spp;
+    rq.ids = device_ids, rq.n = n, rq.listed = true;
+    rq.outRgb = out_rgb, rq.outCov = out_cov, rq.outAlbedo = out_albedo, rq.outNormal = out_normal;
+    rq.stats = stats, rq.multi = multi_info;
+    return frame(rq, err, err_cap);
 }
 
 int ptr_multi_debug_adaptive_on(const PtrSceneDesc* scene, const PtrSettings* settings, const PtrAdaptiveParams* params,
                                 const int* device_ids, int n, float* out_rgb, float* out_cov, uint32_t* out_count, float* out_albedo,
                                 float* out_normal, PtrRenderStats* stats, PtrAdaptiveInfo* adaptive_info, PtrMultiInfo* multi_info,
                                 char* err, size_t err_cap) {
-    return adaptiveFrame("ptr_multi_debug_adaptive_on", scene, settings, params, device_ids, n, true, 0, 0, out_rgb, out_cov, out_count, out_albedo, out_normal,
-                         stats, adaptive_info, multi_info, err, err_cap);
+    Request rq;
+    rq.who = "ptr_multi_debug_adaptive_on", rq.kind = Kind::Adaptive;
+    rq.scene = scene, rq.settings = settings, rq.params = params;
+    rq.ids = device_ids, rq.n = n, rq.listed = true;
+    rq.outRgb = out_rgb, rq.outCov = out_cov, rq.outCount = out_count, rq.outAlbedo = out_albedo, rq.outNormal = out_normal;
+    rq.stats = stats, rq.info = adaptive_info, rq.multi = multi_info;
+    return frame(rq, err, err_cap);
 }
 
 int ptr_multi_debug_adaptive_frame(uint32_t width, uint32_t height, const PtrAdaptiveParams* params, const float* samples,
                                    const int* device_ids, int n, float* out_rgb, float* out_cov, uint32_t* out_count,
                                    PtrAdaptiveInfo* adaptive_info, char* err, size_t err_cap) {
+    PtrSettings size{};
+    size.width = width, size.height = height;
     Request rq;
-    rq.who = "ptr_multi_debug_adaptive_frame";
-    const bool ok = params && samples && device_ids && out_rgb;
-    rq.settings.width = width;
-    rq.settings.height = height;
-    if (!ok) rq.settings.width = rq.settings.height = 1u;   // (the null argument is reported first)
-    rq.params = ok ? params : nullptr;
-    rq.samples = samples;
+    rq.who = "ptr_multi_debug_adaptive_frame", rq.kind = Kind::Probe;
+    rq.settings = &size, rq.params = params, rq.samples = samples;
+    rq.ids = device_ids, rq.n = n, rq.listed = true;
     rq.outRgb = out_rgb, rq.outCov = out_cov, rq.outCount = out_count;
     rq.info = adaptive_info;
-    if (const int rc = admit(rq, ok, device_ids, n, true, 0, err, err_cap)) return rc;
-    return run(rq, err, err_cap);
+    return frame(rq, err, err_cap);
 }
 
 }  // extern "C"

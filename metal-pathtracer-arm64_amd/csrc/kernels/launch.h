@@ -48,10 +48,6 @@ void launchResolve(const RenderParams& rp, const PathPool& pool, uint32_t partCo
 // unnormalised sums until the last pass.
 void launchResolveCov(const RenderParams& rp, const PathPool& pool, uint32_t partCount, float4* dMean, float* dCov, hipStream_t stream);
 
-// Multi-device gather: writes image[y][x][c] from the partitions' band buffers laid end to end (dPartOffset: float offsets).
-void launchInterleaveBands(const float* dGathered, const uint64_t* dPartOffset, uint32_t parts, uint32_t width, uint32_t height, float* dImage,
-                           hipStream_t stream);
-
 void launchTraceRays(const SceneView& sc, const float4* dRays, uint64_t n, bool anyHit, PtrHit* dOut, const LaunchConfig& cfg,
                      uint64_t* dCounters, hipStream_t stream);
 

@@ -87,9 +87,9 @@ PTR_HD void multiFinishBands(const MultiPart& mp, uint32_t i, const AdaptiveStat
     if (count) count[i] = n;
 }
 
-// Interleave, word i of an image of `channels` 4-byte words per pixel (i < width * height * channels): the gather step of
-// k_interleave_bands.  `gathered` holds the partitions' buffers; this output's band layout of partition p starts at word
-// partWordOffset[p] (any layout of the buffers around it).  Words are copied as bits (the count image is uint32).
+// Interleave, word i of an image of `channels` 4-byte words per pixel (i < width * height * channels): the gather step of a frame on
+// several devices, image band b = local band b / P of partition b % P.  `gathered` holds the partitions' buffers; this output's band
+// layout of partition p starts at word partWordOffset[p] (any layout of the buffers around it: ptr_render_multi's hold rgb alone).  Words are copied as bits (the count image is uint32).
 PTR_HD void multiInterleave(uint64_t i, const uint32_t* gathered, const uint64_t* partWordOffset, uint32_t parts, uint32_t width, uint32_t channels,
                             uint32_t* image) {
     const uint64_t rowWords = static_cast<uint64_t>(width) * channels;

@@ -1,10 +1,10 @@
-// The kernels of a multi-device adaptive or covariance-carrying frame (include/ptr_multi.h; the per-element bodies are in multi.h).
+// The kernels of the frames on several devices (include/ptr_multi.h, and the gather of ptr_render_multi; the per-element bodies are in multi.h).
 // Compiled like adaptive.hip, unfused with correctly rounded division: k_multi_finish_bands has to give the bits of k_adaptive_finish.
 //
 // k_multi_halo_pack / k_multi_halo_unpack: one thread per float of the partition's edge rows; consecutive threads walk a row, so a wave
 // reads (pack) or writes (unpack) 256 contiguous bytes of the e image unless it straddles the end of a row.
 // k_multi_finish_bands: one thread per pixel position of the partition's band layout.
-// k_multi_interleave: one thread per 4-byte word of the image; k_interleave_bands of wavefront.hip for 3, 6 or 1 words per pixel.
+// k_multi_interleave: one thread per 4-byte word of the image, the gather step of every multi-device frame, for 3, 6 or 1 words per pixel.
 // k_multi_gather_items (probe only): one thread per (sample, list entry).
 #include <hip/hip_runtime.h>
 

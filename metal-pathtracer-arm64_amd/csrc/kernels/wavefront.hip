@@ -2267,21 +2267,6 @@ __global__ void __launch_bounds__(256) k_resolve(RenderParams rp, PathPool pool,
 }
 
 // =====================================================================================================
-// k_interleave_bands: the gather step of a multi-device frame.  `gathered` holds the band buffers of the P partitions one
-// after the other (partition p starts at float offset partOffset[p]); image band b = local band b / P of partition b % P.
-// =====================================================================================================
-__global__ void __launch_bounds__(256) k_interleave_bands(const float* gathered, const uint64_t* partOffset, uint32_t parts, uint32_t width,
-                                                          uint32_t height, float* image) {
-    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;   // one float of the image
-    const uint64_t rowFloats = static_cast<uint64_t>(width) * 3u;
-    if (i >= rowFloats * height) return;
-    const uint32_t y = static_cast<uint32_t>(i / rowFloats);
-    const uint64_t inRow = i - static_cast<uint64_t>(y) * rowFloats;
-    const uint32_t band = y / PTR_BAND_ROWS, part = band % parts, localBand = band / parts;
-    image[i] = gathered[partOffset[part] + (static_cast<uint64_t>(localBand) * PTR_BAND_ROWS + (y % PTR_BAND_ROWS)) * rowFloats + inRow];
-}
-
-// =====================================================================================================
 // k_aovs: first-hit feature buffers (what the reference hands to its denoiser: shaders/pathtrace.metal:6424-6435 sets
 // albedo = material base colour and normal = shading normal at the first hit; 9813-9815 writes albedo and
 // normal*0.5+0.5 per pixel).  One camera ray per pixel, the one sample `sample` of the path tracer starts with.
@@ -2815,12 +2800,6 @@ void launchTail(const RenderParams& rp, const SceneView& sc, const PathPool& poo
 void launchResolve(const RenderParams& rp, const PathPool& pool, uint32_t partCount, float* dOut, hipStream_t stream) {
     hipLaunchKernelGGL(k_flush, dim3(ceilDiv(pool.slots, 256)), dim3(256), 0, stream, rp, pool);
     hipLaunchKernelGGL(k_resolve, dim3(ceilDiv(rp.localPixels, 256)), dim3(256), 0, stream, rp, pool, partCount, dOut);
-}
-
-void launchInterleaveBands(const float* dGathered, const uint64_t* dPartOffset, uint32_t parts, uint32_t width, uint32_t height, float* dImage,
-                           hipStream_t stream) {
-    const uint64_t floats = static_cast<uint64_t>(width) * height * 3u;
-    hipLaunchKernelGGL(k_interleave_bands, dim3(ceilDiv(floats, 256)), dim3(256), 0, stream, dGathered, dPartOffset, parts, width, height, dImage);
 }
 
 void launchTraceRays(const SceneView& sc, const float4* dRays, uint64_t n, bool anyHit, PtrHit* dOut, const LaunchConfig& cfgIn,

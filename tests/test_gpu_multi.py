@@ -6,6 +6,9 @@ A device id may repeat in an id list, so one GPU runs every partition, the excha
 partition's bands through the pinned-host staging path.  The scene is tests/golden/cornell_small_mesh.scene at depth 4, seed 1337."""
 import importlib
 import os
+import re
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -196,3 +199,72 @@ def test_plain_multi_frame_before_and_after(cornell, frame):
     same_frame(pt.render_multi_adaptive(host.desc, s, p, device_ids=[0, 0, 0]), single, "between two plain frames")
     after, _ = pt.render_multi(host.desc, s, 5, device_ids=[0, 0, 0])
     assert np.array_equal(before, after) and np.array_equal(dev.render_image(s, 5)[0], before)
+
+
+# --------------------------------------------------------------------------- 7. the plain frame goes through the same driver
+def test_plain_frame_with_empty_partitions(cornell):
+    """37x21: three bands, the last of five rows, ragged 8x8 blocks.  The fourth partition owns no band and must not disturb the frame."""
+    host, dev = cornell
+    s = host.settings_for(width=37, height=21, max_depth=4, seed=1337)
+    want = dev.render_image(s, 5)[0]
+    for ids in ([0] * 4, [0, -1, 0, 0]):
+        got, stats = pt.render_multi(host.desc, s, 5, device_ids=ids)
+        assert np.array_equal(got, want), ids
+        assert stats.samples == 37 * 21 * 5, ids
+
+
+def test_plain_frame_takes_the_sample_counts_a_covariance_refuses(cornell):
+    """spp = 1, and spp = 0, which renders one sample and reports one."""
+    host, dev = cornell
+    s = host.settings_for(width=W, height=H, max_depth=4, seed=1337)
+    want = dev.render_image(s, 1)[0]
+    for spp in (1, 0):
+        got, stats = pt.render_multi(host.desc, s, spp, device_ids=[0, 0, 0])
+        assert np.array_equal(got, want), spp
+        assert stats.samples == W * H and stats.avgMsPerSample > 0, spp
+
+
+def test_plain_frame_in_sub_passes(cornell):
+    """PTR_MAX_ITEMS=1024: every partition renders its six samples in six passes, whose stats add up in the frame's."""
+    host, dev = cornell
+    s = host.settings_for(width=W, height=H, max_depth=4, seed=1337)
+    want = dev.render_image(s, 6)[0]
+    os.environ["PTR_MAX_ITEMS"] = "1024"
+    try:
+        got, stats = pt.render_multi(host.desc, s, 6, device_ids=[0, 0, 0])
+    finally:
+        del os.environ["PTR_MAX_ITEMS"]
+    assert np.array_equal(got, want)
+    assert stats.samples == W * H * 6
+
+
+# The child of test_plain_frame_verbose_report: argv = root.
+PLAIN_VERBOSE_CHILD = """
+import importlib, os, sys
+root = sys.argv[1]
+sys.path.insert(0, root)
+pt = importlib.import_module("metal-pathtracer-arm64_amd")
+host = pt.HostScene.load(os.path.join(root, "tests", "golden", "cornell_small_mesh.scene"), os.path.join(root, "scenes"))
+s = host.settings_for(width=%d, height=%d, max_depth=4, seed=1337)
+pt.render_multi(host.desc, s, 4, n_devices=1, verbose=True)
+""" % (W, H)
+
+
+def test_plain_frame_verbose_report():
+    """The plain frame reports two kinds of line: the call's, and one per partition with its bands and render time."""
+    r = subprocess.run([sys.executable, "-c", PLAIN_VERBOSE_CHILD, ROOT], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stderr.splitlines() if l.startswith("[ptr]")]
+    assert len(lines) == 2, lines
+    assert re.match(r"\[ptr\] 1 device\(s\): scene preparation [0-9.]+ s, slowest upload [0-9.]+ s, slowest render \+ hand-over [0-9.]+ s, "
+                    r"whole call [0-9.]+ s$", lines[0]), lines[0]
+    assert re.match(r"\[ptr\]   device 0: 9 bands, render [0-9.]+ s$", lines[1]), lines[1]
+
+
+def test_plain_frame_refusals_that_need_a_device(cornell):
+    host, _ = cornell
+    s = host.settings_for(width=W, height=H, max_depth=4, seed=1337)
+    with pytest.raises(pt.PtrError, match="ptr_render_multi: .*devices requested"):
+        pt.render_multi(host.desc, s, 4, n_devices=pt.device_count() + 1)
+    with pytest.raises(pt.PtrError, match="ptr_debug_render_multi_on: no such HIP device"):
+        pt.render_multi(host.desc, s, 4, device_ids=[0, pt.device_count()])

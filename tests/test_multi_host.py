@@ -19,6 +19,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 COUNTS = {"ptr_render_multi_cov": 13, "ptr_render_multi_adaptive": 15, "ptr_multi_debug_cov_on": 13, "ptr_multi_debug_adaptive_on": 15,
           "ptr_multi_debug_adaptive_frame": 12}
+# the plain frame (include/ptr_abi.h and its test-only variant of include/ptr_debug.h) goes through the same driver and the same checks
+PLAIN = ("ptr_render_multi", "ptr_debug_render_multi_on")
 
 
 # --------------------------------------------------------------------------- the surface
@@ -96,7 +98,11 @@ def _call(name, buf, desc="ok", settings="ok", params="ok", spp=4, ids=(0, 0), n
     stats, info, multi = pt.PtrRenderStats(), pt.PtrAdaptiveInfo(), pt.PtrMultiInfo()
     tail = (C.byref(stats), C.byref(multi), err, len(err))
     atail = (C.byref(stats), C.byref(info), C.byref(multi), err, len(err))
-    if name == "ptr_render_multi_cov":
+    if name == "ptr_render_multi":
+        rc = lib.ptr_render_multi(d, s, spp, n_devices, 0, out, C.byref(stats), err, len(err))
+    elif name == "ptr_debug_render_multi_on":
+        rc = lib.ptr_debug_render_multi_on(d, s, spp, idl, n, out, C.byref(stats), err, len(err))
+    elif name == "ptr_render_multi_cov":
         rc = lib.ptr_render_multi_cov(d, s, spp, n_devices, 0, out, fp(buf.cov), fp(buf.albedo), fp(buf.normal), *tail)
     elif name == "ptr_multi_debug_cov_on":
         rc = lib.ptr_multi_debug_cov_on(d, s, spp, idl, n, out, fp(buf.cov), fp(buf.albedo), fp(buf.normal), *tail)
@@ -118,7 +124,7 @@ def _bad_cases(name):
         cases += [dict(samples=None)]
     if "adaptive" in name:
         cases += [dict(params=None)] + [dict(params=p) for p in BAD_PARAMS]
-    else:
+    elif name not in PLAIN:
         cases += [dict(spp=0), dict(spp=1)]                      # a sample covariance needs two samples
     if "debug" in name:
         cases += [dict(ids=None), dict(ids=()), dict(ids=(0,) * 65)]
@@ -136,6 +142,29 @@ def test_bad_arguments_are_refused_by_name(name):
     if "adaptive" in name:
         assert "minSpp" in _call(name, buf, params=_params(min_spp=1))[1]
         assert "threshold" in _call(name, buf, params=_params(threshold=math.nan))[1]
+    assert buf.untouched()
+
+
+@pytest.mark.parametrize("name", PLAIN)
+def test_plain_frame_refuses_bad_arguments_by_name(name):
+    buf = Buffers()
+    cases = _bad_cases(name)
+    assert len(cases) == (8 if "debug" in name else 6)       # three null pointers, two sizes, the device count or the three id lists
+    for case in cases:
+        rc, message = _call(name, buf, **case)
+        assert rc == 1 and message.startswith(name + ":"), (case, rc, message)
+    assert buf.untouched()
+
+
+@pytest.mark.parametrize("name", PLAIN)
+def test_plain_frame_takes_any_spp_and_fails_loudly_without_gpu(name):
+    """spp = 0 and spp = 1 are no refusal of the plain frame's: without a GPU such a call gets as far as the device check."""
+    if pt.device_count() > 0:
+        pytest.skip("a GPU is present")
+    buf = Buffers()
+    for spp in (4, 1, 0):
+        rc, message = _call(name, buf, spp=spp)
+        assert rc == 2 and message == name + ": no HIP device (the HIP path has no CPU fallback)", (spp, rc, message)
     assert buf.untouched()
 
 

@@ -6,7 +6,7 @@
 //       tools/multi_host_check.cpp -o /tmp/multi_host_check && /tmp/multi_host_check
 // Checked besides the addresses: pack -> collect -> unpack puts exactly the rows above and below a partition's bands, with the owners'
 // values, into its e image and touches nothing else; every image row is written by exactly one partition's finish; the interleaved
-// images of 3, 6 and 1 words per pixel are the single-device outputs.
+// images of 3, 6 and 1 words per pixel are the single-device outputs, and so is the rgb image of the plain frame's rgb-only layout.
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -119,6 +119,19 @@ int checkSize(uint32_t w, uint32_t h, uint32_t parts) {
     for (uint64_t i = 0; i < pixels * 3; ++i) ptrk::multiInterleave(i, gathered.get(), rgbAt.data(), parts, w, 3u, reinterpret_cast<uint32_t*>(iRgb.get()));
     for (uint64_t i = 0; i < pixels * 6; ++i) ptrk::multiInterleave(i, gathered.get(), covAt.data(), parts, w, 6u, reinterpret_cast<uint32_t*>(iCov.get()));
     for (uint64_t i = 0; i < pixels; ++i) ptrk::multiInterleave(i, gathered.get(), countAt.data(), parts, w, 1u, iCount.get());
+    // the plain frame's layout: every partition's rgb and nothing else, in a buffer of exactly that size
+    std::unique_ptr<uint32_t[]> plain(new uint32_t[partPixel[parts] * 3]);
+    std::vector<uint64_t> plainAt(parts);
+    for (uint32_t p = 0; p < parts; ++p) {
+        plainAt[p] = partPixel[p] * 3u;
+        std::memcpy(plain.get() + plainAt[p], gathered.get() + rgbAt[p], static_cast<size_t>(partPixel[p + 1u] - partPixel[p]) * 3 * sizeof(float));
+    }
+    std::unique_ptr<float[]> iPlain(new float[pixels * 3]);
+    for (uint64_t i = 0; i < pixels * 3; ++i) ptrk::multiInterleave(i, plain.get(), plainAt.data(), parts, w, 3u, reinterpret_cast<uint32_t*>(iPlain.get()));
+    if (std::memcmp(iPlain.get(), iRgb.get(), pixels * 3 * sizeof(float)) != 0) {
+        std::printf("%ux%u P=%u: the image interleaved from the rgb-only layout is not the one from the full layout\n", w, h, parts);
+        return 1;
+    }
     for (size_t p = 0; p < pixels; ++p) {
         const float fn = static_cast<float>(n[p]), norm = fn * static_cast<float>(n[p] - 1u);
         bool same = iCount[p] == n[p];
