@@ -394,6 +394,16 @@ bool parseOptions(int argc, const char** argv, CliOptions& o, std::string& error
     return true;
 }
 
+// The combinations of modes that parse but do not render: reported without the usage text, before the scene is loaded.  Empty = none.
+std::string modeRefusal(const CliOptions& o) {
+    const std::string devices = "; it cannot be combined with --devices=" + std::to_string(o.devices);
+    if (o.denoiseSampleVariance && o.devices != 1u) return "--denoiseVariance=sample renders on one device" + devices;
+    if (o.adaptive && o.devices != 1u) return "--adaptive renders on one device" + devices;
+    if (!o.snapshots.empty() && o.adaptive) return "--snapshots continues a uniform frame; it cannot be combined with --adaptive";
+    if (!o.snapshots.empty() && o.devices != 1u) return "--snapshots renders on one device" + devices;
+    return std::string();
+}
+
 std::string sanitizeSceneName(const std::string& input) {
     if (input.empty()) return "scene";
     std::string name = fs::path(input).stem().string();
@@ -415,22 +425,9 @@ int main(int argc, const char** argv) {
         return 1;
     }
 
-    if (options.denoiseSampleVariance && options.devices != 1u) {
-        std::cerr << "Error: --denoiseVariance=sample renders on one device; it cannot be combined with --devices=" << options.devices << std::endl;
-        return 1;
-    }
-
-    if (options.adaptive && options.devices != 1u) {
-        std::cerr << "Error: --adaptive renders on one device; it cannot be combined with --devices=" << options.devices << std::endl;
-        return 1;
-    }
-
-    if (!options.snapshots.empty() && options.adaptive) {
-        std::cerr << "Error: --snapshots continues a uniform frame; it cannot be combined with --adaptive" << std::endl;
-        return 1;
-    }
-    if (!options.snapshots.empty() && options.devices != 1u) {
-        std::cerr << "Error: --snapshots renders on one device; it cannot be combined with --devices=" << options.devices << std::endl;
+    const std::string refusal = modeRefusal(options);
+    if (!refusal.empty()) {
+        std::cerr << "Error: " << refusal << std::endl;
         return 1;
     }
 
@@ -512,11 +509,12 @@ int main(int argc, const char** argv) {
         name << sanitizeSceneName(options.scene) << "_" << width << "x" << height << "." << ptr::FormatExtension(options.format);
         return (fs::path("renders") / name.str()).string();
     };
+    auto makeParentDirectory = [](const fs::path& path) {
+        std::error_code ec;
+        if (!path.parent_path().empty()) fs::create_directories(path.parent_path(), ec);
+    };
     auto writeImageFile = [&](const fs::path& path, const float* linearRGB, uint32_t width, uint32_t height, std::string& writeError) {
-        if (!path.parent_path().empty()) {
-            std::error_code ec;
-            fs::create_directories(path.parent_path(), ec);
-        }
+        makeParentDirectory(path);
         if (options.format == ptr::ImageFileFormat::EXR && options.rgbaExr) {
             std::vector<float> rgba(static_cast<size_t>(width) * height * 4u, 1.0f);
             for (size_t i = 0; i < static_cast<size_t>(width) * height; ++i) {
@@ -565,10 +563,7 @@ int main(int argc, const char** argv) {
     }
     if (!options.aovExrPath.empty()) {
         const fs::path aovFs(options.aovExrPath);
-        if (!aovFs.parent_path().empty()) {
-            std::error_code ec;
-            fs::create_directories(aovFs.parent_path(), ec);
-        }
+        makeParentDirectory(aovFs);
         if (!ptr::WriteExrAovs(options.aovExrPath, output.linearRGB.data(), hip->aovAlbedo().data(), hip->aovNormal().data(), output.width,
                                output.height, &writeError)) {
             std::cerr << "Failed to write AOV image: " << writeError << std::endl;

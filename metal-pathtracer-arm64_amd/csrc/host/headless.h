@@ -50,11 +50,26 @@ public:
     virtual ~IHeadlessRenderer() = default;
 };
 
-// MI355X backend: wraps the C-ABI (ptr_render) behind the reference's interface.
+// What HipHeadlessRenderer::render decides before its first device call.
+struct HeadlessPlan {
+    // the call the frame comes from: ptr_render, ptr_render_multi, ptr_render_bands[_cov], ptr_render_adaptive, a PtrFrame
+    enum class Frame { Whole, Multi, Bands, Adaptive, Snapshots };
+    Frame frame = Frame::Whole;
+    uint32_t spp = 1;
+    bool features = false;     // the first-hit feature buffers: asked for, or the denoiser's guides
+    bool covariance = false;   // the frame's per-pixel sample covariance: the denoiser's variance
+    bool ownScene = false;     // render() uploads a scene of its own to device 0: for Bands, Adaptive, Snapshots and for the feature buffers
+};
+
+// MI355X backend: wraps the C-ABI (include/ptr_abi.h and the five headers beside it) behind the reference's interface.
 class HipHeadlessRenderer : public IHeadlessRenderer {
 public:
+    // plan(), then in one line: the frame, the feature buffers (ptr_render_aovs, sample 0), the denoiser.  Anything thrown on the way
+    // comes back as false with "exception: <what>".
     bool render(const HeadlessScene& scene, const HeadlessCamera& camera, const RenderSettings& settings,
                 uint32_t sppTotal, bool verbose, HeadlessRenderOutput& out, std::string& error) override;
+    // what render() would do with the setters' state as it is, or false and why it refuses; makes no device call
+    bool plan(const HeadlessScene& scene, uint32_t sppTotal, HeadlessPlan& plan, std::string& error) const;
     const PtrRenderStats& lastStats() const { return m_stats; }
     // devices of this node to spread the frame over (1 = the first device only, 0 = all visible): --devices of the CLI
     void setDeviceCount(int n) { m_devices = n; }
