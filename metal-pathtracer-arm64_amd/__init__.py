@@ -426,6 +426,23 @@ _FRAME_SIGNATURES = {
 }
 FRAME_SYMBOLS = tuple(_FRAME_SIGNATURES)
 
+# ... and of include/ptr_multi_frame.h (resumable frames on several devices): tests/test_multi_frame_host.py holds it against that header
+_MULTI_FRAME_SIGNATURES = {
+    "ptr_multi_frame_create": (_int, [_desc, _settings, _int, C.POINTER(_vp)] + _err),
+    "ptr_multi_frame_release": (None, [_vp]),
+    "ptr_multi_frame_reset": (_int, [_vp, _settings] + _err),
+    "ptr_multi_frame_accumulate": (_int, [_vp, _u32, _stats] + _err),
+    "ptr_multi_frame_refine": (_int, [_vp, _adaptive, _stats, _adaptive_info] + _err),
+    "ptr_multi_frame_resolve": (_int, [_vp, _fp, _fp, _up, _fp, _fp] + _err),
+    "ptr_multi_frame_resolve_device": (_int, [_vp, _vp, _vp, _vp, _vp] + _err),
+    "ptr_multi_frame_info": (_int, [_vp, _frame_info, _multi_info]),
+    "ptr_multi_frame_export": (_int, [_vp, _fp, _fp, _fp, _up, _fp] + _err),
+    "ptr_multi_frame_import": (_int, [_vp, _fp, _fp, _fp, _up, _fp] + _err),
+    "ptr_multi_frame_debug_create_on": (_int, [_desc, _settings, _ids, _int, C.POINTER(_vp)] + _err),
+    "ptr_multi_frame_debug_create": (_int, [_u32, _u32, _fp, _u32, _ids, _int, C.POINTER(_vp)] + _err),
+}
+MULTI_FRAME_SYMBOLS = tuple(_MULTI_FRAME_SIGNATURES)
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -443,7 +460,7 @@ def load_library() -> C.CDLL:
         raise PtrError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` first")
     lib = C.CDLL(path)
     for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_POST_SIGNATURES.items()) + list(_STATS_SIGNATURES.items()) + \
-            list(_ADAPTIVE_SIGNATURES.items()) + list(_MULTI_SIGNATURES.items()) + list(_FRAME_SIGNATURES.items()):
+            list(_ADAPTIVE_SIGNATURES.items()) + list(_MULTI_SIGNATURES.items()) + list(_FRAME_SIGNATURES.items()) + list(_MULTI_FRAME_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -1017,6 +1034,129 @@ def multi_adaptive_debug_frame(samples: np.ndarray, params: PtrAdaptiveParams, d
     _check(load_library().ptr_multi_debug_adaptive_frame(w, h, C.byref(params), _fptr(samples), ids, len(device_ids), _fptr(rgb), _fptr(cov),
                                                          _uptr(count), C.byref(info), err, len(err)), err)
     return rgb, cov, count, info
+
+
+class MultiFrame:
+    """include/ptr_multi_frame.h: a resumable frame on several devices, continued call by call; made by multi_frame() or
+    debug_multi_frame().  The calls mirror Frame's; the state, the images and every info are bit for bit those of a single-device Frame
+    given the same calls, and a checkpoint (export_state / import_state) passes between the two and between device counts."""
+
+    def __init__(self, handle: C.c_void_p, keepalive=None):
+        self._h = handle
+        self._keepalive = keepalive
+
+    def _handle(self):
+        if not self._h:
+            raise PtrError("the frame is closed")
+        return self._h
+
+    def accumulate(self, spp: int) -> PtrRenderStats:
+        """Every pixel gets `spp` more samples (the frame must be uniform)."""
+        stats = PtrRenderStats()
+        err = _err_buf()
+        _check(load_library().ptr_multi_frame_accumulate(self._handle(), spp, C.byref(stats), err, len(err)), err)
+        return stats
+
+    def refine(self, params: PtrAdaptiveParams) -> Tuple[PtrRenderStats, PtrAdaptiveInfo]:
+        """The resumable adaptive loop of Frame.refine in lock step over the partitions.  Returns (stats, info) of this call."""
+        stats, info = PtrRenderStats(), PtrAdaptiveInfo()
+        err = _err_buf()
+        _check(load_library().ptr_multi_frame_refine(self._handle(), C.byref(params), C.byref(stats), C.byref(info), err, len(err)), err)
+        return stats, info
+
+    def info(self) -> PtrFrameInfo:
+        out = PtrFrameInfo()
+        if load_library().ptr_multi_frame_info(self._handle(), C.byref(out), None) != 0:
+            raise PtrError("ptr_multi_frame_info failed")
+        return out
+
+    def multi_info(self) -> PtrMultiInfo:
+        """The partitions of the last accumulate, refine or resolve."""
+        out, multi = PtrFrameInfo(), PtrMultiInfo()
+        if load_library().ptr_multi_frame_info(self._handle(), C.byref(out), C.byref(multi)) != 0:
+            raise PtrError("ptr_multi_frame_info failed")
+        return multi
+
+    def resolve(self, want_cov: bool = True, want_count: bool = True, want_aovs: bool = False):
+        """([H, W, 3] image, [H, W, 6] covariance of the pixel means, [H, W] uint32 samples per pixel), image order; with want_aovs also
+        the first-hit feature buffers ([H, W, 4] albedo, [H, W, 4] normal) of the first partition's resident scene.  The state stays."""
+        i = self.info()
+        rgb = np.zeros((i.height, i.width, 3), dtype=np.float32)
+        cov = np.zeros((i.height, i.width, 6), dtype=np.float32) if want_cov else None
+        count = np.zeros((i.height, i.width), dtype=np.uint32) if want_count else None
+        albedo = np.zeros((i.height, i.width, 4), dtype=np.float32) if want_aovs else None
+        normal = np.zeros((i.height, i.width, 4), dtype=np.float32) if want_aovs else None
+        err = _err_buf()
+        _check(load_library().ptr_multi_frame_resolve(self._handle(), _fptr(rgb), _opt(cov, _fptr), _opt(count, _uptr), _opt(albedo, _fptr),
+                                                      _opt(normal, _fptr), err, len(err)), err)
+        return (rgb, cov, count, albedo, normal) if want_aovs else (rgb, cov, count)
+
+    def resolve_device(self, d_rgb: int, d_cov: int = 0, d_count: int = 0, stream: int = 0) -> None:
+        """resolve() into caller-owned image-order buffers on the frame's FIRST device, on `stream` of that device."""
+        err = _err_buf()
+        _check(load_library().ptr_multi_frame_resolve_device(self._handle(), C.c_void_p(d_rgb), C.c_void_p(d_cov or None),
+                                                             C.c_void_p(d_count or None), C.c_void_p(stream or None), err, len(err)), err)
+
+    def export_state(self) -> dict:
+        """The checkpoint of Frame.export_state, image order, each pixel from its owner: it does not depend on the device count."""
+        i = self.info()
+        pixels = i.width * i.height
+        st = {k: np.zeros((pixels, cols) if cols else pixels, dtype=dt) for k, cols, dt in FRAME_STATE}
+        err = _err_buf()
+        _check(load_library().ptr_multi_frame_export(self._handle(), _fptr(st["sum"]), _fptr(st["mean"]), _fptr(st["m"]), _uptr(st["n"]),
+                                                     _fptr(st["e"]), err, len(err)), err)
+        return st
+
+    def import_state(self, state: dict) -> None:
+        i = self.info()
+        pixels = i.width * i.height
+        st = {k: np.ascontiguousarray(state[k], dtype=dt).reshape((pixels, cols) if cols else pixels) for k, cols, dt in FRAME_STATE}
+        err = _err_buf()
+        _check(load_library().ptr_multi_frame_import(self._handle(), _fptr(st["sum"]), _fptr(st["mean"]), _fptr(st["m"]), _uptr(st["n"]),
+                                                     _fptr(st["e"]), err, len(err)), err)
+
+    def reset(self, settings: Optional[PtrSettings] = None) -> None:
+        """The state back to zero on every device; `settings` of the same size replace the stored ones."""
+        err = _err_buf()
+        _check(load_library().ptr_multi_frame_reset(self._handle(), C.byref(settings) if settings is not None else None, err, len(err)), err)
+
+    def close(self) -> None:
+        if self._h:
+            load_library().ptr_multi_frame_release(self._h)
+            self._h = None
+        self._keepalive = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def multi_frame(desc: PtrSceneDesc, settings: PtrSettings, n_devices: int = 0, device_ids=None) -> MultiFrame:
+    """A resumable frame on several devices of this node (include/ptr_multi_frame.h): the scene is prepared once and uploaded to every
+    device once, for the frame's life.  `device_ids` (tests) names the devices explicitly as render_multi_adaptive's does."""
+    handle = C.c_void_p()
+    err = _err_buf()
+    if device_ids is not None:
+        ids = (C.c_int * len(device_ids))(*device_ids)
+        _check(load_library().ptr_multi_frame_debug_create_on(C.byref(desc), C.byref(settings), ids, len(device_ids), C.byref(handle), err, len(err)), err)
+    else:
+        _check(load_library().ptr_multi_frame_create(C.byref(desc), C.byref(settings), n_devices, C.byref(handle), err, len(err)), err)
+    return MultiFrame(handle)
+
+
+def debug_multi_frame(samples: np.ndarray, device_ids) -> MultiFrame:
+    """ptr_multi_frame_debug_create (tests): debug_frame() on the partitions `device_ids` names; samples [S, H, W, 3 or 4]."""
+    samples = np.asarray(samples, dtype=np.float32)
+    count, h, w = samples.shape[:3]
+    x4 = np.zeros((count, h, w, 4), dtype=np.float32)
+    x4[..., :3] = samples[..., :3]
+    ids = (C.c_int * len(device_ids))(*device_ids)
+    handle = C.c_void_p()
+    err = _err_buf()
+    _check(load_library().ptr_multi_frame_debug_create(w, h, _fptr(x4), count, ids, len(device_ids), C.byref(handle), err, len(err)), err)
+    return MultiFrame(handle)
 
 
 def decode_image(data: bytes) -> np.ndarray:

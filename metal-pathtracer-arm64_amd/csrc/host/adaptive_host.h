@@ -1,5 +1,6 @@
 // What the three adaptive round loops share on the host - the frame of one device (adaptive.cpp, include/ptr_adaptive.h), the lock-step
-// frame on several devices (multi.cpp, include/ptr_multi.h) and the resumable frame (frame.cpp, include/ptr_frame.h): the parameter check,
+// frame on several devices (multi.cpp, include/ptr_multi.h) and the resumable frame (frame.cpp, include/ptr_frame.h; on several devices
+// multi_frame.cpp, include/ptr_multi_frame.h, which runs frame.cpp's loop in lock step and adds none of its own): the parameter check,
 // the rules by which a frame is cut into rounds and a round into sub-passes, the sample source of a pass, the sample step of a round,
 // the device events of PTR_VERBOSE=launches, and the finish into staging with its downloads.  The owner of the per-pixel state is
 // AdaptiveStore (adaptive_state.h, through device_scene.h); the refusals are beside deviceCall in device_scene.h.  Each loop keeps what is

@@ -4,7 +4,9 @@
 // rows of e between them, the hand-over of the band-layout buffers to the first device, which interleaves them into the image.  The
 // sample source of a pass is a parameter of the partition loop: the traced one for the renderer, the gathered one for the test-only probe,
 // which therefore runs everything else the renderer runs.  The state's buffers, the sources and the sample step are the ones adaptive.cpp
-// and frame.cpp use (adaptive_host.h); the halo goes out from the step's hook.
+// and frame.cpp use (adaptive_host.h); the halo goes out from the step's hook.  The device list of a call, the exchange's pinned memory
+// with its publish and collect halves and the hand-over to the first device are stated once, below, for this driver and for the
+// resumable frame of multi_frame.cpp (multi_host.h).
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -18,6 +20,7 @@
 #include "adaptive_host.h"
 #include "device_scene.h"
 #include "knobs.h"
+#include "multi_host.h"
 #include "parallel.h"
 #include "ptr_debug.h"
 #include "ptr_multi.h"
@@ -25,6 +28,103 @@
 
 using namespace ptrhost;
 using namespace ptrk;
+
+// ---- what multi_host.h declares for both drivers ----
+namespace ptrhost {
+
+std::string badDeviceRequest(const std::string& w, bool listed, int n) {
+    if (listed && (n < 1 || n > PTR_MULTI_MAX_PARTS)) return w + ": the id list must name 1 .. " + std::to_string(PTR_MULTI_MAX_PARTS) + " devices";
+    if (!listed && n > PTR_MULTI_MAX_PARTS) return w + ": at most " + std::to_string(PTR_MULTI_MAX_PARTS) + " devices";
+    return std::string();
+}
+
+int pickDevices(const char* who, const int* ids, int n, bool listed, uint32_t height, std::vector<int>& devices, std::vector<char>& forceStaged,
+                char* err, size_t cap) {
+    const std::string w(who);
+    const int available = ptr_device_count();
+    if (available < 1) return noDevice(who, err, cap);
+    if (listed) {   // (an id given as -(id + 1) sends that partition's bands through pinned host memory: the tests' hook)
+        for (int i = 0; i < n; ++i) {
+            const int id = ids[i] < 0 ? -(ids[i] + 1) : ids[i];
+            if (id < 0 || id >= available) return refuse(err, cap, w + ": no such HIP device");
+            devices.push_back(id);
+            forceStaged.push_back(ids[i] < 0 ? 1 : 0);
+        }
+        return 0;
+    }
+    int count = n <= 0 ? available : n;
+    if (count > available) {
+        setErr(err, cap, w + ": " + std::to_string(count) + " devices requested, " + std::to_string(available) + " visible");
+        return 2;
+    }
+    count = std::min(count, PTR_MULTI_MAX_PARTS);
+    // never more partitions than bands
+    count = static_cast<int>(std::min<uint32_t>(static_cast<uint32_t>(count), std::max(1u, (height + PTR_BAND_ROWS - 1u) / PTR_BAND_ROWS)));
+    for (int i = 0; i < count; ++i) devices.push_back(i);
+    forceStaged.assign(static_cast<size_t>(count), 0);
+    return 0;
+}
+
+void HaloExchange::allocate(const std::vector<uint32_t>& partBands, uint32_t width) {
+    const uint32_t parts = static_cast<uint32_t>(partBands.size());
+    offset.assign(parts + 1u, 0u);
+    for (uint32_t p = 0; p < parts; ++p) offset[p + 1u] = offset[p] + static_cast<size_t>(partBands[p]) * 2u * width;
+    const size_t bytes = offset.back() * 2u * sizeof(float);
+    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&host), std::max<size_t>(bytes, sizeof(float)), hipHostMallocPortable));
+    std::memset(host, 0, bytes);
+}
+
+void HaloExchange::publishZeros() {
+    if (host) std::memset(host, 0, offset.back() * sizeof(float));
+}
+
+void haloPublish(const MultiPart& mp, const float* dE, float* dEdge, const HaloExchange& ex, hipStream_t stream, hipEvent_t before, hipEvent_t after) {
+    if (before) HIP_CHECK(hipEventRecord(before, stream));
+    launchMultiHaloPack(mp, dE, dEdge, stream);
+    HIP_CHECK(hipMemcpyAsync(ex.outbox(mp.part), dEdge, ex.haloBytes(mp.part), hipMemcpyDeviceToHost, stream));
+    if (after) HIP_CHECK(hipEventRecord(after, stream));
+}
+
+void haloCollect(const MultiPart& mp, float* dEdge, float* dE, const HaloExchange& ex, hipStream_t stream, hipEvent_t before, hipEvent_t after) {
+    multiCollectNeighbourRows(mp, ex.host, ex.offset.data(), ex.inbox(mp.part));
+    if (before) HIP_CHECK(hipEventRecord(before, stream));
+    HIP_CHECK(hipMemcpyAsync(dEdge, ex.inbox(mp.part), ex.haloBytes(mp.part), hipMemcpyHostToDevice, stream));
+    launchMultiHaloUnpack(mp, dEdge, dE, stream);
+    if (after) HIP_CHECK(hipEventRecord(after, stream));
+}
+
+// A partition's band buffer travels to the first device of the frame (multi_host.h).
+bool sendBandsToRoot(void* dRootDst, int rootDevice, const void* dSrc, int device, size_t bytes, bool forceStaged, hipStream_t stream) {
+    if (device == rootDevice && !forceStaged) {
+        HIP_CHECK(hipMemcpyAsync(dRootDst, dSrc, bytes, hipMemcpyDeviceToDevice, stream));
+        return false;
+    }
+    int direct = 0;
+    if (device != rootDevice) HIP_CHECK(hipDeviceCanAccessPeer(&direct, device, rootDevice));
+    if (forceStaged) direct = 0;
+    if (direct) {
+        const hipError_t enabled = hipDeviceEnablePeerAccess(rootDevice, 0);   // (this thread's current device is `device`)
+        if (enabled != hipSuccess && enabled != hipErrorPeerAccessAlreadyEnabled) direct = 0;
+        (void)hipGetLastError();
+    }
+    if (direct) {
+        HIP_CHECK(hipMemcpyPeerAsync(dRootDst, rootDevice, dSrc, device, bytes, stream));
+        return false;
+    }
+    std::fprintf(stderr, "[ptr] device %d does not address device %d directly: its bands go through pinned host memory\n", device, rootDevice);
+    void* staging = nullptr;
+    HIP_CHECK(hipHostMalloc(&staging, bytes, hipHostMallocDefault));
+    hipError_t copied = hipMemcpyAsync(staging, dSrc, bytes, hipMemcpyDeviceToHost, stream);
+    if (copied == hipSuccess) copied = hipStreamSynchronize(stream);
+    if (copied == hipSuccess) copied = hipSetDevice(rootDevice);
+    if (copied == hipSuccess) copied = hipMemcpy(dRootDst, staging, bytes, hipMemcpyHostToDevice);
+    (void)hipSetDevice(device);
+    (void)hipHostFree(staging);
+    HIP_CHECK(copied);
+    return true;
+}
+
+}  // namespace ptrhost
 
 namespace {
 
@@ -57,51 +157,6 @@ struct Request {
     std::vector<int> devices;   // admit fills these two in
     std::vector<char> forceStaged;
 };
-
-// The pinned host memory the partitions exchange their edge rows through (portable: every device's copies may use it).  Partition p
-// publishes into its outbox - its edge rows as k_multi_halo_pack lays them out - and collects its neighbours' rows in its inbox.
-struct Exchange {
-    float* host = nullptr;
-    std::vector<size_t> offset;   // of partition p's edge rows in either half, in floats; [parts] = the size of a half
-    ~Exchange() {
-        if (host) (void)hipHostFree(host);
-    }
-    float* outbox(uint32_t p) const { return host + offset[p]; }
-    float* inbox(uint32_t p) const { return host + offset.back() + offset[p]; }
-};
-
-// A partition's band buffer travels to the first device of the frame: a plain copy when it is local, device-to-device over the fabric
-// when the two devices can address each other, through pinned host memory otherwise (or with forceStaged, the tests' hook).  Called on
-// the partition's thread with `device` current; asynchronous on `stream` except for the staged path.  True when the bytes were staged.
-bool sendBandsToRoot(void* dRootDst, int rootDevice, const void* dSrc, int device, size_t bytes, bool forceStaged, hipStream_t stream) {
-    if (device == rootDevice && !forceStaged) {
-        HIP_CHECK(hipMemcpyAsync(dRootDst, dSrc, bytes, hipMemcpyDeviceToDevice, stream));
-        return false;
-    }
-    int direct = 0;
-    if (device != rootDevice) HIP_CHECK(hipDeviceCanAccessPeer(&direct, device, rootDevice));
-    if (forceStaged) direct = 0;
-    if (direct) {
-        const hipError_t enabled = hipDeviceEnablePeerAccess(rootDevice, 0);   // (this thread's current device is `device`)
-        if (enabled != hipSuccess && enabled != hipErrorPeerAccessAlreadyEnabled) direct = 0;
-        (void)hipGetLastError();
-    }
-    if (direct) {
-        HIP_CHECK(hipMemcpyPeerAsync(dRootDst, rootDevice, dSrc, device, bytes, stream));
-        return false;
-    }
-    std::fprintf(stderr, "[ptr] device %d does not address device %d directly: its bands go through pinned host memory\n", device, rootDevice);
-    void* staging = nullptr;
-    HIP_CHECK(hipHostMalloc(&staging, bytes, hipHostMallocDefault));
-    hipError_t copied = hipMemcpyAsync(staging, dSrc, bytes, hipMemcpyDeviceToHost, stream);
-    if (copied == hipSuccess) copied = hipStreamSynchronize(stream);
-    if (copied == hipSuccess) copied = hipSetDevice(rootDevice);
-    if (copied == hipSuccess) copied = hipMemcpy(dRootDst, staging, bytes, hipMemcpyHostToDevice);
-    (void)hipSetDevice(device);
-    (void)hipHostFree(staging);
-    HIP_CHECK(copied);
-    return true;
-}
 
 void runFrame(const Request& rq) {
     const bool probe = rq.kind == Kind::Probe, adaptive = probe || rq.kind == Kind::Adaptive;
@@ -142,14 +197,8 @@ void runFrame(const Request& rq) {
     image.ensure(pixels * pixelWords);
     dWordOffset.upload(wordOffset.data(), wordOffset.size());
 
-    Exchange ex;
-    if (adaptive && parts > 1u) {
-        ex.offset.assign(parts + 1u, 0u);
-        for (uint32_t p = 0; p < parts; ++p) ex.offset[p + 1u] = ex.offset[p] + static_cast<size_t>(partBands[p]) * 2u * width;
-        const size_t bytes = ex.offset.back() * 2u * sizeof(float);
-        HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&ex.host), bytes, hipHostMallocPortable));
-        std::memset(ex.host, 0, bytes);
-    }
+    HaloExchange ex;
+    if (adaptive && parts > 1u) ex.allocate(partBands, width);
 
     std::vector<std::unique_ptr<PtrDeviceScene>> scenes(parts);
     std::vector<PtrRenderStats> partStats(parts);
@@ -241,10 +290,7 @@ void runFrame(const Request& rq) {
             if (active > 0u) {
                 addSamples(step, list, active, n, roundSpp, [&](uint32_t, uint32_t, bool last) {
                     if (!last || parts == 1u) return;
-                    if (timed) HIP_CHECK(hipEventRecord(marks[0], stream));
-                    launchMultiHaloPack(mp, step.state.e, edge.ptr, stream);
-                    HIP_CHECK(hipMemcpyAsync(ex.outbox(p), edge.ptr, haloBytes, hipMemcpyDeviceToHost, stream));
-                    if (timed) HIP_CHECK(hipEventRecord(marks[1], stream));
+                    haloPublish(mp, step.state.e, edge.ptr, ex, stream, marks[0], marks[1]);
                 });
                 HIP_CHECK(hipStreamSynchronize(stream));   // (the source joined the stream already: the outbox is written)
                 partSamples[p] += static_cast<uint64_t>(active) * roundSpp;
@@ -256,11 +302,7 @@ void runFrame(const Request& rq) {
             // 3. the neighbours' rows, select and compact on the own list, the own total
             if (active > 0u) {
                 if (parts > 1u) {
-                    multiCollectNeighbourRows(mp, ex.host, ex.offset.data(), ex.inbox(p));
-                    if (timed) HIP_CHECK(hipEventRecord(marks[2], stream));
-                    HIP_CHECK(hipMemcpyAsync(edge.ptr, ex.inbox(p), haloBytes, hipMemcpyHostToDevice, stream));
-                    launchMultiHaloUnpack(mp, edge.ptr, step.state.e, stream);
-                    if (timed) HIP_CHECK(hipEventRecord(marks[3], stream));
+                    haloCollect(mp, edge.ptr, step.state.e, ex, stream, marks[2], marks[3]);
                 }
                 launchAdaptiveSelect(list, active, width, height, step.state, params.maxSpp, params.threshold, b.scratch(), b.list(turn ^ 1u), stream);
                 HIP_CHECK(hipGetLastError());
@@ -417,31 +459,9 @@ int admit(Request& rq, char* err, size_t cap) {
     if (rq.settings->width == 0u || rq.settings->height == 0u) bad = w + ": render size must be non-zero";
     else if (adaptive) bad = badAdaptiveParams(rq.who, *rq.params);
     else if (rq.kind == Kind::Covariance && rq.spp < 2u) bad = w + ": a sample covariance needs spp >= 2";
-    if (bad.empty() && rq.listed && (rq.n < 1 || rq.n > PTR_MULTI_MAX_PARTS)) bad = w + ": the id list must name 1 .. " + std::to_string(PTR_MULTI_MAX_PARTS) + " devices";
-    if (bad.empty() && !rq.listed && rq.n > PTR_MULTI_MAX_PARTS) bad = w + ": at most " + std::to_string(PTR_MULTI_MAX_PARTS) + " devices";
+    if (bad.empty()) bad = badDeviceRequest(w, rq.listed, rq.n);
     if (!bad.empty()) return refuse(err, cap, bad);
-    const int available = ptr_device_count();
-    if (available < 1) return noDevice(rq.who, err, cap);
-    if (rq.listed) {   // (an id given as -(id + 1) sends that partition's bands through pinned host memory: the tests' hook)
-        for (int i = 0; i < rq.n; ++i) {
-            const int id = rq.ids[i] < 0 ? -(rq.ids[i] + 1) : rq.ids[i];
-            if (id < 0 || id >= available) return refuse(err, cap, w + ": no such HIP device");
-            rq.devices.push_back(id);
-            rq.forceStaged.push_back(rq.ids[i] < 0 ? 1 : 0);
-        }
-        return 0;
-    }
-    int count = rq.n <= 0 ? available : rq.n;
-    if (count > available) {
-        setErr(err, cap, w + ": " + std::to_string(count) + " devices requested, " + std::to_string(available) + " visible");
-        return 2;
-    }
-    count = std::min(count, PTR_MULTI_MAX_PARTS);
-    // never more partitions than bands
-    count = static_cast<int>(std::min<uint32_t>(static_cast<uint32_t>(count), std::max(1u, (rq.settings->height + PTR_BAND_ROWS - 1u) / PTR_BAND_ROWS)));
-    for (int i = 0; i < count; ++i) rq.devices.push_back(i);
-    rq.forceStaged.assign(static_cast<size_t>(count), 0);
-    return 0;
+    return pickDevices(rq.who, rq.ids, rq.n, rq.listed, rq.settings->height, rq.devices, rq.forceStaged, err, cap);
 }
 
 int frame(Request& rq, char* err, size_t cap) {

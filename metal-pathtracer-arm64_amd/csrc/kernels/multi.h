@@ -1,6 +1,7 @@
 // An adaptive or covariance-carrying frame on several devices (include/ptr_multi.h, whose text this file follows): the per-element
 // bodies of the kernels in multi.hip, written as host + device functions on plain pointers so that the renderer, the test-only probe and
-// a host program that walks the index arithmetic (tools/multi_host_check.cpp) all run the same code, and the launchers.
+// a host program that walks the index arithmetic (tools/multi_host_check.cpp) all run the same code, and the launchers.  The two
+// checkpoint bodies of the resumable frame on several devices (include/ptr_multi_frame.h; tools/multi_frame_host_check.cpp) are here too.
 //
 // A partition p of P owns the image bands b = p + k P, k = 0 .. bands_p - 1 (k: its local band).  Band b covers the image rows
 // 8 b .. min(8 b + 8, height) - 1.  Two layouts besides the image:
@@ -121,7 +122,48 @@ inline void multiCollectNeighbourRows(const MultiPart& mp, const float* outboxes
     }
 }
 
+// The checkpoint buffer of a partition (include/ptr_multi_frame.h): its own pixels' state, dense, in band layout and planar - with
+// B = bands * 8 * width band pixels the words sum [B][3] at 0, mean [B][3] at 3 B, M [B][6] at 6 B, n [B] at 12 B, e [B] at 13 B.
+constexpr uint32_t kMultiStateWords = 14u;
+PTR_HD size_t multiBandPixels(const MultiPart& mp) { return static_cast<size_t>(mp.bands) * kMultiBandRows * mp.width; }
+// the image pixel at position i of the band layout; false for a row of a ragged last band that lies outside the image
+PTR_HD bool multiBandPixel(const MultiPart& mp, uint32_t i, size_t* pixel) {
+    const uint32_t row = i / mp.width, x = i - row * mp.width;
+    const uint32_t y = multiBandTop(mp, row / kMultiBandRows) + row % kMultiBandRows;
+    if (y >= mp.height) return false;
+    *pixel = static_cast<size_t>(y) * mp.width + x;
+    return true;
+}
+
+// Pack, position i of the band layout (i < B): the state of the image pixel at that position goes from the image-order arrays into the
+// planes of `packed`.  Positions outside the image are neither read nor written.  Words are copied as they are (n is a uint32 plane).
+PTR_HD void multiStatePack(const MultiPart& mp, uint32_t i, const AdaptiveState& st, float* packed) {
+    size_t p;
+    if (!multiBandPixel(mp, i, &p)) return;
+    const size_t b = multiBandPixels(mp), at = i;
+    for (uint32_t c = 0; c < 3u; ++c) packed[at * 3u + c] = st.sum[p * 3u + c];
+    for (uint32_t c = 0; c < 3u; ++c) packed[3u * b + at * 3u + c] = st.mean[p * 3u + c];
+    for (uint32_t c = 0; c < 6u; ++c) packed[6u * b + at * 6u + c] = st.m[p * 6u + c];
+    reinterpret_cast<uint32_t*>(packed)[12u * b + at] = st.n[p];
+    packed[13u * b + at] = st.e[p];
+}
+
+// Unpack, position i of the band layout: the reverse.
+PTR_HD void multiStateUnpack(const MultiPart& mp, uint32_t i, const float* packed, const AdaptiveState& st) {
+    size_t p;
+    if (!multiBandPixel(mp, i, &p)) return;
+    const size_t b = multiBandPixels(mp), at = i;
+    for (uint32_t c = 0; c < 3u; ++c) st.sum[p * 3u + c] = packed[at * 3u + c];
+    for (uint32_t c = 0; c < 3u; ++c) st.mean[p * 3u + c] = packed[3u * b + at * 3u + c];
+    for (uint32_t c = 0; c < 6u; ++c) st.m[p * 6u + c] = packed[6u * b + at * 6u + c];
+    st.n[p] = reinterpret_cast<const uint32_t*>(packed)[12u * b + at];
+    st.e[p] = packed[13u * b + at];
+}
+
 #if defined(__HIPCC__)
+// dPacked: multiBandPixels(mp) * kMultiStateWords words.  Nothing is launched for a partition without bands.
+void launchMultiStatePack(const MultiPart& mp, const AdaptiveState& state, float* dPacked, hipStream_t stream);
+void launchMultiStateUnpack(const MultiPart& mp, const float* dPacked, const AdaptiveState& state, hipStream_t stream);
 // dEdge: mp.bands * 2 * mp.width floats.  Nothing is launched for a partition without bands.
 void launchMultiHaloPack(const MultiPart& mp, const float* dE, float* dEdge, hipStream_t stream);
 void launchMultiHaloUnpack(const MultiPart& mp, const float* dEdge, float* dE, hipStream_t stream);

@@ -6,6 +6,10 @@
 // k_multi_finish_bands: one thread per pixel position of the partition's band layout.
 // k_multi_interleave: one thread per 4-byte word of the image, the gather step of every multi-device frame, for 3, 6 or 1 words per pixel.
 // k_multi_gather_items (probe only): one thread per (sample, list entry).
+// k_multi_state_pack / k_multi_state_unpack (include/ptr_multi_frame.h): one thread per pixel position of the partition's band layout.
+// Consecutive threads walk an image row, and a band's rows are contiguous in the image, so a wave reads (pack) or writes (unpack) one
+// contiguous run of each image-order array - 768 / 768 / 1536 / 256 / 256 bytes of sum / mean / M / n / e - and the same run of each
+// plane; only a wave that straddles the end of a band touches two runs.  Streaming copies: 56 bytes in, 56 out per pixel, no reuse.
 #include <hip/hip_runtime.h>
 
 #include "multi.h"
@@ -51,9 +55,31 @@ __global__ void __launch_bounds__(kBlock) k_multi_gather_items(const float4* __r
     items[i] = samples[static_cast<size_t>(nBefore + c) * pixels + list[j]];
 }
 
+__global__ void __launch_bounds__(kBlock) k_multi_state_pack(MultiPart mp, AdaptiveState st, float* __restrict__ packed) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= mp.bands * kMultiBandRows * mp.width) return;
+    multiStatePack(mp, i, st, packed);
+}
+
+__global__ void __launch_bounds__(kBlock) k_multi_state_unpack(MultiPart mp, const float* __restrict__ packed, AdaptiveState st) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= mp.bands * kMultiBandRows * mp.width) return;
+    multiStateUnpack(mp, i, packed, st);
+}
+
 uint32_t blocksFor(uint64_t n) { return static_cast<uint32_t>((n + kBlock - 1u) / kBlock); }
 
 }  // namespace
+
+void launchMultiStatePack(const MultiPart& mp, const AdaptiveState& state, float* dPacked, hipStream_t stream) {
+    const uint32_t blocks = blocksFor(multiBandPixels(mp));
+    if (blocks) hipLaunchKernelGGL(k_multi_state_pack, dim3(blocks), dim3(kBlock), 0, stream, mp, state, dPacked);
+}
+
+void launchMultiStateUnpack(const MultiPart& mp, const float* dPacked, const AdaptiveState& state, hipStream_t stream) {
+    const uint32_t blocks = blocksFor(multiBandPixels(mp));
+    if (blocks) hipLaunchKernelGGL(k_multi_state_unpack, dim3(blocks), dim3(kBlock), 0, stream, mp, dPacked, state);
+}
 
 void launchMultiHaloPack(const MultiPart& mp, const float* dE, float* dEdge, hipStream_t stream) {
     const uint32_t blocks = blocksFor(static_cast<uint64_t>(mp.bands) * 2u * mp.width);
