@@ -443,6 +443,60 @@ _MULTI_FRAME_SIGNATURES = {
 }
 MULTI_FRAME_SYMBOLS = tuple(_MULTI_FRAME_SIGNATURES)
 
+
+
+class PtrMeshTransform(C.Structure):
+    """include/ptr_dynamic.h PtrMeshTransform."""
+    _fields_ = [("meshIndex", C.c_uint32), ("pad", C.c_uint32), ("localToWorld", C.c_float * 16)]
+
+
+class PtrUpdateInfo(C.Structure):
+    """include/ptr_dynamic.h PtrUpdateInfo."""
+    _fields_ = [
+        ("totalSeconds", C.c_double),
+        ("bakeMs", C.c_double),
+        ("refitMs", C.c_double),
+        ("quantiseMs", C.c_double),
+        ("wideMs", C.c_double),
+        ("trianglesMoved", C.c_uint64),
+        ("nodes", C.c_uint64),
+        ("levels", C.c_uint64),
+        ("wideNodes", C.c_uint64),
+        ("sceneLo", C.c_float * 3),
+        ("sceneHi", C.c_float * 3),
+        ("gridOrigin", C.c_float * 3),
+        ("gridCell", C.c_float * 3),
+        ("cellOverExtent", C.c_float),
+        ("pad", C.c_uint32),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: (list(getattr(self, name)) if hasattr(getattr(self, name), "__len__") else getattr(self, name))
+                for name, _ in self._fields_ if name != "pad"}
+
+
+# ... and of include/ptr_dynamic.h (dynamic scenes): tests/test_dynamic_host.py holds it against that header
+_DYNAMIC_SIGNATURES = {
+    "ptr_scene_upload_dynamic": (_int, [_desc, _int, C.POINTER(_vp)] + _err),
+    "ptr_scene_set_mesh_transforms": (_int, [_vp, C.POINTER(PtrMeshTransform), _u32, _vp, C.POINTER(PtrUpdateInfo)] + _err),
+    "ptr_scene_is_dynamic": (_int, [_vp]),
+    # its test-only probes
+    "ptr_debug_scene_arrays": (_int, [_vp, _u32, _vp, _u64, _u64p]),
+    "ptr_debug_dynamic_tables": (_int, [_desc, _u32, _vp, _u64, _u64p] + _err),
+}
+DYNAMIC_SYMBOLS = tuple(_DYNAMIC_SIGNATURES)
+
+# ptr_debug_scene_arrays / ptr_debug_dynamic_tables: name -> (selector, dtype, trailing shape)
+SCENE_ARRAYS = {"tris": (0, np.float32, (3, 4)), "triNormals": (1, np.float32, (3, 4)), "triUv": (2, np.float32, (4, 4)),
+                "triTangent": (3, np.float32, (3, 4)), "triBounds": (4, np.float32, (2, 4)), "sphereBounds": (5, np.float32, (2, 4)),
+                "boxes": (6, np.float32, (4, 4)), "qnodes": (7, np.uint32, (2, 4)), "wnodes": (8, np.uint32, (4, 4)), "grid": (9, np.float32, (3,))}
+DYNAMIC_TABLES = {"nodes": (0, np.float32, (4, 4)), "qnodes": (1, np.uint32, (2, 4)), "wnodes": (2, np.uint32, (4, 4)),
+                  "triBounds": (3, np.float32, (2, 4)), "sphereBounds": (4, np.float32, (2, 4)), "schedule": (5, np.uint32, ()),
+                  "levelOffsets": (6, np.uint32, ()), "wideSource": (7, np.uint32, (4,)), "grid": (8, np.float32, (3,)),
+                  "requantised": (9, np.uint32, (2, 4)), "meshTriOffsets": (10, np.uint32, ()), "meshTris": (11, np.uint32, ()),
+                  "info": (12, np.uint32, ())}
+DYNAMIC_TABLE_INFO = ("nodes", "levels", "wide_nodes", "quantized", "triangles", "spheres", "max_depth", "root_ref", "oversize_ref", "wide_depth")
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -460,7 +514,8 @@ def load_library() -> C.CDLL:
         raise PtrError(f"{path} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` first")
     lib = C.CDLL(path)
     for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_POST_SIGNATURES.items()) + list(_STATS_SIGNATURES.items()) + \
-            list(_ADAPTIVE_SIGNATURES.items()) + list(_MULTI_SIGNATURES.items()) + list(_FRAME_SIGNATURES.items()) + list(_MULTI_FRAME_SIGNATURES.items()):
+            list(_ADAPTIVE_SIGNATURES.items()) + list(_MULTI_SIGNATURES.items()) + list(_FRAME_SIGNATURES.items()) + list(_MULTI_FRAME_SIGNATURES.items()) + \
+            list(_DYNAMIC_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -576,19 +631,56 @@ def prepare_geometry(desc: PtrSceneDesc, path: str) -> float:
 class DeviceScene:
     """A scene resident in HBM: SAH BVH + SoA primitive/material/light arrays (ptr_scene_upload)."""
 
-    def __init__(self, desc: PtrSceneDesc, device: int = 0, keepalive=None, prepared: Optional[str] = None):
+    def __init__(self, desc: PtrSceneDesc, device: int = 0, keepalive=None, prepared: Optional[str] = None, dynamic: bool = False):
         """prepared: a geometry cache written by prepare_geometry() for this description - the BVH is read, not built
-        (the processes of a multi-GPU render build it once)."""
+        (the processes of a multi-GPU render build it once).  dynamic: ptr_scene_upload_dynamic - the scene also keeps what
+        set_mesh_transforms needs to move its meshes on the device (not with `prepared`)."""
         lib = load_library()
         if lib.ptr_device_count() <= 0:
             raise PtrError("no HIP device visible: the HIP render path has no CPU fallback")
         self._keepalive = keepalive
         self._h = C.c_void_p()
         err = _err_buf()
-        if prepared:
+        if dynamic and prepared:
+            raise PtrError("a dynamic scene is not read from a geometry cache")
+        if dynamic:
+            _check(lib.ptr_scene_upload_dynamic(C.byref(desc), device, C.byref(self._h), err, len(err)), err)
+        elif prepared:
             _check(lib.ptr_scene_upload_prepared(C.byref(desc), prepared.encode(), device, C.byref(self._h), err, len(err)), err)
         else:
             _check(lib.ptr_scene_upload(C.byref(desc), device, C.byref(self._h), err, len(err)), err)
+
+    @property
+    def is_dynamic(self) -> bool:
+        return bool(load_library().ptr_scene_is_dynamic(self._h))
+
+    def set_mesh_transforms(self, transforms: dict, stream: int = 0) -> dict:
+        """ptr_scene_set_mesh_transforms: {mesh index: 4x4 array (row, column), the new localToWorld}; returns PtrUpdateInfo as a dict."""
+        items = (PtrMeshTransform * max(len(transforms), 1))()
+        for k, (index, matrix) in enumerate(transforms.items()):
+            items[k].meshIndex = int(index)
+            m = np.asarray(matrix, np.float32).reshape(4, 4)
+            items[k].localToWorld[:] = m.T.reshape(-1).tolist()   # column-major
+        info = PtrUpdateInfo()
+        err = _err_buf()
+        _check(load_library().ptr_scene_set_mesh_transforms(self._h, items, len(transforms), C.c_void_p(stream), C.byref(info), err, len(err)), err)
+        return info.as_dict()
+
+    def arrays(self, names=None) -> dict:
+        """ptr_debug_scene_arrays: the named device arrays (all of SCENE_ARRAYS by default) as numpy arrays."""
+        lib = load_library()
+        out = {}
+        for name in (names or SCENE_ARRAYS):
+            which, dtype, shape = SCENE_ARRAYS[name]
+            size = C.c_uint64(0)
+            if lib.ptr_debug_scene_arrays(self._h, which, None, 0, C.byref(size)) != 0:
+                raise PtrError("ptr_debug_scene_arrays(%s) failed" % name)
+            buf = np.zeros(size.value // np.dtype(dtype).itemsize, dtype)
+            rc = lib.ptr_debug_scene_arrays(self._h, which, buf.ctypes.data_as(C.c_void_p), buf.nbytes, C.byref(size))
+            if rc != 0:
+                raise PtrError("ptr_debug_scene_arrays(%s) failed (%d)" % (name, rc))
+            out[name] = buf.reshape((-1,) + shape) if name != "grid" else buf.reshape(2, 3)
+        return out
 
     def timings(self) -> dict:
         """Seconds of the upload: geometry preparation (or cache read), shading tables, copies to the device."""
@@ -1390,6 +1482,23 @@ def debug_scene_geometry(desc: PtrSceneDesc, leaf_max: int = 0) -> dict:
     g["wide_problems"] = word >> 63                      # bad references / primitives not reached exactly once through them
     g["quantized_usable"] = word & 0xFF
     return g
+
+
+def debug_dynamic_tables(desc: PtrSceneDesc, names=None) -> dict:
+    """ptr_debug_dynamic_tables (host only): the tables ptr_scene_upload_dynamic prepares for `desc` as numpy arrays; "info" as a dict."""
+    lib = load_library()
+    out = {}
+    for name in (names or DYNAMIC_TABLES):
+        which, dtype, shape = DYNAMIC_TABLES[name]
+        size = C.c_uint64(0)
+        err = _err_buf()
+        _check(lib.ptr_debug_dynamic_tables(C.byref(desc), which, None, 0, C.byref(size), err, len(err)), err)
+        buf = np.zeros(size.value // np.dtype(dtype).itemsize, dtype)
+        _check(lib.ptr_debug_dynamic_tables(C.byref(desc), which, buf.ctypes.data_as(C.c_void_p), buf.nbytes, C.byref(size), err, len(err)), err)
+        out[name] = buf.reshape(2, 3) if name == "grid" else buf.reshape((-1,) + shape)
+    if "info" in out:
+        out["info"] = dict(zip(DYNAMIC_TABLE_INFO, (int(v) for v in out["info"])))
+    return out
 
 
 def walk_stack_depths(desc: PtrSceneDesc, rays: np.ndarray) -> np.ndarray:

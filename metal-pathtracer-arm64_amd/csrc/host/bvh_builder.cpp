@@ -17,6 +17,7 @@
 #include <emmintrin.h>
 #endif
 
+#include "../kernels/bvh_grid.h"
 #include "../kernels/bvh_layout.h"
 #include "knobs.h"
 #include "parallel.h"
@@ -664,6 +665,40 @@ struct Flattener {
 
 }  // namespace
 
+void QuantiseNode(const float* node, const float origin[3], const float cell[3], uint32_t* q) {
+    for (int c = 0; c < 2; ++c) {
+        uint32_t ref;
+        std::memcpy(&ref, node + (c == 0 ? 3 : 7), 4);
+        ptrk::quantiseChild(node + c * 8, node + c * 8 + 4, ref, origin, cell, q + c * 4);
+    }
+}
+
+void BuildRefitSchedule(const FlatBvh& bvh, std::vector<uint32_t>& schedule, std::vector<uint32_t>& levelOffsets) {
+    schedule.clear();
+    levelOffsets.assign(1, 0u);
+    const uint32_t nodeCount = bvh.nodeCount;
+    if (nodeCount == 0) return;
+    // device indices are preorder (children after parents): one backward pass settles every height
+    std::vector<uint8_t> height(nodeCount, 0);
+    uint32_t levels = 0;
+    for (uint32_t i = nodeCount; i-- > 0;) {
+        uint32_t h = 0;
+        for (int c = 0; c < 2; ++c) {
+            uint32_t ref;
+            std::memcpy(&ref, bvh.nodes.data() + static_cast<size_t>(i) * 16 + (c == 0 ? 3 : 7), 4);
+            if (ref != ptrk::kRefEmpty && !(ref & ptrk::kRefLeafBit)) h = std::max<uint32_t>(h, 1u + height[ref]);
+        }
+        height[i] = static_cast<uint8_t>(h);
+        levels = std::max(levels, h + 1u);
+    }
+    levelOffsets.assign(levels + 1u, 0u);
+    for (uint32_t i = 0; i < nodeCount; ++i) ++levelOffsets[height[i] + 1u];
+    for (uint32_t l = 0; l < levels; ++l) levelOffsets[l + 1u] += levelOffsets[l];
+    schedule.resize(nodeCount);
+    std::vector<uint32_t> at(levelOffsets.begin(), levelOffsets.end() - 1);
+    for (uint32_t i = 0; i < nodeCount; ++i) schedule[at[height[i]]++] = i;
+}
+
 void BuildFlatBvh(const std::vector<BuildPrim>& prims, FlatBvh& out, uint32_t threads, uint32_t leafMax) {
     out = FlatBvh{};
     const uint32_t n = static_cast<uint32_t>(prims.size());
@@ -810,39 +845,10 @@ void BuildFlatBvh(const std::vector<BuildPrim>& prims, FlatBvh& out, uint32_t th
     // 16-bit grid version of the nodes.  lo is rounded down and hi up, plus one cell of padding on each
     // side, so a quantised box always contains the float box (the traversal stays conservative).
     const Aabb& scene = b.nodes[0].box;
-    double cell[3];
-    for (int a = 0; a < 3; ++a) {
-        const double extent = static_cast<double>(scene.hi[a]) - scene.lo[a];
-        cell[a] = extent > 0.0 ? extent / 65531.0 : 1.0;          // cells 2..65533 span the scene, rest is padding
-        out.gridCell[a] = static_cast<float>(cell[a]);
-        out.gridOrigin[a] = static_cast<float>(scene.lo[a] - 2.0 * cell[a]);
-    }
+    for (int a = 0; a < 3; ++a) ptrk::gridAxis(scene.lo[a], scene.hi[a], out.gridOrigin[a], out.gridCell[a]);
     out.qnodes.assign(static_cast<size_t>(out.nodeCount) * 8, 0u);
-    auto quant = [&](float v, int axis, bool up) -> uint32_t {
-        const double g = (static_cast<double>(v) - out.gridOrigin[axis]) / static_cast<double>(out.gridCell[axis]);
-        const double q = up ? std::ceil(g) + 1.0 : std::floor(g) - 1.0;
-        return static_cast<uint32_t>(std::min(std::max(q, 0.0), 65535.0));
-    };
     auto quantiseRange = [&](uint32_t begin, uint32_t end) {
-        for (uint32_t i = begin; i < end; ++i) {
-            const float* n = out.nodes.data() + static_cast<size_t>(i) * 16;
-            uint32_t* q = out.qnodes.data() + static_cast<size_t>(i) * 8;
-            for (int c = 0; c < 2; ++c) {
-                const float* lo = n + c * 8;
-                const float* hi = n + c * 8 + 4;
-                uint32_t ref;
-                std::memcpy(&ref, n + (c == 0 ? 3 : 7), 4);
-                uint32_t* w = q + c * 4;
-                if (ref == ptrk::kRefEmpty) {
-                    w[0] = w[1] = w[2] = 0u;
-                } else {
-                    w[0] = quant(lo[0], 0, false) | (quant(lo[1], 1, false) << 16);
-                    w[1] = quant(lo[2], 2, false) | (quant(hi[0], 0, true) << 16);
-                    w[2] = quant(hi[1], 1, true) | (quant(hi[2], 2, true) << 16);
-                }
-                w[3] = ref;
-            }
-        }
+        for (uint32_t i = begin; i < end; ++i) QuantiseNode(out.nodes.data() + static_cast<size_t>(i) * 16, out.gridOrigin, out.gridCell, out.qnodes.data() + static_cast<size_t>(i) * 8);
     };
     {
         const uint32_t workers = out.nodeCount >= (1u << 16) ? std::min(threads, 32u) : 1u;
@@ -928,7 +934,7 @@ WideChoice chooseWideChildren(const uint32_t* q, uint32_t nodeCount, const float
 
 }  // namespace
 
-uint32_t BuildWideNodes(const FlatBvh& bvh, WideCollapse how, std::unique_ptr<uint32_t[]>& wide, uint32_t* depthOut) {
+uint32_t BuildWideNodes(const FlatBvh& bvh, WideCollapse how, std::unique_ptr<uint32_t[]>& wide, uint32_t* depthOut, std::vector<uint32_t>* sourceOut) {
     const uint32_t* q = bvh.qnodes.data();
     const uint32_t nodeCount = bvh.nodeCount;
     constexpr uint32_t kNotWide = 0xFFFFFFFFu;
@@ -956,6 +962,7 @@ uint32_t BuildWideNodes(const FlatBvh& bvh, WideCollapse how, std::unique_ptr<ui
     uint32_t wideCount = 0;
     for (uint32_t n = 0; n < nodeCount; ++n) wideIndex[n] = depth[n] ? wideCount++ : kNotWide;
     wide.reset(new uint32_t[static_cast<size_t>(wideCount) * 16u]);
+    if (sourceOut) sourceOut->assign(static_cast<size_t>(wideCount) * 4u, kNoWideSource);
     const uint32_t workers = nodeCount >= (1u << 16) ? std::min(32u, std::max(1u, std::thread::hardware_concurrency())) : 1u;
     auto collapse = [&](uint32_t begin, uint32_t end) {
         for (uint32_t n = begin; n < end; ++n) {
@@ -965,6 +972,7 @@ uint32_t BuildWideNodes(const FlatBvh& bvh, WideCollapse how, std::unique_ptr<ui
             for (uint32_t k = 0; k < c.count; ++k) {
                 uint32_t* dst = w + 4u * k;
                 std::memcpy(dst, c.rec[k], 16);
+                if (sourceOut) (*sourceOut)[static_cast<size_t>(wideIndex[n]) * 4u + k] = static_cast<uint32_t>((c.rec[k] - q) / 4);   // node * 2 + side
                 if (internalRef(dst[3], nodeCount)) dst[3] = wideIndex[dst[3]];   // its wide node
             }
             for (uint32_t k = c.count; k < 4u; ++k) emptyWidePlace(w + 4u * k);

@@ -52,7 +52,19 @@ void BuildFlatBvh(const std::vector<BuildPrim>& prims, FlatBvh& out, uint32_t th
 //   ByLevel:  the children's children (every second level of the binary tree collapsed; a child that is a leaf keeps its record).
 // Wide nodes are numbered in the order of the binary (preorder) indices of their roots, internal references renumbered to match.
 // Returns the number of wide nodes; depthOut (nullable): levels of the wide tree (a step pushes at most three entries per level).
+// sourceOut (nullable): for every place of every wide node, the quantised binary record the place copies as node * 2 + side, or
+// kNoWideSource for an unused place: what a refit needs to fill the wide nodes again from requantised binary nodes.
 enum class WideCollapse { ByArea, ByLevel };
-uint32_t BuildWideNodes(const FlatBvh& bvh, WideCollapse how, std::unique_ptr<uint32_t[]>& wide, uint32_t* depthOut = nullptr);
+constexpr uint32_t kNoWideSource = 0xFFFFFFFFu;
+uint32_t BuildWideNodes(const FlatBvh& bvh, WideCollapse how, std::unique_ptr<uint32_t[]>& wide, uint32_t* depthOut = nullptr,
+                        std::vector<uint32_t>* sourceOut = nullptr);
+
+// The two 16 B quantised child records of one 64 B float node (the grid rule and the quantiser are kernels/bvh_grid.h's).
+void QuantiseNode(const float* node, const float origin[3], const float cell[3], uint32_t* q);
+
+// The order a refit visits the nodes in.  A node's height is 0 when it has only leaf children, otherwise 1 + the largest height of its
+// internal children; `schedule` holds the node indices grouped by height, lowest first, and levelOffsets[h] .. levelOffsets[h + 1] is
+// level h (levelOffsets.size() - 1 levels; none for a tree without nodes).
+void BuildRefitSchedule(const FlatBvh& bvh, std::vector<uint32_t>& schedule, std::vector<uint32_t>& levelOffsets);
 
 }  // namespace ptr

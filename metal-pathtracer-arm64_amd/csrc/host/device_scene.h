@@ -9,6 +9,7 @@
 #include <cstring>
 #include <exception>
 #include <functional>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -93,6 +94,33 @@ inline float bitsToFloat(uint32_t u) {
 
 using ptrhost::DeviceBuffer;
 
+namespace ptrhost {
+
+// What a dynamic scene (include/ptr_dynamic.h) keeps beside the arrays the kernels render from: ptr::DynamicTables on the device, the
+// float child boxes of every node, and the figures ptr_scene_set_mesh_transforms reports.  A static scene has none of it.
+struct DynamicScene {
+    DeviceBuffer<float4> objPos, objNrm, objTan;   // object-space corners, 3 float4 per triangle, leaf order
+    DeviceBuffer<float4> triBounds, sphereBounds;  // 2 float4 per primitive, leaf order
+    DeviceBuffer<float4> boxes;                    // quantised scenes: the 64 B float nodes (a float scene refits ds.nodes itself)
+    DeviceBuffer<uint32_t> meshTris, schedule, wideSource;
+    DeviceBuffer<float4> meshTable;                // kDynMeshVec4 float4 per named mesh of a call
+    std::vector<uint32_t> meshTriOffsets, levelOffsets;
+    std::vector<uint8_t> meshHasTangents;
+    uint32_t nodeCount = 0, wideCount = 0, triCount = 0, sphereCount = 0;
+    bool textured = false;
+    float meanPrimExtent = 0.0f;
+    hipEvent_t events[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    float4* rootBox = nullptr;   // pinned: node 0 after a refit
+    ~DynamicScene() {
+        for (hipEvent_t e : events) {
+            if (e) (void)hipEventDestroy(e);
+        }
+        if (rootBox) (void)hipHostFree(rootBox);
+    }
+};
+
+}  // namespace ptrhost
+
 struct PtrDeviceScene {
     int device = 0;
     DeviceBuffer<uint4> qnodes;
@@ -108,6 +136,7 @@ struct PtrDeviceScene {
     DeviceBuffer<float4> envMips;
     uint32_t envMipLevels = 0;   // 0: not built
     ptrk::SceneView view{};
+    std::unique_ptr<ptrhost::DynamicScene> dynamic;   // ptr_scene_upload_dynamic only
     uint64_t info[8] = {0};
     double uploadSeconds = 0.0;
     double timings[4] = {0.0, 0.0, 0.0, 0.0};   // geometry preparation (or cache read), shading tables, copies to the device, 1 = geometry came from a cache
@@ -220,11 +249,18 @@ struct PreparedScene {
     double shadingSeconds = 0.0;    // materials, lights, environment tables, texture mips
     bool geometryFromCache = false;
     double seconds = 0.0;           // both
+    bool dynamic = false;           // ptr_scene_upload_dynamic: `dyn` is filled and uploadScene makes the scene dynamic
+    ptr::DynamicTables dyn;
 };
-// cachePath (may be null): read the geometry from that file instead of building it
-void prepareScene(const PtrSceneDesc& desc, PreparedScene& ps, const char* cachePath = nullptr);
+// The geometry half of the preparation: bake, BVH, node format (the PTR_QUANTIZED_NODES / PTR_WIDE_NODES knobs), four-wide nodes.
+// dyn (nullable): the tables of a dynamic scene as well.
+void prepareGeometry(const PtrSceneDesc& desc, ptr::PreparedGeometry& pg, ptr::DynamicTables* dyn = nullptr);
+// cachePath (may be null): read the geometry from that file instead of building it; dynamic: prepare a dynamic scene (no cache)
+void prepareScene(const PtrSceneDesc& desc, PreparedScene& ps, const char* cachePath = nullptr, bool dynamic = false);
 // ds.device names the device
 void uploadScene(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceScene& ds);
+// the dynamic half of uploadScene (dynamic.cpp): ps.dyn and the float nodes to the device, ds.dynamic made
+void uploadDynamicTables(const PreparedScene& ps, PtrDeviceScene& ds);
 
 // What an entry point refuses before any device call: returns the C-ABI's code with the message in `err`.
 inline int refuse(char* err, size_t cap, const std::string& message) {

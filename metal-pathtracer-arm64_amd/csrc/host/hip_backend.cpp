@@ -24,6 +24,7 @@
 #include "env_importance_sampler.h"
 #include "geometry_cache.h"
 #include "knobs.h"
+#include "ptr_dynamic.h"
 #include "scene_geometry.h"
 #include "vecmath.h"
 
@@ -114,13 +115,13 @@ void appendTextureWithMips(const PtrTexture& t, std::vector<float>& texels, std:
 
 }  // namespace ptrhost
 
-namespace {
+namespace ptrhost {
 
 // The geometry half of the preparation: everything a geometry cache file holds (host/geometry_cache.h).
-void prepareGeometry(const PtrSceneDesc& desc, ptr::PreparedGeometry& pg) {
+void prepareGeometry(const PtrSceneDesc& desc, ptr::PreparedGeometry& pg, ptr::DynamicTables* dyn) {
     const ptr::Knobs knobs = ptr::readKnobs();
     std::string geoError;
-    if (!ptr::BuildSceneGeometry(desc, 0, pg.geo, geoError)) throw HipError{geoError};
+    if (!ptr::BuildSceneGeometry(desc, 0, pg.geo, geoError, dyn)) throw HipError{geoError};
     // 32 B quantised nodes halve the node fetches; use them unless the 16-bit grid is coarse next to the primitives (cell > 1/8 of
     // the mean primitive extent would inflate leaf boxes noticeably)
     const ptr::FlatBvh& bvh = pg.geo.bvh;
@@ -131,17 +132,14 @@ void prepareGeometry(const PtrSceneDesc& desc, ptr::PreparedGeometry& pg) {
     if (pg.useQuantized && knobs.wideNodes != 0) {
         // (a tree so lopsided that the by-area wide tree would outgrow the traversal stack keeps the by-level collapse, whose depth is half
         // the binary tree's)
-        pg.wideCount = ptr::BuildWideNodes(bvh, knobs.wideNodes == 2 ? ptr::WideCollapse::ByLevel : ptr::WideCollapse::ByArea, pg.wide, &pg.wideDepth);
-        if (3u * pg.wideDepth + 4u > kTraversalStackDepth) pg.wideCount = ptr::BuildWideNodes(bvh, ptr::WideCollapse::ByLevel, pg.wide, &pg.wideDepth);
+        std::vector<uint32_t>* source = dyn ? &dyn->wideSource : nullptr;
+        pg.wideCount = ptr::BuildWideNodes(bvh, knobs.wideNodes == 2 ? ptr::WideCollapse::ByLevel : ptr::WideCollapse::ByArea, pg.wide, &pg.wideDepth, source);
+        if (3u * pg.wideDepth + 4u > kTraversalStackDepth) pg.wideCount = ptr::BuildWideNodes(bvh, ptr::WideCollapse::ByLevel, pg.wide, &pg.wideDepth, source);
         if (static_cast<uint64_t>(pg.wideCount) * 64u > 0xFFFFFFFFull) throw HipError{"scene exceeds the 4 GiB node array limit"};
     }
 }
 
-}  // namespace
-
-namespace ptrhost {
-
-void prepareScene(const PtrSceneDesc& desc, PreparedScene& ps, const char* cachePath) {
+void prepareScene(const PtrSceneDesc& desc, PreparedScene& ps, const char* cachePath, bool dynamic) {
     using ptr::float3;
     const auto t0 = std::chrono::steady_clock::now();
     if (cachePath && *cachePath) {
@@ -149,7 +147,8 @@ void prepareScene(const PtrSceneDesc& desc, PreparedScene& ps, const char* cache
         if (!ptr::ReadGeometryCache(cachePath, ptr::SceneFingerprint(desc), ps.pg, error)) throw HipError{error};
         ps.geometryFromCache = true;
     } else {
-        prepareGeometry(desc, ps.pg);
+        ps.dynamic = dynamic;
+        prepareGeometry(desc, ps.pg, dynamic ? &ps.dyn : nullptr);
     }
     ps.geometrySeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     const ptr::SceneGeometry& geoRef = ps.pg.geo;
@@ -318,6 +317,8 @@ void uploadScene(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceSce
         v.textureCount = desc.textureCount;
     }
 
+    if (ps.dynamic) uploadDynamicTables(ps, ds);   // dynamic.cpp
+
     ds.info[0] = bvh.nodeCount;
     ds.info[1] = bvh.leafCount;
     ds.info[2] = triCount;
@@ -369,7 +370,8 @@ void uploadScene(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceSce
 namespace {
 
 // ptr_scene_upload and, with the path of a geometry cache file, ptr_scene_upload_prepared
-int uploadTo(const char* who, const PtrSceneDesc* scene, const char* cachePath, int device, PtrDeviceScene** outScene, char* err, size_t cap) {
+int uploadTo(const char* who, const PtrSceneDesc* scene, const char* cachePath, int device, PtrDeviceScene** outScene, char* err, size_t cap,
+             bool dynamic = false) {
     if (!scene || !outScene) return nullArgument(who, err, cap);
     if (ptr_device_count() <= device || device < 0) {
         setErr(err, cap, std::string(who) + ": no such HIP device (the HIP path has no CPU fallback)");
@@ -379,7 +381,7 @@ int uploadTo(const char* who, const PtrSceneDesc* scene, const char* cachePath, 
         auto ds = std::make_unique<PtrDeviceScene>();
         ds->device = device;
         PreparedScene ps;
-        prepareScene(*scene, ps, cachePath);
+        prepareScene(*scene, ps, cachePath, dynamic);
         uploadScene(*scene, ps, *ds);
         *outScene = ds.release();
         return 0;
@@ -1158,6 +1160,11 @@ uint32_t ptr_part_band_count(uint32_t height, uint32_t part_index, uint32_t part
 
 int ptr_scene_upload(const PtrSceneDesc* scene, int device, PtrDeviceScene** out_scene, char* err, size_t err_cap) {
     return uploadTo("ptr_scene_upload", scene, nullptr, device, out_scene, err, err_cap);
+}
+
+int ptr_scene_upload_dynamic(const PtrSceneDesc* scene, int device, PtrDeviceScene** out_scene, char* err, size_t err_cap) {
+    if (scene && out_scene && ptr_device_count() < 1) return noDevice("ptr_scene_upload_dynamic", err, err_cap);
+    return uploadTo("ptr_scene_upload_dynamic", scene, nullptr, device, out_scene, err, err_cap, true);
 }
 
 void ptr_scene_release(PtrDeviceScene* scene) {

@@ -121,7 +121,23 @@ double secondsSince(std::chrono::steady_clock::time_point t0) {
 
 }  // namespace
 
-bool BuildSceneGeometry(const PtrSceneDesc& desc, uint32_t leafMax, SceneGeometry& out, std::string& error) {
+void ComputeMeshBake(const float localToWorld[16], MeshBake& out) {
+    const M4 l2w = loadM4(localToWorld);
+    const M4 w2l = inverse(l2w);
+    const float det3 = l2w.m[0][0] * (l2w.m[1][1] * l2w.m[2][2] - l2w.m[2][1] * l2w.m[1][2]) -
+                       l2w.m[1][0] * (l2w.m[0][1] * l2w.m[2][2] - l2w.m[2][1] * l2w.m[0][2]) +
+                       l2w.m[2][0] * (l2w.m[0][1] * l2w.m[1][2] - l2w.m[1][1] * l2w.m[0][2]);
+    std::memcpy(out.localToWorld, localToWorld, sizeof(out.localToWorld));
+    for (int a = 0; a < 3; ++a) {
+        out.nc0[a] = w2l.m[a][0];
+        out.nc1[a] = w2l.m[a][1];
+        out.nc2[a] = w2l.m[a][2];
+    }
+    out.det3 = det3;
+    out.detSign = det3 < 0.0f ? -1.0f : 1.0f;
+}
+
+bool BuildSceneGeometry(const PtrSceneDesc& desc, uint32_t leafMax, SceneGeometry& out, std::string& error, DynamicTables* dyn) {
     out = SceneGeometry{};
     auto t0 = std::chrono::steady_clock::now();
 
@@ -166,14 +182,12 @@ bool BuildSceneGeometry(const PtrSceneDesc& desc, uint32_t leafMax, SceneGeometr
         const PtrMeshDesc& mesh = desc.meshes[mi];
         if (mesh.vertexCount == 0 || mesh.indexCount == 0) continue;
         const M4 l2w = loadM4(mesh.localToWorld);
-        const M4 w2l = inverse(l2w);
-        const float det3 = l2w.m[0][0] * (l2w.m[1][1] * l2w.m[2][2] - l2w.m[2][1] * l2w.m[1][2]) -
-                           l2w.m[1][0] * (l2w.m[0][1] * l2w.m[2][2] - l2w.m[2][1] * l2w.m[0][2]) +
-                           l2w.m[2][0] * (l2w.m[0][1] * l2w.m[1][2] - l2w.m[1][1] * l2w.m[0][2]);
-        const float detSign = det3 < 0.0f ? -1.0f : 1.0f;
-        const float3 nc0{w2l.m[0][0], w2l.m[1][0], w2l.m[2][0]};
-        const float3 nc1{w2l.m[0][1], w2l.m[1][1], w2l.m[2][1]};
-        const float3 nc2{w2l.m[0][2], w2l.m[1][2], w2l.m[2][2]};
+        MeshBake bake;
+        ComputeMeshBake(mesh.localToWorld, bake);
+        const float detSign = bake.detSign;
+        const float3 nc0{bake.nc0[0], bake.nc0[1], bake.nc0[2]};
+        const float3 nc1{bake.nc1[0], bake.nc1[1], bake.nc1[2]};
+        const float3 nc2{bake.nc2[0], bake.nc2[1], bake.nc2[2]};
         std::vector<float3> pos(mesh.vertexCount), nrm(mesh.vertexCount);
         parallelFor(mesh.vertexCount, [&](size_t b, size_t e) {
             for (size_t v = b; v < e; ++v) {
@@ -317,6 +331,57 @@ bool BuildSceneGeometry(const PtrSceneDesc& desc, uint32_t leafMax, SceneGeometr
                 std::memcpy(&out.triTangent[k * 12], &tanIn[static_cast<size_t>(order[k]) * 12], 48);
             }
         });
+    }
+    if (dyn) {
+        *dyn = DynamicTables{};
+        dyn->textured = textured;
+        dyn->triBounds.assign(static_cast<size_t>(triCount) * 8, 0.0f);
+        dyn->objPos.assign(static_cast<size_t>(triCount) * 12, 0.0f);
+        dyn->objNrm.assign(static_cast<size_t>(triCount) * 12, 0.0f);
+        if (textured) dyn->objTan.assign(static_cast<size_t>(triCount) * 12, 0.0f);
+        std::vector<uint32_t> leafOf(triCount, 0u);   // input index -> leaf-order index
+        parallelFor(order.size(), [&](size_t b, size_t e) {
+            for (size_t k = b; k < e; ++k) {
+                leafOf[order[k]] = static_cast<uint32_t>(k);
+                const BuildPrim& p = prims[order[k]];
+                std::memcpy(&dyn->triBounds[k * 8], p.lo, 12);
+                std::memcpy(&dyn->triBounds[k * 8 + 4], p.hi, 12);
+            }
+        });
+        dyn->meshTriOffsets.assign(static_cast<size_t>(desc.meshCount) + 1u, 0u);
+        dyn->meshHasTangents.assign(desc.meshCount, 0);
+        size_t at = 0;
+        for (uint32_t mi = 0; mi < desc.meshCount; ++mi) {
+            const PtrMeshDesc& mesh = desc.meshes[mi];
+            dyn->meshTriOffsets[mi] = static_cast<uint32_t>(at);
+            if (mesh.vertexCount == 0 || mesh.indexCount == 0) continue;
+            dyn->meshHasTangents[mi] = (textured && mesh.tangents) ? 1 : 0;
+            const size_t meshTris = mesh.indexCount / 3u;
+            dyn->meshTris.resize(at + meshTris);
+            parallelFor(meshTris, [&](size_t b, size_t e) {
+                for (size_t t = b; t < e; ++t) {
+                    const uint32_t k = leafOf[at + t];
+                    dyn->meshTris[at + t] = k;
+                    for (int c = 0; c < 3; ++c) {
+                        const uint32_t v = mesh.indices[3 * t + c];
+                        float* op = &dyn->objPos[static_cast<size_t>(k) * 12 + c * 4];
+                        std::memcpy(op, mesh.positions + 3 * static_cast<size_t>(v), 12);
+                        op[3] = out.triData[static_cast<size_t>(k) * 12 + c * 4 + 3];
+                        std::memcpy(&dyn->objNrm[static_cast<size_t>(k) * 12 + c * 4], mesh.normals + 3 * static_cast<size_t>(v), 12);
+                        if (dyn->meshHasTangents[mi]) std::memcpy(&dyn->objTan[static_cast<size_t>(k) * 12 + c * 4], mesh.tangents + 4 * static_cast<size_t>(v), 16);
+                    }
+                }
+            });
+            at += meshTris;
+        }
+        dyn->meshTriOffsets[desc.meshCount] = static_cast<uint32_t>(at);
+        dyn->sphereBounds.assign(static_cast<size_t>(desc.sphereCount) * 8, 0.0f);
+        for (size_t k = 0; k < out.bvh.sphereOrder.size(); ++k) {
+            const BuildPrim& p = prims[static_cast<size_t>(triCount) + out.bvh.sphereOrder[k]];
+            std::memcpy(&dyn->sphereBounds[k * 8], p.lo, 12);
+            std::memcpy(&dyn->sphereBounds[k * 8 + 4], p.hi, 12);
+        }
+        BuildRefitSchedule(out.bvh, dyn->schedule, dyn->levelOffsets);
     }
     for (uint32_t idx : out.bvh.sphereOrder) {
         const PtrSphere& s = desc.spheres[idx];

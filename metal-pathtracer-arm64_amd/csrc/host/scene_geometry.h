@@ -30,8 +30,34 @@ struct SceneGeometry {
     double gatherSeconds = 0.0, buildSeconds = 0.0, flattenSeconds = 0.0;
 };
 
-// leafMax = 0 picks the default (4).  Returns false with a message on malformed input.
-bool BuildSceneGeometry(const PtrSceneDesc& desc, uint32_t leafMax, SceneGeometry& out, std::string& error);
+// What a dynamic scene (include/ptr_dynamic.h) keeps beside the arrays above so that a mesh can be moved and the tree refitted on the
+// device.  Triangle arrays are in leaf order, like triData.
+struct DynamicTables {
+    std::vector<float> triBounds;      // 8 floats per triangle: the padded box the builder was given (lo xyz, 0, hi xyz, 0)
+    std::vector<float> sphereBounds;   // 8 floats per sphere, likewise
+    // object-space corners of every mesh triangle, 12 floats each (zeros for rectangle halves): position | the w word of the triData row,
+    // normal | 0, and in textured scenes tangent | handedness as the mesh gives it
+    std::vector<float> objPos, objNrm, objTan;
+    std::vector<uint32_t> meshTriOffsets;   // meshCount + 1: mesh m owns meshTris[meshTriOffsets[m] .. meshTriOffsets[m + 1])
+    std::vector<uint32_t> meshTris;         // leaf-order triangle indices, grouped by mesh
+    std::vector<uint8_t> meshHasTangents;   // per mesh: it carries tangents (textured scenes)
+    std::vector<uint32_t> schedule, levelOffsets;   // BuildRefitSchedule
+    std::vector<uint32_t> wideSource;       // BuildWideNodes' source table (empty without four-wide nodes)
+    bool textured = false;
+};
+
+// What the bake of one mesh derives from its localToWorld, by the functions BuildSceneGeometry itself uses: the three columns the normals
+// go through (rows of the cofactor inverse) and the sign of the 3x3 determinant.  det3 is that determinant.
+struct MeshBake {
+    float localToWorld[16];
+    float nc0[3], nc1[3], nc2[3];
+    float detSign, det3;
+};
+void ComputeMeshBake(const float localToWorld[16], MeshBake& out);
+
+// leafMax = 0 picks the default (4).  Returns false with a message on malformed input.  dyn (nullable): also fill the tables of a dynamic
+// scene (everything but wideSource, which comes with the four-wide nodes).
+bool BuildSceneGeometry(const PtrSceneDesc& desc, uint32_t leafMax, SceneGeometry& out, std::string& error, DynamicTables* dyn = nullptr);
 
 struct GeometryCheck {
     uint64_t nodes = 0, leaves = 0, trianglesReferenced = 0, spheresReferenced = 0;

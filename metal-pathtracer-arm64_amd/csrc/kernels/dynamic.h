@@ -1,0 +1,44 @@
+// Launchers of the dynamic-scene kernels (dynamic.hip; include/ptr_dynamic.h): re-bake the triangles of a moved mesh, refit the float
+// child boxes level by level, requantise the binary nodes and refill the four-wide ones.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace ptrk {
+
+// One row of the per-call mesh table: what the host bake derives from localToWorld, computed by the host's own functions
+// (ptr::ComputeMeshBake), so the device multiplies by the host's bits.
+constexpr uint32_t kDynMeshVec4 = 8u;
+struct alignas(16) DynMeshRow {
+    float l2w[16];        // column-major
+    float nc0[3], detSign;
+    float nc1[3], hasTangents;   // 1: the mesh carries tangents
+    float nc2[3], pad0;
+    float pad1[4];
+};
+static_assert(sizeof(DynMeshRow) == kDynMeshVec4 * 16u, "mesh table row layout");
+
+// The arrays a bake writes (leaf order) and the object-space corners it reads.  triUv / triTangent / objTan are null in untextured scenes.
+struct DynBakeArrays {
+    const float4* objPos;
+    const float4* objNrm;
+    const float4* objTan;
+    float4* tris;
+    float4* triNormals;
+    float4* triBounds;
+    float4* triUv;
+    float4* triTangent;
+};
+
+// triangles list[0 .. count) through row `mesh` of the table
+void launchDynBake(const DynBakeArrays& a, const float4* dMeshTable, uint32_t mesh, const uint32_t* dList, uint32_t count, hipStream_t stream);
+// one height level: nodes dSchedule[0 .. count), both child boxes each; children of internal children were written by earlier launches
+void launchDynRefitLevel(float4* dBoxes, const uint32_t* dSchedule, uint32_t count, const float4* dTriBounds, const float4* dSphereBounds,
+                         hipStream_t stream);
+void launchDynQuantise(const float4* dBoxes, uint4* dQnodes, uint32_t nodeCount, const float origin[3], const float cell[3], hipStream_t stream);
+// every place of every wide node takes the three box words of its source record; the reference word stays
+void launchDynWide(const uint4* dQnodes, uint4* dWnodes, const uint32_t* dWideSource, uint32_t places, hipStream_t stream);
+
+}  // namespace ptrk
