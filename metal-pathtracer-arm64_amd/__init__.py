@@ -486,6 +486,12 @@ _DYNAMIC_SIGNATURES = {
 }
 DYNAMIC_SYMBOLS = tuple(_DYNAMIC_SIGNATURES)
 
+# ... and of include/ptr_background.h (the primary-ray bounds cull): tests/test_background_cull_host.py holds it against that header
+_BACKGROUND_SIGNATURES = {
+    "ptr_background_debug_cull": (_int, [_vp, _desc, _settings, _u32, _u32, _int, _up, C.POINTER(C.c_double)] + _err),
+}
+BACKGROUND_SYMBOLS = tuple(_BACKGROUND_SIGNATURES)
+
 # ptr_debug_scene_arrays / ptr_debug_dynamic_tables: name -> (selector, dtype, trailing shape)
 SCENE_ARRAYS = {"tris": (0, np.float32, (3, 4)), "triNormals": (1, np.float32, (3, 4)), "triUv": (2, np.float32, (4, 4)),
                 "triTangent": (3, np.float32, (3, 4)), "triBounds": (4, np.float32, (2, 4)), "sphereBounds": (5, np.float32, (2, 4)),
@@ -515,7 +521,7 @@ def load_library() -> C.CDLL:
     lib = C.CDLL(path)
     for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_POST_SIGNATURES.items()) + list(_STATS_SIGNATURES.items()) + \
             list(_ADAPTIVE_SIGNATURES.items()) + list(_MULTI_SIGNATURES.items()) + list(_FRAME_SIGNATURES.items()) + list(_MULTI_FRAME_SIGNATURES.items()) + \
-            list(_DYNAMIC_SIGNATURES.items()):
+            list(_DYNAMIC_SIGNATURES.items()) + list(_BACKGROUND_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -1467,6 +1473,19 @@ def debug_env_distribution(rgba: np.ndarray) -> dict:
 GEOMETRY_FIELDS = ("nodes", "leaves", "triangles_referenced", "spheres_referenced", "max_depth", "max_leaf_size",
                    "unreferenced", "multiply_referenced", "box_violations", "quant_violations", "bad_refs", "triangles",
                    "spheres", "sah_cost_milli", "build_ms", "quantized_usable")
+
+
+def background_cull(settings: PtrSettings, scene: Optional["DeviceScene"] = None, desc: Optional[PtrSceneDesc] = None, part: int = 0,
+                    parts: int = 1, count: bool = False) -> dict:
+    """ptr_background_debug_cull (host only): which pixels a plain frame keeps out of the path pool.  The bounds are those of the device
+    scene `scene`, or those of `desc` prepared on the host.  rect = (x0, x1, y0, y1): pixels outside [x0, x1) x [y0, y1) are background."""
+    out = (C.c_uint32 * 8)()
+    bounds = (C.c_double * 7)()
+    err = _err_buf()
+    _check(load_library().ptr_background_debug_cull(scene._h if scene is not None else None, C.byref(desc) if desc is not None else None,
+                                                    C.byref(settings), part, parts, int(count), out, bounds, err, len(err)), err)
+    return {"culling": bool(out[0]), "rect": (int(out[1]), int(out[2]), int(out[3]), int(out[4])), "traced": int(out[5]),
+            "background": int(out[6]), "lo": np.array(bounds[0:3]), "hi": np.array(bounds[3:6]), "bounds_valid": bool(bounds[6])}
 
 
 def debug_scene_geometry(desc: PtrSceneDesc, leaf_max: int = 0) -> dict:

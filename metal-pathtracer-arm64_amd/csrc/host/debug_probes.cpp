@@ -7,6 +7,7 @@
 #include <cmath>
 
 #include "device_scene.h"
+#include "ptr_background.h"
 #include "ptr_debug.h"
 
 using namespace ptrk;
@@ -253,6 +254,36 @@ int ptr_debug_connect_rays(PtrDeviceScene* scene, const float* rays, const uint3
             occluded[i] = (a.x == 0.0f && a.y == 0.0f && a.z == 0.0f) ? 1u : 0u;
         }
     });
+}
+
+int ptr_background_debug_cull(const PtrDeviceScene* scene, const PtrSceneDesc* desc, const PtrSettings* settings, uint32_t part, uint32_t parts,
+                              int count, uint32_t out[8], double bounds[7], char* err, size_t err_cap) {
+    const char* who = "ptr_background_debug_cull";
+    if ((!scene && !desc) || !settings || !out) return nullArgument(who, err, err_cap);
+    if (parts == 0u || part >= parts) return refuse(err, err_cap, std::string(who) + ": bad partition");
+    try {
+        ptr::WorldBounds world;
+        if (scene) {
+            world = scene->worldBounds;
+        } else {
+            ptr::PreparedGeometry pg;
+            prepareGeometry(*desc, pg);
+            world = ptr::boundsOfPrimitives(pg.geo.triData.data(), pg.geo.triData.size() / 12u, pg.geo.sphereData.data(), pg.geo.sphereData.size() / 4u);
+        }
+        const ptr::CullRect rect = passCullRect(world, *settings, false, count != 0 ? 1 : 0);
+        std::vector<uint32_t> pixels;
+        partitionPixels(settings->width, settings->height, part, parts, pixels);
+        uint32_t traced = 0u;
+        for (const uint32_t pixel : pixels) traced += (!rect.cull || rect.inside(pixel % settings->width, pixel / settings->width)) ? 1u : 0u;
+        const uint32_t words[8] = {rect.cull ? 1u : 0u, rect.x0, rect.x1, rect.y0, rect.y1, traced, static_cast<uint32_t>(pixels.size()) - traced, 0u};
+        std::copy(words, words + 8, out);
+        if (bounds) {
+            for (int a = 0; a < 3; ++a) bounds[a] = world.lo[a], bounds[3 + a] = world.hi[a];
+            bounds[6] = world.valid ? 1.0 : 0.0;
+        }
+        return 0;
+    }
+    PTR_CATCH_ALL(err, err_cap)
 }
 
 int ptr_debug_exact_division(uint32_t d, const uint32_t* n, uint64_t count, uint32_t* out) {

@@ -15,6 +15,7 @@
 
 #include "../kernels/device_types.h"
 #include "../kernels/launch.h"
+#include "background_cull.h"
 #include "env_importance_sampler.h"
 #include "geometry_cache.h"
 #include "ptr_abi.h"
@@ -185,8 +186,13 @@ struct PtrDeviceScene {
     uint32_t* pinnedAlive = nullptr;
     uint32_t traceGrid = 0;       // persistent blocks of the traversal kernels: fills every wave slot (also sizes the spill area)
     uint32_t traceGridHalf = 0;   // ... of k_extend / k_connect when several pool groups run large launches side by side
-    // cached partition
-    uint32_t cachedW = 0, cachedH = 0, cachedPart = 0, cachedParts = 0, cachedLocalPixels = 0;
+    // cached partition: pixelOfLocal holds the pixels renderPass traces, backgroundPixels the ones cachedCull keeps out of the pool
+    uint32_t cachedW = 0, cachedH = 0, cachedPart = 0, cachedParts = 0, cachedLocalPixels = 0, cachedBackgroundPixels = 0;
+    ptr::CullRect cachedCull;
+    DeviceBuffer<uint32_t> backgroundPixels;
+    // world box of everything a ray can hit (csrc/host/background_cull.h): from the primitives at upload, from the refitted root box
+    // after ptr_scene_set_mesh_transforms (invalid there when the scene keeps triangles out of the tree: nothing is culled then)
+    ptr::WorldBounds worldBounds;
 
     ~PtrDeviceScene() {
         if (pinnedAlive) (void)hipHostFree(pinnedAlive);
@@ -205,7 +211,11 @@ void appendTextureWithMips(const PtrTexture& t, std::vector<float>& texels, std:
 double ensureEnvMips(PtrDeviceScene& ds);
 void fillRenderParams(const PtrSettings& s, uint32_t spp, ptrk::RenderParams& rp);
 ptrk::LaunchConfig coldLaunchConfig(const PtrDeviceScene& ds);
+// What renderPass does with a plain frame's pixels (csrc/host/background_cull.h): the rectangle of the pixels it traces, or no culling
+// (the knob, a covariance frame, the counting build or mode bit 2, maxDepth 0, unknown bounds) for a scene of world box `world`.  Host only.
+ptr::CullRect passCullRect(const ptr::WorldBounds& world, const PtrSettings& settings, bool covariance, int mode);
 // dCov (nullable): the covariance of the pixel mean beside the image (include/ptr_stats.h), six floats per pixel in dOut's band layout
+// mode: bit 0 the counting build, bit 1 the pool as one group (solo), bit 2 every pixel through the pool (no background cull)
 void renderBands(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, uint32_t part, uint32_t parts, float* dOut, hipStream_t stream,
                  int mode, PtrRenderStats* stats, float* dCov = nullptr);
 // passes renderBands splits a frame of `spp` samples per pixel into (the per-sample accumulators of a pass have to fit in memory)

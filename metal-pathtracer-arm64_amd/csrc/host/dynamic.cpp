@@ -156,6 +156,13 @@ int ptr_scene_set_mesh_transforms(PtrDeviceScene* scene, const PtrMeshTransform*
                 }
             }
         }
+        // What a ray can hit now (csrc/host/background_cull.h): the refitted root box holds every primitive of the tree.  Triangles kept
+        // out of the tree moved on the device only, and a scene without nodes has no root box: nothing is culled there.
+        ds.worldBounds = ptr::WorldBounds{};
+        if (dyn.nodeCount > 0u && v.oversizeRef == kRefEmpty && rootBoxOf(dyn.rootBox, lo, hi)) {
+            for (int a = 0; a < 3; ++a) ds.worldBounds.lo[a] = lo[a], ds.worldBounds.hi[a] = hi[a];
+            ds.worldBounds.valid = true;
+        }
         if (v.useQuantized) launchDynQuantise(boxes, ds.qnodes.ptr, dyn.nodeCount, v.gridOrigin, v.gridCell, st);
         HIP_CHECK(hipEventRecord(dyn.events[3], st));
         if (v.useWide) launchDynWide(ds.qnodes.ptr, ds.wnodes.ptr, dyn.wideSource.ptr, dyn.wideCount * 4u, st);

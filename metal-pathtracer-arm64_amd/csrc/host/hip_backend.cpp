@@ -317,6 +317,8 @@ void uploadScene(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceSce
         v.textureCount = desc.textureCount;
     }
 
+    ds.worldBounds = ptr::boundsOfPrimitives(geo.triData.data(), geo.triData.size() / 12u, geo.sphereData.data(), geo.sphereData.size() / 4u);
+
     if (ps.dynamic) uploadDynamicTables(ps, ds);   // dynamic.cpp
 
     ds.info[0] = bvh.nodeCount;
@@ -515,6 +517,18 @@ void partitionPixels(uint32_t width, uint32_t height, uint32_t part, uint32_t pa
             }
         }
     }
+}
+
+ptr::CullRect passCullRect(const ptr::WorldBounds& world, const PtrSettings& settings, bool covariance, int mode) {
+    // (the counting build's counters mirror the reference's rays, camera rays that miss included; at maxDepth 0 a frame adds nothing,
+    // not even the background; mode bit 2: the caller reads the pass's accumulators and wants every pixel's)
+    if (!ptr::readKnobs().backgroundCull || covariance || (mode & 5) != 0 || settings.width == 0u || settings.height == 0u) return ptr::CullRect{};
+    RenderParams rp;
+    fillRenderParams(settings, 1u, rp);
+    if (rp.maxDepth == 0u) return ptr::CullRect{};
+    const CameraParams& c = rp.cam;
+    return ptr::backgroundCullRect(ptr::CullCamera{c.origin, c.lowerLeft, c.horizontal, c.vertical, c.u, c.v, c.lensRadius}, settings.width,
+                                   settings.height, world);
 }
 
 // Adds the per-launch figures of `b` to `a`: kernel times, k_extend launches, samples.
@@ -798,7 +812,7 @@ PollResult poll(PtrDeviceScene& ds, std::vector<PoolGroup>& groups, const Render
     return r;
 }
 
-enum class SpanKind : int { Extend = 0, Shade = 1, Connect = 2, Tail = 3, ResolveCov = 4 };   // the `kind` of a [launch] line
+enum class SpanKind : int { Extend = 0, Shade = 1, Connect = 2, Tail = 3, ResolveCov = 4, Background = 5 };   // the `kind` of a [launch] line
 
 // Start and end events around the launches of a timed pass.
 struct LaunchTimer {
@@ -856,6 +870,7 @@ void passStats(const PtrDeviceScene& ds, const RenderParams& rp, const std::vect
             case SpanKind::Connect: stats.shadowKernelMs += ms; break;
             case SpanKind::Tail: stats.tailKernelMs += ms; break;
             case SpanKind::ResolveCov: break;   // (PTR_VERBOSE=launches shows it: tools/cov_cost.py)
+            case SpanKind::Background: break;   // (likewise: k_background runs beside the loop's first launches)
         }
     }
     if (!count) return;
@@ -903,9 +918,17 @@ void passStats(const PtrDeviceScene& ds, const RenderParams& rp, const std::vect
                  100.0 * static_cast<double>(c[kCntExtendRefillTicks]) / std::max(static_cast<double>(c[kCntExtendWaveTicks]), 1.0));
 }
 
+// The pixels of a pass that k_background resolves beside the traced ones (none: count 0)
+struct BackgroundPixels {
+    const uint32_t* pixels = nullptr;
+    uint32_t count = 0, parts = 1;
+    float* out = nullptr;
+};
+
 template <typename Resolve>
 void tracePass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, uint32_t sampleBase, uint32_t sppTotal, uint32_t passFlags,
-               const uint32_t* dPixelOfLocal, uint32_t localPixels, hipStream_t stream, int mode, PtrRenderStats* stats, Resolve&& resolve);
+               const uint32_t* dPixelOfLocal, uint32_t localPixels, hipStream_t stream, int mode, PtrRenderStats* stats, Resolve&& resolve,
+               const BackgroundPixels& background = BackgroundPixels{});
 
 // One pass over `spp` samples per pixel starting at sample `sampleBase` of a frame of `sppTotal`; passFlags bit 0 = first pass of
 // the frame (output and counters start from zero), bit 1 = last pass (the running sum in dOut is divided by sppTotal).
@@ -913,23 +936,55 @@ void tracePass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, ui
 // dCov (nullable; include/ptr_stats.h): six floats per pixel in the band layout of dOut, the covariance of the pixel mean.
 void renderPass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, uint32_t sampleBase, uint32_t sppTotal, uint32_t passFlags,
                 uint32_t part, uint32_t parts, float* dOut, float* dCov, hipStream_t stream, int mode, PtrRenderStats* stats) {
-    if (ds.cachedW != settings.width || ds.cachedH != settings.height || ds.cachedPart != part || ds.cachedParts != parts) {
-        std::vector<uint32_t> pixels;
+    // Pixels whose camera rays cannot reach the scene stay out of the pool: k_background resolves them (csrc/host/background_cull.h).
+    // The rectangle is part of the cache key: camera and bounds may change between two calls on one scene handle.
+    const ptr::CullRect cull = ptrhost::passCullRect(ds.worldBounds, settings, dCov != nullptr, mode);
+    if (ds.cachedW != settings.width || ds.cachedH != settings.height || ds.cachedPart != part || ds.cachedParts != parts || !(ds.cachedCull == cull)) {
+        std::vector<uint32_t> pixels, background;
         partitionPixels(settings.width, settings.height, part, parts, pixels);
+        if (cull.cull) {   // split, order kept
+            size_t kept = 0;
+            for (const uint32_t pixel : pixels) {
+                if (cull.inside(pixel % settings.width, pixel / settings.width)) pixels[kept++] = pixel;
+                else background.push_back(pixel);
+            }
+            pixels.resize(kept);
+        }
         ds.pixelOfLocal.upload(pixels.data(), pixels.size());
+        ds.backgroundPixels.upload(background.data(), background.size());
         ds.cachedW = settings.width;
         ds.cachedH = settings.height;
         ds.cachedPart = part;
         ds.cachedParts = parts;
+        ds.cachedCull = cull;
         ds.cachedLocalPixels = static_cast<uint32_t>(pixels.size());
+        ds.cachedBackgroundPixels = static_cast<uint32_t>(background.size());
     }
     const uint32_t localPixels = ds.cachedLocalPixels;
+    const BackgroundPixels background{ds.backgroundPixels.ptr, ds.cachedBackgroundPixels, parts, dOut};
     const uint32_t bandCount = ptr_part_band_count(settings.height, part, parts);
     const size_t outFloats = static_cast<size_t>(bandCount) * PTR_BAND_ROWS * settings.width * 3u;
     if (passFlags & 1u) HIP_CHECK(hipMemsetAsync(dOut, 0, outFloats * sizeof(float), stream));
     if (dCov && (passFlags & 1u)) HIP_CHECK(hipMemsetAsync(dCov, 0, outFloats * 2u * sizeof(float), stream));
     if (localPixels == 0) {
+        const auto wall0 = std::chrono::steady_clock::now();
+        if (background.count > 0u) {   // every pixel of the partition was culled: the background kernel is the whole pass
+            RenderParams rp;
+            fillRenderParams(settings, spp, rp);
+            rp.sampleBase = sampleBase;
+            rp.sppTotal = std::max(1u, sppTotal);
+            rp.passFlags = passFlags;
+            launchBackground(rp, ds.view, background.pixels, background.count, parts, dOut, stream);
+            HIP_CHECK(hipGetLastError());
+        }
         HIP_CHECK(hipStreamSynchronize(stream));
+        if (stats && background.count > 0u) {
+            std::memset(stats, 0, sizeof(*stats));
+            stats->totalSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - wall0).count();
+            stats->avgMsPerSample = stats->totalSeconds * 1000.0 / std::max(1u, spp);
+            stats->uploadSeconds = ds.uploadSeconds;
+            stats->samples = static_cast<uint64_t>(background.count) * std::max(1u, spp);
+        }
         return;
     }
     tracePass(ds, settings, spp, sampleBase, sppTotal, passFlags, ds.pixelOfLocal.ptr, localPixels, stream, mode, stats,
@@ -939,15 +994,19 @@ void renderPass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, u
                       ds.covMean.ensure(localPixels);
                       timer.launch(SpanKind::ResolveCov, stream, [&] { launchResolveCov(rp, pool, parts, ds.covMean.ptr, dCov, stream); });
                   }
-              });
+              },
+              background);
+    if (stats) stats->samples += static_cast<uint64_t>(background.count) * std::max(1u, spp);   // resolved like the traced ones
 }
 
 // The part of a pass that traces its work items: from the parameter set-up through the end-of-frame kernels, then `resolve` (what
 // reads the per-sample accumulators: see renderPass), the stream joined and the figures of the pass.  dPixelOfLocal: the image pixel
 // of each of the pass's `localPixels` (> 0) local pixels, on the device.
+// `background`: pixels the pool never sees; k_background writes them on `stream` while the other groups' first launches run.
 template <typename Resolve>
 void tracePass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, uint32_t sampleBase, uint32_t sppTotal, uint32_t passFlags,
-               const uint32_t* dPixelOfLocal, uint32_t localPixels, hipStream_t stream, int mode, PtrRenderStats* stats, Resolve&& resolve) {
+               const uint32_t* dPixelOfLocal, uint32_t localPixels, hipStream_t stream, int mode, PtrRenderStats* stats, Resolve&& resolve,
+               const BackgroundPixels& background) {
     const bool count = (mode & 1) != 0;         // counting instantiation of the kernels
     const bool soloGroup = (mode & 2) != 0;     // one pool group: kernels run alone, for clean per-kernel timings
 
@@ -1005,6 +1064,10 @@ void tracePass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, ui
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipEventRecord(ds.groupEvents[0], stream));
     for (size_t g = 1; g < groups.size(); ++g) HIP_CHECK(hipStreamWaitEvent(groups[g].stream, ds.groupEvents[0], 0));
+    if (background.count > 0u) {
+        timer.launch(SpanKind::Background, stream,
+                     [&] { launchBackground(rp, ds.view, background.pixels, background.count, background.parts, background.out, stream); });
+    }
     uint64_t iterations = 0;
     // Worst case: every sample runs maxDepth bounces in sequence on its slot.
     // (a subsurface random walk adds up to sssMaxSteps iterations to a bounce)

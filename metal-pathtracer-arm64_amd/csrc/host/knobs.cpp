@@ -44,6 +44,7 @@ Knobs readKnobs() {
     k.refillBelow = static_cast<int>(std::min<long long>(std::max<long long>(numberOr("PTR_REFILL_BELOW", 0), 0), 64));
     k.buildThreads = static_cast<uint32_t>(std::min<long long>(std::max<long long>(numberOr("PTR_BUILD_THREADS", 0), 0), 256));
     k.noOversize = numberOr("PTR_NO_OVERSIZE", 0) != 0;
+    k.backgroundCull = numberOr("PTR_BACKGROUND_CULL", 1) != 0;
     k.denoiseTiled = static_cast<int>(numberOr("PTR_DENOISE_TILED", -1));
     const char* verbose = std::getenv("PTR_VERBOSE");
     k.verboseBuild = hasTopic(verbose, "build");

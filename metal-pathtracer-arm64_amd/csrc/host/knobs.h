@@ -1,6 +1,6 @@
 // Every environment variable the library reads, in one place.  They exist for tests (scheduling must not change the image:
-// tests/test_gpu_parity.py::test_scheduling_knobs_do_not_change_the_image sets each of them) and for A/B measurements; a product run
-// sets none.  Read afresh at every scene upload / render, so a test can change them between two calls of one process.
+// tests/test_gpu_parity.py::test_scheduling_knobs_do_not_change_the_image sets each of them, and tests/test_gpu_background_cull.py sets
+// PTR_BACKGROUND_CULL) and for A/B measurements; a product run sets none.  Read afresh at every scene upload / render, so a test can change them between two calls of one process.
 #pragma once
 
 #include <cstdint>
@@ -18,6 +18,7 @@ struct Knobs {
     int refillBelow = 0;           // PTR_REFILL_BELOW      traversing lanes below which a persistent wave refills, 1..64 (0: default 40)
     uint32_t buildThreads = 0;     // PTR_BUILD_THREADS     BVH builder threads (0: all cores)
     bool noOversize = false;       // PTR_NO_OVERSIZE       keep every triangle in the tree
+    bool backgroundCull = true;    // PTR_BACKGROUND_CULL   0: a plain frame traces every pixel (default: pixels whose camera rays cannot reach the scene are resolved by k_background, csrc/host/background_cull.h)
     int denoiseTiled = -1;         // PTR_DENOISE_TILED     0: every denoiser kernel reads its taps through the caches; 1: the LDS-tiled kernel wherever there is one (-1: default, csrc/host/denoise.cpp)
     // PTR_VERBOSE: comma-separated topics printed to stderr - build (BVH / upload timings), polls (live slots per host poll),
     // launches (when each kernel ran), steps (lane-utilisation counters of a counting render)

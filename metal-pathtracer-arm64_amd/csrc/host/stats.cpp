@@ -74,7 +74,8 @@ int ptr_stats_debug_samples(PtrDeviceScene* scene, const PtrSettings* settings, 
         if (framePasses(*scene, *settings, spp) > 1u) throw HipError{"ptr_stats_debug_samples: the frame needs more than one pass"};
         const size_t pixels = static_cast<size_t>(settings->width) * settings->height;
         scene->outBands.ensure(bandPixels(*settings, 0u, 1u) * 3u);
-        renderBands(*scene, *settings, spp, 0u, 1u, scene->outBands.ptr, nullptr, 0, nullptr);
+        // (mode 4: every pixel through the pool - the accumulators read below are the per-sample values of the whole image)
+        renderBands(*scene, *settings, spp, 0u, 1u, scene->outBands.ptr, nullptr, 4, nullptr);
         std::vector<float4> items(pixels * spp);
         std::vector<uint32_t> pixelOfLocal(pixels);
         scene->itemAccum.download(items.data(), items.size());

@@ -43,6 +43,11 @@ void launchTail(const RenderParams& rp, const SceneView& sc, const PathPool& poo
 // Adds outstanding light connections, reduces the slots of each pixel in fixed order and writes
 // out[((localBand*PTR_BAND_ROWS + row) * width + x) * 3 + c] = sum / spp.
 void launchResolve(const RenderParams& rp, const PathPool& pool, uint32_t partCount, float* dOut, hipStream_t stream);
+// The `pixelCount` image pixels dPixels names, whose camera rays cannot reach the scene (csrc/host/background_cull.h): all rp.spp samples
+// of the pass, written to dOut as launchResolve writes the traced pixels (same band layout, same pass logic).  rp: the pass's, with
+// sampleBase, sppTotal and passFlags set.  Touches no pool.
+void launchBackground(const RenderParams& rp, const SceneView& sc, const uint32_t* dPixels, uint32_t pixelCount, uint32_t partCount, float* dOut,
+                      hipStream_t stream);
 // After launchResolve of the same pass (defined in stats.hip; include/ptr_stats.h): the covariance of every pixel's mean, six floats per
 // pixel in the band layout of dOut.  dMean: localPixels float4, the running mean between the passes of a frame; dCov holds the
 // unnormalised sums until the last pass.

@@ -1293,6 +1293,28 @@ __device__ __forceinline__ bool surfaceIsDelta(const Mat& mat, uint32_t type, co
     return surfaceDelta;
 }
 
+// A ray that left the scene: adds to `acc` the background by mode (storedLod: the environment level PTR_METAL_ENV_LOD stored for the
+// slot's ray; otherwise level 0), MIS-weighted against environment sampling, through the firefly clamp.  envWidth / envSampling: the
+// scene's, or zero where the caller's instantiation compiles the environment out.  Shared by shadeSlot and k_background.
+__device__ __forceinline__ void addEscapedRadiance(const RenderParams& rp, const SceneView& sc, const EnvLodView& env, const ClampCfg& cc, const f3& rayD, const f3& thr,
+                                                   const bool lastDelta, const float lastPdf, const bool storedLod, const uint32_t slot, const uint32_t envWidth,
+                                                   const bool envSampling,
+                                                   f3& acc) {
+    f3 bg;
+    if (rp.backgroundMode == PTR_BG_SOLID) {
+        bg = ld3(rp.backgroundColor);
+    } else if (rp.backgroundMode == PTR_BG_ENVIRONMENT && envWidth > 0u) {
+        const float lod = storedLod ? env.slotLod[slot] : -1.0f;
+        bg = lod >= 0.0f ? envLookupLod(sc, env, rayD, rp.envRotation, rp.envIntensity, lod) : envLookup(sc, rayD, rp.envRotation, rp.envIntensity);
+    } else {
+        bg = skyColor(rayD);
+    }
+    float mis = 1.0f;
+    const bool useMis = (!lastDelta) || rp.enableSpecularNee || rp.enableMnee;
+    if (useMis && envSampling) mis = bsdfSideMis(lastPdf, envPdfOf(sc, rayD, rp.envRotation));
+    acc += clampFirefly(thr, bg * mis, cc);
+}
+
 // One visit of a path slot: what k_shade does for its thread's slot.  MODE kShadeDense: lane l of wave w holds slot 64 w + l.
 // kShadeListed: the lanes hold the slots of a busy list (end of the frame) - the wave is converged but its slots are arbitrary, so
 // work items are claimed lane by lane.  kShadeTail: the caller is the end-of-frame kernel (k_tail_run), whose lanes hold arbitrary
@@ -1477,20 +1499,8 @@ __device__ __forceinline__ void shadeSlot(const RenderParams& rp, const SceneVie
             } else if (prim == kHitMiss) {
                 // ---- escaped: background, MIS-weighted against environment sampling ----
                 const long long tMiss = partBegin<COUNT>();
-                f3 bg;
-                if (rp.backgroundMode == PTR_BG_SOLID) {
-                    bg = ld3(rp.backgroundColor);
-                } else if (rp.backgroundMode == PTR_BG_ENVIRONMENT && envWidth > 0u) {
-                    // (a camera ray, depth 0, always reads level 0; every deeper ray's LOD was stored at the visit that sampled it)
-                    const float lod = (envLodOn && depth > 0u) ? env.slotLod[slot] : -1.0f;
-                    bg = lod >= 0.0f ? envLookupLod(sc, env, rayD, rp.envRotation, rp.envIntensity, lod) : envLookup(sc, rayD, rp.envRotation, rp.envIntensity);
-                } else {
-                    bg = skyColor(rayD);
-                }
-                float mis = 1.0f;
-                const bool useMis = (!lastDelta) || rp.enableSpecularNee || rp.enableMnee;
-                if (useMis && envSampling) mis = bsdfSideMis(lastPdf, envPdfOf(sc, rayD, rp.envRotation));
-                acc += clampFirefly(thr, bg * mis, cc);
+                // (a camera ray, depth 0, always reads level 0; every deeper ray's LOD was stored at the visit that sampled it)
+                addEscapedRadiance(rp, sc, env, cc, rayD, thr, lastDelta, lastPdf, envLodOn && depth > 0u, slot, envWidth, envSampling, acc);
                 if (COUNT) sig = (sig & 0xFFFFu) | (sigHashStep(sig >> 16, 7u, 0u, 0u) << 16);
                 endPath = true;
                 partEnd<COUNT>(counts, kShadePartMiss, tMiss);
@@ -2267,6 +2277,40 @@ __global__ void __launch_bounds__(256) k_resolve(RenderParams rp, PathPool pool,
 }
 
 // =====================================================================================================
+// k_background: the pixels whose camera rays cannot reach the scene (csrc/host/background_cull.h), one thread per pixel.  Every sample
+// of the pass is what k_shade makes of a camera ray that escapes - same seed, same ray, addEscapedRadiance with the state of a fresh
+// sample - summed and written as k_flush / k_resolve would: sample value = 0 + contribution, sum += value in sample order, then the
+// pass logic of k_resolve.  A cold kernel: the environment features are run-time branches, only the Metal-only clamps are compiled
+// (SSS, as in k_shade).
+// =====================================================================================================
+template <bool SSS>
+__global__ void __launch_bounds__(256) k_background(RenderParams rp, SceneView sc, const uint32_t* pixels, uint32_t pixelCount, uint32_t partCount,
+                                                    float* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= pixelCount) return;
+    const uint32_t pixel = pixels[i];
+    const ClampCfg cc = clampCfg<SSS>(rp);
+    const EnvLodView noLod{};   // a camera ray reads level 0
+    f3 sum = mk3(0.0f);
+    for (uint32_t s = 0; s < rp.spp; ++s) {
+        uint32_t rng;
+        f3 org, dir;
+        beginSample(rp, pixel, s, rng, org, dir);
+        f3 value = mk3(0.0f);
+        addEscapedRadiance(rp, sc, noLod, cc, dir, mk3(1.0f), true, 1.0f, false, 0u, sc.envWidth, sc.envSampling != 0u, value);
+        sum += value;
+    }
+    const uint32_t x = pixel % rp.width, y = pixel / rp.width;
+    const uint32_t localBand = (y / PTR_BAND_ROWS) / partCount;
+    float* o = out + (static_cast<size_t>(localBand * PTR_BAND_ROWS + (y % PTR_BAND_ROWS)) * rp.width + x) * 3u;
+    f3 total = (rp.passFlags & 1u) ? sum : mk3(o[0], o[1], o[2]) + sum;
+    if (rp.passFlags & 2u) total = total / static_cast<float>(rp.sppTotal);
+    o[0] = total.x;
+    o[1] = total.y;
+    o[2] = total.z;
+}
+
+// =====================================================================================================
 // k_aovs: first-hit feature buffers (what the reference hands to its denoiser: shaders/pathtrace.metal:6424-6435 sets
 // albedo = material base colour and normal = shading normal at the first hit; 9813-9815 writes albedo and
 // normal*0.5+0.5 per pixel).  One camera ray per pixel, the one sample `sample` of the path tracer starts with.
@@ -2800,6 +2844,15 @@ void launchTail(const RenderParams& rp, const SceneView& sc, const PathPool& poo
 void launchResolve(const RenderParams& rp, const PathPool& pool, uint32_t partCount, float* dOut, hipStream_t stream) {
     hipLaunchKernelGGL(k_flush, dim3(ceilDiv(pool.slots, 256)), dim3(256), 0, stream, rp, pool);
     hipLaunchKernelGGL(k_resolve, dim3(ceilDiv(rp.localPixels, 256)), dim3(256), 0, stream, rp, pool, partCount, dOut);
+}
+
+void launchBackground(const RenderParams& rp, const SceneView& sc, const uint32_t* dPixels, uint32_t pixelCount, uint32_t partCount, float* dOut,
+                      hipStream_t stream) {
+    if (pixelCount == 0u) return;
+    withBools([&](auto sssTag) {
+        hipLaunchKernelGGL(k_background<decltype(sssTag)::value>, dim3(ceilDiv(pixelCount, 256)), dim3(256), 0, stream, rp, sc, dPixels, pixelCount,
+                           partCount, dOut);
+    }, shadeVariant(rp, sc, false).sss);
 }
 
 void launchTraceRays(const SceneView& sc, const float4* dRays, uint64_t n, bool anyHit, PtrHit* dOut, const LaunchConfig& cfgIn,
