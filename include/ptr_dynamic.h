@@ -15,8 +15,10 @@
  * PtrUpdateInfo::cellOverExtent tells when a fresh upload would have chosen otherwise.  A refit does not rebuild: when boxes overlap
  * much more than a fresh tree's would, the caller uploads again.
  *
- * Only meshes move.  Rectangles, spheres, lights, materials, textures, vertex data and topology stay; ptr_render_multi*,
- * ptr_multi_frame_* and the geometry cache (ptr_scene_upload_prepared) do not take part: one dynamic scene per device handle.
+ * This header moves whole meshes rigidly.  ptr_deform.h adds, for scenes uploaded with its flags, new vertex data for a mesh and new
+ * places for spheres and rectangles, the lights among them.  Materials, emission, textures, uv coordinates and topology stay;
+ * ptr_render_multi*, ptr_multi_frame_* and the geometry cache (ptr_scene_upload_prepared) do not take part: one dynamic scene per
+ * device handle.
  *
  * Resumable frames (ptr_frame.h) on a dynamic scene keep working.  The samples a frame holds belong to the pose they were taken in:
  * after an update call ptr_frame_reset before accumulating again.  Nothing here tracks that.
@@ -66,7 +68,9 @@ int ptr_scene_is_dynamic(const PtrDeviceScene* scene);
  * The arrays of a device scene, dynamic or not, downloaded: *size_out = the array's size in bytes (0: the scene
  * has no such array); out may be NULL (size only).  tris, triNormals (48 B per triangle), triUv (64 B), triTangent (48 B), in leaf order;
  * the padded primitive bounds of a dynamic scene (32 B per triangle / sphere: lo xyz, 0, hi xyz, 0); the 64 B float nodes (a dynamic
- * scene, or a static one that renders from them); qnodes (32 B per node); wnodes (64 B per wide node); the grid (origin xyz, cell xyz).
+ * scene, or a static one that renders from them); qnodes (32 B per node); wnodes (64 B per wide node); the grid (origin xyz, cell xyz);
+ * the rects rows (80 B per rectangle), the rectLights rows (176 B per light) and the spheres rows (16 B, leaf order); the object-space
+ * corner rows of a dynamic scene (48 B per triangle each; objTan in textured scenes).
  * 1: bad argument, 2: cap_bytes too small, 3: the copy failed. */
 enum {
     PTR_SCENE_ARRAY_TRIS = 0,
@@ -78,7 +82,13 @@ enum {
     PTR_SCENE_ARRAY_BOXES = 6,
     PTR_SCENE_ARRAY_QNODES = 7,
     PTR_SCENE_ARRAY_WNODES = 8,
-    PTR_SCENE_ARRAY_GRID = 9
+    PTR_SCENE_ARRAY_GRID = 9,
+    PTR_SCENE_ARRAY_RECTS = 10,
+    PTR_SCENE_ARRAY_RECT_LIGHTS = 11,
+    PTR_SCENE_ARRAY_SPHERES = 12,
+    PTR_SCENE_ARRAY_OBJ_POS = 13,
+    PTR_SCENE_ARRAY_OBJ_NRM = 14,
+    PTR_SCENE_ARRAY_OBJ_TAN = 15
 };
 int ptr_debug_scene_arrays(PtrDeviceScene* scene, uint32_t which, void* out, uint64_t cap_bytes, uint64_t* size_out);
 /* Host-side (no GPU): the preparation ptr_scene_upload_dynamic performs on a description, one table per call, with the same outputs
@@ -86,7 +96,10 @@ int ptr_debug_scene_arrays(PtrDeviceScene* scene, uint32_t which, void* out, uin
  * bounds; the refit schedule (node indices grouped by height) and its level offsets (levels + 1 words); the wide-source table (per wide
  * place node * 2 + side, 0xFFFFFFFF: unused); the grid; the shared quantiser (csrc/kernels/bvh_grid.h) applied to the float nodes with
  * the grid the shared rule derives from node 0; the per-mesh triangle lists and their offsets; and info = {nodes, levels, wide nodes,
- * quantised nodes in use, triangles, spheres, tree depth, root reference, oversize reference, wide depth}. */
+ * quantised nodes in use, triangles, spheres, tree depth, root reference, oversize reference, wide depth}.  The tables of ptr_deform.h:
+ * the corner table (3 vertex indices per entry of the per-mesh lists), the leaf-order indices of every rectangle's two triangles, the
+ * leaf slot of every sphere; and the leaf-order arrays an upload copies to the device as they stand (tris, triNormals, spheres, rects,
+ * rectLights), which the row writers of ptr_deform.h are held against. */
 enum {
     PTR_DYNAMIC_TABLE_NODES = 0,
     PTR_DYNAMIC_TABLE_QNODES = 1,
@@ -100,7 +113,15 @@ enum {
     PTR_DYNAMIC_TABLE_REQUANTISED = 9,
     PTR_DYNAMIC_TABLE_MESH_TRI_OFFSETS = 10,
     PTR_DYNAMIC_TABLE_MESH_TRIS = 11,
-    PTR_DYNAMIC_TABLE_INFO = 12
+    PTR_DYNAMIC_TABLE_INFO = 12,
+    PTR_DYNAMIC_TABLE_MESH_CORNERS = 13,
+    PTR_DYNAMIC_TABLE_RECT_TRI_LEAF = 14,
+    PTR_DYNAMIC_TABLE_SPHERE_LEAF = 15,
+    PTR_DYNAMIC_TABLE_TRIS = 16,
+    PTR_DYNAMIC_TABLE_TRI_NORMALS = 17,
+    PTR_DYNAMIC_TABLE_SPHERES = 18,
+    PTR_DYNAMIC_TABLE_RECTS = 19,
+    PTR_DYNAMIC_TABLE_RECT_LIGHTS = 20
 };
 int ptr_debug_dynamic_tables(const PtrSceneDesc* scene, uint32_t which, void* out, uint64_t cap_bytes, uint64_t* size_out, char* err, size_t err_cap);
 

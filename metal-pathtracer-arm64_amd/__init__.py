@@ -486,6 +486,41 @@ _DYNAMIC_SIGNATURES = {
 }
 DYNAMIC_SYMBOLS = tuple(_DYNAMIC_SIGNATURES)
 
+# ... and of include/ptr_deform.h (deforming meshes, moving spheres and rectangles): tests/test_dynamic_deform_host.py holds it against that header
+PTR_DYNAMIC_DEFORMABLE = 1
+PTR_DYNAMIC_PRIMITIVES = 2
+
+
+class PtrMeshVertices(C.Structure):
+    """include/ptr_deform.h PtrMeshVertices."""
+    _fields_ = [("meshIndex", C.c_uint32), ("vertexCount", C.c_uint32), ("positions", C.POINTER(C.c_float)), ("normals", C.POINTER(C.c_float)),
+                ("tangents", C.POINTER(C.c_float))]
+
+
+class PtrSphereUpdate(C.Structure):
+    """include/ptr_deform.h PtrSphereUpdate."""
+    _fields_ = [("sphereIndex", C.c_uint32), ("pad", C.c_uint32 * 3), ("centerRadius", C.c_float * 4)]
+
+
+class PtrRectUpdate(C.Structure):
+    """include/ptr_deform.h PtrRectUpdate."""
+    _fields_ = [("rectIndex", C.c_uint32), ("pad", C.c_uint32 * 3), ("corner", C.c_float * 4), ("edgeU", C.c_float * 4), ("edgeV", C.c_float * 4),
+                ("normalAndPlane", C.c_float * 4)]
+
+
+_DEFORM_SIGNATURES = {
+    "ptr_scene_upload_dynamic_ex": (_int, [_desc, _int, _u32, C.POINTER(_vp)] + _err),
+    "ptr_scene_dynamic_flags": (_u32, [_vp]),
+    "ptr_scene_set_mesh_vertices": (_int, [_vp, C.POINTER(PtrMeshVertices), _u32, _vp, C.POINTER(PtrUpdateInfo)] + _err),
+    "ptr_scene_set_spheres": (_int, [_vp, C.POINTER(PtrSphereUpdate), _u32, _vp, C.POINTER(PtrUpdateInfo)] + _err),
+    "ptr_scene_set_rects": (_int, [_vp, C.POINTER(PtrRectUpdate), _u32, _vp, C.POINTER(PtrUpdateInfo)] + _err),
+    # its test-only probe
+    "ptr_debug_dynamic_update_rows": (_int, [_desc, _u32, _vp, _vp, _u64, _u64p] + _err),
+}
+DEFORM_SYMBOLS = tuple(_DEFORM_SIGNATURES)
+# ptr_debug_dynamic_update_rows: the arrays a destination word names, (array << 28) | row
+SCATTER_ARRAYS = ("tris", "triNormals", "triBounds", "spheres", "sphereBounds", "rects", "rectLights")
+
 # ... and of include/ptr_background.h (the primary-ray bounds cull): tests/test_background_cull_host.py holds it against that header
 _BACKGROUND_SIGNATURES = {
     "ptr_background_debug_cull": (_int, [_vp, _desc, _settings, _u32, _u32, _int, _up, C.POINTER(C.c_double)] + _err),
@@ -495,12 +530,16 @@ BACKGROUND_SYMBOLS = tuple(_BACKGROUND_SIGNATURES)
 # ptr_debug_scene_arrays / ptr_debug_dynamic_tables: name -> (selector, dtype, trailing shape)
 SCENE_ARRAYS = {"tris": (0, np.float32, (3, 4)), "triNormals": (1, np.float32, (3, 4)), "triUv": (2, np.float32, (4, 4)),
                 "triTangent": (3, np.float32, (3, 4)), "triBounds": (4, np.float32, (2, 4)), "sphereBounds": (5, np.float32, (2, 4)),
-                "boxes": (6, np.float32, (4, 4)), "qnodes": (7, np.uint32, (2, 4)), "wnodes": (8, np.uint32, (4, 4)), "grid": (9, np.float32, (3,))}
+                "boxes": (6, np.float32, (4, 4)), "qnodes": (7, np.uint32, (2, 4)), "wnodes": (8, np.uint32, (4, 4)), "grid": (9, np.float32, (3,)),
+                "rects": (10, np.float32, (5, 4)), "rectLights": (11, np.float32, (11, 4)), "spheres": (12, np.float32, (4,)),
+                "objPos": (13, np.float32, (3, 4)), "objNrm": (14, np.float32, (3, 4)), "objTan": (15, np.float32, (3, 4))}
 DYNAMIC_TABLES = {"nodes": (0, np.float32, (4, 4)), "qnodes": (1, np.uint32, (2, 4)), "wnodes": (2, np.uint32, (4, 4)),
                   "triBounds": (3, np.float32, (2, 4)), "sphereBounds": (4, np.float32, (2, 4)), "schedule": (5, np.uint32, ()),
                   "levelOffsets": (6, np.uint32, ()), "wideSource": (7, np.uint32, (4,)), "grid": (8, np.float32, (3,)),
                   "requantised": (9, np.uint32, (2, 4)), "meshTriOffsets": (10, np.uint32, ()), "meshTris": (11, np.uint32, ()),
-                  "info": (12, np.uint32, ())}
+                  "info": (12, np.uint32, ()), "meshCorners": (13, np.uint32, (3,)), "rectTriLeaf": (14, np.uint32, (2,)),
+                  "sphereLeaf": (15, np.uint32, ()), "tris": (16, np.float32, (3, 4)), "triNormals": (17, np.float32, (3, 4)),
+                  "spheres": (18, np.float32, (4,)), "rects": (19, np.float32, (5, 4)), "rectLights": (20, np.float32, (11, 4))}
 DYNAMIC_TABLE_INFO = ("nodes", "levels", "wide_nodes", "quantized", "triangles", "spheres", "max_depth", "root_ref", "oversize_ref", "wide_depth")
 
 _lib: Optional[C.CDLL] = None
@@ -521,7 +560,7 @@ def load_library() -> C.CDLL:
     lib = C.CDLL(path)
     for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_POST_SIGNATURES.items()) + list(_STATS_SIGNATURES.items()) + \
             list(_ADAPTIVE_SIGNATURES.items()) + list(_MULTI_SIGNATURES.items()) + list(_FRAME_SIGNATURES.items()) + list(_MULTI_FRAME_SIGNATURES.items()) + \
-            list(_DYNAMIC_SIGNATURES.items()) + list(_BACKGROUND_SIGNATURES.items()):
+            list(_DYNAMIC_SIGNATURES.items()) + list(_DEFORM_SIGNATURES.items()) + list(_BACKGROUND_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -637,10 +676,12 @@ def prepare_geometry(desc: PtrSceneDesc, path: str) -> float:
 class DeviceScene:
     """A scene resident in HBM: SAH BVH + SoA primitive/material/light arrays (ptr_scene_upload)."""
 
-    def __init__(self, desc: PtrSceneDesc, device: int = 0, keepalive=None, prepared: Optional[str] = None, dynamic: bool = False):
+    def __init__(self, desc: PtrSceneDesc, device: int = 0, keepalive=None, prepared: Optional[str] = None, dynamic: bool = False,
+                 deformable: bool = False, primitives: bool = False):
         """prepared: a geometry cache written by prepare_geometry() for this description - the BVH is read, not built
         (the processes of a multi-GPU render build it once).  dynamic: ptr_scene_upload_dynamic - the scene also keeps what
-        set_mesh_transforms needs to move its meshes on the device (not with `prepared`)."""
+        set_mesh_transforms needs to move its meshes on the device (not with `prepared`).  deformable / primitives (with dynamic):
+        ptr_scene_upload_dynamic_ex with PTR_DYNAMIC_DEFORMABLE / PTR_DYNAMIC_PRIMITIVES, for set_mesh_vertices / set_spheres and set_rects."""
         lib = load_library()
         if lib.ptr_device_count() <= 0:
             raise PtrError("no HIP device visible: the HIP render path has no CPU fallback")
@@ -649,7 +690,12 @@ class DeviceScene:
         err = _err_buf()
         if dynamic and prepared:
             raise PtrError("a dynamic scene is not read from a geometry cache")
-        if dynamic:
+        if (deformable or primitives) and not dynamic:
+            raise PtrError("deformable / primitives need dynamic=True")
+        if deformable or primitives:
+            flags = (PTR_DYNAMIC_DEFORMABLE if deformable else 0) | (PTR_DYNAMIC_PRIMITIVES if primitives else 0)
+            _check(lib.ptr_scene_upload_dynamic_ex(C.byref(desc), device, flags, C.byref(self._h), err, len(err)), err)
+        elif dynamic:
             _check(lib.ptr_scene_upload_dynamic(C.byref(desc), device, C.byref(self._h), err, len(err)), err)
         elif prepared:
             _check(lib.ptr_scene_upload_prepared(C.byref(desc), prepared.encode(), device, C.byref(self._h), err, len(err)), err)
@@ -670,6 +716,49 @@ class DeviceScene:
         info = PtrUpdateInfo()
         err = _err_buf()
         _check(load_library().ptr_scene_set_mesh_transforms(self._h, items, len(transforms), C.c_void_p(stream), C.byref(info), err, len(err)), err)
+        return info.as_dict()
+
+    @property
+    def dynamic_flags(self) -> int:
+        return int(load_library().ptr_scene_dynamic_flags(self._h))
+
+    def set_mesh_vertices(self, meshes: dict, stream: int = 0) -> dict:
+        """ptr_scene_set_mesh_vertices: {mesh index: (positions [n, 3], normals [n, 3][, tangents [n, 4]])}, object space; returns
+        PtrUpdateInfo as a dict."""
+        items = (PtrMeshVertices * max(len(meshes), 1))()
+        keep = []
+        fp = C.POINTER(C.c_float)
+        for k, (index, data) in enumerate(meshes.items()):
+            arrays = [np.ascontiguousarray(a, np.float32).reshape(-1, w) for a, w in zip(data, (3, 3, 4))]
+            keep.append(arrays)
+            items[k].meshIndex, items[k].vertexCount = int(index), len(arrays[0])
+            items[k].positions, items[k].normals = arrays[0].ctypes.data_as(fp), arrays[1].ctypes.data_as(fp)
+            items[k].tangents = arrays[2].ctypes.data_as(fp) if len(arrays) > 2 else None
+        info = PtrUpdateInfo()
+        err = _err_buf()
+        _check(load_library().ptr_scene_set_mesh_vertices(self._h, items, len(meshes), C.c_void_p(stream), C.byref(info), err, len(err)), err)
+        return info.as_dict()
+
+    def set_spheres(self, spheres: dict, stream: int = 0) -> dict:
+        """ptr_scene_set_spheres: {sphere index: (cx, cy, cz, radius)}; returns PtrUpdateInfo as a dict."""
+        items = (PtrSphereUpdate * max(len(spheres), 1))()
+        for k, (index, row) in enumerate(spheres.items()):
+            items[k].sphereIndex = int(index)
+            items[k].centerRadius[:] = np.asarray(row, np.float32).reshape(4).tolist()
+        info = PtrUpdateInfo()
+        err = _err_buf()
+        _check(load_library().ptr_scene_set_spheres(self._h, items, len(spheres), C.c_void_p(stream), C.byref(info), err, len(err)), err)
+        return info.as_dict()
+
+    def set_rects(self, rects: dict, stream: int = 0) -> dict:
+        """ptr_scene_set_rects: {rectangle index: dict(corner=, edgeU=, edgeV=, normal=)}, three components each; the w words are filled
+        as the scene loader fills them (rect_update).  Returns PtrUpdateInfo as a dict."""
+        items = (PtrRectUpdate * max(len(rects), 1))()
+        for k, (index, r) in enumerate(rects.items()):
+            items[k] = rect_update(index, **r)
+        info = PtrUpdateInfo()
+        err = _err_buf()
+        _check(load_library().ptr_scene_set_rects(self._h, items, len(rects), C.c_void_p(stream), C.byref(info), err, len(err)), err)
         return info.as_dict()
 
     def arrays(self, names=None) -> dict:
@@ -1501,6 +1590,40 @@ def debug_scene_geometry(desc: PtrSceneDesc, leaf_max: int = 0) -> dict:
     g["wide_problems"] = word >> 63                      # bad references / primitives not reached exactly once through them
     g["quantized_usable"] = word & 0xFF
     return g
+
+
+def rect_update(index: int, corner, edgeU, edgeV, normal) -> PtrRectUpdate:
+    """A PtrRectUpdate with the w words the scene loader stores (SceneResources::storeRectangleOriented): 0, 1/|U|^2, 1/|V|^2, and the
+    unit normal with dot(normal, corner); float32 arithmetic in the loader's order."""
+    f = np.float32
+    c, u, v, n = (np.asarray(a, f).reshape(3) for a in (corner, edgeU, edgeV, normal))
+
+    def dot(a, b):
+        return f(f(f(a[0] * b[0]) + f(a[1] * b[1])) + f(a[2] * b[2]))
+
+    out = PtrRectUpdate()
+    out.rectIndex = int(index)
+    with np.errstate(all="ignore"):
+        unit = n / np.sqrt(dot(n, n)) if dot(n, n) > 0 else n
+        out.corner[:] = [float(c[0]), float(c[1]), float(c[2]), 0.0]
+        out.edgeU[:] = [float(u[0]), float(u[1]), float(u[2]), float(f(1.0) / dot(u, u))]
+        out.edgeV[:] = [float(v[0]), float(v[1]), float(v[2]), float(f(1.0) / dot(v, v))]
+        out.normalAndPlane[:] = [float(unit[0]), float(unit[1]), float(unit[2]), float(dot(unit, c))]
+    return out
+
+
+def debug_dynamic_update_rows(desc: PtrSceneDesc, update) -> list:
+    """ptr_debug_dynamic_update_rows (host only): what ptr_scene_set_spheres / ptr_scene_set_rects would scatter for one PtrSphereUpdate /
+    PtrRectUpdate on `desc`, as [(array name of SCATTER_ARRAYS, row, float32[4])]."""
+    lib = load_library()
+    err = _err_buf()
+    kind = 0 if isinstance(update, PtrSphereUpdate) else 1
+    n = C.c_uint64(0)
+    _check(lib.ptr_debug_dynamic_update_rows(C.byref(desc), kind, C.byref(update), None, 0, C.byref(n), err, len(err)), err)
+    buf = np.zeros(n.value * 5, np.uint32)
+    _check(lib.ptr_debug_dynamic_update_rows(C.byref(desc), kind, C.byref(update), buf.ctypes.data_as(C.c_void_p), buf.nbytes, C.byref(n), err, len(err)), err)
+    rows, dest = buf[: n.value * 4].view(np.float32).reshape(-1, 4), buf[n.value * 4:]
+    return [(SCATTER_ARRAYS[int(d) >> 28], int(d) & 0x0FFFFFFF, rows[i]) for i, d in enumerate(dest)]
 
 
 def debug_dynamic_tables(desc: PtrSceneDesc, names=None) -> dict:

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../kernels/device_types.h"
+#include "../kernels/dynamic.h"
 #include "../kernels/launch.h"
 #include "background_cull.h"
 #include "env_importance_sampler.h"
@@ -97,6 +98,19 @@ using ptrhost::DeviceBuffer;
 
 namespace ptrhost {
 
+// Host side of PTR_DYNAMIC_PRIMITIVES (include/ptr_deform.h): where the rows of every rectangle and sphere live on the device, what does
+// not change about them, and the records they currently hold.  Filled from a description and its preparation (dynamic.cpp).
+struct PrimitiveRecords {
+    std::vector<uint32_t> rectTriLeaf;   // 2 per rectangle: leaf-order indices of its triangles (0xFFFFFFFF: not in the geometry)
+    std::vector<uint32_t> sphereLeaf;    // original sphere index -> leaf slot
+    std::vector<uint32_t> rectShadeKey;  // per rectangle: the shade key in the meta word of its triangles
+    std::vector<int32_t> lightIndexByRect;
+    std::vector<float> rectEmission;     // 3 per rectangle (zeros for one that is no light)
+    std::vector<PtrRect> rects;
+    std::vector<PtrSphere> spheres;
+    uint32_t triCount = 0;               // rows of the arrays, for the destinations' bounds
+};
+
 // What a dynamic scene (include/ptr_dynamic.h) keeps beside the arrays the kernels render from: ptr::DynamicTables on the device, the
 // float child boxes of every node, and the figures ptr_scene_set_mesh_transforms reports.  A static scene has none of it.
 struct DynamicScene {
@@ -112,11 +126,35 @@ struct DynamicScene {
     float meanPrimExtent = 0.0f;
     hipEvent_t events[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     float4* rootBox = nullptr;   // pinned: node 0 after a refit
+    // the matrix every mesh currently has, as the bake reads it: from the description at upload, then from ptr_scene_set_mesh_transforms
+    std::vector<ptrk::DynMeshRow> meshRows;
+    // include/ptr_deform.h.  flags: what the upload kept (PTR_DYNAMIC_*).
+    uint32_t flags = 0;
+    // PTR_DYNAMIC_DEFORMABLE: the corner table (3 vertex indices per entry of meshTris) and what validates a call
+    DeviceBuffer<uint32_t> meshCorners;
+    std::vector<uint32_t> meshVertexCount;
+    std::vector<uint8_t> meshTangentsGiven;
+    // PTR_DYNAMIC_PRIMITIVES: where the rows of a rectangle and of a sphere live, and the records they currently hold
+    PrimitiveRecords prims;
+    // staging of the update calls, grown on demand and kept: a pinned host buffer and its device twin
+    DeviceBuffer<float4> staging;
+    void* pinned = nullptr;
+    size_t pinnedBytes = 0;
+    void* pinnedFor(size_t bytes) {
+        if (bytes > pinnedBytes) {
+            if (pinned) (void)hipHostFree(pinned);
+            pinned = nullptr, pinnedBytes = 0;
+            HIP_CHECK(hipHostMalloc(&pinned, bytes, hipHostMallocDefault));
+            pinnedBytes = bytes;
+        }
+        return pinned;
+    }
     ~DynamicScene() {
         for (hipEvent_t e : events) {
             if (e) (void)hipEventDestroy(e);
         }
         if (rootBox) (void)hipHostFree(rootBox);
+        if (pinned) (void)hipHostFree(pinned);
     }
 };
 
@@ -191,7 +229,7 @@ struct PtrDeviceScene {
     ptr::CullRect cachedCull;
     DeviceBuffer<uint32_t> backgroundPixels;
     // world box of everything a ray can hit (csrc/host/background_cull.h): from the primitives at upload, from the refitted root box
-    // after ptr_scene_set_mesh_transforms (invalid there when the scene keeps triangles out of the tree: nothing is culled then)
+    // after an update call of ptr_dynamic.h / ptr_deform.h (invalid there when the scene keeps triangles out of the tree: nothing is culled then)
     ptr::WorldBounds worldBounds;
 
     ~PtrDeviceScene() {
@@ -266,11 +304,15 @@ struct PreparedScene {
 // dyn (nullable): the tables of a dynamic scene as well.
 void prepareGeometry(const PtrSceneDesc& desc, ptr::PreparedGeometry& pg, ptr::DynamicTables* dyn = nullptr);
 // cachePath (may be null): read the geometry from that file instead of building it; dynamic: prepare a dynamic scene (no cache)
-void prepareScene(const PtrSceneDesc& desc, PreparedScene& ps, const char* cachePath = nullptr, bool dynamic = false);
+// dynamicFlags: PTR_DYNAMIC_* of include/ptr_deform.h, what a dynamic scene keeps beyond ptr_scene_upload_dynamic
+void prepareScene(const PtrSceneDesc& desc, PreparedScene& ps, const char* cachePath = nullptr, bool dynamic = false, uint32_t dynamicFlags = 0);
 // ds.device names the device
 void uploadScene(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceScene& ds);
 // the dynamic half of uploadScene (dynamic.cpp): ps.dyn and the float nodes to the device, ds.dynamic made
-void uploadDynamicTables(const PreparedScene& ps, PtrDeviceScene& ds);
+void uploadDynamicTables(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceScene& ds);
+// the rectangle-light half of prepareScene: the light table of `desc` over the geometry `geo`
+void buildRectLights(const PtrSceneDesc& desc, const ptr::SceneGeometry& geo, std::vector<float>& lights, std::vector<int32_t>& lightIndexByRect,
+                     uint32_t& lightCount, bool& lightsHaveTriangles);
 
 // What an entry point refuses before any device call: returns the C-ABI's code with the message in `err`.
 inline int refuse(char* err, size_t cap, const std::string& message) {

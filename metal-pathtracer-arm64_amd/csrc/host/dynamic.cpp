@@ -1,6 +1,7 @@
-// Dynamic scenes (include/ptr_dynamic.h): the upload of the extra device data, ptr_scene_set_mesh_transforms, and that header's two
-// test-only probes, which look at a scene's arrays.  Compiled with hipcc (host code only), like hip_backend.cpp; the kernels are in
-// kernels/dynamic.hip.
+// Dynamic scenes (include/ptr_dynamic.h, include/ptr_deform.h): the upload of the extra device data, ptr_scene_set_mesh_transforms,
+// ptr_scene_set_mesh_vertices, ptr_scene_set_spheres and ptr_scene_set_rects, which all end in the same refit (finishUpdate), and the
+// headers' test-only probes, which look at a scene's arrays.  Compiled with hipcc (host code only), like hip_backend.cpp; the kernels are
+// in kernels/dynamic.hip.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -8,14 +9,46 @@
 #include "../kernels/bvh_grid.h"
 #include "../kernels/dynamic.h"
 #include "device_scene.h"
+#include "ptr_deform.h"
 #include "ptr_dynamic.h"
+#include "vecmath.h"
 
 using namespace ptrk;
 using namespace ptrhost;
 
 namespace ptrhost {
 
-void uploadDynamicTables(const PreparedScene& ps, PtrDeviceScene& ds) {
+ptrk::DynMeshRow meshRowOf(const ptr::MeshBake& bake, bool hasTangents) {
+    DynMeshRow r;
+    std::memset(&r, 0, sizeof(r));
+    std::memcpy(r.l2w, bake.localToWorld, sizeof(r.l2w));
+    std::memcpy(r.nc0, bake.nc0, 12);
+    std::memcpy(r.nc1, bake.nc1, 12);
+    std::memcpy(r.nc2, bake.nc2, 12);
+    r.detSign = bake.detSign;
+    r.hasTangents = hasTangents ? 1.0f : 0.0f;
+    return r;
+}
+
+void fillPrimitiveRecords(const PtrSceneDesc& desc, const ptr::SceneGeometry& geo, const ptr::DynamicTables& t, const std::vector<int32_t>& lightIndexByRect,
+                          PrimitiveRecords& out) {
+    out = PrimitiveRecords{};
+    out.rectTriLeaf = geo.rectTriLeaf;
+    out.sphereLeaf = t.sphereLeaf;
+    out.rectShadeKey = t.rectShadeKey;
+    out.lightIndexByRect = lightIndexByRect;
+    out.rectEmission.assign(static_cast<size_t>(desc.rectCount) * 3u, 0.0f);
+    for (uint32_t i = 0; i < desc.rectCount; ++i) {
+        if (lightIndexByRect[i] < 0) continue;
+        const PtrMaterial& m = desc.materials[std::min(desc.rects[i].materialTwoSided[0], desc.materialCount - 1u)];
+        std::memcpy(&out.rectEmission[static_cast<size_t>(i) * 3u], m.emission, 12);
+    }
+    out.rects.assign(desc.rects, desc.rects + desc.rectCount);
+    out.spheres.assign(desc.spheres, desc.spheres + desc.sphereCount);
+    out.triCount = geo.triCount;
+}
+
+void uploadDynamicTables(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceScene& ds) {
     const ptr::DynamicTables& t = ps.dyn;
     const ptr::FlatBvh& bvh = ps.pg.geo.bvh;
     auto dyn = std::make_unique<DynamicScene>();
@@ -38,6 +71,17 @@ void uploadDynamicTables(const PreparedScene& ps, PtrDeviceScene& ds) {
     dyn->triCount = ps.pg.geo.triCount;
     dyn->sphereCount = ps.pg.geo.sphereCount;
     dyn->meanPrimExtent = bvh.meanPrimExtent;
+    dyn->meshRows.resize(t.meshBakes.size());
+    for (size_t m = 0; m < t.meshBakes.size(); ++m) dyn->meshRows[m] = meshRowOf(t.meshBakes[m], t.meshHasTangents[m] != 0);
+    dyn->flags = t.flags;
+    if (t.flags & PTR_DYNAMIC_DEFORMABLE) {
+        dyn->meshCorners.upload(t.meshCorners.data(), t.meshCorners.size());
+        dyn->meshVertexCount = t.meshVertexCount;
+        dyn->meshTangentsGiven = t.meshTangentsGiven;
+    }
+    if (t.flags & PTR_DYNAMIC_PRIMITIVES) {
+        fillPrimitiveRecords(desc, ps.pg.geo, t, ps.lightIndexByRect, dyn->prims);
+    }
     for (hipEvent_t& e : dyn->events) HIP_CHECK(hipEventCreate(&e));
     HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&dyn->rootBox), 4 * sizeof(float4), hipHostMallocDefault));
     ds.dynamic = std::move(dyn);
@@ -48,6 +92,26 @@ void uploadDynamicTables(const PreparedScene& ps, PtrDeviceScene& ds) {
 namespace {
 
 float4* floatBoxes(PtrDeviceScene& ds) { return ds.view.useQuantized ? ds.dynamic->boxes.ptr : ds.nodes.ptr; }
+
+DynBakeArrays bakeArrays(PtrDeviceScene& ds) {
+    DynamicScene& dyn = *ds.dynamic;
+    return DynBakeArrays{dyn.objPos.ptr, dyn.objNrm.ptr, dyn.textured ? dyn.objTan.ptr : nullptr, ds.tris.ptr, ds.triNormals.ptr, dyn.triBounds.ptr,
+                         dyn.textured ? ds.triUv.ptr : nullptr, dyn.textured ? ds.triTangent.ptr : nullptr};
+}
+
+// The staging buffer of ptr_scene_set_spheres / ptr_scene_set_rects: 16 B rows and where each goes, (PTR_SCATTER_* << 28) | row
+struct ScatterRows {
+    std::vector<float> rows;
+    std::vector<uint32_t> dest;
+};
+
+// (defined below the entry points)
+void finishUpdate(PtrDeviceScene& ds, hipStream_t st, std::chrono::steady_clock::time_point t0, uint64_t moved, PtrUpdateInfo* info);
+// The host half of a sphere's / a rectangle's move: the new record into `prims`, its rows appended to `out`.  "" or what is wrong with it.
+std::string sphereRows(PrimitiveRecords& prims, const PtrSphereUpdate& u, ScatterRows& out);
+std::string rectRows(PrimitiveRecords& prims, const PtrRectUpdate& u, ScatterRows& out);
+int setPrimitives(const char* who, uint32_t kind, PtrDeviceScene* scene, const void* list, uint32_t count, void* stream, PtrUpdateInfo* info, char* err,
+                  size_t err_cap);
 
 // the root box of the tree from node 0: the union of its children that exist
 bool rootBoxOf(const float4 row[4], float lo[3], float hi[3]) {
@@ -107,14 +171,7 @@ int ptr_scene_set_mesh_transforms(PtrDeviceScene* scene, const PtrMeshTransform*
             ptr::ComputeMeshBake(t.localToWorld, bake);
             const std::string problem = matrixProblem(t.localToWorld, bake);
             if (!problem.empty()) return refuse(err, err_cap, std::string(who) + ": the matrix of mesh " + std::to_string(t.meshIndex) + " " + problem);
-            DynMeshRow& r = rows[i];
-            std::memset(&r, 0, sizeof(r));
-            std::memcpy(r.l2w, bake.localToWorld, sizeof(r.l2w));
-            std::memcpy(r.nc0, bake.nc0, 12);
-            std::memcpy(r.nc1, bake.nc1, 12);
-            std::memcpy(r.nc2, bake.nc2, 12);
-            r.detSign = bake.detSign;
-            r.hasTangents = dyn.meshHasTangents[t.meshIndex] ? 1.0f : 0.0f;
+            rows[i] = meshRowOf(bake, dyn.meshHasTangents[t.meshIndex] != 0);
         }
     }
     PTR_CATCH_ALL(err, err_cap)
@@ -123,19 +180,182 @@ int ptr_scene_set_mesh_transforms(PtrDeviceScene* scene, const PtrMeshTransform*
         const auto t0 = std::chrono::steady_clock::now();
         hipStream_t st = static_cast<hipStream_t>(stream);
         PtrDeviceScene& ds = *scene;
-        SceneView& v = ds.view;
         dyn.meshTable.ensure(static_cast<size_t>(count) * kDynMeshVec4);
         HIP_CHECK(hipMemcpyAsync(dyn.meshTable.ptr, rows.data(), rows.size() * sizeof(DynMeshRow), hipMemcpyHostToDevice, st));
         HIP_CHECK(hipEventRecord(dyn.events[0], st));
-        DynBakeArrays arrays{dyn.objPos.ptr, dyn.objNrm.ptr, dyn.textured ? dyn.objTan.ptr : nullptr, ds.tris.ptr, ds.triNormals.ptr, dyn.triBounds.ptr,
-                             dyn.textured ? ds.triUv.ptr : nullptr, dyn.textured ? ds.triTangent.ptr : nullptr};
+        const DynBakeArrays arrays = bakeArrays(ds);
         uint64_t moved = 0;
         for (uint32_t i = 0; i < count; ++i) {
             const uint32_t m = transforms[i].meshIndex;
             const uint32_t first = dyn.meshTriOffsets[m], n = dyn.meshTriOffsets[m + 1u] - first;
             launchDynBake(arrays, dyn.meshTable.ptr, i, dyn.meshTris.ptr + first, n, st);
+            dyn.meshRows[m] = rows[i];   // the matrix a later ptr_scene_set_mesh_vertices bakes under
             moved += n;
         }
+        finishUpdate(ds, st, t0, moved, info);
+    });
+}
+
+int ptr_scene_set_mesh_vertices(PtrDeviceScene* scene, const PtrMeshVertices* meshes, uint32_t count, void* stream, PtrUpdateInfo* info, char* err,
+                                size_t err_cap) {
+    const char* who = "ptr_scene_set_mesh_vertices";
+    if (!scene) return nullArgument(who, err, err_cap);
+    if (!scene->dynamic || !(scene->dynamic->flags & PTR_DYNAMIC_DEFORMABLE)) {
+        return refuse(err, err_cap, std::string(who) + ": the scene is not deformable (upload it with ptr_scene_upload_dynamic_ex and PTR_DYNAMIC_DEFORMABLE)");
+    }
+    if (!meshes) return refuse(err, err_cap, std::string(who) + ": null mesh list");
+    if (count == 0u) return refuse(err, err_cap, std::string(who) + ": count is 0");
+    DynamicScene& dyn = *scene->dynamic;
+    const uint32_t meshCount = static_cast<uint32_t>(dyn.meshTriOffsets.size()) - 1u;
+    // where the arrays of every named mesh go in the staging buffer, in floats (a mesh without triangles stages nothing)
+    struct Staged {
+        size_t positions = 0, normals = 0, tangents = 0;
+        bool used = false, hasTangents = false;
+    };
+    std::vector<Staged> staged(count);
+    std::vector<DynMeshRow> rows(count);
+    size_t floats = 0;
+    try {
+        std::vector<uint8_t> named(meshCount, 0);
+        for (uint32_t i = 0; i < count; ++i) {
+            const PtrMeshVertices& mv = meshes[i];
+            const std::string mesh = "mesh " + std::to_string(mv.meshIndex);
+            if (mv.meshIndex >= meshCount) {
+                return refuse(err, err_cap, std::string(who) + ": mesh index " + std::to_string(mv.meshIndex) + " out of range (the scene has " +
+                                                std::to_string(meshCount) + " meshes)");
+            }
+            if (named[mv.meshIndex]++) return refuse(err, err_cap, std::string(who) + ": mesh index " + std::to_string(mv.meshIndex) + " named twice");
+            rows[i] = dyn.meshRows[mv.meshIndex];
+            if (dyn.meshTriOffsets[mv.meshIndex + 1u] == dyn.meshTriOffsets[mv.meshIndex]) continue;   // no triangles: nothing to change
+            if (mv.vertexCount != dyn.meshVertexCount[mv.meshIndex]) {
+                return refuse(err, err_cap, std::string(who) + ": " + mesh + " was uploaded with " + std::to_string(dyn.meshVertexCount[mv.meshIndex]) +
+                                                " vertices, not vertexCount " + std::to_string(mv.vertexCount));
+            }
+            if (!mv.positions) return refuse(err, err_cap, std::string(who) + ": " + mesh + " has null positions");
+            if (!mv.normals) return refuse(err, err_cap, std::string(who) + ": " + mesh + " has null normals");
+            if (mv.tangents && !dyn.meshTangentsGiven[mv.meshIndex]) {
+                return refuse(err, err_cap, std::string(who) + ": " + mesh + " was uploaded without tangents and is given some");
+            }
+            if (!mv.tangents && dyn.meshTangentsGiven[mv.meshIndex]) {
+                return refuse(err, err_cap, std::string(who) + ": " + mesh + " was uploaded with tangents and is given none");
+            }
+            Staged& s = staged[i];
+            s.used = true;
+            s.hasTangents = dyn.meshHasTangents[mv.meshIndex] != 0;   // (an untextured scene keeps no tangents: they are checked and dropped)
+            s.positions = floats, floats += static_cast<size_t>(mv.vertexCount) * 3u;
+            s.normals = floats, floats += static_cast<size_t>(mv.vertexCount) * 3u;
+            if (s.hasTangents) s.tangents = floats, floats += static_cast<size_t>(mv.vertexCount) * 4u;
+        }
+        // staging: every array into the scene's pinned buffer, each component looked at on the way
+        HIP_CHECK(hipSetDevice(scene->device));
+        float* pinned = static_cast<float*>(dyn.pinnedFor(std::max<size_t>(floats, 4u) * sizeof(float)));
+        auto stage = [&](const float* src, size_t n, float* dst) {
+            bool finite = true;
+            for (size_t k = 0; k < n; ++k) {
+                finite = finite && std::isfinite(src[k]);
+                dst[k] = src[k];
+            }
+            return finite;
+        };
+        for (uint32_t i = 0; i < count; ++i) {
+            const PtrMeshVertices& mv = meshes[i];
+            const Staged& s = staged[i];
+            if (!s.used) continue;
+            const size_t n = mv.vertexCount;
+            const char* bad = nullptr;
+            if (!stage(mv.positions, n * 3u, pinned + s.positions)) bad = "position";
+            else if (!stage(mv.normals, n * 3u, pinned + s.normals)) bad = "normal";
+            else if (mv.tangents) {
+                std::vector<float> dropped;
+                if (!s.hasTangents) dropped.resize(n * 4u);
+                if (!stage(mv.tangents, n * 4u, s.hasTangents ? pinned + s.tangents : dropped.data())) bad = "tangent";
+            }
+            if (bad) return refuse(err, err_cap, std::string(who) + ": mesh " + std::to_string(mv.meshIndex) + " has a non-finite " + bad + " component");
+        }
+    }
+    PTR_CATCH_ALL(err, err_cap)
+
+    return deviceCall(who, scene, true, err, err_cap, [&] {
+        const auto t0 = std::chrono::steady_clock::now();
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        PtrDeviceScene& ds = *scene;
+        dyn.staging.ensure((floats + 3u) / 4u);
+        const float* dStaged = reinterpret_cast<const float*>(dyn.staging.ptr);
+        if (floats) HIP_CHECK(hipMemcpyAsync(dyn.staging.ptr, dyn.pinned, floats * sizeof(float), hipMemcpyHostToDevice, st));
+        dyn.meshTable.ensure(static_cast<size_t>(count) * kDynMeshVec4);
+        HIP_CHECK(hipMemcpyAsync(dyn.meshTable.ptr, rows.data(), rows.size() * sizeof(DynMeshRow), hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipEventRecord(dyn.events[0], st));
+        const DynBakeArrays arrays = bakeArrays(ds);
+        uint64_t moved = 0;
+        for (uint32_t i = 0; i < count; ++i) {
+            const Staged& s = staged[i];
+            if (!s.used) continue;
+            const uint32_t m = meshes[i].meshIndex;
+            const uint32_t first = dyn.meshTriOffsets[m], n = dyn.meshTriOffsets[m + 1u] - first;
+            const DynVertexArrays v{dStaged + s.positions, dStaged + s.normals, s.hasTangents ? dStaged + s.tangents : nullptr};
+            launchDynGatherCorners(dyn.objPos.ptr, dyn.objNrm.ptr, dyn.textured ? dyn.objTan.ptr : nullptr, v, dyn.meshTris.ptr + first,
+                                   dyn.meshCorners.ptr + static_cast<size_t>(first) * 3u, n, st);
+            launchDynBake(arrays, dyn.meshTable.ptr, i, dyn.meshTris.ptr + first, n, st);
+            moved += n;
+        }
+        finishUpdate(ds, st, t0, moved, info);
+    });
+}
+
+int ptr_scene_set_spheres(PtrDeviceScene* scene, const PtrSphereUpdate* spheres, uint32_t count, void* stream, PtrUpdateInfo* info, char* err,
+                          size_t err_cap) {
+    return setPrimitives("ptr_scene_set_spheres", 0u, scene, spheres, count, stream, info, err, err_cap);
+}
+
+int ptr_scene_set_rects(PtrDeviceScene* scene, const PtrRectUpdate* rects, uint32_t count, void* stream, PtrUpdateInfo* info, char* err, size_t err_cap) {
+    return setPrimitives("ptr_scene_set_rects", 1u, scene, rects, count, stream, info, err, err_cap);
+}
+
+uint32_t ptr_scene_dynamic_flags(const PtrDeviceScene* scene) { return scene && scene->dynamic ? scene->dynamic->flags : 0u; }
+
+int ptr_debug_dynamic_update_rows(const PtrSceneDesc* scene, uint32_t kind, const void* update, void* out, uint64_t cap_bytes, uint64_t* rows_out,
+                                  char* err, size_t err_cap) {
+    const char* who = "ptr_debug_dynamic_update_rows";
+    if (!scene || !update || !rows_out) return nullArgument(who, err, err_cap);
+    if (kind > 1u) return refuse(err, err_cap, std::string(who) + ": no such kind");
+    try {
+        ptr::PreparedGeometry pg;
+        ptr::DynamicTables t;
+        t.flags = PTR_DYNAMIC_DEFORMABLE | PTR_DYNAMIC_PRIMITIVES;
+        prepareGeometry(*scene, pg, &t);
+        std::vector<float> lights;
+        std::vector<int32_t> lightIndexByRect;
+        uint32_t lightCount = 0;
+        bool haveTriangles = true;
+        buildRectLights(*scene, pg.geo, lights, lightIndexByRect, lightCount, haveTriangles);
+        PrimitiveRecords prims;
+        fillPrimitiveRecords(*scene, pg.geo, t, lightIndexByRect, prims);
+        ScatterRows rows;
+        const std::string problem = kind == 0u ? sphereRows(prims, *static_cast<const PtrSphereUpdate*>(update), rows)
+                                               : rectRows(prims, *static_cast<const PtrRectUpdate*>(update), rows);
+        if (!problem.empty()) return refuse(err, err_cap, std::string(who) + ": " + problem);
+        const uint64_t n = rows.dest.size();
+        *rows_out = n;
+        if (!out) return 0;
+        if (cap_bytes < n * 20u) return refuse(err, err_cap, std::string(who) + ": the buffer is too small");
+        std::memcpy(out, rows.rows.data(), n * 16u);
+        std::memcpy(static_cast<char*>(out) + n * 16u, rows.dest.data(), n * 4u);
+        return 0;
+    }
+    PTR_CATCH_ALL(err, err_cap)
+}
+
+}  // extern "C"
+
+namespace {
+
+// What every update call ends with, after its own kernels (which ran between events 0 and 1 once this has recorded event 1): the refit of
+// the float boxes level by level, the grid from the refitted root box, the requantisation and the wide copy; the world bounds the
+// background cull reads; the figures of PtrUpdateInfo.
+void finishUpdate(PtrDeviceScene& ds, hipStream_t st, std::chrono::steady_clock::time_point t0, uint64_t moved, PtrUpdateInfo* info) {
+    DynamicScene& dyn = *ds.dynamic;
+    SceneView& v = ds.view;
+    {
         HIP_CHECK(hipEventRecord(dyn.events[1], st));
         float4* boxes = floatBoxes(ds);
         const uint32_t levels = static_cast<uint32_t>(dyn.levelOffsets.size()) - 1u;
@@ -185,8 +405,144 @@ int ptr_scene_set_mesh_transforms(PtrDeviceScene* scene, const PtrMeshTransform*
             info->cellOverExtent = dyn.meanPrimExtent > 0.0f ? maxCell / dyn.meanPrimExtent : 0.0f;
             info->totalSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         }
+    }
+}
+
+bool allFinite(const float* p, int n) {
+    for (int i = 0; i < n; ++i) {
+        if (!std::isfinite(p[i])) return false;
+    }
+    return true;
+}
+
+void putRow(ScatterRows& out, uint32_t array, size_t row, const float* src) {
+    out.rows.insert(out.rows.end(), src, src + 4);
+    out.dest.push_back((array << kScatterArrayShift) | static_cast<uint32_t>(row));
+}
+
+void putBounds(ScatterRows& out, uint32_t array, size_t slot, const ptr::BuildPrim& p) {
+    const float lo[4] = {p.lo[0], p.lo[1], p.lo[2], 0.0f}, hi[4] = {p.hi[0], p.hi[1], p.hi[2], 0.0f};
+    putRow(out, array, slot * 2u, lo);
+    putRow(out, array, slot * 2u + 1u, hi);
+}
+
+std::string sphereRows(PrimitiveRecords& prims, const PtrSphereUpdate& u, ScatterRows& out) {
+    const std::string name = "sphere " + std::to_string(u.sphereIndex);
+    if (u.sphereIndex >= prims.spheres.size()) {
+        return "sphere index " + std::to_string(u.sphereIndex) + " out of range (the scene has " + std::to_string(prims.spheres.size()) + " spheres)";
+    }
+    if (!allFinite(u.centerRadius, 4)) return name + " has a non-finite entry";
+    PtrSphere s = prims.spheres[u.sphereIndex];
+    std::memcpy(s.centerRadius, u.centerRadius, 16);
+    float row[4];
+    ptr::BuildPrim prim{};
+    ptr::WriteSphere(s, row, prim);
+    const size_t slot = prims.sphereLeaf[u.sphereIndex];
+    putRow(out, PTR_SCATTER_SPHERES, slot, row);
+    putBounds(out, PTR_SCATTER_SPHERE_BOUNDS, slot, prim);
+    prims.spheres[u.sphereIndex] = s;
+    return "";
+}
+
+std::string rectRows(PrimitiveRecords& prims, const PtrRectUpdate& u, ScatterRows& out) {
+    const std::string name = "rectangle " + std::to_string(u.rectIndex);
+    if (u.rectIndex >= prims.rects.size()) {
+        return "rectangle index " + std::to_string(u.rectIndex) + " out of range (the scene has " + std::to_string(prims.rects.size()) + " rectangles)";
+    }
+    if (!allFinite(u.corner, 4) || !allFinite(u.edgeU, 4) || !allFinite(u.edgeV, 4) || !allFinite(u.normalAndPlane, 4)) return name + " has a non-finite entry";
+    const ptr::float3 eu{u.edgeU[0], u.edgeU[1], u.edgeU[2]}, ev{u.edgeV[0], u.edgeV[1], u.edgeV[2]};
+    const ptr::float3 n{u.normalAndPlane[0], u.normalAndPlane[1], u.normalAndPlane[2]};
+    if (!(ptr::length(ptr::cross(eu, ev)) > 0.0f)) return name + " has cross(edgeU, edgeV) of length zero";
+    if (!(ptr::length(n) > 0.0f)) return name + " has a normal of length zero";
+    const uint32_t i = u.rectIndex;
+    PtrRect r = prims.rects[i];
+    std::memcpy(r.corner, u.corner, 16);
+    std::memcpy(r.edgeU, u.edgeU, 16);
+    std::memcpy(r.edgeV, u.edgeV, 16);
+    std::memcpy(r.normalAndPlane, u.normalAndPlane, 16);
+    float tri[2][12], nrm[2][12];
+    ptr::BuildPrim half[2];
+    ptr::WriteRectTriangles(r, i, prims.rectShadeKey[i], tri, nrm, half);
+    const uint32_t slots[2] = {prims.rectTriLeaf[static_cast<size_t>(i) * 2u], prims.rectTriLeaf[static_cast<size_t>(i) * 2u + 1u]};
+    for (int h = 0; h < 2; ++h) {
+        if (slots[h] == 0xFFFFFFFFu) continue;   // (a half the geometry does not hold has no rows)
+        for (size_t c = 0; c < 3; ++c) {
+            putRow(out, PTR_SCATTER_TRIS, static_cast<size_t>(slots[h]) * 3u + c, &tri[h][c * 4]);
+            putRow(out, PTR_SCATTER_TRI_NORMALS, static_cast<size_t>(slots[h]) * 3u + c, &nrm[h][c * 4]);
+        }
+        putBounds(out, PTR_SCATTER_TRI_BOUNDS, slots[h], half[h]);
+    }
+    float row[20];
+    ptr::WriteRectRow(r, row);
+    for (size_t q = 0; q < 5; ++q) putRow(out, PTR_SCATTER_RECTS, static_cast<size_t>(i) * 5u + q, &row[q * 4]);
+    const int32_t light = prims.lightIndexByRect[i];
+    if (light >= 0) {
+        const bool haveTris = slots[0] != 0xFFFFFFFFu && slots[1] != 0xFFFFFFFFu;
+        float lrow[ptr::kRectLightFloats];
+        ptr::WriteRectLightRow(r, i, &prims.rectEmission[static_cast<size_t>(i) * 3u], haveTris ? tri[0] : nullptr, haveTris ? tri[1] : nullptr, lrow);
+        for (size_t q = 0; q < kRectLightVec4; ++q) putRow(out, PTR_SCATTER_RECT_LIGHTS, static_cast<size_t>(light) * kRectLightVec4 + q, &lrow[q * 4]);
+    }
+    prims.rects[i] = r;
+    return "";
+}
+
+// ptr_scene_set_spheres (kind 0) and ptr_scene_set_rects (kind 1): the rows on the host, one copy, one scatter, the refit
+int setPrimitives(const char* who, uint32_t kind, PtrDeviceScene* scene, const void* list, uint32_t count, void* stream, PtrUpdateInfo* info, char* err,
+                  size_t err_cap) {
+    if (!scene) return nullArgument(who, err, err_cap);
+    if (!scene->dynamic || !(scene->dynamic->flags & PTR_DYNAMIC_PRIMITIVES)) {
+        return refuse(err, err_cap, std::string(who) + ": the scene does not keep its primitives (upload it with ptr_scene_upload_dynamic_ex and PTR_DYNAMIC_PRIMITIVES)");
+    }
+    if (!list) return refuse(err, err_cap, std::string(who) + ": null list");
+    if (count == 0u) return refuse(err, err_cap, std::string(who) + ": count is 0");
+    DynamicScene& dyn = *scene->dynamic;
+    ScatterRows rows;
+    PrimitiveRecords next;
+    try {
+        next = dyn.prims;   // the records change only when the whole call is accepted
+        std::vector<uint8_t> named(kind == 0u ? next.spheres.size() : next.rects.size(), 0);
+        for (uint32_t i = 0; i < count; ++i) {
+            const uint32_t index = kind == 0u ? static_cast<const PtrSphereUpdate*>(list)[i].sphereIndex : static_cast<const PtrRectUpdate*>(list)[i].rectIndex;
+            if (index < named.size() && named[index]++) {
+                return refuse(err, err_cap, std::string(who) + ": " + (kind == 0u ? "sphere" : "rectangle") + " index " + std::to_string(index) + " named twice");
+            }
+            const std::string problem = kind == 0u ? sphereRows(next, static_cast<const PtrSphereUpdate*>(list)[i], rows)
+                                                   : rectRows(next, static_cast<const PtrRectUpdate*>(list)[i], rows);
+            if (!problem.empty()) return refuse(err, err_cap, std::string(who) + ": " + problem);
+        }
+    }
+    PTR_CATCH_ALL(err, err_cap)
+
+    return deviceCall(who, scene, true, err, err_cap, [&] {
+        const auto t0 = std::chrono::steady_clock::now();
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        PtrDeviceScene& ds = *scene;
+        const size_t n = rows.dest.size();
+        char* pinned = static_cast<char*>(dyn.pinnedFor(std::max<size_t>(n, 1u) * 20u));
+        std::memcpy(pinned, rows.rows.data(), n * 16u);
+        std::memcpy(pinned + n * 16u, rows.dest.data(), n * 4u);
+        dyn.staging.ensure(n + (n + 3u) / 4u);
+        HIP_CHECK(hipMemcpyAsync(dyn.staging.ptr, pinned, n * 20u, hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipEventRecord(dyn.events[0], st));
+        const size_t tris = dyn.triCount, spheres = dyn.sphereCount;
+        DynScatterTargets t{};
+        auto target = [&](uint32_t array, float4* base, size_t rowCount) { t.base[array] = base, t.rows[array] = static_cast<uint32_t>(rowCount); };
+        target(PTR_SCATTER_TRIS, ds.tris.ptr, tris * 3u);
+        target(PTR_SCATTER_TRI_NORMALS, ds.triNormals.ptr, tris * 3u);
+        target(PTR_SCATTER_TRI_BOUNDS, dyn.triBounds.ptr, tris * 2u);
+        target(PTR_SCATTER_SPHERES, ds.spheres.ptr, spheres);
+        target(PTR_SCATTER_SPHERE_BOUNDS, dyn.sphereBounds.ptr, spheres * 2u);
+        target(PTR_SCATTER_RECTS, ds.rects.ptr, dyn.prims.rects.size() * 5u);
+        target(PTR_SCATTER_RECT_LIGHTS, ds.rectLights.ptr, static_cast<size_t>(ds.view.rectLightCount) * kRectLightVec4);
+        launchDynScatterRows(t, dyn.staging.ptr, reinterpret_cast<const uint32_t*>(dyn.staging.ptr + n), static_cast<uint32_t>(n), st);
+        dyn.prims = std::move(next);
+        finishUpdate(ds, st, t0, kind == 1u ? static_cast<uint64_t>(count) * 2u : 0u, info);
     });
 }
+
+}  // namespace
+
+extern "C" {
 
 int ptr_debug_scene_arrays(PtrDeviceScene* scene, uint32_t which, void* out, uint64_t cap_bytes, uint64_t* size_out) {
     if (!scene || !size_out) return 1;
@@ -209,6 +565,12 @@ int ptr_debug_scene_arrays(PtrDeviceScene* scene, uint32_t which, void* out, uin
         case PTR_SCENE_ARRAY_QNODES: src = ds.qnodes.ptr, bytes = ds.view.useQuantized ? nodes * 32u : 0u; break;
         case PTR_SCENE_ARRAY_WNODES: src = ds.wnodes.ptr, bytes = ds.view.useWide ? ds.view.wideBytes : 0u; break;
         case PTR_SCENE_ARRAY_GRID: bytes = 24u; break;
+        case PTR_SCENE_ARRAY_RECTS: src = ds.rects.ptr, bytes = static_cast<uint64_t>(ds.view.rectCount) * 80u; break;
+        case PTR_SCENE_ARRAY_RECT_LIGHTS: src = ds.rectLights.ptr, bytes = static_cast<uint64_t>(ds.view.rectLightCount) * kRectLightVec4 * 16u; break;
+        case PTR_SCENE_ARRAY_SPHERES: src = ds.spheres.ptr, bytes = spheres * 16u; break;
+        case PTR_SCENE_ARRAY_OBJ_POS: src = dyn ? dyn->objPos.ptr : nullptr, bytes = dyn ? tris * 48u : 0u; break;
+        case PTR_SCENE_ARRAY_OBJ_NRM: src = dyn ? dyn->objNrm.ptr : nullptr, bytes = dyn ? tris * 48u : 0u; break;
+        case PTR_SCENE_ARRAY_OBJ_TAN: src = dyn ? dyn->objTan.ptr : nullptr, bytes = dyn && dyn->textured ? tris * 48u : 0u; break;
         default: return 1;
     }
     *size_out = bytes;
@@ -229,9 +591,11 @@ int ptr_debug_dynamic_tables(const PtrSceneDesc* scene, uint32_t which, void* ou
     try {
         ptr::PreparedGeometry pg;
         ptr::DynamicTables t;
+        t.flags = PTR_DYNAMIC_DEFORMABLE | PTR_DYNAMIC_PRIMITIVES;
         prepareGeometry(*scene, pg, &t);
         const ptr::FlatBvh& bvh = pg.geo.bvh;
         std::vector<uint32_t> words;
+        std::vector<float> lights;
         const void* src = nullptr;
         uint64_t bytes = 0;
         auto take = [&](const void* p, size_t n) { src = p, bytes = n; };
@@ -270,6 +634,21 @@ int ptr_debug_dynamic_tables(const PtrSceneDesc* scene, uint32_t which, void* ou
                          pg.geo.sphereCount, bvh.maxDepth, bvh.rootRef, bvh.oversizeRef, pg.wideDepth};
                 take(words.data(), words.size() * 4u);
                 break;
+            case PTR_DYNAMIC_TABLE_MESH_CORNERS: take(t.meshCorners.data(), t.meshCorners.size() * 4u); break;
+            case PTR_DYNAMIC_TABLE_RECT_TRI_LEAF: take(pg.geo.rectTriLeaf.data(), pg.geo.rectTriLeaf.size() * 4u); break;
+            case PTR_DYNAMIC_TABLE_SPHERE_LEAF: take(t.sphereLeaf.data(), t.sphereLeaf.size() * 4u); break;
+            case PTR_DYNAMIC_TABLE_TRIS: take(pg.geo.triData.data(), pg.geo.triData.size() * 4u); break;
+            case PTR_DYNAMIC_TABLE_TRI_NORMALS: take(pg.geo.triNormals.data(), pg.geo.triNormals.size() * 4u); break;
+            case PTR_DYNAMIC_TABLE_SPHERES: take(pg.geo.sphereData.data(), pg.geo.sphereData.size() * 4u); break;
+            case PTR_DYNAMIC_TABLE_RECTS: take(scene->rects, static_cast<size_t>(scene->rectCount) * sizeof(PtrRect)); break;
+            case PTR_DYNAMIC_TABLE_RECT_LIGHTS: {
+                std::vector<int32_t> lightIndexByRect;
+                uint32_t lightCount = 0;
+                bool haveTriangles = true;
+                buildRectLights(*scene, pg.geo, lights, lightIndexByRect, lightCount, haveTriangles);
+                take(lights.data(), lights.size() * 4u);
+                break;
+            }
             default: return refuse(err, err_cap, "ptr_debug_dynamic_tables: no such table");
         }
         *size_out = bytes;

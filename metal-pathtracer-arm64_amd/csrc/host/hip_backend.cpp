@@ -24,6 +24,7 @@
 #include "env_importance_sampler.h"
 #include "geometry_cache.h"
 #include "knobs.h"
+#include "ptr_deform.h"
 #include "ptr_dynamic.h"
 #include "scene_geometry.h"
 #include "vecmath.h"
@@ -34,13 +35,6 @@ using namespace ptrhost;
 namespace {
 
 using ptr::float3;
-
-void put4(std::vector<float>& dst, const float3& v, float w) {
-    dst.push_back(v.x);
-    dst.push_back(v.y);
-    dst.push_back(v.z);
-    dst.push_back(w);
-}
 
 // per-group scalars: [0] unused, [1] k_extend work head, [2] k_connect work head, [3] pad,
 //                    [4..19] ring of live-slot counters (one per iteration, written by k_extend at the end of a frame)
@@ -139,7 +133,31 @@ void prepareGeometry(const PtrSceneDesc& desc, ptr::PreparedGeometry& pg, ptr::D
     }
 }
 
-void prepareScene(const PtrSceneDesc& desc, PreparedScene& ps, const char* cachePath, bool dynamic) {
+// rectangle lights: DiffuseLight rectangles with non-zero emission (:2484-2522)
+void buildRectLights(const PtrSceneDesc& desc, const ptr::SceneGeometry& geo, std::vector<float>& lights, std::vector<int32_t>& lightIndexByRect,
+                     uint32_t& lightCount, bool& lightsHaveTriangles) {
+    lightIndexByRect.assign(desc.rectCount, -1);
+    if (desc.rectCount == 0 || desc.materialCount == 0) return;
+    for (uint32_t i = 0; i < desc.rectCount; ++i) {
+        const PtrRect& r = desc.rects[i];
+        const PtrMaterial& m = desc.materials[std::min(r.materialTwoSided[0], desc.materialCount - 1u)];
+        if (static_cast<uint32_t>(m.typeEta[0]) != PTR_MAT_DIFFUSE_LIGHT) continue;
+        const ptr::float3 e{m.emission[0], m.emission[1], m.emission[2]};
+        if (!(ptr::dot(e, e) > 0.0f)) continue;
+        // the light's own two triangles exactly as the traversal reads them (leaf-order records); normal.w = 1 when they are present
+        const uint32_t t0 = geo.rectTriLeaf[static_cast<size_t>(i) * 2u], t1 = geo.rectTriLeaf[static_cast<size_t>(i) * 2u + 1u];
+        const bool haveTris = t0 != 0xFFFFFFFFu && t1 != 0xFFFFFFFFu;
+        lightsHaveTriangles = lightsHaveTriangles && haveTris;
+        static_assert(ptr::kRectLightFloats == kRectLightVec4 * 4u, "light row layout");
+        float row[ptr::kRectLightFloats];
+        ptr::WriteRectLightRow(r, i, m.emission, haveTris ? &geo.triData[static_cast<size_t>(t0) * 12u] : nullptr,
+                               haveTris ? &geo.triData[static_cast<size_t>(t1) * 12u] : nullptr, row);
+        lights.insert(lights.end(), row, row + ptr::kRectLightFloats);
+        lightIndexByRect[i] = static_cast<int32_t>(lightCount++);
+    }
+}
+
+void prepareScene(const PtrSceneDesc& desc, PreparedScene& ps, const char* cachePath, bool dynamic, uint32_t dynamicFlags) {
     using ptr::float3;
     const auto t0 = std::chrono::steady_clock::now();
     if (cachePath && *cachePath) {
@@ -148,6 +166,7 @@ void prepareScene(const PtrSceneDesc& desc, PreparedScene& ps, const char* cache
         ps.geometryFromCache = true;
     } else {
         ps.dynamic = dynamic;
+        ps.dyn.flags = dynamic ? dynamicFlags : 0u;
         prepareGeometry(desc, ps.pg, dynamic ? &ps.dyn : nullptr);
     }
     ps.geometrySeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -161,37 +180,7 @@ void prepareScene(const PtrSceneDesc& desc, PreparedScene& ps, const char* cache
         if (static_cast<uint32_t>(m.typeEta[0]) == PTR_MAT_SUBSURFACE && m.sssParams[1] >= 0.5f) ps.hasRandomWalkMaterial = true;
     }
 
-    // rectangle lights: DiffuseLight rectangles with non-zero emission (:2484-2522)
-    ps.lightIndexByRect.assign(desc.rectCount, -1);
-    if (desc.rectCount > 0 && desc.materialCount > 0) {
-        for (uint32_t i = 0; i < desc.rectCount; ++i) {
-            const PtrRect& r = desc.rects[i];
-            const PtrMaterial& m = desc.materials[std::min(r.materialTwoSided[0], desc.materialCount - 1u)];
-            if (static_cast<uint32_t>(m.typeEta[0]) != PTR_MAT_DIFFUSE_LIGHT) continue;
-            const float3 e{m.emission[0], m.emission[1], m.emission[2]};
-            if (!(ptr::dot(e, e) > 0.0f)) continue;
-            const float3 c{r.corner[0], r.corner[1], r.corner[2]}, eu{r.edgeU[0], r.edgeU[1], r.edgeU[2]},
-                ev{r.edgeV[0], r.edgeV[1], r.edgeV[2]};
-            const float3 n = ptr::normalize(float3{r.normalAndPlane[0], r.normalAndPlane[1], r.normalAndPlane[2]});
-            put4(ps.lights, c, ptr::length(ptr::cross(eu, ev)));
-            put4(ps.lights, eu, r.materialTwoSided[1] != 0u ? 1.0f : 0.0f);
-            put4(ps.lights, ev, bitsToFloat(i));
-            // rows 5..10: the light's own two triangles exactly as the traversal reads them (leaf-order records), for k_shade's
-            // self-occlusion test of a light sample; normal.w = 1 when they are present
-            const uint32_t t0 = geoRef.rectTriLeaf[static_cast<size_t>(i) * 2u], t1 = geoRef.rectTriLeaf[static_cast<size_t>(i) * 2u + 1u];
-            const bool haveTris = t0 != 0xFFFFFFFFu && t1 != 0xFFFFFFFFu;
-            put4(ps.lights, n, haveTris ? 1.0f : 0.0f);
-            ps.lightsHaveTriangles = ps.lightsHaveTriangles && haveTris;
-            put4(ps.lights, e, 0.0f);
-            for (uint32_t t : {t0, t1}) {
-                for (int row = 0; row < 3; ++row) {
-                    const float* src = haveTris ? &geoRef.triData[static_cast<size_t>(t) * 12u + static_cast<size_t>(row) * 4u] : nullptr;
-                    for (int c = 0; c < 4; ++c) ps.lights.push_back(src ? src[c] : 0.0f);
-                }
-            }
-            ps.lightIndexByRect[i] = static_cast<int32_t>(ps.lightCount++);
-        }
-    }
+    buildRectLights(desc, geoRef, ps.lights, ps.lightIndexByRect, ps.lightCount, ps.lightsHaveTriangles);
     if (desc.envRgba && desc.envWidth > 0 && desc.envHeight > 0) {
         ps.hasEnvDist = ptr::BuildEnvImportanceDistribution(desc.envRgba, desc.envWidth, desc.envHeight, &ps.envDist);
     }
@@ -319,7 +308,7 @@ void uploadScene(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceSce
 
     ds.worldBounds = ptr::boundsOfPrimitives(geo.triData.data(), geo.triData.size() / 12u, geo.sphereData.data(), geo.sphereData.size() / 4u);
 
-    if (ps.dynamic) uploadDynamicTables(ps, ds);   // dynamic.cpp
+    if (ps.dynamic) uploadDynamicTables(desc, ps, ds);   // dynamic.cpp
 
     ds.info[0] = bvh.nodeCount;
     ds.info[1] = bvh.leafCount;
@@ -373,7 +362,7 @@ namespace {
 
 // ptr_scene_upload and, with the path of a geometry cache file, ptr_scene_upload_prepared
 int uploadTo(const char* who, const PtrSceneDesc* scene, const char* cachePath, int device, PtrDeviceScene** outScene, char* err, size_t cap,
-             bool dynamic = false) {
+             bool dynamic = false, uint32_t dynamicFlags = 0) {
     if (!scene || !outScene) return nullArgument(who, err, cap);
     if (ptr_device_count() <= device || device < 0) {
         setErr(err, cap, std::string(who) + ": no such HIP device (the HIP path has no CPU fallback)");
@@ -383,7 +372,7 @@ int uploadTo(const char* who, const PtrSceneDesc* scene, const char* cachePath, 
         auto ds = std::make_unique<PtrDeviceScene>();
         ds->device = device;
         PreparedScene ps;
-        prepareScene(*scene, ps, cachePath, dynamic);
+        prepareScene(*scene, ps, cachePath, dynamic, dynamicFlags);
         uploadScene(*scene, ps, *ds);
         *outScene = ds.release();
         return 0;
@@ -1228,6 +1217,13 @@ int ptr_scene_upload(const PtrSceneDesc* scene, int device, PtrDeviceScene** out
 int ptr_scene_upload_dynamic(const PtrSceneDesc* scene, int device, PtrDeviceScene** out_scene, char* err, size_t err_cap) {
     if (scene && out_scene && ptr_device_count() < 1) return noDevice("ptr_scene_upload_dynamic", err, err_cap);
     return uploadTo("ptr_scene_upload_dynamic", scene, nullptr, device, out_scene, err, err_cap, true);
+}
+
+int ptr_scene_upload_dynamic_ex(const PtrSceneDesc* scene, int device, uint32_t flags, PtrDeviceScene** out_scene, char* err, size_t err_cap) {
+    const char* who = "ptr_scene_upload_dynamic_ex";
+    if (flags & ~static_cast<uint32_t>(PTR_DYNAMIC_DEFORMABLE | PTR_DYNAMIC_PRIMITIVES)) return refuse(err, err_cap, std::string(who) + ": unknown flag");
+    if (scene && out_scene && ptr_device_count() < 1) return noDevice(who, err, err_cap);
+    return uploadTo(who, scene, nullptr, device, out_scene, err, err_cap, true, flags);
 }
 
 void ptr_scene_release(PtrDeviceScene* scene) {

@@ -137,6 +137,54 @@ void ComputeMeshBake(const float localToWorld[16], MeshBake& out) {
     out.detSign = det3 < 0.0f ? -1.0f : 1.0f;
 }
 
+void WriteRectTriangles(const PtrRect& r, uint32_t rectIndex, uint32_t shadeKey, float tri[2][12], float nrm[2][12], BuildPrim prim[2]) {
+    const float3 c{r.corner[0], r.corner[1], r.corner[2]}, eu{r.edgeU[0], r.edgeU[1], r.edgeU[2]}, ev{r.edgeV[0], r.edgeV[1], r.edgeV[2]};
+    const float3 n = normalize(float3{r.normalAndPlane[0], r.normalAndPlane[1], r.normalAndPlane[2]});
+    const float3 p[4] = {c, c + eu, c + ev, (c + eu) + ev};
+    const bool flip = dot(normalize(cross(eu, ev)), n) < 0.0f;
+    const int order[2][6] = {{0, 1, 2, 2, 1, 3}, {0, 2, 1, 1, 2, 3}};
+    const int* o = order[flip ? 1 : 0];
+    for (int half = 0; half < 2; ++half) {
+        prim[half] = BuildPrim{};
+        storeTri(tri[half], nrm[half], prim[half], p[o[half * 3]], p[o[half * 3 + 1]], p[o[half * 3 + 2]], n, n, n, r.materialTwoSided[0], shadeKey, 2u,
+                 rectIndex, rectIndex * 2u + static_cast<uint32_t>(half));
+    }
+}
+
+void WriteRectRow(const PtrRect& r, float row[20]) {
+    static_assert(sizeof(PtrRect) == 80, "a rects row is the description's record");
+    std::memcpy(row, &r, sizeof(PtrRect));
+}
+
+void WriteRectLightRow(const PtrRect& r, uint32_t rectIndex, const float emission[3], const float* tri0, const float* tri1, float row[kRectLightFloats]) {
+    const float3 eu{r.edgeU[0], r.edgeU[1], r.edgeU[2]}, ev{r.edgeV[0], r.edgeV[1], r.edgeV[2]};
+    const float3 n = normalize(float3{r.normalAndPlane[0], r.normalAndPlane[1], r.normalAndPlane[2]});
+    const bool haveTris = tri0 && tri1;
+    auto put = [&](int at, float x, float y, float z, float w) { row[at * 4] = x, row[at * 4 + 1] = y, row[at * 4 + 2] = z, row[at * 4 + 3] = w; };
+    put(0, r.corner[0], r.corner[1], r.corner[2], length(cross(eu, ev)));
+    put(1, eu.x, eu.y, eu.z, r.materialTwoSided[1] != 0u ? 1.0f : 0.0f);
+    put(2, ev.x, ev.y, ev.z, bitsToFloat(rectIndex));
+    put(3, n.x, n.y, n.z, haveTris ? 1.0f : 0.0f);
+    put(4, emission[0], emission[1], emission[2], 0.0f);
+    // rows 5..10: the light's own two triangles exactly as the traversal reads them (leaf-order records), for k_shade's self-occlusion
+    // test of a light sample
+    for (int t = 0; t < 2; ++t) {
+        const float* src = t == 0 ? tri0 : tri1;
+        for (int i = 0; i < 12; ++i) row[20 + t * 12 + i] = haveTris ? src[i] : 0.0f;
+    }
+}
+
+void WriteSphere(const PtrSphere& s, float row[4], BuildPrim& p) {
+    std::memcpy(row, s.centerRadius, 16);
+    const float rad = std::fabs(s.centerRadius[3]);
+    for (int a = 0; a < 3; ++a) {
+        p.lo[a] = s.centerRadius[a] - rad;
+        p.hi[a] = s.centerRadius[a] + rad;
+    }
+    p.isSphere = 1;
+    padBounds(p);
+}
+
 bool BuildSceneGeometry(const PtrSceneDesc& desc, uint32_t leafMax, SceneGeometry& out, std::string& error, DynamicTables* dyn) {
     out = SceneGeometry{};
     auto t0 = std::chrono::steady_clock::now();
@@ -268,30 +316,18 @@ bool BuildSceneGeometry(const PtrSceneDesc& desc, uint32_t leafMax, SceneGeometr
     // rectangles: two triangles each, winding chosen to agree with the stored normal (:2211-2257)
     for (uint32_t ri = 0; ri < desc.rectCount; ++ri) {
         const PtrRect& r = desc.rects[ri];
-        const float3 c{r.corner[0], r.corner[1], r.corner[2]}, eu{r.edgeU[0], r.edgeU[1], r.edgeU[2]},
-            ev{r.edgeV[0], r.edgeV[1], r.edgeV[2]};
-        const float3 n = normalize(float3{r.normalAndPlane[0], r.normalAndPlane[1], r.normalAndPlane[2]});
-        const float3 p[4] = {c, c + eu, c + ev, (c + eu) + ev};
-        const bool flip = dot(normalize(cross(eu, ev)), n) < 0.0f;
-        const int order[2][6] = {{0, 1, 2, 2, 1, 3}, {0, 2, 1, 1, 2, 3}};
-        const int* o = order[flip ? 1 : 0];
-        for (int half = 0; half < 2; ++half) {
+        float tri[2][12], nrm[2][12];
+        BuildPrim half[2];
+        WriteRectTriangles(r, ri, shadeKeyOf(r.materialTwoSided[0]), tri, nrm, half);
+        for (int h = 0; h < 2; ++h) {
             const size_t k = cursor++;
-            storeTri(&triIn[k * 12], &nrmIn[k * 12], prims[k], p[o[half * 3]], p[o[half * 3 + 1]], p[o[half * 3 + 2]], n, n, n,
-                     r.materialTwoSided[0], shadeKeyOf(r.materialTwoSided[0]), 2u, ri, ri * 2u + static_cast<uint32_t>(half));
+            std::memcpy(&triIn[k * 12], tri[h], 48);
+            std::memcpy(&nrmIn[k * 12], nrm[h], 48);
+            prims[k] = half[h];
         }
     }
-    for (uint32_t si = 0; si < desc.sphereCount; ++si) {
-        const PtrSphere& s = desc.spheres[si];
-        BuildPrim& p = prims[static_cast<size_t>(triCount) + si];
-        const float rad = std::fabs(s.centerRadius[3]);
-        for (int a = 0; a < 3; ++a) {
-            p.lo[a] = s.centerRadius[a] - rad;
-            p.hi[a] = s.centerRadius[a] + rad;
-        }
-        p.isSphere = 1;
-        padBounds(p);
-    }
+    std::vector<float> sphereRows(static_cast<size_t>(desc.sphereCount) * 4u);
+    for (uint32_t si = 0; si < desc.sphereCount; ++si) WriteSphere(desc.spheres[si], &sphereRows[static_cast<size_t>(si) * 4u], prims[static_cast<size_t>(triCount) + si]);
     out.gatherSeconds = secondsSince(t0);
 
     t0 = std::chrono::steady_clock::now();
@@ -333,7 +369,10 @@ bool BuildSceneGeometry(const PtrSceneDesc& desc, uint32_t leafMax, SceneGeometr
         });
     }
     if (dyn) {
+        const uint32_t flags = dyn->flags;
         *dyn = DynamicTables{};
+        dyn->flags = flags;
+        const bool wantCorners = (flags & PTR_DYNAMIC_DEFORMABLE) != 0u, wantPrimitives = (flags & PTR_DYNAMIC_PRIMITIVES) != 0u;
         dyn->textured = textured;
         dyn->triBounds.assign(static_cast<size_t>(triCount) * 8, 0.0f);
         dyn->objPos.assign(static_cast<size_t>(triCount) * 12, 0.0f);
@@ -350,6 +389,15 @@ bool BuildSceneGeometry(const PtrSceneDesc& desc, uint32_t leafMax, SceneGeometr
         });
         dyn->meshTriOffsets.assign(static_cast<size_t>(desc.meshCount) + 1u, 0u);
         dyn->meshHasTangents.assign(desc.meshCount, 0);
+        dyn->meshBakes.assign(desc.meshCount, MeshBake{});
+        if (wantCorners) {
+            dyn->meshVertexCount.assign(desc.meshCount, 0u);
+            dyn->meshTangentsGiven.assign(desc.meshCount, 0);
+            for (uint32_t mi = 0; mi < desc.meshCount; ++mi) {
+                dyn->meshVertexCount[mi] = desc.meshes[mi].vertexCount;
+                dyn->meshTangentsGiven[mi] = desc.meshes[mi].tangents ? 1 : 0;
+            }
+        }
         size_t at = 0;
         for (uint32_t mi = 0; mi < desc.meshCount; ++mi) {
             const PtrMeshDesc& mesh = desc.meshes[mi];
@@ -358,6 +406,11 @@ bool BuildSceneGeometry(const PtrSceneDesc& desc, uint32_t leafMax, SceneGeometr
             dyn->meshHasTangents[mi] = (textured && mesh.tangents) ? 1 : 0;
             const size_t meshTris = mesh.indexCount / 3u;
             dyn->meshTris.resize(at + meshTris);
+            ComputeMeshBake(mesh.localToWorld, dyn->meshBakes[mi]);
+            if (wantCorners) {
+                dyn->meshCorners.resize((at + meshTris) * 3u);
+                std::memcpy(&dyn->meshCorners[at * 3u], mesh.indices, meshTris * 12u);
+            }
             parallelFor(meshTris, [&](size_t b, size_t e) {
                 for (size_t t = b; t < e; ++t) {
                     const uint32_t k = leafOf[at + t];
@@ -382,10 +435,16 @@ bool BuildSceneGeometry(const PtrSceneDesc& desc, uint32_t leafMax, SceneGeometr
             std::memcpy(&dyn->sphereBounds[k * 8 + 4], p.hi, 12);
         }
         BuildRefitSchedule(out.bvh, dyn->schedule, dyn->levelOffsets);
+        if (wantPrimitives) {
+            dyn->sphereLeaf.assign(desc.sphereCount, 0xFFFFFFFFu);
+            for (size_t k = 0; k < out.bvh.sphereOrder.size(); ++k) dyn->sphereLeaf[out.bvh.sphereOrder[k]] = static_cast<uint32_t>(k);
+            dyn->rectShadeKey.resize(desc.rectCount);
+            for (uint32_t ri = 0; ri < desc.rectCount; ++ri) dyn->rectShadeKey[ri] = shadeKeyOf(desc.rects[ri].materialTwoSided[0]);
+        }
     }
     for (uint32_t idx : out.bvh.sphereOrder) {
         const PtrSphere& s = desc.spheres[idx];
-        out.sphereData.insert(out.sphereData.end(), s.centerRadius, s.centerRadius + 4);
+        out.sphereData.insert(out.sphereData.end(), &sphereRows[static_cast<size_t>(idx) * 4u], &sphereRows[static_cast<size_t>(idx) * 4u] + 4);
         out.sphereInfo.push_back(idx);
         out.sphereInfo.push_back(s.materialIndex[0]);
     }

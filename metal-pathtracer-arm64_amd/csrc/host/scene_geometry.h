@@ -13,6 +13,7 @@
 
 #include "bvh_builder.h"
 #include "ptr_abi.h"
+#include "ptr_deform.h"
 
 namespace ptr {
 
@@ -30,6 +31,15 @@ struct SceneGeometry {
     double gatherSeconds = 0.0, buildSeconds = 0.0, flattenSeconds = 0.0;
 };
 
+// What the bake of one mesh derives from its localToWorld, by the functions BuildSceneGeometry itself uses: the three columns the normals
+// go through (rows of the cofactor inverse) and the sign of the 3x3 determinant.  det3 is that determinant.
+struct MeshBake {
+    float localToWorld[16];
+    float nc0[3], nc1[3], nc2[3];
+    float detSign, det3;
+};
+void ComputeMeshBake(const float localToWorld[16], MeshBake& out);
+
 // What a dynamic scene (include/ptr_dynamic.h) keeps beside the arrays above so that a mesh can be moved and the tree refitted on the
 // device.  Triangle arrays are in leaf order, like triData.
 struct DynamicTables {
@@ -44,16 +54,31 @@ struct DynamicTables {
     std::vector<uint32_t> schedule, levelOffsets;   // BuildRefitSchedule
     std::vector<uint32_t> wideSource;       // BuildWideNodes' source table (empty without four-wide nodes)
     bool textured = false;
+    // Set by the caller before BuildSceneGeometry (PTR_DYNAMIC_DEFORMABLE / PTR_DYNAMIC_PRIMITIVES of include/ptr_deform.h): which of the
+    // tables below to fill.  The rest of this struct does not depend on it.
+    uint32_t flags = 0;
+    std::vector<MeshBake> meshBakes;           // per mesh: what its localToWorld bakes to (a mesh without triangles: zeros)
+    // deformable scenes
+    std::vector<uint32_t> meshCorners;         // 3 per entry of meshTris, in its order: the vertex indices of that triangle
+    std::vector<uint32_t> meshVertexCount;     // per mesh, as the description gave it
+    std::vector<uint8_t> meshTangentsGiven;    // per mesh: the description carried tangents (kept or not)
+    // scenes whose spheres and rectangles move
+    std::vector<uint32_t> sphereLeaf;          // original sphere index -> leaf slot (the inverse of SceneGeometry::sphereInfo)
+    std::vector<uint32_t> rectShadeKey;        // per rectangle: the shade key of its material, which the meta word of its triangles carries
 };
 
-// What the bake of one mesh derives from its localToWorld, by the functions BuildSceneGeometry itself uses: the three columns the normals
-// go through (rows of the cofactor inverse) and the sign of the 3x3 determinant.  det3 is that determinant.
-struct MeshBake {
-    float localToWorld[16];
-    float nc0[3], nc1[3], nc2[3];
-    float detSign, det3;
-};
-void ComputeMeshBake(const float localToWorld[16], MeshBake& out);
+// The rows of one rectangle and of one sphere, written by the upload (BuildSceneGeometry, the light table) and by ptr_scene_set_rects /
+// ptr_scene_set_spheres alike: one statement of their arithmetic.
+// the two triangles of rectangle `rectIndex`, winding chosen to agree with the stored normal: tris / triNormals rows and padded bounds
+void WriteRectTriangles(const PtrRect& r, uint32_t rectIndex, uint32_t shadeKey, float tri[2][12], float nrm[2][12], BuildPrim prim[2]);
+// the `rects` row: the description's record as it stands (5 float4)
+void WriteRectRow(const PtrRect& r, float row[20]);
+// one `rectLights` row (kRectLightVec4 float4): corner|area, edgeU|two-sided, edgeV|rectangle index, normal|has-triangles, emission|0, and
+// the light's own two triangles as the traversal reads them (null: the geometry does not hold them)
+constexpr uint32_t kRectLightFloats = 44u;
+void WriteRectLightRow(const PtrRect& r, uint32_t rectIndex, const float emission[3], const float* tri0, const float* tri1, float row[kRectLightFloats]);
+// the `spheres` row and the sphere's padded bounds
+void WriteSphere(const PtrSphere& s, float row[4], BuildPrim& prim);
 
 // leafMax = 0 picks the default (4).  Returns false with a message on malformed input.  dyn (nullable): also fill the tables of a dynamic
 // scene (everything but wideSource, which comes with the four-wide nodes).

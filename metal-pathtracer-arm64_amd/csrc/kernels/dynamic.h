@@ -1,5 +1,6 @@
 // Launchers of the dynamic-scene kernels (dynamic.hip; include/ptr_dynamic.h): re-bake the triangles of a moved mesh, refit the float
-// child boxes level by level, requantise the binary nodes and refill the four-wide ones.
+// child boxes level by level, requantise the binary nodes and refill the four-wide ones; and, for include/ptr_deform.h, gather new vertex
+// data into the corner rows the bake reads and scatter the host-computed rows of moved spheres and rectangles.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -31,6 +32,27 @@ struct DynBakeArrays {
     float4* triUv;
     float4* triTangent;
 };
+
+// New per-vertex data of one mesh in device scratch (include/ptr_deform.h): float3 positions and normals, float4 tangents (null: the mesh
+// carries none, or the scene is untextured).  Packed as the caller gave them, so only 4 B aligned.
+struct DynVertexArrays {
+    const float* positions;
+    const float* normals;
+    const float* tangents;
+};
+// triangles list[0 .. count) of one mesh: corners[3 i ..] are the vertex indices of list[i]; writes its object-space corner rows
+void launchDynGatherCorners(float4* dObjPos, float4* dObjNrm, float4* dObjTan, const DynVertexArrays& v, const uint32_t* dList, const uint32_t* dCorners,
+                            uint32_t count, hipStream_t stream);
+
+// The arrays ptr_scene_set_spheres / ptr_scene_set_rects scatter rows into, indexed by PTR_SCATTER_*: a destination word is
+// (array << kScatterArrayShift) | row, the row counted in float4.
+constexpr uint32_t kScatterArrays = 7u, kScatterArrayShift = 28u, kScatterRowMask = (1u << kScatterArrayShift) - 1u;
+struct DynScatterTargets {
+    float4* base[kScatterArrays];
+    uint32_t rows[kScatterArrays];   // float4 in each: a destination past it is skipped
+};
+// dst[dest[i]] = rows[i], i < count
+void launchDynScatterRows(const DynScatterTargets& t, const float4* dRows, const uint32_t* dDest, uint32_t count, hipStream_t stream);
 
 // triangles list[0 .. count) through row `mesh` of the table
 void launchDynBake(const DynBakeArrays& a, const float4* dMeshTable, uint32_t mesh, const uint32_t* dList, uint32_t count, hipStream_t stream);

@@ -9,7 +9,10 @@
 //                     EARLIER launch wrote: the launch boundary is the only hand-off between workgroups.
 // k_dyn_quantise      one node per lane: both 16 B records from the float boxes through kernels/bvh_grid.h.
 // k_dyn_wide          one wide place per lane: the three box words of its source record.
-// Every access is one 16 B load or store.
+// Every access of these is one 16 B load or store.  include/ptr_deform.h adds two kernels that compute nothing:
+// k_dyn_gather_corners  one triangle of a deformed mesh per lane: its three vertices, through the corner table, to the object-space rows
+//                       k_dyn_bake reads (4 B gather loads - packed float3 is only 4 B aligned - and 16 B stores).
+// k_dyn_scatter_rows    one 16 B row of a moved sphere or rectangle per lane, computed on the host, to the array it belongs to.
 #include <hip/hip_runtime.h>
 
 #include "bvh_grid.h"
@@ -130,6 +133,45 @@ __global__ void __launch_bounds__(kBlock) k_dyn_bake(DynBakeArrays a, const floa
     }
 }
 
+// One triangle of a deformed mesh per lane: its three vertices through the corner table into the object-space corner rows k_dyn_bake
+// reads.  The vertex arrays are packed float3 (4 B aligned), so the gather loads are 4 B; every store is 16 B.  The w words of objPos
+// carry the w words of the triangle's tris row and stay.
+__global__ void __launch_bounds__(kBlock) k_dyn_gather_corners(float4* __restrict__ objPos, float4* __restrict__ objNrm, float4* __restrict__ objTan,
+                                                               DynVertexArrays v, const uint32_t* __restrict__ list,
+                                                               const uint32_t* __restrict__ corners, uint32_t count) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= count) return;
+    const size_t k = list[i];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const size_t vi = corners[static_cast<size_t>(i) * 3 + c];
+        const float* p = v.positions + vi * 3;
+        const float* n = v.normals + vi * 3;
+        const float w = objPos[k * 3 + c].w;
+        objPos[k * 3 + c] = make_float4(p[0], p[1], p[2], w);
+        objNrm[k * 3 + c] = make_float4(n[0], n[1], n[2], 0.0f);
+        if (v.tangents) {
+            const float* t = v.tangents + vi * 4;
+            objTan[k * 3 + c] = make_float4(t[0], t[1], t[2], t[3]);
+        }
+    }
+}
+
+// One 16 B row per lane: the rows of moved spheres and rectangles, computed on the host, to the arrays they belong to.
+__global__ void __launch_bounds__(kBlock) k_dyn_scatter_rows(DynScatterTargets t, const float4* __restrict__ rows, const uint32_t* __restrict__ dest,
+                                                             uint32_t count) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= count) return;
+    const uint32_t d = dest[i], array = d >> kScatterArrayShift, row = d & kScatterRowMask;
+    float4* base = nullptr;
+    uint32_t limit = 0u;
+#pragma unroll
+    for (uint32_t a = 0; a < kScatterArrays; ++a) {
+        if (array == a) base = t.base[a], limit = t.rows[a];
+    }
+    if (row < limit) base[row] = rows[i];
+}
+
 struct Box {
     float lo[3], hi[3];
 };
@@ -212,6 +254,15 @@ uint32_t blocksFor(uint32_t n) { return (n + kBlock - 1u) / kBlock; }
 
 void launchDynBake(const DynBakeArrays& a, const float4* dMeshTable, uint32_t mesh, const uint32_t* dList, uint32_t count, hipStream_t stream) {
     if (count > 0u) hipLaunchKernelGGL(k_dyn_bake, dim3(blocksFor(count)), dim3(kBlock), 0, stream, a, dMeshTable, mesh, dList, count);
+}
+
+void launchDynGatherCorners(float4* dObjPos, float4* dObjNrm, float4* dObjTan, const DynVertexArrays& v, const uint32_t* dList, const uint32_t* dCorners,
+                            uint32_t count, hipStream_t stream) {
+    if (count > 0u) hipLaunchKernelGGL(k_dyn_gather_corners, dim3(blocksFor(count)), dim3(kBlock), 0, stream, dObjPos, dObjNrm, dObjTan, v, dList, dCorners, count);
+}
+
+void launchDynScatterRows(const DynScatterTargets& t, const float4* dRows, const uint32_t* dDest, uint32_t count, hipStream_t stream) {
+    if (count > 0u) hipLaunchKernelGGL(k_dyn_scatter_rows, dim3(blocksFor(count)), dim3(kBlock), 0, stream, t, dRows, dDest, count);
 }
 
 void launchDynRefitLevel(float4* dBoxes, const uint32_t* dSchedule, uint32_t count, const float4* dTriBounds, const float4* dSphereBounds,
