@@ -521,6 +521,24 @@ DEFORM_SYMBOLS = tuple(_DEFORM_SIGNATURES)
 # ptr_debug_dynamic_update_rows: the arrays a destination word names, (array << 28) | row
 SCATTER_ARRAYS = ("tris", "triNormals", "triBounds", "spheres", "sphereBounds", "rects", "rectLights")
 
+# ... and of include/ptr_deform_device.h (deforming meshes from device-resident arrays, vertex normals on the device):
+# tests/test_deform_device_host.py holds it against that header
+PTR_DYNAMIC_VERTEX_NORMALS = 4
+
+
+class PtrMeshVerticesDevice(C.Structure):
+    """include/ptr_deform_device.h PtrMeshVerticesDevice: the pointers are device addresses."""
+    _fields_ = [("meshIndex", C.c_uint32), ("vertexCount", C.c_uint32), ("positions", C.c_void_p), ("normals", C.c_void_p), ("tangents", C.c_void_p)]
+
+
+_DEFORM_DEVICE_SIGNATURES = {
+    "ptr_scene_upload_deformable": (_int, [_desc, _int, _u32, C.POINTER(_vp)] + _err),
+    "ptr_scene_set_mesh_vertices_device": (_int, [_vp, C.POINTER(PtrMeshVerticesDevice), _u32, _vp, C.POINTER(PtrUpdateInfo)] + _err),
+    # its test-only probe
+    "ptr_debug_vertex_adjacency": (_int, [_desc, _u32, _vp, _u64, _u64p] + _err),
+}
+DEFORM_DEVICE_SYMBOLS = tuple(_DEFORM_DEVICE_SIGNATURES)
+
 # ... and of include/ptr_background.h (the primary-ray bounds cull): tests/test_background_cull_host.py holds it against that header
 _BACKGROUND_SIGNATURES = {
     "ptr_background_debug_cull": (_int, [_vp, _desc, _settings, _u32, _u32, _int, _up, C.POINTER(C.c_double)] + _err),
@@ -560,7 +578,8 @@ def load_library() -> C.CDLL:
     lib = C.CDLL(path)
     for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_POST_SIGNATURES.items()) + list(_STATS_SIGNATURES.items()) + \
             list(_ADAPTIVE_SIGNATURES.items()) + list(_MULTI_SIGNATURES.items()) + list(_FRAME_SIGNATURES.items()) + list(_MULTI_FRAME_SIGNATURES.items()) + \
-            list(_DYNAMIC_SIGNATURES.items()) + list(_DEFORM_SIGNATURES.items()) + list(_BACKGROUND_SIGNATURES.items()):
+            list(_DYNAMIC_SIGNATURES.items()) + list(_DEFORM_SIGNATURES.items()) + list(_DEFORM_DEVICE_SIGNATURES.items()) + \
+            list(_BACKGROUND_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -677,23 +696,30 @@ class DeviceScene:
     """A scene resident in HBM: SAH BVH + SoA primitive/material/light arrays (ptr_scene_upload)."""
 
     def __init__(self, desc: PtrSceneDesc, device: int = 0, keepalive=None, prepared: Optional[str] = None, dynamic: bool = False,
-                 deformable: bool = False, primitives: bool = False):
+                 deformable: bool = False, primitives: bool = False, vertex_normals: bool = False):
         """prepared: a geometry cache written by prepare_geometry() for this description - the BVH is read, not built
         (the processes of a multi-GPU render build it once).  dynamic: ptr_scene_upload_dynamic - the scene also keeps what
         set_mesh_transforms needs to move its meshes on the device (not with `prepared`).  deformable / primitives (with dynamic):
-        ptr_scene_upload_dynamic_ex with PTR_DYNAMIC_DEFORMABLE / PTR_DYNAMIC_PRIMITIVES, for set_mesh_vertices / set_spheres and set_rects."""
+        ptr_scene_upload_dynamic_ex with PTR_DYNAMIC_DEFORMABLE / PTR_DYNAMIC_PRIMITIVES, for set_mesh_vertices / set_spheres and set_rects.
+        vertex_normals (with deformable): ptr_scene_upload_deformable with PTR_DYNAMIC_VERTEX_NORMALS as well - set_mesh_vertices_device may
+        then be given positions alone."""
         lib = load_library()
         if lib.ptr_device_count() <= 0:
             raise PtrError("no HIP device visible: the HIP render path has no CPU fallback")
         self._keepalive = keepalive
         self._h = C.c_void_p()
+        self._device = int(device)
         err = _err_buf()
         if dynamic and prepared:
             raise PtrError("a dynamic scene is not read from a geometry cache")
         if (deformable or primitives) and not dynamic:
             raise PtrError("deformable / primitives need dynamic=True")
-        if deformable or primitives:
-            flags = (PTR_DYNAMIC_DEFORMABLE if deformable else 0) | (PTR_DYNAMIC_PRIMITIVES if primitives else 0)
+        if vertex_normals and not deformable:
+            raise PtrError("vertex_normals needs deformable=True")
+        flags = (PTR_DYNAMIC_DEFORMABLE if deformable else 0) | (PTR_DYNAMIC_PRIMITIVES if primitives else 0)
+        if vertex_normals:
+            _check(lib.ptr_scene_upload_deformable(C.byref(desc), device, flags | PTR_DYNAMIC_VERTEX_NORMALS, C.byref(self._h), err, len(err)), err)
+        elif deformable or primitives:
             _check(lib.ptr_scene_upload_dynamic_ex(C.byref(desc), device, flags, C.byref(self._h), err, len(err)), err)
         elif dynamic:
             _check(lib.ptr_scene_upload_dynamic(C.byref(desc), device, C.byref(self._h), err, len(err)), err)
@@ -737,6 +763,41 @@ class DeviceScene:
         info = PtrUpdateInfo()
         err = _err_buf()
         _check(load_library().ptr_scene_set_mesh_vertices(self._h, items, len(meshes), C.c_void_p(stream), C.byref(info), err, len(err)), err)
+        return info.as_dict()
+
+    def set_mesh_vertices_device(self, meshes: dict, stream=None) -> dict:
+        """ptr_scene_set_mesh_vertices_device: {mesh index: (positions [n, 3], normals [n, 3] or None[, tangents [n, 4]])} of torch tensors
+        on the scene's device, float32 and contiguous, passed by data_ptr(); None for the normals has them computed on the device (a
+        scene made with vertex_normals=True).  The tensors are read on `stream` (a raw stream handle; None: torch's current stream of the
+        scene's device): whatever produces them is enqueued there before the call, or has finished.  Returns PtrUpdateInfo as a dict."""
+        items = (PtrMeshVerticesDevice * max(len(meshes), 1))()
+        for k, (index, data) in enumerate(meshes.items()):
+            data = tuple(data)
+            if not 2 <= len(data) <= 3:
+                raise PtrError("set_mesh_vertices_device: mesh %s needs (positions, normals or None[, tangents])" % (index,))
+            for name, t, width in zip(("positions", "normals", "tangents"), data, (3, 3, 4)):
+                if t is None and name == "normals":
+                    continue
+                device = getattr(t, "device", None)
+                if not hasattr(t, "data_ptr") or device is None:
+                    raise PtrError("set_mesh_vertices_device: the %s of mesh %s are not a torch tensor" % (name, index))
+                if device.type != "cuda" or device.index != self._device:
+                    raise PtrError("set_mesh_vertices_device: the %s of mesh %s are on %s, not on device %d of the scene" % (name, index, device, self._device))
+                if str(t.dtype) != "torch.float32":
+                    raise PtrError("set_mesh_vertices_device: the %s of mesh %s are %s, not float32" % (name, index, t.dtype))
+                if t.dim() != 2 or t.shape[1] != width or (name != "positions" and t.shape[0] != data[0].shape[0]):
+                    raise PtrError("set_mesh_vertices_device: the %s of mesh %s have shape %s, not [n, %d]" % (name, index, tuple(t.shape), width))
+                if not t.is_contiguous():
+                    raise PtrError("set_mesh_vertices_device: the %s of mesh %s are not contiguous" % (name, index))
+                setattr(items[k], name, t.data_ptr())
+            items[k].meshIndex, items[k].vertexCount = int(index), int(data[0].shape[0])
+        if stream is None:
+            import torch   # (only here: the module itself does not need torch)
+
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+        info = PtrUpdateInfo()
+        err = _err_buf()
+        _check(load_library().ptr_scene_set_mesh_vertices_device(self._h, items, len(meshes), C.c_void_p(stream), C.byref(info), err, len(err)), err)
         return info.as_dict()
 
     def set_spheres(self, spheres: dict, stream: int = 0) -> dict:
@@ -1624,6 +1685,19 @@ def debug_dynamic_update_rows(desc: PtrSceneDesc, update) -> list:
     _check(lib.ptr_debug_dynamic_update_rows(C.byref(desc), kind, C.byref(update), buf.ctypes.data_as(C.c_void_p), buf.nbytes, C.byref(n), err, len(err)), err)
     rows, dest = buf[: n.value * 4].view(np.float32).reshape(-1, 4), buf[n.value * 4:]
     return [(SCATTER_ARRAYS[int(d) >> 28], int(d) & 0x0FFFFFFF, rows[i]) for i, d in enumerate(dest)]
+
+
+def debug_vertex_adjacency(desc: PtrSceneDesc, mesh: int) -> Tuple[np.ndarray, np.ndarray]:
+    """ptr_debug_vertex_adjacency (host only): the vertex adjacency PTR_DYNAMIC_VERTEX_NORMALS keeps for mesh `mesh` of `desc`, as (row offsets
+    [vertexCount + 1], entries [corners]): an entry is the number, within the mesh, of a description triangle that names the vertex."""
+    lib = load_library()
+    err = _err_buf()
+    size = C.c_uint64(0)
+    _check(lib.ptr_debug_vertex_adjacency(C.byref(desc), mesh, None, 0, C.byref(size), err, len(err)), err)
+    buf = np.zeros(size.value // 4, np.uint32)
+    _check(lib.ptr_debug_vertex_adjacency(C.byref(desc), mesh, buf.ctypes.data_as(C.c_void_p), buf.nbytes, C.byref(size), err, len(err)), err)
+    n = int(desc.meshes[mesh].vertexCount) + 1
+    return buf[:n], buf[n:]
 
 
 def debug_dynamic_tables(desc: PtrSceneDesc, names=None) -> dict:

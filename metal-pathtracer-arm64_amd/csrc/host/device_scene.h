@@ -134,6 +134,12 @@ struct DynamicScene {
     DeviceBuffer<uint32_t> meshCorners;
     std::vector<uint32_t> meshVertexCount;
     std::vector<uint8_t> meshTangentsGiven;
+    // PTR_DYNAMIC_VERTEX_NORMALS (include/ptr_deform_device.h): the vertex adjacency of every mesh (ptr::DynamicTables::adjOffsets /
+    // adjEntries / adjBase), uploaded once; the normals k_dyn_vertex_normals computes in a call; the flag words of k_dyn_check_finite
+    DeviceBuffer<uint32_t> adjOffsets, adjEntries;
+    std::vector<uint64_t> adjBase;
+    DeviceBuffer<float> computedNormals;
+    DeviceBuffer<uint32_t> checkFlags;
     // PTR_DYNAMIC_PRIMITIVES: where the rows of a rectangle and of a sphere live, and the records they currently hold
     PrimitiveRecords prims;
     // staging of the update calls, grown on demand and kept: a pinned host buffer and its device twin

@@ -1,7 +1,7 @@
-// Dynamic scenes (include/ptr_dynamic.h, include/ptr_deform.h): the upload of the extra device data, ptr_scene_set_mesh_transforms,
-// ptr_scene_set_mesh_vertices, ptr_scene_set_spheres and ptr_scene_set_rects, which all end in the same refit (finishUpdate), and the
-// headers' test-only probes, which look at a scene's arrays.  Compiled with hipcc (host code only), like hip_backend.cpp; the kernels are
-// in kernels/dynamic.hip.
+// Dynamic scenes (include/ptr_dynamic.h, include/ptr_deform.h, include/ptr_deform_device.h): the upload of the extra device data,
+// ptr_scene_set_mesh_transforms, ptr_scene_set_mesh_vertices and its device-pointer form, ptr_scene_set_spheres and ptr_scene_set_rects,
+// which all end in the same refit (finishUpdate), and the headers' test-only probes, which look at a scene's arrays.  Compiled with
+// hipcc (host code only), like hip_backend.cpp; the kernels are in kernels/dynamic.hip.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -9,7 +9,7 @@
 #include "../kernels/bvh_grid.h"
 #include "../kernels/dynamic.h"
 #include "device_scene.h"
-#include "ptr_deform.h"
+#include "ptr_deform_device.h"
 #include "ptr_dynamic.h"
 #include "vecmath.h"
 
@@ -79,6 +79,11 @@ void uploadDynamicTables(const PtrSceneDesc& desc, const PreparedScene& ps, PtrD
         dyn->meshVertexCount = t.meshVertexCount;
         dyn->meshTangentsGiven = t.meshTangentsGiven;
     }
+    if (t.flags & PTR_DYNAMIC_VERTEX_NORMALS) {
+        dyn->adjOffsets.upload(t.adjOffsets.data(), t.adjOffsets.size());
+        dyn->adjEntries.upload(t.adjEntries.data(), t.adjEntries.size());
+        dyn->adjBase = t.adjBase;
+    }
     if (t.flags & PTR_DYNAMIC_PRIMITIVES) {
         fillPrimitiveRecords(desc, ps.pg.geo, t, ps.lightIndexByRect, dyn->prims);
     }
@@ -142,6 +147,79 @@ std::string matrixProblem(const float m[16], const ptr::MeshBake& bake) {
     return "";
 }
 
+// One named mesh of ptr_scene_set_mesh_vertices / ptr_scene_set_mesh_vertices_device once the call is accepted
+struct MeshSource {
+    bool used = false;   // false: a mesh without triangles, which changes nothing
+    DynVertexArrays v{nullptr, nullptr, nullptr};   // where the gather reads its arrays, on the device
+};
+
+// What both calls refuse about entry `mv` of their list (PtrMeshVertices and PtrMeshVerticesDevice have the same members): "" or the
+// cause.  named: per mesh of the scene, how often the list has named it so far.  used: the mesh has triangles.
+template <typename V>
+std::string namedMeshProblem(const DynamicScene& dyn, const V& mv, std::vector<uint8_t>& named, bool normalsMayBeNull, const char* nullNormalsHint, bool& used) {
+    used = false;
+    const uint32_t meshCount = static_cast<uint32_t>(named.size());
+    if (mv.meshIndex >= meshCount) {
+        return "mesh index " + std::to_string(mv.meshIndex) + " out of range (the scene has " + std::to_string(meshCount) + " meshes)";
+    }
+    if (named[mv.meshIndex]++) return "mesh index " + std::to_string(mv.meshIndex) + " named twice";
+    if (dyn.meshTriOffsets[mv.meshIndex + 1u] == dyn.meshTriOffsets[mv.meshIndex]) return "";   // no triangles: nothing to change
+    const std::string mesh = "mesh " + std::to_string(mv.meshIndex);
+    if (mv.vertexCount != dyn.meshVertexCount[mv.meshIndex]) {
+        return mesh + " was uploaded with " + std::to_string(dyn.meshVertexCount[mv.meshIndex]) + " vertices, not vertexCount " + std::to_string(mv.vertexCount);
+    }
+    if (!mv.positions) return mesh + " has null positions";
+    if (!mv.normals && !normalsMayBeNull) return mesh + " has null normals" + nullNormalsHint;
+    if (mv.tangents && !dyn.meshTangentsGiven[mv.meshIndex]) return mesh + " was uploaded without tangents and is given some";
+    if (!mv.tangents && dyn.meshTangentsGiven[mv.meshIndex]) return mesh + " was uploaded with tangents and is given none";
+    used = true;
+    return "";
+}
+
+// What both calls run once the mesh table is on the device and event 0 is recorded: per named mesh with triangles the gather of its
+// arrays into the object-space corner rows and the bake under the matrix the mesh has (row i of the table), then the shared tail.
+template <typename V>
+void gatherBakeFinish(PtrDeviceScene& ds, const V* meshes, const std::vector<MeshSource>& src, hipStream_t st, std::chrono::steady_clock::time_point t0,
+                      PtrUpdateInfo* info) {
+    DynamicScene& dyn = *ds.dynamic;
+    const DynBakeArrays arrays = bakeArrays(ds);
+    uint64_t moved = 0;
+    for (uint32_t i = 0; i < src.size(); ++i) {
+        if (!src[i].used) continue;
+        const uint32_t m = meshes[i].meshIndex;
+        const uint32_t first = dyn.meshTriOffsets[m], n = dyn.meshTriOffsets[m + 1u] - first;
+        launchDynGatherCorners(dyn.objPos.ptr, dyn.objNrm.ptr, dyn.textured ? dyn.objTan.ptr : nullptr, src[i].v, dyn.meshTris.ptr + first,
+                               dyn.meshCorners.ptr + static_cast<size_t>(first) * 3u, n, st);
+        launchDynBake(arrays, dyn.meshTable.ptr, i, dyn.meshTris.ptr + first, n, st);
+        moved += n;
+    }
+    finishUpdate(ds, st, t0, moved, info);
+}
+
+// What is wrong with `bytes` of a caller's array at `p` for a kernel on `device` to read, or "": the host half of
+// ptr_scene_set_mesh_vertices_device looks at the pointer alone, never at what it points to.
+std::string devicePointerProblem(const void* p, size_t bytes, int device) {
+    if (reinterpret_cast<uintptr_t>(p) & 3u) return "is not 4 B aligned";
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void)hipGetLastError();   // (a pointer the runtime has never seen)
+        return "is host memory, not device memory";
+    }
+    if (attr.isManaged || attr.type == hipMemoryTypeManaged) return "is managed memory, not plain device memory";
+    if (attr.type == hipMemoryTypeHost) return "is registered or pinned host memory, not device memory";
+    if (attr.type == hipMemoryTypeUnregistered) return "is host memory, not device memory";
+    if (attr.type != hipMemoryTypeDevice) return "is not plain device memory";
+    if (attr.device != device) return "is memory of device " + std::to_string(attr.device) + ", not of the scene's device " + std::to_string(device);
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
+        (void)hipGetLastError();   // (no range on record: the kind and the device are what is known)
+        return "";
+    }
+    const uintptr_t end = reinterpret_cast<uintptr_t>(base) + size, at = reinterpret_cast<uintptr_t>(p);
+    if (at > end || end - at < bytes) return "has " + std::to_string(end - std::min(at, end)) + " B left in its allocation, fewer than the " + std::to_string(bytes) + " B of the array";
+    return "";
+}
 }  // namespace
 
 extern "C" {
@@ -219,28 +297,11 @@ int ptr_scene_set_mesh_vertices(PtrDeviceScene* scene, const PtrMeshVertices* me
         std::vector<uint8_t> named(meshCount, 0);
         for (uint32_t i = 0; i < count; ++i) {
             const PtrMeshVertices& mv = meshes[i];
-            const std::string mesh = "mesh " + std::to_string(mv.meshIndex);
-            if (mv.meshIndex >= meshCount) {
-                return refuse(err, err_cap, std::string(who) + ": mesh index " + std::to_string(mv.meshIndex) + " out of range (the scene has " +
-                                                std::to_string(meshCount) + " meshes)");
-            }
-            if (named[mv.meshIndex]++) return refuse(err, err_cap, std::string(who) + ": mesh index " + std::to_string(mv.meshIndex) + " named twice");
-            rows[i] = dyn.meshRows[mv.meshIndex];
-            if (dyn.meshTriOffsets[mv.meshIndex + 1u] == dyn.meshTriOffsets[mv.meshIndex]) continue;   // no triangles: nothing to change
-            if (mv.vertexCount != dyn.meshVertexCount[mv.meshIndex]) {
-                return refuse(err, err_cap, std::string(who) + ": " + mesh + " was uploaded with " + std::to_string(dyn.meshVertexCount[mv.meshIndex]) +
-                                                " vertices, not vertexCount " + std::to_string(mv.vertexCount));
-            }
-            if (!mv.positions) return refuse(err, err_cap, std::string(who) + ": " + mesh + " has null positions");
-            if (!mv.normals) return refuse(err, err_cap, std::string(who) + ": " + mesh + " has null normals");
-            if (mv.tangents && !dyn.meshTangentsGiven[mv.meshIndex]) {
-                return refuse(err, err_cap, std::string(who) + ": " + mesh + " was uploaded without tangents and is given some");
-            }
-            if (!mv.tangents && dyn.meshTangentsGiven[mv.meshIndex]) {
-                return refuse(err, err_cap, std::string(who) + ": " + mesh + " was uploaded with tangents and is given none");
-            }
             Staged& s = staged[i];
-            s.used = true;
+            const std::string problem = namedMeshProblem(dyn, mv, named, false, "", s.used);
+            if (!problem.empty()) return refuse(err, err_cap, std::string(who) + ": " + problem);
+            rows[i] = dyn.meshRows[mv.meshIndex];
+            if (!s.used) continue;
             s.hasTangents = dyn.meshHasTangents[mv.meshIndex] != 0;   // (an untextured scene keeps no tangents: they are checked and dropped)
             s.positions = floats, floats += static_cast<size_t>(mv.vertexCount) * 3u;
             s.normals = floats, floats += static_cast<size_t>(mv.vertexCount) * 3u;
@@ -278,27 +339,121 @@ int ptr_scene_set_mesh_vertices(PtrDeviceScene* scene, const PtrMeshVertices* me
     return deviceCall(who, scene, true, err, err_cap, [&] {
         const auto t0 = std::chrono::steady_clock::now();
         hipStream_t st = static_cast<hipStream_t>(stream);
-        PtrDeviceScene& ds = *scene;
         dyn.staging.ensure((floats + 3u) / 4u);
         const float* dStaged = reinterpret_cast<const float*>(dyn.staging.ptr);
         if (floats) HIP_CHECK(hipMemcpyAsync(dyn.staging.ptr, dyn.pinned, floats * sizeof(float), hipMemcpyHostToDevice, st));
         dyn.meshTable.ensure(static_cast<size_t>(count) * kDynMeshVec4);
         HIP_CHECK(hipMemcpyAsync(dyn.meshTable.ptr, rows.data(), rows.size() * sizeof(DynMeshRow), hipMemcpyHostToDevice, st));
         HIP_CHECK(hipEventRecord(dyn.events[0], st));
-        const DynBakeArrays arrays = bakeArrays(ds);
-        uint64_t moved = 0;
+        std::vector<MeshSource> src(count);
         for (uint32_t i = 0; i < count; ++i) {
             const Staged& s = staged[i];
-            if (!s.used) continue;
-            const uint32_t m = meshes[i].meshIndex;
-            const uint32_t first = dyn.meshTriOffsets[m], n = dyn.meshTriOffsets[m + 1u] - first;
-            const DynVertexArrays v{dStaged + s.positions, dStaged + s.normals, s.hasTangents ? dStaged + s.tangents : nullptr};
-            launchDynGatherCorners(dyn.objPos.ptr, dyn.objNrm.ptr, dyn.textured ? dyn.objTan.ptr : nullptr, v, dyn.meshTris.ptr + first,
-                                   dyn.meshCorners.ptr + static_cast<size_t>(first) * 3u, n, st);
-            launchDynBake(arrays, dyn.meshTable.ptr, i, dyn.meshTris.ptr + first, n, st);
-            moved += n;
+            src[i].used = s.used;
+            if (s.used) src[i].v = DynVertexArrays{dStaged + s.positions, dStaged + s.normals, s.hasTangents ? dStaged + s.tangents : nullptr};
         }
-        finishUpdate(ds, st, t0, moved, info);
+        gatherBakeFinish(*scene, meshes, src, st, t0, info);
+    });
+}
+
+int ptr_scene_set_mesh_vertices_device(PtrDeviceScene* scene, const PtrMeshVerticesDevice* meshes, uint32_t count, void* stream, PtrUpdateInfo* info,
+                                       char* err, size_t err_cap) {
+    const char* who = "ptr_scene_set_mesh_vertices_device";
+    if (!scene) return nullArgument(who, err, err_cap);
+    if (!scene->dynamic || !(scene->dynamic->flags & PTR_DYNAMIC_DEFORMABLE)) {
+        return refuse(err, err_cap, std::string(who) + ": the scene is not deformable (upload it with ptr_scene_upload_dynamic_ex and PTR_DYNAMIC_DEFORMABLE)");
+    }
+    if (!meshes) return refuse(err, err_cap, std::string(who) + ": null mesh list");
+    if (count == 0u) return refuse(err, err_cap, std::string(who) + ": count is 0");
+    DynamicScene& dyn = *scene->dynamic;
+    const uint32_t meshCount = static_cast<uint32_t>(dyn.meshTriOffsets.size()) - 1u;
+    const bool computes = (dyn.flags & PTR_DYNAMIC_VERTEX_NORMALS) != 0u;
+    std::vector<MeshSource> src(count);
+    std::vector<DynMeshRow> rows(count);
+    // the arrays k_dyn_check_finite looks at, in the order a refusal names them: per named mesh positions, normals, tangents
+    struct Checked {
+        uint32_t entry;      // of the list
+        const char* what;
+        bool computed;       // normals this call computes: the row's pointer is set once the scratch is there
+    };
+    std::vector<DynCheckRow> checks;
+    std::vector<Checked> checked;
+    std::vector<size_t> computedAt(count, 0);   // per entry whose normals are computed: where, in floats of the scratch
+    size_t computedFloats = 0;
+    uint64_t largest = 0;
+    try {
+        std::vector<uint8_t> named(meshCount, 0);
+        for (uint32_t i = 0; i < count; ++i) {
+            const PtrMeshVerticesDevice& mv = meshes[i];
+            const std::string problem = namedMeshProblem(dyn, mv, named, computes, " (computing them needs a scene uploaded with PTR_DYNAMIC_VERTEX_NORMALS)", src[i].used);
+            if (!problem.empty()) return refuse(err, err_cap, std::string(who) + ": " + problem);
+            rows[i] = dyn.meshRows[mv.meshIndex];
+            if (!src[i].used) continue;
+            const size_t n = mv.vertexCount;
+            const struct {
+                const float* data;
+                size_t floats;
+                const char* what;
+                bool computedIfNull;
+            } given[3] = {{mv.positions, n * 3u, "position", false}, {mv.normals, n * 3u, "normal", true}, {mv.tangents, n * 4u, "tangent", false}};
+            for (const auto& g : given) {
+                if (!g.data && !g.computedIfNull) continue;   // (no tangents: the mesh carries none)
+                if (g.data) {
+                    const std::string bad = devicePointerProblem(g.data, g.floats * sizeof(float), scene->device);
+                    if (!bad.empty()) return refuse(err, err_cap, std::string(who) + ": the " + g.what + " array of mesh " + std::to_string(mv.meshIndex) + " " + bad);
+                }
+                checks.push_back(DynCheckRow{g.data, g.floats});
+                checked.push_back(Checked{i, g.what, !g.data});
+                largest = std::max<uint64_t>(largest, g.floats);
+            }
+            if (!mv.normals) computedAt[i] = computedFloats, computedFloats += n * 3u;
+            // (an untextured scene keeps no tangents: they are checked and dropped)
+            src[i].v = DynVertexArrays{mv.positions, mv.normals, dyn.meshHasTangents[mv.meshIndex] ? mv.tangents : nullptr};
+        }
+        if (pastIndexLimit(checks.size())) return refuse(err, err_cap, std::string(who) + ": too many meshes in one call");
+    }
+    PTR_CATCH_ALL(err, err_cap)
+
+    return deviceCall(who, scene, true, err, err_cap, [&] {
+        const auto t0 = std::chrono::steady_clock::now();
+        hipStream_t st = static_cast<hipStream_t>(stream);
+        if (computedFloats) dyn.computedNormals.ensure(computedFloats);
+        for (size_t r = 0; r < checks.size(); ++r) {
+            if (!checked[r].computed) continue;
+            const uint32_t i = checked[r].entry;
+            src[i].v.normals = checks[r].data = dyn.computedNormals.ptr + computedAt[i];
+        }
+        // the check rows ride behind the mesh rows of the table (both are 16 B units)
+        dyn.meshTable.ensure(static_cast<size_t>(count) * kDynMeshVec4 + checks.size());
+        HIP_CHECK(hipMemcpyAsync(dyn.meshTable.ptr, rows.data(), rows.size() * sizeof(DynMeshRow), hipMemcpyHostToDevice, st));
+        const DynCheckRow* dChecks = reinterpret_cast<const DynCheckRow*>(dyn.meshTable.ptr + static_cast<size_t>(count) * kDynMeshVec4);
+        const size_t words = (checks.size() + 31u) / 32u;
+        if (!checks.empty()) {
+            HIP_CHECK(hipMemcpyAsync(const_cast<DynCheckRow*>(dChecks), checks.data(), checks.size() * sizeof(DynCheckRow), hipMemcpyHostToDevice, st));
+            dyn.checkFlags.ensure(words);
+            HIP_CHECK(hipMemsetAsync(dyn.checkFlags.ptr, 0, words * sizeof(uint32_t), st));
+        }
+        HIP_CHECK(hipEventRecord(dyn.events[0], st));
+        for (uint32_t i = 0; i < count; ++i) {
+            if (!src[i].used || meshes[i].normals) continue;
+            const uint32_t m = meshes[i].meshIndex;
+            const size_t first = dyn.meshTriOffsets[m];
+            launchDynVertexNormals(meshes[i].positions, dyn.adjOffsets.ptr + dyn.adjBase[m], dyn.adjEntries.ptr + first * 3u, dyn.meshCorners.ptr + first * 3u,
+                                   dyn.computedNormals.ptr + computedAt[i], meshes[i].vertexCount, st);
+        }
+        if (!checks.empty()) {
+            // nothing the renderer reads has been written yet: the flag words come back first, and a set bit ends the call here
+            launchDynCheckFinite(dChecks, static_cast<uint32_t>(checks.size()), largest, dyn.checkFlags.ptr, st);
+            const uint32_t* flags = static_cast<const uint32_t*>(dyn.pinnedFor(words * sizeof(uint32_t)));
+            HIP_CHECK(hipMemcpyAsync(dyn.pinned, dyn.checkFlags.ptr, words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+            for (size_t r = 0; r < checks.size(); ++r) {
+                if (flags[r >> 5] >> (r & 31u) & 1u) {
+                    throw HipError{std::string(who) + ": mesh " + std::to_string(meshes[checked[r].entry].meshIndex) + " has a non-finite " + checked[r].what +
+                                   " component"};
+                }
+            }
+        }
+        gatherBakeFinish(*scene, meshes, src, st, t0, info);
     });
 }
 
@@ -584,6 +739,27 @@ int ptr_debug_scene_arrays(PtrDeviceScene* scene, uint32_t which, void* out, uin
     }
     if (hipSetDevice(ds.device) != hipSuccess || hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) return 3;
     return 0;
+}
+
+int ptr_debug_vertex_adjacency(const PtrSceneDesc* scene, uint32_t mesh, void* out, uint64_t cap_bytes, uint64_t* size_out, char* err, size_t err_cap) {
+    const char* who = "ptr_debug_vertex_adjacency";
+    if (!scene || !size_out) return nullArgument(who, err, err_cap);
+    if (mesh >= scene->meshCount) return refuse(err, err_cap, std::string(who) + ": mesh index out of range");
+    try {
+        ptr::PreparedGeometry pg;
+        ptr::DynamicTables t;
+        t.flags = PTR_DYNAMIC_DEFORMABLE | PTR_DYNAMIC_PRIMITIVES | PTR_DYNAMIC_VERTEX_NORMALS;
+        prepareGeometry(*scene, pg, &t);
+        const size_t offsets = static_cast<size_t>(t.adjBase[mesh + 1u] - t.adjBase[mesh]);
+        const size_t entries = static_cast<size_t>(t.meshTriOffsets[mesh + 1u] - t.meshTriOffsets[mesh]) * 3u;
+        *size_out = (offsets + entries) * 4u;
+        if (!out) return 0;
+        if (cap_bytes < *size_out) return refuse(err, err_cap, std::string(who) + ": the buffer is too small");
+        std::memcpy(out, t.adjOffsets.data() + t.adjBase[mesh], offsets * 4u);
+        if (entries) std::memcpy(static_cast<char*>(out) + offsets * 4u, t.adjEntries.data() + static_cast<size_t>(t.meshTriOffsets[mesh]) * 3u, entries * 4u);
+        return 0;
+    }
+    PTR_CATCH_ALL(err, err_cap)
 }
 
 int ptr_debug_dynamic_tables(const PtrSceneDesc* scene, uint32_t which, void* out, uint64_t cap_bytes, uint64_t* size_out, char* err, size_t err_cap) {

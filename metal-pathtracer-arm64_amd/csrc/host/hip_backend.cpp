@@ -24,7 +24,7 @@
 #include "env_importance_sampler.h"
 #include "geometry_cache.h"
 #include "knobs.h"
-#include "ptr_deform.h"
+#include "ptr_deform_device.h"
 #include "ptr_dynamic.h"
 #include "scene_geometry.h"
 #include "vecmath.h"
@@ -378,6 +378,17 @@ int uploadTo(const char* who, const PtrSceneDesc* scene, const char* cachePath, 
         return 0;
     }
     PTR_CATCH_ALL(err, cap)
+}
+
+// The three uploads of a dynamic scene: `known` is the mask of the PTR_DYNAMIC_* flags the entry point `who` knows
+int uploadDynamic(const char* who, uint32_t known, const PtrSceneDesc* scene, int device, uint32_t flags, PtrDeviceScene** out_scene, char* err,
+                  size_t err_cap) {
+    if (flags & ~known) return refuse(err, err_cap, std::string(who) + ": unknown flag");
+    if ((flags & PTR_DYNAMIC_VERTEX_NORMALS) && !(flags & PTR_DYNAMIC_DEFORMABLE)) {
+        return refuse(err, err_cap, std::string(who) + ": PTR_DYNAMIC_VERTEX_NORMALS needs PTR_DYNAMIC_DEFORMABLE");
+    }
+    if (scene && out_scene && ptr_device_count() < 1) return noDevice(who, err, err_cap);
+    return uploadTo(who, scene, nullptr, device, out_scene, err, err_cap, true, flags);
 }
 
 // Camera basis on the host (BuildCamera, EmbreeHeadlessRenderer.mm:150-198).
@@ -1215,15 +1226,16 @@ int ptr_scene_upload(const PtrSceneDesc* scene, int device, PtrDeviceScene** out
 }
 
 int ptr_scene_upload_dynamic(const PtrSceneDesc* scene, int device, PtrDeviceScene** out_scene, char* err, size_t err_cap) {
-    if (scene && out_scene && ptr_device_count() < 1) return noDevice("ptr_scene_upload_dynamic", err, err_cap);
-    return uploadTo("ptr_scene_upload_dynamic", scene, nullptr, device, out_scene, err, err_cap, true);
+    return uploadDynamic("ptr_scene_upload_dynamic", 0u, scene, device, 0u, out_scene, err, err_cap);
 }
 
 int ptr_scene_upload_dynamic_ex(const PtrSceneDesc* scene, int device, uint32_t flags, PtrDeviceScene** out_scene, char* err, size_t err_cap) {
-    const char* who = "ptr_scene_upload_dynamic_ex";
-    if (flags & ~static_cast<uint32_t>(PTR_DYNAMIC_DEFORMABLE | PTR_DYNAMIC_PRIMITIVES)) return refuse(err, err_cap, std::string(who) + ": unknown flag");
-    if (scene && out_scene && ptr_device_count() < 1) return noDevice(who, err, err_cap);
-    return uploadTo(who, scene, nullptr, device, out_scene, err, err_cap, true, flags);
+    return uploadDynamic("ptr_scene_upload_dynamic_ex", PTR_DYNAMIC_DEFORMABLE | PTR_DYNAMIC_PRIMITIVES, scene, device, flags, out_scene, err, err_cap);
+}
+
+int ptr_scene_upload_deformable(const PtrSceneDesc* scene, int device, uint32_t flags, PtrDeviceScene** out_scene, char* err, size_t err_cap) {
+    return uploadDynamic("ptr_scene_upload_deformable", PTR_DYNAMIC_DEFORMABLE | PTR_DYNAMIC_PRIMITIVES | PTR_DYNAMIC_VERTEX_NORMALS, scene, device, flags,
+                         out_scene, err, err_cap);
 }
 
 void ptr_scene_release(PtrDeviceScene* scene) {

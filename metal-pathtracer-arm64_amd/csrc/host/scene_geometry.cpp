@@ -398,6 +398,19 @@ bool BuildSceneGeometry(const PtrSceneDesc& desc, uint32_t leafMax, SceneGeometr
                 dyn->meshTangentsGiven[mi] = desc.meshes[mi].tangents ? 1 : 0;
             }
         }
+        if (wantCorners && (flags & PTR_DYNAMIC_VERTEX_NORMALS) != 0u) {
+            dyn->adjBase.assign(static_cast<size_t>(desc.meshCount) + 1u, 0u);
+            std::vector<uint32_t> offsets, entries;
+            for (uint32_t mi = 0; mi < desc.meshCount; ++mi) {
+                const PtrMeshDesc& mesh = desc.meshes[mi];
+                // (a mesh the bake skips has no corners: its rows are all empty)
+                const size_t meshTris = mesh.vertexCount == 0 ? 0u : mesh.indexCount / 3u;
+                BuildVertexAdjacency(mesh.indices, meshTris, mesh.vertexCount, offsets, entries);
+                dyn->adjOffsets.insert(dyn->adjOffsets.end(), offsets.begin(), offsets.end());
+                dyn->adjEntries.insert(dyn->adjEntries.end(), entries.begin(), entries.end());
+                dyn->adjBase[mi + 1u] = dyn->adjOffsets.size();
+            }
+        }
         size_t at = 0;
         for (uint32_t mi = 0; mi < desc.meshCount; ++mi) {
             const PtrMeshDesc& mesh = desc.meshes[mi];
@@ -454,6 +467,17 @@ bool BuildSceneGeometry(const PtrSceneDesc& desc, uint32_t leafMax, SceneGeometr
                      out.buildSeconds, out.flattenSeconds, out.triCount, out.sphereCount);
     }
     return true;
+}
+
+void BuildVertexAdjacency(const uint32_t* indices, size_t triangleCount, uint32_t vertexCount, std::vector<uint32_t>& offsets, std::vector<uint32_t>& entries) {
+    offsets.assign(static_cast<size_t>(vertexCount) + 1u, 0u);
+    entries.assign(triangleCount * 3u, 0u);
+    for (size_t k = 0; k < triangleCount * 3u; ++k) ++offsets[static_cast<size_t>(indices[k]) + 1u];
+    for (size_t v = 0; v < vertexCount; ++v) offsets[v + 1u] += offsets[v];
+    std::vector<uint32_t> next(offsets.begin(), offsets.end() - 1);
+    for (size_t t = 0; t < triangleCount; ++t) {
+        for (size_t c = 0; c < 3u; ++c) entries[next[indices[t * 3u + c]]++] = static_cast<uint32_t>(t);
+    }
 }
 
 void ValidateSceneGeometry(const SceneGeometry& g, GeometryCheck& out) {

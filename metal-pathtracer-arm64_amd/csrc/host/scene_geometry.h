@@ -13,7 +13,7 @@
 
 #include "bvh_builder.h"
 #include "ptr_abi.h"
-#include "ptr_deform.h"
+#include "ptr_deform_device.h"
 
 namespace ptr {
 
@@ -54,18 +54,28 @@ struct DynamicTables {
     std::vector<uint32_t> schedule, levelOffsets;   // BuildRefitSchedule
     std::vector<uint32_t> wideSource;       // BuildWideNodes' source table (empty without four-wide nodes)
     bool textured = false;
-    // Set by the caller before BuildSceneGeometry (PTR_DYNAMIC_DEFORMABLE / PTR_DYNAMIC_PRIMITIVES of include/ptr_deform.h): which of the
-    // tables below to fill.  The rest of this struct does not depend on it.
+    // Set by the caller before BuildSceneGeometry (PTR_DYNAMIC_DEFORMABLE / PTR_DYNAMIC_PRIMITIVES of include/ptr_deform.h,
+    // PTR_DYNAMIC_VERTEX_NORMALS of include/ptr_deform_device.h): which of the tables below to fill.  The rest of this struct does not depend on it.
     uint32_t flags = 0;
     std::vector<MeshBake> meshBakes;           // per mesh: what its localToWorld bakes to (a mesh without triangles: zeros)
     // deformable scenes
     std::vector<uint32_t> meshCorners;         // 3 per entry of meshTris, in its order: the vertex indices of that triangle
     std::vector<uint32_t> meshVertexCount;     // per mesh, as the description gave it
     std::vector<uint8_t> meshTangentsGiven;    // per mesh: the description carried tangents (kept or not)
+    // scenes that compute vertex normals: BuildVertexAdjacency of every mesh, one after the other.  Mesh m owns the row offsets
+    // adjOffsets[adjBase[m] .. adjBase[m + 1]) (its vertex count + 1 of them, counted from 0) and the entries adjEntries[3 meshTriOffsets[m] ..)
+    std::vector<uint32_t> adjOffsets, adjEntries;
+    std::vector<uint64_t> adjBase;             // meshCount + 1
     // scenes whose spheres and rectangles move
     std::vector<uint32_t> sphereLeaf;          // original sphere index -> leaf slot (the inverse of SceneGeometry::sphereInfo)
     std::vector<uint32_t> rectShadeKey;        // per rectangle: the shade key of its material, which the meta word of its triangles carries
 };
+
+// The vertex adjacency of one mesh, CSR by a counting sort over its index array: vertex v owns entries[offsets[v] .. offsets[v + 1]), one
+// per corner that names it, in ascending triangle order (a triangle that names v twice is there twice); an entry is the triangle's number.
+// This order is the order k_dyn_vertex_normals sums in (include/ptr_deform_device.h); it depends on the index array alone.  Indices must
+// be below vertexCount.
+void BuildVertexAdjacency(const uint32_t* indices, size_t triangleCount, uint32_t vertexCount, std::vector<uint32_t>& offsets, std::vector<uint32_t>& entries);
 
 // The rows of one rectangle and of one sphere, written by the upload (BuildSceneGeometry, the light table) and by ptr_scene_set_rects /
 // ptr_scene_set_spheres alike: one statement of their arithmetic.

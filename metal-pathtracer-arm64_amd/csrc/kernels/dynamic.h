@@ -1,6 +1,7 @@
 // Launchers of the dynamic-scene kernels (dynamic.hip; include/ptr_dynamic.h): re-bake the triangles of a moved mesh, refit the float
 // child boxes level by level, requantise the binary nodes and refill the four-wide ones; and, for include/ptr_deform.h, gather new vertex
-// data into the corner rows the bake reads and scatter the host-computed rows of moved spheres and rectangles.
+// data into the corner rows the bake reads and scatter the host-computed rows of moved spheres and rectangles; and, for
+// include/ptr_deform_device.h, check a caller's device arrays for non-finite components and compute vertex normals.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -43,6 +44,20 @@ struct DynVertexArrays {
 // triangles list[0 .. count) of one mesh: corners[3 i ..] are the vertex indices of list[i]; writes its object-space corner rows
 void launchDynGatherCorners(float4* dObjPos, float4* dObjNrm, float4* dObjTan, const DynVertexArrays& v, const uint32_t* dList, const uint32_t* dCorners,
                             uint32_t count, hipStream_t stream);
+
+// include/ptr_deform_device.h: the caller's arrays are read where they are, so their components are looked at on the device.  One row per
+// array, behind the mesh rows of the per-call mesh table: `count` floats at `data`; row r of a launch owns bit r of the flag words.
+struct alignas(16) DynCheckRow {
+    const float* data;
+    uint64_t count;
+};
+static_assert(sizeof(DynCheckRow) == 16u, "check row layout");
+// ORs bit r into dFlags (32 rows per word; cleared by the caller) when row r holds a non-finite float.  largest: the longest row.
+void launchDynCheckFinite(const DynCheckRow* dRows, uint32_t rows, uint64_t largest, uint32_t* dFlags, hipStream_t stream);
+// Area-weighted vertex normals of one mesh, one vertex per lane, by the rule of include/ptr_deform_device.h: offsets / entries are the
+// mesh's vertex adjacency (ptr::BuildVertexAdjacency), corners its corner table in the description's triangle order; packed float3 out.
+void launchDynVertexNormals(const float* dPositions, const uint32_t* dOffsets, const uint32_t* dEntries, const uint32_t* dCorners, float* dNormals,
+                            uint32_t vertexCount, hipStream_t stream);
 
 // The arrays ptr_scene_set_spheres / ptr_scene_set_rects scatter rows into, indexed by PTR_SCATTER_*: a destination word is
 // (array << kScatterArrayShift) | row, the row counted in float4.

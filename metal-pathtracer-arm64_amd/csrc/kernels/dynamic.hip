@@ -13,7 +13,12 @@
 // k_dyn_gather_corners  one triangle of a deformed mesh per lane: its three vertices, through the corner table, to the object-space rows
 //                       k_dyn_bake reads (4 B gather loads - packed float3 is only 4 B aligned - and 16 B stores).
 // k_dyn_scatter_rows    one 16 B row of a moved sphere or rectangle per lane, computed on the host, to the array it belongs to.
+// include/ptr_deform_device.h adds two that write nothing the renderer reads:
+// k_dyn_check_finite    a grid-stride pass over the caller's device arrays; a bit per array with a non-finite float, by atomic OR.
+// k_dyn_vertex_normals  one vertex per lane: area-weighted normals through the vertex adjacency, into scratch the gather then reads.
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 #include "bvh_grid.h"
 #include "bvh_layout.h"
@@ -157,6 +162,49 @@ __global__ void __launch_bounds__(kBlock) k_dyn_gather_corners(float4* __restric
     }
 }
 
+// include/ptr_deform_device.h.  One grid-stride pass over every array an update from device pointers will read: blockIdx.y names the row
+// of the table (an array: pointer and float count), the blocks of a row stride over its floats with coalesced 4 B loads (packed float3 is
+// only 4 B aligned).  Reads the caller's arrays, writes the flag words alone: at most one atomic OR per wave, and none on finite data.
+__global__ void __launch_bounds__(kBlock) k_dyn_check_finite(const DynCheckRow* __restrict__ rows, uint32_t rowBase, uint32_t* __restrict__ flags) {
+    const uint32_t r = rowBase + blockIdx.y;
+    const DynCheckRow row = rows[r];
+    bool bad = false;
+    const size_t stride = static_cast<size_t>(gridDim.x) * kBlock;
+    for (size_t i = static_cast<size_t>(blockIdx.x) * kBlock + threadIdx.x; i < row.count; i += stride) {
+        bad = bad || (__float_as_uint(row.data[i]) & 0x7F800000u) == 0x7F800000u;   // exponent all ones: infinite or NaN
+    }
+    if (__ballot(bad) != 0ull && (threadIdx.x & 63u) == 0u) atomicOr(&flags[r >> 5], 1u << (r & 31u));
+}
+
+// One vertex per lane: the sum of the cross products of the triangles that name it, in the adjacency's order (ascending triangle of the
+// description, so the sum does not depend on the tree), normalised by the bake's rule.  Unfused like everything here: the values are
+// tests/deform_device_ref.py's bit for bit.  Per vertex 8 B of row offsets read (4 B fresh) and 12 B written; per incident corner one 4 B
+// entry, three 4 B indices and nine 4 B position gathers - scattered, but a mesh's vertices and triangles that are close in the arrays
+// are close in space more often than not, and the arrays of one mesh stay in L2.
+__global__ void __launch_bounds__(kBlock) k_dyn_vertex_normals(const float* __restrict__ positions, const uint32_t* __restrict__ offsets,
+                                                               const uint32_t* __restrict__ entries, const uint32_t* __restrict__ corners,
+                                                               float* __restrict__ normals, uint32_t vertexCount) {
+    const uint32_t v = blockIdx.x * kBlock + threadIdx.x;
+    if (v >= vertexCount) return;
+    V3 s{0.0f, 0.0f, 0.0f};
+    const uint32_t end = offsets[v + 1u];
+    for (uint32_t e = offsets[v]; e < end; ++e) {
+        const size_t t = entries[e];
+        V3 p[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float* q = positions + static_cast<size_t>(corners[t * 3 + c]) * 3;
+            p[c] = {q[0], q[1], q[2]};
+        }
+        const V3 n = cross3(sub(p[1], p[0]), sub(p[2], p[0]));
+        s = {s.x + n.x, s.y + n.y, s.z + n.z};
+    }
+    const float d = dot3(s, s);
+    const V3 out = d > 0.0f ? scale(s, 1.0f / sqrtf(d)) : s;
+    float* dst = normals + static_cast<size_t>(v) * 3;
+    dst[0] = out.x, dst[1] = out.y, dst[2] = out.z;
+}
+
 // One 16 B row per lane: the rows of moved spheres and rectangles, computed on the host, to the arrays they belong to.
 __global__ void __launch_bounds__(kBlock) k_dyn_scatter_rows(DynScatterTargets t, const float4* __restrict__ rows, const uint32_t* __restrict__ dest,
                                                              uint32_t count) {
@@ -259,6 +307,22 @@ void launchDynBake(const DynBakeArrays& a, const float4* dMeshTable, uint32_t me
 void launchDynGatherCorners(float4* dObjPos, float4* dObjNrm, float4* dObjTan, const DynVertexArrays& v, const uint32_t* dList, const uint32_t* dCorners,
                             uint32_t count, hipStream_t stream) {
     if (count > 0u) hipLaunchKernelGGL(k_dyn_gather_corners, dim3(blocksFor(count)), dim3(kBlock), 0, stream, dObjPos, dObjNrm, dObjTan, v, dList, dCorners, count);
+}
+
+void launchDynCheckFinite(const DynCheckRow* dRows, uint32_t rows, uint64_t largest, uint32_t* dFlags, hipStream_t stream) {
+    // enough blocks per row for the longest one at a few floats per lane, and no more than fill the device a few times over
+    const uint32_t perRow = static_cast<uint32_t>(std::min<uint64_t>(std::max<uint64_t>((largest + kBlock * 4u - 1u) / (kBlock * 4u), 1u), 2048u));
+    constexpr uint32_t kMaxGridY = 65535u;
+    for (uint32_t base = 0; base < rows; base += kMaxGridY) {
+        hipLaunchKernelGGL(k_dyn_check_finite, dim3(perRow, std::min(rows - base, kMaxGridY)), dim3(kBlock), 0, stream, dRows, base, dFlags);
+    }
+}
+
+void launchDynVertexNormals(const float* dPositions, const uint32_t* dOffsets, const uint32_t* dEntries, const uint32_t* dCorners, float* dNormals,
+                            uint32_t vertexCount, hipStream_t stream) {
+    if (vertexCount > 0u) {
+        hipLaunchKernelGGL(k_dyn_vertex_normals, dim3(blocksFor(vertexCount)), dim3(kBlock), 0, stream, dPositions, dOffsets, dEntries, dCorners, dNormals, vertexCount);
+    }
 }
 
 void launchDynScatterRows(const DynScatterTargets& t, const float4* dRows, const uint32_t* dDest, uint32_t count, hipStream_t stream) {
