@@ -254,7 +254,48 @@ __device__ __forceinline__ f3 sampleGgxHalf(uint32_t& rng, float alpha, f3 n) {
     return normalize(frameToWorld(mk3(cosf(phi) * sinT, sinf(phi) * sinT, cosT), makeFrame(n)));
 }
 
+// Sine (x) and cosine (y) of an azimuth phi in [0, 2 pi], evaluated in double and rounded to float once.  A quadrant reduction and two
+// short Taylor polynomials (error 2e-14 on that range): no large-argument path, a dozen FP64 multiply-adds.  The result is the
+// correctly rounded float up to double rounding; a libm whose sinf / cosf err by little more than half an ulp, as the oracle's does,
+// returns the same float for nearly every argument - often, not always.
+// Out of line on purpose, and returning in registers: inlined, its doubles are alive at the point of highest register pressure of the
+// kernels that sample (k_connect_chain went from 4 waves per SIMD to 3, one k_tail_run from 2 to 1); as a call it costs those kernels
+// no register and no scratch (DESIGN.md has the table).
+__device__ __noinline__ float2 azimuthSinCos(float phi) {
+    const float kf = rintf(phi * 0.636619772f);   // the quadrant, 0..4: an integer, so any rounding of the product gives a valid one
+    const int q = static_cast<int>(kf);
+    double r = fma(static_cast<double>(kf), -1.5707963267948966, static_cast<double>(phi));
+    r = fma(static_cast<double>(kf), -6.123233995736766e-17, r);
+    const double r2 = r * r;
+    double sp = fma(r2, 1.6059043836821613e-10, -2.5052108385441720e-8);
+    sp = fma(r2, sp, 2.7557319223985893e-6);
+    sp = fma(r2, sp, -1.9841269841269841e-4);
+    sp = fma(r2, sp, 8.3333333333333332e-3);
+    sp = fma(r2, sp, -1.6666666666666666e-1);
+    const float sr = static_cast<float>(fma(r2 * r, sp, r));
+    double cp = fma(r2, -1.1470745597729725e-11, 2.0876756987868100e-9);
+    cp = fma(r2, cp, -2.7557319223985888e-7);
+    cp = fma(r2, cp, 2.4801587301587302e-5);
+    cp = fma(r2, cp, -1.3888888888888889e-3);
+    cp = fma(r2, cp, 4.1666666666666664e-2);
+    cp = fma(r2, cp, -0.5);
+    const float cr = static_cast<float>(fma(r2, cp, 1.0));
+    const float sq = (q & 1) ? cr : sr, cq = (q & 1) ? sr : cr;
+    return make_float2((q & 2) ? -sq : sq, ((q + 1) & 2) ? -cq : cq);
+}
+
 __device__ __forceinline__ f3 sampleGgxVndf(uint32_t& rng, float roughness, f3 n, f3 wo) {
+    // The two draws and the azimuth first, while nothing else of the function is live.  Sine and cosine come from azimuthSinCos, not
+    // from ocml's sinf / cosf: here, unlike in the other samplers, they enter the half vector at full size, and a narrow lobe turns
+    // their last bit into another value of D (at alpha^2 <= 1.6e-7 ggxD's denominator moves in steps of its own size).  With sinf /
+    // cosf the metals of roughness 1.1e-3 and 0.02 missed the oracle in 1 to 6 % of their samples (tests/test_gpu_bsdf_domain.py,
+    // group metal_narrow); DESIGN.md has what the change costs.
+    const float u1 = rngNext(rng);
+    const float u2 = rngNext(rng);
+    const float r = sqrtf(u1);
+    const float2 sc = azimuthSinCos(2.0f * kPi * u2);
+    const float t1r = r * sc.y;
+    const float t2r = r * sc.x;
     const float alpha = smax(roughness * roughness, 1.0e-4f);
     const Frame fr = makeFrame(n);
     const f3 won = normalize(wo);
@@ -264,12 +305,6 @@ __device__ __forceinline__ f3 sampleGgxVndf(uint32_t& rng, float roughness, f3 n
     const float lensq = vh.x * vh.x + vh.y * vh.y;
     const f3 t1 = lensq > 0.0f ? mk3(-vh.y, vh.x, 0.0f) / sqrtf(lensq) : mk3(1.0f, 0.0f, 0.0f);
     const f3 t2 = cross(vh, t1);
-    const float u1 = rngNext(rng);
-    const float u2 = rngNext(rng);
-    const float r = sqrtf(u1);
-    const float phi = 2.0f * kPi * u2;
-    const float t1r = r * cosf(phi);
-    const float t2r = r * sinf(phi);
     const float s = 0.5f * (1.0f + vh.z);
     const float t2a = (1.0f - s) * sqrtf(smax(0.0f, 1.0f - t1r * t1r)) + s * t2r;
     const float t3 = sqrtf(smax(0.0f, (1.0f - t1r * t1r) - t2a * t2a));
@@ -637,6 +672,10 @@ __device__ bool roughTransmission(const Mat& m, const PbrMetal& p, f3 n, f3 wo, 
     const float pdfWh = ggxVndfPdf(alpha, n, wo, wh);
     const float dwhDwi = fabsf((eta * eta * cosIWh) / smax(denomSq, 1.0e-8f));
     pdfTrans = pdfWh * dwhDwi;
+    // Not in the reference: with alpha at its floor 1e-4, alpha^2 - 1 rounds to -1 and D is a2 / 0 where wh == n to the last bit (a delta
+    // refraction at ior 1 and grazing wo, evaluated again: the 'grazing/lobe' class of tests/bsdf_domain.py).  The reference then hands
+    // out inf and NaN, which its firefly clamp drops; here the term is rejected, so nothing non-finite leaves the function.
+    if (!finite3(ft) || !isfinite(pdfTrans)) return false;
     return true;
 }
 

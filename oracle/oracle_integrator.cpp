@@ -1262,6 +1262,10 @@ bool roughTransmission(const PtrMaterial& m, const PbrMetal& p, V3 normal, V3 wo
     const float pdfWh = ggxVndfPdf(alpha, normal, wo, wh);
     const float dwhDwi = std::fabs((eta * eta * cosIWh) / std::max(denomSq, 1.0e-8f));
     pdfTrans = pdfWh * dwhDwi;
+    // Not in the reference: with alpha at its floor 1e-4, alpha^2 - 1 rounds to -1 and D is a2 / 0 where wh == n to the last bit (a delta
+    // refraction at ior 1 and grazing wo, evaluated again: the 'grazing/lobe' class of tests/bsdf_domain.py).  The reference then hands
+    // out inf and NaN, which its firefly clamp drops; here the term is rejected, so nothing non-finite leaves the function.
+    if (!finite3(ft) || !std::isfinite(pdfTrans)) return false;
     return true;
 }
 

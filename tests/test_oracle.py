@@ -253,11 +253,13 @@ def test_sample_bsdf_matches_eval_pdf_and_weight():
         assert (new_states != states).all() or mtype == 1
         d = out[ok, :3]
         assert np.allclose(np.linalg.norm(d, axis=1), 1.0, atol=1e-5)
-        if mtype in (0, 4, 5, 6, 7) or (mtype == 1 and mat.baseColorRoughness[3] > 1e-3):
+        # (materials.scene holds no type 7, so none ever reached this line; the identity below does not hold for type 7 in any case:
+        # test_bsdf_domain_host.py, which runs type-7 materials, says why)
+        if mtype in (0, 4, 5, 6) or (mtype == 1 and mat.baseColorRoughness[3] > 1e-3):
             nd = ~(out[ok, 7] > 0)
             ev = ol.eval_bsdf(mat, s, np.concatenate([pos[ok], normal[ok], wo[ok], d], axis=1))
             # weight = f * cos / pdf and pdf agrees with EvaluateBsdf's pdf for the sampled direction
-            if mtype in (0, 5, 4, 7):
+            if mtype in (0, 5, 4):
                 assert np.allclose(out[ok, 6][nd], ev[nd, 3], rtol=2e-3, atol=1e-6)
                 w = ev[nd, :3] * d[nd, 2:3] / ev[nd, 3:4]
                 assert np.allclose(out[ok, 3:6][nd], w, rtol=5e-3, atol=1e-5)
