@@ -545,6 +545,45 @@ _BACKGROUND_SIGNATURES = {
 }
 BACKGROUND_SYMBOLS = tuple(_BACKGROUND_SIGNATURES)
 
+# ... and of include/ptr_temporal.h (temporal accumulation for sequences): tests/test_temporal_host.py holds it against that header
+class PtrTemporalParams(C.Structure):
+    """include/ptr_temporal.h PtrTemporalParams; PtrTemporalParams.defaults() asks the library for its defaults."""
+    _fields_ = [("maxHistory", C.c_uint32), ("normalCos", C.c_float), ("planeTolerance", C.c_float), ("flags", C.c_uint32)]
+
+    @classmethod
+    def defaults(cls, **overrides) -> "PtrTemporalParams":
+        p = cls()
+        load_library().ptr_temporal_default_params(C.byref(p))
+        for k, v in overrides.items():
+            setattr(p, k, v)
+        return p
+
+
+class PtrTemporalInfo(C.Structure):
+    """include/ptr_temporal.h PtrTemporalInfo."""
+    _fields_ = [("frameIndex", C.c_uint32), ("hadHistory", C.c_uint32), ("surfaceMs", C.c_double), ("accumulateMs", C.c_double),
+                ("snapshotMs", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_}
+
+
+_temporal, _temporal_info = C.POINTER(PtrTemporalParams), C.POINTER(PtrTemporalInfo)
+_TEMPORAL_SIGNATURES = {
+    "ptr_temporal_default_params": (None, [_temporal]),
+    "ptr_temporal_check_params": (_int, [_temporal] + _err),
+    "ptr_temporal_create": (_int, [_vp, _u32, _u32, _temporal, C.POINTER(_vp)] + _err),
+    "ptr_temporal_release": (None, [_vp]),
+    "ptr_temporal_reset": (_int, [_vp]),
+    "ptr_temporal_step_device": (_int, [_vp, _settings, _vp, _vp, _vp, _vp, _vp, _vp, _temporal_info] + _err),
+    "ptr_temporal_step": (_int, [_vp, _settings, _fp, _fp, _fp, _fp, _fp, _temporal_info] + _err),
+    # its test-only probes
+    "ptr_debug_temporal_accumulate": (_int, [_u32, _u32, _temporal, _int, _fp, _fp, _fp, _fp, _fp, _fp, _int, _fp, _fp, _fp] + _err),
+    "ptr_debug_temporal_records": (_int, [_vp, _fp, _fp, _fp] + _err),
+    "ptr_debug_temporal_camera": (_int, [_settings, _fp]),
+}
+TEMPORAL_SYMBOLS = tuple(_TEMPORAL_SIGNATURES)
+
 # ptr_debug_scene_arrays / ptr_debug_dynamic_tables: name -> (selector, dtype, trailing shape)
 SCENE_ARRAYS = {"tris": (0, np.float32, (3, 4)), "triNormals": (1, np.float32, (3, 4)), "triUv": (2, np.float32, (4, 4)),
                 "triTangent": (3, np.float32, (3, 4)), "triBounds": (4, np.float32, (2, 4)), "sphereBounds": (5, np.float32, (2, 4)),
@@ -579,7 +618,7 @@ def load_library() -> C.CDLL:
     for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_POST_SIGNATURES.items()) + list(_STATS_SIGNATURES.items()) + \
             list(_ADAPTIVE_SIGNATURES.items()) + list(_MULTI_SIGNATURES.items()) + list(_FRAME_SIGNATURES.items()) + list(_MULTI_FRAME_SIGNATURES.items()) + \
             list(_DYNAMIC_SIGNATURES.items()) + list(_DEFORM_SIGNATURES.items()) + list(_DEFORM_DEVICE_SIGNATURES.items()) + \
-            list(_BACKGROUND_SIGNATURES.items()):
+            list(_BACKGROUND_SIGNATURES.items()) + list(_TEMPORAL_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -958,6 +997,13 @@ class DeviceScene:
         _check(load_library().ptr_frame_create(self._h, C.byref(settings), C.byref(h), err, len(err)), err)
         return Frame(h, keepalive=self)
 
+    def temporal(self, width: int, height: int, params: Optional["PtrTemporalParams"] = None) -> "Temporal":
+        """ptr_temporal_create: a temporal-accumulation handle for width x height frames of this scene (include/ptr_temporal.h)."""
+        h = C.c_void_p()
+        err = _err_buf()
+        _check(load_library().ptr_temporal_create(self._h, width, height, C.byref(params) if params is not None else None, C.byref(h), err, len(err)), err)
+        return Temporal(h, width, height, self._device, keepalive=self)
+
     def render_aovs(self, settings: PtrSettings, sample_index: int = 0) -> Tuple[np.ndarray, np.ndarray]:
         """First-hit feature buffers: ([H, W, 4] albedo rgb | hit flag, [H, W, 4] encoded normal | distance)."""
         albedo = np.zeros((settings.height, settings.width, 4), dtype=np.float32)
@@ -1180,6 +1226,123 @@ class Frame:
             self.close()
         except Exception:
             pass
+
+
+class Temporal:
+    """Temporal accumulation over the frames of a sequence (include/ptr_temporal.h): each step blends a frame with the history of the
+    surfaces it shows.  Made by DeviceScene.temporal(); the scene must be in the pose of the frame a step is given."""
+
+    def __init__(self, handle: C.c_void_p, width: int, height: int, device: int, keepalive=None):
+        self._h, self._keepalive = handle, keepalive
+        self.width, self.height, self._device = int(width), int(height), int(device)
+
+    def _handle(self):
+        if not self._h:
+            raise PtrError("the temporal handle is closed")
+        return self._h
+
+    def step(self, settings: PtrSettings, rgb: np.ndarray, want_length: bool = True, want_aovs: bool = False) -> dict:
+        """ptr_temporal_step on a host image [H, W, 3]: {"rgb", "info", and when asked for "length" [H, W], "albedo" and "normal" [H, W, 4]}."""
+        rgb = np.ascontiguousarray(rgb, np.float32)
+        if rgb.size != self.width * self.height * 3:
+            raise PtrError("Temporal.step: the image has %d floats, not %d x %d x 3" % (rgb.size, self.height, self.width))
+        h, w = self.height, self.width
+        out = {"rgb": np.zeros((h, w, 3), np.float32)}
+        if want_length:
+            out["length"] = np.zeros((h, w), np.float32)
+        if want_aovs:
+            out["albedo"], out["normal"] = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 4), np.float32)
+        opt = lambda key: _fptr(out[key]) if key in out else None
+        info = PtrTemporalInfo()
+        err = _err_buf()
+        _check(load_library().ptr_temporal_step(self._handle(), C.byref(settings), _fptr(rgb), _fptr(out["rgb"]), opt("length"), opt("albedo"),
+                                                opt("normal"), C.byref(info), err, len(err)), err)
+        out["info"] = info.as_dict()
+        return out
+
+    def step_device(self, settings: PtrSettings, rgb, out_rgb=None, out_length=None, out_albedo=None, out_normal=None, stream=None,
+                    want_info: bool = False) -> Optional[dict]:
+        """ptr_temporal_step_device on torch tensors of the scene's device, float32 and contiguous, passed by data_ptr(): rgb [H, W, 3];
+        out_rgb (None: rgb itself, filtered in place); out_length [H, W], out_albedo and out_normal [H, W, 4] may be None.  The step is
+        enqueued on `stream` (a raw stream handle; None: torch's current stream of the scene's device) and the call returns at once,
+        unless want_info: then it waits and returns PtrTemporalInfo as a dict."""
+        if out_rgb is None:
+            out_rgb = rgb
+        pixels = self.width * self.height
+        ptrs = []
+        for name, t, floats in (("rgb", rgb, 3), ("out_rgb", out_rgb, 3), ("out_length", out_length, 1), ("out_albedo", out_albedo, 4),
+                                ("out_normal", out_normal, 4)):
+            if t is None:
+                ptrs.append(None)
+                continue
+            device = getattr(t, "device", None)
+            if not hasattr(t, "data_ptr") or device is None:
+                raise PtrError("Temporal.step_device: %s is not a torch tensor" % name)
+            if device.type != "cuda" or device.index != self._device:
+                raise PtrError("Temporal.step_device: %s is on %s, not on device %d of the scene" % (name, device, self._device))
+            if str(t.dtype) != "torch.float32" or not t.is_contiguous() or t.numel() != pixels * floats:
+                raise PtrError("Temporal.step_device: %s must be contiguous float32 with %d elements" % (name, pixels * floats))
+            ptrs.append(C.c_void_p(t.data_ptr()))
+        if stream is None:
+            import torch   # (only here: the module itself does not need torch)
+
+            stream = torch.cuda.current_stream(self._device).cuda_stream
+        info = PtrTemporalInfo()
+        err = _err_buf()
+        _check(load_library().ptr_temporal_step_device(self._handle(), C.byref(settings), *ptrs, C.c_void_p(stream),
+                                                       C.byref(info) if want_info else None, err, len(err)), err)
+        return info.as_dict() if want_info else None
+
+    def records(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """ptr_debug_temporal_records: R0, R1, R2 of the last step, [H, W, 4] float32 each."""
+        out = [np.zeros((self.height, self.width, 4), np.float32) for _ in range(3)]
+        err = _err_buf()
+        _check(load_library().ptr_debug_temporal_records(self._handle(), *map(_fptr, out), err, len(err)), err)
+        return tuple(out)
+
+    def reset(self) -> None:
+        """ptr_temporal_reset: the next step is a first step."""
+        load_library().ptr_temporal_reset(self._handle())
+
+    def close(self) -> None:
+        if self._h:
+            load_library().ptr_temporal_release(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def debug_temporal_camera(settings: PtrSettings) -> np.ndarray:
+    """ptr_debug_temporal_camera: [4, 3] origin, lowerLeft, horizontal, vertical of the renderer's camera."""
+    out = np.zeros((4, 3), np.float32)
+    if load_library().ptr_debug_temporal_camera(C.byref(settings), _fptr(out)) != 0:
+        raise PtrError("ptr_debug_temporal_camera failed")
+    return out
+
+
+def debug_temporal_accumulate(rgb: np.ndarray, cur_records, prev_records, history: np.ndarray, cam_cur, cam_prev,
+                              params: Optional[PtrTemporalParams] = None, has_history: bool = True, device: int = 0):
+    """ptr_debug_temporal_accumulate: k_temporal_accumulate alone.  rgb [H, W, 3]; cur_records (R0, R1, R2) and prev_records (R0, R1) of
+    [H, W, 4]; history [H, W, 4]; cameras [4, 3].  Returns (rgb [H, W, 3], length [H, W], history [H, W, 4])."""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    h, w = rgb.shape[:2]
+    cur = np.ascontiguousarray(np.stack([np.asarray(r, np.float32).reshape(h, w, 4) for r in cur_records]))
+    prev = np.ascontiguousarray(np.stack([np.asarray(r, np.float32).reshape(h, w, 4) for r in prev_records]))
+    history = np.ascontiguousarray(history, np.float32).reshape(h, w, 4)
+    cams = [np.ascontiguousarray(c, np.float32).reshape(12) for c in (cam_cur, cam_prev)]
+    if len(cur) != 3 or len(prev) != 2:
+        raise PtrError("debug_temporal_accumulate: three current and two previous records")
+    p = params if params is not None else PtrTemporalParams.defaults()
+    out, length, hist = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32), np.zeros((h, w, 4), np.float32)
+    err = _err_buf()
+    _check(load_library().ptr_debug_temporal_accumulate(w, h, C.byref(p), int(has_history), _fptr(rgb), _fptr(cur), _fptr(prev), _fptr(history),
+                                                        _fptr(cams[0]), _fptr(cams[1]), device, _fptr(out), _fptr(length), _fptr(hist), err,
+                                                        len(err)), err)
+    return out, length, hist
 
 
 def debug_frame(samples: np.ndarray, device: int = 0) -> Frame:

@@ -60,6 +60,12 @@ void launchTraceRays(const SceneView& sc, const float4* dRays, uint64_t n, bool 
 void launchAovs(const RenderParams& rp, const SceneView& sc, uint32_t sample, float4* dAlbedo, float4* dNormal, const LaunchConfig& cfg,
                 hipStream_t stream);
 
+// The surface records of a temporal step (include/ptr_temporal.h) for every pixel of the frame: dR0, dR1, dR2, and the two buffers of
+// launchAovs (sample 0) when dAlbedo / dNormal are not null.  dPrevTris / dPrevSpheres: the rows of the previous pose, laid out like
+// sc.tris / sc.spheres (which they may be).
+void launchSurface(const RenderParams& rp, const SceneView& sc, const float4* dPrevTris, const float4* dPrevSpheres, float4* dR0, float4* dR1,
+                   float4* dR2, float4* dAlbedo, float4* dNormal, const LaunchConfig& cfg, hipStream_t stream);
+
 // ---- tests only: debug / known-answer kernels (ptr_debug.h) ----
 // evaluate and sample a material for a batch of inputs
 void launchDebugEvalBsdf(const float4* dMaterial, const RenderParams& rp, const float* dIn, uint64_t n, float* dOut,

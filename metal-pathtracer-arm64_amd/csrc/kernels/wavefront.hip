@@ -2345,6 +2345,71 @@ __global__ void __launch_bounds__(kTraceBlock) k_aovs(RenderParams rp, SceneView
 }
 
 // =====================================================================================================
+// k_surface: the per-pixel surface records of a temporal step (include/ptr_temporal.h, where every field is defined).  The camera ray
+// of sample 0 - k_aovs' trace, and its two buffers with the same bits when asked for - and three records per pixel:
+//   R0 = (X, bits(id))   R1 = (unit normal of k_aovs' rule, t)   R2 = (Xprev, bits(hit word))
+// X is the hit point interpolated from the rows the traversal tested, Xprev the same expression with the same barycentrics (or the same
+// sphere point) on prevTris / prevSpheres, the rows of the previous step's pose in the same leaf order.  Where the two sets of rows hold
+// the same values - nothing moved, or the caller passes sc.tris / sc.spheres themselves - X and Xprev are the same bits.
+// =====================================================================================================
+__global__ void __launch_bounds__(kTraceBlock) k_surface(RenderParams rp, SceneView sc, const float4* prevTris, const float4* prevSpheres, float4* r0,
+                                                          float4* r1, float4* r2, float4* albedo, float4* normal, uint32_t* spill,
+                                                          uint32_t spillStride) {
+    __shared__ uint32_t ldsStack[kLdsStackLevels * kTraceBlock];
+    const uint32_t gtid = blockIdx.x * kTraceBlock + threadIdx.x;
+    LaneStack stack = laneStack(ldsStack, spill, spillStride, sc);
+    TraceCounters cnt{0u, 0u};
+    const uint32_t pixels = rp.width * rp.height;
+    for (uint32_t pixel = gtid; pixel < pixels; pixel += gridDim.x * kTraceBlock) {
+        uint32_t rng;
+        f3 org, dir;
+        beginSample(rp, pixel, 0u, rng, org, dir);
+        const TraceHit h = traverse<false, false>(sc, org, dir, kEps, INFINITY, stack, cnt);
+        float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n = make_float4(0.5f, 0.5f, 0.5f, 0.0f);
+        float4 q0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q1 = q0, q2 = mk4(mk3(0.0f), __uint_as_float(kHitMiss));
+        if (h.prim != kHitMiss) {
+            const Surface sf = reconstruct(sc, org, dir, h.t, h.prim);
+            f3 sn = sf.hitShadingNormal;
+            if (dot(sn, sn) <= 0.0f) sn = sf.normal;
+            if (sc.materialCount > 0u) {
+                const Mat mat{sc.materials + static_cast<size_t>(min(sf.material, sc.materialCount - 1u)) * kMaterialVec4};
+                if (mat.type() == 2u) sn = sf.normal;
+                a = mk4(mat.baseColor(), 1.0f);
+            }
+            sn = normalize(sn);
+            if (sc.materialCount > 0u) n = mk4(sn * 0.5f + mk3(0.5f), h.t);
+            f3 x, xPrev;
+            if (h.prim & kHitSphereBit) {
+                const uint32_t idx = h.prim & ~kHitSphereBit;
+                const float4 s = sc.spheres[idx], p = prevSpheres[idx];
+                const f3 fromCentre = sf.position - mk3(s);
+                x = mk3(s) + fromCentre * (s.w / s.w);
+                xPrev = mk3(p) + fromCentre * (p.w / s.w);
+            } else {
+                const uint32_t triOffset = h.prim * 48u;
+                const float4* tp = byteOffset(sc.tris, triOffset);
+                const float4* pp = byteOffset(prevTris, triOffset);
+                const float4 a0 = tp[0], a1 = tp[1], a2 = tp[2];
+                const float4 p0 = pp[0], p1 = pp[1], p2 = pp[2];
+                float u, v;
+                triangleUv(mk3(a0), mk3(a1), mk3(a2), org, dir, u, v);
+                x = (mk3(a0) - u * mk3(a1)) + v * mk3(a2);
+                xPrev = (mk3(p0) - u * mk3(p1)) + v * mk3(p2);
+            }
+            const uint32_t index = sf.primType == 0u ? sf.geomIndex : sf.primIndex;
+            q0 = mk4(x, __uint_as_float(sf.primType << 30 | index));
+            q1 = mk4(sn, h.t);
+            q2 = mk4(xPrev, __uint_as_float(h.prim));
+        }
+        r0[pixel] = q0;
+        r1[pixel] = q1;
+        r2[pixel] = q2;
+        if (albedo) albedo[pixel] = a;
+        if (normal) normal[pixel] = n;
+    }
+}
+
+// =====================================================================================================
 // k_trace_rays: ray-batch queries for ptr_trace_rays (parity tests against the oracle ray caster)
 // =====================================================================================================
 // The PtrHit of a traced ray: t (-1: miss, 0: an any-hit query found something), and for a closest hit the primitive, the barycentrics
@@ -2868,6 +2933,13 @@ void launchAovs(const RenderParams& rp, const SceneView& sc, uint32_t sample, fl
                 hipStream_t stream) {
     const TraceLaunch t = traceLaunch(cfgIn, rp.width * rp.height);
     hipLaunchKernelGGL(k_aovs, dim3(t.grid), dim3(kTraceBlock), 0, stream, rp, sc, sample, dAlbedo, dNormal, t.cfg.spill, t.stride);
+}
+
+void launchSurface(const RenderParams& rp, const SceneView& sc, const float4* dPrevTris, const float4* dPrevSpheres, float4* dR0, float4* dR1,
+                   float4* dR2, float4* dAlbedo, float4* dNormal, const LaunchConfig& cfgIn, hipStream_t stream) {
+    const TraceLaunch t = traceLaunch(cfgIn, rp.width * rp.height);
+    hipLaunchKernelGGL(k_surface, dim3(t.grid), dim3(kTraceBlock), 0, stream, rp, sc, dPrevTris, dPrevSpheres, dR0, dR1, dR2, dAlbedo, dNormal,
+                       t.cfg.spill, t.stride);
 }
 
 // ---- tests only: the probes ----
