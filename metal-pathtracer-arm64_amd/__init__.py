@@ -353,6 +353,12 @@ _SIGNATURES = {
 DEBUG_SYMBOLS = tuple(name for name in _SIGNATURES if name.startswith("ptr_debug_"))
 ABI_SYMBOLS = tuple(name for name in _SIGNATURES if name not in DEBUG_SYMBOLS)
 
+# ... of include/ptr_debug_pbr.h (the per-hit material probe), a table of its own: tests/test_pbr_hit_host.py holds it against that header
+_PBR_HIT_SIGNATURES = {
+    "ptr_debug_pbr_hits": (_int, [_vp, _fp, _u64, _fp] + _err),
+}
+PBR_HIT_SYMBOLS = tuple(_PBR_HIT_SIGNATURES)
+
 # ... and of include/ptr_post.h (the denoiser), a table of its own: tests/test_post_host.py holds it against that header
 _denoise = C.POINTER(PtrDenoiseParams)
 _POST_SIGNATURES = {
@@ -618,7 +624,7 @@ def load_library() -> C.CDLL:
     for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_POST_SIGNATURES.items()) + list(_STATS_SIGNATURES.items()) + \
             list(_ADAPTIVE_SIGNATURES.items()) + list(_MULTI_SIGNATURES.items()) + list(_FRAME_SIGNATURES.items()) + list(_MULTI_FRAME_SIGNATURES.items()) + \
             list(_DYNAMIC_SIGNATURES.items()) + list(_DEFORM_SIGNATURES.items()) + list(_DEFORM_DEVICE_SIGNATURES.items()) + \
-            list(_BACKGROUND_SIGNATURES.items()) + list(_TEMPORAL_SIGNATURES.items()):
+            list(_BACKGROUND_SIGNATURES.items()) + list(_TEMPORAL_SIGNATURES.items()) + list(_PBR_HIT_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -1044,6 +1050,45 @@ class DeviceScene:
         res = {k: out[:, v] for k, v in self.FIRST_HIT_FIELDS.items()}
         res["raw"] = out
         return res
+
+    # field -> (columns, dtype) of the rows of ptr_debug_pbr_hits (include/ptr_debug_pbr.h); the oracle's oracle_pbr_hits reports the same rows
+    PBR_HIT_FIELDS = {"hit": (0, np.float32), "t": (1, np.float32), "mesh": (2, np.uint32), "triangle": (3, np.uint32), "bu": (4, np.float32),
+                      "bv": (5, np.float32), "front_face": (6, np.float32), "geometric_normal": (slice(7, 10), np.float32),
+                      "hit_normal": (slice(10, 13), np.float32), "textured": (13, np.float32), "base_color": (slice(14, 17), np.float32),
+                      "roughness": (17, np.float32), "emissive": (slice(18, 21), np.float32), "metallic": (21, np.float32),
+                      "transmission": (22, np.float32), "occlusion": (23, np.float32), "normal": (slice(24, 27), np.float32),
+                      "two_sided": (27, np.float32), "discard": (28, np.float32), "state": (29, np.uint32), "basis": (30, np.uint32)}
+
+    @staticmethod
+    def pbr_hit_rows(rays, cones, states, materials=None, instantiation=0, grads=None, valid=None) -> np.ndarray:
+        """The [n, 20] input rows of ptr_debug_pbr_hits: rays [n, 6] {origin, direction}, cones [n, 2] {width, spread}, random states [n],
+        material indices [n] (None: the hit's own), the instantiation (0 / 1, a scalar or [n]), grads [n, 8] and valid bits [n]."""
+        rays = np.asarray(rays, dtype=np.float32).reshape(-1, 6)
+        n = rays.shape[0]
+        rows = np.zeros((n, 20), dtype=np.float32)
+        words = rows.view(np.uint32)
+        rows[:, 0:6] = rays
+        rows[:, 6:8] = np.asarray(cones, dtype=np.float32).reshape(-1, 2)
+        words[:, 8] = np.asarray(states, dtype=np.uint32)
+        words[:, 9] = 0xFFFFFFFF if materials is None else np.asarray(materials, dtype=np.uint32)
+        words[:, 10] = np.asarray(instantiation, dtype=np.uint32)
+        if grads is not None:
+            rows[:, 11:19] = np.asarray(grads, dtype=np.float32).reshape(-1, 8)
+        if valid is not None:
+            words[:, 19] = np.asarray(valid, dtype=np.uint32)
+        return rows
+
+    @classmethod
+    def pbr_hit_fields(cls, out: np.ndarray) -> dict:
+        words = out.view(np.uint32)
+        res = {k: (words if dt == np.uint32 else out)[:, cols] for k, (cols, dt) in cls.PBR_HIT_FIELDS.items()}
+        res["raw"] = out
+        return res
+
+    def pbr_hits(self, rows: np.ndarray) -> dict:
+        """ptr_debug_pbr_hits: the per-hit material of the textured metallic-roughness model (applyPbrTextures) at the closest hit of
+        the rays of rows [n, 20] (pbr_hit_rows).  Returns PBR_HIT_FIELDS -> arrays, plus "raw" [n, 32]."""
+        return self.pbr_hit_fields(_batch(load_library().ptr_debug_pbr_hits, (self._h,), rows, np.float32, 20, [((32,), np.float32)]))
 
     def env_lookup(self, settings: PtrSettings, dir_roughness: np.ndarray) -> np.ndarray:
         """ptr_debug_env_lookup: the PTR_METAL_ENV_LOD lookup of the scene's environment map with the settings' rotation and intensity:

@@ -9,6 +9,7 @@
 #include "device_scene.h"
 #include "ptr_background.h"
 #include "ptr_debug.h"
+#include "ptr_debug_pbr.h"
 
 using namespace ptrk;
 using namespace ptrhost;
@@ -122,6 +123,17 @@ int ptr_debug_first_hit_textures(PtrDeviceScene* scene, const PtrSettings* setti
         dout.ensure(n * kFloats);
         launchDebugFirstHit(rp, scene->view, dxy.ptr, n, dout.ptr, coldLaunchConfig(*scene), nullptr);
         dout.download(out, n * kFloats);
+    });
+}
+
+int ptr_debug_pbr_hits(PtrDeviceScene* scene, const float* in, uint64_t n, float* out, char* err, size_t err_cap) {
+    return deviceCall("ptr_debug_pbr_hits", scene, scene && (in || !n) && (out || !n), err, err_cap, [&] {
+        if (n == 0) return;
+        DeviceBuffer<float> din, dout;
+        din.upload(in, n * 20);
+        dout.ensure(n * 32);
+        launchDebugPbrHits(scene->view, din.ptr, n, dout.ptr, coldLaunchConfig(*scene), nullptr);
+        dout.download(out, n * 32);
     });
 }
 

@@ -85,6 +85,9 @@ void launchDebugTexSample(const SceneView& sc, uint32_t texture, const float* dI
 void launchDebugTexSampleGrad(const SceneView& sc, uint32_t texture, const float* dIn, uint64_t n, float4* dOut, hipStream_t stream);
 void launchDebugFirstHit(const RenderParams& rp, const SceneView& sc, const uint32_t* dXys, uint64_t n, float* dOut, const LaunchConfig& cfg,
                          hipStream_t stream);
+// ptr_debug_pbr_hits: applyPbrTextures at the closest hit of n rays with each row's own cone, random state, material and instantiation
+// (in n x 20, out n x 32 words)
+void launchDebugPbrHits(const SceneView& sc, const float* dIn, uint64_t n, float* dOut, const LaunchConfig& cfg, hipStream_t stream);
 // ptr_debug_extend_rays: k_extend's hit words (dHits, n) of the rays dRays (n x 2 float4) as PtrHit records
 void launchDebugHitRecords(const SceneView& sc, const float4* dRays, const float2* dHits, uint64_t n, uint32_t triCount, uint32_t sphereCount,
                            PtrHit* dOut, hipStream_t stream);

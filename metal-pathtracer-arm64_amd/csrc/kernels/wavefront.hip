@@ -906,7 +906,8 @@ __device__ __forceinline__ UvGrads noUvGrads() {
 // lookups of every other hit (!RD, grads ignored) compile to the ray-cone code alone and keep its registers.
 template <bool RD>
 __device__ __forceinline__ bool applyPbrTextures(const SceneView& sc, const Surface& sf, uint32_t materialIndex, const Mat& mat, f3 wo, float2 cone,
-                                                 float hitDistance, const UvGrads& grads, uint32_t& rng, PbrHit& out) {
+                                                 float hitDistance, const UvGrads& grads, uint32_t& rng, PbrHit& out, uint32_t* basisOut = nullptr) {
+    if (basisOut) *basisOut = 0u;   // (k_debug_pbr_hits only: which basis the normal map took)
     const float4* mt = sc.materialTex + static_cast<size_t>(materialIndex) * kMaterialTexVec4;
     const float4 idx0 = mt[12], idx1 = mt[13], pbrParams = mt[14], pbrExtras = mt[15];
     const uint32_t texBase = __float_as_uint(idx0.x), texOrm = __float_as_uint(idx0.y), texNormal = __float_as_uint(idx0.z),
@@ -995,14 +996,16 @@ __device__ __forceinline__ bool applyPbrTextures(const SceneView& sc, const Surf
             const float len2 = dot(tw, tw);
             tw = (finite3(tw) && len2 > 1.0e-12f) ? tw * (1.0f / sqrtf(len2)) : mk3(1.0f, 0.0f, 0.0f);
             if (fabsf(tsign) > 0.5f) {
-                t = tw - shadingNormal * dot(shadingNormal, tw);
+                // (the projection is normalised and then tested, as the reference has it: only one that vanishes is refused, and a
+                // tangent a milliradian from the normal still gives its own basis)
+                t = normalize(tw - shadingNormal * dot(shadingNormal, tw));
                 if (finite3(t) && dot(t, t) > 1.0e-6f) {
-                    t = normalize(t);
                     bt = normalize(cross(shadingNormal, t)) * (tsign < 0.0f ? -1.0f : 1.0f);
                     hasBasis = finite3(bt) && dot(bt, bt) > 1.0e-6f;
                 }
             }
         }
+        const bool vertexBasis = hasBasis;
         if (!hasBasis) {
             // compute_tangent_basis_from_uv (:843-911) in world space: the triangle's edges and the UV deltas of the normal map's set
             const float4* tp = sc.tris + static_cast<size_t>(sf.prim) * 3u;
@@ -1020,9 +1023,8 @@ __device__ __forceinline__ bool applyPbrTextures(const SceneView& sc, const Surf
                 if (finite3(tangentW) && tl > 1.0e-12f && finite3(bitangentW) && bl > 1.0e-12f) {
                     tangentW = tangentW * (1.0f / sqrtf(tl));
                     bitangentW = bitangentW * (1.0f / sqrtf(bl));
-                    t = tangentW - shadingNormal * dot(shadingNormal, tangentW);
+                    t = normalize(tangentW - shadingNormal * dot(shadingNormal, tangentW));
                     if (finite3(t) && dot(t, t) > 1.0e-6f) {
-                        t = normalize(t);
                         const float handed = dot(cross(shadingNormal, t), bitangentW) < 0.0f ? -1.0f : 1.0f;
                         bt = normalize(cross(shadingNormal, t)) * (handed * (per.z < 0.0f ? -1.0f : 1.0f));   // x sign of det(localToWorld), as the reference has it
                         hasBasis = true;
@@ -1030,13 +1032,19 @@ __device__ __forceinline__ bool applyPbrTextures(const SceneView& sc, const Surf
                 }
             }
         }
+        if (basisOut) *basisOut = vertexBasis ? 1u : (hasBasis ? 2u : 3u);
         if (!hasBasis) {   // build_onb (:934-940)
             const f3 up = fabsf(shadingNormal.z) < 0.999f ? mk3(0.0f, 0.0f, 1.0f) : mk3(1.0f, 0.0f, 0.0f);
             t = normalize(cross(up, shadingNormal));
             bt = cross(shadingNormal, t);
         }
         f3 mapped = normalize((t * nts.x + bt * nts.y) + shadingNormal * nts.z);
-        if (dot(mapped, sf.normal) < 0.0f) mapped = -mapped;
+        // (rec.normal of the reference is turned towards the ray, set_face_normal :1183-1193: a back-face hit keeps the mapped normal on
+        // the viewer's side)
+        if (dot(mapped, sf.frontFace ? sf.normal : -sf.normal) < 0.0f) {
+            mapped = -mapped;
+            if (basisOut) *basisOut |= 4u;
+        }
         shadingNormal = mapped;
         // shortened (filtered) normals widen the lobe (:6348-6388)
         float tok = smax((1.0f - normalLength) / smax(normalLength, 1.0e-6f), 0.0f);
@@ -2625,6 +2633,65 @@ __global__ void __launch_bounds__(kTraceBlock) k_debug_first_hit(RenderParams rp
     }
 }
 
+// The per-hit material of the textured model at the closest hit of each ray (ptr_debug_pbr.h ptr_debug_pbr_hits: in n x 20, out n x 32 words):
+// the cone, the random state, the material and the instantiation (with its gradients) are the row's own
+constexpr uint32_t kPbrHitIn = 20u, kPbrHitOut = 32u;
+__global__ void __launch_bounds__(kTraceBlock) k_debug_pbr_hits(SceneView sc, const float* in, uint64_t n, float* out, uint32_t* spill, uint32_t spillStride) {
+    __shared__ uint32_t ldsStack[kLdsStackLevels * kTraceBlock];
+    const uint32_t gtid = blockIdx.x * kTraceBlock + threadIdx.x;
+    LaneStack stack = laneStack(ldsStack, spill, spillStride, sc);
+    TraceCounters cnt{0u, 0u};
+    for (uint64_t i = gtid; i < n; i += static_cast<uint64_t>(gridDim.x) * kTraceBlock) {
+        const float* r = in + i * kPbrHitIn;
+        float* o = out + i * kPbrHitOut;
+        for (uint32_t k = 0; k < kPbrHitOut; ++k) o[k] = 0.0f;
+        const f3 org = ld3(r), dir = ld3(r + 3);
+        uint32_t rng = __float_as_uint(r[8]);
+        o[29] = __uint_as_float(rng);
+        const TraceHit h = traverse<false, false>(sc, org, dir, kEps, INFINITY, stack, cnt);
+        if (h.prim == kHitMiss) continue;
+        const Surface sf = reconstruct(sc, org, dir, h.t, h.prim);
+        const PtrHit ph = ptrHitOf(sc, org, dir, h, false);
+        o[0] = 1.0f;
+        o[1] = h.t;
+        o[2] = __uint_as_float(ph.geomIndex);
+        o[3] = __uint_as_float(ph.primIndex);
+        o[4] = sf.bu; o[5] = sf.bv;
+        o[6] = sf.frontFace ? 1.0f : 0.0f;
+        o[7] = sf.normal.x; o[8] = sf.normal.y; o[9] = sf.normal.z;
+        o[10] = sf.hitShadingNormal.x; o[11] = sf.hitShadingNormal.y; o[12] = sf.hitShadingNormal.z;
+        if (sc.materialCount == 0u) continue;
+        const uint32_t wanted = __float_as_uint(r[9]);
+        const uint32_t materialIndex = min(wanted == 0xFFFFFFFFu ? sf.material : wanted, sc.materialCount - 1u);
+        const Mat mat{byteOffset(sc.materials, materialIndex * (kMaterialVec4 * 16u))};
+        if (!(mat.type() == 7u && sf.primType == 0u && sc.textureCount > 0u && sc.triUv != nullptr)) continue;
+        o[13] = 1.0f;
+        const float2 cone = make_float2(r[6], r[7]);
+        const f3 wo = -normalize(dir);
+        PbrHit hit;
+        uint32_t basis = 0u;
+        bool discard;
+        if (__float_as_uint(r[10]) != 0u) {
+            UvGrads grads;
+            grads.set[0] = make_float4(r[11], r[12], r[13], r[14]);
+            grads.set[1] = make_float4(r[15], r[16], r[17], r[18]);
+            grads.valid = __float_as_uint(r[19]) & 3u;
+            discard = applyPbrTextures<true>(sc, sf, materialIndex, mat, wo, cone, h.t, grads, rng, hit, &basis);
+        } else {
+            discard = applyPbrTextures<false>(sc, sf, materialIndex, mat, wo, cone, h.t, noUvGrads(), rng, hit, &basis);
+        }
+        o[29] = __uint_as_float(rng);
+        o[28] = discard ? 1.0f : 0.0f;
+        if (discard) continue;
+        o[14] = hit.ov[0].x; o[15] = hit.ov[0].y; o[16] = hit.ov[0].z; o[17] = hit.ov[0].w;
+        o[18] = hit.ov[1].x; o[19] = hit.ov[1].y; o[20] = hit.ov[1].z;
+        o[21] = hit.ov[2].x; o[22] = hit.ov[2].y; o[23] = hit.ov[2].z;
+        o[24] = hit.shadingNormal.x; o[25] = hit.shadingNormal.y; o[26] = hit.shadingNormal.z;
+        o[27] = hit.twoSided ? 1.0f : 0.0f;
+        o[30] = __uint_as_float(basis);
+    }
+}
+
 // closest hit + surface reconstruction + next-ray origin, the pieces k_shade builds a bounce from (tests of a13 / a14)
 __global__ void __launch_bounds__(kTraceBlock) k_debug_surface(SceneView sc, const float* in, uint64_t n, float* out, uint32_t* spill, uint32_t spillStride) {
     __shared__ uint32_t ldsStack[kLdsStackLevels * kTraceBlock];
@@ -2974,6 +3041,11 @@ void launchDebugFirstHit(const RenderParams& rp, const SceneView& sc, const uint
                          hipStream_t stream) {
     const TraceLaunch t = traceLaunch(cfgIn, n);
     hipLaunchKernelGGL(k_debug_first_hit, dim3(t.grid), dim3(kTraceBlock), 0, stream, rp, sc, dXys, n, dOut, t.cfg.spill, t.stride);
+}
+
+void launchDebugPbrHits(const SceneView& sc, const float* dIn, uint64_t n, float* dOut, const LaunchConfig& cfgIn, hipStream_t stream) {
+    const TraceLaunch t = traceLaunch(cfgIn, n);
+    hipLaunchKernelGGL(k_debug_pbr_hits, dim3(t.grid), dim3(kTraceBlock), 0, stream, sc, dIn, n, dOut, t.cfg.spill, t.stride);
 }
 
 void launchDebugHitRecords(const SceneView& sc, const float4* dRays, const float2* dHits, uint64_t n, uint32_t triCount, uint32_t sphereCount,

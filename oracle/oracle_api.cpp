@@ -261,4 +261,7 @@ void oracle_light_connection(const OracleScene* s, const PtrSettings* settings, 
     lightConnectionBatch(s->scene, s->desc, *settings, in, n, out);
 }
 
+// The per-hit material of the textured model at the closest hit of each ray (oracle_integrator.h pbrHitsBatch): in n * 20, out n * 32 words
+void oracle_pbr_hits(const OracleScene* s, const float* in, uint64_t n, float* out) { pbrHitsBatch(s->scene, s->desc, in, n, out); }
+
 }  // extern "C"

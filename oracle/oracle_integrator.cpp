@@ -2012,7 +2012,9 @@ static float triangleUvPerWorld(V3 edge1, V3 edge2, float du1, float dv1, float 
 // The per-hit material of the textured model (M:5919-6400).  `material` is the hit's own copy and is modified in place;
 // returns true when the alpha test discards the hit.
 static bool applyPbrTextures(const Scene& scene, const std::vector<OracleTexture>& textures, const HitInfo& hit, PtrMaterial& material, V3 wo,
-                             float coneWidth, float coneSpread, float hitDistance, Rng& rng, V3& shadingNormalOut, bool& twoSidedOut) {
+                             float coneWidth, float coneSpread, float hitDistance, Rng& rng, V3& shadingNormalOut, bool& twoSidedOut,
+                             uint32_t* basisOut = nullptr) {
+    if (basisOut) *basisOut = 0u;   // (pbrHitsBatch: which basis the normal map took)
     const Geom& g = scene.geoms[hit.geom];
     const uint32_t base = hit.primitiveIndex * 3u;
     const uint32_t i0 = g.indices[base], i1 = g.indices[base + 1u], i2 = g.indices[base + 2u];
@@ -2094,14 +2096,14 @@ static bool applyPbrTextures(const Scene& scene, const std::vector<OracleTexture
             const float len2 = dot(tw, tw);
             tw = (finite3(tw) && len2 > 1.0e-12f) ? tw * (1.0f / std::sqrt(len2)) : V3(1.0f, 0.0f, 0.0f);
             if (std::fabs(tsign) > 0.5f) {
-                t = tw - shadingNormal * dot(shadingNormal, tw);
+                t = normalize(tw - shadingNormal * dot(shadingNormal, tw));   // normalised, then tested (M:6325-6326)
                 if (finite3(t) && dot(t, t) > 1.0e-6f) {
-                    t = normalize(t);
                     bt = normalize(cross(shadingNormal, t)) * (tsign < 0.0f ? -1.0f : 1.0f);
                     hasBasis = finite3(bt) && dot(bt, bt) > 1.0e-6f;
                 }
             }
         }
+        uint32_t basis = hasBasis ? 1u : 3u;
         if (!hasBasis) {   // M:843-911, in world space
             const bool set1 = uvSetOf[2] != 0u;
             const float* q0 = set1 ? a1 : a0;
@@ -2125,12 +2127,12 @@ static bool applyPbrTextures(const Scene& scene, const std::vector<OracleTexture
                 if (finite3(tangentW) && tl > 1.0e-12f && finite3(bitangentW) && bl > 1.0e-12f) {
                     tangentW = tangentW * (1.0f / std::sqrt(tl));
                     bitangentW = bitangentW * (1.0f / std::sqrt(bl));
-                    t = tangentW - shadingNormal * dot(shadingNormal, tangentW);
+                    t = normalize(tangentW - shadingNormal * dot(shadingNormal, tangentW));   // (M:903-906)
                     if (finite3(t) && dot(t, t) > 1.0e-6f) {
-                        t = normalize(t);
                         const float handed = dot(cross(shadingNormal, t), bitangentW) < 0.0f ? -1.0f : 1.0f;
                         bt = normalize(cross(shadingNormal, t)) * (handed * (g.detSign < 0.0f ? -1.0f : 1.0f));
                         hasBasis = true;
+                        basis = 2u;
                     }
                 }
             }
@@ -2141,7 +2143,11 @@ static bool applyPbrTextures(const Scene& scene, const std::vector<OracleTexture
             bt = cross(shadingNormal, t);
         }
         V3 mapped = normalize((t * nts.x + bt * nts.y) + shadingNormal * nts.z);
-        if (dot(mapped, hit.normal) < 0.0f) mapped = -mapped;
+        if (dot(mapped, hit.frontFace ? hit.normal : -hit.normal) < 0.0f) {   // rec.normal faces the ray (M:1183-1193, 6353)
+            mapped = -mapped;
+            basis |= 4u;
+        }
+        if (basisOut) *basisOut = basis;
         shadingNormal = mapped;
         const float tok = std::max((1.0f - normalLength) / std::max(normalLength, 1.0e-6f), 0.0f);   // M:6348-6388 without the gradient term
         roughness = clampf(std::sqrt(roughness * roughness + tok), 0.0f, 1.0f);
@@ -2770,6 +2776,57 @@ void rectLightNeeBatch(const Scene& scene, const PtrSceneDesc& desc, const PtrSe
             }
         }
         outStates[i] = rng.state;
+    }
+}
+
+void pbrHitsBatch(const Scene& scene, const PtrSceneDesc& desc, const float* in, uint64_t n, float* out) {
+    const std::vector<OracleTexture> textures = buildTextures(desc);
+    auto word = [](float f) {
+        uint32_t u;
+        std::memcpy(&u, &f, 4);
+        return u;
+    };
+    auto put = [](float* o, uint32_t u) { std::memcpy(o, &u, 4); };
+    for (uint64_t i = 0; i < n; ++i) {
+        const float* r = in + i * kPbrHitIn;
+        float* o = out + i * kPbrHitOut;
+        std::memset(o, 0, kPbrHitOut * sizeof(float));
+        Rng rng;
+        rng.state = word(r[8]);
+        put(o + 29, rng.state);
+        HitInfo hit;
+        const Ray ray{V3(r), V3(r + 3)};
+        if (!intersectScene(scene, ray, hit)) continue;
+        o[0] = 1.0f;
+        o[1] = hit.t;
+        put(o + 2, hit.geomIndex);
+        put(o + 3, hit.primitiveIndex);
+        o[4] = hit.bu, o[5] = hit.bv;
+        o[6] = hit.frontFace ? 1.0f : 0.0f;
+        o[7] = hit.normal.x, o[8] = hit.normal.y, o[9] = hit.normal.z;
+        o[10] = hit.shadingNormal.x, o[11] = hit.shadingNormal.y, o[12] = hit.shadingNormal.z;
+        if (!desc.materials || desc.materialCount == 0u) continue;
+        const uint32_t wanted = word(r[9]);
+        const uint32_t materialIndex = std::min(wanted == 0xFFFFFFFFu ? hit.materialIndex : wanted, desc.materialCount - 1u);
+        PtrMaterial material = desc.materials[materialIndex];
+        if (!(matType(material) == 7u && hit.primitiveType == GeomType::Mesh && !textures.empty() && !scene.geoms[hit.geom].positions.empty())) continue;   // as render()
+        o[13] = 1.0f;
+        V3 mapped;
+        bool twoSided = false;
+        uint32_t basis = 0u;
+        const bool discard = applyPbrTextures(scene, textures, hit, material, -normalize(ray.direction), r[6], r[7], hit.t, rng, mapped, twoSided, &basis);
+        put(o + 29, rng.state);
+        o[28] = discard ? 1.0f : 0.0f;
+        if (discard) continue;
+        o[14] = material.baseColorRoughness[0], o[15] = material.baseColorRoughness[1], o[16] = material.baseColorRoughness[2];
+        o[17] = material.baseColorRoughness[3];
+        o[18] = material.emission[0], o[19] = material.emission[1], o[20] = material.emission[2];
+        o[21] = material.pbrParams[0];
+        o[22] = material.pbrExtras[2];
+        std::memcpy(o + 23, &material.materialPad[0], 4);
+        o[24] = mapped.x, o[25] = mapped.y, o[26] = mapped.z;
+        o[27] = twoSided ? 1.0f : 0.0f;
+        put(o + 30, basis);
     }
 }
 

@@ -148,6 +148,12 @@ void rectLightNeeBatch(const Scene& scene, const PtrSceneDesc& desc, const PtrSe
 constexpr uint32_t kLightConnectionFloats = 12;
 void lightConnectionBatch(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& settings, const float* in, uint64_t n, float* out);
 
+// pbrHitsBatch: the per-hit material of the textured metallic-roughness model (applyPbrTextures) at the closest hit of each ray, row for
+// row what ptr_debug_pbr_hits (include/ptr_debug_pbr.h) takes and reports; no gradient path here: the instantiation and the gradients of a
+// row are ignored.
+constexpr uint32_t kPbrHitIn = 20, kPbrHitOut = 32;
+void pbrHitsBatch(const Scene& scene, const PtrSceneDesc& desc, const float* in, uint64_t n, float* out);
+
 // Renders pixels with y in [y0, y1) (full width); out_rgb is the full W*H*3 image, other rows untouched.
 // out_signature / out_marginal (optional, W*H each): path signature of every pixel's last sample and whether one of its
 // rectangle-light shadow tests is decided within rounding noise of the ray length (deterministic-stream diagnostics).

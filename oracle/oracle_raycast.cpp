@@ -157,6 +157,12 @@ void Scene::build(const PtrSceneDesc& desc) {
     rects = desc.rects;
     rectCount = desc.rectCount;
 
+    // a scene is textured when it has textures and some mesh has a uv set; every mesh of it then carries texture attributes, zeros
+    // where it has none of its own (what the HIP upload bakes, and what the shader reads from such vertices)
+    bool texturedScene = false;
+    if (desc.textures && desc.textureCount > 0) {
+        for (uint32_t mi = 0; mi < desc.meshCount; ++mi) texturedScene = texturedScene || desc.meshes[mi].uv0 || desc.meshes[mi].uv1;
+    }
     for (uint32_t mi = 0; mi < desc.meshCount; ++mi) {
         const PtrMeshDesc& mesh = desc.meshes[mi];
         if (mesh.vertexCount == 0 || mesh.indexCount == 0) continue;
@@ -185,7 +191,7 @@ void Scene::build(const PtrSceneDesc& desc) {
                            l2w.m[1][0] * (l2w.m[0][1] * l2w.m[2][2] - l2w.m[2][1] * l2w.m[0][2]) +
                            l2w.m[2][0] * (l2w.m[0][1] * l2w.m[1][2] - l2w.m[1][1] * l2w.m[0][2]);
         g.detSign = det3 < 0.0f ? -1.0f : 1.0f;
-        if (mesh.uv0 || mesh.uv1) {
+        if (texturedScene) {
             g.positions = positions;
             g.uv0.assign(static_cast<size_t>(mesh.vertexCount) * 2, 0.0f);
             g.uv1.assign(static_cast<size_t>(mesh.vertexCount) * 2, 0.0f);

@@ -48,6 +48,7 @@ def lib():
         l.oracle_env_eval.restype = C.c_int
         l.oracle_rect_light_nee.argtypes = [vp, C.POINTER(pt.PtrSettings), C.POINTER(pt.PtrMaterial), fp, fp, up, u64, fp, up]
         l.oracle_light_connection.argtypes = [vp, C.POINTER(pt.PtrSettings), fp, u64, fp]
+        l.oracle_pbr_hits.argtypes = [vp, fp, u64, fp]
         _lib = l
     return _lib
 
@@ -135,6 +136,14 @@ class OracleScene:
         res = {k: out[:, v] for k, v in self.CONNECTION_FIELDS.items()}
         res["raw"] = out
         return res
+
+    def pbr_hits(self, rows):
+        """The oracle's applyPbrTextures at the closest hit of the rays of rows [n, 20] (pt.DeviceScene.pbr_hit_rows; no gradient path: the
+        instantiation and the gradients are ignored): the fields of pt.DeviceScene.PBR_HIT_FIELDS, plus "raw" [n, 32]."""
+        rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, 20)
+        out = np.zeros((rows.shape[0], 32), dtype=np.float32)
+        lib().oracle_pbr_hits(self._h, _f(rows), rows.shape[0], _f(out))
+        return pt.DeviceScene.pbr_hit_fields(out)
 
     def close(self):
         if self._h:

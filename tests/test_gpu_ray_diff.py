@@ -1,6 +1,6 @@
 """GPU tests of the first-hit ray differentials of the textured Metal path (PTR_METAL_RAY_DIFF, include/ptr_abi.h bit 8).
 
-The scenes are built here from numpy arrays: quads with known vertices and uvs and small generated textures.  The restatements of the
+The scenes are built from numpy arrays (the builder of tests/pbr_hit_domain.py): quads with known vertices and uvs and small generated textures.  The restatements of the
 rule are in this file: the gradients in float64 and the anisotropic filter of csrc/kernels/texture.h in float32.  The filter reads a mip
 chain taken from ptr_debug_env_mips, which uses the same chain rule.
 """
@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+import pbr_hit_domain as D
 
 pt = importlib.import_module("metal-pathtracer-arm64_amd")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -49,81 +50,9 @@ def _settings(tmp_path, **kw):
     return _with(s, **kw)
 
 
-class Texture:
-    def __init__(self, rgba, wrap_s=0, wrap_t=0, linear=True):
-        self.rgba = np.ascontiguousarray(rgba, dtype=np.float32)
-        self.wrap_s, self.wrap_t, self.linear = wrap_s, wrap_t, linear
-        self.levels = pt.debug_env_mips(self.rgba)   # the material-texture chain rule
-
-
-def _pbr_material(base=(1.0, 1.0, 1.0), roughness=1.0, emission=(0.0, 0.0, 0.0), textures=None, uv_sets=None, transforms=None,
-                  normal_scale=1.0):
-    m = pt.PtrMaterial()
-    m.baseColorRoughness[:] = [base[0], base[1], base[2], roughness]
-    m.typeEta[:] = [7.0, 1.5, 1.0, 0.0]   # metallic-roughness, double-sided
-    m.emission[:] = [emission[0], emission[1], emission[2], 0.0]
-    m.carpaintBaseTint[:] = [1.0, 1.0, 1.0, 0.0]
-    m.textureIndices0[:] = [NO_TEX] * 4
-    m.textureIndices1[:] = [NO_TEX] * 4
-    for slot, tex in (textures or {}).items():   # slots: 0 base, 1 orm, 2 normal, 3 occlusion, 4 emissive, 5 transmission
-        if slot < 4:
-            m.textureIndices0[slot] = tex
-        else:
-            m.textureIndices1[slot - 4] = tex
-    for slot, uv_set in (uv_sets or {}).items():
-        if slot < 4:
-            m.textureUvSet0[slot] = uv_set
-        else:
-            m.textureUvSet1[slot - 4] = uv_set
-    for k in range(6):
-        rows = (transforms or {}).get(k, ((1.0, 0.0, 0.0), (0.0, 1.0, 0.0)))
-        m.textureTransform[2 * k][:] = [rows[0][0], rows[0][1], rows[0][2], 0.0]
-        m.textureTransform[2 * k + 1][:] = [rows[1][0], rows[1][1], rows[1][2], 0.0]
-    m.pbrParams[:] = [0.0, roughness, 1.0, normal_scale]
-    m.pbrExtras[:] = [1.0, 0.5, 0.0, 0.0]
-    return m
-
-
-class Scene:
-    """A PtrSceneDesc of triangle meshes {positions [n, 3], indices [m, 3], uv0 [n, 2], uv1 [n, 2], material} and textures."""
-
-    def __init__(self, meshes, materials, textures):
-        self._keep = []
-        keep = self._keep.append
-        self.textures = textures
-        self.meshes = meshes
-        desc = pt.PtrSceneDesc()
-        mats = (pt.PtrMaterial * len(materials))(*materials)
-        keep(mats)
-        descs = (pt.PtrMeshDesc * len(meshes))()
-        for i, mesh in enumerate(meshes):
-            pos = np.ascontiguousarray(mesh["positions"], dtype=np.float32)
-            idx = np.ascontiguousarray(mesh["indices"], dtype=np.uint32)
-            nrm = np.ascontiguousarray(np.broadcast_to(np.array([0.0, 1.0, 0.0], np.float32), pos.shape))
-            uv0 = np.ascontiguousarray(mesh["uv0"], dtype=np.float32)
-            uv1 = np.ascontiguousarray(mesh.get("uv1", mesh["uv0"]), dtype=np.float32)
-            keep((pos, idx, nrm, uv0, uv1))
-            d = descs[i]
-            d.positions = pos.ctypes.data_as(C.POINTER(C.c_float))
-            d.normals = nrm.ctypes.data_as(C.POINTER(C.c_float))
-            d.indices = idx.ctypes.data_as(C.POINTER(C.c_uint32))
-            d.vertexCount, d.indexCount = pos.shape[0], idx.size
-            d.localToWorld[:] = [1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 0.0, 1.0]
-            d.materialIndex = mesh["material"]
-            d.uv0 = uv0.ctypes.data_as(C.POINTER(C.c_float))
-            d.uv1 = uv1.ctypes.data_as(C.POINTER(C.c_float))
-        keep(descs)
-        texs = (pt.PtrTexture * len(textures))()
-        for i, t in enumerate(textures):
-            texs[i].rgba = t.rgba.ctypes.data_as(C.POINTER(C.c_float))
-            texs[i].width, texs[i].height = t.rgba.shape[1], t.rgba.shape[0]
-            texs[i].wrapS, texs[i].wrapT, texs[i].filter = t.wrap_s, t.wrap_t, 1 if t.linear else 0
-        keep(texs)
-        desc.materials, desc.materialCount = mats, len(materials)
-        desc.meshes, desc.meshCount = descs, len(meshes)
-        desc.textures, desc.textureCount = texs, len(textures)
-        self.desc = desc
-        self.dev = pt.DeviceScene(desc, 0, keepalive=self)
+# The scene builder is shared with the per-hit material classes (tests/pbr_hit_domain.py), which extend it with normals, tangents and
+# localToWorld
+Texture, Scene, _pbr_material = D.Texture, D.Scene, D.pbr_material
 
 
 def _ground(x0, x1, z0, z1, uv_of, material=0, uv1_of=None):
