@@ -359,6 +359,34 @@ _PBR_HIT_SIGNATURES = {
 }
 PBR_HIT_SYMBOLS = tuple(_PBR_HIT_SIGNATURES)
 
+# ... of include/ptr_debug_sss.h (the random-walk subsurface probes), a table of its own: tests/test_sss_walk_host.py holds it against that header
+_SSS_WALK_SIGNATURES = {
+    "ptr_debug_sss_walk_begin": (_int, [_material, _settings, _fp, _up, _u64, _fp, _up] + _err),
+    "ptr_debug_sss_walk_step": (_int, [_material, _settings, _fp, _up, _u64, _fp, _up] + _err),
+    "ptr_debug_sss_walks": (_int, [_vp, _settings, _up, _u64, _u32, _fp, _fp] + _err),
+}
+SSS_WALK_SYMBOLS = tuple(_SSS_WALK_SIGNATURES)
+# columns of their rows (the oracle's oracle_sss_* report the same rows); "u:" marks a uint32 word
+SSS_BEGIN_FIELDS = {"outcome": 0, "direction": slice(1, 4), "weight": slice(4, 7), "pdf": 7, "is_delta": 8, "position": slice(9, 12)}
+SSS_STEP_IN_FIELDS = {"position": slice(0, 3), "direction": slice(3, 6), "throughput": slice(6, 9), "u:step": 9, "hit": 10, "t": 11,
+                      "point": slice(12, 15), "normal": slice(15, 18)}
+SSS_STEP_FIELDS = {"outcome": 0, "position": slice(1, 4), "direction": slice(4, 7), "throughput": slice(7, 10), "u:step": 10,
+                   "exit_direction": slice(11, 14), "exit_weight": slice(14, 17), "exit_pdf": 17, "has_exit": 18, "exit_point": slice(19, 22)}
+SSS_WALK_STEP_FIELDS = dict(SSS_STEP_IN_FIELDS, **{"u:state_before": 18, "outcome": 19, "u:state_after": 20})
+SSS_WALK_FINAL_FIELDS = {"first_hit": 0, "started": 1, "queries": 2, "outcome": 3, "goes_on": 4, "next_origin": slice(5, 8),
+                         "next_direction": slice(8, 11), "throughput": slice(11, 14), "u:state": 14, "escapes": 15, "unsupported": 16,
+                         "parked_normal": slice(17, 20), "u:camera_state": 20}
+SSS_MAX_STEPS = 64   # PTR_SSS_MAX_STEPS
+
+
+def sss_fields(rows: np.ndarray, fields: dict) -> dict:
+    """name -> columns of [..., k] float32 rows of the random-walk probes (a "u:" field as uint32, without the mark), and the rows themselves as "raw"."""
+    words = rows.view(np.uint32)
+    res = {k[2:] if k.startswith("u:") else k: (words if k.startswith("u:") else rows)[..., v] for k, v in fields.items()}
+    res["raw"] = rows
+    return res
+
+
 # ... and of include/ptr_post.h (the denoiser), a table of its own: tests/test_post_host.py holds it against that header
 _denoise = C.POINTER(PtrDenoiseParams)
 _POST_SIGNATURES = {
@@ -624,7 +652,8 @@ def load_library() -> C.CDLL:
     for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_POST_SIGNATURES.items()) + list(_STATS_SIGNATURES.items()) + \
             list(_ADAPTIVE_SIGNATURES.items()) + list(_MULTI_SIGNATURES.items()) + list(_FRAME_SIGNATURES.items()) + list(_MULTI_FRAME_SIGNATURES.items()) + \
             list(_DYNAMIC_SIGNATURES.items()) + list(_DEFORM_SIGNATURES.items()) + list(_DEFORM_DEVICE_SIGNATURES.items()) + \
-            list(_BACKGROUND_SIGNATURES.items()) + list(_TEMPORAL_SIGNATURES.items()) + list(_PBR_HIT_SIGNATURES.items()):
+            list(_BACKGROUND_SIGNATURES.items()) + list(_TEMPORAL_SIGNATURES.items()) + list(_PBR_HIT_SIGNATURES.items()) + \
+            list(_SSS_WALK_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -1089,6 +1118,18 @@ class DeviceScene:
         """ptr_debug_pbr_hits: the per-hit material of the textured metallic-roughness model (applyPbrTextures) at the closest hit of
         the rays of rows [n, 20] (pbr_hit_rows).  Returns PBR_HIT_FIELDS -> arrays, plus "raw" [n, 32]."""
         return self.pbr_hit_fields(_batch(load_library().ptr_debug_pbr_hits, (self._h,), rows, np.float32, 20, [((32,), np.float32)]))
+
+    def sss_walks(self, settings: PtrSettings, xys: np.ndarray, step_cap: int = SSS_MAX_STEPS):
+        """ptr_debug_sss_walks: the first bounce of the camera samples xys [n, 3] {x, y, sample} with its whole subsurface random walk, by
+        the device code shadeSlot calls (include/ptr_debug_sss.h; meaningful only on scenes without lights and sampled environment).
+        Returns (SSS_WALK_STEP_FIELDS -> [n, step_cap, ..] arrays, SSS_WALK_FINAL_FIELDS -> [n, ..] arrays), each with its "raw" rows."""
+        xys = np.ascontiguousarray(xys, dtype=np.uint32).reshape(-1, 3)
+        steps = np.zeros((xys.shape[0], step_cap, 24), dtype=np.float32)
+        final = np.zeros((xys.shape[0], 24), dtype=np.float32)
+        err = _err_buf()
+        _check(load_library().ptr_debug_sss_walks(self._h, C.byref(settings), _uptr(xys), xys.shape[0], step_cap, _fptr(steps), _fptr(final),
+                                                  err, len(err)), err)
+        return sss_fields(steps, SSS_WALK_STEP_FIELDS), sss_fields(final, SSS_WALK_FINAL_FIELDS)
 
     def env_lookup(self, settings: PtrSettings, dir_roughness: np.ndarray) -> np.ndarray:
         """ptr_debug_env_lookup: the PTR_METAL_ENV_LOD lookup of the scene's environment map with the settings' rotation and intensity:
@@ -1786,6 +1827,22 @@ def debug_sample_lobes(material: PtrMaterial, settings: PtrSettings, inputs: np.
                                      [((3,), np.float32), ((8,), np.float32), ((), np.uint32)], more=(_uptr(front), _uptr(states)),
                                      tail=(C.byref(env_rough),))
     return out, sample, out_states, float(env_rough.value)
+
+
+def debug_sss_walk_begin(material: PtrMaterial, settings: PtrSettings, inputs: np.ndarray, states: np.ndarray):
+    """ptr_debug_sss_walk_begin: sssWalkBegin on inputs [n, 12] {point, entry normal, wo, incident} with random states [n]:
+    ([n, 16] rows of SSS_BEGIN_FIELDS, the states afterwards)."""
+    states = np.ascontiguousarray(states, dtype=np.uint32)
+    return _batch(load_library().ptr_debug_sss_walk_begin, (C.byref(material), C.byref(settings)), inputs, np.float32, 12,
+                  [((16,), np.float32), ((), np.uint32)], more=(_uptr(states),))
+
+
+def debug_sss_walk_step(material: PtrMaterial, settings: PtrSettings, rows: np.ndarray, states: np.ndarray):
+    """ptr_debug_sss_walk_step: sssWalkStep with maxSteps = settings.sssMaxSteps on rows [n, 20] (SSS_STEP_IN_FIELDS) with random states
+    [n]: ([n, 24] rows of SSS_STEP_FIELDS, the states afterwards)."""
+    states = np.ascontiguousarray(states, dtype=np.uint32)
+    return _batch(load_library().ptr_debug_sss_walk_step, (C.byref(material), C.byref(settings)), rows, np.float32, 20,
+                  [((24,), np.float32), ((), np.uint32)], more=(_uptr(states),))
 
 
 def debug_env_mips(rgba: np.ndarray):

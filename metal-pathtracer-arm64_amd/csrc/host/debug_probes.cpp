@@ -10,6 +10,7 @@
 #include "ptr_background.h"
 #include "ptr_debug.h"
 #include "ptr_debug_pbr.h"
+#include "ptr_debug_sss.h"
 
 using namespace ptrk;
 using namespace ptrhost;
@@ -477,6 +478,87 @@ int ptr_debug_light_connection(PtrDeviceScene* scene, const PtrSettings* setting
         dout.ensure(n * 12);
         launchDebugLightConnection(rp, scene->view, din.ptr, n, dout.ptr, nullptr);
         dout.download(out, n * 12);
+    });
+}
+
+// ---- the random-walk subsurface path (ptr_debug_sss.h) ----
+// what all three refuse before any launch
+static int sssProbeRefusal(const char* who, bool argsOk, const PtrSettings* settings, uint64_t n, char* err, size_t err_cap) {
+    if (!argsOk) return nullArgument(who, err, err_cap);
+    if (n == 0) return refuse(err, err_cap, std::string(who) + ": n == 0");
+    if (settings->sssMaxSteps > PTR_SSS_MAX_STEPS) return refuse(err, err_cap, std::string(who) + ": sssMaxSteps > 64");
+    return 0;
+}
+
+int ptr_debug_sss_walk_begin(const PtrMaterial* material, const PtrSettings* settings, const float* in, const uint32_t* rng_states, uint64_t n,
+                             float* out, uint32_t* out_states, char* err, size_t err_cap) {
+    const bool argsOk = material && settings && in && rng_states && out && out_states;
+    if (const int rc = sssProbeRefusal("ptr_debug_sss_walk_begin", argsOk, settings, n, err, err_cap)) return rc;
+    return deviceCall("ptr_debug_sss_walk_begin", nullptr, argsOk, err, err_cap, [&] {
+        BsdfProbe probe(*material, *settings);
+        DeviceBuffer<float> din, dout;
+        DeviceBuffer<uint32_t> drng, drngOut;
+        din.upload(in, n * PTR_SSS_BEGIN_IN);
+        drng.upload(rng_states, n);
+        dout.ensure(n * PTR_SSS_BEGIN_OUT);
+        drngOut.ensure(n);
+        launchDebugSssBegin(probe.material.ptr, probe.rp, din.ptr, drng.ptr, n, dout.ptr, drngOut.ptr, nullptr);
+        dout.download(out, n * PTR_SSS_BEGIN_OUT);
+        drngOut.download(out_states, n);
+    });
+}
+
+int ptr_debug_sss_walk_step(const PtrMaterial* material, const PtrSettings* settings, const float* in, const uint32_t* rng_states, uint64_t n,
+                            float* out, uint32_t* out_states, char* err, size_t err_cap) {
+    const bool argsOk = material && settings && in && rng_states && out && out_states;
+    if (const int rc = sssProbeRefusal("ptr_debug_sss_walk_step", argsOk, settings, n, err, err_cap)) return rc;
+    return deviceCall("ptr_debug_sss_walk_step", nullptr, argsOk, err, err_cap, [&] {
+        BsdfProbe probe(*material, *settings);
+        DeviceBuffer<float> din, dout;
+        DeviceBuffer<uint32_t> drng, drngOut;
+        din.upload(in, n * PTR_SSS_STEP_IN);
+        drng.upload(rng_states, n);
+        dout.ensure(n * PTR_SSS_STEP_OUT);
+        drngOut.ensure(n);
+        // (the limit as the settings state it, not the render's max(., 1): the function's own clamp is part of what is tested)
+        launchDebugSssStep(probe.material.ptr, settings->sssMaxSteps, din.ptr, drng.ptr, n, dout.ptr, drngOut.ptr, nullptr);
+        dout.download(out, n * PTR_SSS_STEP_OUT);
+        drngOut.download(out_states, n);
+    });
+}
+
+int ptr_debug_sss_walks(PtrDeviceScene* scene, const PtrSettings* settings, const uint32_t* xys, uint64_t n, uint32_t step_cap, float* out_steps,
+                        float* out_final, char* err, size_t err_cap) {
+    const bool argsOk = scene && settings && xys && out_steps && out_final;
+    if (const int rc = sssProbeRefusal("ptr_debug_sss_walks", argsOk, settings, n, err, err_cap)) return rc;
+    if (step_cap == 0u || step_cap > PTR_SSS_MAX_STEPS) return refuse(err, err_cap, "ptr_debug_sss_walks: step_cap must be 1..64");
+    for (uint64_t i = 0; i < n; ++i) {
+        if (xys[i * 3] >= settings->width || xys[i * 3 + 1] >= settings->height) {
+            return refuse(err, err_cap, "ptr_debug_sss_walks: sample " + std::to_string(i) + " is outside the image");
+        }
+    }
+    return deviceCall("ptr_debug_sss_walks", scene, argsOk, err, err_cap, [&] {
+        RenderParams rp;
+        fillRenderParams(*settings, 1, rp);
+        DeviceBuffer<uint32_t> dxy;
+        DeviceBuffer<float> dsteps, dfinal;
+        dxy.upload(xys, n * 3);
+        dsteps.ensure(n * step_cap * PTR_SSS_WALK_STEP);
+        dfinal.ensure(n * PTR_SSS_WALK_FINAL);
+        HIP_CHECK(hipMemset(dsteps.ptr, 0, n * step_cap * PTR_SSS_WALK_STEP * sizeof(float)));
+        DeviceBuffer<float> dstate, drows, dstepOut;
+        DeviceBuffer<uint32_t> drowRng, drowMaterial, dstepRng;
+        dstate.ensure(n * kSssWalkStateWords);
+        drows.ensure(n * PTR_SSS_STEP_IN);
+        dstepOut.ensure(n * PTR_SSS_STEP_OUT);
+        drowRng.ensure(n);
+        drowMaterial.ensure(n);
+        dstepRng.ensure(n);
+        const SssWalkScratch scratch{dstate.ptr, drows.ptr, drowRng.ptr, drowMaterial.ptr, dstepOut.ptr, dstepRng.ptr};
+        launchDebugSssWalks(rp, scene->view, dxy.ptr, n, step_cap, dsteps.ptr, dfinal.ptr, scratch, coldLaunchConfig(*scene), nullptr);
+        HIP_CHECK(hipDeviceSynchronize());
+        dsteps.download(out_steps, n * step_cap * PTR_SSS_WALK_STEP);
+        dfinal.download(out_final, n * PTR_SSS_WALK_FINAL);
     });
 }
 

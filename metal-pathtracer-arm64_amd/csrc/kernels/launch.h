@@ -103,5 +103,24 @@ void launchDebugRectLightNee(const RenderParams& rp, const SceneView& sc, const 
                              const float* dThr, const uint32_t* dRng, uint64_t n, float4* dHead, uint32_t* dRngOut, const LaunchConfig& cfg,
                              hipStream_t stream);
 void launchDebugLightConnection(const RenderParams& rp, const SceneView& sc, const float* dIn, uint64_t n, float* dOut, hipStream_t stream);
+// The random-walk subsurface path (ptr_debug_sss.h): sssWalkBegin (in n x 12, out n x 16), sssWalkStep with the step limit as given (in n x
+// 20, out n x 24 words), and the first bounce of n camera samples with its whole walk (dSteps n x stepCap x 24, dFinal n x 24 words)
+void launchDebugSssBegin(const float4* dMaterial, const RenderParams& rp, const float* dIn, const uint32_t* dRng, uint64_t n, float* dOut,
+                         uint32_t* dRngOut, hipStream_t stream);
+void launchDebugSssStep(const float4* dMaterial, uint32_t maxSteps, const float* dIn, const uint32_t* dRng, uint64_t n, float* dOut, uint32_t* dRngOut,
+                        hipStream_t stream);
+// (scratch of the whole walk, per sample: the record of kSssWalkStateWords words, the step probe's row of 20 words, random state and
+// material index in, and its 24 words and random state out)
+constexpr uint32_t kSssWalkStateWords = 48;
+struct SssWalkScratch {
+    float* state;
+    float* rows;
+    uint32_t* rowRng;
+    uint32_t* rowMaterial;
+    float* stepOut;
+    uint32_t* stepRng;
+};
+void launchDebugSssWalks(const RenderParams& rp, const SceneView& sc, const uint32_t* dXys, uint64_t n, uint32_t stepCap, float* dSteps, float* dFinal,
+                         const SssWalkScratch& scratch, const LaunchConfig& cfg, hipStream_t stream);
 
 }  // namespace ptrk

@@ -2692,6 +2692,265 @@ __global__ void __launch_bounds__(kTraceBlock) k_debug_pbr_hits(SceneView sc, co
     }
 }
 
+// ---- the random-walk subsurface path (ptr_debug_sss.h): sssWalkBegin, sssWalkStep, and the whole walk as shadeSlot runs it ----
+// METAL: the instantiation launchShade picks (shadeVariant().sss); the two functions themselves are no templates.
+// flatten: the two function probes inline their calls, so that they add no caller to the out-of-line copies of sssWalkBegin / sssWalkStep
+// that the render's kernels share.  With -ffp-contract=off an inlined copy performs the same IEEE operations: the probes answer bit for
+// bit what the render computes.
+constexpr uint32_t kSssBeginIn = 12u, kSssBeginOut = 16u, kSssStepIn = 20u, kSssStepOut = 24u, kSssWalkStep = 24u, kSssWalkFinal = 24u;
+template <bool METAL>
+__global__ void __attribute__((flatten)) k_debug_sss_begin(const float4* material, RenderParams rp, const float* in, const uint32_t* rngIn, uint64_t n, float* out,
+                                  uint32_t* rngOut) {
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* p = in + i * kSssBeginIn;
+    float* o = out + i * kSssBeginOut;
+    for (uint32_t k = 0; k < kSssBeginOut; ++k) o[k] = 0.0f;
+    const Mat m{material};
+    uint32_t rng = rngIn[i];
+    BsdfSampleResult bs{mk3(0.0f), mk3(0.0f), 0.0f, false, 0, false, mk3(0.0f)};
+    SssWalk walk{mk3(0.0f), mk3(0.0f), mk3(0.0f), 0u};
+    const int outcome = sssWalkBegin(m, ld3(p), ld3(p + 3), ld3(p + 6), ld3(p + 9), rng, clampCfg<METAL>(rp), bs, walk);
+    o[0] = static_cast<float>(outcome);
+    if (outcome == kWalkSample) {
+        o[1] = bs.dir.x; o[2] = bs.dir.y; o[3] = bs.dir.z;
+        o[4] = bs.weight.x; o[5] = bs.weight.y; o[6] = bs.weight.z;
+        o[7] = bs.pdf; o[8] = bs.isDelta ? 1.0f : 0.0f;
+    } else if (outcome == kWalkWalking) {
+        o[1] = walk.direction.x; o[2] = walk.direction.y; o[3] = walk.direction.z;
+        o[4] = walk.throughput.x; o[5] = walk.throughput.y; o[6] = walk.throughput.z;
+        o[9] = walk.position.x; o[10] = walk.position.y; o[11] = walk.position.z;
+    }
+    rngOut[i] = rng;
+}
+
+// (materialIndex, null in the function probe: row i reads material materialIndex[i] of `material`, the scene's array)
+__global__ void __attribute__((flatten)) k_debug_sss_step(const float4* material, const uint32_t* materialIndex, uint32_t maxSteps, const float* in,
+                                                         const uint32_t* rngIn, uint64_t n, float* out, uint32_t* rngOut) {
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float* p = in + i * kSssStepIn;
+    float* o = out + i * kSssStepOut;
+    for (uint32_t k = 0; k < kSssStepOut; ++k) o[k] = 0.0f;
+    const Mat m{materialIndex ? material + static_cast<size_t>(materialIndex[i]) * kMaterialVec4 : material};
+    uint32_t rng = rngIn[i];
+    SssWalk walk{ld3(p), ld3(p + 3), ld3(p + 6), __float_as_uint(p[9])};
+    BsdfSampleResult bs{mk3(0.0f), mk3(0.0f), 0.0f, false, 0, false, mk3(0.0f)};
+    const int outcome = sssWalkStep(m, maxSteps, walk, p[10] != 0.0f, p[11], ld3(p + 12), ld3(p + 15), rng, bs);
+    o[0] = static_cast<float>(outcome);
+    o[1] = walk.position.x; o[2] = walk.position.y; o[3] = walk.position.z;
+    o[4] = walk.direction.x; o[5] = walk.direction.y; o[6] = walk.direction.z;
+    o[7] = walk.throughput.x; o[8] = walk.throughput.y; o[9] = walk.throughput.z;
+    o[10] = __uint_as_float(walk.step);
+    if (outcome == kWalkSample) {
+        o[11] = bs.dir.x; o[12] = bs.dir.y; o[13] = bs.dir.z;
+        o[14] = bs.weight.x; o[15] = bs.weight.y; o[16] = bs.weight.z;
+        o[17] = bs.pdf; o[18] = bs.hasExit ? 1.0f : 0.0f;
+        o[19] = bs.exitPoint.x; o[20] = bs.exitPoint.y; o[21] = bs.exitPoint.z;
+    }
+    rngOut[i] = rng;
+}
+
+// The first bounce of a camera sample with its whole walk (ptr_debug_sss_walks), as the wavefront runs it: one kernel per stage and the
+// host's loop over the boundary queries in between, the walk riding in a record per sample the way it rides in a path slot.  The
+// statements are shadeSlot's, in shadeSlot's order.  sssWalkStep itself runs in k_debug_sss_step on the rows k_debug_sss_walk_query
+// lays out: the render's kernels that texture share ONE out-of-line copy of that function, and another caller in a kernel that also
+// traverses changes the code the compiler makes of that copy, and with it of them (profiles/sss_walk_asm_diff.txt).
+// A sample's record (kSssWalkStateWords words, launch.h): what shadeSlot keeps in the slot and in record slot 4 between two visits
+enum : uint32_t { kWsOutcome = 0, kWsQueries, kWsPos, kWsDir = 5, kWsThr = 8, kWsStep = 11, kWsRng, kWsStarted, kWsMaterial, kWsFront, kWsHitPos,
+                  kWsOffsetN = 19, kWsOffsetDist = 22, kWsNormal, kWsWo = 26, kWsOutward = 29, kWsBsDir = 32, kWsBsWeight = 35, kWsBsPdf = 38,
+                  kWsBsHasExit, kWsBsExit, kWsActive = 43, kWsAlive, kSssWalkState = kSssWalkStateWords };   // (launch.h: what the host allocates)
+static_assert(kWsAlive < kSssWalkState, "the record of a walk outgrew the words the host allocates per sample");
+__device__ __forceinline__ void st3(float* p, f3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
+
+template <bool SSS>
+__global__ void __launch_bounds__(kTraceBlock) k_debug_sss_walk_first(RenderParams rp, SceneView sc, const uint32_t* xys, uint64_t n, float* state,
+                                                                      float* outFinal, uint32_t* spill, uint32_t spillStride) {
+    __shared__ uint32_t ldsStack[kLdsStackLevels * kTraceBlock];
+    const uint32_t gtid = blockIdx.x * kTraceBlock + threadIdx.x;
+    LaneStack stack = laneStack(ldsStack, spill, spillStride, sc);
+    TraceCounters cnt{0u, 0u};
+    const ClampCfg cc = clampCfg<SSS>(rp);
+    for (uint64_t i = gtid; i < n; i += static_cast<uint64_t>(gridDim.x) * kTraceBlock) {
+        float* f = outFinal + i * kSssWalkFinal;
+        float* w = state + i * kSssWalkState;
+        for (uint32_t k = 0; k < kSssWalkFinal; ++k) f[k] = 0.0f;
+        for (uint32_t k = 0; k < kSssWalkState; ++k) w[k] = 0.0f;
+        f[3] = -1.0f;
+        uint32_t rng;
+        f3 rayO, rayD;
+        beginSample(rp, xys[i * 3u + 1u] * rp.width + xys[i * 3u], xys[i * 3u + 2u], rng, rayO, rayD);
+        f[20] = __uint_as_float(rng);
+        f[14] = __uint_as_float(rng);
+        const TraceHit h = traverse<false, false>(sc, rayO, rayD, kEps, INFINITY, stack, cnt);
+        if (h.prim == kHitMiss || sc.materialCount == 0u) continue;
+        f[0] = 1.0f;
+        const Surface sf = reconstruct(sc, rayO, rayD, h.t, h.prim);
+        const OffsetFrame of = offsetFrame(sf);
+        const uint32_t materialIndex = min(sf.material, sc.materialCount - 1u);
+        const Mat mat{byteOffset(sc.materials, materialIndex * (kMaterialVec4 * 16u))};
+        const uint32_t type = mat.type();
+        if (type == 3u || (SSS && cc.metalPbr && type == 7u) || (type == 2u && (rp.mediaMode & (PTR_METAL_MEDIA | PTR_METAL_FACE_NORMAL)))) {
+            f[16] = 1.0f;
+            continue;
+        }
+        const f3 incident = normalize(rayD);
+        const f3 wo = -incident;
+        f3 nrm = sf.hitShadingNormal;
+        if (dot(nrm, nrm) <= 0.0f) nrm = sf.normal;
+        if (type == 2u) nrm = sf.normal;
+        nrm = normalize(nrm);
+        BsdfSampleResult bs{mk3(0.0f), mk3(0.0f), 0.0f, false, 0, false, mk3(0.0f)};
+        SssWalk walk{mk3(0.0f), mk3(0.0f), mk3(0.0f), 0u};
+        int outcome = kWalkFallback;
+        bool started = false;
+        if (SSS && type == 5u && cc.metalSss && rp.sssMode == 2u && mat.v(kMatSssParams).y >= 0.5f && sf.frontFace) {
+            started = true;
+            outcome = sssWalkBegin(mat, sf.position, sf.normal, wo, incident, rng, cc, bs, walk);
+            f[17] = nrm.x; f[18] = nrm.y; f[19] = nrm.z;   // what shadeSlot parks in wr.b
+        }
+        w[kWsOutcome] = static_cast<float>(outcome);
+        st3(w + kWsPos, walk.position); st3(w + kWsDir, walk.direction); st3(w + kWsThr, walk.throughput);
+        w[kWsStep] = __uint_as_float(walk.step);
+        w[kWsRng] = __uint_as_float(rng);
+        w[kWsStarted] = started ? 1.0f : 0.0f;
+        w[kWsMaterial] = __uint_as_float(materialIndex);
+        w[kWsFront] = sf.frontFace ? 1.0f : 0.0f;
+        st3(w + kWsHitPos, sf.position); st3(w + kWsOffsetN, of.n);
+        w[kWsOffsetDist] = of.distance;
+        st3(w + kWsNormal, nrm); st3(w + kWsWo, wo);
+        st3(w + kWsBsDir, bs.dir); st3(w + kWsBsWeight, bs.weight);
+        w[kWsBsPdf] = bs.pdf;
+        w[kWsAlive] = 1.0f;
+    }
+}
+
+// boundary query `q` of every walk still under way: the rows k_debug_sss_step takes (kSssStepIn words, its random states and material
+// indices beside them), and the same as the step's record
+__global__ void __launch_bounds__(kTraceBlock) k_debug_sss_walk_query(SceneView sc, uint64_t n, uint32_t q, uint32_t stepCap, float* state, float* rows,
+                                                                      uint32_t* rowRng, uint32_t* rowMaterial, float* outSteps, uint32_t* spill,
+                                                                      uint32_t spillStride) {
+    __shared__ uint32_t ldsStack[kLdsStackLevels * kTraceBlock];
+    const uint32_t gtid = blockIdx.x * kTraceBlock + threadIdx.x;
+    LaneStack stack = laneStack(ldsStack, spill, spillStride, sc);
+    TraceCounters cnt{0u, 0u};
+    for (uint64_t i = gtid; i < n; i += static_cast<uint64_t>(gridDim.x) * kTraceBlock) {
+        float* w = state + i * kSssWalkState;
+        float* r = rows + i * kSssStepIn;
+        for (uint32_t k = 0; k < kSssStepIn; ++k) r[k] = 0.0f;
+        rowRng[i] = 1u;
+        rowMaterial[i] = 0u;
+        const bool active = w[kWsAlive] != 0.0f && w[kWsStarted] != 0.0f && static_cast<int>(w[kWsOutcome]) == kWalkWalking;
+        w[kWsActive] = active ? 1.0f : 0.0f;
+        if (!active) continue;
+        const f3 org = ld3(w + kWsPos), dir = ld3(w + kWsDir);
+        const TraceHit bh = traverse<false, false>(sc, org, dir, kEps, INFINITY, stack, cnt);
+        f3 hitPoint = org, outward = mk3(0.0f);
+        if (bh.prim != kHitMiss) {
+            const Surface bsf = reconstruct(sc, org, dir, bh.t, bh.prim);
+            hitPoint = bsf.position;
+            outward = bsf.normal;
+        }
+        st3(w + kWsOutward, outward);
+        st3(r, org); st3(r + 3, dir);
+        r[6] = w[kWsThr]; r[7] = w[kWsThr + 1u]; r[8] = w[kWsThr + 2u];
+        r[9] = w[kWsStep];
+        r[10] = bh.prim != kHitMiss ? 1.0f : 0.0f;
+        r[11] = bh.t;
+        st3(r + 12, hitPoint); st3(r + 15, outward);
+        rowRng[i] = __float_as_uint(w[kWsRng]);
+        rowMaterial[i] = __float_as_uint(w[kWsMaterial]);
+        if (q < stepCap) {
+            float* s = outSteps + (i * stepCap + q) * kSssWalkStep;
+            for (uint32_t k = 0; k < 18u; ++k) s[k] = r[k];
+            s[18] = w[kWsRng];
+        }
+    }
+}
+
+// what k_debug_sss_step made of query `q`, taken back into the samples' records
+__global__ void k_debug_sss_walk_apply(uint64_t n, uint32_t q, uint32_t stepCap, float* state, const float* stepOut, const uint32_t* stepRng,
+                                       float* outSteps) {
+    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float* w = state + i * kSssWalkState;
+    if (w[kWsActive] == 0.0f) return;
+    const float* o = stepOut + i * kSssStepOut;
+    w[kWsOutcome] = o[0];
+    for (uint32_t k = 0; k < 10u; ++k) w[kWsPos + k] = o[1u + k];   // position, direction, throughput, step
+    w[kWsRng] = __uint_as_float(stepRng[i]);
+    w[kWsQueries] += 1.0f;
+    if (static_cast<int>(o[0]) == kWalkSample) {
+        for (uint32_t k = 0; k < 7u; ++k) w[kWsBsDir + k] = o[11u + k];   // direction, weight, pdf
+        w[kWsBsHasExit] = o[18];
+        for (uint32_t k = 0; k < 3u; ++k) w[kWsBsExit + k] = o[19u + k];
+    }
+    if (q < stepCap) {
+        float* s = outSteps + (i * stepCap + q) * kSssWalkStep;
+        s[19] = o[0];
+        s[20] = __uint_as_float(stepRng[i]);
+    }
+}
+
+// the end of the first bounce as shadeSlot ends it, and whether the next ray escapes
+template <bool SSS>
+__global__ void __launch_bounds__(kTraceBlock) k_debug_sss_walk_end(RenderParams rp, SceneView sc, uint64_t n, const float* state, float* outFinal,
+                                                                    uint32_t* spill, uint32_t spillStride) {
+    __shared__ uint32_t ldsStack[kLdsStackLevels * kTraceBlock];
+    const uint32_t gtid = blockIdx.x * kTraceBlock + threadIdx.x;
+    LaneStack stack = laneStack(ldsStack, spill, spillStride, sc);
+    TraceCounters cnt{0u, 0u};
+    const ClampCfg cc = clampCfg<SSS>(rp);
+    for (uint64_t i = gtid; i < n; i += static_cast<uint64_t>(gridDim.x) * kTraceBlock) {
+        const float* w = state + i * kSssWalkState;
+        float* f = outFinal + i * kSssWalkFinal;
+        if (w[kWsAlive] == 0.0f) continue;
+        const int outcome = static_cast<int>(w[kWsOutcome]);
+        const bool started = w[kWsStarted] != 0.0f;
+        const uint32_t queries = static_cast<uint32_t>(w[kWsQueries]);
+        uint32_t rng = __float_as_uint(w[kWsRng]);
+        f[1] = started ? 1.0f : 0.0f;
+        f[2] = w[kWsQueries];
+        f[3] = started ? w[kWsOutcome] : -1.0f;
+        f[14] = __uint_as_float(rng);
+        if (outcome == kWalkWalking) continue;   // (the step limit ends every walk: not reached)
+        const Mat mat{byteOffset(sc.materials, __float_as_uint(w[kWsMaterial]) * (kMaterialVec4 * 16u))};
+        const f3 nrm = ld3(w + kWsNormal), wo = ld3(w + kWsWo);
+        BsdfSampleResult bs{ld3(w + kWsBsDir), ld3(w + kWsBsWeight), w[kWsBsPdf], false, 0, w[kWsBsHasExit] != 0.0f, ld3(w + kWsBsExit)};
+        const bool exited = queries > 0u && outcome == kWalkSample;
+        if (queries > 0u && outcome == kWalkFallback) {
+            // a walk abandoned: the ordinary sample at the entry point, with the parked shading normal
+            bs = sampleBsdf<true>(mat, ld3(w + kWsHitPos), nrm, nrm, -nrm, true, rng, cc);
+        } else if (queries == 0u && outcome != kWalkSample) {
+            // no walk, or sssWalkBegin fell back: the ordinary sample at the hit
+            if (SSS) bs = sampleBsdf<true>(mat, ld3(w + kWsHitPos), nrm, wo, -wo, w[kWsFront] != 0.0f, rng, cc);
+            else bs = sampleBsdf<false>(mat, ld3(w + kWsHitPos), nrm, wo, -wo, w[kWsFront] != 0.0f, rng, cc);
+        }
+        f[14] = __uint_as_float(rng);
+        if (bs.pdf <= 0.0f || dot(bs.dir, bs.dir) <= 0.0f || !finite3(bs.weight)) continue;
+        f3 thr = mk3(1.0f);
+        thr *= bs.weight;
+        thr = clampThroughput(thr, cc);
+        const float maxComp = smax(smax(thr.x, thr.y), thr.z);
+        if (!finite3(thr) || maxComp <= 0.0f) continue;
+        OffsetFrame of;
+        of.position = ld3(w + kWsHitPos);
+        of.n = ld3(w + kWsOffsetN);
+        of.distance = w[kWsOffsetDist];
+        f3 nextO;
+        if (exited) nextO = sssExitOrigin(bs.exitPoint, ld3(w + kWsOutward), bs.dir);
+        else if (SSS && bs.hasExit) nextO = sssExitOrigin(bs.exitPoint, nrm, bs.dir);
+        else nextO = offsetOrigin(of, bs.dir);
+        const f3 nextD = bs.dir;
+        f[4] = 1.0f;
+        f[5] = nextO.x; f[6] = nextO.y; f[7] = nextO.z;
+        f[8] = nextD.x; f[9] = nextD.y; f[10] = nextD.z;
+        f[11] = thr.x; f[12] = thr.y; f[13] = thr.z;
+        const TraceHit eh = traverse<false, false>(sc, nextO, nextD, kEps, INFINITY, stack, cnt);
+        f[15] = eh.prim == kHitMiss ? 1.0f : 0.0f;
+    }
+}
+
 // closest hit + surface reconstruction + next-ray origin, the pieces k_shade builds a bounce from (tests of a13 / a14)
 __global__ void __launch_bounds__(kTraceBlock) k_debug_surface(SceneView sc, const float* in, uint64_t n, float* out, uint32_t* spill, uint32_t spillStride) {
     __shared__ uint32_t ldsStack[kLdsStackLevels * kTraceBlock];
@@ -3084,6 +3343,43 @@ void launchDebugRectLightNee(const RenderParams& rp, const SceneView& sc, const 
 
 void launchDebugLightConnection(const RenderParams& rp, const SceneView& sc, const float* dIn, uint64_t n, float* dOut, hipStream_t stream) {
     launchFlat(k_debug_light_connection, 128, n, stream, rp, sc, shadeVariant(rp, sc, false).sss, dIn, n, dOut);
+}
+
+// the random-walk probes: the Metal-semantics instantiation exactly when launchShade's k_shade is one (a probe without a scene asks with
+// an empty one: the choice hangs on the settings alone)
+void launchDebugSssBegin(const float4* dMaterial, const RenderParams& rp, const float* dIn, const uint32_t* dRng, uint64_t n, float* dOut,
+                         uint32_t* dRngOut, hipStream_t stream) {
+    withBools([&](auto sssTag) {
+        launchFlat(k_debug_sss_begin<decltype(sssTag)::value>, 128, n, stream, dMaterial, rp, dIn, dRng, n, dOut, dRngOut);
+    }, shadeVariant(rp, SceneView{}, false).sss);
+}
+
+void launchDebugSssStep(const float4* dMaterial, uint32_t maxSteps, const float* dIn, const uint32_t* dRng, uint64_t n, float* dOut, uint32_t* dRngOut,
+                        hipStream_t stream) {
+    launchFlat(k_debug_sss_step, 128, n, stream, dMaterial, static_cast<const uint32_t*>(nullptr), maxSteps, dIn, dRng, n, dOut, dRngOut);
+}
+
+// the wavefront's shape: the first hit and sssWalkBegin, then per boundary query a traversal, sssWalkStep on its rows and the records'
+// update, max(sssMaxSteps, 1) times (the step limit ends every walk by then), then the end of the bounce
+void launchDebugSssWalks(const RenderParams& rp, const SceneView& sc, const uint32_t* dXys, uint64_t n, uint32_t stepCap, float* dSteps, float* dFinal,
+                         const SssWalkScratch& scratch, const LaunchConfig& cfgIn, hipStream_t stream) {
+    const TraceLaunch t = traceLaunch(cfgIn, n);
+    const uint32_t limit = std::max(rp.sssMaxSteps, 1u);
+    withBools([&](auto sssTag) {
+        constexpr bool S = decltype(sssTag)::value;
+        hipLaunchKernelGGL(k_debug_sss_walk_first<S>, dim3(t.grid), dim3(kTraceBlock), 0, stream, rp, sc, dXys, n, scratch.state, dFinal, t.cfg.spill,
+                           t.stride);
+        for (uint32_t q = 0; q < limit; ++q) {
+            hipLaunchKernelGGL(k_debug_sss_walk_query, dim3(t.grid), dim3(kTraceBlock), 0, stream, sc, n, q, stepCap, scratch.state, scratch.rows,
+                               scratch.rowRng, scratch.rowMaterial, dSteps, t.cfg.spill, t.stride);
+            launchFlat(k_debug_sss_step, 128, n, stream, sc.materials, static_cast<const uint32_t*>(scratch.rowMaterial), rp.sssMaxSteps,
+                       static_cast<const float*>(scratch.rows), static_cast<const uint32_t*>(scratch.rowRng), n, scratch.stepOut, scratch.stepRng);
+            launchFlat(k_debug_sss_walk_apply, 128, n, stream, n, q, stepCap, scratch.state, static_cast<const float*>(scratch.stepOut),
+                       static_cast<const uint32_t*>(scratch.stepRng), dSteps);
+        }
+        hipLaunchKernelGGL(k_debug_sss_walk_end<S>, dim3(t.grid), dim3(kTraceBlock), 0, stream, rp, sc, n, static_cast<const float*>(scratch.state), dFinal,
+                           t.cfg.spill, t.stride);
+    }, shadeVariant(rp, sc, false).sss);
 }
 
 }  // namespace ptrk

@@ -264,4 +264,20 @@ void oracle_light_connection(const OracleScene* s, const PtrSettings* settings, 
 // The per-hit material of the textured model at the closest hit of each ray (oracle_integrator.h pbrHitsBatch): in n * 20, out n * 32 words
 void oracle_pbr_hits(const OracleScene* s, const float* in, uint64_t n, float* out) { pbrHitsBatch(s->scene, s->desc, in, n, out); }
 
+// The random-walk subsurface path (oracle_integrator.h sssWalkBeginBatch / sssWalkStepBatch / sssWalksBatch): the rows of include/ptr_debug_sss.h
+void oracle_sss_walk_begin(const PtrMaterial* m, const PtrSettings* s, const float* in, const uint32_t* rng_states, uint64_t n, float* out,
+                           uint32_t* out_states) {
+    sssWalkBeginBatch(*m, *s, in, rng_states, n, out, out_states);
+}
+
+void oracle_sss_walk_step(const PtrMaterial* m, const PtrSettings* s, const float* in, const uint32_t* rng_states, uint64_t n, float* out,
+                          uint32_t* out_states) {
+    sssWalkStepBatch(*m, *s, in, rng_states, n, out, out_states);
+}
+
+void oracle_sss_walks(const OracleScene* s, const PtrSettings* settings, const uint32_t* xys, uint64_t n, uint32_t step_cap, float* out_steps,
+                      float* out_final) {
+    sssWalksBatch(s->scene, s->desc, *settings, xys, n, step_cap, out_steps, out_final);
+}
+
 }  // extern "C"

@@ -2861,4 +2861,146 @@ void lightConnectionBatch(const Scene& scene, const PtrSceneDesc& desc, const Pt
     }
 }
 
+// ---- the random-walk subsurface path, row for row what the probes of include/ptr_debug_sss.h take and report ----
+namespace {
+uint32_t wordOf(float f) {
+    uint32_t u;
+    std::memcpy(&u, &f, 4);
+    return u;
+}
+void putWord(float* o, uint32_t u) { std::memcpy(o, &u, 4); }
+void put3(float* o, V3 v) { o[0] = v.x, o[1] = v.y, o[2] = v.z; }
+}  // namespace
+
+void sssWalkBeginBatch(const PtrMaterial& m, const PtrSettings& settings, const float* in, const uint32_t* states, uint64_t n, float* out,
+                       uint32_t* outStates) {
+    const ClampParams cp = makeClampParams(settings);
+    for (uint64_t i = 0; i < n; ++i) {
+        const float* p = in + i * kSssBeginIn;
+        float* o = out + i * kSssBeginOut;
+        std::memset(o, 0, kSssBeginOut * sizeof(float));
+        Rng rng;
+        rng.state = states[i];
+        BsdfSample bs;
+        SssWalk walk;
+        const WalkOutcome outcome = sssWalkBegin(m, V3(p), V3(p + 3), V3(p + 6), V3(p + 9), rng, cp, bs, walk);
+        o[0] = static_cast<float>(static_cast<int>(outcome));
+        if (outcome == WalkOutcome::Sample) {
+            put3(o + 1, bs.direction);
+            put3(o + 4, bs.weight);
+            o[7] = bs.pdf, o[8] = bs.isDelta ? 1.0f : 0.0f;
+        } else if (outcome == WalkOutcome::Walking) {
+            put3(o + 1, walk.direction);
+            put3(o + 4, walk.throughput);
+            put3(o + 9, walk.position);
+        }
+        outStates[i] = rng.state;
+    }
+}
+
+void sssWalkStepBatch(const PtrMaterial& m, const PtrSettings& settings, const float* in, const uint32_t* states, uint64_t n, float* out,
+                      uint32_t* outStates) {
+    for (uint64_t i = 0; i < n; ++i) {
+        const float* p = in + i * kSssStepIn;
+        float* o = out + i * kSssStepOut;
+        std::memset(o, 0, kSssStepOut * sizeof(float));
+        Rng rng;
+        rng.state = states[i];
+        BsdfSample bs;
+        SssWalk walk;
+        walk.position = V3(p), walk.direction = V3(p + 3), walk.throughput = V3(p + 6), walk.step = wordOf(p[9]);
+        const WalkOutcome outcome = sssWalkStep(m, settings.sssMaxSteps, walk, p[10] != 0.0f, p[11], V3(p + 12), V3(p + 15), rng, bs);
+        o[0] = static_cast<float>(static_cast<int>(outcome));
+        put3(o + 1, walk.position);
+        put3(o + 4, walk.direction);
+        put3(o + 7, walk.throughput);
+        putWord(o + 10, walk.step);
+        if (outcome == WalkOutcome::Sample) {
+            put3(o + 11, bs.direction);
+            put3(o + 14, bs.weight);
+            o[17] = bs.pdf, o[18] = bs.hasExitPoint ? 1.0f : 0.0f;
+            put3(o + 19, bs.exitPoint);
+        }
+        outStates[i] = rng.state;
+    }
+}
+
+void sssWalksBatch(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& settings, const uint32_t* xys, uint64_t n, uint32_t stepCap,
+                   float* outSteps, float* outFinal) {
+    const ClampParams cp = makeClampParams(settings);
+    const Camera cam = buildCamera(settings);
+    const uint32_t seedBase = settings.seed != 0 ? settings.seed : 0x9e3779b9u;
+    const bool media = (settings.metalSemantics & (PTR_METAL_MEDIA | PTR_METAL_FACE_NORMAL)) != 0u;
+    std::memset(outSteps, 0, n * stepCap * kSssWalkStep * sizeof(float));
+    for (uint64_t i = 0; i < n; ++i) {
+        float* f = outFinal + i * kSssWalkFinal;
+        std::memset(f, 0, kSssWalkFinal * sizeof(float));
+        f[3] = -1.0f;
+        const uint32_t x = xys[i * 3], y = xys[i * 3 + 1], smp = xys[i * 3 + 2];
+        Rng rng;
+        rng.state = Rng::hash(seedBase ^ (y * settings.width + x) ^ (smp * 0x9e3779b9u));
+        const Ray ray = generateCameraRay(cam, settings.width, settings.height, x, y, rng);
+        putWord(f + 20, rng.state);
+        putWord(f + 14, rng.state);
+        HitInfo hit;
+        if (!intersectScene(scene, ray, hit) || !desc.materials || desc.materialCount == 0u) continue;
+        f[0] = 1.0f;
+        const PtrMaterial& material = desc.materials[std::min(hit.materialIndex, desc.materialCount - 1u)];
+        const uint32_t type = matType(material);
+        if (type == PTR_MAT_DIFFUSE_LIGHT || (cp.metalPbr && type == PTR_MAT_PBR) || (type == PTR_MAT_DIELECTRIC && media)) {
+            f[16] = 1.0f;
+            continue;
+        }
+        const V3 incidentDir = normalize(ray.direction);
+        const V3 wo = -incidentDir;
+        const V3 shadingNormal = vertexShadingNormal(hit, type, settings);
+        BsdfSample bs;
+        WalkOutcome outcome = WalkOutcome::Fallback;
+        bool started = false;
+        uint32_t queries = 0;
+        if (cp.metalSss && cp.sssMode == 2u && type == PTR_MAT_SUBSURFACE && material.sssParams[1] >= 0.5f && hit.frontFace) {   // as render()
+            started = true;
+            SssWalk walk;
+            outcome = sssWalkBegin(material, hit.position, hit.normal, wo, incidentDir, rng, cp, bs, walk);
+            put3(f + 17, shadingNormal);
+            while (outcome == WalkOutcome::Walking) {
+                HitInfo boundary;
+                const bool hitBoundary = intersectScene(scene, Ray{walk.position, walk.direction}, boundary);
+                // (what the device passes where nothing was hit: the ray's origin and a zero normal; sssWalkStep reads neither then)
+                const V3 point = hitBoundary ? boundary.position : walk.position;
+                const V3 normal = hitBoundary ? boundary.normal : V3();
+                float* s = queries < stepCap ? outSteps + (i * stepCap + queries) * kSssWalkStep : nullptr;
+                if (s) {
+                    put3(s, walk.position), put3(s + 3, walk.direction), put3(s + 6, walk.throughput);
+                    putWord(s + 9, walk.step);
+                    s[10] = hitBoundary ? 1.0f : 0.0f;
+                    s[11] = boundary.t;
+                    put3(s + 12, point), put3(s + 15, normal);
+                    putWord(s + 18, rng.state);
+                }
+                outcome = sssWalkStep(material, cp.sssMaxSteps, walk, hitBoundary, boundary.t, point, normal, rng, bs);
+                if (s) {
+                    s[19] = static_cast<float>(static_cast<int>(outcome));
+                    putWord(s + 20, rng.state);
+                }
+                ++queries;
+            }
+        }
+        f[1] = started ? 1.0f : 0.0f;
+        f[2] = static_cast<float>(queries);
+        f[3] = started ? static_cast<float>(static_cast<int>(outcome)) : -1.0f;
+        if (outcome != WalkOutcome::Sample) bs = sampleBsdf(material, hit.position, shadingNormal, wo, incidentDir, hit.frontFace, rng, cp);
+        putWord(f + 14, rng.state);
+        if (bs.pdf <= 0.0f || dot(bs.direction, bs.direction) <= 0.0f || !finite3(bs.weight)) continue;
+        V3 throughput = clampPathThroughput(bs.weight, cp);
+        if (!finite3(throughput) || std::max(std::max(throughput.x, throughput.y), throughput.z) <= 0.0f) continue;
+        const V3 origin = bs.hasExitPoint ? sssExitOrigin(bs.exitPoint, dot(bs.exitNormal, bs.exitNormal) > 0.0f ? bs.exitNormal : shadingNormal, bs.direction)
+                                          : offsetRayOrigin(hit, bs.direction);
+        f[4] = 1.0f;
+        put3(f + 5, origin), put3(f + 8, bs.direction), put3(f + 11, throughput);
+        HitInfo next;
+        f[15] = intersectScene(scene, Ray{origin, bs.direction}, next) ? 0.0f : 1.0f;
+    }
+}
+
 }  // namespace oracle

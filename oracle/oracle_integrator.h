@@ -154,6 +154,16 @@ void lightConnectionBatch(const Scene& scene, const PtrSceneDesc& desc, const Pt
 constexpr uint32_t kPbrHitIn = 20, kPbrHitOut = 32;
 void pbrHitsBatch(const Scene& scene, const PtrSceneDesc& desc, const float* in, uint64_t n, float* out);
 
+// The random-walk subsurface path (sssWalkBegin, sssWalkStep, and the first bounce of a camera sample with its whole walk as render() runs
+// it, on the oracle's own intersectScene), row for row what the probes of include/ptr_debug_sss.h take and report.
+constexpr uint32_t kSssBeginIn = 12, kSssBeginOut = 16, kSssStepIn = 20, kSssStepOut = 24, kSssWalkStep = 24, kSssWalkFinal = 24;
+void sssWalkBeginBatch(const PtrMaterial& m, const PtrSettings& settings, const float* in, const uint32_t* states, uint64_t n, float* out,
+                       uint32_t* outStates);
+void sssWalkStepBatch(const PtrMaterial& m, const PtrSettings& settings, const float* in, const uint32_t* states, uint64_t n, float* out,
+                      uint32_t* outStates);
+void sssWalksBatch(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& settings, const uint32_t* xys, uint64_t n, uint32_t stepCap,
+                   float* outSteps, float* outFinal);
+
 // Renders pixels with y in [y0, y1) (full width); out_rgb is the full W*H*3 image, other rows untouched.
 // out_signature / out_marginal (optional, W*H each): path signature of every pixel's last sample and whether one of its
 // rectangle-light shadow tests is decided within rounding noise of the ray length (deterministic-stream diagnostics).

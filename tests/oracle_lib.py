@@ -49,6 +49,9 @@ def lib():
         l.oracle_rect_light_nee.argtypes = [vp, C.POINTER(pt.PtrSettings), C.POINTER(pt.PtrMaterial), fp, fp, up, u64, fp, up]
         l.oracle_light_connection.argtypes = [vp, C.POINTER(pt.PtrSettings), fp, u64, fp]
         l.oracle_pbr_hits.argtypes = [vp, fp, u64, fp]
+        l.oracle_sss_walk_begin.argtypes = [C.POINTER(pt.PtrMaterial), C.POINTER(pt.PtrSettings), fp, up, u64, fp, up]
+        l.oracle_sss_walk_step.argtypes = [C.POINTER(pt.PtrMaterial), C.POINTER(pt.PtrSettings), fp, up, u64, fp, up]
+        l.oracle_sss_walks.argtypes = [vp, C.POINTER(pt.PtrSettings), up, u64, u32, fp, fp]
         _lib = l
     return _lib
 
@@ -145,6 +148,15 @@ class OracleScene:
         lib().oracle_pbr_hits(self._h, _f(rows), rows.shape[0], _f(out))
         return pt.DeviceScene.pbr_hit_fields(out)
 
+    def sss_walks(self, settings, xys, step_cap=64):
+        """The oracle's first bounce of the camera samples xys [n, 3] with its whole subsurface random walk, on its own intersectScene: the
+        rows of pt.DeviceScene.sss_walks."""
+        xys = np.ascontiguousarray(xys, dtype=np.uint32).reshape(-1, 3)
+        steps = np.zeros((xys.shape[0], step_cap, 24), dtype=np.float32)
+        final = np.zeros((xys.shape[0], 24), dtype=np.float32)
+        lib().oracle_sss_walks(self._h, C.byref(settings), _u(xys), xys.shape[0], step_cap, _f(steps), _f(final))
+        return pt.sss_fields(steps, pt.SSS_WALK_STEP_FIELDS), pt.sss_fields(final, pt.SSS_WALK_FINAL_FIELDS)
+
     def close(self):
         if self._h:
             lib().oracle_scene_destroy(self._h)
@@ -205,6 +217,25 @@ def sample_bsdf(material, settings, inputs, front, states):
     out_states = np.zeros(inputs.shape[0], dtype=np.uint32)
     lib().oracle_sample_bsdf(C.byref(material), C.byref(settings), _f(inputs), _u(front), _u(states), inputs.shape[0], _f(out), _u(out_states))
     return out, out_states
+
+
+def _sss_batch(fn, material, settings, rows, cols, out_cols, states):
+    rows = np.ascontiguousarray(rows, dtype=np.float32).reshape(-1, cols)
+    states = np.ascontiguousarray(states, dtype=np.uint32)
+    out = np.zeros((rows.shape[0], out_cols), dtype=np.float32)
+    out_states = np.zeros(rows.shape[0], dtype=np.uint32)
+    fn(C.byref(material), C.byref(settings), _f(rows), _u(states), rows.shape[0], _f(out), _u(out_states))
+    return out, out_states
+
+
+def sss_walk_begin(material, settings, inputs, states):
+    """The oracle's sssWalkBegin: the rows of pt.debug_sss_walk_begin."""
+    return _sss_batch(lib().oracle_sss_walk_begin, material, settings, inputs, 12, 16, states)
+
+
+def sss_walk_step(material, settings, rows, states):
+    """The oracle's sssWalkStep with maxSteps = settings.sssMaxSteps as given: the rows of pt.debug_sss_walk_step."""
+    return _sss_batch(lib().oracle_sss_walk_step, material, settings, rows, 20, 24, states)
 
 
 def env_build(rgba):
