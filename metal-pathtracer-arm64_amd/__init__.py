@@ -387,6 +387,18 @@ def sss_fields(rows: np.ndarray, fields: dict) -> dict:
     return res
 
 
+# ... of include/ptr_debug_path.h (the stepping probe of the path state), a table of its own: tests/test_path_state_host.py holds it against that header
+_PATH_STATE_SIGNATURES = {
+    "ptr_debug_path_states": (_int, [_vp, _settings, _up, _u64, _u32, _u32, _up, _up, _fp] + _err),
+}
+PATH_STATE_SYMBOLS = tuple(_PATH_STATE_SIGNATURES)
+PATH_STATE_WORDS = 48   # PTR_PATH_STATE_WORDS
+# words of a slot's snapshot; "u:" marks a uint32 word
+PATH_STATE_FIELDS = {"origin": slice(0, 3), "direction": slice(3, 6), "last_pdf": 6, "u:flags": 7, "t": 8, "u:hit_word": 9, "throughput": slice(10, 13),
+                     "u:rng": 13, "accum": slice(14, 17), "u:item": 17, "u:medium": slice(18, 22), "cone": slice(22, 24), "u:record_kind": slice(24, 29),
+                     "u:flush_item": 29, "record_value": slice(32, 47)}
+
+
 # ... and of include/ptr_post.h (the denoiser), a table of its own: tests/test_post_host.py holds it against that header
 _denoise = C.POINTER(PtrDenoiseParams)
 _POST_SIGNATURES = {
@@ -653,7 +665,7 @@ def load_library() -> C.CDLL:
             list(_ADAPTIVE_SIGNATURES.items()) + list(_MULTI_SIGNATURES.items()) + list(_FRAME_SIGNATURES.items()) + list(_MULTI_FRAME_SIGNATURES.items()) + \
             list(_DYNAMIC_SIGNATURES.items()) + list(_DEFORM_SIGNATURES.items()) + list(_DEFORM_DEVICE_SIGNATURES.items()) + \
             list(_BACKGROUND_SIGNATURES.items()) + list(_TEMPORAL_SIGNATURES.items()) + list(_PBR_HIT_SIGNATURES.items()) + \
-            list(_SSS_WALK_SIGNATURES.items()):
+            list(_SSS_WALK_SIGNATURES.items()) + list(_PATH_STATE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -1130,6 +1142,20 @@ class DeviceScene:
         _check(load_library().ptr_debug_sss_walks(self._h, C.byref(settings), _uptr(xys), xys.shape[0], step_cap, _fptr(steps), _fptr(final),
                                                   err, len(err)), err)
         return sss_fields(steps, SSS_WALK_STEP_FIELDS), sss_fields(final, SSS_WALK_FINAL_FIELDS)
+
+    def path_states(self, settings: PtrSettings, pixels: np.ndarray, sample: int = 0, max_iterations: int = 64):
+        """ptr_debug_path_states: sample `sample` of the pixels [n] (y * width + x) through the production kernels, one iteration at a
+        time over a pool of one slot per pixel (include/ptr_debug_path.h).  Returns (PATH_STATE_FIELDS -> [iterations recorded, n, ..]
+        arrays plus "raw", the iterations the loop ran, itemAccum [n, 4])."""
+        pixels = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1)
+        states = np.zeros((max_iterations, pixels.shape[0], PATH_STATE_WORDS), dtype=np.uint32)
+        items = np.zeros((pixels.shape[0], 4), dtype=np.float32)
+        ran = C.c_uint32(0)
+        err = _err_buf()
+        _check(load_library().ptr_debug_path_states(self._h, C.byref(settings), _uptr(pixels), pixels.shape[0], sample, max_iterations,
+                                                    _uptr(states), C.byref(ran), _fptr(items), err, len(err)), err)
+        rows = states[: min(int(ran.value), max_iterations)].view(np.float32)
+        return sss_fields(rows, PATH_STATE_FIELDS), int(ran.value), items
 
     def env_lookup(self, settings: PtrSettings, dir_roughness: np.ndarray) -> np.ndarray:
         """ptr_debug_env_lookup: the PTR_METAL_ENV_LOD lookup of the scene's environment map with the settings' rotation and intensity:

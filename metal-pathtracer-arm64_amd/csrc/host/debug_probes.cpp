@@ -9,6 +9,7 @@
 #include "device_scene.h"
 #include "ptr_background.h"
 #include "ptr_debug.h"
+#include "ptr_debug_path.h"
 #include "ptr_debug_pbr.h"
 #include "ptr_debug_sss.h"
 
@@ -559,6 +560,69 @@ int ptr_debug_sss_walks(PtrDeviceScene* scene, const PtrSettings* settings, cons
         HIP_CHECK(hipDeviceSynchronize());
         dsteps.download(out_steps, n * step_cap * PTR_SSS_WALK_STEP);
         dfinal.download(out_final, n * PTR_SSS_WALK_FINAL);
+    });
+}
+
+// ---- the path state, iteration by iteration (ptr_debug_path.h) ----
+int ptr_debug_path_states(PtrDeviceScene* scene, const PtrSettings* settings, const uint32_t* pixels, uint64_t n, uint32_t sample,
+                          uint32_t max_iterations, uint32_t* out_states, uint32_t* out_iterations, float* out_items, char* err, size_t err_cap) {
+    const char* who = "ptr_debug_path_states";
+    const bool argsOk = scene && settings && pixels && out_states && out_iterations && out_items;
+    if (!argsOk) return nullArgument(who, err, err_cap);
+    if (n == 0 || n > PTR_PATH_MAX_PIXELS) return refuse(err, err_cap, std::string(who) + ": n must be 1..2^20");
+    if (max_iterations == 0u) return refuse(err, err_cap, std::string(who) + ": max_iterations == 0");
+    for (uint64_t i = 0; i < n; ++i) {
+        if (pixels[i] >= static_cast<uint64_t>(settings->width) * settings->height) {
+            return refuse(err, err_cap, std::string(who) + ": pixel " + std::to_string(i) + " is outside the image");
+        }
+    }
+    return deviceCall(who, scene, argsOk, err, err_cap, [&] {
+        // the production loop over one group of exactly n slots, no tail kernels: the scene's knobs are put back whatever happens
+        struct Knobs {
+            PtrDeviceScene& ds;
+            const uint64_t tailBelow, poolSlots;
+            ~Knobs() { ds.tailBelow = tailBelow, ds.poolSlots = poolSlots; }
+        } knobs{*scene, scene->tailBelow, scene->poolSlots};
+        scene->tailBelow = 0u;
+        scene->poolSlots = std::max<uint64_t>(scene->poolSlots, n);
+        const uint32_t slots = static_cast<uint32_t>(n);
+        DeviceBuffer<uint32_t> dPixels;
+        dPixels.upload(pixels, n);
+        std::memset(out_states, 0, static_cast<size_t>(max_iterations) * n * PTR_PATH_STATE_WORDS * sizeof(uint32_t));
+        std::vector<float4> state(n * 4u), rec(n * kRecSlots * 4u);
+        std::vector<float2> hit(n), cone(n);
+        std::vector<uint4> medium(n);
+        std::vector<uint32_t> flushItem(n);
+        uint64_t ran = 0;
+        const IterationHook hook = [&](uint64_t iteration, const PathPool& pool) {
+            HIP_CHECK(hipDeviceSynchronize());
+            ran = iteration + 1u;
+            if (iteration >= max_iterations) return;
+            if (pool.slots != slots || pool.recStride != slots) throw HipError{"ptr_debug_path_states: the pool is not one slot per pixel"};
+            // (ray0, ray1, thr, accum and the record rows are one allocation each, `slots` apart: slotRange)
+            HIP_CHECK(hipMemcpy(state.data(), pool.ray0, state.size() * sizeof(float4), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(rec.data(), pool.rec[0].org, rec.size() * sizeof(float4), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(hit.data(), pool.hit, n * sizeof(float2), hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(flushItem.data(), pool.flushItem, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            if (pool.medium) HIP_CHECK(hipMemcpy(medium.data(), pool.medium, n * sizeof(uint4), hipMemcpyDeviceToHost));
+            if (pool.cone) HIP_CHECK(hipMemcpy(cone.data(), pool.cone, n * sizeof(float2), hipMemcpyDeviceToHost));
+            for (uint64_t i = 0; i < n; ++i) {
+                uint32_t* o = out_states + (iteration * n + i) * PTR_PATH_STATE_WORDS;
+                for (uint32_t f = 0; f < 2u; ++f) std::memcpy(o + 4u * f, &state[f * n + i], sizeof(float4));
+                std::memcpy(o + 8, &hit[i], sizeof(float2));
+                for (uint32_t f = 2; f < 4u; ++f) std::memcpy(o + 2u + 4u * f, &state[f * n + i], sizeof(float4));
+                if (pool.medium) std::memcpy(o + 18, &medium[i], sizeof(uint4));
+                if (pool.cone) std::memcpy(o + 22, &cone[i], sizeof(float2));
+                for (uint32_t k = 0; k < kRecSlots; ++k) {
+                    std::memcpy(o + 24u + k, &rec[(k * 4u + 1u) * n + i].w, sizeof(uint32_t));
+                    std::memcpy(o + 32u + 3u * k, &rec[(k * 4u + 2u) * n + i], 3u * sizeof(float));
+                }
+                o[29] = flushItem[i];
+            }
+        };
+        traceItems(*scene, *settings, 1u, sample, dPixels.ptr, slots, nullptr, nullptr,
+                   [&](const float4* items) { HIP_CHECK(hipMemcpyAsync(out_items, items, n * sizeof(float4), hipMemcpyDeviceToHost, nullptr)); }, 2, &hook);
+        *out_iterations = static_cast<uint32_t>(ran);
     });
 }
 

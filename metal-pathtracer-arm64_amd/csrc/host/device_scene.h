@@ -271,8 +271,12 @@ uint64_t maxPassItems(const PtrDeviceScene* ds);
 // sampleBase + spp - 1 of the `localPixels` (> 0) pixels dPixelOfLocal names, non-counting kernels.  `consume` is handed the pass's
 // accumulators - sample c of local pixel lp at [c * localPixels + lp] - and launches what reads them on `stream`; the stream is joined
 // before the call returns.  Uses ds.outBands as scratch; leaves the scene's cached partition table alone.
+// `mode` as renderBands takes it (0 in every render); `hook` (null in every render): what the stepping probe (include/ptr_debug_path.h)
+// runs after the launches of each iteration, with the iteration's index and the whole pool; it joins the device itself.
+using IterationHook = std::function<void(uint64_t, const ptrk::PathPool&)>;
 void traceItems(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, uint32_t sampleBase, const uint32_t* dPixelOfLocal,
-                uint32_t localPixels, hipStream_t stream, PtrRenderStats* stats, const std::function<void(const float4*)>& consume);
+                uint32_t localPixels, hipStream_t stream, PtrRenderStats* stats, const std::function<void(const float4*)>& consume,
+                int mode = 0, const IterationHook* hook = nullptr);
 // the local-pixel order of a one-partition frame (8-row bands, 8x8 blocks)
 void imagePixelOrder(uint32_t width, uint32_t height, std::vector<uint32_t>& out);
 // adds the times, launches and samples of pass `one` to `sum`

@@ -157,8 +157,14 @@ void buildRectLights(const PtrSceneDesc& desc, const ptr::SceneGeometry& geo, st
     }
 }
 
+constexpr uint32_t kMaxMaterials = 65536u;   // material ids 0 .. 0xFFFF
+std::string tooManyMaterials(uint32_t count) {
+    return std::to_string(count) + " materials; at most 65536 (the medium stack holds 16-bit material ids)";
+}
+
 void prepareScene(const PtrSceneDesc& desc, PreparedScene& ps, const char* cachePath, bool dynamic, uint32_t dynamicFlags) {
     using ptr::float3;
+    if (desc.materialCount > kMaxMaterials) throw HipError{tooManyMaterials(desc.materialCount)};   // (uploads that do not come through uploadTo)
     const auto t0 = std::chrono::steady_clock::now();
     if (cachePath && *cachePath) {
         std::string error;
@@ -364,6 +370,9 @@ namespace {
 int uploadTo(const char* who, const PtrSceneDesc* scene, const char* cachePath, int device, PtrDeviceScene** outScene, char* err, size_t cap,
              bool dynamic = false, uint32_t dynamicFlags = 0) {
     if (!scene || !outScene) return nullArgument(who, err, cap);
+    // The medium stack of the Metal media semantics keeps material ids in 16 bits (csrc/kernels/wavefront.hip mediumWithEntry), and which
+    // semantics a render asks for is not known here: a table the ids cannot address is refused for every one of them.
+    if (scene->materialCount > kMaxMaterials) return refuse(err, cap, std::string(who) + ": " + tooManyMaterials(scene->materialCount));
     if (ptr_device_count() <= device || device < 0) {
         setErr(err, cap, std::string(who) + ": no such HIP device (the HIP path has no CPU fallback)");
         return 2;
@@ -928,7 +937,7 @@ struct BackgroundPixels {
 template <typename Resolve>
 void tracePass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, uint32_t sampleBase, uint32_t sppTotal, uint32_t passFlags,
                const uint32_t* dPixelOfLocal, uint32_t localPixels, hipStream_t stream, int mode, PtrRenderStats* stats, Resolve&& resolve,
-               const BackgroundPixels& background = BackgroundPixels{});
+               const BackgroundPixels& background = BackgroundPixels{}, const ptrhost::IterationHook* hook = nullptr);
 
 // One pass over `spp` samples per pixel starting at sample `sampleBase` of a frame of `sppTotal`; passFlags bit 0 = first pass of
 // the frame (output and counters start from zero), bit 1 = last pass (the running sum in dOut is divided by sppTotal).
@@ -1003,10 +1012,11 @@ void renderPass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, u
 // reads the per-sample accumulators: see renderPass), the stream joined and the figures of the pass.  dPixelOfLocal: the image pixel
 // of each of the pass's `localPixels` (> 0) local pixels, on the device.
 // `background`: pixels the pool never sees; k_background writes them on `stream` while the other groups' first launches run.
+// `hook`: null in every render; the stepping probe's (ptr_debug_path_states), called after the launches of every iteration.
 template <typename Resolve>
 void tracePass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, uint32_t sampleBase, uint32_t sppTotal, uint32_t passFlags,
                const uint32_t* dPixelOfLocal, uint32_t localPixels, hipStream_t stream, int mode, PtrRenderStats* stats, Resolve&& resolve,
-               const BackgroundPixels& background) {
+               const BackgroundPixels& background, const ptrhost::IterationHook* hook) {
     const bool count = (mode & 1) != 0;         // counting instantiation of the kernels
     const bool soloGroup = (mode & 2) != 0;     // one pool group: kernels run alone, for clean per-kernel timings
 
@@ -1106,6 +1116,7 @@ void tracePass(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, ui
             }
         }
         ++iterations;
+        if (hook) (*hook)(iterations - 1u, pool);
         if (iterations >= last.nextCheck || iterations >= maxIterations) {
             last = poll(ds, groups, rp, slots, iterations, last.queueDry, knobs.verbosePolls);
             if (last.allDone || last.runTail) break;
@@ -1186,15 +1197,17 @@ void renderBands(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, 
 }
 
 void traceItems(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, uint32_t sampleBase, const uint32_t* dPixelOfLocal,
-                uint32_t localPixels, hipStream_t stream, PtrRenderStats* stats, const std::function<void(const float4*)>& consume) {
+                uint32_t localPixels, hipStream_t stream, PtrRenderStats* stats, const std::function<void(const float4*)>& consume,
+                int mode, const IterationHook* hook) {
     // (pass flags 1: k_resolve, which launchResolve runs behind the flush of the outstanding connections, overwrites dScratch)
     const size_t scratchFloats = static_cast<size_t>(ptr_part_band_count(settings.height, 0u, 1u)) * PTR_BAND_ROWS * settings.width * 3u;
     ds.outBands.ensure(scratchFloats);
-    tracePass(ds, settings, spp, sampleBase, spp, 1u, dPixelOfLocal, localPixels, stream, 0, stats,
+    tracePass(ds, settings, spp, sampleBase, spp, 1u, dPixelOfLocal, localPixels, stream, mode, stats,
               [&](const RenderParams& rp, const PathPool& pool, LaunchTimer&) {
                   launchResolve(rp, pool, 1u, ds.outBands.ptr, stream);
                   consume(pool.itemAccum);
-              });
+              },
+              BackgroundPixels{}, hook);
 }
 
 void imagePixelOrder(uint32_t width, uint32_t height, std::vector<uint32_t>& out) { partitionPixels(width, height, 0u, 1u, out); }

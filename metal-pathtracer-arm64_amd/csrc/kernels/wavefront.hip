@@ -2203,7 +2203,11 @@ __global__ void __launch_bounds__(kTraceBlock) k_tail_run(RenderParams rp, Scene
                 shadeSlot<COUNT, SSS, TEX, kShadeTail>(rp, sc, pool, slot, true, false, 0u, counts, env);
                 __threadfence();
                 // k_connect's part: the records this visit queued
-                uint32_t bits = (__float_as_uint(pool.ray1[slot].w) >> kFlagPendingShift) & kFlagPendingMask;
+                const uint32_t flagsOut = __float_as_uint(pool.ray1[slot].w);
+                // a slot that took a leftover work item of its group's reservation starts a new path (alive at depth 0, no walk): the
+                // limit counts that path's visits from here, not the visits of the paths the lane has finished
+                if ((flagsOut & kFlagAlive) && !(flagsOut & kFlagWalk) && ((flagsOut >> kFlagDepthShift) & kFlagFieldMask) == 0u) visit = 0u;
+                uint32_t bits = (flagsOut >> kFlagPendingShift) & kFlagPendingMask;
                 while (bits != 0u) {
                     const uint32_t rec = static_cast<uint32_t>(__ffs(static_cast<int>(bits))) - 1u;
                     bits &= bits - 1u;

@@ -3,6 +3,7 @@
 #include <chrono>
 #include <cstring>
 #include <memory>
+#include <vector>
 
 #include "oracle_integrator.h"
 
@@ -58,6 +59,24 @@ double oracle_render_signatures(const OracleScene* s, const PtrSettings* setting
     const auto t0 = std::chrono::steady_clock::now();
     render(s->scene, s->desc, *settings, spp, threads, y0, y1, out_rgb, nullptr, out_signature, out_marginal);
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// The per-vertex recorder of render() (oracle_integrator.h PathSink): sample `sample` of the n pixels `pixels` (y * width + x),
+// out_rows n * vertex_cap * 68 words, out_finals n * 4 {radiance, 0}.  Returns non-zero for a pixel outside the image or named twice.
+int oracle_path_states(const OracleScene* s, const PtrSettings* settings, const uint32_t* pixels, uint64_t n, uint32_t sample,
+                       uint32_t vertex_cap, float* out_rows, float* out_finals) {
+    const uint64_t count = static_cast<uint64_t>(settings->width) * settings->height;
+    std::vector<int32_t> rowOfPixel(count, -1);
+    for (uint64_t i = 0; i < n; ++i) {
+        if (pixels[i] >= count || rowOfPixel[pixels[i]] >= 0) return 1;
+        rowOfPixel[pixels[i]] = static_cast<int32_t>(i);
+    }
+    std::memset(out_rows, 0, n * vertex_cap * kPathVertexWords * sizeof(float));
+    std::memset(out_finals, 0, n * 4 * sizeof(float));
+    std::vector<float> image(count * 3u);
+    const PathSink sink{rowOfPixel.data(), sample, vertex_cap, out_rows, out_finals};
+    render(s->scene, s->desc, *settings, 1u, 0u, 0u, settings->height, image.data(), nullptr, nullptr, nullptr, &sink);
+    return 0;
 }
 
 // Texture filtering rule (oracle_integrator.cpp "material textures"): in: n * 3 floats {u, v, lod}; out: n * 4 floats RGBA

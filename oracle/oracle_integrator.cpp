@@ -3,6 +3,8 @@
 #include "oracle_integrator.h"
 
 #include <atomic>
+#include <cmath>
+#include <functional>
 #include <cstring>
 #include <limits>
 #include <thread>
@@ -1422,7 +1424,9 @@ BsdfSample sampleBsdf(const PtrMaterial& m, V3 position, V3 normal, V3 wo, V3 in
         const float diffuseWeight = 1.0f - specWeight;
         V3 wi, f;
         float pdfSpec = 0.0f, pdfDiffuse = 0.0f;
-        if (rng.nextFloat() < specWeight) {
+        const float pick = rng.nextFloat();
+        r.pickMargin = std::fabs(pick - specWeight);
+        if (pick < specWeight) {
             if (roughness <= 1.0e-3f) {
                 wi = normalize(reflect(incidentDir, normal));
                 if (dot(normal, wi) <= 0.0f) return r;
@@ -1609,7 +1613,9 @@ BsdfSample sampleBsdf(const PtrMaterial& m, V3 position, V3 normal, V3 wo, V3 in
         const float Fr = fresnelDielectricExact(cosO, etaI, etaT, cosT);
         V3 direction, weight;
         V3 refracted;
-        if (rng.nextFloat() < Fr) {
+        const float pick = rng.nextFloat();
+        r.pickMargin = std::fabs(pick - Fr);
+        if (pick < Fr) {
             direction = reflect(incidentDir, normal);
             weight = splat(Fr);
         } else if (!refract(incidentDir, normal, relativeEta, refracted) || dot(refracted, refracted) <= 0.0f) {
@@ -2334,8 +2340,23 @@ bool rectLightAlong(const std::vector<int32_t>& lightIndexByRect, const std::vec
 
 }  // namespace
 
+namespace {
+// what the recorder notes of a vertex while render() walks it (PathSink)
+struct PathVertexNotes {
+    bool hit = false, roulette = false;
+    int sampled = 0;   // 0: the vertex took no BSDF sample, 1: a sample the path follows, 2: a sample that ends the path
+    uint32_t rngEntry = 0, rngRect = 0, rngEnv = 0, rngBsdf = 0, queuedMask = 0;
+    float rouletteDraw = 0.0f, rouletteThreshold = 0.0f;
+    float nextGap = 0.0f;   // distance from the closest hit to the next primitive along the ray when under 1e-5 of t (0: none so close)
+    V3 immediate, queued;
+    Ray ray;
+};
+inline void store3(float* at, V3 v) { at[0] = v.x, at[1] = v.y, at[2] = v.z; }
+}  // namespace
+
 void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& settings, uint32_t spp, uint32_t threads,
-            uint32_t yBegin, uint32_t yEnd, float* outRgb, RenderCounters* outCounters, uint32_t* outSignature, uint8_t* outMarginal) {
+            uint32_t yBegin, uint32_t yEnd, float* outRgb, RenderCounters* outCounters, uint32_t* outSignature, uint8_t* outMarginal,
+            const PathSink* sink) {
     const uint32_t width = settings.width, height = settings.height;
     const PtrMaterial* materials = desc.materials;
     const uint32_t materialCount = desc.materialCount;
@@ -2393,9 +2414,13 @@ void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& set
             return scene.occluded(o, d, kEpsilon, tMax, false, tcp);
         };
 
+        // the recorder (oracle_path_states): the rows of this pixel, or none
+        float* const sinkRows = (sink && sink->rowOfPixel[pixelIndex] >= 0)
+                                    ? sink->rows + static_cast<size_t>(sink->rowOfPixel[pixelIndex]) * sink->vertexCap * kPathVertexWords
+                                    : nullptr;
         for (uint32_t s = 0; s < targetSamples; ++s) {
             Rng rng;
-            rng.state = Rng::hash(seedBase ^ pixelIndex ^ (s * 0x9e3779b9u));
+            rng.state = Rng::hash(seedBase ^ pixelIndex ^ ((s + (sink ? sink->sample : 0u)) * 0x9e3779b9u));
             Ray ray = generateCameraRay(camera, width, height, x, y, rng);
             V3 throughput(1.0f, 1.0f, 1.0f), radiance;
             sig = 0u;
@@ -2413,6 +2438,54 @@ void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& set
 
             for (uint32_t depth = 0; depth < settings.maxDepth; ++depth) {
                 HitInfo hit;
+                // what the recorder keeps of this vertex; written when the vertex is left, by whichever way (`goesOn`: by none of the breaks)
+                PathVertexNotes notes;
+                notes.rngEntry = notes.rngRect = notes.rngEnv = notes.rngBsdf = rng.state;
+                notes.ray = ray;
+                const bool marginalBefore = marginal;
+                bool goesOn = false;
+                BsdfSample bs;
+                struct AtExit {
+                    std::function<void()> run;
+                    ~AtExit() { if (run) run(); }
+                } atExit;
+                if (sinkRows && depth < sink->vertexCap) {
+                    atExit.run = [&] {
+                        float* row = sinkRows + static_cast<size_t>(depth) * kPathVertexWords;
+                        uint32_t* word = reinterpret_cast<uint32_t*>(row);
+                        row[0] = 1.0f, row[1] = notes.hit ? 1.0f : 0.0f, row[2] = hit.t;
+                        word[3] = hit.primitiveType == GeomType::Mesh ? 0u : (hit.primitiveType == GeomType::Spheres ? 1u : 2u);
+                        word[4] = hit.primitiveIndex, word[5] = hit.materialIndex;
+                        row[6] = hit.frontFace ? 1.0f : 0.0f;
+                        word[7] = notes.rngEntry, word[8] = notes.rngRect, word[9] = notes.rngEnv, word[10] = notes.rngBsdf, word[11] = rng.state;
+                        store3(row + 12, bs.direction), store3(row + 15, bs.weight);
+                        row[18] = bs.pdf, row[19] = bs.isDelta ? 1.0f : 0.0f, row[20] = static_cast<float>(bs.mediumEvent);
+                        row[21] = static_cast<float>(notes.sampled);
+                        row[22] = notes.roulette ? 1.0f : 0.0f, row[23] = notes.rouletteDraw, row[24] = notes.rouletteThreshold;
+                        store3(row + 25, throughput);
+                        row[28] = lastBsdfPdf, row[29] = lastScatterWasDelta ? 1.0f : 0.0f;
+                        word[30] = specularDepth, word[31] = mediumDepth;
+                        for (uint32_t k = 0; k < kMaxMediumStack; ++k) word[32 + k] = mediumStack[k];
+                        store3(row + 40, ray.origin), store3(row + 43, ray.direction);
+                        store3(row + 46, notes.immediate), store3(row + 49, notes.queued);
+                        word[52] = notes.queuedMask;
+                        row[53] = (goesOn && depth + 1u < settings.maxDepth) ? 0.0f : 1.0f;
+                        word[54] = (bs.pickMargin < 1.0e-5f ? 1u : 0u) | ((notes.roulette && std::fabs(notes.rouletteDraw - notes.rouletteThreshold) < 1.0e-5f) ? 2u : 0u) |
+                                   ((marginal && !marginalBefore) ? 4u : 0u) | (notes.nextGap > 0.0f ? 8u : 0u);
+                        row[64] = notes.nextGap;
+                        store3(row + 55, notes.ray.origin), store3(row + 58, notes.ray.direction), store3(row + 61, hit.normal);
+                    };
+                }
+                // radiance of this vertex: what the wavefront adds at once (kind < 0) or queues as a light connection of record slot `kind`
+                auto addRadiance = [&](V3 c, int kind) {
+                    radiance += c;
+                    if (kind < 0) {
+                        notes.immediate += c;
+                    } else {
+                        notes.queued += c;
+                        if (c.x > 0.0f || c.y > 0.0f || c.z > 0.0f) notes.queuedMask |= 1u << kind;
+                    }
+                };
                 if (!trace(ray, hit)) {
                     if (wantSignature) sig = (sig & 0xFFFFu) | (sigHashStep(sig >> 16, 7u, 0u, 0u) << 16);
                     const V3 background = evaluateBackground(settings, env, ray.direction);
@@ -2424,8 +2497,14 @@ void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& set
                         if (denom > 0.0f) misWeight = lastBsdfPdf / denom;
                         misWeight = clampf(misWeight, kMisWeightClampMin, kMisWeightClampMax);
                     }
-                    radiance += clampFireflyContribution(throughput, background * misWeight, cp);
+                    addRadiance(clampFireflyContribution(throughput, background * misWeight, cp), -1);
                     break;
+                }
+                notes.hit = true;
+                if (sinkRows) {   // the next primitive along the ray, when it lies within 1e-5 of t behind the closest one
+                    RayHit behind;
+                    const float from = std::nextafter(hit.t, kInf);
+                    if (scene.intersect(ray.origin, ray.direction, from, hit.t * (1.0f + 1.0e-5f), behind)) notes.nextGap = std::max(behind.t - hit.t, 1.0e-30f);
                 }
                 if (!materials || materialCount == 0) break;
                 if (counting) {
@@ -2469,12 +2548,13 @@ void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& set
                         lastBsdfPdf = 1.0f;
                         lastScatterWasDelta = true;
                         specularDepth += 1u;
+                        goesOn = true;
                         continue;
                     }
                     // an emissive metallic-roughness surface adds its emission and the path goes on (M:6437-6442)
                     const V3 emission(materialPtr->emission);
                     if ((emission.x != 0.0f || emission.y != 0.0f || emission.z != 0.0f) && (hit.frontFace || hit.twoSided)) {
-                        radiance += clampFireflyContribution(throughput, emission, cp);
+                        addRadiance(clampFireflyContribution(throughput, emission, cp), -1);
                     }
                 }
                 const PtrMaterial& material = *materialPtr;
@@ -2493,7 +2573,7 @@ void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& set
                             if (denom > 0.0f) misWeight = lastBsdfPdf / denom;
                             misWeight = clampf(misWeight, kMisWeightClampMin, kMisWeightClampMax);
                         }
-                        radiance += clampFireflyContribution(throughput, emission * misWeight, cp);
+                        addRadiance(clampFireflyContribution(throughput, emission * misWeight, cp), -1);
                     }
                     break;
                 }
@@ -2503,11 +2583,12 @@ void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& set
                 if (!surfaceIsDelta && rectLightCount > 0) {  // rect-light NEE, E:2710-2772
                     V3 clamped;
                     if (rectLightNeeAt(scene, rectLights, env, settings, cp, shadowSlack, hit, material, shadingNormal, wo, throughput, rng, occluded,
-                                       outMarginal ? &marginal : nullptr, clamped)) {
-                        radiance += clamped;
+                                       (outMarginal || sinkRows) ? &marginal : nullptr, clamped)) {
+                        addRadiance(clamped, 0);
                         if (wantSignature && depth < 16u && (clamped.x > 0.0f || clamped.y > 0.0f || clamped.z > 0.0f)) sig |= 1u << depth;
                     }
                 }
+                notes.rngRect = notes.rngEnv = notes.rngBsdf = rng.state;
 
                 if (!surfaceIsDelta && envSampling) {  // environment NEE, E:2774-2811
                     // draw into named locals: argument evaluation order is unspecified (quirk Q10);
@@ -2526,13 +2607,13 @@ void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& set
                                 const float weight = neeWeight(es.pdf, be.pdf, cp);
                                 V3 contribution = (envRadiance * be.value) * nDotL;
                                 contribution *= weight / es.pdf;
-                                if (finite3(contribution)) radiance += clampFireflyContribution(throughput, contribution, cp);
+                                if (finite3(contribution)) addRadiance(clampFireflyContribution(throughput, contribution, cp), 1);
                             }
                         }
                     }
                 }
+                notes.rngEnv = notes.rngBsdf = rng.state;
 
-                BsdfSample bs;
                 bool usedRandomWalk = false;   // M:6650-6676
                 if (cp.metalSss && cp.sssMode == 2u && matType(material) == PTR_MAT_SUBSURFACE && material.sssParams[1] >= 0.5f && hit.frontFace) {
                     SssWalk walk;
@@ -2545,7 +2626,10 @@ void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& set
                     usedRandomWalk = outcome == WalkOutcome::Sample;
                 }
                 if (!usedRandomWalk) bs = sampleBsdf(material, hit.position, shadingNormal, wo, incidentDir, hit.frontFace, rng, cp);
+                notes.rngBsdf = rng.state;
+                notes.sampled = 2;
                 if (bs.pdf <= 0.0f || dot(bs.direction, bs.direction) <= 0.0f || !finite3(bs.weight)) break;
+                notes.sampled = 1;
 
                 if (media && bs.mediumEvent != 0) {  // M:6694-6709
                     if (bs.mediumEvent > 0) {
@@ -2570,7 +2654,7 @@ void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& set
 
                 // Extra "NEE along the specular direction" rays.  The specular-NEE (E:2856-2917) and MNEE
                 // (E:2919-2980) blocks are the same computation behind different gates.
-                auto envAlong = [&](V3 origin, V3 dir, V3 weight, float bsdfPdfFloorInput) {
+                auto envAlong = [&](V3 origin, V3 dir, V3 weight, float bsdfPdfFloorInput, int kind) {
                     if (occluded(origin, dir, kInf)) return;
                     const float envPdf = std::max(environmentPdf(*env, settings.environmentRotation, dir), kSpecularNeePdfFloor);
                     const float invEnvPdf = std::min(1.0f / envPdf, kSpecularNeeInvPdfClamp);
@@ -2580,21 +2664,21 @@ void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& set
                     misWeight = clampf(misWeight, kMisWeightClampMin, kMisWeightClampMax);
                     const V3 envColor = sampleEnvironment(*env, dir, settings.environmentRotation, settings.environmentIntensity);
                     const V3 c = (weight * envColor) * (misWeight * invEnvPdf);
-                    if (finite3(c)) radiance += clampFireflyContribution(throughput, c, cp);
+                    if (finite3(c)) addRadiance(clampFireflyContribution(throughput, c, cp), kind);
                 };
-                auto rectAlong = [&](V3 origin, V3 dir, V3 weight, float bsdfPdfFloorInput) {
+                auto rectAlong = [&](V3 origin, V3 dir, V3 weight, float bsdfPdfFloorInput, int kind) {
                     V3 clamped;
                     if (rectLightAlong(lightIndexByRect, rectLights, rectangles, rectangleCount, env, settings, cp, origin, dir, weight, bsdfPdfFloorInput,
                                        throughput, trace, clamped)) {
-                        radiance += clamped;
+                        addRadiance(clamped, kind);
                     }
                 };
 
                 if (specNeeEligible || mneeEligible) {
                     const V3 dir = normalize(bs.direction);
                     const V3 origin = offsetRayOrigin(hit, dir);
-                    if (envSampling) envAlong(origin, dir, bs.weight, bs.pdf);
-                    if (rectLightCount > 0) rectAlong(origin, dir, bs.weight, bs.pdf);
+                    if (envSampling) envAlong(origin, dir, bs.weight, bs.pdf, 2);
+                    if (rectLightCount > 0) rectAlong(origin, dir, bs.weight, bs.pdf, 3);
                 }
 
                 if (mneeEligible && settings.enableMneeSecondary) {  // two-bounce specular chain, E:2982-3096
@@ -2623,8 +2707,8 @@ void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& set
                                     const V3 secondOrigin = offsetRayOrigin(chainHit, secondDir);
                                     const V3 combinedWeight = bs.weight * cs.weight;
                                     const float chainPdf = bs.pdf * cs.pdf;
-                                    if (envSampling) envAlong(secondOrigin, secondDir, combinedWeight, chainPdf);
-                                    if (rectLightCount > 0) rectAlong(secondOrigin, secondDir, combinedWeight, chainPdf);
+                                    if (envSampling) envAlong(secondOrigin, secondDir, combinedWeight, chainPdf, 4);
+                                    if (rectLightCount > 0) rectAlong(secondOrigin, secondDir, combinedWeight, chainPdf, 4);
                                 }
                             }
                         }
@@ -2656,9 +2740,16 @@ void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& set
 
                 if (settings.enableRussianRoulette && depth >= 5) {
                     const float rrProb = clampf(maxComp, 0.05f, 0.95f);
-                    if (rng.nextFloat() > rrProb) break;
+                    const float rrDraw = rng.nextFloat();
+                    notes.roulette = true, notes.rouletteDraw = rrDraw, notes.rouletteThreshold = rrProb;
+                    if (rrDraw > rrProb) break;
                     throughput /= rrProb;
                 }
+                goesOn = true;
+            }
+            if (sinkRows) {
+                float* fin = sink->finals + static_cast<size_t>(sink->rowOfPixel[pixelIndex]) * 4u;
+                fin[0] = radiance.x, fin[1] = radiance.y, fin[2] = radiance.z, fin[3] = 0.0f;
             }
             pixelRadiance += radiance;
         }

@@ -100,6 +100,7 @@ struct BsdfSample {
     V3 exitNormal;               // random walk: outward normal at the exit (zero: use the shading normal of the entry)
     int lobe = 0;                // Metal metallic-roughness sampler: 0 diffuse, 1 specular, 2 transmission (ray-cone widening)
     float lobeRoughness = 0.0f;
+    float pickMargin = 1.0e30f;  // |draw - threshold| of the Fresnel / lobe pick, where the sampler takes one (the recorder's near-tie flag)
 };
 
 struct HitInfo {  // :97-107
@@ -167,8 +168,30 @@ void sssWalksBatch(const Scene& scene, const PtrSceneDesc& desc, const PtrSettin
 // Renders pixels with y in [y0, y1) (full width); out_rgb is the full W*H*3 image, other rows untouched.
 // out_signature / out_marginal (optional, W*H each): path signature of every pixel's last sample and whether one of its
 // rectangle-light shadow tests is decided within rounding noise of the ray length (deterministic-stream diagnostics).
+// sink (optional): the per-vertex recorder below; the loop body is the one every render runs.
+struct PathSink;
 void render(const Scene& scene, const PtrSceneDesc& desc, const PtrSettings& settings, uint32_t spp,
             uint32_t threads, uint32_t y0, uint32_t y1, float* out_rgb, RenderCounters* counters,
-            uint32_t* out_signature = nullptr, uint8_t* out_marginal = nullptr);
+            uint32_t* out_signature = nullptr, uint8_t* out_marginal = nullptr, const PathSink* sink = nullptr);
+
+// The per-vertex recorder of render() (oracle_path_states): sample `sample` of every pixel with rowOfPixel[y * width + x] = r >= 0 (spp 1)
+// writes vertex d < vertexCap to rows + (r * vertexCap + d) * kPathVertexWords and its radiance to finals + r * 4.  A row, floats unless
+// marked u (uint32): 0 valid; 1 hit; 2 t; 3u primitive type (0 mesh, 1 sphere, 2 rectangle); 4u primitive; 5u material index; 6 front face;
+// the random state 7u on entry, 8u after rectangle NEE, 9u after environment NEE, 10u after the BSDF sample, 11u after roulette (= on
+// leaving); the BSDF sample 12..14 direction, 15..17 weight, 18 pdf, 19 isDelta, 20 mediumEvent, 21 taken (0 none, 1 followed, 2 it ended
+// the path); roulette 22 taken, 23 draw, 24 threshold; the state afterwards 25..27 throughput, 28 lastBsdfPdf, 29 lastScatterWasDelta,
+// 30u specularDepth, 31u medium depth, 32u..39u medium stack, 40..45 next ray; radiance added here 46..48 at once (emission, background),
+// 49..51 by light connections (what the wavefront queues), 52u which of them were positive (bit k: record slot k of the wavefront: 0
+// rectangle NEE, 1 environment NEE, 2 / 3 specular environment / rectangle, 4 the MNEE chain); 53 the path ends here; 54u near ties
+// (bit 0 Fresnel / lobe pick within 1e-5, bit 1 roulette within 1e-5, bit 2 a shadow test within +-2e-6 of the ray length, bit 3 another
+// primitive within 1e-5 of t behind the closest hit); 55..60 the ray traced to this vertex; 61..63 the geometric normal; 64 that
+// primitive's distance from the closest hit (0: none so close); 65..67 0.
+constexpr uint32_t kPathVertexWords = 68;
+struct PathSink {
+    const int32_t* rowOfPixel;
+    uint32_t sample, vertexCap;
+    float* rows;
+    float* finals;
+};
 
 }  // namespace oracle

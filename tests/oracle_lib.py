@@ -52,6 +52,8 @@ def lib():
         l.oracle_sss_walk_begin.argtypes = [C.POINTER(pt.PtrMaterial), C.POINTER(pt.PtrSettings), fp, up, u64, fp, up]
         l.oracle_sss_walk_step.argtypes = [C.POINTER(pt.PtrMaterial), C.POINTER(pt.PtrSettings), fp, up, u64, fp, up]
         l.oracle_sss_walks.argtypes = [vp, C.POINTER(pt.PtrSettings), up, u64, u32, fp, fp]
+        l.oracle_path_states.argtypes = [vp, C.POINTER(pt.PtrSettings), up, u64, u32, u32, fp, fp]
+        l.oracle_path_states.restype = C.c_int
         _lib = l
     return _lib
 
@@ -156,6 +158,16 @@ class OracleScene:
         final = np.zeros((xys.shape[0], 24), dtype=np.float32)
         lib().oracle_sss_walks(self._h, C.byref(settings), _u(xys), xys.shape[0], step_cap, _f(steps), _f(final))
         return pt.sss_fields(steps, pt.SSS_WALK_STEP_FIELDS), pt.sss_fields(final, pt.SSS_WALK_FINAL_FIELDS)
+
+    def path_states(self, settings, pixels, sample=0, vertex_cap=64):
+        """The per-vertex recorder of the oracle's render loop (oracle/oracle_integrator.h PathSink): sample `sample` of the pixels [n]
+        (y * width + x).  Returns (rows [n, vertex_cap, 68] float32 - path_state_cases.ORACLE_ROW names the columns -, radiance [n, 3])."""
+        pixels = np.ascontiguousarray(pixels, dtype=np.uint32).reshape(-1)
+        rows = np.zeros((pixels.shape[0], vertex_cap, 68), dtype=np.float32)
+        final = np.zeros((pixels.shape[0], 4), dtype=np.float32)
+        rc = lib().oracle_path_states(self._h, C.byref(settings), _u(pixels), pixels.shape[0], sample, vertex_cap, _f(rows), _f(final))
+        assert rc == 0, "oracle_path_states: a pixel outside the image or named twice"
+        return rows, final[:, :3]
 
     def close(self):
         if self._h:
