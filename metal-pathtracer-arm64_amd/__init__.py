@@ -630,6 +630,33 @@ _TEMPORAL_SIGNATURES = {
 }
 TEMPORAL_SYMBOLS = tuple(_TEMPORAL_SIGNATURES)
 
+
+# ... and of include/ptr_temporal_cov.h (the same handle carrying the covariance of its colour): tests/test_temporal_cov_host.py
+class PtrTemporalCovParams(C.Structure):
+    """include/ptr_temporal_cov.h PtrTemporalCovParams; PtrTemporalCovParams.defaults() asks the library for its defaults."""
+    _fields_ = [("rejectSigma", C.c_float), ("flags", C.c_uint32)]
+
+    @classmethod
+    def defaults(cls, **overrides) -> "PtrTemporalCovParams":
+        p = cls()
+        load_library().ptr_temporal_cov_default_params(C.byref(p))
+        for k, v in overrides.items():
+            setattr(p, k, v)
+        return p
+
+
+_temporal_cov = C.POINTER(PtrTemporalCovParams)
+_TEMPORAL_COV_SIGNATURES = {
+    "ptr_temporal_cov_default_params": (None, [_temporal_cov]),
+    "ptr_temporal_cov_check_params": (_int, [_temporal_cov] + _err),
+    "ptr_temporal_create_cov": (_int, [_vp, _u32, _u32, _temporal, _temporal_cov, C.POINTER(_vp)] + _err),
+    "ptr_temporal_step_cov_device": (_int, [_vp, _settings, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _temporal_info] + _err),
+    "ptr_temporal_step_cov": (_int, [_vp, _settings, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _temporal_info] + _err),
+    # its test-only probe
+    "ptr_debug_temporal_accumulate_cov": (_int, [_u32, _u32, _temporal, _temporal_cov, _int] + [_fp] * 8 + [_int] + [_fp] * 5 + _err),
+}
+TEMPORAL_COV_SYMBOLS = tuple(_TEMPORAL_COV_SIGNATURES)
+
 # ptr_debug_scene_arrays / ptr_debug_dynamic_tables: name -> (selector, dtype, trailing shape)
 SCENE_ARRAYS = {"tris": (0, np.float32, (3, 4)), "triNormals": (1, np.float32, (3, 4)), "triUv": (2, np.float32, (4, 4)),
                 "triTangent": (3, np.float32, (3, 4)), "triBounds": (4, np.float32, (2, 4)), "sphereBounds": (5, np.float32, (2, 4)),
@@ -664,7 +691,7 @@ def load_library() -> C.CDLL:
     for name, (restype, argtypes) in list(_SIGNATURES.items()) + list(_POST_SIGNATURES.items()) + list(_STATS_SIGNATURES.items()) + \
             list(_ADAPTIVE_SIGNATURES.items()) + list(_MULTI_SIGNATURES.items()) + list(_FRAME_SIGNATURES.items()) + list(_MULTI_FRAME_SIGNATURES.items()) + \
             list(_DYNAMIC_SIGNATURES.items()) + list(_DEFORM_SIGNATURES.items()) + list(_DEFORM_DEVICE_SIGNATURES.items()) + \
-            list(_BACKGROUND_SIGNATURES.items()) + list(_TEMPORAL_SIGNATURES.items()) + list(_PBR_HIT_SIGNATURES.items()) + \
+            list(_BACKGROUND_SIGNATURES.items()) + list(_TEMPORAL_SIGNATURES.items()) + list(_TEMPORAL_COV_SIGNATURES.items()) + list(_PBR_HIT_SIGNATURES.items()) + \
             list(_SSS_WALK_SIGNATURES.items()) + list(_PATH_STATE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
@@ -1044,12 +1071,19 @@ class DeviceScene:
         _check(load_library().ptr_frame_create(self._h, C.byref(settings), C.byref(h), err, len(err)), err)
         return Frame(h, keepalive=self)
 
-    def temporal(self, width: int, height: int, params: Optional["PtrTemporalParams"] = None) -> "Temporal":
-        """ptr_temporal_create: a temporal-accumulation handle for width x height frames of this scene (include/ptr_temporal.h)."""
+    def temporal(self, width: int, height: int, params: Optional["PtrTemporalParams"] = None, cov=None) -> "Temporal":
+        """ptr_temporal_create: a temporal-accumulation handle for width x height frames of this scene (include/ptr_temporal.h).
+        cov=True or a PtrTemporalCovParams: ptr_temporal_create_cov, a handle that carries covariance (include/ptr_temporal_cov.h)."""
         h = C.c_void_p()
         err = _err_buf()
-        _check(load_library().ptr_temporal_create(self._h, width, height, C.byref(params) if params is not None else None, C.byref(h), err, len(err)), err)
-        return Temporal(h, width, height, self._device, keepalive=self)
+        p = C.byref(params) if params is not None else None
+        if cov is None or cov is False:
+            _check(load_library().ptr_temporal_create(self._h, width, height, p, C.byref(h), err, len(err)), err)
+            return Temporal(h, width, height, self._device, keepalive=self)
+        if cov is not True and not isinstance(cov, PtrTemporalCovParams):
+            raise PtrError("DeviceScene.temporal: cov is True or a PtrTemporalCovParams")
+        _check(load_library().ptr_temporal_create_cov(self._h, width, height, p, None if cov is True else C.byref(cov), C.byref(h), err, len(err)), err)
+        return Temporal(h, width, height, self._device, keepalive=self, carries_cov=True)
 
     def render_aovs(self, settings: PtrSettings, sample_index: int = 0) -> Tuple[np.ndarray, np.ndarray]:
         """First-hit feature buffers: ([H, W, 4] albedo rgb | hit flag, [H, W, 4] encoded normal | distance)."""
@@ -1342,10 +1376,12 @@ class Frame:
 
 class Temporal:
     """Temporal accumulation over the frames of a sequence (include/ptr_temporal.h): each step blends a frame with the history of the
-    surfaces it shows.  Made by DeviceScene.temporal(); the scene must be in the pose of the frame a step is given."""
+    surfaces it shows.  Made by DeviceScene.temporal(); the scene must be in the pose of the frame a step is given.  A handle made with
+    cov carries the covariance of its colour (include/ptr_temporal_cov.h): its steps take the frame's covariance and return the blend's;
+    the library refuses a step of the other kind."""
 
-    def __init__(self, handle: C.c_void_p, width: int, height: int, device: int, keepalive=None):
-        self._h, self._keepalive = handle, keepalive
+    def __init__(self, handle: C.c_void_p, width: int, height: int, device: int, keepalive=None, carries_cov: bool = False):
+        self._h, self._keepalive, self.carries_cov = handle, keepalive, bool(carries_cov)
         self.width, self.height, self._device = int(width), int(height), int(device)
 
     def _handle(self):
@@ -1353,13 +1389,20 @@ class Temporal:
             raise PtrError("the temporal handle is closed")
         return self._h
 
-    def step(self, settings: PtrSettings, rgb: np.ndarray, want_length: bool = True, want_aovs: bool = False) -> dict:
-        """ptr_temporal_step on a host image [H, W, 3]: {"rgb", "info", and when asked for "length" [H, W], "albedo" and "normal" [H, W, 4]}."""
+    def step(self, settings: PtrSettings, rgb: np.ndarray, cov: Optional[np.ndarray] = None, want_length: bool = True,
+             want_aovs: bool = False) -> dict:
+        """ptr_temporal_step on a host image [H, W, 3]: {"rgb", "info", and when asked for "length" [H, W], "albedo" and "normal" [H, W, 4]}.
+        With cov [H, W, 6] (a handle that carries covariance needs it): ptr_temporal_step_cov, and "cov" [H, W, 6] beside them."""
         rgb = np.ascontiguousarray(rgb, np.float32)
         if rgb.size != self.width * self.height * 3:
             raise PtrError("Temporal.step: the image has %d floats, not %d x %d x 3" % (rgb.size, self.height, self.width))
         h, w = self.height, self.width
         out = {"rgb": np.zeros((h, w, 3), np.float32)}
+        if cov is not None:
+            cov = np.ascontiguousarray(cov, np.float32)
+            if cov.size != w * h * 6:
+                raise PtrError("Temporal.step: the covariance has %d floats, not %d x %d x 6" % (cov.size, h, w))
+            out["cov"] = np.zeros((h, w, 6), np.float32)
         if want_length:
             out["length"] = np.zeros((h, w), np.float32)
         if want_aovs:
@@ -1367,23 +1410,34 @@ class Temporal:
         opt = lambda key: _fptr(out[key]) if key in out else None
         info = PtrTemporalInfo()
         err = _err_buf()
-        _check(load_library().ptr_temporal_step(self._handle(), C.byref(settings), _fptr(rgb), _fptr(out["rgb"]), opt("length"), opt("albedo"),
-                                                opt("normal"), C.byref(info), err, len(err)), err)
+        if cov is not None:
+            _check(load_library().ptr_temporal_step_cov(self._handle(), C.byref(settings), _fptr(rgb), _fptr(cov), _fptr(out["rgb"]), _fptr(out["cov"]),
+                                                        opt("length"), opt("albedo"), opt("normal"), C.byref(info), err, len(err)), err)
+        else:
+            _check(load_library().ptr_temporal_step(self._handle(), C.byref(settings), _fptr(rgb), _fptr(out["rgb"]), opt("length"), opt("albedo"),
+                                                    opt("normal"), C.byref(info), err, len(err)), err)
         out["info"] = info.as_dict()
         return out
 
     def step_device(self, settings: PtrSettings, rgb, out_rgb=None, out_length=None, out_albedo=None, out_normal=None, stream=None,
-                    want_info: bool = False) -> Optional[dict]:
+                    want_info: bool = False, cov=None, out_cov=None) -> Optional[dict]:
         """ptr_temporal_step_device on torch tensors of the scene's device, float32 and contiguous, passed by data_ptr(): rgb [H, W, 3];
         out_rgb (None: rgb itself, filtered in place); out_length [H, W], out_albedo and out_normal [H, W, 4] may be None.  The step is
         enqueued on `stream` (a raw stream handle; None: torch's current stream of the scene's device) and the call returns at once,
-        unless want_info: then it waits and returns PtrTemporalInfo as a dict."""
+        unless want_info: then it waits and returns PtrTemporalInfo as a dict.  With cov [H, W, 6] (a handle that carries covariance needs
+        it): ptr_temporal_step_cov_device; out_cov [H, W, 6] (None: cov itself, in place) goes as it is into denoise_device(d_cov=...)."""
         if out_rgb is None:
             out_rgb = rgb
+        if cov is not None and out_cov is None:
+            out_cov = cov
+        if cov is None and out_cov is not None:
+            raise PtrError("Temporal.step_device: out_cov without cov")
         pixels = self.width * self.height
         ptrs = []
-        for name, t, floats in (("rgb", rgb, 3), ("out_rgb", out_rgb, 3), ("out_length", out_length, 1), ("out_albedo", out_albedo, 4),
-                                ("out_normal", out_normal, 4)):
+        for name, t, floats in (("rgb", rgb, 3), ("cov", cov, 6), ("out_rgb", out_rgb, 3), ("out_cov", out_cov, 6), ("out_length", out_length, 1),
+                                ("out_albedo", out_albedo, 4), ("out_normal", out_normal, 4)):
+            if t is None and name in ("cov", "out_cov"):
+                continue
             if t is None:
                 ptrs.append(None)
                 continue
@@ -1401,8 +1455,8 @@ class Temporal:
             stream = torch.cuda.current_stream(self._device).cuda_stream
         info = PtrTemporalInfo()
         err = _err_buf()
-        _check(load_library().ptr_temporal_step_device(self._handle(), C.byref(settings), *ptrs, C.c_void_p(stream),
-                                                       C.byref(info) if want_info else None, err, len(err)), err)
+        fn = load_library().ptr_temporal_step_device if cov is None else load_library().ptr_temporal_step_cov_device
+        _check(fn(self._handle(), C.byref(settings), *ptrs, C.c_void_p(stream), C.byref(info) if want_info else None, err, len(err)), err)
         return info.as_dict() if want_info else None
 
     def records(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -1455,6 +1509,33 @@ def debug_temporal_accumulate(rgb: np.ndarray, cur_records, prev_records, histor
                                                         _fptr(cams[0]), _fptr(cams[1]), device, _fptr(out), _fptr(length), _fptr(hist), err,
                                                         len(err)), err)
     return out, length, hist
+
+
+def debug_temporal_accumulate_cov(rgb: np.ndarray, cov: np.ndarray, cur_records, prev_records, history: np.ndarray, cov_history: np.ndarray,
+                                  cam_cur, cam_prev, params: Optional[PtrTemporalParams] = None,
+                                  cov_params: Optional[PtrTemporalCovParams] = None, has_history: bool = True, device: int = 0):
+    """ptr_debug_temporal_accumulate_cov: k_temporal_accumulate_cov alone.  The arguments of debug_temporal_accumulate, and cov and
+    cov_history [H, W, 6].  Returns (rgb [H, W, 3], length [H, W], history [H, W, 4], cov [H, W, 6], cov history [H, W, 6])."""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    h, w = rgb.shape[:2]
+    cov = np.ascontiguousarray(cov, np.float32).reshape(h, w, 6)
+    cov_history = np.ascontiguousarray(cov_history, np.float32).reshape(h, w, 6)
+    cur = np.ascontiguousarray(np.stack([np.asarray(r, np.float32).reshape(h, w, 4) for r in cur_records]))
+    prev = np.ascontiguousarray(np.stack([np.asarray(r, np.float32).reshape(h, w, 4) for r in prev_records]))
+    history = np.ascontiguousarray(history, np.float32).reshape(h, w, 4)
+    cams = [np.ascontiguousarray(c, np.float32).reshape(12) for c in (cam_cur, cam_prev)]
+    if len(cur) != 3 or len(prev) != 2:
+        raise PtrError("debug_temporal_accumulate_cov: three current and two previous records")
+    p = params if params is not None else PtrTemporalParams.defaults()
+    cp = cov_params if cov_params is not None else PtrTemporalCovParams.defaults()
+    out, length, hist = np.zeros((h, w, 3), np.float32), np.zeros((h, w), np.float32), np.zeros((h, w, 4), np.float32)
+    out_cov, cov_hist = np.zeros((h, w, 6), np.float32), np.zeros((h, w, 6), np.float32)
+    err = _err_buf()
+    _check(load_library().ptr_debug_temporal_accumulate_cov(w, h, C.byref(p), C.byref(cp), int(has_history), _fptr(rgb), _fptr(cov), _fptr(cur),
+                                                            _fptr(prev), _fptr(history), _fptr(cov_history), _fptr(cams[0]), _fptr(cams[1]), device,
+                                                            _fptr(out), _fptr(out_cov), _fptr(length), _fptr(hist), _fptr(cov_hist), err,
+                                                            len(err)), err)
+    return out, length, hist, out_cov, cov_hist
 
 
 def debug_frame(samples: np.ndarray, device: int = 0) -> Frame:

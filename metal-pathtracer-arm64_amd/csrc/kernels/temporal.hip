@@ -6,6 +6,10 @@
 // three records (3 x 16 B), its colour (12 B) and its outputs (12 B + 4 B + 16 B), and gathers up to four taps of three 16 B loads each
 // (previous R0, previous R1, history), which neighbouring lanes mostly share.  No LDS, no atomics, nothing passes between workgroups:
 // the history is read from one buffer and written to the other.
+//
+// k_temporal_accumulate_cov is the same body (temporal_pixel.inc) with the covariance rule of include/ptr_temporal_cov.h compiled in
+// (restated in tests/temporal_cov_ref.py): a lane also streams its frame covariance (3 x 8 B), out_cov (3 x 8 B) and its covariance
+// history (16 B + 8 B), 164 B of its own against 92 B, and a tap is 16 B + 8 B more, 72 B against 48 B.
 #include <hip/hip_runtime.h>
 
 #include "temporal.h"
@@ -46,62 +50,46 @@ __device__ __forceinline__ bool project(const Cam& cam, f3 y, float width, float
 __global__ void __launch_bounds__(kTemporalBlock) k_temporal_accumulate(const float* rgb, TemporalBuffers buf, Cam cur, Cam prev,
                                                                          uint32_t width, uint32_t height, float maxHistory, float normalCos,
                                                                          float planeTolerance, uint32_t hasHistory, float* out, float* outLength) {
-    const uint32_t i = blockIdx.x * kTemporalBlock + threadIdx.x;
-    if (i >= width * height) return;
-    const size_t at = static_cast<size_t>(i) * 3u;
-    const f3 c = mk3(rgb[at], rgb[at + 1u], rgb[at + 2u]);   // (read before `out`, which may be the same buffer, is written)
-    const float4 r0 = buf.r0[i], r2 = buf.r2[i];
-    f3 result = c;
-    float length = 1.0f;
-    if (__float_as_uint(r2.w) == kMissWord || !finite3(c)) {
-        length = 0.0f;   // step 1
-    } else if (hasHistory) {
-        const float4 r1 = buf.r1[i];
-        const f3 xPrev = mk3(r2), n = mk3(r1);
-        const float w = static_cast<float>(width), h = static_cast<float>(height);
-        float fcx, fcy, fpx, fpy;
-        if (project(cur, mk3(r0), w, h, fcx, fcy) && project(prev, xPrev, w, h, fpx, fpy)) {
-            const uint32_t px = i % width, py = i / width;
-            const float sx = static_cast<float>(px) + (fpx - fcx), sy = static_cast<float>(py) + (fpy - fcy);
-            if (__builtin_isfinite(sx) && __builtin_isfinite(sy)) {
-                const float x0 = floorf(sx), y0 = floorf(sy);
-                const float ax = sx - x0, ay = sy - y0;
-                const float bx[2] = {1.0f - ax, ax}, by[2] = {1.0f - ay, ay};
-                const f3 toCamera = xPrev - prev.o;
-                const float bound = planeTolerance * sqrtf(dot(toCamera, toCamera));
-                float B = 0.0f, Sn = 0.0f;
-                f3 Sc = mk3(0.0f);
+#define PTR_TEMPORAL_COV 0
+#include "temporal_pixel.inc"
+#undef PTR_TEMPORAL_COV
+}
+
+// What the covariance rule (include/ptr_temporal_cov.h) adds to a pixel's inputs and outputs.  The frame's covariance and out_cov are six
+// floats per pixel in image order, read and written as three 8 B pairs; a covariance history is two planes, (rr, gg, bb, rg) in 16 B and
+// (rb, gb) in 8 B per pixel, so that a tap is one load of each.
+struct CovIo {
+    const float2* cov;        // may be the buffer outCov is
+    float2* outCov;
+    const float4* historyA;   // never read without history
+    const float2* historyB;
+    float4* historyAOut;      // different buffers from historyA / historyB, as historyOut is from history
+    float2* historyBOut;
+    float rejectSigma;
+};
+
+__device__ __forceinline__ float lum(f3 x) { return (0.2126f * x.x + 0.7152f * x.y) + 0.0722f * x.z; }
+
+// C as (rr, gg, bb, rg, rb, gb)
+__device__ __forceinline__ float lumvar(const float (&C)[6]) {
+    constexpr float k[3] = {0.2126f, 0.7152f, 0.0722f};
+    constexpr int at[3][3] = {{0, 3, 4}, {3, 1, 5}, {4, 5, 2}};
+    float v = 0.0f;
 #pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float b = bx[k & 1] * by[k >> 1];
-                    const float tx = x0 + static_cast<float>(k & 1), ty = y0 + static_cast<float>(k >> 1);
-                    if (!(b > 0.0f && tx >= 0.0f && tx < w && ty >= 0.0f && ty < h)) continue;
-                    const uint32_t q = static_cast<uint32_t>(ty) * width + static_cast<uint32_t>(tx);
-                    const float4 hq = buf.history[q], q0 = buf.prevR0[q], q1 = buf.prevR1[q];
-                    const f3 nq = mk3(q1);
-                    const bool counts = hq.w >= 1.0f && finite3(mk3(hq)) && __float_as_uint(q0.w) == __float_as_uint(r0.w) &&
-                                        dot(nq, n) >= normalCos && fabsf(dot(xPrev - mk3(q0), nq)) <= bound;
-                    if (!counts) continue;
-                    B = B + b;
-                    Sc = Sc + b * mk3(hq);
-                    Sn = Sn + b * hq.w;
-                }
-                if (B > 0.0f) {
-                    const f3 hist = Sc / B;
-                    const float N = Sn / B;
-                    const float grown = N + 1.0f;
-                    length = grown < maxHistory ? grown : maxHistory;
-                    const float a = 1.0f / length;
-                    result = hist + (c - hist) * a;
-                }
-            }
-        }
+    for (int c = 0; c < 3; ++c) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) v = v + (k[c] * k[d]) * C[at[c][d]];
     }
-    buf.historyOut[i] = mk4(result, length);
-    out[at] = result.x;
-    out[at + 1u] = result.y;
-    out[at + 2u] = result.z;
-    if (outLength) outLength[i] = length;
+    return __builtin_isfinite(v) && v > 0.0f ? v : 0.0f;
+}
+
+__global__ void __launch_bounds__(kTemporalBlock) k_temporal_accumulate_cov(const float* rgb, TemporalBuffers buf, CovIo cv, Cam cur, Cam prev,
+                                                                             uint32_t width, uint32_t height, float maxHistory, float normalCos,
+                                                                             float planeTolerance, uint32_t hasHistory, float* out,
+                                                                             float* outLength) {
+#define PTR_TEMPORAL_COV 1
+#include "temporal_pixel.inc"
+#undef PTR_TEMPORAL_COV
 }
 
 }  // namespace
@@ -112,6 +100,17 @@ void launchTemporalAccumulate(const float* dRgb, const TemporalBuffers& buf, con
     hipLaunchKernelGGL(k_temporal_accumulate, dim3((pixels + kTemporalBlock - 1u) / kTemporalBlock), dim3(kTemporalBlock), 0, stream, dRgb, buf,
                        camOf(cur), camOf(prev), width, height, static_cast<float>(p.maxHistory), p.normalCos, p.planeTolerance, hasHistory ? 1u : 0u,
                        dOut, dLength);
+}
+
+void launchTemporalAccumulateCov(const float* dRgb, const TemporalBuffers& buf, const TemporalCovBuffers& cov, const TemporalCamera& cur,
+                                 const TemporalCamera& prev, uint32_t width, uint32_t height, const PtrTemporalParams& p, float rejectSigma,
+                                 bool hasHistory, float* dOut, float* dLength, hipStream_t stream) {
+    const uint32_t pixels = width * height;
+    const CovIo cv{reinterpret_cast<const float2*>(cov.cov), reinterpret_cast<float2*>(cov.outCov), covPlaneA(cov.history, pixels),
+                   covPlaneB(cov.history, pixels), covPlaneA(cov.historyOut, pixels), covPlaneB(cov.historyOut, pixels), rejectSigma};
+    hipLaunchKernelGGL(k_temporal_accumulate_cov, dim3((pixels + kTemporalBlock - 1u) / kTemporalBlock), dim3(kTemporalBlock), 0, stream, dRgb, buf,
+                       cv, camOf(cur), camOf(prev), width, height, static_cast<float>(p.maxHistory), p.normalCos, p.planeTolerance,
+                       hasHistory ? 1u : 0u, dOut, dLength);
 }
 
 }  // namespace ptrk

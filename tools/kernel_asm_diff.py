@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel comparison of the gfx950 assembly of kernels/wavefront.hip in two source trees (no GPU needed):
-    python3 tools/kernel_asm_diff.py <tree A> <tree B> [filter regex]
+    python3 tools/kernel_asm_diff.py <tree A> <tree B> [filter regex [kernel file, kernels/wavefront.hip by default]]
 Each tree's file is compiled with its own Makefile's HIPFLAGS plus -S --cuda-device-only, from its csrc directory, so the file name - which
 the HIP compilation-unit id is derived from - is the same in both.  The assembly is split by function label and stripped of comments;
 per function the output says `identical`, or gives the two instruction counts and the number of differing lines.  Text only: nothing
@@ -16,13 +16,13 @@ from concurrent.futures import ThreadPoolExecutor
 CSRC = "metal-pathtracer-arm64_amd/csrc"
 
 
-def assembly(tree):
+def assembly(tree, source="kernels/wavefront.hip"):
     csrc = os.path.join(tree, CSRC)
     show = ["make", "-s", "--no-print-directory", "--eval", "kernel-asm-flags: ; @echo $(HIPCC) $(HIPFLAGS)", "kernel-asm-flags"]
     flags = subprocess.run(show, cwd=csrc, check=True, capture_output=True, text=True).stdout.split()
     with tempfile.TemporaryDirectory() as tmp:
-        out = os.path.join(tmp, "wavefront.s")
-        subprocess.run(flags + ["-S", "--cuda-device-only", "kernels/wavefront.hip", "-o", out], cwd=csrc, check=True)
+        out = os.path.join(tmp, "kernel.s")
+        subprocess.run(flags + ["-S", "--cuda-device-only", source, "-o", out], cwd=csrc, check=True)
         with open(out) as f:
             return f.read()
 
@@ -63,7 +63,7 @@ def differing(a, b):
 def main():
     pattern = re.compile(sys.argv[3] if len(sys.argv) > 3 else ".")
     with ThreadPoolExecutor(2) as pool:
-        a, b = (functions(t) for t in pool.map(assembly, sys.argv[1:3]))
+        a, b = (functions(t) for t in pool.map(lambda tree: assembly(tree, *sys.argv[4:5]), sys.argv[1:3]))
     for name in sorted(set(a) | set(b)):
         if not pattern.search(name):
             continue
