@@ -13,7 +13,7 @@
  *
  * The node format (float, quantised binary, four-wide; PTR_QUANTIZED_NODES and PTR_WIDE_NODES) is decided once, at upload, and kept:
  * PtrUpdateInfo::cellOverExtent tells when a fresh upload would have chosen otherwise.  A refit does not rebuild: when boxes overlap
- * much more than a fresh tree's would, the caller uploads again.
+ * much more than a fresh tree's would, ptr_rebuild.h measures it (ptr_scene_tree_cost) and rebuilds the tree above the leaves on the device.
  *
  * This header moves whole meshes rigidly.  ptr_deform.h adds, for scenes uploaded with its flags, new vertex data for a mesh and new
  * places for spheres and rectangles, the lights among them.  Materials, emission, textures, uv coordinates and topology stay;

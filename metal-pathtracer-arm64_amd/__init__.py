@@ -657,6 +657,50 @@ _TEMPORAL_COV_SIGNATURES = {
 }
 TEMPORAL_COV_SYMBOLS = tuple(_TEMPORAL_COV_SIGNATURES)
 
+PTR_REBUILD_KEEP_IF_BETTER = 1
+
+
+class PtrRebuildInfo(C.Structure):
+    """include/ptr_rebuild.h PtrRebuildInfo."""
+    _fields_ = [
+        ("totalSeconds", C.c_double),
+        ("costBefore", C.c_double),
+        ("costAfter", C.c_double),
+        ("keysSortMs", C.c_double),
+        ("topologyMs", C.c_double),
+        ("fitMs", C.c_double),
+        ("quantiseMs", C.c_double),
+        ("wideMs", C.c_double),
+        ("nodes", C.c_uint64),
+        ("levels", C.c_uint64),
+        ("wideNodes", C.c_uint64),
+        ("wideDepth", C.c_uint64),
+        ("leaves", C.c_uint64),
+        ("installed", C.c_uint32),
+        ("pad", C.c_uint32),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: getattr(self, name) for name, _ in self._fields_ if name != "pad"}
+
+
+# ... and of include/ptr_rebuild.h (tree cost and the rebuild above the leaves): tests/test_rebuild_host.py holds it against that header
+_REBUILD_SIGNATURES = {
+    "ptr_scene_tree_cost": (_int, [_vp, _vp, C.POINTER(C.c_double)] + _err),
+    "ptr_scene_rebuild_tree": (_int, [_vp, _u32, _vp, C.POINTER(PtrRebuildInfo)] + _err),
+    # its test-only probes
+    "ptr_debug_rebuild_arrays": (_int, [_vp, _u32, _vp, _u64, _u64p]),
+    "ptr_debug_rebuild_tables": (_int, [_fp, _u32, _u32, _vp, _u64, _u64p] + _err),
+}
+REBUILD_SYMBOLS = tuple(_REBUILD_SIGNATURES)
+# ptr_debug_rebuild_arrays / ptr_debug_rebuild_tables: name -> (selector, dtype, trailing shape)
+REBUILD_ARRAYS = {"schedule": (0, np.uint32, ()), "levelOffsets": (1, np.uint32, ()), "wideSource": (2, np.uint32, (4,)), "info": (3, np.uint32, ()),
+                  "leafTable": (4, np.uint32, ()), "pointers": (5, np.uint64, ())}
+REBUILD_ARRAY_INFO = ("nodes", "levels", "wide_nodes", "wide_depth", "stack_limit", "leaves")
+REBUILD_TABLES = {"schedule": (0, np.uint32, ()), "levelOffsets": (1, np.uint32, ()), "grid": (2, np.float32, (3,)), "qnodes": (3, np.uint32, (2, 4)),
+                  "wnodes": (4, np.uint32, (4, 4)), "wideSource": (5, np.uint32, (4,)), "wideDepth": (6, np.uint32, ()), "sah": (7, np.float64, ()),
+                  "leafTable": (8, np.uint32, ()), "depthCheck": (9, np.uint32, ())}
+
 # ptr_debug_scene_arrays / ptr_debug_dynamic_tables: name -> (selector, dtype, trailing shape)
 SCENE_ARRAYS = {"tris": (0, np.float32, (3, 4)), "triNormals": (1, np.float32, (3, 4)), "triUv": (2, np.float32, (4, 4)),
                 "triTangent": (3, np.float32, (3, 4)), "triBounds": (4, np.float32, (2, 4)), "sphereBounds": (5, np.float32, (2, 4)),
@@ -692,7 +736,7 @@ def load_library() -> C.CDLL:
             list(_ADAPTIVE_SIGNATURES.items()) + list(_MULTI_SIGNATURES.items()) + list(_FRAME_SIGNATURES.items()) + list(_MULTI_FRAME_SIGNATURES.items()) + \
             list(_DYNAMIC_SIGNATURES.items()) + list(_DEFORM_SIGNATURES.items()) + list(_DEFORM_DEVICE_SIGNATURES.items()) + \
             list(_BACKGROUND_SIGNATURES.items()) + list(_TEMPORAL_SIGNATURES.items()) + list(_TEMPORAL_COV_SIGNATURES.items()) + list(_PBR_HIT_SIGNATURES.items()) + \
-            list(_SSS_WALK_SIGNATURES.items()) + list(_PATH_STATE_SIGNATURES.items()):
+            list(_SSS_WALK_SIGNATURES.items()) + list(_PATH_STATE_SIGNATURES.items()) + list(_REBUILD_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -934,6 +978,40 @@ class DeviceScene:
         err = _err_buf()
         _check(load_library().ptr_scene_set_rects(self._h, items, len(rects), C.c_void_p(stream), C.byref(info), err, len(err)), err)
         return info.as_dict()
+
+    def tree_cost(self, stream: int = 0) -> float:
+        """ptr_scene_tree_cost: the builder's SAH figure of the scene's current tree, computed on the device in float64."""
+        cost = C.c_double(0.0)
+        err = _err_buf()
+        _check(load_library().ptr_scene_tree_cost(self._h, C.c_void_p(stream), C.byref(cost), err, len(err)), err)
+        return float(cost.value)
+
+    def rebuild_tree(self, keep_if_better: bool = True, stream: int = 0) -> dict:
+        """ptr_scene_rebuild_tree: a new tree above the upload's leaves, built on the device from the current geometry; with keep_if_better
+        it is installed only when its tree_cost() is below the current tree's.  Returns PtrRebuildInfo as a dict."""
+        info = PtrRebuildInfo()
+        err = _err_buf()
+        flags = PTR_REBUILD_KEEP_IF_BETTER if keep_if_better else 0
+        _check(load_library().ptr_scene_rebuild_tree(self._h, flags, C.c_void_p(stream), C.byref(info), err, len(err)), err)
+        return info.as_dict()
+
+    def rebuild_arrays(self, names=None) -> dict:
+        """ptr_debug_rebuild_arrays: the schedule, level offsets, wide-source table, leaf table and SceneView pointers of a dynamic scene as
+        it is now; "info" as a dict."""
+        lib = load_library()
+        out = {}
+        for name in (names or REBUILD_ARRAYS):
+            which, dtype, shape = REBUILD_ARRAYS[name]
+            size = C.c_uint64(0)
+            if lib.ptr_debug_rebuild_arrays(self._h, which, None, 0, C.byref(size)) != 0:
+                raise PtrError("ptr_debug_rebuild_arrays(%s) failed" % name)
+            buf = np.zeros(size.value // np.dtype(dtype).itemsize, dtype)
+            if lib.ptr_debug_rebuild_arrays(self._h, which, buf.ctypes.data_as(C.c_void_p), buf.nbytes, C.byref(size)) != 0:
+                raise PtrError("ptr_debug_rebuild_arrays(%s) failed" % name)
+            out[name] = buf.reshape((-1,) + shape)
+        if "info" in out:
+            out["info"] = dict(zip(REBUILD_ARRAY_INFO, (int(v) for v in out["info"])))
+        return out
 
     def arrays(self, names=None) -> dict:
         """ptr_debug_scene_arrays: the named device arrays (all of SCENE_ARRAYS by default) as numpy arrays."""
@@ -2086,6 +2164,28 @@ def debug_dynamic_tables(desc: PtrSceneDesc, names=None) -> dict:
         out[name] = buf.reshape(2, 3) if name == "grid" else buf.reshape((-1,) + shape)
     if "info" in out:
         out["info"] = dict(zip(DYNAMIC_TABLE_INFO, (int(v) for v in out["info"])))
+    return out
+
+
+def debug_rebuild_tables(nodes: np.ndarray, names=None) -> dict:
+    """ptr_debug_rebuild_tables (host only): the builder's own functions on a preorder array of 64 B float nodes, as numpy arrays ("sah" a
+    float, "wideDepth" and "depthCheck" ints).  Raises PtrError for what the probe refuses ("depthCheck": a tree too deep to install)."""
+    lib = load_library()
+    nodes = np.ascontiguousarray(nodes, np.float32).reshape(-1, 16)
+    out = {}
+    for name in (names or [n for n in REBUILD_TABLES if n != "depthCheck"]):
+        which, dtype, shape = REBUILD_TABLES[name]
+        size = C.c_uint64(0)
+        err = _err_buf()
+        _check(lib.ptr_debug_rebuild_tables(_fptr(nodes), len(nodes), which, None, 0, C.byref(size), err, len(err)), err)
+        buf = np.zeros(size.value // np.dtype(dtype).itemsize, dtype)
+        _check(lib.ptr_debug_rebuild_tables(_fptr(nodes), len(nodes), which, buf.ctypes.data_as(C.c_void_p), buf.nbytes, C.byref(size), err, len(err)), err)
+        if name == "grid":
+            out[name] = buf.reshape(2, 3)
+        elif name in ("sah", "wideDepth", "depthCheck"):
+            out[name] = buf[0].item()
+        else:
+            out[name] = buf.reshape((-1,) + shape)
     return out
 
 

@@ -111,6 +111,28 @@ struct PrimitiveRecords {
     uint32_t triCount = 0;               // rows of the arrays, for the destinations' bounds
 };
 
+// What ptr_scene_rebuild_tree (include/ptr_rebuild.h) keeps, allocated at its first call: the second set of node arrays a rebuild
+// builds into (swapped with the scene's on install) and the scratch of its steps.
+struct RebuildState {
+    DeviceBuffer<float4> boxes;
+    DeviceBuffer<uint4> qnodes, wnodes;
+    DeviceBuffer<uint32_t> schedule, wideSource;
+    std::vector<uint32_t> levelOffsets;
+    DeviceBuffer<uint32_t> leaves;                 // the leaf table on the device
+    DeviceBuffer<uint64_t> keys, sortedKeys;
+    DeviceBuffer<uint8_t> sortScratch;             // rocprim's, sized for the largest of the two sorts and the scan
+    DeviceBuffer<uint32_t> first, parent, pre, iota, marks, wideIndex, small;   // small: level offsets (64 words), then reached (64 words)
+    DeviceBuffer<uint2> kids;
+    DeviceBuffer<uint8_t> heights, sortedHeights, depth;
+    DeviceBuffer<double> partials;                 // k_tree_cost: the block sums of two trees
+    hipEvent_t events[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    ~RebuildState() {
+        for (hipEvent_t e : events) {
+            if (e) (void)hipEventDestroy(e);
+        }
+    }
+};
+
 // What a dynamic scene (include/ptr_dynamic.h) keeps beside the arrays the kernels render from: ptr::DynamicTables on the device, the
 // float child boxes of every node, and the figures ptr_scene_set_mesh_transforms reports.  A static scene has none of it.
 struct DynamicScene {
@@ -142,6 +164,10 @@ struct DynamicScene {
     DeviceBuffer<uint32_t> checkFlags;
     // PTR_DYNAMIC_PRIMITIVES: where the rows of a rectangle and of a sphere live, and the records they currently hold
     PrimitiveRecords prims;
+    // include/ptr_rebuild.h: the leaf table of the upload's tree (host; it goes to the device at the first rebuild) and what the first
+    // ptr_scene_tree_cost / ptr_scene_rebuild_tree allocates
+    std::vector<uint32_t> leafTable;
+    std::unique_ptr<RebuildState> rebuild;
     // staging of the update calls, grown on demand and kept: a pinned host buffer and its device twin
     DeviceBuffer<float4> staging;
     void* pinned = nullptr;
@@ -320,6 +346,8 @@ void prepareScene(const PtrSceneDesc& desc, PreparedScene& ps, const char* cache
 void uploadScene(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceScene& ds);
 // the dynamic half of uploadScene (dynamic.cpp): ps.dyn and the float nodes to the device, ds.dynamic made
 void uploadDynamicTables(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceScene& ds);
+// the root box of the tree from node 0 (dynamic.cpp): the union of its children that exist
+bool rootBoxOf(const float4 row[4], float lo[3], float hi[3]);
 // the rectangle-light half of prepareScene: the light table of `desc` over the geometry `geo`
 void buildRectLights(const PtrSceneDesc& desc, const ptr::SceneGeometry& geo, std::vector<float>& lights, std::vector<int32_t>& lightIndexByRect,
                      uint32_t& lightCount, bool& lightsHaveTriangles);

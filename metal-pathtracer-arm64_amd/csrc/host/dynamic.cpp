@@ -11,6 +11,7 @@
 #include "device_scene.h"
 #include "ptr_deform_device.h"
 #include "ptr_dynamic.h"
+#include "rebuild_host.h"
 #include "vecmath.h"
 
 using namespace ptrk;
@@ -89,7 +90,25 @@ void uploadDynamicTables(const PtrSceneDesc& desc, const PreparedScene& ps, PtrD
     }
     for (hipEvent_t& e : dyn->events) HIP_CHECK(hipEventCreate(&e));
     HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&dyn->rootBox), 4 * sizeof(float4), hipHostMallocDefault));
+    ptr::BuildLeafTable(bvh.nodes.data(), bvh.nodeCount, dyn->leafTable);   // include/ptr_rebuild.h, step 1
     ds.dynamic = std::move(dyn);
+}
+
+bool rootBoxOf(const float4 row[4], float lo[3], float hi[3]) {
+    bool any = false;
+    for (int c = 0; c < 2; ++c) {
+        uint32_t ref;
+        std::memcpy(&ref, &row[c].w, 4);
+        if (ref == kRefEmpty) continue;
+        const float4 l = row[c * 2], h = row[c * 2 + 1];
+        const float cl[3] = {l.x, l.y, l.z}, ch[3] = {h.x, h.y, h.z};
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = any ? std::min(lo[a], cl[a]) : cl[a];
+            hi[a] = any ? std::max(hi[a], ch[a]) : ch[a];
+        }
+        any = true;
+    }
+    return any;
 }
 
 }  // namespace ptrhost
@@ -117,24 +136,6 @@ std::string sphereRows(PrimitiveRecords& prims, const PtrSphereUpdate& u, Scatte
 std::string rectRows(PrimitiveRecords& prims, const PtrRectUpdate& u, ScatterRows& out);
 int setPrimitives(const char* who, uint32_t kind, PtrDeviceScene* scene, const void* list, uint32_t count, void* stream, PtrUpdateInfo* info, char* err,
                   size_t err_cap);
-
-// the root box of the tree from node 0: the union of its children that exist
-bool rootBoxOf(const float4 row[4], float lo[3], float hi[3]) {
-    bool any = false;
-    for (int c = 0; c < 2; ++c) {
-        uint32_t ref;
-        std::memcpy(&ref, &row[c].w, 4);
-        if (ref == kRefEmpty) continue;
-        const float4 l = row[c * 2], h = row[c * 2 + 1];
-        const float cl[3] = {l.x, l.y, l.z}, ch[3] = {h.x, h.y, h.z};
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = any ? std::min(lo[a], cl[a]) : cl[a];
-            hi[a] = any ? std::max(hi[a], ch[a]) : ch[a];
-        }
-        any = true;
-    }
-    return any;
-}
 
 std::string matrixProblem(const float m[16], const ptr::MeshBake& bake) {
     for (int i = 0; i < 16; ++i) {
