@@ -17,8 +17,8 @@
  *
  * This header moves whole meshes rigidly.  ptr_deform.h adds, for scenes uploaded with its flags, new vertex data for a mesh and new
  * places for spheres and rectangles, the lights among them.  Materials, emission, textures, uv coordinates and topology stay;
- * ptr_render_multi*, ptr_multi_frame_* and the geometry cache (ptr_scene_upload_prepared) do not take part: one dynamic scene per
- * device handle.
+ * the one-shot ptr_render_multi* calls and the geometry cache (ptr_scene_upload_prepared) do not take part.  A frame on several devices
+ * (ptr_multi_frame.h) is created over dynamic scenes and updated in place on all of them through ptr_multi_dynamic.h.
  *
  * Resumable frames (ptr_frame.h) on a dynamic scene keep working.  The samples a frame holds belong to the pose they were taken in:
  * after an update call ptr_frame_reset before accumulating again.  Nothing here tracks that.

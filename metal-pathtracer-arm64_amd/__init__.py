@@ -701,6 +701,40 @@ REBUILD_TABLES = {"schedule": (0, np.uint32, ()), "levelOffsets": (1, np.uint32,
                   "wnodes": (4, np.uint32, (4, 4)), "wideSource": (5, np.uint32, (4,)), "wideDepth": (6, np.uint32, ()), "sah": (7, np.float64, ()),
                   "leafTable": (8, np.uint32, ()), "depthCheck": (9, np.uint32, ())}
 
+
+class PtrMultiUpdateInfo(C.Structure):
+    """include/ptr_multi_dynamic.h PtrMultiUpdateInfo."""
+    _fields_ = [("parts", C.c_uint32), ("stagedParts", C.c_uint32), ("totalSeconds", C.c_double), ("distributeSeconds", C.c_double),
+                ("partSeconds", C.c_double * MULTI_MAX_PARTS), ("first", PtrUpdateInfo)]
+
+    def as_dict(self) -> dict:
+        """PtrUpdateInfo of partition 0 as DeviceScene's update calls return it, with the figures of the fan-out beside it."""
+        out = self.first.as_dict()
+        out.update(parts=int(self.parts), stagedParts=int(self.stagedParts), totalSeconds=self.totalSeconds, distributeSeconds=self.distributeSeconds,
+                   partSeconds=list(self.partSeconds[:self.parts]), partTotalSeconds=self.first.totalSeconds)
+        return out
+
+
+# ... and of include/ptr_multi_dynamic.h (dynamic scenes on several devices): tests/test_multi_dynamic_host.py holds it against that header
+_multi_update = C.POINTER(PtrMultiUpdateInfo)
+_MULTI_DYNAMIC_SIGNATURES = {
+    "ptr_multi_frame_create_dynamic": (_int, [_desc, _settings, _int, _u32, C.POINTER(_vp)] + _err),
+    "ptr_multi_frame_debug_create_dynamic_on": (_int, [_desc, _settings, _u32, _ids, _int, C.POINTER(_vp)] + _err),
+    "ptr_multi_frame_is_dynamic": (_int, [_vp]),
+    "ptr_multi_frame_dynamic_flags": (_u32, [_vp]),
+    "ptr_multi_frame_set_mesh_transforms": (_int, [_vp, C.POINTER(PtrMeshTransform), _u32, _multi_update] + _err),
+    "ptr_multi_frame_set_mesh_vertices": (_int, [_vp, C.POINTER(PtrMeshVertices), _u32, _multi_update] + _err),
+    "ptr_multi_frame_set_spheres": (_int, [_vp, C.POINTER(PtrSphereUpdate), _u32, _multi_update] + _err),
+    "ptr_multi_frame_set_rects": (_int, [_vp, C.POINTER(PtrRectUpdate), _u32, _multi_update] + _err),
+    "ptr_multi_frame_set_mesh_vertices_device": (_int, [_vp, C.POINTER(PtrMeshVerticesDevice), _u32, _int, _vp, _multi_update] + _err),
+    "ptr_multi_frame_tree_cost": (_int, [_vp, C.POINTER(C.c_double)] + _err),
+    "ptr_multi_frame_rebuild_tree": (_int, [_vp, _u32, C.POINTER(PtrRebuildInfo)] + _err),
+    "ptr_multi_frame_part_scene": (_vp, [_vp, _u32]),
+    # its test-only probe
+    "ptr_multi_frame_debug_check_update": (_int, [_desc, _u32, _u32, _vp, _u32] + _err),
+}
+MULTI_DYNAMIC_SYMBOLS = tuple(_MULTI_DYNAMIC_SIGNATURES)
+
 # ptr_debug_scene_arrays / ptr_debug_dynamic_tables: name -> (selector, dtype, trailing shape)
 SCENE_ARRAYS = {"tris": (0, np.float32, (3, 4)), "triNormals": (1, np.float32, (3, 4)), "triUv": (2, np.float32, (4, 4)),
                 "triTangent": (3, np.float32, (3, 4)), "triBounds": (4, np.float32, (2, 4)), "sphereBounds": (5, np.float32, (2, 4)),
@@ -736,7 +770,7 @@ def load_library() -> C.CDLL:
             list(_ADAPTIVE_SIGNATURES.items()) + list(_MULTI_SIGNATURES.items()) + list(_FRAME_SIGNATURES.items()) + list(_MULTI_FRAME_SIGNATURES.items()) + \
             list(_DYNAMIC_SIGNATURES.items()) + list(_DEFORM_SIGNATURES.items()) + list(_DEFORM_DEVICE_SIGNATURES.items()) + \
             list(_BACKGROUND_SIGNATURES.items()) + list(_TEMPORAL_SIGNATURES.items()) + list(_TEMPORAL_COV_SIGNATURES.items()) + list(_PBR_HIT_SIGNATURES.items()) + \
-            list(_SSS_WALK_SIGNATURES.items()) + list(_PATH_STATE_SIGNATURES.items()) + list(_REBUILD_SIGNATURES.items()):
+            list(_SSS_WALK_SIGNATURES.items()) + list(_PATH_STATE_SIGNATURES.items()) + list(_REBUILD_SIGNATURES.items()) + list(_MULTI_DYNAMIC_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -849,6 +883,76 @@ def prepare_geometry(desc: PtrSceneDesc, path: str) -> float:
     return float(seconds.value)
 
 
+def _transform_items(transforms: dict):
+    """{mesh index: 4x4 array (row, column)} as the PtrMeshTransform list of the set_mesh_transforms calls."""
+    items = (PtrMeshTransform * max(len(transforms), 1))()
+    for k, (index, matrix) in enumerate(transforms.items()):
+        items[k].meshIndex = int(index)
+        m = np.asarray(matrix, np.float32).reshape(4, 4)
+        items[k].localToWorld[:] = m.T.reshape(-1).tolist()   # column-major
+    return items
+
+
+def _vertex_items(meshes: dict):
+    """{mesh index: (positions, normals[, tangents])} as the PtrMeshVertices list of the set_mesh_vertices calls, and the arrays it points into."""
+    items = (PtrMeshVertices * max(len(meshes), 1))()
+    keep = []
+    fp = C.POINTER(C.c_float)
+    for k, (index, data) in enumerate(meshes.items()):
+        arrays = [np.ascontiguousarray(a, np.float32).reshape(-1, w) for a, w in zip(data, (3, 3, 4))]
+        keep.append(arrays)
+        items[k].meshIndex, items[k].vertexCount = int(index), len(arrays[0])
+        items[k].positions, items[k].normals = arrays[0].ctypes.data_as(fp), arrays[1].ctypes.data_as(fp)
+        items[k].tangents = arrays[2].ctypes.data_as(fp) if len(arrays) > 2 else None
+    return items, keep
+
+
+def _vertex_device_items(meshes: dict, scene_device: Optional[int]):
+    """{mesh index: (positions, normals or None[, tangents])} of torch tensors as the PtrMeshVerticesDevice list of the
+    set_mesh_vertices_device calls, and the device they are on: scene_device, or with None the one device all of them share."""
+    items = (PtrMeshVerticesDevice * max(len(meshes), 1))()
+    found = scene_device
+    for k, (index, data) in enumerate(meshes.items()):
+        data = tuple(data)
+        if not 2 <= len(data) <= 3:
+            raise PtrError("set_mesh_vertices_device: mesh %s needs (positions, normals or None[, tangents])" % (index,))
+        for name, t, width in zip(("positions", "normals", "tangents"), data, (3, 3, 4)):
+            if t is None and name == "normals":
+                continue
+            device = getattr(t, "device", None)
+            if not hasattr(t, "data_ptr") or device is None:
+                raise PtrError("set_mesh_vertices_device: the %s of mesh %s are not a torch tensor" % (name, index))
+            if found is None and device.type == "cuda":
+                found = device.index
+            if device.type != "cuda" or device.index != found:
+                where = "of the scene" if scene_device is not None else "like the arrays before them"
+                raise PtrError("set_mesh_vertices_device: the %s of mesh %s are on %s, not on device %s %s" % (name, index, device, found, where))
+            if str(t.dtype) != "torch.float32":
+                raise PtrError("set_mesh_vertices_device: the %s of mesh %s are %s, not float32" % (name, index, t.dtype))
+            if t.dim() != 2 or t.shape[1] != width or (name != "positions" and t.shape[0] != data[0].shape[0]):
+                raise PtrError("set_mesh_vertices_device: the %s of mesh %s have shape %s, not [n, %d]" % (name, index, tuple(t.shape), width))
+            if not t.is_contiguous():
+                raise PtrError("set_mesh_vertices_device: the %s of mesh %s are not contiguous" % (name, index))
+            setattr(items[k], name, t.data_ptr())
+        items[k].meshIndex, items[k].vertexCount = int(index), int(data[0].shape[0])
+    return items, found
+
+
+def _sphere_items(spheres: dict):
+    items = (PtrSphereUpdate * max(len(spheres), 1))()
+    for k, (index, row) in enumerate(spheres.items()):
+        items[k].sphereIndex = int(index)
+        items[k].centerRadius[:] = np.asarray(row, np.float32).reshape(4).tolist()
+    return items
+
+
+def _rect_items(rects: dict):
+    items = (PtrRectUpdate * max(len(rects), 1))()
+    for k, (index, r) in enumerate(rects.items()):
+        items[k] = rect_update(index, **r)
+    return items
+
+
 class DeviceScene:
     """A scene resident in HBM: SAH BVH + SoA primitive/material/light arrays (ptr_scene_upload)."""
 
@@ -891,11 +995,7 @@ class DeviceScene:
 
     def set_mesh_transforms(self, transforms: dict, stream: int = 0) -> dict:
         """ptr_scene_set_mesh_transforms: {mesh index: 4x4 array (row, column), the new localToWorld}; returns PtrUpdateInfo as a dict."""
-        items = (PtrMeshTransform * max(len(transforms), 1))()
-        for k, (index, matrix) in enumerate(transforms.items()):
-            items[k].meshIndex = int(index)
-            m = np.asarray(matrix, np.float32).reshape(4, 4)
-            items[k].localToWorld[:] = m.T.reshape(-1).tolist()   # column-major
+        items = _transform_items(transforms)
         info = PtrUpdateInfo()
         err = _err_buf()
         _check(load_library().ptr_scene_set_mesh_transforms(self._h, items, len(transforms), C.c_void_p(stream), C.byref(info), err, len(err)), err)
@@ -908,15 +1008,7 @@ class DeviceScene:
     def set_mesh_vertices(self, meshes: dict, stream: int = 0) -> dict:
         """ptr_scene_set_mesh_vertices: {mesh index: (positions [n, 3], normals [n, 3][, tangents [n, 4]])}, object space; returns
         PtrUpdateInfo as a dict."""
-        items = (PtrMeshVertices * max(len(meshes), 1))()
-        keep = []
-        fp = C.POINTER(C.c_float)
-        for k, (index, data) in enumerate(meshes.items()):
-            arrays = [np.ascontiguousarray(a, np.float32).reshape(-1, w) for a, w in zip(data, (3, 3, 4))]
-            keep.append(arrays)
-            items[k].meshIndex, items[k].vertexCount = int(index), len(arrays[0])
-            items[k].positions, items[k].normals = arrays[0].ctypes.data_as(fp), arrays[1].ctypes.data_as(fp)
-            items[k].tangents = arrays[2].ctypes.data_as(fp) if len(arrays) > 2 else None
+        items, keep = _vertex_items(meshes)
         info = PtrUpdateInfo()
         err = _err_buf()
         _check(load_library().ptr_scene_set_mesh_vertices(self._h, items, len(meshes), C.c_void_p(stream), C.byref(info), err, len(err)), err)
@@ -927,27 +1019,7 @@ class DeviceScene:
         on the scene's device, float32 and contiguous, passed by data_ptr(); None for the normals has them computed on the device (a
         scene made with vertex_normals=True).  The tensors are read on `stream` (a raw stream handle; None: torch's current stream of the
         scene's device): whatever produces them is enqueued there before the call, or has finished.  Returns PtrUpdateInfo as a dict."""
-        items = (PtrMeshVerticesDevice * max(len(meshes), 1))()
-        for k, (index, data) in enumerate(meshes.items()):
-            data = tuple(data)
-            if not 2 <= len(data) <= 3:
-                raise PtrError("set_mesh_vertices_device: mesh %s needs (positions, normals or None[, tangents])" % (index,))
-            for name, t, width in zip(("positions", "normals", "tangents"), data, (3, 3, 4)):
-                if t is None and name == "normals":
-                    continue
-                device = getattr(t, "device", None)
-                if not hasattr(t, "data_ptr") or device is None:
-                    raise PtrError("set_mesh_vertices_device: the %s of mesh %s are not a torch tensor" % (name, index))
-                if device.type != "cuda" or device.index != self._device:
-                    raise PtrError("set_mesh_vertices_device: the %s of mesh %s are on %s, not on device %d of the scene" % (name, index, device, self._device))
-                if str(t.dtype) != "torch.float32":
-                    raise PtrError("set_mesh_vertices_device: the %s of mesh %s are %s, not float32" % (name, index, t.dtype))
-                if t.dim() != 2 or t.shape[1] != width or (name != "positions" and t.shape[0] != data[0].shape[0]):
-                    raise PtrError("set_mesh_vertices_device: the %s of mesh %s have shape %s, not [n, %d]" % (name, index, tuple(t.shape), width))
-                if not t.is_contiguous():
-                    raise PtrError("set_mesh_vertices_device: the %s of mesh %s are not contiguous" % (name, index))
-                setattr(items[k], name, t.data_ptr())
-            items[k].meshIndex, items[k].vertexCount = int(index), int(data[0].shape[0])
+        items, _ = _vertex_device_items(meshes, self._device)
         if stream is None:
             import torch   # (only here: the module itself does not need torch)
 
@@ -959,10 +1031,7 @@ class DeviceScene:
 
     def set_spheres(self, spheres: dict, stream: int = 0) -> dict:
         """ptr_scene_set_spheres: {sphere index: (cx, cy, cz, radius)}; returns PtrUpdateInfo as a dict."""
-        items = (PtrSphereUpdate * max(len(spheres), 1))()
-        for k, (index, row) in enumerate(spheres.items()):
-            items[k].sphereIndex = int(index)
-            items[k].centerRadius[:] = np.asarray(row, np.float32).reshape(4).tolist()
+        items = _sphere_items(spheres)
         info = PtrUpdateInfo()
         err = _err_buf()
         _check(load_library().ptr_scene_set_spheres(self._h, items, len(spheres), C.c_void_p(stream), C.byref(info), err, len(err)), err)
@@ -971,9 +1040,7 @@ class DeviceScene:
     def set_rects(self, rects: dict, stream: int = 0) -> dict:
         """ptr_scene_set_rects: {rectangle index: dict(corner=, edgeU=, edgeV=, normal=)}, three components each; the w words are filled
         as the scene loader fills them (rect_update).  Returns PtrUpdateInfo as a dict."""
-        items = (PtrRectUpdate * max(len(rects), 1))()
-        for k, (index, r) in enumerate(rects.items()):
-            items[k] = rect_update(index, **r)
+        items = _rect_items(rects)
         info = PtrUpdateInfo()
         err = _err_buf()
         _check(load_library().ptr_scene_set_rects(self._h, items, len(rects), C.c_void_p(stream), C.byref(info), err, len(err)), err)
@@ -1361,6 +1428,21 @@ class DeviceScene:
             pass
 
 
+class _BorrowedScene(DeviceScene):
+    """A partition's scene of a MultiFrame (MultiFrame.part_scene): not owned, never released here, never updated but through the frame."""
+
+    def __init__(self, handle: C.c_void_p, device: int, frame):
+        self._h, self._device, self._keepalive = handle, int(device), frame
+
+    def _through_the_frame(self, *args, **kwargs):
+        raise PtrError("a partition's scene is updated through its MultiFrame: a call on one partition would desynchronise them")
+
+    set_mesh_transforms = set_mesh_vertices = set_mesh_vertices_device = set_spheres = set_rects = rebuild_tree = _through_the_frame
+
+    def close(self) -> None:
+        pass
+
+
 FRAME_STATE = (("sum", 3, np.float32), ("mean", 3, np.float32), ("m", 6, np.float32), ("n", 0, np.uint32), ("e", 0, np.float32))
 
 
@@ -1723,9 +1805,10 @@ class MultiFrame:
     debug_multi_frame().  The calls mirror Frame's; the state, the images and every info are bit for bit those of a single-device Frame
     given the same calls, and a checkpoint (export_state / import_state) passes between the two and between device counts."""
 
-    def __init__(self, handle: C.c_void_p, keepalive=None):
+    def __init__(self, handle: C.c_void_p, keepalive=None, devices=None):
         self._h = handle
         self._keepalive = keepalive
+        self._devices = devices   # the device of every partition when the frame was made on an id list
 
     def _handle(self):
         if not self._h:
@@ -1802,6 +1885,71 @@ class MultiFrame:
         err = _err_buf()
         _check(load_library().ptr_multi_frame_reset(self._handle(), C.byref(settings) if settings is not None else None, err, len(err)), err)
 
+    # ---- include/ptr_multi_dynamic.h: a frame made with dynamic=True is updated in place on all its devices.  The calls take what
+    # DeviceScene's take, without the stream, and return PtrMultiUpdateInfo.as_dict().  reset() before accumulating the new pose.
+    def is_dynamic(self) -> bool:
+        return bool(load_library().ptr_multi_frame_is_dynamic(self._handle()))
+
+    def dynamic_flags(self) -> int:
+        return int(load_library().ptr_multi_frame_dynamic_flags(self._handle()))
+
+    def _update(self, name: str, items, count: int, *more) -> dict:
+        info = PtrMultiUpdateInfo()
+        err = _err_buf()
+        _check(getattr(load_library(), name)(self._handle(), items, count, *more, C.byref(info), err, len(err)), err)
+        return info.as_dict()
+
+    def set_mesh_transforms(self, transforms: dict) -> dict:
+        return self._update("ptr_multi_frame_set_mesh_transforms", _transform_items(transforms), len(transforms))
+
+    def set_mesh_vertices(self, meshes: dict) -> dict:
+        items, keep = _vertex_items(meshes)
+        return self._update("ptr_multi_frame_set_mesh_vertices", items, len(meshes))
+
+    def set_spheres(self, spheres: dict) -> dict:
+        return self._update("ptr_multi_frame_set_spheres", _sphere_items(spheres), len(spheres))
+
+    def set_rects(self, rects: dict) -> dict:
+        return self._update("ptr_multi_frame_set_rects", _rect_items(rects), len(rects))
+
+    def set_mesh_vertices_device(self, meshes: dict, stream=None) -> dict:
+        """ptr_multi_frame_set_mesh_vertices_device: torch tensors as DeviceScene.set_mesh_vertices_device takes them, all on one device,
+        which need not be one of the frame's; they are read on `stream` of that device (None: torch's current stream there)."""
+        items, device = _vertex_device_items(meshes, None)
+        if device is None:
+            raise PtrError("set_mesh_vertices_device: no tensor names a device")
+        if stream is None:
+            import torch   # (only here: the module itself does not need torch)
+
+            stream = torch.cuda.current_stream(device).cuda_stream
+        return self._update("ptr_multi_frame_set_mesh_vertices_device", items, len(meshes), device, C.c_void_p(stream))
+
+    def tree_cost(self) -> float:
+        cost = C.c_double(0.0)
+        err = _err_buf()
+        _check(load_library().ptr_multi_frame_tree_cost(self._handle(), C.byref(cost), err, len(err)), err)
+        return float(cost.value)
+
+    def rebuild_tree(self, keep_if_better: bool = True) -> dict:
+        """ptr_multi_frame_rebuild_tree: DeviceScene.rebuild_tree on every partition, which all reach the same tree."""
+        info = PtrRebuildInfo()
+        err = _err_buf()
+        flags = PTR_REBUILD_KEEP_IF_BETTER if keep_if_better else 0
+        _check(load_library().ptr_multi_frame_rebuild_tree(self._handle(), flags, C.byref(info), err, len(err)), err)
+        return info.as_dict()
+
+    def part_scene(self, p: int) -> "DeviceScene":
+        """Partition p's scene, borrowed: it keeps the frame alive, its close() does nothing, and it refuses the update and rebuild
+        calls (they go through the frame).  Rendering, temporal() and the arrays() / rebuild_arrays() probes may use it."""
+        h = load_library().ptr_multi_frame_part_scene(self._handle(), p)
+        if not h:
+            raise PtrError("part_scene: the frame has no partition %d with a scene" % p)
+        return _BorrowedScene(C.c_void_p(h), self._devices[p] if self._devices else p, self)
+
+    def temporal(self, width: int, height: int, params: Optional["PtrTemporalParams"] = None, cov=None) -> "Temporal":
+        """part_scene(0).temporal(...): a Temporal handle on the frame's first device, beside resolve_device."""
+        return self.part_scene(0).temporal(width, height, params, cov)
+
     def close(self) -> None:
         if self._h:
             load_library().ptr_multi_frame_release(self._h)
@@ -1815,17 +1963,46 @@ class MultiFrame:
             pass
 
 
-def multi_frame(desc: PtrSceneDesc, settings: PtrSettings, n_devices: int = 0, device_ids=None) -> MultiFrame:
+def multi_frame(desc: PtrSceneDesc, settings: PtrSettings, n_devices: int = 0, device_ids=None, dynamic: bool = False, deformable: bool = False,
+                primitives: bool = False, vertex_normals: bool = False) -> MultiFrame:
     """A resumable frame on several devices of this node (include/ptr_multi_frame.h): the scene is prepared once and uploaded to every
-    device once, for the frame's life.  `device_ids` (tests) names the devices explicitly as render_multi_adaptive's does."""
+    device once, for the frame's life.  `device_ids` (tests) names the devices explicitly as render_multi_adaptive's does.
+    dynamic (include/ptr_multi_dynamic.h): every device's scene is a dynamic scene and the frame's set_* / rebuild_tree calls update
+    them in place; deformable / primitives / vertex_normals as DeviceScene takes them."""
     handle = C.c_void_p()
     err = _err_buf()
+    lib = load_library()
+    if (deformable or primitives or vertex_normals) and not dynamic:
+        raise PtrError("deformable / primitives / vertex_normals need dynamic=True")
+    flags = (PTR_DYNAMIC_DEFORMABLE if deformable else 0) | (PTR_DYNAMIC_PRIMITIVES if primitives else 0) | (PTR_DYNAMIC_VERTEX_NORMALS if vertex_normals else 0)
+    devices = None
     if device_ids is not None:
         ids = (C.c_int * len(device_ids))(*device_ids)
-        _check(load_library().ptr_multi_frame_debug_create_on(C.byref(desc), C.byref(settings), ids, len(device_ids), C.byref(handle), err, len(err)), err)
+        devices = [-(i + 1) if i < 0 else i for i in device_ids]
+        if dynamic:
+            _check(lib.ptr_multi_frame_debug_create_dynamic_on(C.byref(desc), C.byref(settings), flags, ids, len(device_ids), C.byref(handle), err, len(err)), err)
+        else:
+            _check(lib.ptr_multi_frame_debug_create_on(C.byref(desc), C.byref(settings), ids, len(device_ids), C.byref(handle), err, len(err)), err)
+    elif dynamic:
+        _check(lib.ptr_multi_frame_create_dynamic(C.byref(desc), C.byref(settings), n_devices, flags, C.byref(handle), err, len(err)), err)
     else:
-        _check(load_library().ptr_multi_frame_create(C.byref(desc), C.byref(settings), n_devices, C.byref(handle), err, len(err)), err)
-    return MultiFrame(handle)
+        _check(lib.ptr_multi_frame_create(C.byref(desc), C.byref(settings), n_devices, C.byref(handle), err, len(err)), err)
+    return MultiFrame(handle, devices=devices)
+
+
+def debug_multi_check_update(desc: PtrSceneDesc, call: str, update: dict, deformable: bool = True, primitives: bool = True,
+                             vertex_normals: bool = False) -> None:
+    """ptr_multi_frame_debug_check_update (tests, no GPU): the host checks of MultiFrame.<call>(update) - set_mesh_transforms,
+    set_mesh_vertices, set_spheres or set_rects - against a frame made from `desc` with these flags; raises PtrError with the call's
+    own message when it would be refused."""
+    kinds = {"set_mesh_transforms": (0, _transform_items), "set_mesh_vertices": (1, _vertex_items), "set_spheres": (2, _sphere_items),
+             "set_rects": (3, _rect_items)}
+    kind, make = kinds[call]
+    made = make(update)   # (_vertex_items also returns the arrays its items point into: `made` keeps them until the call has returned)
+    items = made[0] if isinstance(made, tuple) else made
+    flags = (PTR_DYNAMIC_DEFORMABLE if deformable else 0) | (PTR_DYNAMIC_PRIMITIVES if primitives else 0) | (PTR_DYNAMIC_VERTEX_NORMALS if vertex_normals else 0)
+    err = _err_buf()
+    _check(load_library().ptr_multi_frame_debug_check_update(C.byref(desc), flags, kind, C.cast(items, C.c_void_p), len(update), err, len(err)), err)
 
 
 def debug_multi_frame(samples: np.ndarray, device_ids) -> MultiFrame:

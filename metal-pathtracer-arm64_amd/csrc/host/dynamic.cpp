@@ -1,7 +1,9 @@
 // Dynamic scenes (include/ptr_dynamic.h, include/ptr_deform.h, include/ptr_deform_device.h): the upload of the extra device data,
 // ptr_scene_set_mesh_transforms, ptr_scene_set_mesh_vertices and its device-pointer form, ptr_scene_set_spheres and ptr_scene_set_rects,
-// which all end in the same refit (finishUpdate), and the headers' test-only probes, which look at a scene's arrays.  Compiled with
-// hipcc (host code only), like hip_backend.cpp; the kernels are in kernels/dynamic.hip.
+// which all end in the same refit (finishUpdate), and the headers' test-only probes, which look at a scene's arrays.  Every update call
+// is a check half (the rules, on the host) and a run half (the device work on one scene and one stream), declared in dynamic_host.h: the
+// frame on several devices (multi_dynamic.cpp) checks once and runs on every partition.  Compiled with hipcc (host code only), like
+// hip_backend.cpp; the kernels are in kernels/dynamic.hip.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -9,6 +11,7 @@
 #include "../kernels/bvh_grid.h"
 #include "../kernels/dynamic.h"
 #include "device_scene.h"
+#include "dynamic_host.h"
 #include "ptr_deform_device.h"
 #include "ptr_dynamic.h"
 #include "rebuild_host.h"
@@ -49,10 +52,34 @@ void fillPrimitiveRecords(const PtrSceneDesc& desc, const ptr::SceneGeometry& ge
     out.triCount = geo.triCount;
 }
 
+void fillDynamicRecords(const PtrSceneDesc& desc, const ptr::PreparedGeometry& pg, const ptr::DynamicTables& t, const std::vector<int32_t>& lightIndexByRect,
+                        DynamicScene& dyn) {
+    const ptr::FlatBvh& bvh = pg.geo.bvh;
+    dyn.meshTriOffsets = t.meshTriOffsets;
+    dyn.levelOffsets = t.levelOffsets;
+    dyn.meshHasTangents = t.meshHasTangents;
+    dyn.nodeCount = bvh.nodeCount;
+    dyn.wideCount = pg.wideCount;
+    dyn.triCount = pg.geo.triCount;
+    dyn.sphereCount = pg.geo.sphereCount;
+    dyn.meanPrimExtent = bvh.meanPrimExtent;
+    dyn.meshRows.resize(t.meshBakes.size());
+    for (size_t m = 0; m < t.meshBakes.size(); ++m) dyn.meshRows[m] = meshRowOf(t.meshBakes[m], t.meshHasTangents[m] != 0);
+    dyn.flags = t.flags;
+    if (t.flags & PTR_DYNAMIC_DEFORMABLE) {
+        dyn.meshVertexCount = t.meshVertexCount;
+        dyn.meshTangentsGiven = t.meshTangentsGiven;
+    }
+    if (t.flags & PTR_DYNAMIC_VERTEX_NORMALS) dyn.adjBase = t.adjBase;
+    if (t.flags & PTR_DYNAMIC_PRIMITIVES) fillPrimitiveRecords(desc, pg.geo, t, lightIndexByRect, dyn.prims);
+    ptr::BuildLeafTable(bvh.nodes.data(), bvh.nodeCount, dyn.leafTable);   // include/ptr_rebuild.h, step 1
+}
+
 void uploadDynamicTables(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceScene& ds) {
     const ptr::DynamicTables& t = ps.dyn;
     const ptr::FlatBvh& bvh = ps.pg.geo.bvh;
     auto dyn = std::make_unique<DynamicScene>();
+    fillDynamicRecords(desc, ps.pg, t, ps.lightIndexByRect, *dyn);
     dyn->objPos.upload(reinterpret_cast<const float4*>(t.objPos.data()), t.objPos.size() / 4);
     dyn->objNrm.upload(reinterpret_cast<const float4*>(t.objNrm.data()), t.objNrm.size() / 4);
     dyn->textured = ds.view.triUv != nullptr;
@@ -64,33 +91,13 @@ void uploadDynamicTables(const PtrSceneDesc& desc, const PreparedScene& ps, PtrD
     dyn->meshTris.upload(t.meshTris.data(), t.meshTris.size());
     dyn->schedule.upload(t.schedule.data(), t.schedule.size());
     if (ps.pg.wideCount > 0u) dyn->wideSource.upload(t.wideSource.data(), t.wideSource.size());
-    dyn->meshTriOffsets = t.meshTriOffsets;
-    dyn->levelOffsets = t.levelOffsets;
-    dyn->meshHasTangents = t.meshHasTangents;
-    dyn->nodeCount = bvh.nodeCount;
-    dyn->wideCount = ps.pg.wideCount;
-    dyn->triCount = ps.pg.geo.triCount;
-    dyn->sphereCount = ps.pg.geo.sphereCount;
-    dyn->meanPrimExtent = bvh.meanPrimExtent;
-    dyn->meshRows.resize(t.meshBakes.size());
-    for (size_t m = 0; m < t.meshBakes.size(); ++m) dyn->meshRows[m] = meshRowOf(t.meshBakes[m], t.meshHasTangents[m] != 0);
-    dyn->flags = t.flags;
-    if (t.flags & PTR_DYNAMIC_DEFORMABLE) {
-        dyn->meshCorners.upload(t.meshCorners.data(), t.meshCorners.size());
-        dyn->meshVertexCount = t.meshVertexCount;
-        dyn->meshTangentsGiven = t.meshTangentsGiven;
-    }
+    if (t.flags & PTR_DYNAMIC_DEFORMABLE) dyn->meshCorners.upload(t.meshCorners.data(), t.meshCorners.size());
     if (t.flags & PTR_DYNAMIC_VERTEX_NORMALS) {
         dyn->adjOffsets.upload(t.adjOffsets.data(), t.adjOffsets.size());
         dyn->adjEntries.upload(t.adjEntries.data(), t.adjEntries.size());
-        dyn->adjBase = t.adjBase;
-    }
-    if (t.flags & PTR_DYNAMIC_PRIMITIVES) {
-        fillPrimitiveRecords(desc, ps.pg.geo, t, ps.lightIndexByRect, dyn->prims);
     }
     for (hipEvent_t& e : dyn->events) HIP_CHECK(hipEventCreate(&e));
     HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&dyn->rootBox), 4 * sizeof(float4), hipHostMallocDefault));
-    ptr::BuildLeafTable(bvh.nodes.data(), bvh.nodeCount, dyn->leafTable);   // include/ptr_rebuild.h, step 1
     ds.dynamic = std::move(dyn);
 }
 
@@ -123,19 +130,11 @@ DynBakeArrays bakeArrays(PtrDeviceScene& ds) {
                          dyn.textured ? ds.triUv.ptr : nullptr, dyn.textured ? ds.triTangent.ptr : nullptr};
 }
 
-// The staging buffer of ptr_scene_set_spheres / ptr_scene_set_rects: 16 B rows and where each goes, (PTR_SCATTER_* << 28) | row
-struct ScatterRows {
-    std::vector<float> rows;
-    std::vector<uint32_t> dest;
-};
-
 // (defined below the entry points)
 void finishUpdate(PtrDeviceScene& ds, hipStream_t st, std::chrono::steady_clock::time_point t0, uint64_t moved, PtrUpdateInfo* info);
 // The host half of a sphere's / a rectangle's move: the new record into `prims`, its rows appended to `out`.  "" or what is wrong with it.
 std::string sphereRows(PrimitiveRecords& prims, const PtrSphereUpdate& u, ScatterRows& out);
 std::string rectRows(PrimitiveRecords& prims, const PtrRectUpdate& u, ScatterRows& out);
-int setPrimitives(const char* who, uint32_t kind, PtrDeviceScene* scene, const void* list, uint32_t count, void* stream, PtrUpdateInfo* info, char* err,
-                  size_t err_cap);
 
 std::string matrixProblem(const float m[16], const ptr::MeshBake& bake) {
     for (int i = 0; i < 16; ++i) {
@@ -148,13 +147,7 @@ std::string matrixProblem(const float m[16], const ptr::MeshBake& bake) {
     return "";
 }
 
-// One named mesh of ptr_scene_set_mesh_vertices / ptr_scene_set_mesh_vertices_device once the call is accepted
-struct MeshSource {
-    bool used = false;   // false: a mesh without triangles, which changes nothing
-    DynVertexArrays v{nullptr, nullptr, nullptr};   // where the gather reads its arrays, on the device
-};
-
-// What both calls refuse about entry `mv` of their list (PtrMeshVertices and PtrMeshVerticesDevice have the same members): "" or the
+// What both vertex calls refuse about entry `mv` of their list (PtrMeshVertices and PtrMeshVerticesDevice have the same members): "" or the
 // cause.  named: per mesh of the scene, how often the list has named it so far.  used: the mesh has triangles.
 template <typename V>
 std::string namedMeshProblem(const DynamicScene& dyn, const V& mv, std::vector<uint8_t>& named, bool normalsMayBeNull, const char* nullNormalsHint, bool& used) {
@@ -177,19 +170,20 @@ std::string namedMeshProblem(const DynamicScene& dyn, const V& mv, std::vector<u
     return "";
 }
 
-// What both calls run once the mesh table is on the device and event 0 is recorded: per named mesh with triangles the gather of its
-// arrays into the object-space corner rows and the bake under the matrix the mesh has (row i of the table), then the shared tail.
-template <typename V>
-void gatherBakeFinish(PtrDeviceScene& ds, const V* meshes, const std::vector<MeshSource>& src, hipStream_t st, std::chrono::steady_clock::time_point t0,
+// What both vertex calls run once the mesh table is on the device and event 0 is recorded: per named mesh with triangles (entry i: used,
+// mesh, and through arraysOf where the gather reads its arrays) the gather into the object-space corner rows and the bake under the matrix
+// the mesh has (row i of the table), then the shared tail.
+template <typename E, typename ArraysOf>
+void gatherBakeFinish(PtrDeviceScene& ds, const std::vector<E>& entry, ArraysOf&& arraysOf, hipStream_t st, std::chrono::steady_clock::time_point t0,
                       PtrUpdateInfo* info) {
     DynamicScene& dyn = *ds.dynamic;
     const DynBakeArrays arrays = bakeArrays(ds);
     uint64_t moved = 0;
-    for (uint32_t i = 0; i < src.size(); ++i) {
-        if (!src[i].used) continue;
-        const uint32_t m = meshes[i].meshIndex;
+    for (uint32_t i = 0; i < entry.size(); ++i) {
+        if (!entry[i].used) continue;
+        const uint32_t m = entry[i].mesh;
         const uint32_t first = dyn.meshTriOffsets[m], n = dyn.meshTriOffsets[m + 1u] - first;
-        launchDynGatherCorners(dyn.objPos.ptr, dyn.objNrm.ptr, dyn.textured ? dyn.objTan.ptr : nullptr, src[i].v, dyn.meshTris.ptr + first,
+        launchDynGatherCorners(dyn.objPos.ptr, dyn.objNrm.ptr, dyn.textured ? dyn.objTan.ptr : nullptr, arraysOf(entry[i]), dyn.meshTris.ptr + first,
                                dyn.meshCorners.ptr + static_cast<size_t>(first) * 3u, n, st);
         launchDynBake(arrays, dyn.meshTable.ptr, i, dyn.meshTris.ptr + first, n, st);
         moved += n;
@@ -221,6 +215,267 @@ std::string devicePointerProblem(const void* p, size_t bytes, int device) {
     if (at > end || end - at < bytes) return "has " + std::to_string(end - std::min(at, end)) + " B left in its allocation, fewer than the " + std::to_string(bytes) + " B of the array";
     return "";
 }
+
+const char* const kNotDynamic = "the scene is not dynamic (upload it with ptr_scene_upload_dynamic)";
+const char* const kNotDeformable = "the scene is not deformable (upload it with ptr_scene_upload_dynamic_ex and PTR_DYNAMIC_DEFORMABLE)";
+
+// k_dyn_check_finite over `rows`, whose row r is u.checked[index[r]]: the rows and zeroed flag words to the device, the words back, and a
+// set bit ends the call - nothing the renderer reads has been written yet.
+void finiteCheck(const char* who, const DeviceVerticesUpdate& u, const std::vector<DynCheckRow>& rows, const std::vector<size_t>& index, DynCheckRow* dRows,
+                 uint32_t* dFlags, uint32_t* pinnedFlags, hipStream_t st) {
+    const size_t words = (rows.size() + 31u) / 32u;
+    uint64_t largest = 0;
+    for (const DynCheckRow& r : rows) largest = std::max<uint64_t>(largest, r.count);
+    HIP_CHECK(hipMemcpyAsync(dRows, rows.data(), rows.size() * sizeof(DynCheckRow), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(dFlags, 0, words * sizeof(uint32_t), st));
+    launchDynCheckFinite(dRows, static_cast<uint32_t>(rows.size()), largest, dFlags, st);
+    HIP_CHECK(hipMemcpyAsync(pinnedFlags, dFlags, words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    for (size_t r = 0; r < rows.size(); ++r) {
+        if (pinnedFlags[r >> 5] >> (r & 31u) & 1u) {
+            const DeviceVerticesUpdate::Checked& c = u.checked[index[r]];
+            throw Refused{std::string(who) + ": mesh " + std::to_string(u.entry[c.entry].mesh) + " has a non-finite " + c.what + " component"};
+        }
+    }
+}
+
+}  // namespace
+
+namespace ptrhost {
+
+std::string listProblem(const void* list, uint32_t count, const char* nullWords) {
+    if (!list) return nullWords;
+    if (count == 0u) return "count is 0";
+    return "";
+}
+
+std::string checkMeshTransforms(const PtrDeviceScene* scene, const PtrMeshTransform* transforms, uint32_t count, TransformUpdate& out) {
+    if (!scene->dynamic) return kNotDynamic;
+    const std::string bad = listProblem(transforms, count, "null transform list");
+    if (!bad.empty()) return bad;
+    const DynamicScene& dyn = *scene->dynamic;
+    const uint32_t meshCount = static_cast<uint32_t>(dyn.meshTriOffsets.size()) - 1u;
+    out.mesh.resize(count), out.rows.resize(count);
+    std::vector<uint8_t> named(meshCount, 0);
+    for (uint32_t i = 0; i < count; ++i) {
+        const PtrMeshTransform& t = transforms[i];
+        if (t.meshIndex >= meshCount) {
+            return "mesh index " + std::to_string(t.meshIndex) + " out of range (the scene has " + std::to_string(meshCount) + " meshes)";
+        }
+        if (named[t.meshIndex]++) return "mesh index " + std::to_string(t.meshIndex) + " named twice";
+        ptr::MeshBake bake;
+        ptr::ComputeMeshBake(t.localToWorld, bake);
+        const std::string problem = matrixProblem(t.localToWorld, bake);
+        if (!problem.empty()) return "the matrix of mesh " + std::to_string(t.meshIndex) + " " + problem;
+        out.mesh[i] = t.meshIndex;
+        out.rows[i] = meshRowOf(bake, dyn.meshHasTangents[t.meshIndex] != 0);
+    }
+    return "";
+}
+
+void runMeshTransforms(PtrDeviceScene& ds, const TransformUpdate& u, hipStream_t st, PtrUpdateInfo* info, const InputsEnqueued& enqueued) {
+    const auto t0 = std::chrono::steady_clock::now();
+    DynamicScene& dyn = *ds.dynamic;
+    const uint32_t count = static_cast<uint32_t>(u.rows.size());
+    dyn.meshTable.ensure(static_cast<size_t>(count) * kDynMeshVec4);
+    HIP_CHECK(hipMemcpyAsync(dyn.meshTable.ptr, u.rows.data(), u.rows.size() * sizeof(DynMeshRow), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipEventRecord(dyn.events[0], st));
+    if (enqueued) enqueued();
+    const DynBakeArrays arrays = bakeArrays(ds);
+    uint64_t moved = 0;
+    for (uint32_t i = 0; i < count; ++i) {
+        const uint32_t m = u.mesh[i];
+        const uint32_t first = dyn.meshTriOffsets[m], n = dyn.meshTriOffsets[m + 1u] - first;
+        launchDynBake(arrays, dyn.meshTable.ptr, i, dyn.meshTris.ptr + first, n, st);
+        dyn.meshRows[m] = u.rows[i];   // the matrix a later ptr_scene_set_mesh_vertices bakes under
+        moved += n;
+    }
+    finishUpdate(ds, st, t0, moved, info);
+}
+
+std::string checkMeshVertices(const PtrDeviceScene* scene, const PtrMeshVertices* meshes, uint32_t count, VerticesUpdate& out) {
+    if (!scene->dynamic || !(scene->dynamic->flags & PTR_DYNAMIC_DEFORMABLE)) return kNotDeformable;
+    const std::string bad = listProblem(meshes, count, "null mesh list");
+    if (!bad.empty()) return bad;
+    const DynamicScene& dyn = *scene->dynamic;
+    const uint32_t meshCount = static_cast<uint32_t>(dyn.meshTriOffsets.size()) - 1u;
+    out.entry.assign(count, VerticesUpdate::Entry{});
+    out.rows.resize(count);
+    // where the arrays of every named mesh go in the staging buffer, in floats (a mesh without triangles stages nothing)
+    size_t floats = 0;
+    std::vector<uint8_t> named(meshCount, 0);
+    for (uint32_t i = 0; i < count; ++i) {
+        const PtrMeshVertices& mv = meshes[i];
+        VerticesUpdate::Entry& s = out.entry[i];
+        const std::string problem = namedMeshProblem(dyn, mv, named, false, "", s.used);
+        if (!problem.empty()) return problem;
+        s.mesh = mv.meshIndex;
+        out.rows[i] = dyn.meshRows[mv.meshIndex];
+        if (!s.used) continue;
+        s.hasTangents = dyn.meshHasTangents[mv.meshIndex] != 0;   // (an untextured scene keeps no tangents: they are checked and dropped)
+        s.positions = floats, floats += static_cast<size_t>(mv.vertexCount) * 3u;
+        s.normals = floats, floats += static_cast<size_t>(mv.vertexCount) * 3u;
+        if (s.hasTangents) s.tangents = floats, floats += static_cast<size_t>(mv.vertexCount) * 4u;
+    }
+    out.floats = floats;
+    return "";
+}
+
+std::string stageMeshVertices(const PtrMeshVertices* meshes, const VerticesUpdate& u, float* pinned) {
+    auto stage = [&](const float* src, size_t n, float* dst) {
+        bool finite = true;
+        for (size_t k = 0; k < n; ++k) {
+            finite = finite && std::isfinite(src[k]);
+            dst[k] = src[k];
+        }
+        return finite;
+    };
+    for (uint32_t i = 0; i < u.entry.size(); ++i) {
+        const PtrMeshVertices& mv = meshes[i];
+        const VerticesUpdate::Entry& s = u.entry[i];
+        if (!s.used) continue;
+        const size_t n = mv.vertexCount;
+        const char* bad = nullptr;
+        if (!stage(mv.positions, n * 3u, pinned + s.positions)) bad = "position";
+        else if (!stage(mv.normals, n * 3u, pinned + s.normals)) bad = "normal";
+        else if (mv.tangents) {
+            std::vector<float> dropped;
+            if (!s.hasTangents) dropped.resize(n * 4u);
+            if (!stage(mv.tangents, n * 4u, s.hasTangents ? pinned + s.tangents : dropped.data())) bad = "tangent";
+        }
+        if (bad) return "mesh " + std::to_string(mv.meshIndex) + " has a non-finite " + bad + " component";
+    }
+    return "";
+}
+
+void runMeshVertices(PtrDeviceScene& ds, const VerticesUpdate& u, const float* pinned, hipStream_t st, PtrUpdateInfo* info, const InputsEnqueued& enqueued) {
+    const auto t0 = std::chrono::steady_clock::now();
+    DynamicScene& dyn = *ds.dynamic;
+    dyn.staging.ensure((u.floats + 3u) / 4u);
+    const float* dStaged = reinterpret_cast<const float*>(dyn.staging.ptr);
+    if (u.floats) HIP_CHECK(hipMemcpyAsync(dyn.staging.ptr, pinned, u.floats * sizeof(float), hipMemcpyHostToDevice, st));
+    dyn.meshTable.ensure(u.rows.size() * kDynMeshVec4);
+    HIP_CHECK(hipMemcpyAsync(dyn.meshTable.ptr, u.rows.data(), u.rows.size() * sizeof(DynMeshRow), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipEventRecord(dyn.events[0], st));
+    if (enqueued) enqueued();
+    gatherBakeFinish(ds, u.entry,
+                     [&](const VerticesUpdate::Entry& s) {
+                         return DynVertexArrays{dStaged + s.positions, dStaged + s.normals, s.hasTangents ? dStaged + s.tangents : nullptr};
+                     },
+                     st, t0, info);
+}
+
+std::string checkMeshVerticesDevice(const PtrDeviceScene* scene, const PtrMeshVerticesDevice* meshes, uint32_t count, int arraysDevice,
+                                    DeviceVerticesUpdate& out) {
+    if (!scene->dynamic || !(scene->dynamic->flags & PTR_DYNAMIC_DEFORMABLE)) return kNotDeformable;
+    const std::string badList = listProblem(meshes, count, "null mesh list");
+    if (!badList.empty()) return badList;
+    const DynamicScene& dyn = *scene->dynamic;
+    const uint32_t meshCount = static_cast<uint32_t>(dyn.meshTriOffsets.size()) - 1u;
+    const bool computes = (dyn.flags & PTR_DYNAMIC_VERTEX_NORMALS) != 0u;
+    out.entry.assign(count, DeviceVerticesUpdate::Entry{});
+    out.rows.resize(count);
+    std::vector<uint8_t> named(meshCount, 0);
+    for (uint32_t i = 0; i < count; ++i) {
+        const PtrMeshVerticesDevice& mv = meshes[i];
+        DeviceVerticesUpdate::Entry& e = out.entry[i];
+        const std::string problem = namedMeshProblem(dyn, mv, named, computes, " (computing them needs a scene uploaded with PTR_DYNAMIC_VERTEX_NORMALS)", e.used);
+        if (!problem.empty()) return problem;
+        e.mesh = mv.meshIndex, e.vertexCount = mv.vertexCount;
+        out.rows[i] = dyn.meshRows[mv.meshIndex];
+        if (!e.used) continue;
+        const size_t n = mv.vertexCount;
+        const struct {
+            const float* data;
+            size_t floats;
+            const char* what;
+            bool computedIfNull;
+        } given[3] = {{mv.positions, n * 3u, "position", false}, {mv.normals, n * 3u, "normal", true}, {mv.tangents, n * 4u, "tangent", false}};
+        for (const auto& g : given) {
+            if (!g.data && !g.computedIfNull) continue;   // (no tangents: the mesh carries none)
+            if (g.data) {
+                const std::string bad = devicePointerProblem(g.data, g.floats * sizeof(float), arraysDevice);
+                if (!bad.empty()) return std::string("the ") + g.what + " array of mesh " + std::to_string(mv.meshIndex) + " " + bad;
+            }
+            out.checked.push_back(DeviceVerticesUpdate::Checked{i, g.what, !g.data, g.data, g.floats});
+        }
+        e.computes = !mv.normals;
+        if (e.computes) e.computedAt = out.computedFloats, out.computedFloats += n * 3u;
+        // (an untextured scene keeps no tangents: they are checked and dropped)
+        e.v = DynVertexArrays{mv.positions, mv.normals, dyn.meshHasTangents[mv.meshIndex] ? mv.tangents : nullptr};
+    }
+    if (pastIndexLimit(out.checked.size())) return "too many meshes in one call";
+    return "";
+}
+
+void checkGivenArrays(const char* who, const DeviceVerticesUpdate& u, DeviceBuffer<float4>& dRows, DeviceBuffer<uint32_t>& dFlags, uint32_t* pinnedFlags,
+                      hipStream_t st) {
+    std::vector<DynCheckRow> rows;
+    std::vector<size_t> index;
+    for (size_t r = 0; r < u.checked.size(); ++r) {
+        if (u.checked[r].computed) continue;
+        rows.push_back(DynCheckRow{u.checked[r].data, u.checked[r].floats});
+        index.push_back(r);
+    }
+    if (rows.empty()) return;
+    dRows.ensure(rows.size());
+    dFlags.ensure((rows.size() + 31u) / 32u);
+    finiteCheck(who, u, rows, index, reinterpret_cast<DynCheckRow*>(dRows.ptr), dFlags.ptr, pinnedFlags, st);
+}
+
+void runMeshVerticesDevice(const char* who, PtrDeviceScene& ds, const DeviceVerticesUpdate& u, bool checkGiven, hipStream_t st, PtrUpdateInfo* info) {
+    const auto t0 = std::chrono::steady_clock::now();
+    DynamicScene& dyn = *ds.dynamic;
+    const size_t count = u.entry.size();
+    if (u.computedFloats) dyn.computedNormals.ensure(u.computedFloats);
+    std::vector<DynCheckRow> checks;
+    std::vector<size_t> index;
+    for (size_t r = 0; r < u.checked.size(); ++r) {
+        const DeviceVerticesUpdate::Checked& c = u.checked[r];
+        if (!c.computed && !checkGiven) continue;
+        checks.push_back(DynCheckRow{c.computed ? dyn.computedNormals.ptr + u.entry[c.entry].computedAt : c.data, c.floats});
+        index.push_back(r);
+    }
+    // the check rows ride behind the mesh rows of the table (both are 16 B units)
+    dyn.meshTable.ensure(count * kDynMeshVec4 + checks.size());
+    HIP_CHECK(hipMemcpyAsync(dyn.meshTable.ptr, u.rows.data(), u.rows.size() * sizeof(DynMeshRow), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipEventRecord(dyn.events[0], st));
+    for (size_t i = 0; i < count; ++i) {
+        const DeviceVerticesUpdate::Entry& e = u.entry[i];
+        if (!e.used || !e.computes) continue;
+        const size_t first = dyn.meshTriOffsets[e.mesh];
+        launchDynVertexNormals(e.v.positions, dyn.adjOffsets.ptr + dyn.adjBase[e.mesh], dyn.adjEntries.ptr + first * 3u, dyn.meshCorners.ptr + first * 3u,
+                               dyn.computedNormals.ptr + e.computedAt, e.vertexCount, st);
+    }
+    if (!checks.empty()) {
+        const size_t words = (checks.size() + 31u) / 32u;
+        dyn.checkFlags.ensure(words);
+        finiteCheck(who, u, checks, index, reinterpret_cast<DynCheckRow*>(dyn.meshTable.ptr + count * kDynMeshVec4), dyn.checkFlags.ptr,
+                    static_cast<uint32_t*>(dyn.pinnedFor(words * sizeof(uint32_t))), st);
+    }
+    gatherBakeFinish(ds, u.entry,
+                     [&](const DeviceVerticesUpdate::Entry& e) {
+                         return DynVertexArrays{e.v.positions, e.computes ? dyn.computedNormals.ptr + e.computedAt : e.v.normals, e.v.tangents};
+                     },
+                     st, t0, info);
+}
+
+}  // namespace ptrhost
+
+namespace {
+
+// What every update entry point of this file is: a null scene refused, the call's rules (check), the device work (run)
+template <typename Check, typename Run>
+int updateCall(const char* who, PtrDeviceScene* scene, char* err, size_t err_cap, Check&& check, Run&& run) {
+    if (!scene) return nullArgument(who, err, err_cap);
+    try {
+        const std::string problem = check();
+        if (!problem.empty()) return refuse(err, err_cap, std::string(who) + ": " + problem);
+    }
+    PTR_CATCH_ALL(err, err_cap)
+    return deviceCall(who, scene, true, err, err_cap, run);
+}
+
 }  // namespace
 
 extern "C" {
@@ -229,242 +484,47 @@ int ptr_scene_is_dynamic(const PtrDeviceScene* scene) { return scene && scene->d
 
 int ptr_scene_set_mesh_transforms(PtrDeviceScene* scene, const PtrMeshTransform* transforms, uint32_t count, void* stream, PtrUpdateInfo* info,
                                   char* err, size_t err_cap) {
-    const char* who = "ptr_scene_set_mesh_transforms";
-    if (!scene) return nullArgument(who, err, err_cap);
-    if (!scene->dynamic) return refuse(err, err_cap, std::string(who) + ": the scene is not dynamic (upload it with ptr_scene_upload_dynamic)");
-    if (!transforms) return refuse(err, err_cap, std::string(who) + ": null transform list");
-    if (count == 0u) return refuse(err, err_cap, std::string(who) + ": count is 0");
-    DynamicScene& dyn = *scene->dynamic;
-    const uint32_t meshCount = static_cast<uint32_t>(dyn.meshTriOffsets.size()) - 1u;
-    std::vector<DynMeshRow> rows(count);
-    try {
-        std::vector<uint8_t> named(meshCount, 0);
-        for (uint32_t i = 0; i < count; ++i) {
-            const PtrMeshTransform& t = transforms[i];
-            if (t.meshIndex >= meshCount) {
-                return refuse(err, err_cap, std::string(who) + ": mesh index " + std::to_string(t.meshIndex) + " out of range (the scene has " +
-                                                std::to_string(meshCount) + " meshes)");
-            }
-            if (named[t.meshIndex]++) return refuse(err, err_cap, std::string(who) + ": mesh index " + std::to_string(t.meshIndex) + " named twice");
-            ptr::MeshBake bake;
-            ptr::ComputeMeshBake(t.localToWorld, bake);
-            const std::string problem = matrixProblem(t.localToWorld, bake);
-            if (!problem.empty()) return refuse(err, err_cap, std::string(who) + ": the matrix of mesh " + std::to_string(t.meshIndex) + " " + problem);
-            rows[i] = meshRowOf(bake, dyn.meshHasTangents[t.meshIndex] != 0);
-        }
-    }
-    PTR_CATCH_ALL(err, err_cap)
-
-    return deviceCall(who, scene, true, err, err_cap, [&] {
-        const auto t0 = std::chrono::steady_clock::now();
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        PtrDeviceScene& ds = *scene;
-        dyn.meshTable.ensure(static_cast<size_t>(count) * kDynMeshVec4);
-        HIP_CHECK(hipMemcpyAsync(dyn.meshTable.ptr, rows.data(), rows.size() * sizeof(DynMeshRow), hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipEventRecord(dyn.events[0], st));
-        const DynBakeArrays arrays = bakeArrays(ds);
-        uint64_t moved = 0;
-        for (uint32_t i = 0; i < count; ++i) {
-            const uint32_t m = transforms[i].meshIndex;
-            const uint32_t first = dyn.meshTriOffsets[m], n = dyn.meshTriOffsets[m + 1u] - first;
-            launchDynBake(arrays, dyn.meshTable.ptr, i, dyn.meshTris.ptr + first, n, st);
-            dyn.meshRows[m] = rows[i];   // the matrix a later ptr_scene_set_mesh_vertices bakes under
-            moved += n;
-        }
-        finishUpdate(ds, st, t0, moved, info);
-    });
+    TransformUpdate u;
+    return updateCall("ptr_scene_set_mesh_transforms", scene, err, err_cap, [&] { return checkMeshTransforms(scene, transforms, count, u); },
+                      [&] { runMeshTransforms(*scene, u, static_cast<hipStream_t>(stream), info); });
 }
 
 int ptr_scene_set_mesh_vertices(PtrDeviceScene* scene, const PtrMeshVertices* meshes, uint32_t count, void* stream, PtrUpdateInfo* info, char* err,
                                 size_t err_cap) {
-    const char* who = "ptr_scene_set_mesh_vertices";
-    if (!scene) return nullArgument(who, err, err_cap);
-    if (!scene->dynamic || !(scene->dynamic->flags & PTR_DYNAMIC_DEFORMABLE)) {
-        return refuse(err, err_cap, std::string(who) + ": the scene is not deformable (upload it with ptr_scene_upload_dynamic_ex and PTR_DYNAMIC_DEFORMABLE)");
-    }
-    if (!meshes) return refuse(err, err_cap, std::string(who) + ": null mesh list");
-    if (count == 0u) return refuse(err, err_cap, std::string(who) + ": count is 0");
-    DynamicScene& dyn = *scene->dynamic;
-    const uint32_t meshCount = static_cast<uint32_t>(dyn.meshTriOffsets.size()) - 1u;
-    // where the arrays of every named mesh go in the staging buffer, in floats (a mesh without triangles stages nothing)
-    struct Staged {
-        size_t positions = 0, normals = 0, tangents = 0;
-        bool used = false, hasTangents = false;
-    };
-    std::vector<Staged> staged(count);
-    std::vector<DynMeshRow> rows(count);
-    size_t floats = 0;
-    try {
-        std::vector<uint8_t> named(meshCount, 0);
-        for (uint32_t i = 0; i < count; ++i) {
-            const PtrMeshVertices& mv = meshes[i];
-            Staged& s = staged[i];
-            const std::string problem = namedMeshProblem(dyn, mv, named, false, "", s.used);
-            if (!problem.empty()) return refuse(err, err_cap, std::string(who) + ": " + problem);
-            rows[i] = dyn.meshRows[mv.meshIndex];
-            if (!s.used) continue;
-            s.hasTangents = dyn.meshHasTangents[mv.meshIndex] != 0;   // (an untextured scene keeps no tangents: they are checked and dropped)
-            s.positions = floats, floats += static_cast<size_t>(mv.vertexCount) * 3u;
-            s.normals = floats, floats += static_cast<size_t>(mv.vertexCount) * 3u;
-            if (s.hasTangents) s.tangents = floats, floats += static_cast<size_t>(mv.vertexCount) * 4u;
-        }
-        // staging: every array into the scene's pinned buffer, each component looked at on the way
-        HIP_CHECK(hipSetDevice(scene->device));
-        float* pinned = static_cast<float*>(dyn.pinnedFor(std::max<size_t>(floats, 4u) * sizeof(float)));
-        auto stage = [&](const float* src, size_t n, float* dst) {
-            bool finite = true;
-            for (size_t k = 0; k < n; ++k) {
-                finite = finite && std::isfinite(src[k]);
-                dst[k] = src[k];
-            }
-            return finite;
-        };
-        for (uint32_t i = 0; i < count; ++i) {
-            const PtrMeshVertices& mv = meshes[i];
-            const Staged& s = staged[i];
-            if (!s.used) continue;
-            const size_t n = mv.vertexCount;
-            const char* bad = nullptr;
-            if (!stage(mv.positions, n * 3u, pinned + s.positions)) bad = "position";
-            else if (!stage(mv.normals, n * 3u, pinned + s.normals)) bad = "normal";
-            else if (mv.tangents) {
-                std::vector<float> dropped;
-                if (!s.hasTangents) dropped.resize(n * 4u);
-                if (!stage(mv.tangents, n * 4u, s.hasTangents ? pinned + s.tangents : dropped.data())) bad = "tangent";
-            }
-            if (bad) return refuse(err, err_cap, std::string(who) + ": mesh " + std::to_string(mv.meshIndex) + " has a non-finite " + bad + " component");
-        }
-    }
-    PTR_CATCH_ALL(err, err_cap)
-
-    return deviceCall(who, scene, true, err, err_cap, [&] {
-        const auto t0 = std::chrono::steady_clock::now();
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        dyn.staging.ensure((floats + 3u) / 4u);
-        const float* dStaged = reinterpret_cast<const float*>(dyn.staging.ptr);
-        if (floats) HIP_CHECK(hipMemcpyAsync(dyn.staging.ptr, dyn.pinned, floats * sizeof(float), hipMemcpyHostToDevice, st));
-        dyn.meshTable.ensure(static_cast<size_t>(count) * kDynMeshVec4);
-        HIP_CHECK(hipMemcpyAsync(dyn.meshTable.ptr, rows.data(), rows.size() * sizeof(DynMeshRow), hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipEventRecord(dyn.events[0], st));
-        std::vector<MeshSource> src(count);
-        for (uint32_t i = 0; i < count; ++i) {
-            const Staged& s = staged[i];
-            src[i].used = s.used;
-            if (s.used) src[i].v = DynVertexArrays{dStaged + s.positions, dStaged + s.normals, s.hasTangents ? dStaged + s.tangents : nullptr};
-        }
-        gatherBakeFinish(*scene, meshes, src, st, t0, info);
-    });
+    VerticesUpdate u;
+    const float* pinned = nullptr;
+    return updateCall("ptr_scene_set_mesh_vertices", scene, err, err_cap,
+                      [&] {
+                          const std::string problem = checkMeshVertices(scene, meshes, count, u);
+                          if (!problem.empty()) return problem;
+                          // staging: every array into the scene's pinned buffer, each component looked at on the way
+                          HIP_CHECK(hipSetDevice(scene->device));
+                          float* staged = static_cast<float*>(scene->dynamic->pinnedFor(std::max<size_t>(u.floats, 4u) * sizeof(float)));
+                          pinned = staged;
+                          return stageMeshVertices(meshes, u, staged);
+                      },
+                      [&] { runMeshVertices(*scene, u, pinned, static_cast<hipStream_t>(stream), info); });
 }
 
 int ptr_scene_set_mesh_vertices_device(PtrDeviceScene* scene, const PtrMeshVerticesDevice* meshes, uint32_t count, void* stream, PtrUpdateInfo* info,
                                        char* err, size_t err_cap) {
-    const char* who = "ptr_scene_set_mesh_vertices_device";
-    if (!scene) return nullArgument(who, err, err_cap);
-    if (!scene->dynamic || !(scene->dynamic->flags & PTR_DYNAMIC_DEFORMABLE)) {
-        return refuse(err, err_cap, std::string(who) + ": the scene is not deformable (upload it with ptr_scene_upload_dynamic_ex and PTR_DYNAMIC_DEFORMABLE)");
-    }
-    if (!meshes) return refuse(err, err_cap, std::string(who) + ": null mesh list");
-    if (count == 0u) return refuse(err, err_cap, std::string(who) + ": count is 0");
-    DynamicScene& dyn = *scene->dynamic;
-    const uint32_t meshCount = static_cast<uint32_t>(dyn.meshTriOffsets.size()) - 1u;
-    const bool computes = (dyn.flags & PTR_DYNAMIC_VERTEX_NORMALS) != 0u;
-    std::vector<MeshSource> src(count);
-    std::vector<DynMeshRow> rows(count);
-    // the arrays k_dyn_check_finite looks at, in the order a refusal names them: per named mesh positions, normals, tangents
-    struct Checked {
-        uint32_t entry;      // of the list
-        const char* what;
-        bool computed;       // normals this call computes: the row's pointer is set once the scratch is there
-    };
-    std::vector<DynCheckRow> checks;
-    std::vector<Checked> checked;
-    std::vector<size_t> computedAt(count, 0);   // per entry whose normals are computed: where, in floats of the scratch
-    size_t computedFloats = 0;
-    uint64_t largest = 0;
-    try {
-        std::vector<uint8_t> named(meshCount, 0);
-        for (uint32_t i = 0; i < count; ++i) {
-            const PtrMeshVerticesDevice& mv = meshes[i];
-            const std::string problem = namedMeshProblem(dyn, mv, named, computes, " (computing them needs a scene uploaded with PTR_DYNAMIC_VERTEX_NORMALS)", src[i].used);
-            if (!problem.empty()) return refuse(err, err_cap, std::string(who) + ": " + problem);
-            rows[i] = dyn.meshRows[mv.meshIndex];
-            if (!src[i].used) continue;
-            const size_t n = mv.vertexCount;
-            const struct {
-                const float* data;
-                size_t floats;
-                const char* what;
-                bool computedIfNull;
-            } given[3] = {{mv.positions, n * 3u, "position", false}, {mv.normals, n * 3u, "normal", true}, {mv.tangents, n * 4u, "tangent", false}};
-            for (const auto& g : given) {
-                if (!g.data && !g.computedIfNull) continue;   // (no tangents: the mesh carries none)
-                if (g.data) {
-                    const std::string bad = devicePointerProblem(g.data, g.floats * sizeof(float), scene->device);
-                    if (!bad.empty()) return refuse(err, err_cap, std::string(who) + ": the " + g.what + " array of mesh " + std::to_string(mv.meshIndex) + " " + bad);
-                }
-                checks.push_back(DynCheckRow{g.data, g.floats});
-                checked.push_back(Checked{i, g.what, !g.data});
-                largest = std::max<uint64_t>(largest, g.floats);
-            }
-            if (!mv.normals) computedAt[i] = computedFloats, computedFloats += n * 3u;
-            // (an untextured scene keeps no tangents: they are checked and dropped)
-            src[i].v = DynVertexArrays{mv.positions, mv.normals, dyn.meshHasTangents[mv.meshIndex] ? mv.tangents : nullptr};
-        }
-        if (pastIndexLimit(checks.size())) return refuse(err, err_cap, std::string(who) + ": too many meshes in one call");
-    }
-    PTR_CATCH_ALL(err, err_cap)
-
-    return deviceCall(who, scene, true, err, err_cap, [&] {
-        const auto t0 = std::chrono::steady_clock::now();
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        if (computedFloats) dyn.computedNormals.ensure(computedFloats);
-        for (size_t r = 0; r < checks.size(); ++r) {
-            if (!checked[r].computed) continue;
-            const uint32_t i = checked[r].entry;
-            src[i].v.normals = checks[r].data = dyn.computedNormals.ptr + computedAt[i];
-        }
-        // the check rows ride behind the mesh rows of the table (both are 16 B units)
-        dyn.meshTable.ensure(static_cast<size_t>(count) * kDynMeshVec4 + checks.size());
-        HIP_CHECK(hipMemcpyAsync(dyn.meshTable.ptr, rows.data(), rows.size() * sizeof(DynMeshRow), hipMemcpyHostToDevice, st));
-        const DynCheckRow* dChecks = reinterpret_cast<const DynCheckRow*>(dyn.meshTable.ptr + static_cast<size_t>(count) * kDynMeshVec4);
-        const size_t words = (checks.size() + 31u) / 32u;
-        if (!checks.empty()) {
-            HIP_CHECK(hipMemcpyAsync(const_cast<DynCheckRow*>(dChecks), checks.data(), checks.size() * sizeof(DynCheckRow), hipMemcpyHostToDevice, st));
-            dyn.checkFlags.ensure(words);
-            HIP_CHECK(hipMemsetAsync(dyn.checkFlags.ptr, 0, words * sizeof(uint32_t), st));
-        }
-        HIP_CHECK(hipEventRecord(dyn.events[0], st));
-        for (uint32_t i = 0; i < count; ++i) {
-            if (!src[i].used || meshes[i].normals) continue;
-            const uint32_t m = meshes[i].meshIndex;
-            const size_t first = dyn.meshTriOffsets[m];
-            launchDynVertexNormals(meshes[i].positions, dyn.adjOffsets.ptr + dyn.adjBase[m], dyn.adjEntries.ptr + first * 3u, dyn.meshCorners.ptr + first * 3u,
-                                   dyn.computedNormals.ptr + computedAt[i], meshes[i].vertexCount, st);
-        }
-        if (!checks.empty()) {
-            // nothing the renderer reads has been written yet: the flag words come back first, and a set bit ends the call here
-            launchDynCheckFinite(dChecks, static_cast<uint32_t>(checks.size()), largest, dyn.checkFlags.ptr, st);
-            const uint32_t* flags = static_cast<const uint32_t*>(dyn.pinnedFor(words * sizeof(uint32_t)));
-            HIP_CHECK(hipMemcpyAsync(dyn.pinned, dyn.checkFlags.ptr, words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            for (size_t r = 0; r < checks.size(); ++r) {
-                if (flags[r >> 5] >> (r & 31u) & 1u) {
-                    throw HipError{std::string(who) + ": mesh " + std::to_string(meshes[checked[r].entry].meshIndex) + " has a non-finite " + checked[r].what +
-                                   " component"};
-                }
-            }
-        }
-        gatherBakeFinish(*scene, meshes, src, st, t0, info);
-    });
+    static const char* const who = "ptr_scene_set_mesh_vertices_device";
+    DeviceVerticesUpdate u;
+    return updateCall(who, scene, err, err_cap, [&] { return checkMeshVerticesDevice(scene, meshes, count, scene->device, u); },
+                      [&] { runMeshVerticesDevice(who, *scene, u, true, static_cast<hipStream_t>(stream), info); });
 }
 
 int ptr_scene_set_spheres(PtrDeviceScene* scene, const PtrSphereUpdate* spheres, uint32_t count, void* stream, PtrUpdateInfo* info, char* err,
                           size_t err_cap) {
-    return setPrimitives("ptr_scene_set_spheres", 0u, scene, spheres, count, stream, info, err, err_cap);
+    PrimitivesUpdate u;
+    return updateCall("ptr_scene_set_spheres", scene, err, err_cap, [&] { return checkPrimitives(0u, scene, spheres, count, u); },
+                      [&] { runPrimitives(*scene, u, static_cast<hipStream_t>(stream), info); });
 }
 
 int ptr_scene_set_rects(PtrDeviceScene* scene, const PtrRectUpdate* rects, uint32_t count, void* stream, PtrUpdateInfo* info, char* err, size_t err_cap) {
-    return setPrimitives("ptr_scene_set_rects", 1u, scene, rects, count, stream, info, err, err_cap);
+    PrimitivesUpdate u;
+    return updateCall("ptr_scene_set_rects", scene, err, err_cap, [&] { return checkPrimitives(1u, scene, rects, count, u); },
+                      [&] { runPrimitives(*scene, u, static_cast<hipStream_t>(stream), info); });
 }
 
 uint32_t ptr_scene_dynamic_flags(const PtrDeviceScene* scene) { return scene && scene->dynamic ? scene->dynamic->flags : 0u; }
@@ -642,61 +702,60 @@ std::string rectRows(PrimitiveRecords& prims, const PtrRectUpdate& u, ScatterRow
     return "";
 }
 
-// ptr_scene_set_spheres (kind 0) and ptr_scene_set_rects (kind 1): the rows on the host, one copy, one scatter, the refit
-int setPrimitives(const char* who, uint32_t kind, PtrDeviceScene* scene, const void* list, uint32_t count, void* stream, PtrUpdateInfo* info, char* err,
-                  size_t err_cap) {
-    if (!scene) return nullArgument(who, err, err_cap);
-    if (!scene->dynamic || !(scene->dynamic->flags & PTR_DYNAMIC_PRIMITIVES)) {
-        return refuse(err, err_cap, std::string(who) + ": the scene does not keep its primitives (upload it with ptr_scene_upload_dynamic_ex and PTR_DYNAMIC_PRIMITIVES)");
-    }
-    if (!list) return refuse(err, err_cap, std::string(who) + ": null list");
-    if (count == 0u) return refuse(err, err_cap, std::string(who) + ": count is 0");
-    DynamicScene& dyn = *scene->dynamic;
-    ScatterRows rows;
-    PrimitiveRecords next;
-    try {
-        next = dyn.prims;   // the records change only when the whole call is accepted
-        std::vector<uint8_t> named(kind == 0u ? next.spheres.size() : next.rects.size(), 0);
-        for (uint32_t i = 0; i < count; ++i) {
-            const uint32_t index = kind == 0u ? static_cast<const PtrSphereUpdate*>(list)[i].sphereIndex : static_cast<const PtrRectUpdate*>(list)[i].rectIndex;
-            if (index < named.size() && named[index]++) {
-                return refuse(err, err_cap, std::string(who) + ": " + (kind == 0u ? "sphere" : "rectangle") + " index " + std::to_string(index) + " named twice");
-            }
-            const std::string problem = kind == 0u ? sphereRows(next, static_cast<const PtrSphereUpdate*>(list)[i], rows)
-                                                   : rectRows(next, static_cast<const PtrRectUpdate*>(list)[i], rows);
-            if (!problem.empty()) return refuse(err, err_cap, std::string(who) + ": " + problem);
-        }
-    }
-    PTR_CATCH_ALL(err, err_cap)
+}  // namespace
 
-    return deviceCall(who, scene, true, err, err_cap, [&] {
-        const auto t0 = std::chrono::steady_clock::now();
-        hipStream_t st = static_cast<hipStream_t>(stream);
-        PtrDeviceScene& ds = *scene;
-        const size_t n = rows.dest.size();
-        char* pinned = static_cast<char*>(dyn.pinnedFor(std::max<size_t>(n, 1u) * 20u));
-        std::memcpy(pinned, rows.rows.data(), n * 16u);
-        std::memcpy(pinned + n * 16u, rows.dest.data(), n * 4u);
-        dyn.staging.ensure(n + (n + 3u) / 4u);
-        HIP_CHECK(hipMemcpyAsync(dyn.staging.ptr, pinned, n * 20u, hipMemcpyHostToDevice, st));
-        HIP_CHECK(hipEventRecord(dyn.events[0], st));
-        const size_t tris = dyn.triCount, spheres = dyn.sphereCount;
-        DynScatterTargets t{};
-        auto target = [&](uint32_t array, float4* base, size_t rowCount) { t.base[array] = base, t.rows[array] = static_cast<uint32_t>(rowCount); };
-        target(PTR_SCATTER_TRIS, ds.tris.ptr, tris * 3u);
-        target(PTR_SCATTER_TRI_NORMALS, ds.triNormals.ptr, tris * 3u);
-        target(PTR_SCATTER_TRI_BOUNDS, dyn.triBounds.ptr, tris * 2u);
-        target(PTR_SCATTER_SPHERES, ds.spheres.ptr, spheres);
-        target(PTR_SCATTER_SPHERE_BOUNDS, dyn.sphereBounds.ptr, spheres * 2u);
-        target(PTR_SCATTER_RECTS, ds.rects.ptr, dyn.prims.rects.size() * 5u);
-        target(PTR_SCATTER_RECT_LIGHTS, ds.rectLights.ptr, static_cast<size_t>(ds.view.rectLightCount) * kRectLightVec4);
-        launchDynScatterRows(t, dyn.staging.ptr, reinterpret_cast<const uint32_t*>(dyn.staging.ptr + n), static_cast<uint32_t>(n), st);
-        dyn.prims = std::move(next);
-        finishUpdate(ds, st, t0, kind == 1u ? static_cast<uint64_t>(count) * 2u : 0u, info);
-    });
+namespace ptrhost {
+
+// ptr_scene_set_spheres (kind 0) and ptr_scene_set_rects (kind 1): the rows on the host ...
+std::string checkPrimitives(uint32_t kind, const PtrDeviceScene* scene, const void* list, uint32_t count, PrimitivesUpdate& out) {
+    if (!scene->dynamic || !(scene->dynamic->flags & PTR_DYNAMIC_PRIMITIVES)) {
+        return "the scene does not keep its primitives (upload it with ptr_scene_upload_dynamic_ex and PTR_DYNAMIC_PRIMITIVES)";
+    }
+    const std::string bad = listProblem(list, count, "null list");
+    if (!bad.empty()) return bad;
+    out.kind = kind, out.count = count;
+    PrimitiveRecords& next = out.next;
+    next = scene->dynamic->prims;   // the records change only when the whole call is accepted
+    std::vector<uint8_t> named(kind == 0u ? next.spheres.size() : next.rects.size(), 0);
+    for (uint32_t i = 0; i < count; ++i) {
+        const uint32_t index = kind == 0u ? static_cast<const PtrSphereUpdate*>(list)[i].sphereIndex : static_cast<const PtrRectUpdate*>(list)[i].rectIndex;
+        if (index < named.size() && named[index]++) return std::string(kind == 0u ? "sphere" : "rectangle") + " index " + std::to_string(index) + " named twice";
+        const std::string problem = kind == 0u ? sphereRows(next, static_cast<const PtrSphereUpdate*>(list)[i], out.rows)
+                                               : rectRows(next, static_cast<const PtrRectUpdate*>(list)[i], out.rows);
+        if (!problem.empty()) return problem;
+    }
+    return "";
 }
 
-}  // namespace
+// ... one copy, one scatter, the refit
+void runPrimitives(PtrDeviceScene& ds, const PrimitivesUpdate& u, hipStream_t st, PtrUpdateInfo* info, const InputsEnqueued& enqueued) {
+    const auto t0 = std::chrono::steady_clock::now();
+    DynamicScene& dyn = *ds.dynamic;
+    const ScatterRows& rows = u.rows;
+    const size_t n = rows.dest.size();
+    char* pinned = static_cast<char*>(dyn.pinnedFor(std::max<size_t>(n, 1u) * 20u));
+    std::memcpy(pinned, rows.rows.data(), n * 16u);
+    std::memcpy(pinned + n * 16u, rows.dest.data(), n * 4u);
+    dyn.staging.ensure(n + (n + 3u) / 4u);
+    HIP_CHECK(hipMemcpyAsync(dyn.staging.ptr, pinned, n * 20u, hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipEventRecord(dyn.events[0], st));
+    if (enqueued) enqueued();
+    const size_t tris = dyn.triCount, spheres = dyn.sphereCount;
+    DynScatterTargets t{};
+    auto target = [&](uint32_t array, float4* base, size_t rowCount) { t.base[array] = base, t.rows[array] = static_cast<uint32_t>(rowCount); };
+    target(PTR_SCATTER_TRIS, ds.tris.ptr, tris * 3u);
+    target(PTR_SCATTER_TRI_NORMALS, ds.triNormals.ptr, tris * 3u);
+    target(PTR_SCATTER_TRI_BOUNDS, dyn.triBounds.ptr, tris * 2u);
+    target(PTR_SCATTER_SPHERES, ds.spheres.ptr, spheres);
+    target(PTR_SCATTER_SPHERE_BOUNDS, dyn.sphereBounds.ptr, spheres * 2u);
+    target(PTR_SCATTER_RECTS, ds.rects.ptr, dyn.prims.rects.size() * 5u);
+    target(PTR_SCATTER_RECT_LIGHTS, ds.rectLights.ptr, static_cast<size_t>(ds.view.rectLightCount) * kRectLightVec4);
+    launchDynScatterRows(t, dyn.staging.ptr, reinterpret_cast<const uint32_t*>(dyn.staging.ptr + n), static_cast<uint32_t>(n), st);
+    dyn.prims = u.next;
+    finishUpdate(ds, st, t0, u.kind == 1u ? static_cast<uint64_t>(u.count) * 2u : 0u, info);
+}
+
+}  // namespace ptrhost
 
 extern "C" {
 

@@ -1,0 +1,115 @@
+// What the update calls of a dynamic scene (dynamic.cpp, rebuild.cpp: include/ptr_dynamic.h, ptr_deform.h, ptr_deform_device.h,
+// ptr_rebuild.h) share with the frame on several devices that fans them out (multi_dynamic.cpp: include/ptr_multi_dynamic.h).  Every call
+// is two halves: check*, the rules of the call on the host - no device work, "" or the refusal without the caller's name in front - which
+// leaves the accepted update behind, and run*, the device work of that update on one scene and one stream, joined before it returns.
+// Scenes uploaded from one preparation with the same flags and given the same calls hold the same host-side records, so an update checked
+// against one of them runs on all of them.  Internal: not part of the C-ABI.
+#pragma once
+
+#include <functional>
+#include <string>
+#include <vector>
+
+#include "device_scene.h"
+#include "ptr_deform_device.h"
+#include "ptr_rebuild.h"
+
+namespace ptrhost {
+
+// A call refused after device work began, the scene as it was (a non-finite component found on the device, the depth bounds of a
+// rebuild): reported like any failure by the single-device calls, told apart from a device failure by multi_dynamic.cpp.
+struct Refused : HipError {
+    explicit Refused(std::string m) : HipError{std::move(m)} {}
+};
+
+// The host-side records of a dynamic scene, the ones the check halves read, from a description and its preparation: what
+// uploadDynamicTables keeps beside the device arrays.  No device call.
+void fillDynamicRecords(const PtrSceneDesc& desc, const ptr::PreparedGeometry& pg, const ptr::DynamicTables& t, const std::vector<int32_t>& lightIndexByRect,
+                        DynamicScene& dyn);
+
+// What a run half calls (when given) once the copies that bring the scene the call's inputs are enqueued on its stream
+using InputsEnqueued = std::function<void()>;
+
+// "" or what is wrong with a call's list before anyone looks into it
+std::string listProblem(const void* list, uint32_t count, const char* nullWords);
+// "" or what the uploads of a dynamic scene refuse about `flags`; `known` is the mask of the PTR_DYNAMIC_* flags the entry point knows
+std::string dynamicFlagsProblem(uint32_t flags, uint32_t known);
+
+// ---- ptr_scene_set_mesh_transforms
+struct TransformUpdate {
+    std::vector<uint32_t> mesh;
+    std::vector<ptrk::DynMeshRow> rows;
+};
+std::string checkMeshTransforms(const PtrDeviceScene* scene, const PtrMeshTransform* transforms, uint32_t count, TransformUpdate& out);
+void runMeshTransforms(PtrDeviceScene& ds, const TransformUpdate& u, hipStream_t st, PtrUpdateInfo* info, const InputsEnqueued& enqueued = {});
+
+// ---- ptr_scene_set_mesh_vertices: the layout of the staging buffer, the staging (each component looked at on the way), the device half
+struct VerticesUpdate {
+    struct Entry {
+        uint32_t mesh = 0;
+        size_t positions = 0, normals = 0, tangents = 0;   // where the arrays go in the staging buffer, in floats
+        bool used = false, hasTangents = false;            // used false: a mesh without triangles stages nothing
+    };
+    std::vector<Entry> entry;
+    std::vector<ptrk::DynMeshRow> rows;
+    size_t floats = 0;
+};
+std::string checkMeshVertices(const PtrDeviceScene* scene, const PtrMeshVertices* meshes, uint32_t count, VerticesUpdate& out);
+std::string stageMeshVertices(const PtrMeshVertices* meshes, const VerticesUpdate& u, float* pinned);
+// pinned: u.floats staged floats in pinned host memory this device's copies may read
+void runMeshVertices(PtrDeviceScene& ds, const VerticesUpdate& u, const float* pinned, hipStream_t st, PtrUpdateInfo* info,
+                     const InputsEnqueued& enqueued = {});
+
+// ---- ptr_scene_set_mesh_vertices_device
+struct DeviceVerticesUpdate {
+    struct Entry {
+        uint32_t mesh = 0, vertexCount = 0;
+        bool used = false, computes = false;                      // computes: null normals, k_dyn_vertex_normals fills them
+        ptrk::DynVertexArrays v{nullptr, nullptr, nullptr};       // where the gather reads its arrays, on the device
+        size_t computedAt = 0;                                    // computes: where in the scene's scratch, in floats
+    };
+    // the arrays k_dyn_check_finite looks at, in the order a refusal names them: per named mesh positions, normals, tangents
+    struct Checked {
+        uint32_t entry;      // of the list
+        const char* what;
+        bool computed;       // normals the call computes: the row's pointer is set once the scratch is there
+        const float* data;   // given: the caller's array
+        uint64_t floats;
+    };
+    std::vector<Entry> entry;
+    std::vector<Checked> checked;
+    std::vector<ptrk::DynMeshRow> rows;
+    size_t computedFloats = 0;
+};
+// arraysDevice: the device the caller's arrays must live on
+std::string checkMeshVerticesDevice(const PtrDeviceScene* scene, const PtrMeshVerticesDevice* meshes, uint32_t count, int arraysDevice,
+                                    DeviceVerticesUpdate& out);
+// k_dyn_check_finite over the given arrays of `u` alone, on the current device (the one they live on) and `st`, which is joined: throws
+// Refused "<who>: mesh M has a non-finite ... component".  dRows / dFlags: scratch on that device; pinnedFor: its pinned twin.
+void checkGivenArrays(const char* who, const DeviceVerticesUpdate& u, DeviceBuffer<float4>& dRows, DeviceBuffer<uint32_t>& dFlags, uint32_t* pinnedFlags,
+                      hipStream_t st);
+// The arrays of u.entry are on ds.device.  checkGiven false: the given arrays were looked at already and only computed normals are.
+void runMeshVerticesDevice(const char* who, PtrDeviceScene& ds, const DeviceVerticesUpdate& u, bool checkGiven, hipStream_t st, PtrUpdateInfo* info);
+
+// ---- ptr_scene_set_spheres (kind 0) and ptr_scene_set_rects (kind 1)
+// The staging buffer of the two calls: 16 B rows and where each goes, (PTR_SCATTER_* << 28) | row
+struct ScatterRows {
+    std::vector<float> rows;
+    std::vector<uint32_t> dest;
+};
+struct PrimitivesUpdate {
+    uint32_t kind = 0, count = 0;
+    ScatterRows rows;
+    PrimitiveRecords next;   // the records once the call is accepted
+};
+std::string checkPrimitives(uint32_t kind, const PtrDeviceScene* scene, const void* list, uint32_t count, PrimitivesUpdate& out);
+void runPrimitives(PtrDeviceScene& ds, const PrimitivesUpdate& u, hipStream_t st, PtrUpdateInfo* info, const InputsEnqueued& enqueued = {});
+
+// ---- ptr_scene_tree_cost and ptr_scene_rebuild_tree (rebuild.cpp)
+std::string rebuildFlagsProblem(uint32_t flags);
+std::string checkTreeCall(const PtrDeviceScene* scene, uint32_t flags);
+double treeCost(PtrDeviceScene& ds, hipStream_t st);
+// a depth refusal of step 8 is thrown as Refused "<who>: ...", the scene unchanged
+void rebuildTree(const char* who, PtrDeviceScene& ds, uint32_t flags, hipStream_t st, PtrRebuildInfo& info);
+
+}  // namespace ptrhost

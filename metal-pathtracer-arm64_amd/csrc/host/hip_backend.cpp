@@ -24,6 +24,7 @@
 #include "env_importance_sampler.h"
 #include "geometry_cache.h"
 #include "knobs.h"
+#include "dynamic_host.h"
 #include "ptr_deform_device.h"
 #include "ptr_dynamic.h"
 #include "scene_geometry.h"
@@ -389,13 +390,21 @@ int uploadTo(const char* who, const PtrSceneDesc* scene, const char* cachePath, 
     PTR_CATCH_ALL(err, cap)
 }
 
+}  // namespace
+
+std::string ptrhost::dynamicFlagsProblem(uint32_t flags, uint32_t known) {
+    if (flags & ~known) return "unknown flag";
+    if ((flags & PTR_DYNAMIC_VERTEX_NORMALS) && !(flags & PTR_DYNAMIC_DEFORMABLE)) return "PTR_DYNAMIC_VERTEX_NORMALS needs PTR_DYNAMIC_DEFORMABLE";
+    return "";
+}
+
+namespace {
+
 // The three uploads of a dynamic scene: `known` is the mask of the PTR_DYNAMIC_* flags the entry point `who` knows
 int uploadDynamic(const char* who, uint32_t known, const PtrSceneDesc* scene, int device, uint32_t flags, PtrDeviceScene** out_scene, char* err,
                   size_t err_cap) {
-    if (flags & ~known) return refuse(err, err_cap, std::string(who) + ": unknown flag");
-    if ((flags & PTR_DYNAMIC_VERTEX_NORMALS) && !(flags & PTR_DYNAMIC_DEFORMABLE)) {
-        return refuse(err, err_cap, std::string(who) + ": PTR_DYNAMIC_VERTEX_NORMALS needs PTR_DYNAMIC_DEFORMABLE");
-    }
+    const std::string problem = dynamicFlagsProblem(flags, known);
+    if (!problem.empty()) return refuse(err, err_cap, std::string(who) + ": " + problem);
     if (scene && out_scene && ptr_device_count() < 1) return noDevice(who, err, err_cap);
     return uploadTo(who, scene, nullptr, device, out_scene, err, err_cap, true, flags);
 }

@@ -3,7 +3,8 @@
 // buffers; on the host the count classes - the argument checks, and one driver that runs a call's partitions on threads which meet at
 // a round barrier (round_barrier.h) and end together when one of them fails.  The only loop of its own is ptr_frame.h's refine run in
 // lock step over the partitions; the sample step, the sources and the state's owner are adaptive_host.h's, the class kernels frame.h's,
-// the exchange, the device list and the hand-over to the first device multi_host.h's, finish and interleave multi.h's.
+// the exchange, the device list and the hand-over to the first device multi_host.h's, finish and interleave multi.h's.  The frame
+// object, what a partition keeps and the partition driver are declared in multi_frame_host.h, which multi_dynamic.cpp shares.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -19,6 +20,7 @@
 #include "adaptive_host.h"
 #include "device_scene.h"
 #include "knobs.h"
+#include "multi_frame_host.h"
 #include "multi_host.h"
 #include "parallel.h"
 #include "ptr_multi_frame.h"
@@ -29,55 +31,7 @@ using namespace ptrk;
 
 namespace {
 
-using Clock = std::chrono::steady_clock;
-double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
-
 constexpr uint32_t kOutWords = 10u;   // a partition's outputs in band layout: rgb 3, cov 6, count 1 words per pixel, one after the other
-
-// what one partition keeps for the frame's life; everything of it lives on `device`
-struct Part {
-    int device = 0;
-    bool forceStaged = false;
-    MultiPart mp{};
-    uint32_t local = 0;                      // its pixels
-    std::unique_ptr<PtrDeviceScene> scene;   // null: the test-only frame
-    hipStream_t stream = nullptr;
-    AdaptiveStore store;   // the state, image order; L_p's two buffers; the compaction's scratch and the class-minimum word
-    DeviceBuffer<uint32_t> order, listS;   // the first list; S_p
-    DeviceBuffer<uint8_t> inS;
-    DeviceBuffer<float> edge, bandOut, packed;   // the exchange's edge rows; the outputs in band layout; the checkpoint buffer
-    DeviceBuffer<float4> probeSamples, probeItems;
-    std::vector<float> hostPacked;   // the checkpoint buffer's host side
-};
-
-}  // namespace
-
-struct PtrMultiFrame {
-    PtrSettings settings{};
-    uint32_t width = 0, height = 0, parts = 0, sampleCount = 0;
-    size_t pixels = 0;
-    bool sceneless = false;
-    std::vector<std::unique_ptr<Part>> part;
-    HaloExchange ex;
-    // the first device: the partitions' band buffers one after the other, where each output of each partition starts
-    // (k_multi_interleave's table: [output][partition]), the image-order outputs of a host resolve, the feature buffers
-    int rootDevice = 0;
-    std::vector<uint64_t> wordOffset;
-    DeviceBuffer<float> gathered, image;
-    DeviceBuffer<uint64_t> dWordOffset;
-    DeviceBuffer<float4> albedo, normal;
-    // pixels per count, kept on the host as PtrFrame keeps them: the checks and ptr_multi_frame_info need no device call
-    std::map<uint32_t, uint64_t> classes;
-    bool broken = false;   // a call failed on a device: only release is left
-    PtrMultiInfo last{};
-
-    bool uniform() const { return classes.size() == 1u; }
-    uint32_t minCount() const { return classes.begin()->first; }
-    uint32_t maxCount() const { return classes.rbegin()->first; }
-    bool empty() const { return uniform() && minCount() == 0u; }
-};
-
-namespace {
 
 void destroy(PtrMultiFrame* f) {
     if (!f) return;
@@ -96,64 +50,6 @@ void destroy(PtrMultiFrame* f) {
 struct Destroy {
     void operator()(PtrMultiFrame* f) const { destroy(f); }
 };
-
-// One call's partitions on threads: body(me, p, meet) with me's device current.  meet() is the round barrier - false once a partition
-// has failed, and the body then returns at once.  Every way out of a worker but the regular one releases the partitions that wait for
-// it; every worker joins its own stream.  A failure is reported with the device's id and leaves the frame broken.
-template <typename Body>
-void runParts(PtrMultiFrame& f, Body&& body) {
-    const uint32_t parts = f.parts;
-    std::vector<std::string> errors(parts);
-    std::vector<double> seconds(parts, 0.0), waited(parts, 0.0);
-    ptr::RoundBarrier barrier(parts);
-    auto worker = [&](uint32_t p) {
-        Part& me = *f.part[p];
-        const auto t0 = Clock::now();
-        auto meet = [&]() -> bool {
-            const auto m0 = Clock::now();
-            const bool all = barrier.arriveAndWait();
-            waited[p] += since(m0);
-            return all;
-        };
-        try {
-            HIP_CHECK(hipSetDevice(me.device));
-            body(me, p, meet);
-            HIP_CHECK(hipGetLastError());
-        } catch (const HipError& e) {
-            barrier.fail();
-            errors[p] = e.message;
-        } catch (const std::exception& e) {
-            barrier.fail();
-            errors[p] = std::string("exception: ") + e.what();
-        } catch (...) {
-            barrier.fail();
-            errors[p] = "unknown exception";
-        }
-        if (me.stream) (void)hipStreamSynchronize(me.stream);
-        seconds[p] = since(t0);
-    };
-    try {
-        ptr::runOnThreads(parts, worker, [&] { barrier.fail(); });   // (a thread that could not be started never arrives)
-    } catch (...) {
-        f.broken = true;
-        (void)hipSetDevice(f.rootDevice);
-        throw;
-    }
-    (void)hipSetDevice(f.rootDevice);
-    for (uint32_t p = 0; p < parts; ++p) {
-        if (errors[p].empty()) continue;
-        f.broken = true;
-        throw HipError{"device " + std::to_string(f.part[p]->device) + ": " + errors[p]};
-    }
-    if (barrier.failed()) {
-        f.broken = true;
-        throw HipError{"a partition left the frame early"};
-    }
-    for (uint32_t p = 0; p < parts; ++p) {
-        f.last.partRenderSeconds[p] = seconds[p];
-        f.last.partWaitSeconds[p] = waited[p];
-    }
-}
 
 void beginCall(PtrMultiFrame& f) {
     std::memset(&f.last, 0, sizeof(f.last));
@@ -459,9 +355,12 @@ std::string badSize(const std::string& w, uint32_t width, uint32_t height) {
     return std::string();
 }
 
-// Create, for all three entry points: a scene (or, for the test-only frame, samples), the size, the devices asked for.
-int create(const char* who, const PtrSceneDesc* scene, const PtrSettings* settings, const float* samples, uint32_t sampleCount, bool sceneless,
-           const int* ids, int n, bool listed, PtrMultiFrame** out, char* err, size_t cap) {
+}  // namespace
+
+// Create, for every entry point: a scene (or, for the test-only frame, samples), the size, the devices asked for (multi_frame_host.h).
+int ptrhost::createMultiFrame(const char* who, const PtrSceneDesc* scene, const PtrSettings* settings, const float* samples, uint32_t sampleCount,
+                              bool sceneless, const int* ids, int n, bool listed, bool dynamic, uint32_t dynamicFlags, PtrMultiFrame** out, char* err,
+                              size_t cap) {
     const std::string w(who);
     if (!(sceneless ? samples != nullptr : scene != nullptr) || !settings || !out || (listed && !ids)) return nullArgument(who, err, cap);
     std::string bad = badSize(w, settings->width, settings->height);
@@ -480,7 +379,11 @@ int create(const char* who, const PtrSceneDesc* scene, const PtrSettings* settin
         f->sceneless = sceneless, f->sampleCount = sampleCount;
         f->rootDevice = devices[0];
         PreparedScene prepared;
-        if (!sceneless) prepareScene(*scene, prepared);   // once, for every device
+        if (!sceneless) prepareScene(*scene, prepared, nullptr, dynamic, dynamicFlags);   // once, for every device
+        if (dynamic) {
+            f->dynamic = std::make_unique<MultiDynamic>();
+            f->dynamic->flags = dynamicFlags;
+        }
 
         const uint32_t parts = f->parts;
         std::vector<uint32_t> partBands(parts, 0u);
@@ -537,29 +440,27 @@ int create(const char* who, const PtrSceneDesc* scene, const PtrSettings* settin
 }
 
 // what every call on an existing frame refuses first
-int refuseBroken(const char* who, const PtrMultiFrame* f, char* err, size_t cap) {
+int ptrhost::refuseBroken(const char* who, const PtrMultiFrame* f, char* err, size_t cap) {
     return f->broken ? refuse(err, cap, std::string(who) + ": an earlier call failed on a device; the frame can only be released") : 0;
 }
-
-}  // namespace
 
 extern "C" {
 
 int ptr_multi_frame_create(const PtrSceneDesc* scene, const PtrSettings* settings, int n_devices, PtrMultiFrame** out_frame, char* err,
                            size_t err_cap) {
-    return create("ptr_multi_frame_create", scene, settings, nullptr, 0u, false, nullptr, n_devices, false, out_frame, err, err_cap);
+    return createMultiFrame("ptr_multi_frame_create", scene, settings, nullptr, 0u, false, nullptr, n_devices, false, false, 0u, out_frame, err, err_cap);
 }
 
 int ptr_multi_frame_debug_create_on(const PtrSceneDesc* scene, const PtrSettings* settings, const int* device_ids, int n,
                                     PtrMultiFrame** out_frame, char* err, size_t err_cap) {
-    return create("ptr_multi_frame_debug_create_on", scene, settings, nullptr, 0u, false, device_ids, n, true, out_frame, err, err_cap);
+    return createMultiFrame("ptr_multi_frame_debug_create_on", scene, settings, nullptr, 0u, false, device_ids, n, true, false, 0u, out_frame, err, err_cap);
 }
 
 int ptr_multi_frame_debug_create(uint32_t width, uint32_t height, const float* samples, uint32_t sample_count, const int* device_ids, int n,
                                  PtrMultiFrame** out_frame, char* err, size_t err_cap) {
     PtrSettings size{};
     size.width = width, size.height = height;
-    return create("ptr_multi_frame_debug_create", nullptr, &size, samples, sample_count, true, device_ids, n, true, out_frame, err, err_cap);
+    return createMultiFrame("ptr_multi_frame_debug_create", nullptr, &size, samples, sample_count, true, device_ids, n, true, false, 0u, out_frame, err, err_cap);
 }
 
 void ptr_multi_frame_release(PtrMultiFrame* frame) { destroy(frame); }

@@ -9,6 +9,7 @@
 #include "../kernels/dynamic.h"
 #include "../kernels/rebuild.h"
 #include "device_scene.h"
+#include "dynamic_host.h"
 #include "ptr_rebuild.h"
 #include "rebuild_host.h"
 
@@ -67,7 +68,23 @@ void fillInfo(const PtrDeviceScene& ds, PtrRebuildInfo& info) {
     info.leaves = dyn.leafTable.size();
 }
 
-void rebuildTree(PtrDeviceScene& ds, uint32_t flags, hipStream_t stream, PtrRebuildInfo& info) {
+}  // namespace
+
+namespace ptrhost {
+
+std::string rebuildFlagsProblem(uint32_t flags) { return flags & ~static_cast<uint32_t>(PTR_REBUILD_KEEP_IF_BETTER) ? "unknown flag bits" : ""; }
+
+std::string checkTreeCall(const PtrDeviceScene* scene, uint32_t flags) {
+    if (!scene->dynamic) return "the scene is not dynamic (upload it with ptr_scene_upload_dynamic)";
+    return rebuildFlagsProblem(flags);
+}
+
+double treeCost(PtrDeviceScene& ds, hipStream_t st) {
+    DynamicScene& dyn = *ds.dynamic;
+    return treeCostOf(dyn, stateOf(dyn), floatBoxes(ds), dyn.nodeCount, st);
+}
+
+void rebuildTree(const char* who, PtrDeviceScene& ds, uint32_t flags, hipStream_t stream, PtrRebuildInfo& info) {
     const auto t0 = std::chrono::steady_clock::now();
     DynamicScene& dyn = *ds.dynamic;
     SceneView& v = ds.view;
@@ -81,7 +98,7 @@ void rebuildTree(PtrDeviceScene& ds, uint32_t flags, hipStream_t stream, PtrRebu
     };
     info.costBefore = info.costAfter = treeCostOf(dyn, st, floatBoxes(ds), nodeCount, stream);
     if (nodeCount == 0u || leafCount < 2u) return finish();   // nothing above the leaves to rebuild
-    if (leafCount != nodeCount + 1u) throw HipError{"ptr_scene_rebuild_tree: the scene's tree is not a full binary tree over its leaves"};
+    if (leafCount != nodeCount + 1u) throw HipError{std::string(who) + ": the scene's tree is not a full binary tree over its leaves"};
 
     // the second set of arrays and the scratch, once
     const size_t n = nodeCount;
@@ -124,7 +141,7 @@ void rebuildTree(PtrDeviceScene& ds, uint32_t flags, hipStream_t stream, PtrRebu
     HIP_CHECK(hipStreamSynchronize(stream));
     const uint32_t levels = pinnedBytes[0] == kHeightUnknown ? kMaxTreeDepth : pinnedBytes[0] + 1u;
     std::string problem = ptr::RebuildDepthProblem(levels, false, 0u);
-    if (!problem.empty()) throw HipError{"ptr_scene_rebuild_tree: " + problem};
+    if (!problem.empty()) throw Refused{std::string(who) + ": " + problem};
     launchRebuildSchedule(st.sortScratch.ptr, scheduleScratch, st.heights.ptr, st.sortedHeights.ptr, st.iota.ptr, st.schedule.ptr, nodeCount, st.small.ptr, stream);
     uint32_t* pinnedWords = reinterpret_cast<uint32_t*>(pinnedBytes);
     HIP_CHECK(hipMemcpyAsync(pinnedWords, st.small.ptr, levels * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -172,8 +189,8 @@ void rebuildTree(PtrDeviceScene& ds, uint32_t flags, hipStream_t stream, PtrRebu
             if (pinnedWords[d]) wideDepth = d;
         }
         problem = ptr::RebuildDepthProblem(levels, true, wideDepth);
-        if (!problem.empty()) throw HipError{"ptr_scene_rebuild_tree: " + problem};
-        if (static_cast<uint64_t>(wideCount) * 64u > 0xFFFFFFFFull) throw HipError{"ptr_scene_rebuild_tree: the four-wide nodes exceed the 4 GiB node array limit"};
+        if (!problem.empty()) throw Refused{std::string(who) + ": " + problem};
+        if (static_cast<uint64_t>(wideCount) * 64u > 0xFFFFFFFFull) throw HipError{std::string(who) + ": the four-wide nodes exceed the 4 GiB node array limit"};
         st.wnodes.ensure(static_cast<size_t>(wideCount) * 4u);
         st.wideSource.ensure(static_cast<size_t>(wideCount) * 4u);
         launchRebuildWideWrite(st.qnodes.ptr, nodeCount, cell, st.marks.ptr, st.wideIndex.ptr, st.wnodes.ptr, st.wideSource.ptr, stream);
@@ -222,28 +239,26 @@ void rebuildTree(PtrDeviceScene& ds, uint32_t flags, hipStream_t stream, PtrRebu
     finish();
 }
 
-}  // namespace
+}  // namespace ptrhost
 
 extern "C" {
 
 int ptr_scene_tree_cost(PtrDeviceScene* scene, void* stream, double* cost, char* err, size_t err_cap) {
     const char* who = "ptr_scene_tree_cost";
     if (!scene || !cost) return nullArgument(who, err, err_cap);
-    if (!scene->dynamic) return refuse(err, err_cap, std::string(who) + ": the scene is not dynamic (upload it with ptr_scene_upload_dynamic)");
-    return deviceCall(who, scene, true, err, err_cap, [&] {
-        DynamicScene& dyn = *scene->dynamic;
-        *cost = treeCostOf(dyn, stateOf(dyn), floatBoxes(*scene), dyn.nodeCount, static_cast<hipStream_t>(stream));
-    });
+    const std::string problem = checkTreeCall(scene, 0u);
+    if (!problem.empty()) return refuse(err, err_cap, std::string(who) + ": " + problem);
+    return deviceCall(who, scene, true, err, err_cap, [&] { *cost = treeCost(*scene, static_cast<hipStream_t>(stream)); });
 }
 
 int ptr_scene_rebuild_tree(PtrDeviceScene* scene, uint32_t flags, void* stream, PtrRebuildInfo* info, char* err, size_t err_cap) {
     const char* who = "ptr_scene_rebuild_tree";
     if (!scene) return nullArgument(who, err, err_cap);
-    if (!scene->dynamic) return refuse(err, err_cap, std::string(who) + ": the scene is not dynamic (upload it with ptr_scene_upload_dynamic)");
-    if (flags & ~static_cast<uint32_t>(PTR_REBUILD_KEEP_IF_BETTER)) return refuse(err, err_cap, std::string(who) + ": unknown flag bits");
+    const std::string problem = checkTreeCall(scene, flags);
+    if (!problem.empty()) return refuse(err, err_cap, std::string(who) + ": " + problem);
     return deviceCall(who, scene, true, err, err_cap, [&] {
         PtrRebuildInfo local;
-        rebuildTree(*scene, flags, static_cast<hipStream_t>(stream), local);
+        rebuildTree(who, *scene, flags, static_cast<hipStream_t>(stream), local);
         if (info) *info = local;
     });
 }
