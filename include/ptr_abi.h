@@ -339,9 +339,29 @@ int ptr_render_bands(PtrDeviceScene* scene, const PtrSettings* settings, uint32_
 
 /* First-hit feature buffers ("AOVs") of the whole frame, the inputs the reference gives its denoiser
  * (shaders/pathtrace.metal:6424-6435, 9813-9815; src/renderer/Accumulation.mm:130): for every pixel the camera ray of
- * sample `sample_index` (same jitter stream as the path tracer) is traced to its closest hit.
+ * sample `sample_index` (same jitter stream as the path tracer) is followed to the first surface the path of that sample shades
+ * under settings->metalSemantics: vertex 0 as the integrator sees it.
  * out_albedo: width*height*4 floats {base colour rgb, 1 if hit else 0}; out_normal: width*height*4 floats
- * {shading normal * 0.5 + 0.5, hit distance (0 on a miss)}; either may be NULL.  Row 0 = top. */
+ * {shading normal * 0.5 + 0.5, distance (0 on a miss)}; either may be NULL.  Row 0 = top.  A miss pixel is (0,0,0,0) / (0.5,0.5,0.5,0);
+ * in a scene without materials every pixel is one.
+ *
+ * The rule (ptr_temporal.h, ptr_post.h, INTEGRATION.md and DESIGN.md sections 3 and 6a refer to it; tests/test_gpu_aovs.py holds it):
+ * 1. Without PTR_METAL_PBR, or at a hit that is not textured: the material is the hit's, clamped to the table.  The normal starts as the
+ *    hit record's shading normal (for a mesh the interpolated vertex normal turned to the ray's side, the face normal where that has
+ *    zero length); if it has zero length it is the geometric normal; for a dielectric (type 2) it is the geometric normal as stored,
+ *    negated on a back face with PTR_METAL_FACE_NORMAL.  It is normalised and encoded as n * 0.5 + 0.5.  Albedo is the material's base
+ *    colour factor clamped to [0, 1], albedo.w = 1, normal.w = t.
+ * 2. With PTR_METAL_PBR at a textured hit (a mesh hit of a type-7 material in a scene with textures and texture coordinates): albedo is
+ *    the base colour of the per-hit material and the normal its shading normal (normal map applied), from the same lookups the
+ *    integrator makes at that vertex: with the first-hit uv gradients at vertex 0 under PTR_METAL_RAY_DIFF, else with the primary ray cone.
+ * 3. A hit the alpha test of that material discards (MASK below the cutoff, BLEND by a draw from the sample's random stream) is passed
+ *    through as the path passes through it: the next ray starts at the offset origin the integrator uses and keeps the direction, the
+ *    random stream goes on, the cone stays as the integrator leaves it (unchanged), there are no gradients past vertex 0, at most
+ *    maxDepth surfaces are visited, and Russian roulette takes no part (a path that has only passed through surfaces carries throughput
+ *    1).  The first surface that is not discarded is reported, by rule 1 or 2; normal.w is the float32 sum, in order, of the segments'
+ *    hit distances.  If nothing is left the pixel is a miss pixel.
+ * 4. A temporal step (ptr_temporal.h) writes the same two buffers with the same bits for sample 0, and its records R0, R1, R2 describe
+ *    the same reported surface; R1.w is normal.w. */
 int ptr_render_aovs(PtrDeviceScene* scene, const PtrSettings* settings, uint32_t sample_index, float* out_albedo,
                     float* out_normal, char* err, size_t err_cap);
 

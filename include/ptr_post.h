@@ -11,7 +11,9 @@
  *   rgb     W*H*3 floats.
  *   albedo  W*H*4 floats.  w > 0.5 marks a hit.
  *   normal  W*H*4 floats.  xyz = n*0.5 + 0.5, w = hit distance z.
- *   These are exactly the buffers ptr_render and ptr_render_aovs return.  Albedo and normal are taken to be finite.
+ *   These are exactly the buffers ptr_render and ptr_render_aovs return (ptr_abi.h, the rule at ptr_render_aovs: with PTR_METAL_PBR the
+ *   albedo is the textured base colour, the normal the mapped one, and a cut-out shows what is seen through it).  Albedo and normal are
+ *   taken to be finite.
  *   A pixel is a HIT pixel when albedo.w > 0.5, z > 0 and its three colour channels are finite; every other pixel is a MISS pixel.
  *   (So a pixel with a non-finite colour is a miss pixel: as a tap it has weight 0, as a centre it is copied through.)
  *

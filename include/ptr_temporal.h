@@ -10,12 +10,14 @@
  *
  * ---- The records (k_surface) -----------------------------------------------------------------------------------------------------------
  *
- * One camera ray per pixel: that of sample 0 of `settings`, the ray the path tracer's sample 0 and ptr_render_aovs(sample_index 0) start
- * with.  Per pixel three float4 records:
+ * One surface per pixel: the one ptr_render_aovs(sample_index 0) reports under `settings` (ptr_abi.h: the rule at ptr_render_aovs) - the
+ * closest hit of the camera ray of sample 0, or with PTR_METAL_PBR on a textured scene the first surface along it the alpha test keeps.
+ * "The ray", origin, direction, (u, v) and P below are those of the segment that ends on that surface; t is the rule's distance, the sum
+ * of the segments' hit distances.  Per pixel three float4 records:
  *   R0 = (X.xyz, bits(id))          R1 = (n.xyz, t)          R2 = (Xprev.xyz, bits(hit word))
  *   hit word  the traversal's word for the primitive: 0xFFFFFFFF on a miss, else the leaf-order index (bit 31 set for a sphere)
  *   id        primType << 30 | index: the mesh index (primType 0), the sphere index (1) or the rectangle index (2), as at upload; 0 on a miss
- *   n, t      the unit normal ptr_render_aovs encodes (before n * 0.5 + 0.5) and the hit distance; n = 0 and t = 0 on a miss
+ *   n, t      the unit normal ptr_render_aovs encodes (before n * 0.5 + 0.5) and its distance (normal.w); n = 0 and t = 0 on a miss
  *   X         the hit point interpolated from the rows the renderer traces, NOT origin + t * direction:
  *               triangle (of a mesh or of a rectangle) with leaf-order rows a0 = v0, a1 = v0 - v1, a2 = v2 - v0 and the traversal's own
  *               barycentrics (u, v):   X = (a0 - u a1) + v a2
@@ -25,7 +27,7 @@
  *               (p0 - u p1) + v p2     and     c' + (P - c) * (r' / r0)
  *             Without a snapshot (the first step, after a reset, and always for a scene that is not dynamic) the snapshot rows ARE the
  *             current rows.  When nothing moved, X and Xprev come from identical operations on identical values and are bitwise equal.
- * The two AOV buffers, when asked for, are written exactly as ptr_render_aovs(sample_index 0) writes them: same trace, same bits.
+ * The two AOV buffers, when asked for, are written exactly as ptr_render_aovs(sample_index 0) writes them: same surface, same bits.
  *
  * ---- The filter (k_temporal_accumulate) ------------------------------------------------------------------------------------------------
  *

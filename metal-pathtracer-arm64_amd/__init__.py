@@ -1231,7 +1231,8 @@ class DeviceScene:
         return Temporal(h, width, height, self._device, keepalive=self, carries_cov=True)
 
     def render_aovs(self, settings: PtrSettings, sample_index: int = 0) -> Tuple[np.ndarray, np.ndarray]:
-        """First-hit feature buffers: ([H, W, 4] albedo rgb | hit flag, [H, W, 4] encoded normal | distance)."""
+        """First-hit feature buffers: ([H, W, 4] albedo rgb | hit flag, [H, W, 4] encoded normal | distance) of the first surface the
+        path of sample `sample_index` shades under settings.metalSemantics (include/ptr_abi.h: the rule at ptr_render_aovs)."""
         albedo = np.zeros((settings.height, settings.width, 4), dtype=np.float32)
         normal = np.zeros((settings.height, settings.width, 4), dtype=np.float32)
         err = _err_buf()

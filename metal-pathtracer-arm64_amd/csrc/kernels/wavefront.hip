@@ -2323,11 +2323,83 @@ __global__ void __launch_bounds__(256) k_background(RenderParams rp, SceneView s
 }
 
 // =====================================================================================================
-// k_aovs: first-hit feature buffers (what the reference hands to its denoiser: shaders/pathtrace.metal:6424-6435 sets
-// albedo = material base colour and normal = shading normal at the first hit; 9813-9815 writes albedo and
-// normal*0.5+0.5 per pixel).  One camera ray per pixel, the one sample `sample` of the path tracer starts with.
-// albedo.w = 1 on a hit, 0 on a miss; normal.w = hit distance (0 on a miss).
+// The surface the first-hit feature buffers describe (include/ptr_abi.h, ptr_render_aovs: the rule): vertex 0 of the path of sample
+// `sample` as shadeSlot sees it.  Shared by k_aovs and k_surface.
 // =====================================================================================================
+struct ReportedSurface {
+    uint32_t prim;   // the hit word of the reported surface; kHitMiss: the path met nothing, or only surfaces its alpha test discards
+    float t;         // the float32 sum, in order, of the hit distances of the segments up to it
+    f3 org, dir;     // the ray of the last segment
+    Surface sf;
+    f3 n;            // unit shading normal
+    f3 base;         // base colour (zero in a scene without materials)
+};
+
+// TEX: settings with PTR_METAL_PBR on a scene with textures and uv rows (launchAovs); every other launch reads no texture state and
+// traces one ray.  The statements are shadeSlot's, through the functions shadeSlot calls.
+template <bool TEX>
+__device__ __forceinline__ void reportedSurface(const RenderParams& rp, const SceneView& sc, uint32_t pixel, uint32_t sample, LaneStack& stack,
+                                                TraceCounters& cnt, ReportedSurface& r) {
+    uint32_t rng;
+    beginSample(rp, pixel, sample, rng, r.org, r.dir);
+    r.t = 0.0f;
+    r.n = mk3(0.0f);
+    r.base = mk3(0.0f);
+    const float2 cone = primaryCone(rp);   // a surface the path passes through leaves its cone as it is (shadeSlot)
+    for (uint32_t depth = 0u;; ++depth) {
+        const TraceHit h = traverse<false, false>(sc, r.org, r.dir, kEps, INFINITY, stack, cnt);
+        r.prim = h.prim;
+        if (h.prim == kHitMiss) return;
+        r.t = depth == 0u ? h.t : r.t + h.t;
+        r.sf = reconstruct(sc, r.org, r.dir, h.t, h.prim);
+        const Surface& sf = r.sf;
+        f3 n = sf.hitShadingNormal;
+        if (dot(n, n) <= 0.0f) n = sf.normal;
+        if (sc.materialCount == 0u) {
+            r.n = normalize(n);
+            return;
+        }
+        const uint32_t materialIndex = min(sf.material, sc.materialCount - 1u);
+        const Mat mat{byteOffset(sc.materials, materialIndex * (kMaterialVec4 * 16u))};
+        const uint32_t type = mat.type();
+        if (type == 2u) {   // dielectrics shade with the geometric normal
+            n = sf.normal;
+            if ((rp.mediaMode & PTR_METAL_FACE_NORMAL) && !sf.frontFace) n = -n;
+        }
+        r.n = normalize(n);
+        r.base = mat.baseColor();
+        if (!TEX) return;
+        if (!(type == 7u && sf.primType == 0u)) return;
+        PbrHit pbrHit;
+        const f3 wo = -normalize(r.dir);
+        bool passThrough;
+        if ((rp.mediaMode & PTR_METAL_RAY_DIFF) && depth == 0u) {
+            passThrough = applyPbrTextures<true>(sc, sf, materialIndex, mat, wo, cone, h.t, firstHitUvGrads(rp, sc, sf, r.dir, h.t), rng, pbrHit);
+        } else {
+            passThrough = applyPbrTextures<false>(sc, sf, materialIndex, mat, wo, cone, h.t, noUvGrads(), rng, pbrHit);
+        }
+        if (!passThrough) {
+            Mat hitMat = mat;
+            hitMat.o = pbrHit.ov;
+            r.base = hitMat.baseColor();
+            r.n = pbrHit.shadingNormal;
+            return;
+        }
+        if (depth + 1u >= rp.maxDepth) {   // the path ends here without a surface of its own
+            r.prim = kHitMiss;
+            return;
+        }
+        r.org = offsetOrigin(sf, r.dir);
+    }
+}
+
+// =====================================================================================================
+// k_aovs: first-hit feature buffers (what the reference hands to its denoiser: shaders/pathtrace.metal:6424-6435 sets
+// albedo = material base colour and normal = shading normal at the first hit the alpha test keeps; 9813-9815 writes albedo and
+// normal*0.5+0.5 per pixel).  Per pixel the reported surface of sample `sample` (reportedSurface).
+// albedo.w = 1 on a hit, 0 on a miss; normal.w = distance (0 on a miss).
+// =====================================================================================================
+template <bool TEX>
 __global__ void __launch_bounds__(kTraceBlock) k_aovs(RenderParams rp, SceneView sc, uint32_t sample, float4* albedo, float4* normal, uint32_t* spill,
                                                        uint32_t spillStride) {
     __shared__ uint32_t ldsStack[kLdsStackLevels * kTraceBlock];
@@ -2336,20 +2408,12 @@ __global__ void __launch_bounds__(kTraceBlock) k_aovs(RenderParams rp, SceneView
     TraceCounters cnt{0u, 0u};
     const uint32_t pixels = rp.width * rp.height;
     for (uint32_t pixel = gtid; pixel < pixels; pixel += gridDim.x * kTraceBlock) {
-        uint32_t rng;
-        f3 org, dir;
-        beginSample(rp, pixel, sample, rng, org, dir);
-        const TraceHit h = traverse<false, false>(sc, org, dir, kEps, INFINITY, stack, cnt);
+        ReportedSurface r;
+        reportedSurface<TEX>(rp, sc, pixel, sample, stack, cnt, r);
         float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n = make_float4(0.5f, 0.5f, 0.5f, 0.0f);
-        if (h.prim != kHitMiss && sc.materialCount > 0u) {
-            const Surface sf = reconstruct(sc, org, dir, h.t, h.prim);
-            const Mat mat{sc.materials + static_cast<size_t>(min(sf.material, sc.materialCount - 1u)) * kMaterialVec4};
-            f3 sn = sf.hitShadingNormal;
-            if (dot(sn, sn) <= 0.0f) sn = sf.normal;
-            if (mat.type() == 2u) sn = sf.normal;
-            sn = normalize(sn);
-            a = mk4(mat.baseColor(), 1.0f);
-            n = mk4(sn * 0.5f + mk3(0.5f), h.t);
+        if (r.prim != kHitMiss && sc.materialCount > 0u) {
+            a = mk4(r.base, 1.0f);
+            n = mk4(r.n * 0.5f + mk3(0.5f), r.t);
         }
         albedo[pixel] = a;
         normal[pixel] = n;
@@ -2357,13 +2421,14 @@ __global__ void __launch_bounds__(kTraceBlock) k_aovs(RenderParams rp, SceneView
 }
 
 // =====================================================================================================
-// k_surface: the per-pixel surface records of a temporal step (include/ptr_temporal.h, where every field is defined).  The camera ray
-// of sample 0 - k_aovs' trace, and its two buffers with the same bits when asked for - and three records per pixel:
-//   R0 = (X, bits(id))   R1 = (unit normal of k_aovs' rule, t)   R2 = (Xprev, bits(hit word))
+// k_surface: the per-pixel surface records of a temporal step (include/ptr_temporal.h, where every field is defined).  The reported
+// surface of sample 0 - k_aovs' rule, and its two buffers with the same bits when asked for - and three records per pixel:
+//   R0 = (X, bits(id))   R1 = (unit normal of k_aovs' rule, distance)   R2 = (Xprev, bits(hit word))
 // X is the hit point interpolated from the rows the traversal tested, Xprev the same expression with the same barycentrics (or the same
 // sphere point) on prevTris / prevSpheres, the rows of the previous step's pose in the same leaf order.  Where the two sets of rows hold
 // the same values - nothing moved, or the caller passes sc.tris / sc.spheres themselves - X and Xprev are the same bits.
 // =====================================================================================================
+template <bool TEX>
 __global__ void __launch_bounds__(kTraceBlock) k_surface(RenderParams rp, SceneView sc, const float4* prevTris, const float4* prevSpheres, float4* r0,
                                                           float4* r1, float4* r2, float4* albedo, float4* normal, uint32_t* spill,
                                                           uint32_t spillStride) {
@@ -2373,45 +2438,38 @@ __global__ void __launch_bounds__(kTraceBlock) k_surface(RenderParams rp, SceneV
     TraceCounters cnt{0u, 0u};
     const uint32_t pixels = rp.width * rp.height;
     for (uint32_t pixel = gtid; pixel < pixels; pixel += gridDim.x * kTraceBlock) {
-        uint32_t rng;
-        f3 org, dir;
-        beginSample(rp, pixel, 0u, rng, org, dir);
-        const TraceHit h = traverse<false, false>(sc, org, dir, kEps, INFINITY, stack, cnt);
+        ReportedSurface r;
+        reportedSurface<TEX>(rp, sc, pixel, 0u, stack, cnt, r);
         float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n = make_float4(0.5f, 0.5f, 0.5f, 0.0f);
         float4 q0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), q1 = q0, q2 = mk4(mk3(0.0f), __uint_as_float(kHitMiss));
-        if (h.prim != kHitMiss) {
-            const Surface sf = reconstruct(sc, org, dir, h.t, h.prim);
-            f3 sn = sf.hitShadingNormal;
-            if (dot(sn, sn) <= 0.0f) sn = sf.normal;
+        if (r.prim != kHitMiss) {
+            const Surface& sf = r.sf;
             if (sc.materialCount > 0u) {
-                const Mat mat{sc.materials + static_cast<size_t>(min(sf.material, sc.materialCount - 1u)) * kMaterialVec4};
-                if (mat.type() == 2u) sn = sf.normal;
-                a = mk4(mat.baseColor(), 1.0f);
+                a = mk4(r.base, 1.0f);
+                n = mk4(r.n * 0.5f + mk3(0.5f), r.t);
             }
-            sn = normalize(sn);
-            if (sc.materialCount > 0u) n = mk4(sn * 0.5f + mk3(0.5f), h.t);
             f3 x, xPrev;
-            if (h.prim & kHitSphereBit) {
-                const uint32_t idx = h.prim & ~kHitSphereBit;
+            if (r.prim & kHitSphereBit) {
+                const uint32_t idx = r.prim & ~kHitSphereBit;
                 const float4 s = sc.spheres[idx], p = prevSpheres[idx];
                 const f3 fromCentre = sf.position - mk3(s);
                 x = mk3(s) + fromCentre * (s.w / s.w);
                 xPrev = mk3(p) + fromCentre * (p.w / s.w);
             } else {
-                const uint32_t triOffset = h.prim * 48u;
+                const uint32_t triOffset = r.prim * 48u;
                 const float4* tp = byteOffset(sc.tris, triOffset);
                 const float4* pp = byteOffset(prevTris, triOffset);
                 const float4 a0 = tp[0], a1 = tp[1], a2 = tp[2];
                 const float4 p0 = pp[0], p1 = pp[1], p2 = pp[2];
                 float u, v;
-                triangleUv(mk3(a0), mk3(a1), mk3(a2), org, dir, u, v);
+                triangleUv(mk3(a0), mk3(a1), mk3(a2), r.org, r.dir, u, v);
                 x = (mk3(a0) - u * mk3(a1)) + v * mk3(a2);
                 xPrev = (mk3(p0) - u * mk3(p1)) + v * mk3(p2);
             }
             const uint32_t index = sf.primType == 0u ? sf.geomIndex : sf.primIndex;
             q0 = mk4(x, __uint_as_float(sf.primType << 30 | index));
-            q1 = mk4(sn, h.t);
-            q2 = mk4(xPrev, __uint_as_float(h.prim));
+            q1 = mk4(r.n, r.t);
+            q2 = mk4(xPrev, __uint_as_float(r.prim));
         }
         r0[pixel] = q0;
         r1[pixel] = q1;
@@ -3259,17 +3317,27 @@ void launchTraceRays(const SceneView& sc, const float4* dRays, uint64_t n, bool 
     }, anyHit);
 }
 
+// The instantiation of k_aovs / k_surface that reads textures: where shadeSlot textures a hit (its condition on the settings and the scene)
+static bool texturedFirstHits(const RenderParams& rp, const SceneView& sc) {
+    return (rp.mediaMode & PTR_METAL_PBR) && sc.textureCount > 0u && sc.triUv != nullptr;
+}
+
 void launchAovs(const RenderParams& rp, const SceneView& sc, uint32_t sample, float4* dAlbedo, float4* dNormal, const LaunchConfig& cfgIn,
                 hipStream_t stream) {
     const TraceLaunch t = traceLaunch(cfgIn, rp.width * rp.height);
-    hipLaunchKernelGGL(k_aovs, dim3(t.grid), dim3(kTraceBlock), 0, stream, rp, sc, sample, dAlbedo, dNormal, t.cfg.spill, t.stride);
+    withBools([&](auto texTag) {
+        hipLaunchKernelGGL(k_aovs<decltype(texTag)::value>, dim3(t.grid), dim3(kTraceBlock), 0, stream, rp, sc, sample, dAlbedo, dNormal, t.cfg.spill,
+                           t.stride);
+    }, texturedFirstHits(rp, sc));
 }
 
 void launchSurface(const RenderParams& rp, const SceneView& sc, const float4* dPrevTris, const float4* dPrevSpheres, float4* dR0, float4* dR1,
                    float4* dR2, float4* dAlbedo, float4* dNormal, const LaunchConfig& cfgIn, hipStream_t stream) {
     const TraceLaunch t = traceLaunch(cfgIn, rp.width * rp.height);
-    hipLaunchKernelGGL(k_surface, dim3(t.grid), dim3(kTraceBlock), 0, stream, rp, sc, dPrevTris, dPrevSpheres, dR0, dR1, dR2, dAlbedo, dNormal,
-                       t.cfg.spill, t.stride);
+    withBools([&](auto texTag) {
+        hipLaunchKernelGGL(k_surface<decltype(texTag)::value>, dim3(t.grid), dim3(kTraceBlock), 0, stream, rp, sc, dPrevTris, dPrevSpheres, dR0, dR1,
+                           dR2, dAlbedo, dNormal, t.cfg.spill, t.stride);
+    }, texturedFirstHits(rp, sc));
 }
 
 // ---- tests only: the probes ----

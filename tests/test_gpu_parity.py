@@ -528,6 +528,14 @@ def test_first_hit_aovs(materials_scene):
     table = np.array([list(d.materials[i].baseColorRoughness)[:3] for i in range(d.materialCount)], np.float32).clip(0, 1)
     dist = np.abs(albedo[..., :3][hit][:, None, :] - table[None]).max(axis=2).min(axis=1)
     assert dist.max() < 1e-6
+    # ... and pixel by pixel the one of the material the oracle's hit names, with the normal of the rule (tests/aov_ref.py; every
+    # frame size, sample, lens and scene of the rule: tests/test_gpu_aovs.py)
+    import aov_ref
+
+    surface = osc.surface_hits(np.concatenate([rays, rays[:, 3:]], axis=1))
+    ref64, ref32 = (aov_ref.first_hit_features(d, hits, surface, 0, dtype) for dtype in (np.float64, np.float32))
+    assert np.array_equal(albedo[..., :3].reshape(-1, 3), ref64["albedo"])
+    assert np.abs(normal[..., :3].reshape(-1, 3) - ref64["normal"]).max() <= aov_ref.normal_tolerance(ref64, ref32)
 
 
 def test_gradient_sky_and_thin_lens(materials_scene):
