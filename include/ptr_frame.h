@@ -6,7 +6,8 @@
  * rendering the first samples again.  Sample s of pixel p is a pure function of (seed, p, s) and the update of ptr_adaptive.h folds
  * samples in sample order, so a frame continued in any number of calls is BIT FOR BIT the frame rendered in one call.
  * Kernels: csrc/kernels/frame.hip (k_frame_class_min, k_frame_split, k_frame_merge; bodies in frame.h) and those of adaptive.hip.
- * Host: csrc/host/frame.cpp.  Restatement in numpy (the tests' reference): tests/frame_ref.py.
+ * Host: csrc/host/frame.cpp, with the round loop of csrc/host/frame_rounds.cpp and the count classes of csrc/host/frame_classes.h, which
+ * the frame on several devices (ptr_multi_frame.h) shares.  Restatement in numpy (the tests' reference): tests/frame_ref.py.
  *
  * Scope: one device, the whole image, the non-counting build of the kernels.
  *

@@ -3,8 +3,9 @@
  * 16-spp preview goes on to 256 spp, a threshold is tightened, a render is checkpointed and continued on another number of devices,
  * without rendering the first samples again and without uploading the scene again.
  * Kernels: those of ptr_frame.h, ptr_adaptive.h and ptr_multi.h, and csrc/kernels/multi.hip's k_multi_state_pack / k_multi_state_unpack
- * (bodies in csrc/kernels/multi.h).  Host: csrc/host/multi_frame.cpp, with the exchange of multi.cpp (csrc/host/multi_host.h) and
- * csrc/host/round_barrier.h.  Restatement in numpy (the tests' reference): tests/multi_frame_ref.py.
+ * (bodies in csrc/kernels/multi.h).  Host: csrc/host/multi_frame.cpp, with ptr_frame.h's round loop and count classes
+ * (csrc/host/frame_rounds.cpp, csrc/host/frame_classes.h), the exchange, the gather and the partition threads of multi.cpp
+ * (csrc/host/multi_host.h) and csrc/host/round_barrier.h.  Restatement in numpy (the tests' reference): tests/multi_frame_ref.py.
  *
  * Scope: the devices of one process, the non-counting build of the kernels; the bands of a partition are fixed for the frame's life.
  *

@@ -1,7 +1,7 @@
 // Host side of include/ptr_adaptive.h: the argument checks, the loop over the rounds of an adaptive frame (every round an ordinary pass
 // of the wavefront kernels over the active list, then update -> select -> compact), and the test-only probe of one round.  Also what
-// adaptive_host.h and adaptive_state.h declare for all three round loops (this one, multi.cpp's and frame.cpp's): the owner of the
-// per-pixel state, the sample sources, the sample step and the finish into staging.
+// adaptive_host.h and adaptive_state.h declare for all three round loops (this one, multi.cpp's and the resumable frames' in
+// frame_rounds.cpp): the owner of the per-pixel state, the sample sources, the sample step and the finish into staging.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>

@@ -1,10 +1,10 @@
 // What the three adaptive round loops share on the host - the frame of one device (adaptive.cpp, include/ptr_adaptive.h), the lock-step
-// frame on several devices (multi.cpp, include/ptr_multi.h) and the resumable frame (frame.cpp, include/ptr_frame.h; on several devices
-// multi_frame.cpp, include/ptr_multi_frame.h, which runs frame.cpp's loop in lock step and adds none of its own): the parameter check,
-// the rules by which a frame is cut into rounds and a round into sub-passes, the sample source of a pass, the sample step of a round,
-// the device events of PTR_VERBOSE=launches, and the finish into staging with its downloads.  The owner of the per-pixel state is
-// AdaptiveStore (adaptive_state.h, through device_scene.h); the refusals are beside deviceCall in device_scene.h.  Each loop keeps what is
-// its own: its barriers, its classes, its halo.  Implemented in adaptive.cpp.  Internal: not part of the C-ABI.
+// frame on several devices (multi.cpp, include/ptr_multi.h) and the resumable frame (frame_rounds.cpp, which frame.cpp,
+// include/ptr_frame.h, calls for its one partition and multi_frame.cpp, include/ptr_multi_frame.h, for each of several in lock step):
+// the parameter check, the rules by which a frame is cut into rounds and a round into sub-passes, the sample source of a pass, the
+// sample step of a round, the device events of PTR_VERBOSE=launches, and the finish into staging with its downloads.  The owner of the
+// per-pixel state is AdaptiveStore (adaptive_state.h, through device_scene.h); the refusals are beside deviceCall in device_scene.h.
+// Each loop keeps what is its own: its barriers, its classes, its halo.  Implemented in adaptive.cpp.  Internal: not part of the C-ABI.
 #pragma once
 
 #include <algorithm>
@@ -62,9 +62,9 @@ using SubPassHook = std::function<void(uint32_t done, uint32_t spp, bool last)>;
 void addSamples(const SampleStep& step, const uint32_t* list, uint32_t count, uint32_t nBefore, uint32_t spp, const SubPassHook& inPass = nullptr,
                 const SubPassHook& afterPass = nullptr);
 
-// Up to four device events, created on demand (PTR_VERBOSE=launches) and destroyed with the set.
+// Up to ten device events (the pairs frame_rounds.h names), created on demand (PTR_VERBOSE=launches) and destroyed with the set.
 struct EventSet {
-    hipEvent_t e[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t e[10] = {};
     EventSet() = default;
     EventSet(const EventSet&) = delete;
     EventSet& operator=(const EventSet&) = delete;

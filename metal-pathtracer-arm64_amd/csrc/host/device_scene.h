@@ -303,6 +303,10 @@ using IterationHook = std::function<void(uint64_t, const ptrk::PathPool&)>;
 void traceItems(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t spp, uint32_t sampleBase, const uint32_t* dPixelOfLocal,
                 uint32_t localPixels, hipStream_t stream, PtrRenderStats* stats, const std::function<void(const float4*)>& consume,
                 int mode = 0, const IterationHook* hook = nullptr);
+// The first-hit feature buffers of sample `sample` of the whole image, through the two device buffers (grown on demand) into the host
+// arrays that are not null.  The scene's device is current; blocking.
+void downloadFirstHit(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t sample, DeviceBuffer<float4>& albedo, DeviceBuffer<float4>& normal,
+                      float* outAlbedo, float* outNormal);
 // the local-pixel order of a one-partition frame (8-row bands, 8x8 blocks)
 void imagePixelOrder(uint32_t width, uint32_t height, std::vector<uint32_t>& out);
 // adds the times, launches and samples of pass `one` to `sum`

@@ -1,19 +1,19 @@
 // Host side of include/ptr_frame.h: the frame object (the per-pixel state of an adaptive frame, owned by the frame and kept on the device
-// between calls), the argument checks, accumulate, the loop of refine (class minimum -> split -> an ordinary pass of the wavefront kernels
-// over S -> update -> select on S and merge), resolve, the checkpoint, and the test-only frame whose accumulators are gathered from
-// given samples instead of being traced.  The state's buffers, the sample sources and the sample step are the ones adaptive.cpp and
-// multi.cpp use (adaptive_host.h); the frame's own are the first list, S, and the count classes it keeps on the host.
+// between calls), the argument checks, accumulate, refine, resolve, the checkpoint, and the test-only frame, whose samples are given.
+// A frame is the one-partition case of the frame on several devices: on the device it keeps one FramePart, and refine is the round loop
+// of frame_rounds.h on the calling thread and the caller's stream, with no thread, no barrier and no exchange.  The count classes and
+// their refusals are frame_classes.h's; the state's buffers, the sample sources and the sample step adaptive_host.h's.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <memory>
 #include <string>
 #include <vector>
 
-#include "../kernels/frame.h"
 #include "adaptive_host.h"
 #include "device_scene.h"
+#include "frame_classes.h"
+#include "frame_rounds.h"
 #include "knobs.h"
 #include "ptr_frame.h"
 
@@ -21,67 +21,43 @@ using namespace ptrhost;
 using namespace ptrk;
 
 struct PtrFrame {
-    PtrDeviceScene* scene = nullptr;   // null: the test-only frame
     int device = 0;
     PtrSettings settings{};
     size_t pixels = 0;
-    AdaptiveStore store;   // the state, image order; L's two buffers; the compaction's scratch and the word the class minimum arrives in
-    DeviceBuffer<uint32_t> order, listS;   // the first list; S
-    DeviceBuffer<uint8_t> inS;             // the flag "in S" per entry of L
+    FramePart part;            // the whole image
     DeviceBuffer<float> out;   // ptr_frame_resolve: rgb, cov and count before they go to the host
-    // the test-only frame: the samples it was given, and the accumulators of a pass gathered from them
-    DeviceBuffer<float4> probeSamples, probeItems;
-    uint32_t sampleCount = 0;
-    // pixels per count n_p, kept on the host: a round moves |S| pixels from n_min to n_min + k, so the checks and ptr_frame_info need
-    // no device call
-    std::map<uint32_t, uint64_t> classes;
-
-    bool uniform() const { return classes.size() == 1u; }
-    uint32_t minCount() const { return classes.begin()->first; }
-    uint32_t maxCount() const { return classes.rbegin()->first; }
+    uint32_t sampleCount = 0;  // the test-only frame: the samples it was given; 0 with a scene
+    CountClasses classes;
 };
 
 namespace {
 
-// what the sample steps of one call on the frame share; `sum` (nullable) collects the stats
-SampleStep sampleStep(PtrFrame& f, hipStream_t stream, PtrRenderStats* sum) {
-    return SampleStep{f.scene ? tracedSource(*f.scene, f.settings, stream) : gatheredSource(f.probeSamples.ptr, f.pixels, f.sampleCount, f.probeItems, stream),
-                      maxPassItems(f.scene), f.store.state(), stream, sum};
-}
-
 void zeroState(PtrFrame& f, hipStream_t stream) {
-    f.store.zero(stream);
+    f.part.store.zero(stream);
     HIP_CHECK(hipStreamSynchronize(stream));
-    f.classes.clear();
-    f.classes[0u] = f.pixels;
+    f.classes.reset(f.pixels);
 }
 
 // the buffers of a new frame and its empty state; `device` is current
 void allocate(PtrFrame& f) {
-    f.store.ensure(f.pixels);
-    f.listS.ensure(f.pixels);
-    f.inS.ensure(f.pixels);
+    FramePart& me = f.part;
+    me.mp = MultiPart{0u, 1u, ptr_part_band_count(f.settings.height, 0u, 1u), f.settings.width, f.settings.height};
+    me.local = static_cast<uint32_t>(f.pixels);
+    me.store.ensure(f.pixels);
+    me.listS.ensure(f.pixels);
+    me.inS.ensure(f.pixels);
     std::vector<uint32_t> order;
     imagePixelOrder(f.settings.width, f.settings.height, order);
-    f.order.upload(order.data(), f.pixels);
+    me.order.upload(order.data(), f.pixels);
     zeroState(f, nullptr);
-}
-
-// The samples of one class: `list` (count entries, all at nBefore samples) gets spp more, and its pixels move to the new count.
-void addClassSamples(PtrFrame& f, const SampleStep& step, const uint32_t* list, uint32_t count, uint32_t nBefore, uint32_t spp) {
-    addSamples(step, list, count, nBefore, spp);
-    auto it = f.classes.find(nBefore);
-    if (it != f.classes.end()) {   // (always, unless an import brought counts that disagree with themselves)
-        it->second -= std::min<uint64_t>(it->second, count);
-        if (it->second == 0u) f.classes.erase(it);
-    }
-    f.classes[nBefore + spp] += count;
 }
 
 void accumulate(PtrFrame& f, uint32_t spp, hipStream_t stream, PtrRenderStats* stats) {
     HIP_CHECK(hipSetDevice(f.device));
     PtrRenderStats sum{};
-    addClassSamples(f, sampleStep(f, stream, stats ? &sum : nullptr), f.order.ptr, static_cast<uint32_t>(f.pixels), f.minCount(), spp);
+    const uint32_t n = f.classes.minCount();
+    addSamples(sampleStep(f.part, f.settings, f.sampleCount, stream, stats ? &sum : nullptr), f.part.order.ptr, f.part.local, n, spp);
+    f.classes.move(n, n + spp, f.pixels);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(stream));
     if (stats) {
@@ -93,93 +69,35 @@ void accumulate(PtrFrame& f, uint32_t spp, hipStream_t stream, PtrRenderStats* s
 
 void refine(PtrFrame& f, const PtrAdaptiveParams& params, hipStream_t stream, PtrRenderStats* stats, PtrAdaptiveInfo* info) {
     HIP_CHECK(hipSetDevice(f.device));
-    const uint32_t width = f.settings.width, height = f.settings.height, pixels = static_cast<uint32_t>(f.pixels);
-    const AdaptiveScratch scratch = f.store.scratch();
-    PtrAdaptiveInfo local{};
     PtrRenderStats sum{};
-    const SampleStep step = sampleStep(f, stream, stats ? &sum : nullptr);
-    const AdaptiveState& st = step.state;
-    auto note = [&](uint32_t active) {
-        if (local.rounds < PTR_ADAPTIVE_INFO_ROUNDS) local.activeAfter[local.rounds] = active;
-        ++local.rounds;
-    };
-    // the length of the list a select or a merge just wrote, and (with `min`) the class minimum beside it
-    auto readWords = [&](uint32_t* total, uint32_t* min) {
-        uint32_t words[2] = {0u, 0u};
-        HIP_CHECK(hipMemcpyAsync(words, scratch.total, (min ? 2u : 1u) * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-        HIP_CHECK(hipStreamSynchronize(stream));
-        *total = words[0];
-        if (min) *min = words[1];
-    };
-
-    const bool empty = f.uniform() && f.minCount() == 0u;
-    uint32_t deepest = 0u;   // the most samples this call gave one pixel
-    if (empty) {
-        addClassSamples(f, step, f.order.ptr, pixels, 0u, params.minSpp);
-        local.totalSamples += static_cast<uint64_t>(pixels) * params.minSpp;
-        deepest = params.minSpp;
-    }
-    // the start list, and with it the class minimum of the first round
-    uint32_t turn = 0u, active = 0u, nMin = kFrameNoCount;
-    launchAdaptiveSelect(f.order.ptr, pixels, width, height, st, params.maxSpp, params.threshold, scratch, f.store.list(0u), stream);
-    HIP_CHECK(hipGetLastError());
-    readWords(&active, nullptr);
-    if (empty) note(active);
-
+    RefineCall call("ptr_frame_refine", params, 1u, f.classes.empty(), nullptr);
     // PTR_VERBOSE=launches: device events around the kernels between the rounds (tools/frame_cost.py parses the line)
     EventSet marks;
-    const bool timed = ptr::readKnobs().verboseLaunches;
-    if (timed) marks.create(4u);
-    while (active > 0u) {
-        const uint32_t* list = f.store.list(turn);
-        // n_min, then S
-        if (timed) HIP_CHECK(hipEventRecord(marks[0], stream));
-        HIP_CHECK(hipMemsetAsync(f.store.minWord(), 0xFF, sizeof(uint32_t), stream));   // kFrameNoCount
-        launchFrameClassMin(list, active, st.n, f.store.minWord(), stream);
-        HIP_CHECK(hipGetLastError());
-        uint32_t ignored = 0u, inClass = 0u;
-        readWords(&ignored, &nMin);
-        if (nMin >= params.maxSpp) throw HipError{"ptr_frame_refine: the active list holds a pixel at maxSpp"};   // (select never keeps one)
-        launchFrameSplit(list, active, st.n, nMin, f.inS.ptr, scratch, f.listS.ptr, stream);
-        if (timed) HIP_CHECK(hipEventRecord(marks[1], stream));
-        HIP_CHECK(hipGetLastError());
-        readWords(&inClass, nullptr);
-        if (inClass == 0u || inClass > active) throw HipError{"ptr_frame_refine: the class of the round is empty"};
-        // its samples
-        const uint32_t k = std::min(params.stepSpp, params.maxSpp - nMin);
-        addClassSamples(f, step, f.listS.ptr, inClass, nMin, k);
-        local.totalSamples += static_cast<uint64_t>(inClass) * k;
-        deepest = std::max(deepest, k);
-        // select on S, merged into the next L
-        if (timed) HIP_CHECK(hipEventRecord(marks[2], stream));
-        launchFrameMerge(list, active, f.inS.ptr, width, height, st, params.maxSpp, params.threshold, scratch, f.store.list(turn ^ 1u), stream);
-        if (timed) HIP_CHECK(hipEventRecord(marks[3], stream));
-        HIP_CHECK(hipGetLastError());
-        const uint32_t before = active;
-        readWords(&active, nullptr);
-        if (timed) {   // debugging aid, like the [adaptive] lines of ptr_render_adaptive
-            float splitMs = 0.0f, mergeMs = 0.0f;
-            HIP_CHECK(hipEventElapsedTime(&splitMs, marks[0], marks[1]));
-            HIP_CHECK(hipEventElapsedTime(&mergeMs, marks[2], marks[3]));
-            std::fprintf(stderr, "[frame] round %u: class %u, %u of %u active x %u spp; minimum + split %.4f ms, select + merge %.4f ms\n", local.rounds,
-                         nMin, inClass, before, k, splitMs, mergeMs);
-        }
-        note(active);
-        turn ^= 1u;
-    }
-    const auto atMax = f.classes.find(params.maxSpp);
-    local.pixelsAtMax = atMax == f.classes.end() ? 0u : static_cast<uint32_t>(atMax->second);
+    if (ptr::readKnobs().verboseLaunches) marks.create(kRoundMarks);
+    auto report = [&](const RoundReport& r) {   // debugging aid, like the [adaptive] lines of ptr_render_adaptive
+        if (!marks[0]) return;
+        float minMs = 0.0f, splitMs = 0.0f, mergeMs = 0.0f;
+        HIP_CHECK(hipEventElapsedTime(&minMs, marks[kMarkMinimum], marks[kMarkMinimum + 1]));
+        HIP_CHECK(hipEventElapsedTime(&splitMs, marks[kMarkSplit], marks[kMarkSplit + 1]));
+        HIP_CHECK(hipEventElapsedTime(&mergeMs, marks[kMarkMerge], marks[kMarkMerge + 1]));
+        std::fprintf(stderr, "[frame] round %u: class %u, %u of %u active x %u spp; minimum + split %.4f ms, select + merge %.4f ms\n",
+                     r.round + (call.empty ? 1u : 0u), r.nMin, r.inClass, r.activeBefore, r.spp, minMs + splitMs, mergeMs);
+    };
+    const SampleStep step = sampleStep(f.part, f.settings, f.sampleCount, stream, stats ? &sum : nullptr);
+    refinePartition(call, 0u, f.part, nullptr, step, [] { return true; }, marks, report);
+    for (const ClassMove& mv : call.moves) f.classes.move(mv.from, mv.to, mv.pixels);
+    call.info.pixelsAtMax = static_cast<uint32_t>(f.classes.pixelsAt(params.maxSpp));
     if (stats) {
-        sum.samples = local.totalSamples;
-        sum.avgMsPerSample = sum.totalSeconds * 1000.0 / std::max(1u, deepest);
+        sum.samples = call.info.totalSamples;
+        sum.avgMsPerSample = sum.totalSeconds * 1000.0 / std::max(1u, call.deepest);
         *stats = sum;
     }
-    if (info) *info = local;
+    if (info) *info = call.info;
 }
 
 void resolveDevice(PtrFrame& f, float* dRgb, float* dCov, uint32_t* dCount, hipStream_t stream) {
     HIP_CHECK(hipSetDevice(f.device));
-    launchAdaptiveFinish(f.store.state(), static_cast<uint32_t>(f.pixels), dRgb, dCov, dCount, stream);
+    launchAdaptiveFinish(f.part.store.state(), static_cast<uint32_t>(f.pixels), dRgb, dCov, dCount, stream);
     HIP_CHECK(hipGetLastError());
     HIP_CHECK(hipStreamSynchronize(stream));
 }
@@ -203,7 +121,7 @@ int ptr_frame_create(PtrDeviceScene* scene, const PtrSettings* settings, PtrFram
     try {
         HIP_CHECK(hipSetDevice(scene->device));
         auto f = std::make_unique<PtrFrame>();
-        f->scene = scene;
+        f->part.scene = scene;
         f->device = scene->device;
         f->settings = *settings;
         f->pixels = static_cast<size_t>(settings->width) * settings->height;
@@ -238,7 +156,7 @@ int ptr_frame_debug_create(uint32_t width, uint32_t height, const float* samples
         f->settings.height = height;
         f->pixels = static_cast<size_t>(width) * height;
         f->sampleCount = sample_count;
-        f->probeSamples.upload(reinterpret_cast<const float4*>(samples), f->pixels * sample_count);
+        f->part.probeSamples.upload(reinterpret_cast<const float4*>(samples), f->pixels * sample_count);
         allocate(*f);
         *out_frame = f.release();
         return 0;
@@ -249,9 +167,8 @@ int ptr_frame_debug_create(uint32_t width, uint32_t height, const float* samples
 int ptr_frame_reset(PtrFrame* frame, const PtrSettings* settings, char* err, size_t err_cap) {
     static const char* const who = "ptr_frame_reset";
     if (!frame) return nullArgument(who, err, err_cap);
-    if (settings && (settings->width != frame->settings.width || settings->height != frame->settings.height)) {
-        return refuse(err, err_cap, std::string(who) + ": a frame keeps its width and height for its life");
-    }
+    const std::string bad = badReset(who, frame->settings.width, frame->settings.height, settings);
+    if (!bad.empty()) return refuse(err, err_cap, bad);
     try {
         HIP_CHECK(hipSetDevice(frame->device));
         if (settings) frame->settings = *settings;
@@ -265,14 +182,8 @@ int ptr_frame_accumulate(PtrFrame* frame, uint32_t spp, void* stream, PtrRenderS
     static const char* const who = "ptr_frame_accumulate";
     if (!frame) return nullArgument(who, err, err_cap);
     if (spp == 0u) return refuse(err, err_cap, std::string(who) + ": spp must be >= 1");
-    if (!frame->uniform()) {
-        return refuse(err, err_cap, std::string(who) + ": the frame is not uniform (its pixels hold different sample counts); a refine with threshold 0 "
-                                                       "brings every pixel with a non-zero error up to a common count");
-    }
-    if (static_cast<uint64_t>(frame->minCount()) + spp > 0xFFFFFFF0ull) return refuse(err, err_cap, std::string(who) + ": too many samples");
-    if (!frame->scene && static_cast<uint64_t>(frame->minCount()) + spp > frame->sampleCount) {
-        return refuse(err, err_cap, std::string(who) + ": a sample past the ones the frame was given");
-    }
+    const std::string bad = badAccumulate(who, frame->classes, spp, frame->sampleCount);
+    if (!bad.empty()) return refuse(err, err_cap, bad);
     try {
         accumulate(*frame, spp, static_cast<hipStream_t>(stream), stats);
         return 0;
@@ -284,13 +195,9 @@ int ptr_frame_refine(PtrFrame* frame, const PtrAdaptiveParams* params, void* str
                      size_t err_cap) {
     static const char* const who = "ptr_frame_refine";
     if (!frame || !params) return nullArgument(who, err, err_cap);
-    const std::string bad = badAdaptiveParams(who, *params);
+    std::string bad = badAdaptiveParams(who, *params);
+    if (bad.empty()) bad = badRefine(who, frame->classes, *params, frame->sampleCount);
     if (!bad.empty()) return refuse(err, err_cap, bad);
-    const bool empty = frame->uniform() && frame->minCount() == 0u;
-    if (!empty && frame->minCount() < 2u) {
-        return refuse(err, err_cap, std::string(who) + ": every pixel of a frame that is not empty must hold at least 2 samples");
-    }
-    if (!frame->scene && params->maxSpp > frame->sampleCount) return refuse(err, err_cap, std::string(who) + ": a sample past the ones the frame was given");
     try {
         refine(*frame, *params, static_cast<hipStream_t>(stream), stats, info);
         return 0;
@@ -326,10 +233,7 @@ int ptr_frame_info(const PtrFrame* frame, PtrFrameInfo* out) {
     *out = PtrFrameInfo{};
     out->width = frame->settings.width;
     out->height = frame->settings.height;
-    out->minCount = frame->minCount();
-    out->maxCount = frame->maxCount();
-    for (const auto& c : frame->classes) out->totalSamples += static_cast<uint64_t>(c.first) * c.second;
-    out->uniform = frame->uniform() ? 1u : 0u;
+    frame->classes.fill(*out);
     return 0;
 }
 
@@ -338,7 +242,7 @@ int ptr_frame_export(PtrFrame* frame, float* sum, float* mean, float* m, uint32_
     if (!frame || !sum || !mean || !m || !n || !e) return nullArgument(who, err, err_cap);
     try {
         HIP_CHECK(hipSetDevice(frame->device));
-        frame->store.download(sum, mean, m, n, e);
+        frame->part.store.download(sum, mean, m, n, e);
         return 0;
     }
     PTR_CATCH_ALL(err, err_cap)
@@ -350,9 +254,8 @@ int ptr_frame_import(PtrFrame* frame, const float* sum, const float* mean, const
     if (!frame || !sum || !mean || !m || !n || !e) return nullArgument(who, err, err_cap);
     try {
         HIP_CHECK(hipSetDevice(frame->device));
-        frame->store.upload(sum, mean, m, n, e);
-        frame->classes.clear();
-        for (size_t p = 0; p < frame->pixels; ++p) ++frame->classes[n[p]];
+        frame->part.store.upload(sum, mean, m, n, e);
+        frame->classes.rebuild(n, frame->pixels);
         return 0;
     }
     PTR_CATCH_ALL(err, err_cap)

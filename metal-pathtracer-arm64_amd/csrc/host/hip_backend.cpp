@@ -520,6 +520,20 @@ void fillRenderParams(const PtrSettings& s, uint32_t spp, RenderParams& rp) {
 // Launch configuration of the one-off traversal kernels (ray batches, AOVs, debug queries): whole grid, group 0's heads and spill area
 LaunchConfig coldLaunchConfig(const PtrDeviceScene& ds) { return LaunchConfig{ds.traceGrid, ds.spill.ptr, ds.scalars.ptr + 1, ds.refillBelow}; }
 
+void downloadFirstHit(PtrDeviceScene& ds, const PtrSettings& settings, uint32_t sample, DeviceBuffer<float4>& albedo, DeviceBuffer<float4>& normal,
+                      float* outAlbedo, float* outNormal) {
+    RenderParams rp;
+    fillRenderParams(settings, 1u, rp);
+    const size_t pixels = static_cast<size_t>(settings.width) * settings.height;
+    albedo.ensure(pixels);
+    normal.ensure(pixels);
+    launchAovs(rp, ds.view, sample, albedo.ptr, normal.ptr, coldLaunchConfig(ds), nullptr);
+    HIP_CHECK(hipGetLastError());
+    HIP_CHECK(hipDeviceSynchronize());
+    if (outAlbedo) albedo.download(reinterpret_cast<float4*>(outAlbedo), pixels);
+    if (outNormal) normal.download(reinterpret_cast<float4*>(outNormal), pixels);
+}
+
 // Local pixel order of a partition: its PTR_BAND_ROWS-row bands top to bottom, each walked in 8x8 blocks so the
 // 64 lanes of a wave start with a compact, coherent bundle of primary rays.
 void partitionPixels(uint32_t width, uint32_t height, uint32_t part, uint32_t parts, std::vector<uint32_t>& out) {
@@ -1394,16 +1408,8 @@ int ptr_render_aovs(PtrDeviceScene* scene, const PtrSettings* settings, uint32_t
                     char* err, size_t err_cap) {
     return deviceCall("ptr_render_aovs", scene, scene && settings, err, err_cap, [&] {
         if (settings->width == 0 || settings->height == 0) throw HipError{"render size must be non-zero"};
-        RenderParams rp;
-        fillRenderParams(*settings, 1u, rp);
-        const size_t pixels = static_cast<size_t>(settings->width) * settings->height;
         DeviceBuffer<float4> albedo, normal;
-        albedo.ensure(pixels);
-        normal.ensure(pixels);
-        launchAovs(rp, scene->view, sample_index, albedo.ptr, normal.ptr, coldLaunchConfig(*scene), nullptr);
-        HIP_CHECK(hipDeviceSynchronize());
-        if (out_albedo) albedo.download(reinterpret_cast<float4*>(out_albedo), pixels);
-        if (out_normal) normal.download(reinterpret_cast<float4*>(out_normal), pixels);
+        downloadFirstHit(*scene, *settings, sample_index, albedo, normal, out_albedo, out_normal);
     });
 }
 

@@ -4,12 +4,11 @@
 // rows of e between them, the hand-over of the band-layout buffers to the first device, which interleaves them into the image.  The
 // sample source of a pass is a parameter of the partition loop: the traced one for the renderer, the gathered one for the test-only probe,
 // which therefore runs everything else the renderer runs.  The state's buffers, the sources and the sample step are the ones adaptive.cpp
-// and frame.cpp use (adaptive_host.h); the halo goes out from the step's hook.  The device list of a call, the exchange's pinned memory
-// with its publish and collect halves and the hand-over to the first device are stated once, below, for this driver and for the
-// resumable frame of multi_frame.cpp (multi_host.h).
+// and the resumable frames use (adaptive_host.h); the halo goes out from the step's hook.  The device list of a call, the exchange's
+// pinned memory with its publish and collect halves, the hand-over to the first device and the gather there are stated once, below, for
+// this driver and for the resumable frame of multi_frame.cpp (multi_host.h, which also holds the thread-per-partition driver of both).
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -21,10 +20,8 @@
 #include "device_scene.h"
 #include "knobs.h"
 #include "multi_host.h"
-#include "parallel.h"
 #include "ptr_debug.h"
 #include "ptr_multi.h"
-#include "round_barrier.h"
 
 using namespace ptrhost;
 using namespace ptrk;
@@ -124,12 +121,31 @@ bool sendBandsToRoot(void* dRootDst, int rootDevice, const void* dSrc, int devic
     return true;
 }
 
+void BandGather::allocate(const std::vector<uint32_t>& partBands, uint32_t imageWidth, uint32_t imageHeight, uint32_t covAt, uint32_t countAt, uint32_t words) {
+    parts = static_cast<uint32_t>(partBands.size()), width = imageWidth, height = imageHeight, pixelWords = words;
+    partPixel.assign(parts + 1u, 0u);
+    wordOffset.assign(static_cast<size_t>(parts) * 3u, 0u);
+    for (uint32_t p = 0; p < parts; ++p) {
+        const uint64_t start = partPixel[p] * pixelWords, mine = static_cast<uint64_t>(partBands[p]) * PTR_BAND_ROWS * width;
+        partPixel[p + 1u] = partPixel[p] + mine;
+        wordOffset[p] = start;
+        wordOffset[parts + p] = start + mine * covAt;
+        wordOffset[2u * parts + p] = start + mine * countAt;
+    }
+    gathered.ensure(static_cast<size_t>(partPixel[parts]) * pixelWords);
+    dWordOffset.upload(wordOffset.data(), wordOffset.size());
+}
+
+void BandGather::interleave(float* dRgb, float* dCov, void* dCount, hipStream_t stream) const {
+    launchMultiInterleave(gathered.ptr, dWordOffset.ptr, parts, width, height, 3u, dRgb, stream);
+    if (dCov) launchMultiInterleave(gathered.ptr, dWordOffset.ptr + parts, parts, width, height, 6u, dCov, stream);
+    if (dCount) launchMultiInterleave(gathered.ptr, dWordOffset.ptr + 2u * parts, parts, width, height, 1u, dCount, stream);
+    HIP_CHECK(hipGetLastError());
+}
+
 }  // namespace ptrhost
 
 namespace {
-
-using Clock = std::chrono::steady_clock;
-double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
 
 // What one call asks for.  The kind says which pointers it needs and what it reports; everything else runFrame reads off the outputs asked for.
 enum class Kind { Plain, Covariance, Adaptive, Probe };   // ptr_render_multi; ..._cov; ..._adaptive; the test-only probe, which has no scene
@@ -169,50 +185,34 @@ void runFrame(const Request& rq) {
     PreparedScene prepared;
     if (!probe) prepareScene(*rq.scene, prepared);
 
-    // where partition p's band-layout buffer starts among all of them, in pixels
-    std::vector<uint64_t> partPixel(parts + 1u, 0u);
     std::vector<uint32_t> partBands(parts, 0u);
-    for (uint32_t p = 0; p < parts; ++p) {
-        partBands[p] = ptr_part_band_count(height, p, parts);
-        partPixel[p + 1u] = partPixel[p] + static_cast<uint64_t>(partBands[p]) * PTR_BAND_ROWS * width;
-    }
-    const size_t bandPixels = partPixel[parts];
+    for (uint32_t p = 0; p < parts; ++p) partBands[p] = ptr_part_band_count(height, p, parts);
     const int rootDevice = rq.devices[0];
     const bool wantCov = rq.outCov != nullptr, wantCount = adaptive && rq.outCount != nullptr;
-    // A partition's outputs are one buffer in band layout - rgb, then cov, then count, the last two where they are asked for - so that it
-    // travels to the first device in one transfer.  On the first device: the partitions' buffers one after the other, the word each
-    // output of each partition starts at (k_multi_interleave's table: [output][partition]), and the image-order outputs.
+    // a partition's band buffer holds cov and count only where they are asked for; on the first device the gather and the image-order outputs
     const uint32_t covAt = 3u, countAt = wantCov ? 9u : 3u, pixelWords = countAt + (wantCount ? 1u : 0u);
-    std::vector<uint64_t> wordOffset(static_cast<size_t>(parts) * 3u, 0u);
-    for (uint32_t p = 0; p < parts; ++p) {
-        const uint64_t start = partPixel[p] * pixelWords, mine = partPixel[p + 1u] - partPixel[p];
-        wordOffset[p] = start;
-        wordOffset[parts + p] = start + mine * covAt;
-        wordOffset[2u * parts + p] = start + mine * countAt;
-    }
-    DeviceBuffer<float> gathered, image;
-    DeviceBuffer<uint64_t> dWordOffset;
+    BandGather bands;
+    DeviceBuffer<float> image;
     HIP_CHECK(hipSetDevice(rootDevice));
-    gathered.ensure(bandPixels * pixelWords);
+    bands.allocate(partBands, width, height, covAt, countAt, pixelWords);
     image.ensure(pixels * pixelWords);
-    dWordOffset.upload(wordOffset.data(), wordOffset.size());
 
     HaloExchange ex;
     if (adaptive && parts > 1u) ex.allocate(partBands, width);
 
     std::vector<std::unique_ptr<PtrDeviceScene>> scenes(parts);
     std::vector<PtrRenderStats> partStats(parts);
-    std::vector<std::string> errors(parts);
-    std::vector<double> uploadSeconds(parts, 0.0), stateSeconds(parts, 0.0), renderSeconds(parts, 0.0), waitSeconds(parts, 0.0);
+    std::vector<hipStream_t> streams(parts, nullptr);   // per call: made by a partition's thread and destroyed by it
+    std::vector<double> uploadSeconds(parts, 0.0), stateSeconds(parts, 0.0), renderSeconds(parts, 0.0), workerSeconds(parts, 0.0), waitSeconds(parts, 0.0);
     std::vector<uint64_t> partSamples(parts, 0u);
     std::vector<uint32_t> partAtMax(parts, 0u), published(parts, 0u);
     std::atomic<uint32_t> stagedParts{0};
-    ptr::RoundBarrier barrier(parts);
     PtrAdaptiveInfo info{};   // written by partition 0's thread (every thread computes the same figures)
     uint32_t sharedCount = 0u;
     const double setupSeconds = since(t0) - prepared.seconds;   // the first device's buffers and the exchange memory
 
-    auto body = [&](uint32_t p, hipStream_t& stream) {
+    auto body = [&](uint32_t p, const auto& meet) {
+        hipStream_t& stream = streams[p];
         const auto w0 = Clock::now();
         auto ds = std::make_unique<PtrDeviceScene>();
         ds->device = rq.devices[p];
@@ -221,15 +221,14 @@ void runFrame(const Request& rq) {
         HIP_CHECK(hipSetDevice(ds->device));
         HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         const MultiPart mp{p, parts, partBands[p], width, height};
-        const size_t myBandPixels = static_cast<size_t>(partPixel[p + 1u] - partPixel[p]);
+        const size_t myBandPixels = bands.bandPixels(p);
         ds->adaptiveOut.ensure(myBandPixels * pixelWords);   // the partition's rgb, cov and count in band layout
         float* const dRgb = ds->adaptiveOut.ptr;
         float* const dCov = wantCov ? dRgb + myBandPixels * covAt : nullptr;
         uint32_t* const dCount = wantCount ? reinterpret_cast<uint32_t*>(dRgb + myBandPixels * countAt) : nullptr;
 
         auto handOver = [&] {   // the band buffer travels to the first device in one piece
-            if (myBandPixels && sendBandsToRoot(gathered.ptr + wordOffset[p], rootDevice, dRgb, ds->device, myBandPixels * pixelWords * sizeof(float),
-                                                rq.forceStaged[p] != 0, stream)) {
+            if (myBandPixels && sendBandsToRoot(bands.slot(p), rootDevice, dRgb, ds->device, bands.bandBytes(p), rq.forceStaged[p] != 0, stream)) {
                 stagedParts.fetch_add(1);
             }
             HIP_CHECK(hipStreamSynchronize(stream));
@@ -271,12 +270,6 @@ void runFrame(const Request& rq) {
         stateSeconds[p] = since(w0) - uploadSeconds[p];
 
         const auto r0 = Clock::now();
-        auto meet = [&]() -> bool {
-            const auto m0 = Clock::now();
-            const bool all = barrier.arriveAndWait();
-            waitSeconds[p] += since(m0);
-            return all;
-        };
         uint32_t active = local, n = 0u, turn = 0u, rounds = 0u;
         // PTR_VERBOSE=launches: device events around the two halves of the exchange (tools/multi_adaptive_cost.py parses the line)
         EventSet marks;
@@ -339,56 +332,25 @@ void runFrame(const Request& rq) {
         scenes[p] = std::move(ds);
     };
 
-    // Every way out of a worker but the regular one releases the partitions that wait for it; a worker released that way joins its own
-    // stream and launches nothing more.
-    auto worker = [&](uint32_t p) {
-        hipStream_t stream = nullptr;
-        try {
-            body(p, stream);
-        } catch (const HipError& e) {
-            barrier.fail();
-            errors[p] = e.message;
-        } catch (const std::exception& e) {
-            barrier.fail();
-            errors[p] = std::string("exception: ") + e.what();
-        } catch (...) {
-            barrier.fail();
-            errors[p] = "unknown exception";
-        }
-        if (stream) {
-            (void)hipStreamSynchronize(stream);
-            (void)hipStreamDestroy(stream);
-        }
-    };
-    ptr::runOnThreads(parts, worker, [&] { barrier.fail(); });   // (a thread that could not be started never arrives)
-    for (uint32_t p = 0; p < parts; ++p) {
-        if (!errors[p].empty()) throw HipError{"device " + std::to_string(rq.devices[p]) + ": " + errors[p]};
-    }
-    if (barrier.failed()) throw HipError{"a partition left the frame early"};
+    // a worker, however it ended, joins its stream and launches nothing more; the stream was this call's
+    runPartitionThreads(
+        rq.devices, workerSeconds.data(), waitSeconds.data(), body, [&](uint32_t p) { return streams[p]; },
+        [&](uint32_t p) {
+            if (streams[p]) (void)hipStreamDestroy(streams[p]);
+        });
 
     const double partsDone = since(t0);
     HIP_CHECK(hipSetDevice(rootDevice));
     float* const iRgb = image.ptr;
     float* const iCov = image.ptr + pixels * covAt;
     float* const iCount = image.ptr + pixels * countAt;
-    launchMultiInterleave(gathered.ptr, dWordOffset.ptr, parts, width, height, 3u, iRgb, nullptr);
-    if (wantCov) launchMultiInterleave(gathered.ptr, dWordOffset.ptr + parts, parts, width, height, 6u, iCov, nullptr);
-    if (wantCount) launchMultiInterleave(gathered.ptr, dWordOffset.ptr + 2u * parts, parts, width, height, 1u, iCount, nullptr);
-    HIP_CHECK(hipGetLastError());
+    bands.interleave(iRgb, wantCov ? iCov : nullptr, wantCount ? iCount : nullptr, nullptr);
     HIP_CHECK(hipMemcpy(rq.outRgb, iRgb, pixels * 3u * sizeof(float), hipMemcpyDeviceToHost));
     if (wantCov) HIP_CHECK(hipMemcpy(rq.outCov, iCov, pixels * 6u * sizeof(float), hipMemcpyDeviceToHost));
     if (wantCount) HIP_CHECK(hipMemcpy(rq.outCount, iCount, pixels * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if (!probe && (rq.outAlbedo || rq.outNormal)) {   // the first partition's scene is on the first device
-        RenderParams rp;
-        fillRenderParams(settings, 1u, rp);
         DeviceBuffer<float4> albedo, normal;
-        albedo.ensure(pixels);
-        normal.ensure(pixels);
-        launchAovs(rp, scenes[0]->view, 0u, albedo.ptr, normal.ptr, coldLaunchConfig(*scenes[0]), nullptr);
-        HIP_CHECK(hipGetLastError());
-        HIP_CHECK(hipDeviceSynchronize());
-        if (rq.outAlbedo) albedo.download(reinterpret_cast<float4*>(rq.outAlbedo), pixels);
-        if (rq.outNormal) normal.download(reinterpret_cast<float4*>(rq.outNormal), pixels);
+        downloadFirstHit(*scenes[0], settings, 0u, albedo, normal, rq.outAlbedo, rq.outNormal);
     }
     const double gatherSeconds = since(t0) - partsDone;   // interleave, download, feature buffers
     for (uint32_t p = 0; p < parts; ++p) {

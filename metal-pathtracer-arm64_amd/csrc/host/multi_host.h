@@ -1,14 +1,19 @@
 // What the two drivers of frames on several devices share on the host - the one-shot frames of multi.cpp (include/ptr_multi.h) and the
 // resumable frame of multi_frame.cpp (include/ptr_multi_frame.h): the device list of a call and its refusals, the pinned memory the
-// partitions exchange their band-edge rows of e through with the two halves of that exchange, and the hand-over of a partition's band
-// buffer to the first device.  Implemented in multi.cpp.  Internal: not part of the C-ABI.
+// partitions exchange their band-edge rows of e through with the two halves of that exchange, the hand-over of a partition's band
+// buffer to the first device, the gather there with its interleave into image order, and the one driver that runs a call's partitions
+// on threads which meet at a round barrier (round_barrier.h) and end together when one of them fails.  Implemented in multi.cpp.
+// Internal: not part of the C-ABI.
 #pragma once
 
+#include <chrono>
 #include <string>
 #include <vector>
 
 #include "../kernels/multi.h"
 #include "device_scene.h"
+#include "parallel.h"
+#include "round_barrier.h"
 
 namespace ptrhost {
 
@@ -55,5 +60,71 @@ void haloCollect(const ptrk::MultiPart& mp, float* dEdge, float* dE, const HaloE
 // when the two devices can address each other, through pinned host memory otherwise (or with forceStaged, the tests' hook).  Called on
 // the partition's thread with `device` current; asynchronous on `stream` except for the staged path.  True when the bytes were staged.
 bool sendBandsToRoot(void* dRootDst, int rootDevice, const void* dSrc, int device, size_t bytes, bool forceStaged, hipStream_t stream);
+
+// The gather of the partitions' outputs on the first device.  A partition's outputs are one buffer in band layout - rgb, then cov from
+// word covAt of a pixel on, then count from word countAt on, pixelWords in all - so that it travels in one transfer.  Here: the
+// partitions' buffers one after the other, and the word each output of each partition starts at (k_multi_interleave's table:
+// [output][partition]).
+struct BandGather {
+    uint32_t parts = 0, width = 0, height = 0, pixelWords = 0;
+    std::vector<uint64_t> partPixel;    // where partition p's buffer starts among all of them, in pixels; [parts] = all of them
+    std::vector<uint64_t> wordOffset;
+    DeviceBuffer<float> gathered;
+    DeviceBuffer<uint64_t> dWordOffset;
+
+    // the first device is current
+    void allocate(const std::vector<uint32_t>& partBands, uint32_t imageWidth, uint32_t imageHeight, uint32_t covAt, uint32_t countAt, uint32_t words);
+    size_t bandPixels(uint32_t p) const { return static_cast<size_t>(partPixel[p + 1u] - partPixel[p]); }
+    size_t bandBytes(uint32_t p) const { return bandPixels(p) * pixelWords * sizeof(float); }
+    float* slot(uint32_t p) const { return gathered.ptr + wordOffset[p]; }
+    // from the gathered buffers into image order (dCov and dCount nullable), asynchronous on `stream` of the first device, which is current
+    void interleave(float* dRgb, float* dCov, void* dCount, hipStream_t stream) const;
+};
+
+using Clock = std::chrono::steady_clock;
+inline double since(Clock::time_point t0) { return std::chrono::duration<double>(Clock::now() - t0).count(); }
+
+// One call's partitions on threads, partition p on devices[p]: body(p, meet) with that device current.  meet() is the round barrier -
+// false once a partition has failed, and the body then returns at once.  Every way out of a worker but the regular one releases the
+// partitions that wait for it.  However the body ended, the worker joins streamOf(p) (where not null), then runs done(p).  seconds /
+// waited (an entry per partition): in the worker and of those in meet().  A failure is thrown with the device's id.
+template <typename Body, typename StreamOf, typename Done>
+void runPartitionThreads(const std::vector<int>& devices, double* seconds, double* waited, Body&& body, StreamOf&& streamOf, Done&& done) {
+    const uint32_t parts = static_cast<uint32_t>(devices.size());
+    std::vector<std::string> errors(parts);
+    ptr::RoundBarrier barrier(parts);
+    auto worker = [&](uint32_t p) {
+        const auto t0 = Clock::now();
+        waited[p] = 0.0;
+        auto meet = [&]() -> bool {
+            const auto m0 = Clock::now();
+            const bool all = barrier.arriveAndWait();
+            waited[p] += since(m0);
+            return all;
+        };
+        try {
+            HIP_CHECK(hipSetDevice(devices[p]));
+            body(p, meet);
+            HIP_CHECK(hipGetLastError());
+        } catch (const HipError& e) {
+            barrier.fail();
+            errors[p] = e.message;
+        } catch (const std::exception& e) {
+            barrier.fail();
+            errors[p] = std::string("exception: ") + e.what();
+        } catch (...) {
+            barrier.fail();
+            errors[p] = "unknown exception";
+        }
+        if (hipStream_t stream = streamOf(p)) (void)hipStreamSynchronize(stream);
+        done(p);
+        seconds[p] = since(t0);
+    };
+    ptr::runOnThreads(parts, worker, [&] { barrier.fail(); });   // (a thread that could not be started never arrives)
+    for (uint32_t p = 0; p < parts; ++p) {
+        if (!errors[p].empty()) throw HipError{"device " + std::to_string(devices[p]) + ": " + errors[p]};
+    }
+    if (barrier.failed()) throw HipError{"a partition left the frame early"};
+}
 
 }  // namespace ptrhost

@@ -152,6 +152,27 @@ def test_cli_documents_and_checks_the_snapshots_flag():
         assert "HIP" not in res.stdout, flags                          # refused with a message, before any device call
 
 
+# --------------------------------------------------------------------------- the sanitizer program
+def test_the_stand_alone_host_check_builds_and_runs_clean(tmp_path):
+    """tools/frame_host_check.cpp with -fsanitize=address,undefined: a stand-alone program on the CPU with its own main and the
+    sanitizers' runtimes linked in.  It walks the per-element bodies of csrc/kernels/frame.h over every image size 1x1 .. 130x70 and
+    holds the frames' table of pixels per count (csrc/host/frame_classes.h) against the histogram of the counts after every move."""
+    csrc = os.path.join(ROOT, "metal-pathtracer-arm64_amd", "csrc")
+    exe = tmp_path / "frame_host_check"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
+                    "-I", os.path.join(ROOT, "include"), "-I", os.path.join(csrc, "host"), "-I", os.path.join(csrc, "kernels"),
+                    os.path.join(ROOT, "tools", "frame_host_check.cpp"), "-o", str(exe)], check=True)
+    res = subprocess.run([str(exe)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert res.returncode == 0, res.stdout
+    m = re.fullmatch(r"frame host check: (\d+) entries visited, (\d+) in their round's class, (\d+) kept, (\d+) dropped, (\d+) class moves, no finding",
+                     res.stdout.strip())
+    assert m, res.stdout
+    visited, in_class, kept, dropped, moves = (int(v) for v in m.groups())
+    assert visited == kept + dropped and 0 < in_class < visited and kept > 0 and dropped > 0
+    assert moves >= 130 * 70      # at least one move per image size
+    assert "runtime error" not in res.stdout and "AddressSanitizer" not in res.stdout
+
+
 # --------------------------------------------------------------------------- the restatement's own laws
 def uniform_state(x, n):
     """The state of a uniform frame of n samples, through adaptive_ref alone."""

@@ -372,17 +372,28 @@ frame.close()
 multi = pt.render_multi_adaptive(host.desc, s, p1, device_ids=[0, 0])
 note("multi", multi["info"])
 out["multi_count"] = multi["count"].tolist()
+mf = pt.multi_frame(host.desc, s, device_ids=[0, 0])
+for name, p in (("mf_refine1", p1), ("mf_refine2", p2)):
+    sys.stderr.write("[child] %%s begins\\n" %% name)
+    sys.stderr.flush()
+    info = mf.refine(p)[1]
+    note(name, info)
+    out[name]["total"] = int(info.totalSamples)
+mf.close()
 print(json.dumps(out))
 """ % (W, H, MIN, MAX, STEP, MIN, MORE, STEP)
-# the expressions tools/adaptive_cost.py, tools/frame_cost.py and tools/multi_adaptive_cost.py parse the lines with
+# the expressions tools/adaptive_cost.py, tools/frame_cost.py, tools/multi_adaptive_cost.py and tools/multi_frame_cost.py parse the lines with
 ADAPTIVE_LINE = r"\[adaptive\] .*: (\d+) active x (\d+) spp; update ([0-9.]+) ms, select \+ compact ([0-9.]+) ms"
 FRAME_LINE = r"\[frame\] round (\d+): class (\d+), (\d+) of (\d+) active x (\d+) spp; minimum \+ split ([0-9.]+) ms, select \+ merge ([0-9.]+) ms"
 MULTI_LINE = r"\[multi\] partition (\d+) round (\d+): halo (\d+) bytes each way; pack \+ copy ([0-9.]+) ms, copy \+ unpack ([0-9.]+) ms"
+MULTI_FRAME_LINE = (r"\[multi-frame\] partition (\d+) round (\d+): class (\d+), (\d+) entries x (\d+) spp; halo (\d+) bytes each way; "
+                    r"pack \+ copy ([0-9.]+) ms, copy \+ unpack ([0-9.]+) ms")
 
 
 def test_verbose_lines_of_the_three_loops(resumed):
     """PTR_VERBOSE=launches in a fresh process: ptr_render_adaptive, two refines of a frame and a two-partition frame on one device print
-    one line per round each, with the counts the calls report.  777 x 4 accumulators fit one pass, so no round is split."""
+    one line per round each, with the counts the calls report; so do the same two refines of a resumable two-partition frame, per
+    partition.  777 x 4 accumulators fit one pass, so no round is split."""
     env = dict(os.environ, PTR_VERBOSE="launches")
     r = subprocess.run([sys.executable, "-c", VERBOSE_CHILD, ROOT, repr(float(resumed["p1"].threshold)), repr(float(resumed["p2"].threshold))],
                        capture_output=True, text=True, timeout=120, env=env)
@@ -441,3 +452,21 @@ def test_verbose_lines_of_the_three_loops(resumed):
     assert len(want) == 2 * m["rounds"]      # on this scene both partitions stay active to the end
     bands = [int((band % 2 == q)[::8].sum()) for q in (0, 1)]
     assert all(halo == bands[q] * 2 * W * 4 for q, _, halo in rows)
+    # [multi-frame]: the two refines on a two-partition frame; at most one line per partition and round in which the partition's S_p
+    # is not empty, with the round's class, |S_p| and samples.  The calls are the single-device frame's.
+    marks = [i for i, l in enumerate(lines) if l.startswith("[child] mf_refine")]
+    assert len(marks) == 2
+    for name, single, begin, end, before in (("mf_refine1", r1, marks[0], marks[1], W * H * MIN), ("mf_refine2", r2, marks[1], len(lines), 0)):
+        call = got[name]
+        assert (call["rounds"], call["active"]) == (single["rounds"], single["active"]), name
+        rows = [m.groups() for m in (re.search(MULTI_FRAME_LINE, l) for l in lines[begin:end]) if m]
+        assert all(float(ms) >= 0.0 for row in rows for ms in row[6:]), name
+        rows = [tuple(int(v) for v in row[:6]) for row in rows]
+        print("[multi-frame]", name, rows)
+        assert len({row[:2] for row in rows}) == len(rows), name
+        assert all(entries >= 1 and 1 <= spp <= STEP for _, _, _, entries, spp, _ in rows), name
+        classes = {}
+        for _, rnd, cls, _, _, _ in rows:
+            assert classes.setdefault(rnd, cls) == cls, (name, rnd)
+        assert [classes[rnd] for rnd in sorted(classes)] == sorted(classes.values()), name
+        assert before + sum(entries * spp for _, _, _, entries, spp, _ in rows) == call["total"], name

@@ -104,7 +104,7 @@ def main():
         "at_once_1x64_over_uniform": round(best["frame_1x64"] / best["uniform_64"], 4),
         "between_rounds": {
             "timing": "device events around the launches (PTR_VERBOSE=launches), per round of one refine on a frame with mixed counts "
-                      "(minimum + split includes the host's read of the class minimum between the two)",
+                      "(minimum + split is the sum of the two spans; the host's read of the class minimum lies between them, in neither)",
             "counts_after": [int(info.minCount), int(info.maxCount)], "per_round": between, "hbm_peak_bytes_per_s": HBM_PEAK_BYTES_PER_S,
         },
     }

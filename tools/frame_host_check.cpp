@@ -1,18 +1,49 @@
 // Host check of the index arithmetic of the resumable frame's per-element bodies (csrc/kernels/frame.h): the bodies are host + device
 // functions, and this program drives them - the class minimum, the split predicate and the merge predicate - over every image size
 // 1x1 .. 130x70 on heap buffers of exactly the size the frame gives them, so that an address or undefined-behaviour sanitizer sees any
-// step outside.  Build and run on the host only:
-//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Imetal-pathtracer-arm64_amd/csrc/kernels \
-//       tools/frame_host_check.cpp -o /tmp/frame_host_check && /tmp/frame_host_check
+// step outside.  Beside them it drives the frames' host table of pixels per count (csrc/host/frame_classes.h) with the moves those
+// rounds make - the class minimum, the size of S - and compares it after every move with the histogram of the counts themselves.
+// Build and run on the host only:
+//   g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude -Imetal-pathtracer-arm64_amd/csrc/host \
+//       -Imetal-pathtracer-arm64_amd/csrc/kernels tools/frame_host_check.cpp -o /tmp/frame_host_check && /tmp/frame_host_check
 // (The ranks of the compaction come from a wave ballot and exist on the device only; the tests compare its output with the restatement.)
 #include <cstdio>
 #include <memory>
 #include <vector>
 
 #include "frame.h"
+#include "frame_classes.h"
+
+namespace {
+
+constexpr uint32_t kLastClass = 16u, kMaxCount = kLastClass + 4u;   // the counts start at 4, 8, 12 and 16, and every class takes one step of 4
+
+// the table against the histogram of n, count by count, and what it derives from itself against what n says
+bool sameAsCounts(const ptrhost::CountClasses& classes, const uint32_t* n, size_t pixels) {
+    uint64_t hist[kMaxCount + 1u] = {};
+    uint64_t total = 0;
+    uint32_t lo = n[0], hi = n[0];
+    for (size_t p = 0; p < pixels; ++p) {
+        if (n[p] > kMaxCount) return false;
+        ++hist[n[p]];
+        total += n[p];
+        lo = n[p] < lo ? n[p] : lo;
+        hi = n[p] > hi ? n[p] : hi;
+    }
+    for (uint32_t c = 0; c <= kMaxCount; ++c) {
+        if (classes.pixelsAt(c) != hist[c]) return false;
+    }
+    PtrFrameInfo info{};
+    classes.fill(info);
+    return classes.minCount() == lo && classes.maxCount() == hi && classes.uniform() == (lo == hi) && classes.empty() == (hi == 0u) &&
+           classes.pixelsAt(classes.maxCount()) == hist[hi] && info.minCount == lo && info.maxCount == hi && info.totalSamples == total &&
+           info.uniform == (lo == hi ? 1u : 0u);
+}
+
+}  // namespace
 
 int main() {
-    unsigned long long visited = 0, inClass = 0, kept = 0, dropped = 0;
+    unsigned long long visited = 0, inClass = 0, kept = 0, dropped = 0, moves = 0;
     for (uint32_t h = 1; h <= 70; ++h) {
         for (uint32_t w = 1; w <= 130; ++w) {
             const size_t pixels = static_cast<size_t>(w) * h;
@@ -32,6 +63,14 @@ int main() {
                             if ((y * w + x) % 4u != 1u || pixels == 1u) order.push_back(y * w + x);
             const uint32_t count = static_cast<uint32_t>(order.size());
             if (count == 0u) continue;
+            // the table: every pixel at 0, the first samples of all of them, then the counts as an import brings them
+            ptrhost::CountClasses classes;
+            classes.reset(pixels);
+            if (!classes.empty() || classes.pixelsAt(0u) != pixels) return 6;
+            classes.move(0u, 4u, pixels);
+            if (!classes.uniform() || classes.minCount() != 4u || classes.pixelsAt(4u) != pixels || classes.pixelsAt(0u) != 0u) return 6;
+            classes.rebuild(n.get(), pixels);
+            if (!sameAsCounts(classes, n.get(), pixels)) return 6;
             std::unique_ptr<uint32_t[]> list(new uint32_t[count]);
             for (uint32_t j = 0; j < count; ++j) list[j] = order[j];
             uint32_t nMin = ptrk::kFrameNoCount, want = ptrk::kFrameNoCount;
@@ -59,9 +98,26 @@ int main() {
                 ++visited;
             }
             inClass += members;
+            classes.move(nMin, nMin + 4u, members);
+            ++moves;
+            if (!sameAsCounts(classes, n.get(), pixels)) return 7;
+            // the rounds that follow on the same list, lowest class first, until every entry is past the last class
+            for (;;) {
+                uint32_t next = ptrk::kFrameNoCount, size = 0;
+                for (uint32_t j = 0; j < count; ++j) next = ptrk::frameClassMin(next, list.get(), j, n.get());
+                if (next > kLastClass) break;
+                for (uint32_t j = 0; j < count; ++j) {
+                    if (!ptrk::frameInClass(list.get(), j, n.get(), next)) continue;
+                    n[list[j]] = next + 4u;
+                    ++size;
+                }
+                classes.move(next, next + 4u, size);
+                ++moves;
+                if (size == 0u || !sameAsCounts(classes, n.get(), pixels)) return 7;
+            }
         }
     }
-    std::printf("frame host check: %llu entries visited, %llu in their round's class, %llu kept, %llu dropped, no finding\n", visited, inClass, kept,
-                dropped);
-    return visited > 0 && inClass > 0 && inClass < visited && kept > 0 && dropped > 0 ? 0 : 1;
+    std::printf("frame host check: %llu entries visited, %llu in their round's class, %llu kept, %llu dropped, %llu class moves, no finding\n", visited,
+                inClass, kept, dropped, moves);
+    return visited > 0 && inClass > 0 && inClass < visited && kept > 0 && dropped > 0 && moves > 0 ? 0 : 1;
 }
