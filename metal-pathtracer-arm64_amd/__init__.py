@@ -735,6 +735,56 @@ _MULTI_DYNAMIC_SIGNATURES = {
 }
 MULTI_DYNAMIC_SYMBOLS = tuple(_MULTI_DYNAMIC_SIGNATURES)
 
+
+# ... and of include/ptr_appearance.h (materials, textures and the environment of a resident scene): tests/test_appearance_host.py holds
+# it against that header
+PTR_APPEARANCE_ENV_MAX_DIM = 4096
+
+
+class PtrAppearanceInfo(C.Structure):
+    """include/ptr_appearance.h PtrAppearanceInfo."""
+    _fields_ = [
+        ("totalSeconds", C.c_double),
+        ("stagingMs", C.c_double),
+        ("kernelMs", C.c_double * 6),
+        ("rowsRekeyed", C.c_uint64),
+        ("texelsWritten", C.c_uint64),
+        ("lightsBefore", C.c_uint32),
+        ("lightsAfter", C.c_uint32),
+        ("envSampling", C.c_uint32),
+        ("pad", C.c_uint32),
+    ]
+
+    def as_dict(self) -> dict:
+        return {name: (list(getattr(self, name)) if hasattr(getattr(self, name), "__len__") else getattr(self, name))
+                for name, _ in self._fields_ if name != "pad"}
+
+
+class PtrTextureUpdate(C.Structure):
+    """include/ptr_appearance.h PtrTextureUpdate: rgba is a host address for set_textures, a device address for set_textures_device."""
+    _fields_ = [("textureIndex", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("wrapS", C.c_uint32), ("wrapT", C.c_uint32),
+                ("filter", C.c_uint32), ("rgba", C.c_void_p)]
+
+
+_appearance_info = C.POINTER(PtrAppearanceInfo)
+_APPEARANCE_SIGNATURES = {
+    "ptr_scene_set_materials": (_int, [_vp, _up, _material, _u32, _vp, _appearance_info] + _err),
+    "ptr_scene_set_textures": (_int, [_vp, C.POINTER(PtrTextureUpdate), _u32, _vp, _appearance_info] + _err),
+    "ptr_scene_set_textures_device": (_int, [_vp, C.POINTER(PtrTextureUpdate), _u32, _vp, _appearance_info] + _err),
+    "ptr_scene_set_environment": (_int, [_vp, _vp, _u32, _u32, _vp, _appearance_info] + _err),
+    "ptr_scene_set_environment_device": (_int, [_vp, _vp, _u32, _u32, _vp, _appearance_info] + _err),
+    # its test-only probe
+    "ptr_debug_appearance_arrays": (_int, [_vp, _u32, _vp, _u64, _u64p]),
+}
+APPEARANCE_SYMBOLS = tuple(_APPEARANCE_SIGNATURES)
+# ptr_debug_appearance_arrays: name -> (selector, dtype, trailing shape).  Words that hold bit patterns beside floats (texture indices,
+# alias entries) are read as uint32, so comparisons are of the raw words.
+APPEARANCE_ARRAYS = {"materials": (0, np.uint32, (16, 4)), "materialTex": (1, np.uint32, (16, 4)), "rectLights": (2, np.uint32, (11, 4)),
+                     "lightIndexByRect": (3, np.int32, ()), "texels": (4, np.uint32, (4,)), "texInfo": (5, np.uint32, (20,)),
+                     "envRgba": (6, np.uint32, (4,)), "envCond": (7, np.uint32, (2,)), "envMarg": (8, np.uint32, (2,)), "envPdf": (9, np.uint32, ()),
+                     "envMips": (10, np.uint32, (4,)), "scalars": (11, np.uint32, ())}
+APPEARANCE_SCALARS = ("materialTypes", "rectLightCount", "settleRectLights", "hasRandomWalkMaterial", "envSampling", "envMipLevels")
+
 # ptr_debug_scene_arrays / ptr_debug_dynamic_tables: name -> (selector, dtype, trailing shape)
 SCENE_ARRAYS = {"tris": (0, np.float32, (3, 4)), "triNormals": (1, np.float32, (3, 4)), "triUv": (2, np.float32, (4, 4)),
                 "triTangent": (3, np.float32, (3, 4)), "triBounds": (4, np.float32, (2, 4)), "sphereBounds": (5, np.float32, (2, 4)),
@@ -770,7 +820,8 @@ def load_library() -> C.CDLL:
             list(_ADAPTIVE_SIGNATURES.items()) + list(_MULTI_SIGNATURES.items()) + list(_FRAME_SIGNATURES.items()) + list(_MULTI_FRAME_SIGNATURES.items()) + \
             list(_DYNAMIC_SIGNATURES.items()) + list(_DEFORM_SIGNATURES.items()) + list(_DEFORM_DEVICE_SIGNATURES.items()) + \
             list(_BACKGROUND_SIGNATURES.items()) + list(_TEMPORAL_SIGNATURES.items()) + list(_TEMPORAL_COV_SIGNATURES.items()) + list(_PBR_HIT_SIGNATURES.items()) + \
-            list(_SSS_WALK_SIGNATURES.items()) + list(_PATH_STATE_SIGNATURES.items()) + list(_REBUILD_SIGNATURES.items()) + list(_MULTI_DYNAMIC_SIGNATURES.items()):
+            list(_SSS_WALK_SIGNATURES.items()) + list(_PATH_STATE_SIGNATURES.items()) + list(_REBUILD_SIGNATURES.items()) + list(_MULTI_DYNAMIC_SIGNATURES.items()) + \
+            list(_APPEARANCE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -1045,6 +1096,104 @@ class DeviceScene:
         err = _err_buf()
         _check(load_library().ptr_scene_set_rects(self._h, items, len(rects), C.c_void_p(stream), C.byref(info), err, len(err)), err)
         return info.as_dict()
+
+    def _appearance_call(self, name: str, *args, stream=0) -> dict:
+        info = PtrAppearanceInfo()
+        err = _err_buf()
+        _check(getattr(load_library(), name)(self._h, *args, C.c_void_p(stream), C.byref(info), err, len(err)), err)
+        return info.as_dict()
+
+    def _current_stream(self, stream):
+        if stream is not None:
+            return stream
+        import torch   # (only here: the module itself does not need torch)
+
+        return torch.cuda.current_stream(self._device).cuda_stream
+
+    def set_materials(self, materials: dict, stream: int = 0) -> dict:
+        """ptr_scene_set_materials: {material index: PtrMaterial}, each replacing the whole material; returns PtrAppearanceInfo as a dict.
+        A Frame or a Temporal of the scene is not told: reset them."""
+        indices = (C.c_uint32 * max(len(materials), 1))(*[int(i) for i in materials])
+        items = (PtrMaterial * max(len(materials), 1))()
+        for k, m in enumerate(materials.values()):
+            C.memmove(C.byref(items[k]), C.byref(m), C.sizeof(PtrMaterial))
+        return self._appearance_call("ptr_scene_set_materials", indices, items, len(materials), stream=stream)
+
+    @staticmethod
+    def _texture_items(name: str, textures: dict, address):
+        items = (PtrTextureUpdate * max(len(textures), 1))()
+        keep = []
+        for k, (index, value) in enumerate(textures.items()):
+            pixels, wrap_s, wrap_t, filt = value if isinstance(value, tuple) else (value, 0, 0, 1)
+            data, (h, w) = address(name, "texture %s" % (index,), pixels)
+            keep.append(data)
+            items[k].textureIndex, items[k].width, items[k].height = int(index), w, h
+            items[k].wrapS, items[k].wrapT, items[k].filter = int(wrap_s), int(wrap_t), int(filt)
+            items[k].rgba = data.data_ptr() if hasattr(data, "data_ptr") else data.ctypes.data
+        return items, keep
+
+    @staticmethod
+    def _host_pixels(name: str, what: str, pixels):
+        a = np.ascontiguousarray(pixels, dtype=np.float32)
+        if a.ndim != 3 or a.shape[2] != 4:
+            raise PtrError("%s: the pixels of %s have shape %s, not [height, width, 4]" % (name, what, a.shape))
+        return a, a.shape[:2]
+
+    def _device_pixels(self, name: str, what: str, t):
+        device = getattr(t, "device", None)
+        if not hasattr(t, "data_ptr") or device is None:
+            raise PtrError("%s: the pixels of %s are not a torch tensor" % (name, what))
+        if device.type != "cuda" or device.index != self._device:
+            raise PtrError("%s: the pixels of %s are on %s, not on device %d of the scene" % (name, what, device, self._device))
+        if str(t.dtype) != "torch.float32":
+            raise PtrError("%s: the pixels of %s are %s, not float32" % (name, what, t.dtype))
+        if t.dim() != 3 or t.shape[2] != 4:
+            raise PtrError("%s: the pixels of %s have shape %s, not [height, width, 4]" % (name, what, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise PtrError("%s: the pixels of %s are not contiguous" % (name, what))
+        return t, (int(t.shape[0]), int(t.shape[1]))
+
+    def set_textures(self, textures: dict, stream: int = 0) -> dict:
+        """ptr_scene_set_textures: {texture index: pixels [height, width, 4] linear float32, or (pixels, wrapS, wrapT, filter)} at the
+        upload's size (pixels alone: repeat, repeat, linear); the mip chain is rebuilt on the device.  Returns PtrAppearanceInfo as a dict."""
+        items, keep = self._texture_items("set_textures", textures, self._host_pixels)
+        return self._appearance_call("ptr_scene_set_textures", items, len(textures), stream=stream)
+
+    def set_textures_device(self, textures: dict, stream=None) -> dict:
+        """ptr_scene_set_textures_device: set_textures from torch tensors on the scene's device (float32, contiguous), read where they are
+        on `stream` (a raw stream handle; None: torch's current stream of the scene's device)."""
+        items, keep = self._texture_items("set_textures_device", textures, self._device_pixels)
+        return self._appearance_call("ptr_scene_set_textures_device", items, len(textures), stream=self._current_stream(stream))
+
+    def set_environment(self, pixels, stream: int = 0) -> dict:
+        """ptr_scene_set_environment: new pixels [height, width, 4] (linear float32) for the environment map at the upload's size; the
+        importance tables are rebuilt on the device.  Returns PtrAppearanceInfo as a dict."""
+        a, (h, w) = self._host_pixels("set_environment", "the map", pixels)
+        return self._appearance_call("ptr_scene_set_environment", a.ctypes.data_as(C.c_void_p), w, h, stream=stream)
+
+    def set_environment_device(self, pixels, stream=None) -> dict:
+        """ptr_scene_set_environment_device: set_environment from a torch tensor on the scene's device, read where it is on `stream`
+        (None: torch's current stream of the scene's device)."""
+        t, (h, w) = self._device_pixels("set_environment_device", "the map", pixels)
+        return self._appearance_call("ptr_scene_set_environment_device", C.c_void_p(t.data_ptr()), w, h, stream=self._current_stream(stream))
+
+    def appearance_arrays(self, names=None) -> dict:
+        """ptr_debug_appearance_arrays: the named arrays (all of APPEARANCE_ARRAYS by default) as raw words; "scalars" as a dict."""
+        lib = load_library()
+        out = {}
+        for name in (names or APPEARANCE_ARRAYS):
+            which, dtype, shape = APPEARANCE_ARRAYS[name]
+            size = C.c_uint64(0)
+            if lib.ptr_debug_appearance_arrays(self._h, which, None, 0, C.byref(size)) != 0:
+                raise PtrError("ptr_debug_appearance_arrays(%s) failed" % name)
+            buf = np.zeros(size.value // np.dtype(dtype).itemsize, dtype)
+            rc = lib.ptr_debug_appearance_arrays(self._h, which, buf.ctypes.data_as(C.c_void_p), buf.nbytes, C.byref(size))
+            if rc != 0:
+                raise PtrError("ptr_debug_appearance_arrays(%s) failed (%d)" % (name, rc))
+            out[name] = buf.reshape((-1,) + shape)
+        if "scalars" in out:
+            out["scalars"] = dict(zip(APPEARANCE_SCALARS, (int(v) for v in out["scalars"])))
+        return out
 
     def tree_cost(self, stream: int = 0) -> float:
         """ptr_scene_tree_cost: the builder's SAH figure of the scene's current tree, computed on the device in float64."""

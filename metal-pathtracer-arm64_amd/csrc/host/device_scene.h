@@ -190,6 +190,36 @@ struct DynamicScene {
     }
 };
 
+// What the appearance calls (include/ptr_appearance.h, appearance.cpp) keep, made at the first of them: host mirrors of the arrays their
+// rules read (taken from the device, so a static scene needs nothing from its upload), and the scratch of their kernels.
+struct AppearanceState {
+    std::vector<float> materialRows;       // ds.materials
+    std::vector<uint32_t> rectMaterial;    // per rectangle: its material index as the description gave it
+    std::vector<uint32_t> texInfo;         // ds.texInfo
+    DeviceBuffer<uint8_t> keys;            // k_app_rekey's table
+    DeviceBuffer<uint32_t> words;          // [0] rows rekeyed, [1..] flag words of the finiteness check
+    DeviceBuffer<float4> checkRows;
+    DeviceBuffer<float> envWeight, envRowWeight, envCell, envTotal;
+    hipEvent_t events[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    void* pinned = nullptr;
+    size_t pinnedBytes = 0;
+    void* pinnedFor(size_t bytes) {
+        if (bytes > pinnedBytes) {
+            if (pinned) (void)hipHostFree(pinned);
+            pinned = nullptr, pinnedBytes = 0;
+            HIP_CHECK(hipHostMalloc(&pinned, bytes, hipHostMallocDefault));
+            pinnedBytes = bytes;
+        }
+        return pinned;
+    }
+    ~AppearanceState() {
+        for (hipEvent_t e : events) {
+            if (e) (void)hipEventDestroy(e);
+        }
+        if (pinned) (void)hipHostFree(pinned);
+    }
+};
+
 }  // namespace ptrhost
 
 struct PtrDeviceScene {
@@ -208,6 +238,7 @@ struct PtrDeviceScene {
     uint32_t envMipLevels = 0;   // 0: not built
     ptrk::SceneView view{};
     std::unique_ptr<ptrhost::DynamicScene> dynamic;   // ptr_scene_upload_dynamic only
+    std::unique_ptr<ptrhost::AppearanceState> appearance;   // include/ptr_appearance.h: made by the first call
     uint64_t info[8] = {0};
     double uploadSeconds = 0.0;
     double timings[4] = {0.0, 0.0, 0.0, 0.0};   // geometry preparation (or cache read), shading tables, copies to the device, 1 = geometry came from a cache
@@ -277,6 +308,7 @@ namespace ptrhost {
 
 // Defined in hip_backend.cpp.
 void compactMaterial(const PtrMaterial& m, std::vector<float>& out);
+void materialTexRow(const PtrMaterial& m, float* out);   // kMaterialTexVec4 float4
 void appendTextureWithMips(const PtrTexture& t, std::vector<float>& texels, std::vector<uint32_t>& info);
 double ensureEnvMips(PtrDeviceScene& ds);
 void fillRenderParams(const PtrSettings& s, uint32_t spp, ptrk::RenderParams& rp);

@@ -191,31 +191,6 @@ void gatherBakeFinish(PtrDeviceScene& ds, const std::vector<E>& entry, ArraysOf&
     finishUpdate(ds, st, t0, moved, info);
 }
 
-// What is wrong with `bytes` of a caller's array at `p` for a kernel on `device` to read, or "": the host half of
-// ptr_scene_set_mesh_vertices_device looks at the pointer alone, never at what it points to.
-std::string devicePointerProblem(const void* p, size_t bytes, int device) {
-    if (reinterpret_cast<uintptr_t>(p) & 3u) return "is not 4 B aligned";
-    hipPointerAttribute_t attr{};
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void)hipGetLastError();   // (a pointer the runtime has never seen)
-        return "is host memory, not device memory";
-    }
-    if (attr.isManaged || attr.type == hipMemoryTypeManaged) return "is managed memory, not plain device memory";
-    if (attr.type == hipMemoryTypeHost) return "is registered or pinned host memory, not device memory";
-    if (attr.type == hipMemoryTypeUnregistered) return "is host memory, not device memory";
-    if (attr.type != hipMemoryTypeDevice) return "is not plain device memory";
-    if (attr.device != device) return "is memory of device " + std::to_string(attr.device) + ", not of the scene's device " + std::to_string(device);
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
-        (void)hipGetLastError();   // (no range on record: the kind and the device are what is known)
-        return "";
-    }
-    const uintptr_t end = reinterpret_cast<uintptr_t>(base) + size, at = reinterpret_cast<uintptr_t>(p);
-    if (at > end || end - at < bytes) return "has " + std::to_string(end - std::min(at, end)) + " B left in its allocation, fewer than the " + std::to_string(bytes) + " B of the array";
-    return "";
-}
-
 const char* const kNotDynamic = "the scene is not dynamic (upload it with ptr_scene_upload_dynamic)";
 const char* const kNotDeformable = "the scene is not deformable (upload it with ptr_scene_upload_dynamic_ex and PTR_DYNAMIC_DEFORMABLE)";
 
@@ -242,6 +217,31 @@ void finiteCheck(const char* who, const DeviceVerticesUpdate& u, const std::vect
 }  // namespace
 
 namespace ptrhost {
+
+// What is wrong with `bytes` of a caller's array at `p` for a kernel on `device` to read, or "": the host half of
+// ptr_scene_set_mesh_vertices_device looks at the pointer alone, never at what it points to.
+std::string devicePointerProblem(const void* p, size_t bytes, int device) {
+    if (reinterpret_cast<uintptr_t>(p) & 3u) return "is not 4 B aligned";
+    hipPointerAttribute_t attr{};
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void)hipGetLastError();   // (a pointer the runtime has never seen)
+        return "is host memory, not device memory";
+    }
+    if (attr.isManaged || attr.type == hipMemoryTypeManaged) return "is managed memory, not plain device memory";
+    if (attr.type == hipMemoryTypeHost) return "is registered or pinned host memory, not device memory";
+    if (attr.type == hipMemoryTypeUnregistered) return "is host memory, not device memory";
+    if (attr.type != hipMemoryTypeDevice) return "is not plain device memory";
+    if (attr.device != device) return "is memory of device " + std::to_string(attr.device) + ", not of the scene's device " + std::to_string(device);
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void*>(p)) != hipSuccess) {
+        (void)hipGetLastError();   // (no range on record: the kind and the device are what is known)
+        return "";
+    }
+    const uintptr_t end = reinterpret_cast<uintptr_t>(base) + size, at = reinterpret_cast<uintptr_t>(p);
+    if (at > end || end - at < bytes) return "has " + std::to_string(end - std::min(at, end)) + " B left in its allocation, fewer than the " + std::to_string(bytes) + " B of the array";
+    return "";
+}
 
 std::string listProblem(const void* list, uint32_t count, const char* nullWords) {
     if (!list) return nullWords;

@@ -32,6 +32,8 @@ using InputsEnqueued = std::function<void()>;
 
 // "" or what is wrong with a call's list before anyone looks into it
 std::string listProblem(const void* list, uint32_t count, const char* nullWords);
+// "" or what is wrong with `bytes` of a caller's array at `p` for a kernel on `device` to read (the pointer alone is looked at)
+std::string devicePointerProblem(const void* p, size_t bytes, int device);
 // "" or what the uploads of a dynamic scene refuse about `flags`; `known` is the mask of the PTR_DYNAMIC_* flags the entry point knows
 std::string dynamicFlagsProblem(uint32_t flags, uint32_t known);
 

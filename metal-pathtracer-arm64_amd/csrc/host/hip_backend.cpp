@@ -70,6 +70,20 @@ void compactMaterial(const PtrMaterial& m, std::vector<float>& out) {
     }
 }
 
+// The per-material texture record (kernels/device_types.h kMaterialTexVec4 float4) of one material.
+void materialTexRow(const PtrMaterial& m, float* o) {
+    for (int r = 0; r < 12; ++r) std::memcpy(o + r * 4, m.textureTransform[r], 16);
+    for (int k = 0; k < 4; ++k) o[48 + k] = bitsToFloat(m.textureIndices0[k]);
+    o[52] = bitsToFloat(m.textureIndices1[0]);
+    o[53] = bitsToFloat(m.textureIndices1[1]);
+    const uint32_t uvSets = (std::min(m.textureUvSet0[0], 1u) << 0) | (std::min(m.textureUvSet0[1], 1u) << 1) | (std::min(m.textureUvSet0[2], 1u) << 2) |
+                            (std::min(m.textureUvSet0[3], 1u) << 3) | (std::min(m.textureUvSet1[0], 1u) << 4) | (std::min(m.textureUvSet1[1], 1u) << 5);
+    o[54] = bitsToFloat(uvSets);
+    o[55] = bitsToFloat(m.materialFlags);
+    std::memcpy(o + 56, m.pbrParams, 16);
+    std::memcpy(o + 60, m.pbrExtras, 16);
+}
+
 // Mip chain of one texture appended to `texels`: level l + 1 halves both sizes (at least 1) and averages the 2x2 block of level
 // l under each of its texels, the second tap clamped at the edge of odd-sized levels; sums in the order ((a + b) + (c + d)) * 0.25.
 void appendTextureWithMips(const PtrTexture& t, std::vector<float>& texels, std::vector<uint32_t>& info) {
@@ -198,20 +212,7 @@ void prepareScene(const PtrSceneDesc& desc, PreparedScene& ps, const char* cache
             if (ps.texels.size() / 4u > 0xFFFFFFF0ull) throw HipError{"textures exceed the 4 G texel limit"};
         }
         ps.materialTex.assign(static_cast<size_t>(desc.materialCount) * kMaterialTexVec4 * 4u, 0.0f);
-        for (uint32_t i = 0; i < desc.materialCount; ++i) {
-            const PtrMaterial& m = desc.materials[i];
-            float* o = &ps.materialTex[static_cast<size_t>(i) * kMaterialTexVec4 * 4u];
-            for (int r = 0; r < 12; ++r) std::memcpy(o + r * 4, m.textureTransform[r], 16);
-            for (int k = 0; k < 4; ++k) o[48 + k] = bitsToFloat(m.textureIndices0[k]);
-            o[52] = bitsToFloat(m.textureIndices1[0]);
-            o[53] = bitsToFloat(m.textureIndices1[1]);
-            const uint32_t uvSets = (std::min(m.textureUvSet0[0], 1u) << 0) | (std::min(m.textureUvSet0[1], 1u) << 1) | (std::min(m.textureUvSet0[2], 1u) << 2) |
-                                    (std::min(m.textureUvSet0[3], 1u) << 3) | (std::min(m.textureUvSet1[0], 1u) << 4) | (std::min(m.textureUvSet1[1], 1u) << 5);
-            o[54] = bitsToFloat(uvSets);
-            o[55] = bitsToFloat(m.materialFlags);
-            std::memcpy(o + 56, m.pbrParams, 16);
-            std::memcpy(o + 60, m.pbrExtras, 16);
-        }
+        for (uint32_t i = 0; i < desc.materialCount; ++i) materialTexRow(desc.materials[i], &ps.materialTex[static_cast<size_t>(i) * kMaterialTexVec4 * 4u]);
     }
     ps.seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     ps.shadingSeconds = ps.seconds - ps.geometrySeconds;
