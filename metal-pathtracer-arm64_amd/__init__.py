@@ -1179,18 +1179,11 @@ class DeviceScene:
 
     def appearance_arrays(self, names=None) -> dict:
         """ptr_debug_appearance_arrays: the named arrays (all of APPEARANCE_ARRAYS by default) as raw words; "scalars" as a dict."""
-        lib = load_library()
+        probe = load_library().ptr_debug_appearance_arrays
         out = {}
         for name in (names or APPEARANCE_ARRAYS):
             which, dtype, shape = APPEARANCE_ARRAYS[name]
-            size = C.c_uint64(0)
-            if lib.ptr_debug_appearance_arrays(self._h, which, None, 0, C.byref(size)) != 0:
-                raise PtrError("ptr_debug_appearance_arrays(%s) failed" % name)
-            buf = np.zeros(size.value // np.dtype(dtype).itemsize, dtype)
-            rc = lib.ptr_debug_appearance_arrays(self._h, which, buf.ctypes.data_as(C.c_void_p), buf.nbytes, C.byref(size))
-            if rc != 0:
-                raise PtrError("ptr_debug_appearance_arrays(%s) failed (%d)" % (name, rc))
-            out[name] = buf.reshape((-1,) + shape)
+            out[name] = _sized_array(lambda o, cap, size: probe(self._h, which, o, cap, size), dtype, "ptr_debug_appearance_arrays(%s)" % name).reshape((-1,) + shape)
         if "scalars" in out:
             out["scalars"] = dict(zip(APPEARANCE_SCALARS, (int(v) for v in out["scalars"])))
         return out
@@ -1214,35 +1207,26 @@ class DeviceScene:
     def rebuild_arrays(self, names=None) -> dict:
         """ptr_debug_rebuild_arrays: the schedule, level offsets, wide-source table, leaf table and SceneView pointers of a dynamic scene as
         it is now; "info" as a dict."""
-        lib = load_library()
+        probe = load_library().ptr_debug_rebuild_arrays
         out = {}
         for name in (names or REBUILD_ARRAYS):
             which, dtype, shape = REBUILD_ARRAYS[name]
-            size = C.c_uint64(0)
-            if lib.ptr_debug_rebuild_arrays(self._h, which, None, 0, C.byref(size)) != 0:
-                raise PtrError("ptr_debug_rebuild_arrays(%s) failed" % name)
-            buf = np.zeros(size.value // np.dtype(dtype).itemsize, dtype)
-            if lib.ptr_debug_rebuild_arrays(self._h, which, buf.ctypes.data_as(C.c_void_p), buf.nbytes, C.byref(size)) != 0:
-                raise PtrError("ptr_debug_rebuild_arrays(%s) failed" % name)
-            out[name] = buf.reshape((-1,) + shape)
+
+            def ask(o, cap, size):   # (this probe's failures carry no code)
+                if probe(self._h, which, o, cap, size) != 0:
+                    raise PtrError("ptr_debug_rebuild_arrays(%s) failed" % name)
+            out[name] = _sized_array(ask, dtype).reshape((-1,) + shape)
         if "info" in out:
             out["info"] = dict(zip(REBUILD_ARRAY_INFO, (int(v) for v in out["info"])))
         return out
 
     def arrays(self, names=None) -> dict:
         """ptr_debug_scene_arrays: the named device arrays (all of SCENE_ARRAYS by default) as numpy arrays."""
-        lib = load_library()
+        probe = load_library().ptr_debug_scene_arrays
         out = {}
         for name in (names or SCENE_ARRAYS):
             which, dtype, shape = SCENE_ARRAYS[name]
-            size = C.c_uint64(0)
-            if lib.ptr_debug_scene_arrays(self._h, which, None, 0, C.byref(size)) != 0:
-                raise PtrError("ptr_debug_scene_arrays(%s) failed" % name)
-            buf = np.zeros(size.value // np.dtype(dtype).itemsize, dtype)
-            rc = lib.ptr_debug_scene_arrays(self._h, which, buf.ctypes.data_as(C.c_void_p), buf.nbytes, C.byref(size))
-            if rc != 0:
-                raise PtrError("ptr_debug_scene_arrays(%s) failed (%d)" % (name, rc))
-            out[name] = buf.reshape((-1,) + shape) if name != "grid" else buf.reshape(2, 3)
+            out[name] = _sized_array(lambda o, cap, size: probe(self._h, which, o, cap, size), dtype, "ptr_debug_scene_arrays(%s)" % name).reshape((-1,) + shape)
         return out
 
     def timings(self) -> dict:
@@ -2477,17 +2461,29 @@ def debug_vertex_adjacency(desc: PtrSceneDesc, mesh: int) -> Tuple[np.ndarray, n
     return buf[:n], buf[n:]
 
 
+def _sized_array(call, dtype, what=None) -> np.ndarray:
+    """What every probe that writes into a caller's buffer is asked twice: call(None, 0, size_ref) for the size in bytes, then
+    call(out, cap_bytes, size_ref) with a buffer of that size.  Returns the flat array of `dtype`.  `call` raises on a failure itself
+    or, with `what`, returns the probe's code: a code other than 0 raises "<what> failed", with the code when it is the call that fills."""
+    size = C.c_uint64(0)
+    rc = call(None, 0, C.byref(size))
+    if what and rc != 0:
+        raise PtrError("%s failed" % what)
+    buf = np.zeros(size.value // np.dtype(dtype).itemsize, dtype)
+    rc = call(buf.ctypes.data_as(C.c_void_p), buf.nbytes, C.byref(size))
+    if what and rc != 0:
+        raise PtrError("%s failed (%d)" % (what, rc))
+    return buf
+
+
 def debug_dynamic_tables(desc: PtrSceneDesc, names=None) -> dict:
     """ptr_debug_dynamic_tables (host only): the tables ptr_scene_upload_dynamic prepares for `desc` as numpy arrays; "info" as a dict."""
     lib = load_library()
     out = {}
     for name in (names or DYNAMIC_TABLES):
         which, dtype, shape = DYNAMIC_TABLES[name]
-        size = C.c_uint64(0)
         err = _err_buf()
-        _check(lib.ptr_debug_dynamic_tables(C.byref(desc), which, None, 0, C.byref(size), err, len(err)), err)
-        buf = np.zeros(size.value // np.dtype(dtype).itemsize, dtype)
-        _check(lib.ptr_debug_dynamic_tables(C.byref(desc), which, buf.ctypes.data_as(C.c_void_p), buf.nbytes, C.byref(size), err, len(err)), err)
+        buf = _sized_array(lambda o, cap, size: _check(lib.ptr_debug_dynamic_tables(C.byref(desc), which, o, cap, size, err, len(err)), err), dtype)
         out[name] = buf.reshape(2, 3) if name == "grid" else buf.reshape((-1,) + shape)
     if "info" in out:
         out["info"] = dict(zip(DYNAMIC_TABLE_INFO, (int(v) for v in out["info"])))
@@ -2502,11 +2498,8 @@ def debug_rebuild_tables(nodes: np.ndarray, names=None) -> dict:
     out = {}
     for name in (names or [n for n in REBUILD_TABLES if n != "depthCheck"]):
         which, dtype, shape = REBUILD_TABLES[name]
-        size = C.c_uint64(0)
         err = _err_buf()
-        _check(lib.ptr_debug_rebuild_tables(_fptr(nodes), len(nodes), which, None, 0, C.byref(size), err, len(err)), err)
-        buf = np.zeros(size.value // np.dtype(dtype).itemsize, dtype)
-        _check(lib.ptr_debug_rebuild_tables(_fptr(nodes), len(nodes), which, buf.ctypes.data_as(C.c_void_p), buf.nbytes, C.byref(size), err, len(err)), err)
+        buf = _sized_array(lambda o, cap, size: _check(lib.ptr_debug_rebuild_tables(_fptr(nodes), len(nodes), which, o, cap, size, err, len(err)), err), dtype)
         if name == "grid":
             out[name] = buf.reshape(2, 3)
         elif name in ("sah", "wideDepth", "depthCheck"):

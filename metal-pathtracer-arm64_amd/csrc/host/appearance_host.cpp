@@ -4,6 +4,8 @@
 #include <cmath>
 #include <cstring>
 
+#include "index_rule.h"
+
 namespace ptr {
 namespace {
 
@@ -29,10 +31,8 @@ std::string MaterialListProblem(const uint32_t* indices, const PtrMaterial* mate
     std::vector<uint8_t> named(materialCount, 0);
     for (uint32_t i = 0; i < count; ++i) {
         const uint32_t index = indices[i];
-        if (index >= materialCount) {
-            return "material index " + std::to_string(index) + " out of range (the scene has " + std::to_string(materialCount) + " materials)";
-        }
-        if (named[index]++) return "material index " + std::to_string(index) + " named twice";
+        const std::string bad = NamedIndexProblem("material", "materials", index, named);
+        if (!bad.empty()) return bad;
         const PtrMaterial& m = materials[i];
         const std::string name = "material " + std::to_string(index);
         if (!materialFinite(m)) return name + " has a non-finite entry";
@@ -64,13 +64,12 @@ void BuildShadeKeyTable(const float* rows, uint32_t materialCount, std::vector<u
     for (uint32_t i = 0; i < materialCount; ++i) keys[i] = static_cast<uint8_t>(ShadeKeyOfType(CompactMaterialType(rows + static_cast<size_t>(i) * kCompactMaterialFloats)));
 }
 
-void DeriveRectLights(const PtrRect* rects, uint32_t rectCount, const uint32_t* rectTriLeaf, const float* materialRows, uint32_t materialCount,
-                      RectLightTable& out) {
-    out = RectLightTable{};
+RectLightTable DeriveRectLights(const PtrRect* rects, uint32_t rectCount, const uint32_t* rectTriLeaf, const float* materialRows, uint32_t materialCount) {
+    RectLightTable out;
     out.lightIndexByRect.assign(rectCount, -1);
     out.rectEmission.assign(static_cast<size_t>(rectCount) * 3u, 0.0f);
     out.rectShadeKey.assign(rectCount, 0u);
-    if (rectCount == 0u || materialCount == 0u) return;
+    if (rectCount == 0u || materialCount == 0u) return out;
     for (uint32_t i = 0; i < rectCount; ++i) {
         const PtrRect& r = rects[i];
         const float* m = materialRows + static_cast<size_t>(std::min(r.materialTwoSided[0], materialCount - 1u)) * kCompactMaterialFloats;
@@ -91,6 +90,7 @@ void DeriveRectLights(const PtrRect* rects, uint32_t rectCount, const uint32_t* 
         std::memcpy(&out.rectEmission[static_cast<size_t>(i) * 3u], e, 12);
         out.lightIndexByRect[i] = static_cast<int32_t>(out.lightCount++);
     }
+    return out;
 }
 
 void MipChainLevels(uint32_t width, uint32_t height, std::vector<MipLevel>& levels) {

@@ -29,9 +29,10 @@ void MaterialTableFacts(const float* rows, uint32_t materialCount, uint32_t& typ
 // one byte per material: its shade key (k_app_rekey's table)
 void BuildShadeKeyTable(const float* rows, uint32_t materialCount, std::vector<uint8_t>& keys);
 
-// The rectangle-light half of the upload (buildRectLights) from what a scene with PTR_DYNAMIC_PRIMITIVES keeps: the rectangles' records,
-// the leaf places of their triangles (2 per rectangle, 0xFFFFFFFF: not in the geometry) and the compact material rows.  A light's own
-// two triangle rows are written as the geometry writes them (WriteRectTriangles under the shade key of the rectangle's material).
+// The rectangle-light table, for the upload (prepareScene) and for ptr_scene_set_materials alike: DiffuseLight rectangles with non-zero
+// emission, from the rectangles' records, the leaf places of their triangles (2 per rectangle, 0xFFFFFFFF: not in the geometry) and the
+// compact material rows (a material index past the table reads its last row).  A light's own two triangle rows are written as the
+// geometry writes them (WriteRectTriangles under the shade key of the rectangle's material), so they are the leaf-order records.
 struct RectLightTable {
     std::vector<float> lights;               // kRectLightFloats per light
     std::vector<int32_t> lightIndexByRect;   // -1: no light
@@ -40,8 +41,7 @@ struct RectLightTable {
     uint32_t lightCount = 0;
     bool lightsHaveTriangles = true;
 };
-void DeriveRectLights(const PtrRect* rects, uint32_t rectCount, const uint32_t* rectTriLeaf, const float* materialRows, uint32_t materialCount,
-                      RectLightTable& out);
+RectLightTable DeriveRectLights(const PtrRect* rects, uint32_t rectCount, const uint32_t* rectTriLeaf, const float* materialRows, uint32_t materialCount);
 
 // The sizes of the levels of a mip chain over a width x height image, level 0 first: each size halves down to at least 1, at most 16 levels.
 struct MipLevel {

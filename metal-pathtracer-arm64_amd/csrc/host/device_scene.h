@@ -1,6 +1,6 @@
-// What the two hipcc-compiled host files share (hip_backend.cpp: scene upload and the render loop; debug_probes.cpp: the test-only entry
-// points of include/ptr_debug.h): HIP error handling, device buffers, the device scene, and the few backend functions the probes call.
-// Internal: not part of the C-ABI.
+// What the hipcc-compiled host files share (hip_backend.cpp: scene upload and the render loop; debug_probes.cpp: the test-only entry
+// points of include/ptr_debug.h; the update calls of dynamic_host.h): HIP error handling, device and pinned buffers, the device scene
+// with the host-side records its upload fills, and the few backend functions the probes call.  Internal: not part of the C-ABI.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -16,6 +16,7 @@
 #include "../kernels/device_types.h"
 #include "../kernels/dynamic.h"
 #include "../kernels/launch.h"
+#include "appearance_host.h"
 #include "background_cull.h"
 #include "env_importance_sampler.h"
 #include "geometry_cache.h"
@@ -81,6 +82,28 @@ struct DeviceBuffer {
     }
     void download(T* dst, size_t n) const {   // blocking, like upload
         if (n) HIP_CHECK(hipMemcpy(dst, ptr, n * sizeof(T), hipMemcpyDeviceToHost));
+    }
+};
+
+// A pinned host buffer, grown on demand and kept until its owner goes: what the update calls stage through.  flags: hipHostMalloc's.
+struct PinnedBuffer {
+    void* ptr = nullptr;
+    size_t bytes = 0;
+    unsigned flags = hipHostMallocDefault;
+    explicit PinnedBuffer(unsigned f = hipHostMallocDefault) : flags(f) {}
+    PinnedBuffer(const PinnedBuffer&) = delete;
+    PinnedBuffer& operator=(const PinnedBuffer&) = delete;
+    ~PinnedBuffer() {
+        if (ptr) (void)hipHostFree(ptr);
+    }
+    void* pinnedFor(size_t n) {
+        if (n > bytes) {
+            if (ptr) (void)hipHostFree(ptr);
+            ptr = nullptr, bytes = 0;
+            HIP_CHECK(hipHostMalloc(&ptr, n, flags));
+            bytes = n;
+        }
+        return ptr;
     }
 };
 
@@ -170,53 +193,35 @@ struct DynamicScene {
     std::unique_ptr<RebuildState> rebuild;
     // staging of the update calls, grown on demand and kept: a pinned host buffer and its device twin
     DeviceBuffer<float4> staging;
-    void* pinned = nullptr;
-    size_t pinnedBytes = 0;
-    void* pinnedFor(size_t bytes) {
-        if (bytes > pinnedBytes) {
-            if (pinned) (void)hipHostFree(pinned);
-            pinned = nullptr, pinnedBytes = 0;
-            HIP_CHECK(hipHostMalloc(&pinned, bytes, hipHostMallocDefault));
-            pinnedBytes = bytes;
-        }
-        return pinned;
-    }
+    PinnedBuffer pinned;
     ~DynamicScene() {
         for (hipEvent_t e : events) {
             if (e) (void)hipEventDestroy(e);
         }
         if (rootBox) (void)hipHostFree(rootBox);
-        if (pinned) (void)hipHostFree(pinned);
     }
 };
 
-// What the appearance calls (include/ptr_appearance.h, appearance.cpp) keep, made at the first of them: host mirrors of the arrays their
-// rules read (taken from the device, so a static scene needs nothing from its upload), and the scratch of their kernels.
-struct AppearanceState {
-    std::vector<float> materialRows;       // ds.materials
+// The host-side records of a scene's appearance, the ones the check halves of include/ptr_appearance.h read: filled by uploadScene from
+// the preparation and the description (fillAppearanceRecords, no device call), changed by an accepted call; empty without an upload.
+struct AppearanceRecords {
+    std::vector<float> materialRows;       // the compact rows of ds.materials
     std::vector<uint32_t> rectMaterial;    // per rectangle: its material index as the description gave it
-    std::vector<uint32_t> texInfo;         // ds.texInfo
+    std::vector<uint32_t> texInfo;         // the records of ds.texInfo
+};
+
+// The scratch of the appearance calls' kernels (appearance.cpp), made at the first of them.
+struct AppearanceState {
     DeviceBuffer<uint8_t> keys;            // k_app_rekey's table
     DeviceBuffer<uint32_t> words;          // [0] rows rekeyed, [1..] flag words of the finiteness check
     DeviceBuffer<float4> checkRows;
     DeviceBuffer<float> envWeight, envRowWeight, envCell, envTotal;
     hipEvent_t events[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    void* pinned = nullptr;
-    size_t pinnedBytes = 0;
-    void* pinnedFor(size_t bytes) {
-        if (bytes > pinnedBytes) {
-            if (pinned) (void)hipHostFree(pinned);
-            pinned = nullptr, pinnedBytes = 0;
-            HIP_CHECK(hipHostMalloc(&pinned, bytes, hipHostMallocDefault));
-            pinnedBytes = bytes;
-        }
-        return pinned;
-    }
+    PinnedBuffer pinned, staged;           // the rows and landing places a run lays out (small); the host pixels of a textures or environment call
     ~AppearanceState() {
         for (hipEvent_t e : events) {
             if (e) (void)hipEventDestroy(e);
         }
-        if (pinned) (void)hipHostFree(pinned);
     }
 };
 
@@ -238,7 +243,8 @@ struct PtrDeviceScene {
     uint32_t envMipLevels = 0;   // 0: not built
     ptrk::SceneView view{};
     std::unique_ptr<ptrhost::DynamicScene> dynamic;   // ptr_scene_upload_dynamic only
-    std::unique_ptr<ptrhost::AppearanceState> appearance;   // include/ptr_appearance.h: made by the first call
+    ptrhost::AppearanceRecords appearanceRecords;           // include/ptr_appearance.h: what the scene holds, from its upload
+    std::unique_ptr<ptrhost::AppearanceState> appearance;   // ... and the kernels' scratch, made by the first call
     uint64_t info[8] = {0};
     double uploadSeconds = 0.0;
     double timings[4] = {0.0, 0.0, 0.0, 0.0};   // geometry preparation (or cache read), shading tables, copies to the device, 1 = geometry came from a cache
@@ -353,10 +359,8 @@ void partitionPixels(uint32_t width, uint32_t height, uint32_t part, uint32_t pa
 // and uploaded to every device a frame is rendered on.
 struct PreparedScene {
     ptr::PreparedGeometry pg;   // BVH, leaf-order arrays, four-wide nodes, node format: what a geometry cache file holds
-    std::vector<float> mats, lights;
-    std::vector<int32_t> lightIndexByRect;
-    uint32_t lightCount = 0;
-    bool lightsHaveTriangles = true;   // every rectangle light found its two triangles in the geometry (always, unless degenerate)
+    std::vector<float> mats;
+    ptr::RectLightTable rectLights;    // (lightsHaveTriangles: every light found its two triangles in the geometry - always, unless degenerate)
     bool hasRandomWalkMaterial = false;
     ptr::EnvImportanceDistribution envDist;
     bool hasEnvDist = false;
@@ -384,9 +388,9 @@ void uploadScene(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceSce
 void uploadDynamicTables(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceScene& ds);
 // the root box of the tree from node 0 (dynamic.cpp): the union of its children that exist
 bool rootBoxOf(const float4 row[4], float lo[3], float hi[3]);
-// the rectangle-light half of prepareScene: the light table of `desc` over the geometry `geo`
-void buildRectLights(const PtrSceneDesc& desc, const ptr::SceneGeometry& geo, std::vector<float>& lights, std::vector<int32_t>& lightIndexByRect,
-                     uint32_t& lightCount, bool& lightsHaveTriangles);
+// the rectangle-light table of `desc` over the geometry `geo`, for a caller without the compact material rows (prepareScene has them):
+// ptr::DeriveRectLights on rows made here
+ptr::RectLightTable rectLightsOf(const PtrSceneDesc& desc, const ptr::SceneGeometry& geo);
 
 // What an entry point refuses before any device call: returns the C-ABI's code with the message in `err`.
 inline int refuse(char* err, size_t cap, const std::string& message) {
@@ -397,6 +401,19 @@ inline int nullArgument(const char* who, char* err, size_t cap) { return refuse(
 inline int noDevice(const char* who, char* err, size_t cap) {
     setErr(err, cap, std::string(who) + ": no HIP device (the HIP path has no CPU fallback)");
     return 2;
+}
+// The tail of the array probes (ptr_debug_scene_arrays, ptr_debug_rebuild_arrays, ptr_debug_appearance_arrays) once the selector has named
+// `bytes` at `src`, on the host or in `device`'s memory: the size written, the capacity tested, the copy.  0, 2 (too small), 3 (failed copy).
+inline int probeArrayTail(int device, const void* src, bool host, uint64_t bytes, void* out, uint64_t cap_bytes, uint64_t* size_out) {
+    *size_out = bytes;
+    if (!out || bytes == 0u) return 0;
+    if (cap_bytes < bytes) return 2;
+    if (host) {
+        std::memcpy(out, src, bytes);
+        return 0;
+    }
+    if (hipSetDevice(device) != hipSuccess || hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) return 3;
+    return 0;
 }
 // Pixels, list entries and per-sample accumulators are 32-bit indices with room for a block of threads past the last one.
 constexpr uint64_t kIndexLimit = 0xFFFF0000ull;

@@ -34,25 +34,20 @@ ptrk::DynMeshRow meshRowOf(const ptr::MeshBake& bake, bool hasTangents) {
     return r;
 }
 
-void fillPrimitiveRecords(const PtrSceneDesc& desc, const ptr::SceneGeometry& geo, const ptr::DynamicTables& t, const std::vector<int32_t>& lightIndexByRect,
+void fillPrimitiveRecords(const PtrSceneDesc& desc, const ptr::SceneGeometry& geo, const ptr::DynamicTables& t, const ptr::RectLightTable& lights,
                           PrimitiveRecords& out) {
     out = PrimitiveRecords{};
     out.rectTriLeaf = geo.rectTriLeaf;
     out.sphereLeaf = t.sphereLeaf;
     out.rectShadeKey = t.rectShadeKey;
-    out.lightIndexByRect = lightIndexByRect;
-    out.rectEmission.assign(static_cast<size_t>(desc.rectCount) * 3u, 0.0f);
-    for (uint32_t i = 0; i < desc.rectCount; ++i) {
-        if (lightIndexByRect[i] < 0) continue;
-        const PtrMaterial& m = desc.materials[std::min(desc.rects[i].materialTwoSided[0], desc.materialCount - 1u)];
-        std::memcpy(&out.rectEmission[static_cast<size_t>(i) * 3u], m.emission, 12);
-    }
+    out.lightIndexByRect = lights.lightIndexByRect;
+    out.rectEmission = lights.rectEmission;
     out.rects.assign(desc.rects, desc.rects + desc.rectCount);
     out.spheres.assign(desc.spheres, desc.spheres + desc.sphereCount);
     out.triCount = geo.triCount;
 }
 
-void fillDynamicRecords(const PtrSceneDesc& desc, const ptr::PreparedGeometry& pg, const ptr::DynamicTables& t, const std::vector<int32_t>& lightIndexByRect,
+void fillDynamicRecords(const PtrSceneDesc& desc, const ptr::PreparedGeometry& pg, const ptr::DynamicTables& t, const ptr::RectLightTable& lights,
                         DynamicScene& dyn) {
     const ptr::FlatBvh& bvh = pg.geo.bvh;
     dyn.meshTriOffsets = t.meshTriOffsets;
@@ -71,7 +66,7 @@ void fillDynamicRecords(const PtrSceneDesc& desc, const ptr::PreparedGeometry& p
         dyn.meshTangentsGiven = t.meshTangentsGiven;
     }
     if (t.flags & PTR_DYNAMIC_VERTEX_NORMALS) dyn.adjBase = t.adjBase;
-    if (t.flags & PTR_DYNAMIC_PRIMITIVES) fillPrimitiveRecords(desc, pg.geo, t, lightIndexByRect, dyn.prims);
+    if (t.flags & PTR_DYNAMIC_PRIMITIVES) fillPrimitiveRecords(desc, pg.geo, t, lights, dyn.prims);
     ptr::BuildLeafTable(bvh.nodes.data(), bvh.nodeCount, dyn.leafTable);   // include/ptr_rebuild.h, step 1
 }
 
@@ -79,7 +74,7 @@ void uploadDynamicTables(const PtrSceneDesc& desc, const PreparedScene& ps, PtrD
     const ptr::DynamicTables& t = ps.dyn;
     const ptr::FlatBvh& bvh = ps.pg.geo.bvh;
     auto dyn = std::make_unique<DynamicScene>();
-    fillDynamicRecords(desc, ps.pg, t, ps.lightIndexByRect, *dyn);
+    fillDynamicRecords(desc, ps.pg, t, ps.rectLights, *dyn);
     dyn->objPos.upload(reinterpret_cast<const float4*>(t.objPos.data()), t.objPos.size() / 4);
     dyn->objNrm.upload(reinterpret_cast<const float4*>(t.objNrm.data()), t.objNrm.size() / 4);
     dyn->textured = ds.view.triUv != nullptr;
@@ -133,8 +128,9 @@ DynBakeArrays bakeArrays(PtrDeviceScene& ds) {
 // (defined below the entry points)
 void finishUpdate(PtrDeviceScene& ds, hipStream_t st, std::chrono::steady_clock::time_point t0, uint64_t moved, PtrUpdateInfo* info);
 // The host half of a sphere's / a rectangle's move: the new record into `prims`, its rows appended to `out`.  "" or what is wrong with it.
-std::string sphereRows(PrimitiveRecords& prims, const PtrSphereUpdate& u, ScatterRows& out);
-std::string rectRows(PrimitiveRecords& prims, const PtrRectUpdate& u, ScatterRows& out);
+// named: per sphere / rectangle of the scene, whether the list has named it so far.
+std::string sphereRows(PrimitiveRecords& prims, const PtrSphereUpdate& u, std::vector<uint8_t>& named, ScatterRows& out);
+std::string rectRows(PrimitiveRecords& prims, const PtrRectUpdate& u, std::vector<uint8_t>& named, ScatterRows& out);
 
 std::string matrixProblem(const float m[16], const ptr::MeshBake& bake) {
     for (int i = 0; i < 16; ++i) {
@@ -148,15 +144,12 @@ std::string matrixProblem(const float m[16], const ptr::MeshBake& bake) {
 }
 
 // What both vertex calls refuse about entry `mv` of their list (PtrMeshVertices and PtrMeshVerticesDevice have the same members): "" or the
-// cause.  named: per mesh of the scene, how often the list has named it so far.  used: the mesh has triangles.
+// cause.  named: per mesh of the scene, whether the list has named it so far.  used: the mesh has triangles.
 template <typename V>
 std::string namedMeshProblem(const DynamicScene& dyn, const V& mv, std::vector<uint8_t>& named, bool normalsMayBeNull, const char* nullNormalsHint, bool& used) {
     used = false;
-    const uint32_t meshCount = static_cast<uint32_t>(named.size());
-    if (mv.meshIndex >= meshCount) {
-        return "mesh index " + std::to_string(mv.meshIndex) + " out of range (the scene has " + std::to_string(meshCount) + " meshes)";
-    }
-    if (named[mv.meshIndex]++) return "mesh index " + std::to_string(mv.meshIndex) + " named twice";
+    const std::string bad = ptr::NamedIndexProblem("mesh", "meshes", mv.meshIndex, named);
+    if (!bad.empty()) return bad;
     if (dyn.meshTriOffsets[mv.meshIndex + 1u] == dyn.meshTriOffsets[mv.meshIndex]) return "";   // no triangles: nothing to change
     const std::string mesh = "mesh " + std::to_string(mv.meshIndex);
     if (mv.vertexCount != dyn.meshVertexCount[mv.meshIndex]) {
@@ -194,24 +187,13 @@ void gatherBakeFinish(PtrDeviceScene& ds, const std::vector<E>& entry, ArraysOf&
 const char* const kNotDynamic = "the scene is not dynamic (upload it with ptr_scene_upload_dynamic)";
 const char* const kNotDeformable = "the scene is not deformable (upload it with ptr_scene_upload_dynamic_ex and PTR_DYNAMIC_DEFORMABLE)";
 
-// k_dyn_check_finite over `rows`, whose row r is u.checked[index[r]]: the rows and zeroed flag words to the device, the words back, and a
-// set bit ends the call - nothing the renderer reads has been written yet.
+// firstNonFinite over `rows`, whose row r is u.checked[index[r]]: a flagged row ends the call - nothing the renderer reads has been written yet
 void finiteCheck(const char* who, const DeviceVerticesUpdate& u, const std::vector<DynCheckRow>& rows, const std::vector<size_t>& index, DynCheckRow* dRows,
                  uint32_t* dFlags, uint32_t* pinnedFlags, hipStream_t st) {
-    const size_t words = (rows.size() + 31u) / 32u;
-    uint64_t largest = 0;
-    for (const DynCheckRow& r : rows) largest = std::max<uint64_t>(largest, r.count);
-    HIP_CHECK(hipMemcpyAsync(dRows, rows.data(), rows.size() * sizeof(DynCheckRow), hipMemcpyHostToDevice, st));
-    HIP_CHECK(hipMemsetAsync(dFlags, 0, words * sizeof(uint32_t), st));
-    launchDynCheckFinite(dRows, static_cast<uint32_t>(rows.size()), largest, dFlags, st);
-    HIP_CHECK(hipMemcpyAsync(pinnedFlags, dFlags, words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    for (size_t r = 0; r < rows.size(); ++r) {
-        if (pinnedFlags[r >> 5] >> (r & 31u) & 1u) {
-            const DeviceVerticesUpdate::Checked& c = u.checked[index[r]];
-            throw Refused{std::string(who) + ": mesh " + std::to_string(u.entry[c.entry].mesh) + " has a non-finite " + c.what + " component"};
-        }
-    }
+    const int bad = firstNonFinite(rows.data(), rows.size(), dRows, dFlags, pinnedFlags, st);
+    if (bad < 0) return;
+    const DeviceVerticesUpdate::Checked& c = u.checked[index[static_cast<size_t>(bad)]];
+    throw Refused{std::string(who) + ": mesh " + std::to_string(u.entry[c.entry].mesh) + " has a non-finite " + c.what + " component"};
 }
 
 }  // namespace
@@ -243,6 +225,21 @@ std::string devicePointerProblem(const void* p, size_t bytes, int device) {
     return "";
 }
 
+int firstNonFinite(const DynCheckRow* rows, size_t n, DynCheckRow* dRows, uint32_t* dFlags, uint32_t* pinnedFlags, hipStream_t st) {
+    const size_t words = (n + 31u) / 32u;
+    uint64_t largest = 0;
+    for (size_t r = 0; r < n; ++r) largest = std::max<uint64_t>(largest, rows[r].count);
+    HIP_CHECK(hipMemcpyAsync(dRows, rows, n * sizeof(DynCheckRow), hipMemcpyHostToDevice, st));
+    HIP_CHECK(hipMemsetAsync(dFlags, 0, words * sizeof(uint32_t), st));
+    launchDynCheckFinite(dRows, static_cast<uint32_t>(n), largest, dFlags, st);
+    HIP_CHECK(hipMemcpyAsync(pinnedFlags, dFlags, words * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    for (size_t r = 0; r < n; ++r) {
+        if (pinnedFlags[r >> 5] >> (r & 31u) & 1u) return static_cast<int>(r);
+    }
+    return -1;
+}
+
 std::string listProblem(const void* list, uint32_t count, const char* nullWords) {
     if (!list) return nullWords;
     if (count == 0u) return "count is 0";
@@ -259,10 +256,8 @@ std::string checkMeshTransforms(const PtrDeviceScene* scene, const PtrMeshTransf
     std::vector<uint8_t> named(meshCount, 0);
     for (uint32_t i = 0; i < count; ++i) {
         const PtrMeshTransform& t = transforms[i];
-        if (t.meshIndex >= meshCount) {
-            return "mesh index " + std::to_string(t.meshIndex) + " out of range (the scene has " + std::to_string(meshCount) + " meshes)";
-        }
-        if (named[t.meshIndex]++) return "mesh index " + std::to_string(t.meshIndex) + " named twice";
+        const std::string bad = ptr::NamedIndexProblem("mesh", "meshes", t.meshIndex, named);
+        if (!bad.empty()) return bad;
         ptr::MeshBake bake;
         ptr::ComputeMeshBake(t.localToWorld, bake);
         const std::string problem = matrixProblem(t.localToWorld, bake);
@@ -322,26 +317,18 @@ std::string checkMeshVertices(const PtrDeviceScene* scene, const PtrMeshVertices
 }
 
 std::string stageMeshVertices(const PtrMeshVertices* meshes, const VerticesUpdate& u, float* pinned) {
-    auto stage = [&](const float* src, size_t n, float* dst) {
-        bool finite = true;
-        for (size_t k = 0; k < n; ++k) {
-            finite = finite && std::isfinite(src[k]);
-            dst[k] = src[k];
-        }
-        return finite;
-    };
     for (uint32_t i = 0; i < u.entry.size(); ++i) {
         const PtrMeshVertices& mv = meshes[i];
         const VerticesUpdate::Entry& s = u.entry[i];
         if (!s.used) continue;
         const size_t n = mv.vertexCount;
         const char* bad = nullptr;
-        if (!stage(mv.positions, n * 3u, pinned + s.positions)) bad = "position";
-        else if (!stage(mv.normals, n * 3u, pinned + s.normals)) bad = "normal";
+        if (!stageFinite(mv.positions, n * 3u, pinned + s.positions)) bad = "position";
+        else if (!stageFinite(mv.normals, n * 3u, pinned + s.normals)) bad = "normal";
         else if (mv.tangents) {
             std::vector<float> dropped;
             if (!s.hasTangents) dropped.resize(n * 4u);
-            if (!stage(mv.tangents, n * 4u, s.hasTangents ? pinned + s.tangents : dropped.data())) bad = "tangent";
+            if (!stageFinite(mv.tangents, n * 4u, s.hasTangents ? pinned + s.tangents : dropped.data())) bad = "tangent";
         }
         if (bad) return "mesh " + std::to_string(mv.meshIndex) + " has a non-finite " + bad + " component";
     }
@@ -451,7 +438,7 @@ void runMeshVerticesDevice(const char* who, PtrDeviceScene& ds, const DeviceVert
         const size_t words = (checks.size() + 31u) / 32u;
         dyn.checkFlags.ensure(words);
         finiteCheck(who, u, checks, index, reinterpret_cast<DynCheckRow*>(dyn.meshTable.ptr + count * kDynMeshVec4), dyn.checkFlags.ptr,
-                    static_cast<uint32_t*>(dyn.pinnedFor(words * sizeof(uint32_t))), st);
+                    static_cast<uint32_t*>(dyn.pinned.pinnedFor(words * sizeof(uint32_t))), st);
     }
     gatherBakeFinish(ds, u.entry,
                      [&](const DeviceVerticesUpdate::Entry& e) {
@@ -461,22 +448,6 @@ void runMeshVerticesDevice(const char* who, PtrDeviceScene& ds, const DeviceVert
 }
 
 }  // namespace ptrhost
-
-namespace {
-
-// What every update entry point of this file is: a null scene refused, the call's rules (check), the device work (run)
-template <typename Check, typename Run>
-int updateCall(const char* who, PtrDeviceScene* scene, char* err, size_t err_cap, Check&& check, Run&& run) {
-    if (!scene) return nullArgument(who, err, err_cap);
-    try {
-        const std::string problem = check();
-        if (!problem.empty()) return refuse(err, err_cap, std::string(who) + ": " + problem);
-    }
-    PTR_CATCH_ALL(err, err_cap)
-    return deviceCall(who, scene, true, err, err_cap, run);
-}
-
-}  // namespace
 
 extern "C" {
 
@@ -499,7 +470,7 @@ int ptr_scene_set_mesh_vertices(PtrDeviceScene* scene, const PtrMeshVertices* me
                           if (!problem.empty()) return problem;
                           // staging: every array into the scene's pinned buffer, each component looked at on the way
                           HIP_CHECK(hipSetDevice(scene->device));
-                          float* staged = static_cast<float*>(scene->dynamic->pinnedFor(std::max<size_t>(u.floats, 4u) * sizeof(float)));
+                          float* staged = static_cast<float*>(scene->dynamic->pinned.pinnedFor(std::max<size_t>(u.floats, 4u) * sizeof(float)));
                           pinned = staged;
                           return stageMeshVertices(meshes, u, staged);
                       },
@@ -539,16 +510,12 @@ int ptr_debug_dynamic_update_rows(const PtrSceneDesc* scene, uint32_t kind, cons
         ptr::DynamicTables t;
         t.flags = PTR_DYNAMIC_DEFORMABLE | PTR_DYNAMIC_PRIMITIVES;
         prepareGeometry(*scene, pg, &t);
-        std::vector<float> lights;
-        std::vector<int32_t> lightIndexByRect;
-        uint32_t lightCount = 0;
-        bool haveTriangles = true;
-        buildRectLights(*scene, pg.geo, lights, lightIndexByRect, lightCount, haveTriangles);
         PrimitiveRecords prims;
-        fillPrimitiveRecords(*scene, pg.geo, t, lightIndexByRect, prims);
+        fillPrimitiveRecords(*scene, pg.geo, t, rectLightsOf(*scene, pg.geo), prims);
         ScatterRows rows;
-        const std::string problem = kind == 0u ? sphereRows(prims, *static_cast<const PtrSphereUpdate*>(update), rows)
-                                               : rectRows(prims, *static_cast<const PtrRectUpdate*>(update), rows);
+        std::vector<uint8_t> named(kind == 0u ? prims.spheres.size() : prims.rects.size(), 0);
+        const std::string problem = kind == 0u ? sphereRows(prims, *static_cast<const PtrSphereUpdate*>(update), named, rows)
+                                               : rectRows(prims, *static_cast<const PtrRectUpdate*>(update), named, rows);
         if (!problem.empty()) return refuse(err, err_cap, std::string(who) + ": " + problem);
         const uint64_t n = rows.dest.size();
         *rows_out = n;
@@ -642,11 +609,10 @@ void putBounds(ScatterRows& out, uint32_t array, size_t slot, const ptr::BuildPr
     putRow(out, array, slot * 2u + 1u, hi);
 }
 
-std::string sphereRows(PrimitiveRecords& prims, const PtrSphereUpdate& u, ScatterRows& out) {
+std::string sphereRows(PrimitiveRecords& prims, const PtrSphereUpdate& u, std::vector<uint8_t>& named, ScatterRows& out) {
     const std::string name = "sphere " + std::to_string(u.sphereIndex);
-    if (u.sphereIndex >= prims.spheres.size()) {
-        return "sphere index " + std::to_string(u.sphereIndex) + " out of range (the scene has " + std::to_string(prims.spheres.size()) + " spheres)";
-    }
+    const std::string bad = ptr::NamedIndexProblem("sphere", "spheres", u.sphereIndex, named);
+    if (!bad.empty()) return bad;
     if (!allFinite(u.centerRadius, 4)) return name + " has a non-finite entry";
     PtrSphere s = prims.spheres[u.sphereIndex];
     std::memcpy(s.centerRadius, u.centerRadius, 16);
@@ -660,11 +626,10 @@ std::string sphereRows(PrimitiveRecords& prims, const PtrSphereUpdate& u, Scatte
     return "";
 }
 
-std::string rectRows(PrimitiveRecords& prims, const PtrRectUpdate& u, ScatterRows& out) {
+std::string rectRows(PrimitiveRecords& prims, const PtrRectUpdate& u, std::vector<uint8_t>& named, ScatterRows& out) {
     const std::string name = "rectangle " + std::to_string(u.rectIndex);
-    if (u.rectIndex >= prims.rects.size()) {
-        return "rectangle index " + std::to_string(u.rectIndex) + " out of range (the scene has " + std::to_string(prims.rects.size()) + " rectangles)";
-    }
+    const std::string bad = ptr::NamedIndexProblem("rectangle", "rectangles", u.rectIndex, named);
+    if (!bad.empty()) return bad;
     if (!allFinite(u.corner, 4) || !allFinite(u.edgeU, 4) || !allFinite(u.edgeV, 4) || !allFinite(u.normalAndPlane, 4)) return name + " has a non-finite entry";
     const ptr::float3 eu{u.edgeU[0], u.edgeU[1], u.edgeU[2]}, ev{u.edgeV[0], u.edgeV[1], u.edgeV[2]};
     const ptr::float3 n{u.normalAndPlane[0], u.normalAndPlane[1], u.normalAndPlane[2]};
@@ -718,10 +683,8 @@ std::string checkPrimitives(uint32_t kind, const PtrDeviceScene* scene, const vo
     next = scene->dynamic->prims;   // the records change only when the whole call is accepted
     std::vector<uint8_t> named(kind == 0u ? next.spheres.size() : next.rects.size(), 0);
     for (uint32_t i = 0; i < count; ++i) {
-        const uint32_t index = kind == 0u ? static_cast<const PtrSphereUpdate*>(list)[i].sphereIndex : static_cast<const PtrRectUpdate*>(list)[i].rectIndex;
-        if (index < named.size() && named[index]++) return std::string(kind == 0u ? "sphere" : "rectangle") + " index " + std::to_string(index) + " named twice";
-        const std::string problem = kind == 0u ? sphereRows(next, static_cast<const PtrSphereUpdate*>(list)[i], out.rows)
-                                               : rectRows(next, static_cast<const PtrRectUpdate*>(list)[i], out.rows);
+        const std::string problem = kind == 0u ? sphereRows(next, static_cast<const PtrSphereUpdate*>(list)[i], named, out.rows)
+                                               : rectRows(next, static_cast<const PtrRectUpdate*>(list)[i], named, out.rows);
         if (!problem.empty()) return problem;
     }
     return "";
@@ -733,7 +696,7 @@ void runPrimitives(PtrDeviceScene& ds, const PrimitivesUpdate& u, hipStream_t st
     DynamicScene& dyn = *ds.dynamic;
     const ScatterRows& rows = u.rows;
     const size_t n = rows.dest.size();
-    char* pinned = static_cast<char*>(dyn.pinnedFor(std::max<size_t>(n, 1u) * 20u));
+    char* pinned = static_cast<char*>(dyn.pinned.pinnedFor(std::max<size_t>(n, 1u) * 20u));
     std::memcpy(pinned, rows.rows.data(), n * 16u);
     std::memcpy(pinned + n * 16u, rows.dest.data(), n * 4u);
     dyn.staging.ensure(n + (n + 3u) / 4u);
@@ -764,6 +727,7 @@ int ptr_debug_scene_arrays(PtrDeviceScene* scene, uint32_t which, void* out, uin
     const PtrDeviceScene& ds = *scene;
     const DynamicScene* dyn = ds.dynamic.get();
     const uint64_t tris = ds.info[2], spheres = ds.info[3], nodes = ds.info[0];
+    float grid[6];
     const void* src = nullptr;
     uint64_t bytes = 0;
     switch (which) {
@@ -779,7 +743,10 @@ int ptr_debug_scene_arrays(PtrDeviceScene* scene, uint32_t which, void* out, uin
             break;
         case PTR_SCENE_ARRAY_QNODES: src = ds.qnodes.ptr, bytes = ds.view.useQuantized ? nodes * 32u : 0u; break;
         case PTR_SCENE_ARRAY_WNODES: src = ds.wnodes.ptr, bytes = ds.view.useWide ? ds.view.wideBytes : 0u; break;
-        case PTR_SCENE_ARRAY_GRID: bytes = 24u; break;
+        case PTR_SCENE_ARRAY_GRID:
+            std::memcpy(grid, ds.view.gridOrigin, 12), std::memcpy(grid + 3, ds.view.gridCell, 12);
+            src = grid, bytes = sizeof(grid);
+            break;
         case PTR_SCENE_ARRAY_RECTS: src = ds.rects.ptr, bytes = static_cast<uint64_t>(ds.view.rectCount) * 80u; break;
         case PTR_SCENE_ARRAY_RECT_LIGHTS: src = ds.rectLights.ptr, bytes = static_cast<uint64_t>(ds.view.rectLightCount) * kRectLightVec4 * 16u; break;
         case PTR_SCENE_ARRAY_SPHERES: src = ds.spheres.ptr, bytes = spheres * 16u; break;
@@ -788,17 +755,7 @@ int ptr_debug_scene_arrays(PtrDeviceScene* scene, uint32_t which, void* out, uin
         case PTR_SCENE_ARRAY_OBJ_TAN: src = dyn ? dyn->objTan.ptr : nullptr, bytes = dyn && dyn->textured ? tris * 48u : 0u; break;
         default: return 1;
     }
-    *size_out = bytes;
-    if (!out) return 0;
-    if (cap_bytes < bytes) return 2;
-    if (bytes == 0u) return 0;
-    if (which == PTR_SCENE_ARRAY_GRID) {
-        std::memcpy(out, ds.view.gridOrigin, 12);
-        std::memcpy(static_cast<char*>(out) + 12, ds.view.gridCell, 12);
-        return 0;
-    }
-    if (hipSetDevice(ds.device) != hipSuccess || hipMemcpy(out, src, bytes, hipMemcpyDeviceToHost) != hipSuccess) return 3;
-    return 0;
+    return probeArrayTail(ds.device, src, which == PTR_SCENE_ARRAY_GRID, bytes, out, cap_bytes, size_out);
 }
 
 int ptr_debug_vertex_adjacency(const PtrSceneDesc* scene, uint32_t mesh, void* out, uint64_t cap_bytes, uint64_t* size_out, char* err, size_t err_cap) {
@@ -877,14 +834,10 @@ int ptr_debug_dynamic_tables(const PtrSceneDesc* scene, uint32_t which, void* ou
             case PTR_DYNAMIC_TABLE_TRI_NORMALS: take(pg.geo.triNormals.data(), pg.geo.triNormals.size() * 4u); break;
             case PTR_DYNAMIC_TABLE_SPHERES: take(pg.geo.sphereData.data(), pg.geo.sphereData.size() * 4u); break;
             case PTR_DYNAMIC_TABLE_RECTS: take(scene->rects, static_cast<size_t>(scene->rectCount) * sizeof(PtrRect)); break;
-            case PTR_DYNAMIC_TABLE_RECT_LIGHTS: {
-                std::vector<int32_t> lightIndexByRect;
-                uint32_t lightCount = 0;
-                bool haveTriangles = true;
-                buildRectLights(*scene, pg.geo, lights, lightIndexByRect, lightCount, haveTriangles);
+            case PTR_DYNAMIC_TABLE_RECT_LIGHTS:
+                lights = rectLightsOf(*scene, pg.geo).lights;
                 take(lights.data(), lights.size() * 4u);
                 break;
-            }
             default: return refuse(err, err_cap, "ptr_debug_dynamic_tables: no such table");
         }
         *size_out = bytes;

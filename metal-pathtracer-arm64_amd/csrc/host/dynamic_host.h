@@ -1,16 +1,22 @@
-// What the update calls of a dynamic scene (dynamic.cpp, rebuild.cpp: include/ptr_dynamic.h, ptr_deform.h, ptr_deform_device.h,
-// ptr_rebuild.h) share with the frame on several devices that fans them out (multi_dynamic.cpp: include/ptr_multi_dynamic.h).  Every call
-// is two halves: check*, the rules of the call on the host - no device work, "" or the refusal without the caller's name in front - which
-// leaves the accepted update behind, and run*, the device work of that update on one scene and one stream, joined before it returns.
-// Scenes uploaded from one preparation with the same flags and given the same calls hold the same host-side records, so an update checked
-// against one of them runs on all of them.  Internal: not part of the C-ABI.
+// The update calls of a resident scene - its geometry (dynamic.cpp, rebuild.cpp: include/ptr_dynamic.h, ptr_deform.h, ptr_deform_device.h,
+// ptr_rebuild.h) and its appearance (appearance.cpp: include/ptr_appearance.h) - and what they share with the frame on several devices
+// that fans the geometry ones out (multi_dynamic.cpp: include/ptr_multi_dynamic.h).  Every call is two halves: check*, the rules of the
+// call on the host against the scene's host-side records - no device work, no record changed, "" or the refusal without the caller's name
+// in front - which leaves the accepted update in an ...Update struct, and run*, the device work of that update on one scene and one
+// stream, joined before it returns and before the records follow.  The records come from the preparation at upload (fillDynamicRecords,
+// fillAppearanceRecords), never from the device.  Scenes uploaded from one preparation with the same flags and given the same calls hold
+// the same records, so an update checked against one of them runs on all of them.  Internal: not part of the C-ABI.
 #pragma once
 
+#include <chrono>
+#include <cmath>
 #include <functional>
 #include <string>
 #include <vector>
 
 #include "device_scene.h"
+#include "index_rule.h"
+#include "ptr_appearance.h"
 #include "ptr_deform_device.h"
 #include "ptr_rebuild.h"
 
@@ -24,8 +30,39 @@ struct Refused : HipError {
 
 // The host-side records of a dynamic scene, the ones the check halves read, from a description and its preparation: what
 // uploadDynamicTables keeps beside the device arrays.  No device call.
-void fillDynamicRecords(const PtrSceneDesc& desc, const ptr::PreparedGeometry& pg, const ptr::DynamicTables& t, const std::vector<int32_t>& lightIndexByRect,
+void fillDynamicRecords(const PtrSceneDesc& desc, const ptr::PreparedGeometry& pg, const ptr::DynamicTables& t, const ptr::RectLightTable& lights,
                         DynamicScene& dyn);
+
+// The host-side records of a scene's appearance from the description and its preparation (appearance.cpp): the compact material rows,
+// every rectangle's material index, the texture records.  No device call.
+void fillAppearanceRecords(const PtrSceneDesc& desc, const PreparedScene& ps, AppearanceRecords& rec);
+
+// What every update entry point is: a null scene refused, the call's rules (check), the device work (run)
+template <typename Check, typename Run>
+int updateCall(const char* who, PtrDeviceScene* scene, char* err, size_t err_cap, Check&& check, Run&& run) {
+    if (!scene) return nullArgument(who, err, err_cap);
+    try {
+        const std::string problem = check();
+        if (!problem.empty()) return refuse(err, err_cap, std::string(who) + ": " + problem);
+    }
+    PTR_CATCH_ALL(err, err_cap)
+    return deviceCall(who, scene, true, err, err_cap, run);
+}
+
+// The host staging copy: `n` floats into `dst` (pinned memory, usually); false when one of them is not finite
+inline bool stageFinite(const float* src, size_t n, float* dst) {
+    bool finite = true;
+    for (size_t k = 0; k < n; ++k) {
+        finite = finite && std::isfinite(src[k]);
+        dst[k] = src[k];
+    }
+    return finite;
+}
+
+// The device finiteness check: k_dyn_check_finite over `n` > 0 arrays of the current device (row r: its pointer and its floats).  The rows
+// and zeroed flag words go to the device, the kernel runs, the words come back and `st` is joined: the first row with a non-finite float,
+// or -1.  The scratch is the caller's: dRows (n rows) and dFlags ((n + 31) / 32 words) on the device, pinnedFlags (as many) for the way back.
+int firstNonFinite(const ptrk::DynCheckRow* rows, size_t n, ptrk::DynCheckRow* dRows, uint32_t* dFlags, uint32_t* pinnedFlags, hipStream_t st);
 
 // What a run half calls (when given) once the copies that bring the scene the call's inputs are enqueued on its stream
 using InputsEnqueued = std::function<void()>;
@@ -87,7 +124,7 @@ struct DeviceVerticesUpdate {
 std::string checkMeshVerticesDevice(const PtrDeviceScene* scene, const PtrMeshVerticesDevice* meshes, uint32_t count, int arraysDevice,
                                     DeviceVerticesUpdate& out);
 // k_dyn_check_finite over the given arrays of `u` alone, on the current device (the one they live on) and `st`, which is joined: throws
-// Refused "<who>: mesh M has a non-finite ... component".  dRows / dFlags: scratch on that device; pinnedFor: its pinned twin.
+// Refused "<who>: mesh M has a non-finite ... component".  dRows / dFlags: scratch on that device; pinnedFlags: its pinned twin.
 void checkGivenArrays(const char* who, const DeviceVerticesUpdate& u, DeviceBuffer<float4>& dRows, DeviceBuffer<uint32_t>& dFlags, uint32_t* pinnedFlags,
                       hipStream_t st);
 // The arrays of u.entry are on ds.device.  checkGiven false: the given arrays were looked at already and only computed normals are.
@@ -113,5 +150,55 @@ std::string checkTreeCall(const PtrDeviceScene* scene, uint32_t flags);
 double treeCost(PtrDeviceScene& ds, hipStream_t st);
 // a depth refusal of step 8 is thrown as Refused "<who>: ...", the scene unchanged
 void rebuildTree(const char* who, PtrDeviceScene& ds, uint32_t flags, hipStream_t st, PtrRebuildInfo& info);
+
+// ---- ptr_scene_set_materials (appearance.cpp, like everything below)
+using UpdateClock = std::chrono::steady_clock;
+struct MaterialsUpdate {
+    UpdateClock::time_point began;       // the call's entry: the info's clock includes the check
+    std::vector<uint32_t> index;         // the named materials
+    std::vector<float> rows, texRows;    // their compact rows; their texture rows (a scene with textures)
+    uint32_t typeMask = 0;               // of the table with the rows in it, like everything below
+    bool randomWalk = false;
+    bool touchesRects = false;           // a rectangle uses a named material: `lights` is the scene's new table
+    ptr::RectLightTable lights;
+    bool keyChanged = false;             // a named material changed its shade key: `keys` is k_app_rekey's table
+    std::vector<uint8_t> keys;
+};
+std::string checkMaterials(const PtrDeviceScene* scene, const uint32_t* indices, const PtrMaterial* materials, uint32_t count, MaterialsUpdate& out);
+void runMaterials(PtrDeviceScene& ds, const MaterialsUpdate& u, hipStream_t st, PtrAppearanceInfo* info);
+
+// ---- ptr_scene_set_textures and its device form: the rules and the new records, the staging of host pixels (each component looked at
+// on the way), the device half
+struct TexturesUpdate {
+    UpdateClock::time_point began;
+    bool fromDevice = false;
+    struct Entry {
+        uint32_t texture = 0;
+        const float* rgba = nullptr;     // the caller's level 0: host pixels to stage, or a device array read where it is
+        size_t floats = 0;
+    };
+    std::vector<Entry> entry;
+    std::vector<uint32_t> records;       // per entry the texture's record (kernels/texture.h) with the call's wrap / filter word
+    size_t floats = 0;                   // of the host form: what stageTextures writes, entry after entry
+};
+// arraysDevice: the device the arrays of the device form must live on
+std::string checkTextures(const PtrDeviceScene* scene, const PtrTextureUpdate* textures, uint32_t count, bool fromDevice, int arraysDevice,
+                          TexturesUpdate& out);
+std::string stageTextures(const TexturesUpdate& u, float* pinned);
+// pinned: u.floats staged floats of the host form.  A non-finite component of the device form: Refused "<who>: texture T has ...".
+void runTextures(const char* who, PtrDeviceScene& ds, const TexturesUpdate& u, const float* pinned, hipStream_t st, PtrAppearanceInfo* info);
+
+// ---- ptr_scene_set_environment and its device form
+struct EnvironmentUpdate {
+    UpdateClock::time_point began;
+    bool fromDevice = false;
+    const float* rgba = nullptr;
+    uint32_t width = 0, height = 0;
+    std::vector<float> cell;             // the per-row cell weights of a map of that size
+};
+std::string checkEnvironment(const PtrDeviceScene* scene, const float* rgba, uint32_t width, uint32_t height, bool fromDevice, int arraysDevice,
+                             EnvironmentUpdate& out);
+// A non-finite component, of either form: Refused "<who>: the map has a non-finite component", the scene untouched
+void runEnvironment(const char* who, PtrDeviceScene& ds, const EnvironmentUpdate& u, hipStream_t st, PtrAppearanceInfo* info);
 
 }  // namespace ptrhost

@@ -148,28 +148,12 @@ void prepareGeometry(const PtrSceneDesc& desc, ptr::PreparedGeometry& pg, ptr::D
     }
 }
 
-// rectangle lights: DiffuseLight rectangles with non-zero emission (:2484-2522)
-void buildRectLights(const PtrSceneDesc& desc, const ptr::SceneGeometry& geo, std::vector<float>& lights, std::vector<int32_t>& lightIndexByRect,
-                     uint32_t& lightCount, bool& lightsHaveTriangles) {
-    lightIndexByRect.assign(desc.rectCount, -1);
-    if (desc.rectCount == 0 || desc.materialCount == 0) return;
-    for (uint32_t i = 0; i < desc.rectCount; ++i) {
-        const PtrRect& r = desc.rects[i];
-        const PtrMaterial& m = desc.materials[std::min(r.materialTwoSided[0], desc.materialCount - 1u)];
-        if (static_cast<uint32_t>(m.typeEta[0]) != PTR_MAT_DIFFUSE_LIGHT) continue;
-        const ptr::float3 e{m.emission[0], m.emission[1], m.emission[2]};
-        if (!(ptr::dot(e, e) > 0.0f)) continue;
-        // the light's own two triangles exactly as the traversal reads them (leaf-order records); normal.w = 1 when they are present
-        const uint32_t t0 = geo.rectTriLeaf[static_cast<size_t>(i) * 2u], t1 = geo.rectTriLeaf[static_cast<size_t>(i) * 2u + 1u];
-        const bool haveTris = t0 != 0xFFFFFFFFu && t1 != 0xFFFFFFFFu;
-        lightsHaveTriangles = lightsHaveTriangles && haveTris;
-        static_assert(ptr::kRectLightFloats == kRectLightVec4 * 4u, "light row layout");
-        float row[ptr::kRectLightFloats];
-        ptr::WriteRectLightRow(r, i, m.emission, haveTris ? &geo.triData[static_cast<size_t>(t0) * 12u] : nullptr,
-                               haveTris ? &geo.triData[static_cast<size_t>(t1) * 12u] : nullptr, row);
-        lights.insert(lights.end(), row, row + ptr::kRectLightFloats);
-        lightIndexByRect[i] = static_cast<int32_t>(lightCount++);
-    }
+// rectangle lights: DiffuseLight rectangles with non-zero emission (:2484-2522), by the one derivation of appearance_host.h
+static_assert(ptr::kRectLightFloats == kRectLightVec4 * 4u && ptr::kCompactMaterialFloats == kMaterialVec4 * 4u, "light and material row layouts");
+ptr::RectLightTable rectLightsOf(const PtrSceneDesc& desc, const ptr::SceneGeometry& geo) {
+    std::vector<float> mats;
+    for (uint32_t i = 0; i < desc.materialCount; ++i) compactMaterial(desc.materials[i], mats);
+    return ptr::DeriveRectLights(desc.rects, desc.rectCount, geo.rectTriLeaf.data(), mats.data(), desc.materialCount);
 }
 
 constexpr uint32_t kMaxMaterials = 65536u;   // material ids 0 .. 0xFFFF
@@ -201,7 +185,7 @@ void prepareScene(const PtrSceneDesc& desc, PreparedScene& ps, const char* cache
         if (static_cast<uint32_t>(m.typeEta[0]) == PTR_MAT_SUBSURFACE && m.sssParams[1] >= 0.5f) ps.hasRandomWalkMaterial = true;
     }
 
-    buildRectLights(desc, geoRef, ps.lights, ps.lightIndexByRect, ps.lightCount, ps.lightsHaveTriangles);
+    ps.rectLights = ptr::DeriveRectLights(desc.rects, desc.rectCount, geoRef.rectTriLeaf.data(), ps.mats.data(), desc.materialCount);
     if (desc.envRgba && desc.envWidth > 0 && desc.envHeight > 0) {
         ps.hasEnvDist = ptr::BuildEnvImportanceDistribution(desc.envRgba, desc.envWidth, desc.envHeight, &ps.envDist);
     }
@@ -223,7 +207,7 @@ void uploadScene(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceSce
     const ptr::SceneGeometry& geo = ps.pg.geo;
     const ptr::FlatBvh& bvh = geo.bvh;
     const uint32_t triCount = geo.triCount;
-    const uint32_t lightCount = ps.lightCount;
+    const uint32_t lightCount = ps.rectLights.lightCount;
     ds.hasRandomWalkMaterial = ps.hasRandomWalkMaterial;
 
     HIP_CHECK(hipSetDevice(ds.device));
@@ -243,8 +227,8 @@ void uploadScene(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceSce
     ds.sphereInfo.upload(reinterpret_cast<const uint2*>(geo.sphereInfo.data()), geo.sphereInfo.size() / 2);
     ds.materials.upload(reinterpret_cast<const float4*>(ps.mats.data()), ps.mats.size() / 4);
     ds.rects.upload(reinterpret_cast<const float4*>(desc.rects), static_cast<size_t>(desc.rectCount) * 5);
-    ds.rectLights.upload(reinterpret_cast<const float4*>(ps.lights.data()), ps.lights.size() / 4);
-    ds.lightIndexByRect.upload(ps.lightIndexByRect.data(), ps.lightIndexByRect.size());
+    ds.rectLights.upload(reinterpret_cast<const float4*>(ps.rectLights.lights.data()), ps.rectLights.lights.size() / 4);
+    ds.lightIndexByRect.upload(ps.rectLights.lightIndexByRect.data(), ps.rectLights.lightIndexByRect.size());
 
     SceneView& v = ds.view;
     std::memset(&v, 0, sizeof(v));
@@ -279,7 +263,7 @@ void uploadScene(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceSce
     v.rectCount = desc.rectCount;
     v.rectLightCount = lightCount;
     for (uint32_t i = 0; i < desc.materialCount; ++i) v.materialTypes |= 1u << std::min(static_cast<uint32_t>(desc.materials[i].typeEta[0]), 7u);
-    v.settleRectLights = (lightCount > 0u && lightCount <= kSettleLightsMax && ps.lightsHaveTriangles) ? 1u : 0u;
+    v.settleRectLights = (lightCount > 0u && lightCount <= kSettleLightsMax && ps.rectLights.lightsHaveTriangles) ? 1u : 0u;
 
     if (desc.envRgba && desc.envWidth > 0 && desc.envHeight > 0) {
         const size_t texels = static_cast<size_t>(desc.envWidth) * desc.envHeight;
@@ -317,6 +301,7 @@ void uploadScene(const PtrSceneDesc& desc, const PreparedScene& ps, PtrDeviceSce
     ds.worldBounds = ptr::boundsOfPrimitives(geo.triData.data(), geo.triData.size() / 12u, geo.sphereData.data(), geo.sphereData.size() / 4u);
 
     if (ps.dynamic) uploadDynamicTables(desc, ps, ds);   // dynamic.cpp
+    fillAppearanceRecords(desc, ps, ds.appearanceRecords);   // appearance.cpp
 
     ds.info[0] = bvh.nodeCount;
     ds.info[1] = bvh.leafCount;

@@ -179,7 +179,7 @@ int ptr_multi_frame_set_mesh_vertices(PtrMultiFrame* frame, const PtrMeshVertice
         problem = checkMeshVertices(frame->part[0]->scene.get(), meshes, count, u);
         if (problem.empty()) {   // staged once, for every partition
             HIP_CHECK(hipSetDevice(frame->rootDevice));
-            float* staged = static_cast<float*>(frame->dynamic->pinnedFor(std::max<size_t>(u.floats, 4u) * sizeof(float)));
+            float* staged = static_cast<float*>(frame->dynamic->pinned.pinnedFor(std::max<size_t>(u.floats, 4u) * sizeof(float)));
             pinned = staged;
             problem = stageMeshVertices(meshes, u, staged);
         }
@@ -281,13 +281,13 @@ int ptr_multi_frame_set_mesh_vertices_device(PtrMultiFrame* frame, const PtrMesh
         // the check, once, where the arrays are; a refusal leaves every partition as it was
         try {
             const size_t words = (u.checked.size() + 31u) / 32u;
-            checkGivenArrays(who, u, source->rows, source->flags, static_cast<uint32_t*>(md.pinnedFor(std::max<size_t>(words, 1u) * sizeof(uint32_t))), callers);
+            checkGivenArrays(who, u, source->rows, source->flags, static_cast<uint32_t*>(md.pinned.pinnedFor(std::max<size_t>(words, 1u) * sizeof(uint32_t))), callers);
         } catch (const Refused& r) {
             return refuse(err, err_cap, r.message);
         }
         const float* pinned = nullptr;
         if (stagedParts > 0u && travel.floats > 0u) {   // once, for every partition that cannot pull; the event below is behind these copies
-            float* staged = static_cast<float*>(md.pinnedFor(travel.floats * sizeof(float)));
+            float* staged = static_cast<float*>(md.pinned.pinnedFor(travel.floats * sizeof(float)));
             for (const Travel::Array& a : travel.arrays) {
                 HIP_CHECK(hipMemcpyAsync(staged + a.at, a.src, a.floats * sizeof(float), hipMemcpyDeviceToHost, callers));
             }
@@ -342,14 +342,9 @@ int ptr_multi_frame_debug_check_update(const PtrSceneDesc* scene, uint32_t dynam
         ptr::DynamicTables t;
         t.flags = dynamic_flags;
         prepareGeometry(*scene, pg, &t);
-        std::vector<float> lights;
-        std::vector<int32_t> lightIndexByRect;
-        uint32_t lightCount = 0;
-        bool haveTriangles = true;
-        buildRectLights(*scene, pg.geo, lights, lightIndexByRect, lightCount, haveTriangles);
         PtrDeviceScene ds;
         ds.dynamic = std::make_unique<DynamicScene>();
-        fillDynamicRecords(*scene, pg, t, lightIndexByRect, *ds.dynamic);
+        fillDynamicRecords(*scene, pg, t, rectLightsOf(*scene, pg.geo), *ds.dynamic);
         if (kind == 0u) {
             TransformUpdate u;
             problem = checkMeshTransforms(&ds, static_cast<const PtrMeshTransform*>(list), count, u);

@@ -36,17 +36,7 @@ struct MultiDynamic {
     uint32_t flags = 0;   // PTR_DYNAMIC_*: what every partition's scene was uploaded with
     // portable pinned memory, grown on demand and kept: host vertex data is staged here once for all partitions, and device-resident
     // data passes through here once for the partitions that cannot pull it from a peer
-    void* pinned = nullptr;
-    size_t pinnedBytes = 0;
-    void* pinnedFor(size_t bytes) {
-        if (bytes > pinnedBytes) {
-            if (pinned) (void)hipHostFree(pinned);
-            pinned = nullptr, pinnedBytes = 0;
-            HIP_CHECK(hipHostMalloc(&pinned, bytes, hipHostMallocPortable));
-            pinnedBytes = bytes;
-        }
-        return pinned;
-    }
+    PinnedBuffer pinned{hipHostMallocPortable};
     // per device the caller's arrays have lived on: the scratch of the finiteness check there, and the event the partitions wait on
     struct Source {
         DeviceBuffer<float4> rows;
@@ -58,7 +48,6 @@ struct MultiDynamic {
         for (auto& s : source) {
             if (s.second->ready && hipSetDevice(s.first) == hipSuccess) (void)hipEventDestroy(s.second->ready);
         }
-        if (pinned) (void)hipHostFree(pinned);
     }
 };
 

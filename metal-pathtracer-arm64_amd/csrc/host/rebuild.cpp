@@ -47,7 +47,7 @@ double sumInBlockOrder(const double* partials, uint32_t blocks) {
 double treeCostOf(DynamicScene& dyn, RebuildState& st, const float4* boxes, uint32_t nodeCount, hipStream_t stream) {
     if (nodeCount == 0u) return 0.0;
     const uint32_t blocks = costBlocks(nodeCount);
-    char* pinned = static_cast<char*>(dyn.pinnedFor(64u + static_cast<size_t>(blocks) * sizeof(double)));
+    char* pinned = static_cast<char*>(dyn.pinned.pinnedFor(64u + static_cast<size_t>(blocks) * sizeof(double)));
     HIP_CHECK(hipMemcpyAsync(pinned, boxes, 64u, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     double cost = 0.0, rootHalf = 0.0;
@@ -122,7 +122,7 @@ void rebuildTree(const char* who, PtrDeviceScene& ds, uint32_t flags, hipStream_
 
     // steps 2-4: the root box of the current tree is in the pinned buffer (treeCostOf read node 0)
     float rootLo[3] = {0, 0, 0}, rootHi[3] = {0, 0, 0};
-    ptr::RootBoxOfNode(static_cast<const float*>(dyn.pinned), rootLo, rootHi);
+    ptr::RootBoxOfNode(static_cast<const float*>(dyn.pinned.ptr), rootLo, rootHi);
     HIP_CHECK(hipEventRecord(st.events[0], stream));
     launchRebuildKeys(st.leaves.ptr, leafCount, dyn.triBounds.ptr, dyn.sphereBounds.ptr, rootLo, rootHi, st.keys.ptr, stream);
     launchRebuildSortKeys(st.sortScratch.ptr, keyScratch, st.keys.ptr, st.sortedKeys.ptr, leafCount, stream);
@@ -136,7 +136,7 @@ void rebuildTree(const char* who, PtrDeviceScene& ds, uint32_t flags, hipStream_
     HIP_CHECK(hipMemsetAsync(st.heights.ptr, kHeightUnknown, n, stream));
     HIP_CHECK(hipMemsetAsync(st.small.ptr, 0, 128u * sizeof(uint32_t), stream));
     for (uint32_t k = 0; k + 1u < kMaxTreeDepth; ++k) launchRebuildHeights(st.boxes.ptr, nodeCount, k, st.heights.ptr, st.iota.ptr, stream);
-    uint8_t* pinnedBytes = static_cast<uint8_t*>(dyn.pinnedFor(64u + static_cast<size_t>(costBlocks(nodeCount)) * sizeof(double) + 1024u));
+    uint8_t* pinnedBytes = static_cast<uint8_t*>(dyn.pinned.pinnedFor(64u + static_cast<size_t>(costBlocks(nodeCount)) * sizeof(double) + 1024u));
     HIP_CHECK(hipMemcpyAsync(pinnedBytes, st.heights.ptr, 1u, hipMemcpyDeviceToHost, stream));
     HIP_CHECK(hipStreamSynchronize(stream));
     const uint32_t levels = pinnedBytes[0] == kHeightUnknown ? kMaxTreeDepth : pinnedBytes[0] + 1u;
@@ -165,7 +165,7 @@ void rebuildTree(const char* who, PtrDeviceScene& ds, uint32_t flags, hipStream_
 
     // step 9: the grid of the new root box (the same box: min and max do not depend on the order of the union)
     float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0}, origin[3], cell[3];
-    ptr::RootBoxOfNode(static_cast<const float*>(dyn.pinned), lo, hi);
+    ptr::RootBoxOfNode(static_cast<const float*>(dyn.pinned.ptr), lo, hi);
     for (int a = 0; a < 3; ++a) gridAxis(lo[a], hi[a], origin[a], cell[a]);
     if (v.useQuantized) launchDynQuantise(st.boxes.ptr, st.qnodes.ptr, nodeCount, origin, cell, stream);
     HIP_CHECK(hipEventRecord(st.events[4], stream));
@@ -178,7 +178,7 @@ void rebuildTree(const char* who, PtrDeviceScene& ds, uint32_t flags, hipStream_
         HIP_CHECK(hipMemsetAsync(st.marks.ptr, 0, n * sizeof(uint32_t), stream));
         for (uint32_t d = 1; d <= levels; ++d) launchRebuildWideMark(st.qnodes.ptr, nodeCount, cell, d, st.depth.ptr, st.marks.ptr, reached, stream);
         launchRebuildWideScan(st.sortScratch.ptr, scanScratch, st.marks.ptr, st.wideIndex.ptr, nodeCount, stream);
-        pinnedWords = static_cast<uint32_t*>(dyn.pinnedFor(1024u));
+        pinnedWords = static_cast<uint32_t*>(dyn.pinned.pinnedFor(1024u));
         HIP_CHECK(hipMemcpyAsync(pinnedWords, reached, 64u * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipMemcpyAsync(pinnedWords + 64, st.wideIndex.ptr + (n - 1u), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         HIP_CHECK(hipMemcpyAsync(pinnedWords + 65, st.marks.ptr + (n - 1u), sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
@@ -283,16 +283,7 @@ int ptr_debug_rebuild_arrays(PtrDeviceScene* scene, uint32_t which, void* out, u
         case PTR_REBUILD_ARRAY_POINTERS: host = pointers, bytes = sizeof(pointers); break;
         default: return 1;
     }
-    *size_out = bytes;
-    if (!out) return 0;
-    if (cap_bytes < bytes) return 2;
-    if (bytes == 0u) return 0;
-    if (host) {
-        std::memcpy(out, host, bytes);
-        return 0;
-    }
-    if (hipSetDevice(ds.device) != hipSuccess || hipMemcpy(out, device, bytes, hipMemcpyDeviceToHost) != hipSuccess) return 3;
-    return 0;
+    return probeArrayTail(ds.device, host ? host : device, host != nullptr, bytes, out, cap_bytes, size_out);
 }
 
 int ptr_debug_rebuild_tables(const float* nodes, uint32_t nodeCount, uint32_t which, void* out, uint64_t cap_bytes, uint64_t* size_out, char* err,

@@ -284,6 +284,14 @@ def test_texture_updates_equal_a_fresh_upload():
         assert str(e.value).startswith(name + ": ") and text in str(e.value)
         now = dev.appearance_arrays(["texels", "texInfo"])
         assert all(np.array_equal(kept[k], now[k]) for k in kept), text
+    # a check that refused left nothing behind: an accepted call with the pixels texture 3 has, another wrap and filter, is a fresh upload's
+    old = quads.desc.textures[3]
+    rewrapped = (quads.pixels[3], (old.wrapS + 1) % 3, (old.wrapT + 2) % 3, 1 - old.filter)
+    dev.set_textures({3: rewrapped})
+    now = dev.appearance_arrays(["texels", "texInfo"])
+    assert np.array_equal(kept["texels"], now["texels"]) and (kept["texInfo"] != now["texInfo"]).sum() == 1, "only the wrap / filter word of texture 3"
+    fresh = pt.DeviceScene(aps.Edited(quads.desc, quads, textures={2: new[2], 3: rewrapped}).desc, 0, keepalive=quads)
+    assert_same_scene(dev, fresh, settings, "wrap and filter of one texture after the refusals")
     plain = ts.scene_a()   # (held: the device scene reads the description while it uploads)
     with pytest.raises(pt.PtrError) as e:
         pt.DeviceScene(plain.desc, 0, keepalive=plain).set_textures({0: new[3][0]})
@@ -388,6 +396,11 @@ def test_a_black_map_turns_sampling_off_and_a_lit_one_turns_it_on_again(tmp_path
         assert str(e.value).startswith("ptr_scene_set_environment: ") and text in str(e.value)
     after = dev.appearance_arrays()
     assert all(np.array_equal(before[k], after[k]) for k in before if k != "scalars") and before["scalars"] == after["scalars"]
+    # a check that refused left nothing behind: an accepted call after the refusals is a fresh upload of its map
+    again = new_map(w, h, "noise", 3)
+    assert dev.set_environment(again)["envSampling"] == 1
+    assert_tables_are_the_hosts(dev, again)
+    assert_same_scene(dev, pt.DeviceScene(aps.Edited(host.desc, host, env=again).desc, 0, keepalive=host), settings, "accepted after the refusals")
     plain = ts.scene_a()   # (held: the device scene reads the description while it uploads)
     with pytest.raises(pt.PtrError) as e:
         pt.DeviceScene(plain.desc, 0, keepalive=plain).set_environment(lit)

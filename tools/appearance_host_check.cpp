@@ -8,16 +8,19 @@
 // For descriptions of 0 to 512 materials and 0 to 128 rectangles (material indices past the table included, which the upload clamps) it
 // runs the validation of ptr_scene_set_materials on good and bad lists, the derivation of the rectangle-light table against the
 // geometry's own leaf rows, and the shade-key table against the meta words of the geometry's triangles; then the level sizes of mip
-// chains.  Prints one line per description; exits 1 on the first difference.  No GPU, no HIP.
+// chains, and the index rule every update call's list shares (index_rule.h) with its three message forms.  Prints one line per
+// description; exits 1 on the first difference.  No GPU, no HIP.
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <limits>
 #include <random>
+#include <string>
 #include <vector>
 
 #include "bvh_layout.h"
 #include "appearance_host.h"
+#include "index_rule.h"
 
 namespace {
 
@@ -136,8 +139,7 @@ bool checkTables(uint32_t materials, uint32_t rects, const Scene& s) {
     }
     if (mask != wantMask || walk != wantWalk) return bad("type mask or random-walk flag");
     // the light table against the upload's rule, with the light's own triangles taken from the geometry's leaf rows
-    ptr::RectLightTable got;
-    ptr::DeriveRectLights(s.rects.data(), rects, geo.rectTriLeaf.data(), s.rows.data(), materials, got);
+    const ptr::RectLightTable got = ptr::DeriveRectLights(s.rects.data(), rects, geo.rectTriLeaf.data(), s.rows.data(), materials);
     if (got.lightIndexByRect.size() != rects || got.rectEmission.size() != static_cast<size_t>(rects) * 3u || got.rectShadeKey.size() != rects) return bad("light table sizes");
     std::vector<float> want;
     uint32_t count = 0;
@@ -174,6 +176,33 @@ bool checkMips() {
     return cell.size() == 5u && cell[0] > 0.0f && cell[4] > 0.0f && cell[2] > cell[1] && cell[2] > cell[3];
 }
 
+// the index rule on scenes of 0, 1 and 300 entities, for two kinds whose plurals differ: the three message forms, literally
+bool checkIndexRule() {
+    const char* const kinds[2][2] = {{"mesh", "meshes"}, {"texture", "textures"}};
+    for (const auto& k : kinds) {
+        const std::string kind = k[0], plural = k[1];
+        for (uint32_t count : {0u, 1u, 300u}) {
+            std::vector<uint8_t> named(count, 0);
+            const std::string past = kind + " index " + std::to_string(count) + " out of range (the scene has " + std::to_string(count) + " " + plural + ")";
+            if (ptr::NamedIndexProblem(k[0], k[1], count, named) != past) return false;   // the first index past the table; any index of an empty scene
+            if (ptr::NamedIndexProblem(k[0], k[1], 0xFFFFFFFFu, named) != kind + " index 4294967295 out of range (the scene has " + std::to_string(count) + " " + plural + ")") return false;
+            for (uint8_t byte : named) {
+                if (byte) return false;   // a refused index marks nothing
+            }
+            if (count == 0u) continue;
+            const uint32_t last = count - 1u;
+            if (!ptr::NamedIndexProblem(k[0], k[1], last, named).empty() || !named[last]) return false;   // the last valid index
+            if (ptr::NamedIndexProblem(k[0], k[1], last, named) != kind + " index " + std::to_string(last) + " named twice") return false;
+            if (ptr::NamedIndexProblem(k[0], k[1], last, named) != kind + " index " + std::to_string(last) + " named twice") return false;   // and a third time
+            if (count > 1u && (!ptr::NamedIndexProblem(k[0], k[1], 0u, named).empty() || ptr::NamedIndexProblem(k[0], k[1], 0u, named) != kind + " index 0 named twice")) return false;
+        }
+    }
+    std::vector<uint8_t> named(3, 0);
+    return ptr::NamedIndexProblem("rectangle", "rectangles", 3u, named) == "rectangle index 3 out of range (the scene has 3 rectangles)" &&
+           ptr::NamedIndexProblem("mesh", "meshes", 7u, named) == "mesh index 7 out of range (the scene has 3 meshes)" &&
+           ptr::NamedIndexProblem("mesh", "meshes", 2u, named).empty() && ptr::NamedIndexProblem("mesh", "meshes", 2u, named) == "mesh index 2 named twice";
+}
+
 }  // namespace
 
 int main() {
@@ -188,6 +217,10 @@ int main() {
     }
     if (!checkMips()) {
         std::printf("mip levels and cell weights: differ\n");
+        return 1;
+    }
+    if (!checkIndexRule()) {
+        std::printf("the index rule: differs\n");
         return 1;
     }
     std::printf("mip levels and cell weights: ok\n");
