@@ -53,8 +53,9 @@
  * a height above PTR_APPEARANCE_ENV_MAX_DIM (a row's scaled values and its two work lists take 12 B per entry of LDS: 48 KB at the cap);
  * for the device call a pointer that fails the checks above.
  *
- * Out of scope: adding or removing materials, textures or primitives; changing a texture's or the environment's size; frames on several
- * devices (ptr_multi_frame.h, ptr_multi_dynamic.h) and the one-shot ptr_render_multi*; the command-line program; the geometry cache.
+ * Out of scope: adding or removing materials, textures or primitives; changing a texture's or the environment's size; the one-shot
+ * ptr_render_multi* (a frame on several devices takes these calls through ptr_multi_appearance.h); the command-line program; the
+ * geometry cache.
  */
 #ifndef PTR_APPEARANCE_H
 #define PTR_APPEARANCE_H

@@ -777,6 +777,34 @@ _APPEARANCE_SIGNATURES = {
     "ptr_debug_appearance_arrays": (_int, [_vp, _u32, _vp, _u64, _u64p]),
 }
 APPEARANCE_SYMBOLS = tuple(_APPEARANCE_SIGNATURES)
+
+
+class PtrMultiAppearanceInfo(C.Structure):
+    """include/ptr_multi_appearance.h PtrMultiAppearanceInfo."""
+    _fields_ = [("parts", C.c_uint32), ("stagedParts", C.c_uint32), ("hostStagedBytes", C.c_uint64), ("totalSeconds", C.c_double),
+                ("distributeSeconds", C.c_double), ("partSeconds", C.c_double * MULTI_MAX_PARTS), ("first", PtrAppearanceInfo)]
+
+    def as_dict(self) -> dict:
+        """PtrAppearanceInfo of partition 0 as DeviceScene's appearance calls return it, with the figures of the fan-out beside it."""
+        out = self.first.as_dict()
+        out.update(parts=int(self.parts), stagedParts=int(self.stagedParts), hostStagedBytes=int(self.hostStagedBytes), totalSeconds=self.totalSeconds,
+                   distributeSeconds=self.distributeSeconds, partSeconds=list(self.partSeconds[:self.parts]), partTotalSeconds=self.first.totalSeconds)
+        return out
+
+
+# ... and of include/ptr_multi_appearance.h (the same calls on a frame on several devices): tests/test_multi_appearance_host.py holds it
+# against that header.  (MULTI_APPEARANCE_FUNCTIONS, not ..._SYMBOLS: tests/test_appearance_host.py holds the set of *_SYMBOLS tables fixed.)
+_multi_appearance = C.POINTER(PtrMultiAppearanceInfo)
+_MULTI_APPEARANCE_SIGNATURES = {
+    "ptr_multi_frame_set_materials": (_int, [_vp, _up, _material, _u32, _multi_appearance] + _err),
+    "ptr_multi_frame_set_textures": (_int, [_vp, C.POINTER(PtrTextureUpdate), _u32, _multi_appearance] + _err),
+    "ptr_multi_frame_set_environment": (_int, [_vp, _vp, _u32, _u32, _multi_appearance] + _err),
+    "ptr_multi_frame_set_textures_device": (_int, [_vp, C.POINTER(PtrTextureUpdate), _u32, _int, _vp, _multi_appearance] + _err),
+    "ptr_multi_frame_set_environment_device": (_int, [_vp, _vp, _u32, _u32, _int, _vp, _multi_appearance] + _err),
+    # its test-only probe
+    "ptr_multi_frame_debug_check_appearance": (_int, [_desc, _u32, _u32, _vp, _material, _u32, _u32, _u32] + _err),
+}
+MULTI_APPEARANCE_FUNCTIONS = tuple(_MULTI_APPEARANCE_SIGNATURES)
 # ptr_debug_appearance_arrays: name -> (selector, dtype, trailing shape).  Words that hold bit patterns beside floats (texture indices,
 # alias entries) are read as uint32, so comparisons are of the raw words.
 APPEARANCE_ARRAYS = {"materials": (0, np.uint32, (16, 4)), "materialTex": (1, np.uint32, (16, 4)), "rectLights": (2, np.uint32, (11, 4)),
@@ -821,7 +849,7 @@ def load_library() -> C.CDLL:
             list(_DYNAMIC_SIGNATURES.items()) + list(_DEFORM_SIGNATURES.items()) + list(_DEFORM_DEVICE_SIGNATURES.items()) + \
             list(_BACKGROUND_SIGNATURES.items()) + list(_TEMPORAL_SIGNATURES.items()) + list(_TEMPORAL_COV_SIGNATURES.items()) + list(_PBR_HIT_SIGNATURES.items()) + \
             list(_SSS_WALK_SIGNATURES.items()) + list(_PATH_STATE_SIGNATURES.items()) + list(_REBUILD_SIGNATURES.items()) + list(_MULTI_DYNAMIC_SIGNATURES.items()) + \
-            list(_APPEARANCE_SIGNATURES.items()):
+            list(_APPEARANCE_SIGNATURES.items()) + list(_MULTI_APPEARANCE_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
@@ -1113,11 +1141,16 @@ class DeviceScene:
     def set_materials(self, materials: dict, stream: int = 0) -> dict:
         """ptr_scene_set_materials: {material index: PtrMaterial}, each replacing the whole material; returns PtrAppearanceInfo as a dict.
         A Frame or a Temporal of the scene is not told: reset them."""
+        indices, items = self._material_items(materials)
+        return self._appearance_call("ptr_scene_set_materials", indices, items, len(materials), stream=stream)
+
+    @staticmethod
+    def _material_items(materials: dict):
         indices = (C.c_uint32 * max(len(materials), 1))(*[int(i) for i in materials])
         items = (PtrMaterial * max(len(materials), 1))()
         for k, m in enumerate(materials.values()):
             C.memmove(C.byref(items[k]), C.byref(m), C.sizeof(PtrMaterial))
-        return self._appearance_call("ptr_scene_set_materials", indices, items, len(materials), stream=stream)
+        return indices, items
 
     @staticmethod
     def _texture_items(name: str, textures: dict, address):
@@ -1143,8 +1176,9 @@ class DeviceScene:
         device = getattr(t, "device", None)
         if not hasattr(t, "data_ptr") or device is None:
             raise PtrError("%s: the pixels of %s are not a torch tensor" % (name, what))
-        if device.type != "cuda" or device.index != self._device:
-            raise PtrError("%s: the pixels of %s are on %s, not on device %d of the scene" % (name, what, device, self._device))
+        if device.type != "cuda" or (self._device is not None and device.index != self._device):   # (None: a MultiFrame, which takes any device)
+            where = "a HIP device" if self._device is None else "device %d of the scene" % self._device
+            raise PtrError("%s: the pixels of %s are on %s, not on %s" % (name, what, device, where))
         if str(t.dtype) != "torch.float32":
             raise PtrError("%s: the pixels of %s are %s, not float32" % (name, what, t.dtype))
         if t.dim() != 3 or t.shape[2] != 4:
@@ -1572,6 +1606,7 @@ class _BorrowedScene(DeviceScene):
         raise PtrError("a partition's scene is updated through its MultiFrame: a call on one partition would desynchronise them")
 
     set_mesh_transforms = set_mesh_vertices = set_mesh_vertices_device = set_spheres = set_rects = rebuild_tree = _through_the_frame
+    set_materials = set_textures = set_textures_device = set_environment = set_environment_device = _through_the_frame
 
     def close(self) -> None:
         pass
@@ -2058,6 +2093,54 @@ class MultiFrame:
             stream = torch.cuda.current_stream(device).cuda_stream
         return self._update("ptr_multi_frame_set_mesh_vertices_device", items, len(meshes), device, C.c_void_p(stream))
 
+    # ---- include/ptr_multi_appearance.h: DeviceScene's appearance calls on every partition, on static frames too.  They take what
+    # DeviceScene's take, without the stream, and return PtrMultiAppearanceInfo.as_dict().  reset() before accumulating the edited scene.
+    _device = None   # (for DeviceScene._device_pixels: the tensors of a device form may live on any device)
+
+    def _appearance(self, name: str, *args) -> dict:
+        info = PtrMultiAppearanceInfo()
+        err = _err_buf()
+        _check(getattr(load_library(), name)(self._handle(), *args, C.byref(info), err, len(err)), err)
+        return info.as_dict()
+
+    @staticmethod
+    def _source_of(name: str, tensors, stream):
+        """(src_device, stream) of a device form: the one device all its tensors are on, and torch's current stream there by default."""
+        devices = {t.device.index for t in tensors}
+        if len(devices) != 1:
+            raise PtrError("%s: the tensors are on %d devices, not on one" % (name, len(devices)))
+        device = devices.pop()
+        if stream is None:
+            import torch   # (only here: the module itself does not need torch)
+
+            stream = torch.cuda.current_stream(device).cuda_stream
+        return device, C.c_void_p(stream)
+
+    def set_materials(self, materials: dict) -> dict:
+        indices, items = DeviceScene._material_items(materials)
+        return self._appearance("ptr_multi_frame_set_materials", indices, items, len(materials))
+
+    def set_textures(self, textures: dict) -> dict:
+        items, keep = DeviceScene._texture_items("set_textures", textures, DeviceScene._host_pixels)
+        return self._appearance("ptr_multi_frame_set_textures", items, len(textures))
+
+    def set_textures_device(self, textures: dict, stream=None) -> dict:
+        """ptr_multi_frame_set_textures_device: torch tensors as DeviceScene.set_textures_device takes them, all on one device, which need
+        not be one of the frame's; they are read on `stream` of that device (None: torch's current stream there)."""
+        items, keep = DeviceScene._texture_items("set_textures_device", textures, lambda *a: DeviceScene._device_pixels(self, *a))
+        device, stream = self._source_of("set_textures_device", keep, stream)
+        return self._appearance("ptr_multi_frame_set_textures_device", items, len(textures), device, stream)
+
+    def set_environment(self, pixels) -> dict:
+        a, (h, w) = DeviceScene._host_pixels("set_environment", "the map", pixels)
+        return self._appearance("ptr_multi_frame_set_environment", a.ctypes.data_as(C.c_void_p), w, h)
+
+    def set_environment_device(self, pixels, stream=None) -> dict:
+        """ptr_multi_frame_set_environment_device: a torch tensor on any visible device, read on `stream` of that device."""
+        t, (h, w) = DeviceScene._device_pixels(self, "set_environment_device", "the map", pixels)
+        device, stream = self._source_of("set_environment_device", [t], stream)
+        return self._appearance("ptr_multi_frame_set_environment_device", C.c_void_p(t.data_ptr()), w, h, device, stream)
+
     def tree_cost(self) -> float:
         cost = C.c_double(0.0)
         err = _err_buf()
@@ -2137,6 +2220,26 @@ def debug_multi_check_update(desc: PtrSceneDesc, call: str, update: dict, deform
     flags = (PTR_DYNAMIC_DEFORMABLE if deformable else 0) | (PTR_DYNAMIC_PRIMITIVES if primitives else 0) | (PTR_DYNAMIC_VERTEX_NORMALS if vertex_normals else 0)
     err = _err_buf()
     _check(load_library().ptr_multi_frame_debug_check_update(C.byref(desc), flags, kind, C.cast(items, C.c_void_p), len(update), err, len(err)), err)
+
+
+def debug_multi_check_appearance(desc: PtrSceneDesc, call: str, update, primitives: bool = False) -> None:
+    """ptr_multi_frame_debug_check_appearance (tests, no GPU): the host checks of MultiFrame.<call>(update) - set_materials, set_textures
+    or set_environment, the look at every pixel component included - against a frame made from `desc`, static or (primitives) dynamic with
+    PTR_DYNAMIC_PRIMITIVES; raises PtrError with the call's own message when it would be refused."""
+    flags = PTR_DYNAMIC_PRIMITIVES if primitives else 0
+    if call == "set_materials":
+        indices, items = DeviceScene._material_items(update)
+        args = (0, C.cast(indices, C.c_void_p), items, len(update), 0, 0)
+    elif call == "set_textures":
+        items, keep = DeviceScene._texture_items(call, update, DeviceScene._host_pixels)
+        args = (1, C.cast(items, C.c_void_p), None, len(update), 0, 0)
+    elif call == "set_environment":
+        a, (h, w) = DeviceScene._host_pixels(call, "the map", update)
+        args = (2, a.ctypes.data_as(C.c_void_p), None, 0, w, h)
+    else:
+        raise PtrError("debug_multi_check_appearance: no such call: %s" % call)
+    err = _err_buf()
+    _check(load_library().ptr_multi_frame_debug_check_appearance(C.byref(desc), flags, *args, err, len(err)), err)
 
 
 def debug_multi_frame(samples: np.ndarray, device_ids) -> MultiFrame:

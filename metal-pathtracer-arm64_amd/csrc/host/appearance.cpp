@@ -247,7 +247,8 @@ std::string stageTextures(const TexturesUpdate& u, float* pinned) {
     return "";
 }
 
-void runTextures(const char* who, PtrDeviceScene& ds, const TexturesUpdate& u, const float* staged, hipStream_t stream, PtrAppearanceInfo* infoOut) {
+void runTextures(const char* who, PtrDeviceScene& ds, const TexturesUpdate& u, const float* staged, bool checkGiven, hipStream_t stream,
+                 PtrAppearanceInfo* infoOut, const InputsEnqueued& enqueued) {
     AppearanceState& st = stateOf(ds);
     const size_t count = u.entry.size();
     // one pinned block: the records, then the rows and the flag words of the device form's check
@@ -258,7 +259,7 @@ void runTextures(const char* who, PtrDeviceScene& ds, const TexturesUpdate& u, c
     const double stagingMs = msSince(u.began);
 
     HIP_CHECK(hipEventRecord(st.events[0], stream));
-    if (u.fromDevice) {
+    if (u.fromDevice && checkGiven) {
         const int bad = firstNonFiniteOf(st, pinned + recordBytes, count, [&](size_t r) { return DynCheckRow{u.entry[r].rgba, u.entry[r].floats}; }, stream);
         if (bad >= 0) throw Refused{std::string(who) + ": texture " + std::to_string(u.entry[bad].texture) + " has a non-finite component"};
     }
@@ -273,6 +274,7 @@ void runTextures(const char* who, PtrDeviceScene& ds, const TexturesUpdate& u, c
         if (!u.fromDevice) staged += e.floats;
         written += e.floats / 4u;
     }
+    if (enqueued) enqueued();
     HIP_CHECK(hipEventRecord(st.events[1], stream));
     for (size_t i = 0; i < count; ++i) {
         const uint32_t* rec = records + i * kTexInfoWords;
@@ -315,7 +317,12 @@ std::string checkEnvironment(const PtrDeviceScene* scene, const float* rgba, uin
     return "";
 }
 
-void runEnvironment(const char* who, PtrDeviceScene& ds, const EnvironmentUpdate& u, hipStream_t stream, PtrAppearanceInfo* infoOut) {
+std::string stageEnvironment(const EnvironmentUpdate& u, float* pinned) {
+    return stageFinite(u.rgba, static_cast<size_t>(u.width) * u.height * 4u, pinned) ? "" : "the map has a non-finite component";
+}
+
+void runEnvironment(const char* who, PtrDeviceScene& ds, const EnvironmentUpdate& u, const float* staged, bool checkGiven, hipStream_t stream,
+                    PtrAppearanceInfo* infoOut, const InputsEnqueued& enqueued) {
     AppearanceState& st = stateOf(ds);
     SceneView& v = ds.view;
     const uint32_t w = u.width, h = u.height;
@@ -325,21 +332,21 @@ void runEnvironment(const char* who, PtrDeviceScene& ds, const EnvironmentUpdate
     float* pCell = reinterpret_cast<float*>(pinned);
     float* pTotal = pCell + h;
     char* checkScratch = pinned + cellBytes;   // (behind them: the check must not write over the weights)
-    const std::string nonFinite = std::string(who) + ": the map has a non-finite component";
-    float* staged = u.fromDevice ? nullptr : static_cast<float*>(st.staged.pinnedFor(texels * sizeof(float4)));
-    if (staged && !stageFinite(u.rgba, texels * 4u, staged)) throw Refused{nonFinite};
     std::memcpy(pCell, u.cell.data(), static_cast<size_t>(h) * 4u);
     st.envWeight.ensure(texels), st.envRowWeight.ensure(h), st.envCell.ensure(h), st.envTotal.ensure(1);
     const double stagingMs = msSince(u.began);
 
     HIP_CHECK(hipEventRecord(st.events[0], stream));
     if (u.fromDevice) {
-        if (firstNonFiniteOf(st, checkScratch, 1u, [&](size_t) { return DynCheckRow{u.rgba, static_cast<uint64_t>(texels) * 4u}; }, stream) >= 0) throw Refused{nonFinite};
+        if (checkGiven && firstNonFiniteOf(st, checkScratch, 1u, [&](size_t) { return DynCheckRow{u.rgba, static_cast<uint64_t>(texels) * 4u}; }, stream) >= 0) {
+            throw Refused{std::string(who) + ": the map has a non-finite component"};
+        }
         HIP_CHECK(hipMemcpyAsync(ds.envRgba.ptr, u.rgba, texels * sizeof(float4), hipMemcpyDeviceToDevice, stream));
     } else {
         HIP_CHECK(hipMemcpyAsync(ds.envRgba.ptr, staged, texels * sizeof(float4), hipMemcpyHostToDevice, stream));
     }
     HIP_CHECK(hipMemcpyAsync(st.envCell.ptr, pCell, static_cast<size_t>(h) * 4u, hipMemcpyHostToDevice, stream));
+    if (enqueued) enqueued();
     HIP_CHECK(hipEventRecord(st.events[1], stream));
     launchAppEnvWeights(ds.envRgba.ptr, st.envCell.ptr, w, h, st.envWeight.ptr, st.envRowWeight.ptr, stream);
     HIP_CHECK(hipEventRecord(st.events[2], stream));
@@ -391,14 +398,23 @@ int setTextures(const char* who, PtrDeviceScene* scene, const PtrTextureUpdate* 
                           staged = static_cast<float*>(stateOf(*scene).staged.pinnedFor(u.floats * sizeof(float)));
                           return stageTextures(u, staged);
                       },
-                      [&] { runTextures(who, *scene, u, staged, static_cast<hipStream_t>(stream), info); });
+                      [&] { runTextures(who, *scene, u, staged, true, static_cast<hipStream_t>(stream), info); });
 }
 
 int setEnvironment(const char* who, PtrDeviceScene* scene, const float* rgba, uint32_t width, uint32_t height, bool fromDevice, void* stream,
                    PtrAppearanceInfo* info, char* err, size_t err_cap) {
     EnvironmentUpdate u;
-    return updateCall(who, scene, err, err_cap, [&] { return checkEnvironment(scene, rgba, width, height, fromDevice, scene->device, u); },
-                      [&] { runEnvironment(who, *scene, u, static_cast<hipStream_t>(stream), info); });
+    float* staged = nullptr;
+    return updateCall(who, scene, err, err_cap,
+                      [&] {
+                          const std::string problem = checkEnvironment(scene, rgba, width, height, fromDevice, scene->device, u);
+                          if (!problem.empty() || fromDevice) return problem;
+                          // staging, as for the textures
+                          HIP_CHECK(hipSetDevice(scene->device));
+                          staged = static_cast<float*>(stateOf(*scene).staged.pinnedFor(static_cast<size_t>(width) * height * sizeof(float4)));
+                          return stageEnvironment(u, staged);
+                      },
+                      [&] { runEnvironment(who, *scene, u, staged, true, static_cast<hipStream_t>(stream), info); });
 }
 
 }  // namespace

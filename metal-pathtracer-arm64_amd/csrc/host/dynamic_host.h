@@ -1,7 +1,7 @@
 // The update calls of a resident scene - its geometry (dynamic.cpp, rebuild.cpp: include/ptr_dynamic.h, ptr_deform.h, ptr_deform_device.h,
 // ptr_rebuild.h) and its appearance (appearance.cpp: include/ptr_appearance.h) - and what they share with the frame on several devices
-// that fans the geometry ones out (multi_dynamic.cpp: include/ptr_multi_dynamic.h).  Every call is two halves: check*, the rules of the
-// call on the host against the scene's host-side records - no device work, no record changed, "" or the refusal without the caller's name
+// that fans them out (multi_dynamic.cpp: include/ptr_multi_dynamic.h; multi_appearance.cpp: include/ptr_multi_appearance.h).  Every
+// call is two halves: check*, the rules of the call on the host against the scene's host-side records - no device work, no record changed, "" or the refusal without the caller's name
 // in front - which leaves the accepted update in an ...Update struct, and run*, the device work of that update on one scene and one
 // stream, joined before it returns and before the records follow.  The records come from the preparation at upload (fillDynamicRecords,
 // fillAppearanceRecords), never from the device.  Scenes uploaded from one preparation with the same flags and given the same calls hold
@@ -185,8 +185,10 @@ struct TexturesUpdate {
 std::string checkTextures(const PtrDeviceScene* scene, const PtrTextureUpdate* textures, uint32_t count, bool fromDevice, int arraysDevice,
                           TexturesUpdate& out);
 std::string stageTextures(const TexturesUpdate& u, float* pinned);
-// pinned: u.floats staged floats of the host form.  A non-finite component of the device form: Refused "<who>: texture T has ...".
-void runTextures(const char* who, PtrDeviceScene& ds, const TexturesUpdate& u, const float* pinned, hipStream_t st, PtrAppearanceInfo* info);
+// pinned: u.floats staged floats of the host form, in pinned memory this device's copies may read.  A non-finite component of the device
+// form: Refused "<who>: texture T has ..."; checkGiven false: the arrays were looked at already (where they live) and are not again.
+void runTextures(const char* who, PtrDeviceScene& ds, const TexturesUpdate& u, const float* pinned, bool checkGiven, hipStream_t st, PtrAppearanceInfo* info,
+                 const InputsEnqueued& enqueued = {});
 
 // ---- ptr_scene_set_environment and its device form
 struct EnvironmentUpdate {
@@ -198,7 +200,11 @@ struct EnvironmentUpdate {
 };
 std::string checkEnvironment(const PtrDeviceScene* scene, const float* rgba, uint32_t width, uint32_t height, bool fromDevice, int arraysDevice,
                              EnvironmentUpdate& out);
-// A non-finite component, of either form: Refused "<who>: the map has a non-finite component", the scene untouched
-void runEnvironment(const char* who, PtrDeviceScene& ds, const EnvironmentUpdate& u, hipStream_t st, PtrAppearanceInfo* info);
+// the host form's pixels into `pinned` (width * height * 4 floats), each component looked at on the way: "" or the refusal
+std::string stageEnvironment(const EnvironmentUpdate& u, float* pinned);
+// pinned: the staged pixels of the host form (null for the device form).  A non-finite component of the device form: Refused "<who>: the
+// map has a non-finite component", the scene untouched; checkGiven as for runTextures.
+void runEnvironment(const char* who, PtrDeviceScene& ds, const EnvironmentUpdate& u, const float* pinned, bool checkGiven, hipStream_t st,
+                    PtrAppearanceInfo* info, const InputsEnqueued& enqueued = {});
 
 }  // namespace ptrhost

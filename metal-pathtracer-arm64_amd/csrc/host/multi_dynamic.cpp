@@ -1,13 +1,13 @@
 // Host side of include/ptr_multi_dynamic.h: a frame on several devices whose scenes are dynamic and are updated in place.  Nothing here
 // states a rule or launches a kernel of its own: every call is the check half of the single-device call (dynamic_host.h) against partition
 // 0's records, the fan-out of what the kernels read, and the run half on every partition's scene and stream under the partition driver of
-// multi_frame_host.h.  Compiled with hipcc (host code only), like multi_frame.cpp.
+// multi_frame_host.h; the steps it shares with multi_appearance.cpp are in multi_update_host.h.  Compiled with hipcc (host code only),
+// like multi_frame.cpp.
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
 
-#include "dynamic_host.h"
-#include "multi_frame_host.h"
+#include "multi_update_host.h"
 #include "ptr_multi_dynamic.h"
 
 using namespace ptrhost;
@@ -17,80 +17,7 @@ namespace {
 
 constexpr uint32_t kAllDynamicFlags = PTR_DYNAMIC_DEFORMABLE | PTR_DYNAMIC_PRIMITIVES | PTR_DYNAMIC_VERTEX_NORMALS;
 
-// What a call on an existing frame refuses once its own arguments were found good, before partition 0's records are looked at
-int refuseFrame(const char* who, const PtrMultiFrame* f, char* err, size_t cap) {
-    if (const int rc = refuseBroken(who, f, err, cap)) return rc;
-    if (f->sceneless) return refuse(err, cap, std::string(who) + ": the frame has no scene");
-    return 0;
-}
-
-// Steps 3 and 4 of an update: one(me, p, arrived) on every partition's thread - arrived() once the partition's inputs are on their way -
-// with a Refused of a partition kept apart from a failure.  Returns "" or the refusal every partition reached; partitions that do not
-// agree on it break the frame.  info (nullable) is filled but for `first` and stagedParts.
-template <typename One>
-std::string runUpdate(const char* who, PtrMultiFrame& f, Clock::time_point t0, PtrMultiUpdateInfo* info, One&& one) {
-    std::vector<std::string> refusals(f.parts);
-    std::vector<double> arrivedAt(f.parts, 0.0);
-    const PtrMultiInfo kept = f.last;   // (the driver notes the partitions' times there: an update leaves the frame's own figures alone)
-    runParts(f, [&](Part& me, uint32_t p, const auto&) {
-        auto arrived = [&] { arrivedAt[p] = since(t0); };
-        try {
-            one(me, p, arrived);
-        } catch (const Refused& r) {
-            refusals[p] = r.message;
-        }
-    });
-    const PtrMultiInfo timed = f.last;
-    f.last = kept;
-    for (uint32_t p = 1; p < f.parts; ++p) {
-        if (refusals[p] == refusals[0]) continue;
-        f.broken = true;
-        auto said = [&](uint32_t q) { return refusals[q].empty() ? std::string("accepted the call") : "refused it (" + refusals[q] + ")"; };
-        throw HipError{std::string(who) + ": the partitions disagree: device " + std::to_string(f.part[0]->device) + " (partition 0) " + said(0u) + ", device " +
-                       std::to_string(f.part[p]->device) + " (partition " + std::to_string(p) + ") " + said(p)};
-    }
-    if (info) {
-        std::memset(info, 0, sizeof(*info));
-        info->parts = f.parts;
-        for (uint32_t p = 0; p < f.parts; ++p) {
-            info->partSeconds[p] = timed.partRenderSeconds[p];
-            info->distributeSeconds = std::max(info->distributeSeconds, arrivedAt[p]);
-        }
-        info->totalSeconds = since(t0);
-    }
-    return refusals[0];
-}
-
-// An update call whose inputs every partition copies from the host itself: t0 is the call's entry, `problem` what the check half (and
-// the staging) said, run(scene, stream, info, enqueued) the run half, which calls `enqueued` once the partition's copies are on its stream.
-template <typename Run>
-int hostUpdate(const char* who, PtrMultiFrame& f, Clock::time_point t0, const std::string& problem, PtrMultiUpdateInfo* info, char* err, size_t cap,
-               Run&& run) {
-    if (!problem.empty()) return refuse(err, cap, std::string(who) + ": " + problem);
-    try {
-        PtrUpdateInfo first{};
-        const std::string refused = runUpdate(who, f, t0, info, [&](Part& me, uint32_t p, const auto& arrived) {
-            run(*me.scene, me.stream, p == 0u ? &first : nullptr, InputsEnqueued(arrived));
-        });
-        if (!refused.empty()) return refuse(err, cap, refused);
-        if (info) info->first = first;
-        return 0;
-    }
-    PTR_CATCH_ALL(err, cap)
-}
-
-// where the arrays of a device update that travel lie in a partition's buffer (and in the pinned memory), in floats
-struct Travel {
-    struct Array {
-        const float* src;
-        size_t at, floats;
-        uint32_t entry;
-        int which;   // 0 positions, 1 normals, 2 tangents
-    };
-    std::vector<Array> arrays;
-    size_t floats = 0;
-};
-
+// the arrays of a device update that travel (multi_update_host.h); which: 0 positions, 1 normals, 2 tangents
 Travel travelOf(const DeviceVerticesUpdate& u) {
     Travel t;
     for (uint32_t i = 0; i < u.entry.size(); ++i) {
@@ -100,9 +27,7 @@ Travel travelOf(const DeviceVerticesUpdate& u) {
         const float* const given[3] = {e.v.positions, e.v.normals, e.v.tangents};
         const size_t width[3] = {3u, 3u, 4u};
         for (int k = 0; k < 3; ++k) {
-            if (!given[k]) continue;   // (computed normals, a mesh or a scene without tangents)
-            t.arrays.push_back(Travel::Array{given[k], t.floats, n * width[k], i, k});
-            t.floats += n * width[k];
+            if (given[k]) t.add(given[k], n * width[k], i, k);   // (not: computed normals, a mesh or a scene without tangents)
         }
     }
     return t;
@@ -179,7 +104,7 @@ int ptr_multi_frame_set_mesh_vertices(PtrMultiFrame* frame, const PtrMeshVertice
         problem = checkMeshVertices(frame->part[0]->scene.get(), meshes, count, u);
         if (problem.empty()) {   // staged once, for every partition
             HIP_CHECK(hipSetDevice(frame->rootDevice));
-            float* staged = static_cast<float*>(frame->dynamic->pinned.pinnedFor(std::max<size_t>(u.floats, 4u) * sizeof(float)));
+            float* staged = static_cast<float*>(distributionOf(*frame).pinned.pinnedFor(std::max<size_t>(u.floats, 4u) * sizeof(float)));
             pinned = staged;
             problem = stageMeshVertices(meshes, u, staged);
         }
@@ -240,86 +165,25 @@ int ptr_multi_frame_set_mesh_vertices_device(PtrMultiFrame* frame, const PtrMesh
     }
     PTR_CATCH_ALL(err, err_cap)
 
-    // (the calling thread visits the partitions' devices and the arrays' device: whatever way the call ends, it leaves on the frame's first)
-    struct BackOnRoot {
-        int device;
-        ~BackOnRoot() { (void)hipSetDevice(device); }
-    } backOnRoot{f.rootDevice};
     try {
         hipStream_t callers = static_cast<hipStream_t>(stream);
-        MultiDynamic& md = *f.dynamic;
         const Travel travel = travelOf(u);
-        // how every partition gets the arrays: 0 in place, 1 pulled from its peer, 2 through the pinned memory
-        std::vector<int> how(f.parts, 0);
-        uint32_t stagedParts = 0;
-        for (uint32_t p = 0; p < f.parts; ++p) {
-            const Part& me = *f.part[p];
-            if (me.device == src_device && !me.forceStaged) continue;
-            int direct = 0;
-            if (me.device != src_device && !me.forceStaged) {
-                HIP_CHECK(hipSetDevice(me.device));
-                HIP_CHECK(hipDeviceCanAccessPeer(&direct, me.device, src_device));
-                if (direct) {
-                    const hipError_t enabled = hipDeviceEnablePeerAccess(src_device, 0);
-                    if (enabled != hipSuccess && enabled != hipErrorPeerAccessAlreadyEnabled) direct = 0;
-                    (void)hipGetLastError();
-                }
-            }
-            how[p] = direct ? 1 : 2;
-            if (!direct) {
-                ++stagedParts;
-                std::fprintf(stderr, "[ptr] device %d does not read the vertex arrays of device %d directly: they go through pinned host memory\n", me.device,
-                             src_device);
-            }
-        }
-        HIP_CHECK(hipSetDevice(src_device));
-        auto& source = md.source[src_device];
-        if (!source) {
-            source = std::make_unique<MultiDynamic::Source>();
-            HIP_CHECK(hipEventCreateWithFlags(&source->ready, hipEventDisableTiming));
-        }
         // the check, once, where the arrays are; a refusal leaves every partition as it was
-        try {
+        const DeviceRoute route = routeFromDevice(f, travel, src_device, callers, "vertex", [&](MultiDistribution& md, MultiDistribution::Source& source) {
             const size_t words = (u.checked.size() + 31u) / 32u;
-            checkGivenArrays(who, u, source->rows, source->flags, static_cast<uint32_t*>(md.pinned.pinnedFor(std::max<size_t>(words, 1u) * sizeof(uint32_t))), callers);
-        } catch (const Refused& r) {
-            return refuse(err, err_cap, r.message);
-        }
-        const float* pinned = nullptr;
-        if (stagedParts > 0u && travel.floats > 0u) {   // once, for every partition that cannot pull; the event below is behind these copies
-            float* staged = static_cast<float*>(md.pinned.pinnedFor(travel.floats * sizeof(float)));
-            for (const Travel::Array& a : travel.arrays) {
-                HIP_CHECK(hipMemcpyAsync(staged + a.at, a.src, a.floats * sizeof(float), hipMemcpyDeviceToHost, callers));
-            }
-            pinned = staged;
-        }
-        HIP_CHECK(hipEventRecord(source->ready, callers));
-        HIP_CHECK(hipSetDevice(f.rootDevice));
-
+            checkGivenArrays(who, u, source.rows, source.flags, static_cast<uint32_t*>(md.pinned.pinnedFor(std::max<size_t>(words, 1u) * sizeof(uint32_t))), callers);
+        });
         PtrUpdateInfo first{};
         const std::string refused = runUpdate(who, f, t0, info, [&](Part& me, uint32_t p, const auto& arrived) {
-            HIP_CHECK(hipStreamWaitEvent(me.stream, source->ready, 0));
-            DeviceVerticesUpdate mine;
-            if (how[p] == 0 || travel.floats == 0u) {
-                mine = u;
-            } else {
-                me.pulled.ensure(travel.floats);
-                for (const Travel::Array& a : travel.arrays) {
-                    if (how[p] == 1) {
-                        HIP_CHECK(hipMemcpyPeerAsync(me.pulled.ptr + a.at, me.device, a.src, src_device, a.floats * sizeof(float), me.stream));
-                    } else {
-                        HIP_CHECK(hipMemcpyAsync(me.pulled.ptr + a.at, pinned + a.at, a.floats * sizeof(float), hipMemcpyHostToDevice, me.stream));
-                    }
-                }
-                mine = movedTo(u, travel, me.pulled.ptr);
-            }
+            const float* base = bringArrays(route, travel, me, p);
+            const DeviceVerticesUpdate mine = base ? movedTo(u, travel, base) : u;
             arrived();
             runMeshVerticesDevice(who, *me.scene, mine, false, me.stream, p == 0u ? &first : nullptr);
         });
         if (!refused.empty()) return refuse(err, err_cap, refused);
         if (info) {
             info->first = first;
-            info->stagedParts = stagedParts;
+            info->stagedParts = route.stagedParts;
         }
         return 0;
     }
@@ -384,7 +248,7 @@ int ptr_multi_frame_rebuild_tree(PtrMultiFrame* frame, uint32_t flags, PtrRebuil
     if (!problem.empty()) return refuse(err, err_cap, std::string(who) + ": " + problem);
     try {
         std::vector<PtrRebuildInfo> infos(f.parts);
-        const std::string refused = runUpdate(who, f, Clock::now(), nullptr, [&](Part& me, uint32_t p, const auto& arrived) {
+        const std::string refused = runUpdate(who, f, Clock::now(), static_cast<PtrMultiUpdateInfo*>(nullptr), [&](Part& me, uint32_t p, const auto& arrived) {
             arrived();
             rebuildTree(who, *me.scene, flags, me.stream, infos[p]);
         });

@@ -1,5 +1,6 @@
-// What the two host files of a frame on several devices share: multi_frame.cpp (include/ptr_multi_frame.h), which owns the frame, and
-// multi_dynamic.cpp (include/ptr_multi_dynamic.h), which updates its scenes in place.  The frame object, what a partition keeps beside
+// What the host files of a frame on several devices share: multi_frame.cpp (include/ptr_multi_frame.h), which owns the frame, and
+// multi_dynamic.cpp / multi_appearance.cpp (include/ptr_multi_dynamic.h, include/ptr_multi_appearance.h), which update its scenes in
+// place (what those two share beyond this is in multi_update_host.h).  The frame object, what a partition keeps beside
 // its FramePart (frame_rounds.h), runParts - the partition driver of multi_host.h on a frame - and the one create behind every entry
 // point.  Internal: not part of the C-ABI.
 #pragma once
@@ -27,15 +28,21 @@ struct Part {
     hipStream_t stream = nullptr;
     DeviceBuffer<float> edge, bandOut, packed;   // the exchange's edge rows; the outputs in band layout; the checkpoint buffer
     std::vector<float> hostPacked;   // the checkpoint buffer's host side
-    // include/ptr_multi_dynamic.h: the vertex arrays of another device, pulled here (allocated by the first such call, kept)
+    // include/ptr_multi_dynamic.h, include/ptr_multi_appearance.h: the vertex or pixel arrays of another device, pulled here (allocated by
+    // the first such call, kept)
     DeviceBuffer<float> pulled;
 };
 
 // What a frame created over dynamic scenes keeps beside its partitions (include/ptr_multi_dynamic.h); a static frame has none of it.
 struct MultiDynamic {
     uint32_t flags = 0;   // PTR_DYNAMIC_*: what every partition's scene was uploaded with
-    // portable pinned memory, grown on demand and kept: host vertex data is staged here once for all partitions, and device-resident
-    // data passes through here once for the partitions that cannot pull it from a peer
+};
+
+// What the update calls of a frame distribute their inputs through (include/ptr_multi_dynamic.h, include/ptr_multi_appearance.h), made by
+// the first call that needs it (distributionOf, multi_update_host.h): a frame that is never updated, static or dynamic, has none of it.
+struct MultiDistribution {
+    // portable pinned memory, grown on demand and kept: host vertex data and host pixels are staged here once for all partitions, and
+    // device-resident data passes through here once for the partitions that cannot pull it from a peer
     PinnedBuffer pinned{hipHostMallocPortable};
     // per device the caller's arrays have lived on: the scratch of the finiteness check there, and the event the partitions wait on
     struct Source {
@@ -44,7 +51,7 @@ struct MultiDynamic {
         hipEvent_t ready = nullptr;
     };
     std::map<int, std::unique_ptr<Source>> source;
-    ~MultiDynamic() {
+    ~MultiDistribution() {
         for (auto& s : source) {
             if (s.second->ready && hipSetDevice(s.first) == hipSuccess) (void)hipEventDestroy(s.second->ready);
         }
@@ -70,6 +77,7 @@ struct PtrMultiFrame {
     bool broken = false;   // a call failed on a device: only release is left
     PtrMultiInfo last{};
     std::unique_ptr<ptrhost::MultiDynamic> dynamic;   // ptr_multi_frame_create_dynamic only
+    std::unique_ptr<ptrhost::MultiDistribution> distribution;   // null until an update call distributes something
 };
 
 namespace ptrhost {
